@@ -2,7 +2,9 @@
 """bench.py -- frames/sec of the MI355X-native detect -> match -> pose hot path.
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 the driver launches it
-under torch.distributed.run, one rank per GPU.  One JSON line on rank 0.
+under torch.distributed.run, one rank per GPU.  One JSON line on rank 0.  Such a plain run sets up, warms up, times
+the K steps and prints the line (metric, value, unit, ms_per_step, ...); `--dump-outputs DIR` also writes what the
+last timed step computed (dump_outputs).  The side measurements listed further down are taken only with `--full`.
 
 Headline workload (BASELINE.json configs[1]): synthetic 752x480 mono8 EuRoC-shaped stream ("S-752", integer-only
 generator, vi-slam_amd/csrc/synth_core.h), ORB 1000 keypoints x 8 levels, BF-Hamming k=2 both directions +
@@ -12,7 +14,7 @@ for 1024; `kernels_ms_per_step`, `roofline` and the counter figures are PER LAUN
 Multi-GPU (configs[3]): rank r processes its own stream (seed + r); the only collective is one broadcast of the
 parameter/intrinsics struct from rank 0 (RCCL); scaling is weak.
 
-Beside `value` the line carries (rank 0, N = 1 only, all OUTSIDE the timed region of `value`):
+With `--full`, beside `value` the line carries (rank 0, N = 1 only, all OUTSIDE the timed region of `value`):
   legs.s752_fixed1000   the same stream with ransac_adaptive = 0: 1000 hypotheses per pair (the pose kernels loaded)
   legs.s752_parallax    "S-752P": two depth layers + independently moving objects (adaptive RANSAC does real work)
   legs.s752_results_d2h the headline step + a pinned, overlapped D2H copy of poses and good matches every step
@@ -24,6 +26,7 @@ Beside `value` the line carries (rank 0, N = 1 only, all OUTSIDE the timed regio
                         config 1 (ORB::create(200), first frames of S-752), and frame-parallel on all cores
 """
 import argparse
+import contextlib
 import ctypes as C
 import json
 import os
@@ -407,6 +410,74 @@ def cpu_baseline(p, frames, budget_s, what):
                       f"recoverPose, g++ -O2, 1 thread; host has {os.cpu_count()} logical CPUs"}
 
 
+def headline(a, world, B, Q, dt, ranks):
+    """the fields of the result line that the timed steps alone decide (a plain run prints these and nothing else)"""
+    return {
+        "metric": "frames/sec detect+match+pose, 752x480 mono8", "value": vdist.aggregate_fps(world, a.steps, B * Q, dt), "unit": "frames/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+        "ranks": ranks, **({"rehearsal": "N ranks on ONE device over gloo: exercises the N > 1 code path, not a scaling measurement"} if a.rehearse_on_one_gpu else {}),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload_short": "S-752 synthetic 752x480 mono8 resident in HBM; ORB 1000 kps x 8 levels, knn2 both ways + filters, essential RANSAC + recoverPose",
+                   "workload": "S-752: synthetic 752x480 mono8 EuRoC-shaped stream (frames resident in HBM), 1000 ORB kps x 8 levels, BF-Hamming k=2 "
+                               "both directions + ratio/sym/grid filter, essential RANSAC (adaptive, max 1000) + recoverPose.  S-752 is a planar "
+                               "crop under pure image translation: every grid match is an exact inlier, the adaptive stop ends RANSAC after "
+                               "<= 4 hypotheses (see pose_load) and the recovered pose is degenerate; legs.s752_fixed1000 / legs.s752_parallax load "
+                               "the pose kernels.  Results stay on the device inside the timed region (legs.s752_results_d2h adds the download); "
+                               "Camera::Update's half pyramid (4 levels per frame) is part of the step, as it is of the CPU baseline.  "
+                               "FAST runs at a per-level threshold predicted from the previous batch's retainBest cuts (a corner below the cut "
+                               "is neither kept nor able to suppress a kept one), verified per (frame, level) on the device, mispredictions redone "
+                               "at fast_threshold inside the step: keypoints identical to FAST at 20 for every input (fast_threshold_prediction)",
+                   "frames_per_step_per_gpu": B * Q, "launches_per_step": Q, "frames_per_launch": B,
+                   "parallelism": f"stream-per-gpu x{world}" if world > 1 else "single-gpu"},
+    }
+
+
+DUMP_SAMPLE_FRAMES, DUMP_SAMPLE_SEED = 16, 0xD0      # keypoints / descriptors of this many frames of the last launch, chosen by this seed
+
+
+def dump_outputs(ctx, B, out_dir, first_frame, stages):
+    """what every stage of the timed path wrote in its last step, as the library's accessors hand it to a caller: for the step's last
+    launch of B frames (stream frames first_frame ...) the pose records, good matches and counts of vis_batch_results_async, and for a
+    fixed, seeded sample of that launch's frames the keypoints + descriptors (vis_batch_get_keypoints) and Camera::Update's half
+    pyramid levels 1-4 (vis_batch_half_pyramid; level 0 is the frame itself and is not part of the stage's output).  Integers are
+    stored as float64 (exact); good-match slots past a frame's count are set to -1.  About 12 MB in all."""
+    os.makedirs(out_dir, exist_ok=True)
+    pose, good, ng = ctx.batch_results(B)                 # synchronises every stream of the context
+    valid = np.arange(good.shape[1])[None, :] < ng[:, None]
+    arrays = {"pose_E": pose["E"], "pose_R": pose["R"], "pose_t": pose["t"],
+              "pose_counts": np.stack([pose[k] for k in ("n_inliers", "n_pose_good", "iters_run", "n_points", "n_models")], 1).astype(np.float64),
+              "good_count": ng.astype(np.float64),
+              "good_query": np.where(valid, good["queryIdx"], -1).astype(np.float64),
+              "good_train": np.where(valid, good["trainIdx"], -1).astype(np.float64),
+              "good_distance": np.where(valid, good["distance"], -1).astype(np.float32)}
+    frames = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=min(DUMP_SAMPLE_FRAMES, B), replace=False))
+    kps, descs = [], []
+    for f in frames:
+        k, d = ctx.batch_keypoints(int(f))
+        kps.append(np.stack([np.full(len(k), f, np.float32)] + [k[n].astype(np.float32) for n in vislam.KEYPOINT_DTYPE.names], 1))
+        descs.append(d.astype(np.float32))
+    arrays["keypoints"] = np.concatenate(kps).reshape(-1, 1 + len(vislam.KEYPOINT_DTYPE.names))    # frame, x, y, size, angle, response, octave, class_id
+    arrays["descriptors"] = np.concatenate(descs).reshape(-1, 32)                                    # one byte per column
+    arrays["sample_stream_frames"] = (first_frame + frames).astype(np.float64)                       # which stream frames the sample holds
+    if not stages & (vislam.STAGE_UPDATE | vislam.STAGE_GRADIENT):      # a --stages run without Camera::Update has no half pyramid
+        return _save(out_dir, arrays)
+    d_half, fe = ctx.batch_half_pyramid()
+    lw, lh = vislam.half_pyramid_dims(W, H)
+    o1, n14 = lw[0] * lh[0], sum(lw[l] * lh[l] for l in range(1, 5))
+
+    class _Half:                                          # the plan's half pyramid buffer of this launch as a torch view
+        __cuda_array_interface__ = {"data": (d_half, False), "shape": (B, fe), "typestr": "|u1", "version": 2}
+    half = torch.as_tensor(_Half(), device="cuda")
+    arrays["half_pyramid"] = half[torch.from_numpy(frames).to(half.device), o1:o1 + n14].cpu().numpy().astype(np.float32)   # levels 1..4, row-major, concatenated
+    _save(out_dir, arrays)
+
+
+def _save(out_dir, arrays):
+    assert sum(v.nbytes for v in arrays.values()) <= 64 << 20
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -416,13 +487,20 @@ def main():
     ap.add_argument("--launches-per-step", type=int, default=20,
                     help="a step = this many consecutive launches over consecutive frames of the stream (20 x 1024 = 20480 frames per step, 15 GB of resident "
                          "frames with --ring 2): the driver's --steps 20 is then 400 launches = 1 s of steady state that an outside sampler (rocm-smi) can see "
-                         "(4 launches per step in round 4: 0.2 s, every busy sample read 0 %)")
+                         "(4 launches per step in round 4: 0.2 s, every busy sample read 0 %%)")
     ap.add_argument("--ring", type=int, default=2, help="distinct steps' worth of frames resident in HBM")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="REHEARSAL of the N > 1 code path on a box with ONE GPU: every rank uses device 0 and the ranks talk over gloo (RCCL refuses "
                          "two ranks on one device).  The line says so (\"rehearsal\") and is not a scaling measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the side legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: clocks, per-kernel times, rooflines, pose load, side legs, CPU baselines; the "
+                         "full record goes to --full-out.  A plain run only sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what every stage wrote in the last launch of the last timed step (pose records, good "
+                         "matches and their counts; keypoints, descriptors and half pyramid of a fixed sample of its frames) as DIR/<name>.npy, "
+                         "float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the side legs (profiling runs)")
     ap.add_argument("--full-out", default=None, help="where the FULL record (legs, counter tables, prose) is written; default gpurun_out/bench_full.json. stdout carries "
                                                      "only the compact line (benchline.py)")
     ap.add_argument("--stages", type=int, default=vislam.STAGE_FRAME, help="debug: bitmask of stages (1 detect, 2 match, 4 pose, 8 Camera::Update); the reported metric needs all 15")
@@ -457,7 +535,7 @@ def main():
     seed = vdist.stream_seed(rank, world)
     stream = Stream(ctx, dev, W, H, B * Q * R, seed)      # generated on the device: no host synthesis, no H2D
     ctx.batch_plan(W, H, W, B)
-    clocks = ClockSampler(vislam.device_pci_bus_id(local_rank if world > 1 else 0))
+    clocks = ClockSampler(vislam.device_pci_bus_id(local_rank if world > 1 else 0)) if a.full else contextlib.nullcontext()
     with clocks:
         dt, step_q = timed_steps(ctx, stream, B, R, a.stages, a.steps, a.warmup, dist, dev, q=Q)
     dt_rank = dt
@@ -468,6 +546,18 @@ def main():
                                       dist, ddev, world)
     if not a.rehearse_on_one_gpu:
         vdist.check_distinct_devices(ranks)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(ctx, B, a.dump_outputs, ((a.warmup + a.steps - 1) % R * Q + Q - 1) * B, a.stages)     # the frames timed_steps' last launch read
+    if not a.full:
+        if rank == 0:
+            import benchline
+            print(benchline.compact_line(headline(a, world, B, Q, dt, ranks)), flush=True)
+        ctx.close()
+        del stream
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     def step(i):                                          # ONE launch (per-kernel timings, pose load: per launch of B frames)
         ctx.batch_run(stream.ptr((i % (R * Q)) * B), B, a.stages)
@@ -837,25 +927,9 @@ def main():
                      "pmc_measured_at_commit": pmc_commit}
         except Exception as e:
             issue = {"error": f"profiles/pmc_traffic.json has no step totals: {e!r}"}
-        fps = vdist.aggregate_fps(world, a.steps, B * Q, dt)
         out = {
-            "metric": "frames/sec detect+match+pose, 752x480 mono8", "value": fps, "unit": "frames/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
+            **headline(a, world, B, Q, dt, ranks),
             "clocks": clocks.summary(),
-            "ranks": ranks, **({"rehearsal": "N ranks on ONE device over gloo: exercises the N > 1 code path, not a scaling measurement"} if a.rehearse_on_one_gpu else {}),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload_short": "S-752 synthetic 752x480 mono8 resident in HBM; ORB 1000 kps x 8 levels, knn2 both ways + filters, essential RANSAC + recoverPose",
-                       "workload": "S-752: synthetic 752x480 mono8 EuRoC-shaped stream (frames resident in HBM), 1000 ORB kps x 8 levels, BF-Hamming k=2 "
-                                   "both directions + ratio/sym/grid filter, essential RANSAC (adaptive, max 1000) + recoverPose.  S-752 is a planar "
-                                   "crop under pure image translation: every grid match is an exact inlier, the adaptive stop ends RANSAC after "
-                                   "<= 4 hypotheses (see pose_load) and the recovered pose is degenerate; legs.s752_fixed1000 / legs.s752_parallax load "
-                                   "the pose kernels.  Results stay on the device inside the timed region (legs.s752_results_d2h adds the download); "
-                                   "Camera::Update's half pyramid (4 levels per frame) is part of the step, as it is of the CPU baseline.  "
-                                   "FAST runs at a per-level threshold predicted from the previous batch's retainBest cuts (a corner below the cut "
-                                   "is neither kept nor able to suppress a kept one), verified per (frame, level) on the device, mispredictions redone "
-                                   "at fast_threshold inside the step: keypoints identical to FAST at 20 for every input (fast_threshold_prediction)",
-                       "frames_per_step_per_gpu": B * Q, "launches_per_step": Q, "frames_per_launch": B,
-                       "parallelism": f"stream-per-gpu x{world}" if world > 1 else "single-gpu"},
             # `bound` names the roofline `frac` is priced against (north_star asks for the HBM roofline of detect/describe);
             # `limited_by` is what the counters say actually limits this kernel (see valu_roofline / detect_kernels)
             "roofline": {"bound": "hbm", "limited_by": limited_by, "kernel": kname, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",

@@ -1,9 +1,10 @@
 """benchline.py -- the compact LAST line of bench.py.
 
-bench.py measures many things (legs, counter-derived figures, per-kernel tables).  The full record goes to a file
-(`bench_full.json`); what the driver reads is ONE short strict-JSON line, numbers only, below 1900 bytes so that a 2000-byte
-tail still holds all of it (BENCH_r05.json: the 23 KB line of round 5 could not be parsed).  Pure Python, no torch, no HIP:
-tests/test_benchline.py runs it on the committed full records.
+bench.py --full measures many things (legs, counter-derived figures, per-kernel tables).  The full record goes to a file
+(`bench_full.json`); a plain run measures the headline alone and its line holds just those fields.  What the driver reads
+is ONE short strict-JSON line, numbers only, below 1900 bytes so that a 2000-byte tail still holds all of it (BENCH_r05.json:
+the 23 KB line of round 5 could not be parsed).  Pure Python, no torch, no HIP: tests/test_benchline.py runs it on the
+committed full records.
 """
 import json
 import math
@@ -75,14 +76,18 @@ def compact(full, full_path=None):
         out["rehearsal"] = True
     out["config"] = {"workload": str(cfg.get("workload_short") or cfg.get("workload") or "")[:140],
                      **{k: cfg.get(k) for k in ("frames_per_step_per_gpu", "launches_per_step", "frames_per_launch", "parallelism") if k in cfg}}
-    out["roofline"] = _pick(full.get("roofline"), ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "limited_by"))
+    # a plain bench run measures the headline alone: the blocks below appear only where the record holds what they summarise
+    if "roofline" in full:
+        out["roofline"] = _pick(full.get("roofline"), ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "limited_by"))
     iss = full.get("issue_roofline") or {}
-    if "error" not in iss:
+    if iss and "error" not in iss:
         tera = lambda k: _r(iss[k] / 1e12, 4) if iss.get(k) else None                    # noqa: E731
         out["issue_roofline"] = {"frac": _r(iss.get("frac"), 4), "achieved": tera("achieved"), "peak_half_rate": tera("peak_measured_half_rate_class"),
                                  "peak_full_rate": tera("peak_measured_full_rate_class"), "unit": "Twave-inst/s"}
-    out["matcher_roofline"] = _pick(full.get("matcher_roofline"), ("frac", "l2_hit", "mfma_busy_frac", "traffic_over_algorithmic"), 3)
-    out["t1"] = t1_status(full)
+    if "matcher_roofline" in full:
+        out["matcher_roofline"] = _pick(full.get("matcher_roofline"), ("frac", "l2_hit", "mfma_busy_frac", "traffic_over_algorithmic"), 3)
+    if "roofline" in full:
+        out["t1"] = t1_status(full)
     ms = full.get("kernels_ms_per_launch") or {}
     if ms:
         out["ms"] = {k[3:]: _r(v, 3) for k, v in ms.items()}

@@ -15,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_ranks_on_one_gpu(built, tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29531",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--launches-per-step", "4", "--rehearse-on-one-gpu", "--no-legs",
-           "--full-out", str(tmp_path / "full.json")]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--launches-per-step", "4", "--rehearse-on-one-gpu", "--full",
+           "--no-legs", "--full-out", str(tmp_path / "full.json")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-2000:]          # ONE line, from rank 0: the compact one
@@ -31,3 +31,17 @@ def test_two_ranks_on_one_gpu(built, tmp_path):
     frames = 2 * j["steps"] * j["config"]["frames_per_step_per_gpu"]
     assert abs(j["value"] - frames / (j["ms_per_step"] * 1e-3 * j["steps"])) < 1e-6 * j["value"]
     assert "roofline" in j
+
+
+def test_two_ranks_on_one_gpu_plain(built):
+    """the plain run's N > 1 path: the headline measured by both ranks, ONE line from rank 0, then barrier and teardown on every rank"""
+    env = dict(os.environ, MASTER_ADDR="127.0.0.1")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29532",
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--launches-per-step", "4", "--rehearse-on-one-gpu"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert r.returncode == 0 and len(lines) == 1, (r.stdout + r.stderr)[-2000:]
+    c = json.loads(lines[0])
+    assert c["n_gpus"] == 2 and c["steps"] == 2 and c["rehearsal"] is True and [x[:2] for x in c["ranks"]] == [[0, 0], [1, 0]]
+    assert abs(c["value"] - 2 * 4 * 1024 / (c["ms_per_step"] * 1e-3)) <= 1e-4 * c["value"]    # both ranks' frames / the slowest rank's time
+    assert "roofline" not in c and "clocks" not in c

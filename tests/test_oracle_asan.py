@@ -25,7 +25,8 @@ def test_oracle_units_under_asan_ubsan():
     assert os.path.exists(lib)
     env = dict(os.environ)
     ubsan = _runtime("libubsan.so")
-    env["LD_PRELOAD"] = asan + ((":" + ubsan) if ubsan else "")
+    # the sanitizer runtimes go first; whatever the environment already preloads stays behind them
+    env["LD_PRELOAD"] = ":".join(p for p in (asan, ubsan, os.environ.get("LD_PRELOAD")) if p)
     # python itself "leaks" at exit; any other finding aborts the child with a non-zero exit code
     env["ASAN_OPTIONS"] = "detect_leaks=0:abort_on_error=1:halt_on_error=1"
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"

@@ -20,8 +20,8 @@ cd /tmp && export TMPDIR=/tmp
 PIPE_PASSES=("FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY" "GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum SQ_INSTS_VALU_MFMA_MOPS_F6F4 SQ_VALU_MFMA_BUSY_CYCLES" "SQ_LDS_IDX_ACTIVE SQ_BUSY_CYCLES SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_VALU_MFMA_I8")
 
 if want stats; then
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-legs --full-out $R/$OUT/bench_under_rocprof_full.json > $R/$OUT/bench_under_rocprof.log 2>&1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_legs -- python3 $R/bench.py --steps 10 --warmup 3 --no-cpu-baseline --full-out $R/$OUT/bench_legs_under_rocprof_full.json > $R/$OUT/bench_legs_under_rocprof.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-legs --full-out $R/$OUT/bench_under_rocprof_full.json > $R/$OUT/bench_under_rocprof.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $R/$OUT/stats_legs -- python3 $R/bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --full-out $R/$OUT/bench_legs_under_rocprof_full.json > $R/$OUT/bench_legs_under_rocprof.log 2>&1
   echo "section stats done"
 fi
 
@@ -83,7 +83,7 @@ if want bench; then
   # (round 4's record quoted the previous run's counters beside new timings)
   [ -f $R/$OUT/pipe/pmc_traffic.json ] && cp $R/$OUT/pipe/pmc_traffic.json $R/profiles/pmc_traffic.json
   [ -f $R/$OUT/pose/pmc_pose.json ] && cp $R/$OUT/pose/pmc_pose.json $R/profiles/pmc_pose.json
-  (cd $R && python3 bench.py --steps 20 --warmup 5 --full-out $R/$OUT/bench_full.json > $R/$OUT/bench_line.json 2> $R/$OUT/bench_full.err)
+  (cd $R && python3 bench.py --steps 20 --warmup 5 --full --full-out $R/$OUT/bench_full.json > $R/$OUT/bench_line.json 2> $R/$OUT/bench_full.err)
   echo "section bench done"
 fi
 
