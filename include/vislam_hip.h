@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define VIS_ABI_VERSION 4
+#define VIS_ABI_VERSION 5
 
 /* ---- status codes ------------------------------------------------------- */
 enum {
@@ -100,6 +100,12 @@ typedef struct vis_params {
      * checkerboard) yields more than nfeatures keypoints.  Beyond the capacity a call returns VIS_E_CAPACITY (never a silent cut);
      * the single-frame entry vis_orb_detect_compute grows the capacity itself up to the `cap` its caller passes. <= 65535. */
     int32_t keypoint_capacity;
+    /* Keyframe gate of the batched stream path (vis_batch_run; the frame-at-a-time entry points ignore it).  0 = off: frame i is
+     * matched against frame i-1 whatever it detected.  K >= 1: a frame is SAVED (CameraGPU::addGPUKeyframe, src/CameraGPU.cpp:138-173)
+     * when its keypoint count is > K -- > 1 for the first frame saved after vis_batch_plan / vis_batch_reset (src/Camera.cpp:225,
+     * src/CameraGPU.cpp:164) -- and every saved frame is matched against the last saved one (frameList.back(), :128-129).  K = 1 is
+     * the GPU main's rule, K = 10 the CPU main's (Camera::addKeyframe, src/Camera.cpp:197-235).  0 ... 65535. */
+    int32_t keyframe_min_points;  /* 0 */
 } vis_params;
 enum { VIS_POSE_GOOD = 0, VIS_POSE_SYM = 1 };
 
@@ -274,7 +280,10 @@ int  vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_
                      const float* d_pts, const int32_t* d_npts, int max_pts,
                      const vis_se3f* d_init, vis_align_result* d_out);
 /* the same on the pairs of the last vis_batch_run (stages must have included MATCH): the matched points come from the
- * plan (the grid-filtered good matches of every pair).  Pair 0 (frame 0 against the carried frame) is skipped.
+ * plan (the grid-filtered good matches of every pair).  Gate off: pair i = (frame i-1 -> frame i); pair 0 (frame 0 against the
+ * carried frame) is skipped and d_out[0] is zeroed.  Gate on (keyframe_min_points > 0): pair i = (frame prev -> frame i) with prev =
+ * vis_batch_get_keyframes' entry i when that is >= 0 (its gradients are in the same launch's set); a pair linked to the carried
+ * frame is skipped like pair 0, and every pair that is skipped or has no pair (VIS_KF_*) gets a zeroed record.
  * Runs on the context's POSE stream, ordered behind everything queued on the context's stream so far (the gradients) and
  * behind the matcher, so that it overlaps the next vis_batch_run: d_frames, the gradient buffers and d_out are in use until
  * vis_batch_sync -- or until a later vis_gradient_batch / vis_batch_align / vis_feeder_submit of this context, which wait for it. */
@@ -308,11 +317,16 @@ int  vis_feeder_submit(vis_feeder* f, int which, int n, const uint8_t** d_frames
 int  vis_feeder_release(vis_feeder* f, int which);
 
 /* ---- batched stream API (throughput path) --------------------------------- */
-/* Plan device buffers for batches of up to `max_frames` w x h frames.  Frames in a
- * batch are consecutive frames of ONE camera stream: frame i is matched against frame
- * i-1 (Camera::computeGoodMatches: query = last saved frame, src/Camera.cpp:146-157);
- * frame 0 is matched against the last frame of the previous vis_batch_run call
- * (carried on device), or not at all after vis_batch_reset. */
+/* Plan device buffers for batches of up to `max_frames` w x h frames.  Frames in a batch are consecutive frames of ONE camera
+ * stream, matched against the last SAVED frame before them (Camera::computeGoodMatches: query = frameList.back(),
+ * src/Camera.cpp:146-157).  The plan takes params.keyframe_min_points as it is at this call:
+ *   0 (gate off): every frame is saved; frame i is matched against frame i-1, frame 0 against the last frame of the previous
+ *     vis_batch_run call (carried on device), or not at all after vis_batch_reset.
+ *   K >= 1 (gate on): frame i is saved when it has > K keypoints (> 1 until the first frame is saved after vis_batch_plan /
+ *     vis_batch_reset).  A saved frame is matched against the last saved frame before it -- in the same batch, or the record
+ *     carried from an earlier call; a frame that is not saved, or the first saved frame of a stream, has no pair (n_sym = n_good = 0,
+ *     the pose record of a pair without correspondences).  The carried record is the last saved frame: a batch that saves nothing
+ *     carries the earlier one forward.  Decided on the device, with no host round trip (vis_batch_get_keyframes reports it). */
 int  vis_batch_plan(vis_ctx* ctx, int w, int h, int stride, int max_frames);
 int  vis_batch_reset(vis_ctx* ctx);
 enum { VIS_STAGE_DETECT = 1, VIS_STAGE_MATCH = 2, VIS_STAGE_POSE = 4, VIS_STAGE_ALL = 7,
@@ -359,6 +373,12 @@ int  vis_debug_counters(vis_ctx* ctx, unsigned long long out[4]);
  * correspondence the pose stage saw, in the order it saw them (good matches, or the symmetric matches with VIS_POSE_SYM).
  * VIS_E_CAPACITY if cap < *n_points (which is still returned). */
 int  vis_batch_get_inlier_mask(vis_ctx* ctx, int frame, uint8_t* mask, int cap, int* n_points);
+/* the pairing of the last vis_batch_run: prev[i] = the batch index of the frame that frame i was matched against, or one of
+ * VIS_KF_CARRIED (the record carried from an earlier call), VIS_KF_NOT_SAVED (frame i failed the keyframe gate: no pair),
+ * VIS_KF_FIRST (saved, with no earlier saved frame to match against).  Gate off: i-1, and VIS_KF_CARRIED or VIS_KF_FIRST for
+ * frame 0.  *n_out = frames of the last batch; VIS_E_CAPACITY if cap < *n_out.  Synchronises. */
+enum { VIS_KF_CARRIED = -1, VIS_KF_NOT_SAVED = -2, VIS_KF_FIRST = -3 };
+int  vis_batch_get_keyframes(vis_ctx* ctx, int32_t* prev, int cap, int* n_out);
 /* what the pose stage leaves per pair on the device (vis_batch_results_async copies these records) */
 typedef struct vis_pose_result {
     double E[9], R[9], t[3];
@@ -368,7 +388,9 @@ typedef struct vis_pose_result {
     int32_t reserved_;
 } vis_pose_result;
 /* Queue the device-to-host copy of the last batch's results -- n pose records, the good matches (n x root^2, dense
- * rows) and their counts -- behind the batch's own work; any pointer may be NULL; pinned host memory makes the copy
+ * rows) and their counts, one entry per frame of the batch: the pair (vis_batch_get_keyframes' prev[i] -> frame i); a frame
+ * without a pair (frame 0 after vis_batch_reset; with the keyframe gate on, any VIS_KF_NOT_SAVED / VIS_KF_FIRST frame) has
+ * count 0 and the pose record of zero correspondences -- behind the batch's own work; any pointer may be NULL; pinned host memory makes the copy
  * overlap the next vis_batch_run (pinned = device-accessible, e.g. hipHostMalloc: such destinations are written by one
  * small kernel of the library, which costs the pipeline nothing; anything else goes through hipMemcpyAsync).  n_cap = the number of frames the caller's buffers hold: VIS_E_CAPACITY (nothing is
  * copied) if the last batch had more.  The reference downloads its results every frame (src/CameraGPU.cpp:103, the

@@ -43,6 +43,7 @@ struct AlignArgs {
     const float* pts; const int32_t* npts; int max_pts;   // generated mode: matched keypoints of the previous frame per pair
     const vis_se3f* init; vis_align_result* out;
     int f1_off, f2_off, out_off;                          // frame index of image 1 / image 2 / result slot = pair + offset
+    const int32_t* prev;                                  // generated mode, keyframe gate: image 1 = frame prev[slot]; < 0: no pair (record left as cleared)
 };
 
 // ---- Sophus::SE3f pieces (see oracle/align.cpp for the citations) -------------------------------------------
@@ -226,7 +227,8 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
     __shared__ int s_ok;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int pair = blockIdx.x;
-    const int f1 = pair + G.f1_off, f2 = pair + G.f2_off;
+    const int f1 = G.prev ? G.prev[pair + G.out_off] : pair + G.f1_off, f2 = pair + G.f2_off;
+    if (f1 < 0) return;                                                  // (uniform: the whole workgroup)
     Se3 pose = {{1.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
     if (G.init) {
         const vis_se3f in = G.init[pair + G.out_off];
@@ -544,15 +546,24 @@ extern "C" int vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const u
                                const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
                                const float* d_pts, const int32_t* d_npts, int max_pts,
                                const vis_se3f* d_init, vis_align_result* d_out) {
+    return align_batch_links(ctx, ap, d_frames, w, h, stride, n, d_gray, d_gx, d_gy, d_pts, d_npts, max_pts, nullptr, d_init, d_out);
+}
+
+// d_prev (n entries, device): pair i aligns frame d_prev[i] -> frame i, d_prev[i] < 0 = no pair (a zeroed record); every record is
+// cleared first.  The frames d_prev names are frames of the same batch (d_prev[i] < i: the keyframe links of vis_batch_run).
+int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int w, int h, int stride, int n,
+                      const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy, const float* d_pts, const int32_t* d_npts,
+                      int max_pts, const int32_t* d_prev, const vis_se3f* d_init, vis_align_result* d_out) {
     if (!ctx || !d_frames || !d_gray || !d_gx || !d_gy || !d_pts || !d_npts || !d_out) return VIS_E_INVALID;
     int rc = check_align_params(ap, w, h);
     if (rc) return rc;
     if (stride < w || n < 1 || max_pts < 1) { ctx->err = "vis_align_batch: stride >= w, n >= 1, max_pts >= 1"; return VIS_E_INVALID; }
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    {   // frame 0 has no predecessor in this batch: its record is cleared (by a kernel of the library, not by the runtime's fill)
+    {   // frame 0 has no predecessor in this batch: its record is cleared (by a kernel of the library, not by the runtime's fill);
+        // with a link table every record is, and the pairs without a link leave theirs so
         static_assert(sizeof(vis_align_result) % 4 == 0, "cleared in dwords");
-        void* dsts[1] = {d_out}; const void* srcs[1] = {nullptr}; const size_t bytes[1] = {sizeof(vis_align_result)};
+        void* dsts[1] = {d_out}; const void* srcs[1] = {nullptr}; const size_t bytes[1] = {(d_prev ? (size_t)n : 1) * sizeof(vis_align_result)};
         const int rc0 = launch_copy_jobs(ctx, st, 1, dsts, srcs, bytes);
         if (rc0) return rc0;
     }
@@ -572,6 +583,7 @@ extern "C" int vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const u
     }
     G.pts = d_pts; G.npts = d_npts; G.max_pts = max_pts; G.init = d_init; G.out = d_out;
     G.f1_off = 0; G.f2_off = 1; G.out_off = 1;                                       // workgroup q = pair (frame q -> frame q+1), result slot q+1
+    G.prev = d_prev;                                                                 // (or frame d_prev[q+1] -> frame q+1)
     const int used = std::min(max_pts, AL_MAXKP);
     const size_t lds = (size_t)used * 121 * 4;                                       // largest patch: (2*5+1)^2 pixels per keypoint
     if (lds > 65536 - 4096) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_align<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -601,9 +613,12 @@ extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const u
     HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, sA));
     HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
     if (pl->match_pending[pl->last_base / pl->rec_per_set]) HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_match_done[pl->last_base / pl->rec_per_set], 0));
-    // d_p1 = the matched keypoints of the query frame of every pair (getGoodMatches, src/Matcher.cpp:295-303): pair i = (frame i-1, frame i)
+    // d_p1 = the matched keypoints of the query frame of every pair (getGoodMatches, src/Matcher.cpp:295-303): pair i = (frame i-1, frame i),
+    // or with the keyframe gate (frame link[i], frame i); links to the carried record (VIS_KF_CARRIED < 0) are skipped like pair 0
     ctx->stream = sP;
-    const int rc = vis_align_batch(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->d_p1, pl->d_ngood, pl->root * pl->root, d_init, d_out);
+    const int32_t* links = pl->kf_min ? pl->d_kf_link[pl->last_base / pl->rec_per_set] : nullptr;
+    const int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->d_p1, pl->d_ngood, pl->root * pl->root,
+                                     links, d_init, d_out);
     ctx->stream = sA;
     if (rc) return rc;
     ctx->align_k ^= 1;
@@ -618,5 +633,6 @@ extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const u
         if ((pl->d_half_set[s_] && d_gray == pl->d_half_set[s_]) || (pl->d_gx_set[s_] && d_gx == pl->d_gx_set[s_]) || (pl->d_gy_set[s_] && d_gy == pl->d_gy_set[s_]))
             pl->grad_reader[s_] = ctx->ev_align_done;
     pl->mo_align[pl->last_cur] = ctx->ev_align_done;                                 // it read the matched points of the last step's matcher-output set
+    if (links) pl->kf_reader[pl->last_base / pl->rec_per_set] = ctx->ev_align_done;  // and the links the next gate kernel of that record set rewrites
     return VIS_OK;
 }

@@ -67,6 +67,7 @@ static int validate_params(const vis_params& p) {
     if (p.f2f_iters < 0) return VIS_E_INVALID;
     if (p.pose_input != VIS_POSE_GOOD && p.pose_input != VIS_POSE_SYM) return VIS_E_INVALID;
     if (p.keypoint_capacity < 0 || p.keypoint_capacity > 65535) return VIS_E_INVALID;
+    if (p.keyframe_min_points < 0 || p.keyframe_min_points > 65535) return VIS_E_INVALID;
     return VIS_OK;
 }
 
@@ -155,7 +156,7 @@ static void sync_all(vis_ctx* ctx) {
     if (ctx->match_stream) (void)hipStreamSynchronize(ctx->match_stream);
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
     ctx->pose_pending = false; ctx->results_pending = false; ctx->align_pending = false;
-    if (ctx->batch) { for (int i = 0; i < VIS_BATCH_SETS; i++) ctx->batch->match_pending[i] = false; ctx->batch->grad_reader[0] = ctx->batch->grad_reader[1] = nullptr;
+    if (ctx->batch) { for (int i = 0; i < VIS_BATCH_SETS; i++) ctx->batch->match_pending[i] = false; ctx->batch->grad_reader[0] = ctx->batch->grad_reader[1] = nullptr; ctx->batch->kf_reader[0] = ctx->batch->kf_reader[1] = nullptr;
                       for (int i = 0; i < 2; i++) ctx->batch->mo_pose[i] = ctx->batch->mo_results[i] = ctx->batch->mo_align[i] = nullptr; }
 }
 
@@ -260,7 +261,8 @@ void plan_destroy(Plan* pl) {
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (int i = 0; i < 2; i++) { F(pl->d_half_set[i]); F(pl->d_gx_set[i]); F(pl->d_gy_set[i]); F(pl->d_g_set[i]); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
     F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx);
-    for (int i = 0; i < VIS_BATCH_SETS; i++) { F(pl->d_pq[i]); F(pl->d_pt[i]); F(pl->d_pqn[i]); }
+    for (int i = 0; i < VIS_BATCH_SETS; i++) { F(pl->d_pq[i]); F(pl->d_pt[i]); F(pl->d_pqn[i]); F(pl->d_gq[i]); F(pl->d_kf_link[i]); }
+    F(pl->d_kf_state);
     F(pl->d_knn12); F(pl->d_knn21);
     if (pl->mo_set[0][0] || pl->mo_set[1][0]) { for (int s_ = 0; s_ < 2; s_++) for (int k = 0; k < 6; k++) F(pl->mo_set[s_][k]); }    // (d_sym ... d_p2 alias one of the sets)
     else { F(pl->d_sym); F(pl->d_nsym); F(pl->d_good); F(pl->d_ngood); F(pl->d_p1); F(pl->d_p2); }                                  // a plan that failed before the sets were registered
@@ -330,6 +332,16 @@ int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npa
         HIPCHK(ctx, hipMemcpy(pl->d_pqn[sidx], qn.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
     }
     pl->d_pair_q = pl->d_pq[0]; pl->d_pair_t = pl->d_pt[0]; pl->d_pair_q_noprev = pl->d_pqn[0];
+    if (nsets > 1 && ctx->p.keyframe_min_points > 0) {             // keyframe gate of a batched stream (keyframe.hip): tables written on the device
+        pl->kf_min = ctx->p.keyframe_min_points;
+        for (int sidx = 0; sidx < nsets; sidx++) {
+            DALLOC(pl->d_gq[sidx], npairs); DALLOC(pl->d_kf_link[sidx], npairs);
+            HIPCHK(ctx, hipMemset(pl->d_gq[sidx], 0xFF, (size_t)npairs * 4));       // -1: no pair until a run has written the set
+            HIPCHK(ctx, hipMemset(pl->d_kf_link[sidx], 0xFF, (size_t)npairs * 4));
+        }
+        DALLOC(pl->d_kf_state, 2);
+        { int rc2 = reset_keyframe_state(ctx, pl); if (rc2) { plan_destroy(pl); return rc2; } }
+    }
     DALLOC(pl->d_knn12, (size_t)npairs * kcap * 2); DALLOC(pl->d_knn21, (size_t)npairs * kcap * 2);
     DALLOC(pl->d_sym, (size_t)npairs * kcap); DALLOC(pl->d_nsym, npairs);
     DALLOC(pl->d_good, (size_t)npairs * ncell); DALLOC(pl->d_ngood, npairs);
@@ -1072,6 +1084,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     sync_all(ctx);
     ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
+    { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
         std::vector<int32_t> t0((size_t)ctx->batch->L, ctx->p.fast_threshold);
         HIPCHK(ctx, hipMemcpy(ctx->batch->d_tau, t0.data(), t0.size() * 4, hipMemcpyHostToDevice));
@@ -1104,9 +1117,14 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     // and it is pure streaming work, so it runs on a stream of its own beside the (vector-ALU bound) detect kernels; the detect
     // stream joins it at the end of its chain, so "the detect stream is done" still means "d_frames may be reused".
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[0], sA);
-    if (detect) { VisRange r_("vis: ORB detect + describe"); rc = launch_detect(ctx, pl, d_frames, n, base + 1, pl->carry_from > 0 ? pl->carry_from : -1,
+    // keyframe gate on: the carried record is the last SAVED one, known only on the device -- k_keyframe_links copies it, behind the
+    // records of this batch (it reads their counts) and launch_detect's wait for the matcher that last read this set
+    if (detect) { VisRange r_("vis: ORB detect + describe"); rc = launch_detect(ctx, pl, d_frames, n, base + 1, (pl->carry_from > 0 && !pl->kf_min) ? pl->carry_from : -1,
                                                                              (stages & (VIS_STAGE_UPDATE | VIS_STAGE_GRADIENT)) ? ctx->ev_update_fork : nullptr,
-                                                                             pl->match_pending[cur] ? ctx->ev_match_done[cur] : nullptr); if (rc) return rc; }
+                                                                             pl->match_pending[cur] ? ctx->ev_match_done[cur] : nullptr);
+                  if (!rc && pl->kf_min && pl->kf_reader[cur] && hipStreamWaitEvent(sA, pl->kf_reader[cur], 0) != hipSuccess) rc = VIS_E_HIP;   // (an alignment still reading the links)
+                  if (!rc && pl->kf_min) rc = launch_keyframe_links(ctx, pl, cur, n);
+                  if (rc) return rc; }
     else if (ctx->ev_ok) for (int i = 1; i <= 4; i++) (void)hipEventRecord(ctx->ev[i], sA);
     hipStream_t sU = ctx->update_stream;
     pl->half_valid = false; pl->grad_valid = false;
@@ -1155,8 +1173,9 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     if (update_queued) HIPCHK(ctx, hipStreamWaitEvent(sA, ctx->ev_update_done, 0));
     if (stages & (VIS_STAGE_MATCH | VIS_STAGE_POSE)) HIPCHK(ctx, hipStreamWaitEvent(sM, ctx->ev_detect_done, 0));
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev_match_start, sM);
-    // pair i: query = record base+i (frame i-1, or the carried frame for i = 0), train = record base+i+1 (frame i)
-    pl->d_pair_q = have_prev ? pl->d_pq[cur] : pl->d_pqn[cur];
+    // pair i: query = record base+i (frame i-1, or the carried frame for i = 0), train = record base+i+1 (frame i); keyframe gate on:
+    // query = the record of the last saved frame before i (or -1: no pair), from the table k_keyframe_links wrote for this set
+    pl->d_pair_q = pl->kf_min ? pl->d_gq[cur] : (have_prev ? pl->d_pq[cur] : pl->d_pqn[cur]);
     pl->d_pair_t = pl->d_pt[cur];
     // the matcher-output set of this step: a step that runs the matcher takes the next one, a pose-only step reads the last one
     const int mo = pl->mo_set[1][0] ? ((stages & VIS_STAGE_MATCH) ? (pl->last_cur ^ 1) : pl->last_cur) : 0;
@@ -1210,7 +1229,7 @@ extern "C" int vis_batch_sync(vis_ctx* ctx) {
     const bool had_pose = ctx->pose_pending;
     if (ctx->pose_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->pose_stream));
     ctx->pose_pending = false; ctx->results_pending = false; ctx->align_pending = false;
-    if (ctx->batch) { for (int i = 0; i < VIS_BATCH_SETS; i++) ctx->batch->match_pending[i] = false; ctx->batch->grad_reader[0] = ctx->batch->grad_reader[1] = nullptr;
+    if (ctx->batch) { for (int i = 0; i < VIS_BATCH_SETS; i++) ctx->batch->match_pending[i] = false; ctx->batch->grad_reader[0] = ctx->batch->grad_reader[1] = nullptr; ctx->batch->kf_reader[0] = ctx->batch->kf_reader[1] = nullptr;
                       for (int i = 0; i < 2; i++) ctx->batch->mo_pose[i] = ctx->batch->mo_results[i] = ctx->batch->mo_align[i] = nullptr; }
     if (ctx->ev_ok) {
         collect_detect_timings(ctx);
@@ -1331,10 +1350,11 @@ extern "C" int vis_batch_get_knn(vis_ctx* ctx, int frame, vis_dmatch* out12, int
     Plan* pl = ctx->batch;
     if (frame < 0 || frame >= pl->last_n) return VIS_E_INVALID;
     sync_all(ctx);
-    int32_t nq = 0, nt = 0;
-    HIPCHK(ctx, hipMemcpy(&nq, pl->d_nkp + pl->last_base + frame, 4, hipMemcpyDeviceToHost));
+    int32_t nq = 0, nt = 0, q = pl->last_base + frame;
+    if (pl->kf_min) HIPCHK(ctx, hipMemcpy(&q, pl->d_gq[pl->last_base / pl->rec_per_set] + frame, 4, hipMemcpyDeviceToHost));   // keyframe gate: the query record of the pair, -1 = none
+    if (q >= 0) HIPCHK(ctx, hipMemcpy(&nq, pl->d_nkp + q, 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(&nt, pl->d_nkp + pl->last_base + frame + 1, 4, hipMemcpyDeviceToHost));
-    if (frame == 0 && !pl->pair0_valid) { nq = 0; nt = 0; }      // first frame of a stream has no pair
+    if (q < 0 || (!pl->kf_min && frame == 0 && !pl->pair0_valid)) { nq = 0; nt = 0; }      // no pair: the first frame of a stream, or a frame the gate did not save
     if (n12) *n12 = nq;
     if (n21) *n21 = nt;
     if (out12) { if (2 * nq > cap12) return VIS_E_CAPACITY; int rc = download_knn(ctx, pl->d_knn12 + (size_t)frame * pl->kcap * 2, nq, out12); if (rc) return rc; }
@@ -1365,6 +1385,21 @@ extern "C" int vis_batch_get_inlier_mask(vis_ctx* ctx, int frame, uint8_t* mask,
         if (n > cap) return VIS_E_CAPACITY;
         if (n) HIPCHK(ctx, hipMemcpy(mask, pl->d_mask + (size_t)frame * pl->pose_mcap, (size_t)n, hipMemcpyDeviceToHost));
     }
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_get_keyframes(vis_ctx* ctx, int32_t* prev, int cap, int* n_out) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    const int n = pl->last_n;
+    if (n < 1) return VIS_E_STATE;
+    if (n_out) *n_out = n;
+    if (!prev) return VIS_OK;
+    if (cap < n) return VIS_E_CAPACITY;
+    sync_all(ctx);
+    if (pl->kf_min) { HIPCHK(ctx, hipMemcpy(prev, pl->d_kf_link[pl->last_base / pl->rec_per_set], (size_t)n * 4, hipMemcpyDeviceToHost)); return VIS_OK; }
+    for (int i = 0; i < n; i++) prev[i] = i - 1;
+    prev[0] = pl->pair0_valid ? VIS_KF_CARRIED : VIS_KF_FIRST;
     return VIS_OK;
 }
 

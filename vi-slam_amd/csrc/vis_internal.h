@@ -131,6 +131,14 @@ struct Plan {
     int32_t* d_pq[VIS_BATCH_SETS] = {}; int32_t* d_pt[VIS_BATCH_SETS] = {}; int32_t* d_pqn[VIS_BATCH_SETS] = {};
     bool match_pending[VIS_BATCH_SETS] = {};
     bool pair0_valid = false;                // last run: frame 0 had a predecessor
+    // keyframe gate of a batch plan (vis_params.keyframe_min_points at vis_batch_plan; 0 = off, none of the buffers exist).  Per
+    // record set: the gated query table the matcher reads instead of d_pq / d_pqn (train table unchanged) and the link table
+    // (vis_batch_get_keyframes' prev[], the alignment's previous frames).  d_kf_state = {last saved record (absolute, -1 = none),
+    // a frame has been saved since reset}: written by k_keyframe_links, read by the next one (keyframe.hip) on the detect stream.
+    int kf_min = 0;
+    int32_t* d_gq[VIS_BATCH_SETS] = {}; int32_t* d_kf_link[VIS_BATCH_SETS] = {};
+    int32_t* d_kf_state = nullptr;
+    hipEvent_t kf_reader[VIS_BATCH_SETS] = {};   // the last vis_batch_align that read d_kf_link[s] on the pose stream (nullptr: none pending)
 };
 
 #define VIS_POSE_TABLE_M 64                  // the frame-at-a-time pose entry points take their RANSAC samples from the table for M <= 64 (root^2 = 49 in the reference)
@@ -321,6 +329,11 @@ int launch_expand(vis_ctx* ctx, Plan* pl, int rec_first, int rec_count);
 int launch_match(vis_ctx* ctx, Plan* pl, int npairs);
 int launch_filter(vis_ctx* ctx, Plan* pl, int npairs);
 int launch_pose(vis_ctx* ctx, Plan* pl, int npairs);
+int launch_keyframe_links(vis_ctx* ctx, Plan* pl, int set, int n);   // keyframe.hip: carry the last saved record into the set, gate + link the batch
+int reset_keyframe_state(vis_ctx* ctx, Plan* pl);                     // keyframe.hip: nothing saved, nothing carried
+int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int w, int h, int stride, int n,
+                      const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy, const float* d_pts, const int32_t* d_npts,
+                      int max_pts, const int32_t* d_prev, const vis_se3f* d_init, vis_align_result* d_out);   // align.hip: vis_align_batch with pair i = (d_prev[i] -> i), nullptr = i-1
 int launch_half_pyramid(vis_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, uint8_t* d_out[5]);
 // gradient.hip: Camera::Update / computeGradient / patch builders, batched
 size_t vis_grad_frame_elems(int w, int h);

@@ -47,6 +47,7 @@ class Params(C.Structure):
         ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
         ("f2f_iters", C.c_int32), ("f2f_threshold", C.c_double),
         ("pose_input", C.c_int32), ("keypoint_capacity", C.c_int32),
+        ("keyframe_min_points", C.c_int32),
     ]
 
     def copy(self):
@@ -101,6 +102,7 @@ SYM_REFERENCE_EFFECTIVE, SYM_INTENDED = 0, 1
 STAGE_DETECT, STAGE_MATCH, STAGE_POSE, STAGE_ALL = 1, 2, 4, 7
 STAGE_UPDATE, STAGE_FRAME = 8, 15          # Camera::Update's half pyramid at the head of the detect chain; FRAME = ALL | UPDATE
 STAGE_GRADIENT = 16                        # Camera::computeGradient into plan-owned buffers, beside the detect chain (implies UPDATE)
+KF_CARRIED, KF_NOT_SAVED, KF_FIRST = -1, -2, -3   # batch_get_keyframes(): no frame of this batch to match against
 
 # every symbol include/vislam_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -116,7 +118,7 @@ ABI_SYMBOLS = [
     "vis_feeder_create", "vis_feeder_destroy", "vis_feeder_host_buffer", "vis_feeder_submit", "vis_feeder_release",
     "vis_default_align_params", "vis_estimate_pose_features", "vis_align_batch", "vis_batch_align",
     "vis_synth_frame_parallax", "vis_synth_frames_device", "vis_batch_results_async", "vis_batch_half_pyramid", "vis_batch_gradients", "vis_batch_fast_thresholds",
-    "vis_se3_exp", "vis_se3_mul", "vis_se3_from_rt", "vis_se3_matrix",
+    "vis_se3_exp", "vis_se3_mul", "vis_se3_from_rt", "vis_se3_matrix", "vis_batch_get_keyframes",
 ]
 
 
@@ -163,6 +165,8 @@ def _load():
         lib.vis_batch_get_inlier_mask.argtypes = [vp, ci, vp, ci, ip]
         lib.vis_debug_counters.argtypes = [vp, vp]
     lib.vis_batch_status.argtypes = [vp, ip]
+    if hasattr(lib, "vis_batch_get_keyframes"):         # (absent from older A/B builds)
+        lib.vis_batch_get_keyframes.argtypes = [vp, vp, ci, ip]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -652,6 +656,15 @@ class Context:
         n = C.c_int(0)
         self._chk(lib.vis_batch_get_inlier_mask(self._h, frame, _ptr(mask), cap, C.byref(n)), "vis_batch_get_inlier_mask")
         return mask[:n.value].copy()
+
+    def batch_get_keyframes(self):
+        """the pairing of the last batch_run (int32 per frame): the batch index of the frame each frame was matched against, or
+        KF_CARRIED / KF_NOT_SAVED / KF_FIRST"""
+        n = C.c_int(0)
+        self._chk(lib.vis_batch_get_keyframes(self._h, None, 0, C.byref(n)), "vis_batch_get_keyframes")
+        prev = np.zeros(n.value, np.int32)
+        self._chk(lib.vis_batch_get_keyframes(self._h, _ptr(prev), n.value, C.byref(n)), "vis_batch_get_keyframes")
+        return prev
 
     def batch_pose(self, frame):
         E, R, t = np.zeros(9), np.zeros(9), np.zeros(3)
