@@ -379,6 +379,37 @@ int  vis_batch_get_inlier_mask(vis_ctx* ctx, int frame, uint8_t* mask, int cap, 
  * frame 0.  *n_out = frames of the last batch; VIS_E_CAPACITY if cap < *n_out.  Synchronises. */
 enum { VIS_KF_CARRIED = -1, VIS_KF_NOT_SAVED = -2, VIS_KF_FIRST = -3 };
 int  vis_batch_get_keyframes(vis_ctx* ctx, int32_t* prev, int cap, int* n_out);
+/* ---- batched camera tracking (VISystemGPU::AddFrameGPU after detection, src/VISystemGPU.cpp:137-175) --------------------
+ * For every frame of the last vis_batch_run: the alignment of the frame's keyframe pair (VISystem::EstimatePoseFeatures) and
+ * VISystem::Track (src/VISystem.cpp:1567-1635), final_poseCam = final_poseCam * SE3(matrix(pose).R, pose.t) -- the pose the GPU main
+ * writes to its CSV (positionCam = pose.t, qOrientationCam = pose.q, src/main_vi_slamGPU.cpp:123-150).
+ *   Preconditions (else VIS_E_STATE): the last vis_batch_run had VIS_STAGE_MATCH | VIS_STAGE_GRADIENT, pose_input == VIS_POSE_GOOD,
+ *     n == the frames of that run, and EVERY vis_batch_run since vis_batch_plan / vis_batch_reset was tracked, once (the pair to the
+ *     carried keyframe reads the snapshot the call for the launch before took: a launch that was not tracked leaves none).
+ *   d_align[i] (n records): the alignment of frame i's pair, with vis_batch_get_keyframes' pairing -- gate off (i-1 -> i), gate on
+ *     (prev[i] -> i) -- INCLUDING the pair to the keyframe carried from an earlier launch (VIS_KF_CARRIED), which vis_batch_align
+ *     skips.  A frame without a pair gets a zeroed record.  d_init: n poses or NULL, as for vis_batch_align.
+ *   d_track[i] (n records): final_poseCam after frame i.  A saved frame with a pair composes its own residual; a frame the gate
+ *     refused composes the last residual again once two frames have been saved (AddFrameGPU re-estimates the unchanged last pair,
+ *     frameList.size() > 1) -- that residual may come from an earlier launch; otherwise the pose is unchanged.
+ *   The chain continues across launches.  vis_batch_reset restarts it at the pose last given to vis_batch_track_init and forgets
+ *   the last residual; vis_batch_plan restarts it at identity.
+ *   Asynchronous on the POSE stream with vis_batch_align's ordering (it overlaps the next vis_batch_run the same way): d_frames,
+ *   the plan's gradients, d_align and d_track are in use until vis_batch_sync.  Host and device compose with the same code, so
+ *   d_track equals vis_se3_mul / vis_se3_from_rt / vis_se3_matrix applied in frame order byte for byte. */
+enum { VIS_TRACK_NONE = -4 };
+typedef struct vis_track_result {
+    vis_se3f pose;               /* final_poseCam after this frame */
+    int32_t  composed;           /* the pair whose residual Track composed for this frame: the frame's own batch index (a saved
+                                    frame with a pair); the batch index of the last saved frame (a frame the gate refused);
+                                    VIS_KF_CARRIED (that saved frame is in an earlier launch); VIS_TRACK_NONE: Track did not run
+                                    (fewer than two frames saved since vis_batch_plan / vis_batch_reset) */
+} vis_track_result;              /* 32 bytes */
+/* final_poseCam to continue from (InitializeSystemGPU's initial camera pose, src/VISystemGPU.cpp:107-115); NULL = identity.  Sets
+ * the current pose of the chain (the last residual is kept) and the pose vis_batch_reset restarts at.  Needs a plan; synchronises. */
+int  vis_batch_track_init(vis_ctx* ctx, const vis_se3f* pose);
+int  vis_batch_track(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
+                     const vis_se3f* d_init, vis_align_result* d_align, vis_track_result* d_track);
 /* what the pose stage leaves per pair on the device (vis_batch_results_async copies these records) */
 typedef struct vis_pose_result {
     double E[9], R[9], t[3];

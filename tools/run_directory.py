@@ -10,6 +10,9 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --check K: the first K frames also go through the CPU oracle's per-frame pipeline; keypoints, descriptors, good matches and the pose
              record are compared (bit-exact / 1e-7) -- the same checks as tests/test_configs_gpu.py::test_config1...
   --cpu-seconds S: times the oracle on the same frames for about S seconds (the `cpu_baseline` of this dataset).
+  --track out.csv: the camera trajectory as the reference's GPU main writes it (src/main_vi_slamGPU.cpp:137-144, its first seven
+             columns): one row per frame, positionCam x, y, z, qOrientationCam x, y, z, w -- vis_batch_track after every batch (the
+             GPU main's keyframe rule, keyframe_min_points = 1; alignment with the intrinsics of --K fx,fy,cx,cy), from the identity.
 """
 import argparse
 import json
@@ -34,6 +37,8 @@ def main():
     ap.add_argument("--check", type=int, default=0, help="compare the first K frames against the CPU oracle")
     ap.add_argument("--cpu-seconds", type=float, default=0.0)
     ap.add_argument("--raw-size", default=None, help="WxH of headerless .raw files")
+    ap.add_argument("--track", default=None, metavar="CSV", help="write the per-frame camera pose (positionCam, qOrientationCam) here")
+    ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     a = ap.parse_args()
 
     names = vislam.image_list(a.directory)[:a.frames]
@@ -48,6 +53,17 @@ def main():
     p = vislam.default_params()
     p.nfeatures, p.w_size, p.h_size = a.nfeatures, w, h
     p.fy = p.fx
+    stages = vislam.STAGE_FRAME
+    if a.track:
+        import ctypes as C
+        p.keyframe_min_points = 1                            # CameraGPU::addGPUKeyframe's rule
+        stages |= vislam.STAGE_GRADIENT
+        tap = vislam.default_align_params()
+        tap.fx, tap.fy, tap.cx, tap.cy = (float(x) for x in a.K.split(","))
+        d_align = torch.empty(a.batch * C.sizeof(vislam.AlignResult), dtype=torch.uint8, device="cuda")
+        d_track = torch.empty(a.batch * C.sizeof(vislam.TrackResult), dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        poses = []
     ctx = vislam.Context(0, p)
     B = min(a.batch, len(paths))
     ctx.batch_plan(w, h, w, B)
@@ -67,9 +83,14 @@ def main():
                 host[first + i] = buf[i]
         t_decode += time.perf_counter() - td
         d = feed.submit(k, nb)
-        ctx.batch_run(d, nb, vislam.STAGE_FRAME)
+        ctx.batch_run(d, nb, stages)
+        if a.track:
+            ctx.batch_track(tap, d, nb, 0, d_align.data_ptr(), d_track.data_ptr())
         feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
+        if a.track:
+            raw = d_track[:nb * C.sizeof(vislam.TrackResult)].cpu().numpy().tobytes()
+            poses += [vislam.TrackResult.from_buffer_copy(raw, i * C.sizeof(vislam.TrackResult)).pose for i in range(nb)]
         if ctx.batch_status() != 0:
             raise SystemExit("device capacity flag set")
         for i in range(nb):
@@ -110,6 +131,11 @@ def main():
             if time.perf_counter() - tc > a.cpu_seconds:
                 break
         out["cpu_baseline"] = {"value": m / (time.perf_counter() - tc), "unit": "frames/s", "cores": 1, "kind": "port", "sample": f"{m} frames of this directory"}
+    if a.track:
+        with open(a.track, "w") as f:
+            for e in poses:
+                f.write(",".join("%.9g" % v for v in (e.tx, e.ty, e.tz, e.qx, e.qy, e.qz, e.qw)) + "\n")
+        out["track_csv"] = a.track
     feed.close()
     ctx.close()
     print(json.dumps(out, allow_nan=False))

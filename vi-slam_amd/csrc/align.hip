@@ -24,7 +24,6 @@
 #include <cstring>
 
 #define DEV __device__ __forceinline__
-#define HD __host__ __device__ inline              // the SE3 pieces also back the host-side vis_se3_* helpers of the adapters
 #define AL_THREADS 256
 #define AL_MAXKP 200                     // min(num_max_keypoints, 200), src/Camera.cpp:377
 
@@ -44,111 +43,12 @@ struct AlignArgs {
     const vis_se3f* init; vis_align_result* out;
     int f1_off, f2_off, out_off;                          // frame index of image 1 / image 2 / result slot = pair + offset
     const int32_t* prev;                                  // generated mode, keyframe gate: image 1 = frame prev[slot]; < 0: no pair (record left as cleared)
+    // vis_batch_track: image 1 of a pair whose previous frame is VIS_KF_CARRIED (an earlier launch) is the plan's keyframe snapshot,
+    // one frame in the layout of a gradient set with a dense level 0 (track.hip); nullptr: such a pair is skipped like any link < 0
+    const uint8_t* c_gray; const int16_t* c_gx; const int16_t* c_gy;
 };
 
-// ---- Sophus::SE3f pieces (see oracle/align.cpp for the citations) -------------------------------------------
-struct Quat { float w, x, y, z; };
-struct Se3 { Quat q; float t[3]; };
-
-// deterministic double sin/cos, identical to detect.hip's / the oracle's sincos_det
-HD void al_sincos(double x, double* s, double* c) {
-    const double TWO_OVER_PI = 6.36619772367581382433e-01;
-    const double PIO2_HI = 1.57079632673412561417e+00;
-    const double PIO2_LO = 6.07710050650619224932e-11;
-    const double kd = rint(x * TWO_OVER_PI);
-    const int k = (int)kd;
-    const double r = (x - kd * PIO2_HI) - kd * PIO2_LO;
-    const double z = r * r;
-    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03,
-                 S3 = -1.98412698298579493134e-04, S4 = 2.75573137070700676789e-06,
-                 S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03,
-                 C3 = 2.48015872894767294178e-05, C4 = -2.75573143513906633035e-07,
-                 C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    const double ps = S1 + z * (S2 + z * (S3 + z * (S4 + z * (S5 + z * S6))));
-    const double sr = r + (r * z) * ps;
-    const double pc = C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6))));
-    const double cr = (1.0 - 0.5 * z) + (z * z) * pc;
-    switch (k & 3) {
-        case 0: *s = sr;  *c = cr;  break;
-        case 1: *s = cr;  *c = -sr; break;
-        case 2: *s = -sr; *c = -cr; break;
-        default: *s = -cr; *c = sr; break;
-    }
-}
-HD float sin_det(float a) { double s, c; al_sincos((double)a, &s, &c); return (float)s; }
-HD float cos_det(float a) { double s, c; al_sincos((double)a, &s, &c); return (float)c; }
-
-HD Quat qmul(const Quat& a, const Quat& b) {
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
-HD void qrot(const Quat& q, const float (&v)[3], float (&out)[3]) {
-    float uv0 = q.y * v[2] - q.z * v[1], uv1 = q.z * v[0] - q.x * v[2], uv2 = q.x * v[1] - q.y * v[0];
-    uv0 += uv0; uv1 += uv1; uv2 += uv2;
-    const float c0 = q.y * uv2 - q.z * uv1, c1 = q.z * uv0 - q.x * uv2, c2 = q.x * uv1 - q.y * uv0;
-    out[0] = v[0] + q.w * uv0 + c0;
-    out[1] = v[1] + q.w * uv1 + c1;
-    out[2] = v[2] + q.w * uv2 + c2;
-}
-HD void qmat(const Quat& q, float (&R)[9]) {
-    const float tx = 2.f * q.x, ty = 2.f * q.y, tz = 2.f * q.z;
-    const float twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const float txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const float tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0] = 1.f - (tyy + tzz); R[1] = txy - twz;         R[2] = txz + twy;
-    R[3] = txy + twz;         R[4] = 1.f - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;         R[7] = tyz + twx;         R[8] = 1.f - (txx + tyy);
-}
-HD Se3 se3_exp(const float (&a)[6]) {
-    const float o0 = a[3], o1 = a[4], o2 = a[5];
-    const float theta_sq = o0 * o0 + o1 * o1 + o2 * o2;
-    const float theta = sqrtf(theta_sq);
-    const float half = 0.5f * theta;
-    float imag, real;
-    const float eps = 1e-5f;
-    if (theta < eps) {
-        const float po4 = theta_sq * theta_sq;
-        imag = 0.5f - (float)(1.0 / 48.0) * theta_sq + (float)(1.0 / 3840.0) * po4;
-        real = 1.f - (float)(1.0 / 8.0) * theta_sq + (float)(1.0 / 384.0) * po4;
-    } else {
-        imag = sin_det(half) / theta;
-        real = cos_det(half);
-    }
-    Se3 r;
-    r.q.w = real; r.q.x = imag * o0; r.q.y = imag * o1; r.q.z = imag * o2;
-    const float O[9] = {0.f, -o2, o1, o2, 0.f, -o0, -o1, o0, 0.f};
-    float O2[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    float V[9];
-    if (theta < eps) qmat(r.q, V);
-    else {
-        const float ca = (1.f - cos_det(theta)) / theta_sq;
-        const float cb = (theta - sin_det(theta)) / (theta_sq * theta);
-#pragma unroll
-        for (int i = 0; i < 9; i++) V[i] = ((i % 4 == 0) ? 1.f : 0.f) + ca * O[i] + cb * O2[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 3; i++) r.t[i] = V[3 * i] * a[0] + V[3 * i + 1] * a[1] + V[3 * i + 2] * a[2];
-    return r;
-}
-HD Se3 se3_mul(const Se3& a, const Se3& b) {
-    Se3 r = a;
-    float rt[3];
-    qrot(a.q, b.t, rt);
-    r.t[0] = a.t[0] + rt[0]; r.t[1] = a.t[1] + rt[1]; r.t[2] = a.t[2] + rt[2];
-    r.q = qmul(a.q, b.q);
-    const float sn = r.q.w * r.q.w + r.q.x * r.q.x + r.q.y * r.q.y + r.q.z * r.q.z;
-    if (sn != 1.f) { const float s = 2.f / (1.f + sn); r.q.w *= s; r.q.x *= s; r.q.y *= s; r.q.z *= s; }
-    return r;
-}
+#include "se3_core.h"
 
 // hal::LU32f as cv::invert(DECOMP_LU) uses it: A (6x6, row-major, LDS) -> B = inverse; false = singular.  The matrices are
 // held in registers for the factorisation (fully unrolled; a row exchange with the runtime pivot row is a chain of selects):
@@ -228,7 +128,8 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int pair = blockIdx.x;
     const int f1 = G.prev ? G.prev[pair + G.out_off] : pair + G.f1_off, f2 = pair + G.f2_off;
-    if (f1 < 0) return;                                                  // (uniform: the whole workgroup)
+    const bool carried = f1 == VIS_KF_CARRIED && G.c_gray != nullptr;
+    if (f1 < 0 && !carried) return;                                      // (uniform: the whole workgroup)
     Se3 pose = {{1.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
     if (G.init) {
         const vis_se3f in = G.init[pair + G.out_off];
@@ -284,10 +185,12 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
             N = s_pre[AL_THREADS];
             __syncthreads();
         }
-        const uint8_t* I1 = V.i1 + (size_t)f1 * V.img_fstride;
+        const size_t coff = (size_t)(V.gx - G.lv[0].gx);                     // the level's place in a frame of the set (snapshot: the same)
+        const uint8_t* I1 = carried ? G.c_gray + coff : V.i1 + (size_t)f1 * V.img_fstride;
         const uint8_t* I2 = V.i2 + (size_t)f2 * V.img_fstride;
-        const int16_t* GX = V.gx + (size_t)f1 * V.grad_fstride;
-        const int16_t* GY = V.gy + (size_t)f1 * V.grad_fstride;
+        const int16_t* GX = carried ? G.c_gx + coff : V.gx + (size_t)f1 * V.grad_fstride;
+        const int16_t* GY = carried ? G.c_gy + coff : V.gy + (size_t)f1 * V.grad_fstride;
+        const int rs1 = carried ? V.acols : V.rowstride;                         // (the snapshot's level 0 is dense)
         const float fx = V.fx, fy = V.fy, cx = V.cx, cy = V.cy, invfx = V.invfx, invfy = V.invfy;
         float error = 0.f, last_error = 50000.f;
         int k = 0, nres = 0;
@@ -338,7 +241,7 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
                             int rx = (int)roundf(x2), ry = (int)roundf(y2);
                             if (rx > V.acols - 1) rx = V.acols - 1;
                             if (ry > V.arows - 1) ry = V.arows - 1;
-                            o1 = (size_t)iy1 * V.rowstride + ix1; o2 = (size_t)ry * V.rowstride + rx; go = (size_t)iy1 * V.acols + ix1;   // gradients are dense
+                            o1 = (size_t)iy1 * rs1 + ix1; o2 = (size_t)ry * V.rowstride + rx; go = (size_t)iy1 * V.acols + ix1;   // gradients are dense
                         }
                         ok[u] = v; x2a[u] = x2; y2a[u] = y2; iza[u] = inv_z2;
                     }
@@ -423,8 +326,6 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
 // ------------------------------------------------------------------------------------------------ host side
 // Sophus::SE3f value operations for the host adapters (VISystem::Track composes poses, src/VISystem.cpp:1567-1635): the same
 // functions the kernel runs, evaluated on the host.
-static Se3 to_se3(const vis_se3f& a) { Se3 r; r.q.w = a.qw; r.q.x = a.qx; r.q.y = a.qy; r.q.z = a.qz; r.t[0] = a.tx; r.t[1] = a.ty; r.t[2] = a.tz; return r; }
-static void from_se3(const Se3& e, vis_se3f* o) { o->qx = e.q.x; o->qy = e.q.y; o->qz = e.q.z; o->qw = e.q.w; o->tx = e.t[0]; o->ty = e.t[1]; o->tz = e.t[2]; }
 extern "C" void vis_se3_exp(const float a[6], vis_se3f* out) { const float v[6] = {a[0], a[1], a[2], a[3], a[4], a[5]}; from_se3(se3_exp(v), out); }
 extern "C" void vis_se3_mul(const vis_se3f* a, const vis_se3f* b, vis_se3f* out) { from_se3(se3_mul(to_se3(*a), to_se3(*b)), out); }
 extern "C" void vis_se3_matrix(const vis_se3f* a, float M[16]) {
@@ -432,29 +333,7 @@ extern "C" void vis_se3_matrix(const vis_se3f* a, float M[16]) {
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) M[4 * i + j] = R[3 * i + j];
     M[3] = a->tx; M[7] = a->ty; M[11] = a->tz; M[12] = M[13] = M[14] = 0.f; M[15] = 1.f;
 }
-// SE3(Matrix3 R, Point t): Eigen's rotation-matrix -> quaternion conversion
-extern "C" void vis_se3_from_rt(const float R[9], const float t[3], vis_se3f* out) {
-    float qw, v[3];
-    float tr = R[0] + R[4] + R[8];
-    if (tr > 0.f) {
-        tr = sqrtf(tr + 1.f);
-        qw = 0.5f * tr;
-        tr = 0.5f / tr;
-        v[0] = (R[7] - R[5]) * tr; v[1] = (R[2] - R[6]) * tr; v[2] = (R[3] - R[1]) * tr;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        tr = sqrtf(R[4 * i] - R[4 * j] - R[4 * k] + 1.f);
-        v[i] = 0.5f * tr;
-        tr = 0.5f / tr;
-        qw = (R[3 * k + j] - R[3 * j + k]) * tr;
-        v[j] = (R[3 * j + i] + R[3 * i + j]) * tr;
-        v[k] = (R[3 * k + i] + R[3 * i + k]) * tr;
-    }
-    out->qx = v[0]; out->qy = v[1]; out->qz = v[2]; out->qw = qw; out->tx = t[0]; out->ty = t[1]; out->tz = t[2];
-}
+extern "C" void vis_se3_from_rt(const float R[9], const float t[3], vis_se3f* out) { se3_from_rt_f(R, t, out); }
 
 extern "C" void vis_default_align_params(vis_align_params* ap) {
     if (!ap) return;
@@ -546,14 +425,16 @@ extern "C" int vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const u
                                const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
                                const float* d_pts, const int32_t* d_npts, int max_pts,
                                const vis_se3f* d_init, vis_align_result* d_out) {
-    return align_batch_links(ctx, ap, d_frames, w, h, stride, n, d_gray, d_gx, d_gy, d_pts, d_npts, max_pts, nullptr, d_init, d_out);
+    return align_batch_links(ctx, ap, d_frames, w, h, stride, n, d_gray, d_gx, d_gy, d_pts, d_npts, max_pts, nullptr, nullptr, d_init, d_out);
 }
 
 // d_prev (n entries, device): pair i aligns frame d_prev[i] -> frame i, d_prev[i] < 0 = no pair (a zeroed record); every record is
 // cleared first.  The frames d_prev names are frames of the same batch (d_prev[i] < i: the keyframe links of vis_batch_run).
+// snap (vis_batch_track): the snapshot of the keyframe carried from an earlier launch; pair 0 (gate off) and every pair linked to
+// VIS_KF_CARRIED are aligned against it (one workgroup per frame instead of per pair 1..n-1).  nullptr: those pairs are skipped.
 int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int w, int h, int stride, int n,
                       const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy, const float* d_pts, const int32_t* d_npts,
-                      int max_pts, const int32_t* d_prev, const vis_se3f* d_init, vis_align_result* d_out) {
+                      int max_pts, const int32_t* d_prev, const TrackSnapshot* snap, const vis_se3f* d_init, vis_align_result* d_out) {
     if (!ctx || !d_frames || !d_gray || !d_gx || !d_gy || !d_pts || !d_npts || !d_out) return VIS_E_INVALID;
     int rc = check_align_params(ap, w, h);
     if (rc) return rc;
@@ -567,7 +448,8 @@ int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d
         const int rc0 = launch_copy_jobs(ctx, st, 1, dsts, srcs, bytes);
         if (rc0) return rc0;
     }
-    if (n < 2) return VIS_OK;
+    const int pairs = snap ? n : n - 1;
+    if (pairs < 1) return VIS_OK;
     AlignArgs G; std::memset(&G, 0, sizeof(G));
     fill_level_intrinsics(*ap, G);
     const size_t fe = vis_grad_frame_elems(w, h);
@@ -584,25 +466,45 @@ int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d
     G.pts = d_pts; G.npts = d_npts; G.max_pts = max_pts; G.init = d_init; G.out = d_out;
     G.f1_off = 0; G.f2_off = 1; G.out_off = 1;                                       // workgroup q = pair (frame q -> frame q+1), result slot q+1
     G.prev = d_prev;                                                                 // (or frame d_prev[q+1] -> frame q+1)
+    if (snap) {                                                                      // workgroup q = frame q: (frame q-1, or d_prev[q]) -> frame q
+        G.f1_off = -1; G.f2_off = 0; G.out_off = 0;                                  // (frame -1 = VIS_KF_CARRIED: the snapshot, when there is one)
+        if (snap->valid) { G.c_gray = snap->gray; G.c_gx = snap->gx; G.c_gy = snap->gy; }
+    }
     const int used = std::min(max_pts, AL_MAXKP);
     const size_t lds = (size_t)used * 121 * 4;                                       // largest patch: (2*5+1)^2 pixels per keypoint
     if (lds > 65536 - 4096) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_align<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_align<true>, dim3(n - 1), dim3(AL_THREADS), lds, st, G);
+    hipLaunchKernelGGL(k_align<true>, dim3(pairs), dim3(AL_THREADS), lds, st, G);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }
 
-extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
-                               const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
-                               const vis_se3f* d_init, vis_align_result* d_out) {
-    if (!ctx) return VIS_E_INVALID;
+// vis_batch_align and vis_batch_track: the alignment of the last vis_batch_run's pairs on the pose stream, with its ordering and
+// reader events; d_track != nullptr = vis_batch_track (every frame's pair, then the keyframe snapshot and the trajectory chain)
+static int batch_align_stream(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
+                              const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
+                              const vis_se3f* d_init, vis_align_result* d_out, vis_track_result* d_track) {
+    if (!ctx) return d_track ? VIS_E_STATE : VIS_E_INVALID;
     Plan* pl = ctx->batch;
     if (!pl || pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
     if (ctx->p.pose_input != VIS_POSE_GOOD) return VIS_E_STATE;                       // needs the grid-filtered matches in d_p1
     bool plan_set = false;
     if (!d_gray && !d_gx && !d_gy) {                                                   // the plan's own gradients (VIS_STAGE_GRADIENT of the last vis_batch_run)
-        if (!pl->grad_valid) { ctx->err = "vis_batch_align: no gradient buffers given and the last vis_batch_run had no VIS_STAGE_GRADIENT"; return VIS_E_STATE; }
+        if (!pl->grad_valid) { ctx->err = d_track ? "vis_batch_track: the last vis_batch_run had no VIS_STAGE_GRADIENT"
+                                                  : "vis_batch_align: no gradient buffers given and the last vis_batch_run had no VIS_STAGE_GRADIENT"; return VIS_E_STATE; }
         d_gray = pl->d_half; d_gx = pl->d_gx; d_gy = pl->d_gy; plan_set = true;
+    }
+    if (d_track) {
+        if (!d_frames || !d_out) return VIS_E_INVALID;
+        if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_track: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+        // the pair to the carried keyframe reads the snapshot the call for the launch before wrote: every launch since
+        // vis_batch_plan / vis_batch_reset must have been tracked, once
+        if (pl->run_seq != pl->track_seq + 1) {
+            ctx->err = pl->run_seq == pl->track_seq ? "vis_batch_track: this launch has been tracked already"
+                                                    : "vis_batch_track: a vis_batch_run since vis_batch_plan / vis_batch_reset was not tracked (its keyframe is gone)";
+            return VIS_E_STATE;
+        }
+        const int rc = ensure_track_buffers(ctx, pl);
+        if (rc) return rc;
     }
     // One persistent workgroup per pair, a chain of dependent iterations: latency-bound work that fits beside the next batch's
     // detect chain.  It runs on the pose stream, behind (a) everything queued on the context's stream so far -- the gradients of
@@ -614,13 +516,19 @@ extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const u
     HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
     if (pl->match_pending[pl->last_base / pl->rec_per_set]) HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_match_done[pl->last_base / pl->rec_per_set], 0));
     // d_p1 = the matched keypoints of the query frame of every pair (getGoodMatches, src/Matcher.cpp:295-303): pair i = (frame i-1, frame i),
-    // or with the keyframe gate (frame link[i], frame i); links to the carried record (VIS_KF_CARRIED < 0) are skipped like pair 0
+    // or with the keyframe gate (frame link[i], frame i); links to the carried record (VIS_KF_CARRIED < 0) are skipped like pair 0 --
+    // except by vis_batch_track, which aligns them against the snapshot of that keyframe (its matched points are in d_p1 like any other)
     ctx->stream = sP;
     const int32_t* links = pl->kf_min ? pl->d_kf_link[pl->last_base / pl->rec_per_set] : nullptr;
-    const int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->d_p1, pl->d_ngood, pl->root * pl->root,
-                                     links, d_init, d_out);
+    TrackSnapshot snap{};
+    if (d_track) { snap = pl->snap; snap.valid = pl->kf_min ? pl->track_seq > 0 : pl->pair0_valid; }   // (gate on: only a link says whether it is used)
+    int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->d_p1, pl->d_ngood, pl->root * pl->root,
+                               links, d_track ? &snap : nullptr, d_init, d_out);
+    if (!rc && d_track) rc = launch_track_snapshot(ctx, pl, d_frames, d_gray, d_gx, d_gy, links, n);
+    if (!rc && d_track) rc = launch_track_chain(ctx, pl, links, n, d_out, d_track);
     ctx->stream = sA;
     if (rc) return rc;
+    if (d_track) pl->track_seq = pl->run_seq;
     ctx->align_k ^= 1;
     ctx->ev_align_done = ctx->ev_align_done2[ctx->align_k];                           // (two events in turn: the one before stays valid for the set it guards)
     HIPCHK(ctx, hipEventRecord(ctx->ev_align_done, sP));
@@ -635,4 +543,16 @@ extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const u
     pl->mo_align[pl->last_cur] = ctx->ev_align_done;                                 // it read the matched points of the last step's matcher-output set
     if (links) pl->kf_reader[pl->last_base / pl->rec_per_set] = ctx->ev_align_done;  // and the links the next gate kernel of that record set rewrites
     return VIS_OK;
+}
+
+extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
+                               const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
+                               const vis_se3f* d_init, vis_align_result* d_out) {
+    return batch_align_stream(ctx, ap, d_frames, n, d_gray, d_gx, d_gy, d_init, d_out, nullptr);
+}
+
+extern "C" int vis_batch_track(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
+                               const vis_se3f* d_init, vis_align_result* d_align, vis_track_result* d_track) {
+    if (!d_track) return ctx && ctx->batch ? VIS_E_INVALID : VIS_E_STATE;
+    return batch_align_stream(ctx, ap, d_frames, n, nullptr, nullptr, nullptr, d_init, d_align, d_track);
 }

@@ -263,6 +263,7 @@ void plan_destroy(Plan* pl) {
     F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx);
     for (int i = 0; i < VIS_BATCH_SETS; i++) { F(pl->d_pq[i]); F(pl->d_pt[i]); F(pl->d_pqn[i]); F(pl->d_gq[i]); F(pl->d_kf_link[i]); }
     F(pl->d_kf_state);
+    F(pl->snap.gray); F(pl->d_track_state);
     F(pl->d_knn12); F(pl->d_knn21);
     if (pl->mo_set[0][0] || pl->mo_set[1][0]) { for (int s_ = 0; s_ < 2; s_++) for (int k = 0; k < 6; k++) F(pl->mo_set[s_][k]); }    // (d_sym ... d_p2 alias one of the sets)
     else { F(pl->d_sym); F(pl->d_nsym); F(pl->d_good); F(pl->d_ngood); F(pl->d_p1); F(pl->d_p2); }                                  // a plan that failed before the sets were registered
@@ -1085,6 +1086,8 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     sync_all(ctx);
     ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
+    ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
+    { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
         std::vector<int32_t> t0((size_t)ctx->batch->L, ctx->p.fast_threshold);
         HIPCHK(ctx, hipMemcpy(ctx->batch->d_tau, t0.data(), t0.size() * 4, hipMemcpyHostToDevice));
@@ -1218,7 +1221,18 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     if (detect) { pl->run_count++; pl->carry_from = base + n; }
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[8], sA);
     pl->last_n = n; pl->last_base = base; pl->last_cur = mo;
+    pl->last_stages = stages; pl->run_seq++;                      // (what vis_batch_track checks)
     return VIS_OK;
+}
+
+extern "C" int vis_batch_track_init(vis_ctx* ctx, const vis_se3f* pose) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                // (a chain kernel in flight writes the state)
+    Plan* pl = ctx->batch;
+    pl->track_init = pose ? *pose : vis_se3f{0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    const int rc = ensure_track_buffers(ctx, pl);
+    return rc ? rc : reset_track_state(ctx, pl, true);
 }
 
 extern "C" int vis_batch_sync(vis_ctx* ctx) {

@@ -39,6 +39,11 @@ struct LevelInfo {
 // device-resident compact kNN entry: key = (dist << 16) | trainIdx, 0xFFFFFFFF = none
 typedef vis_pose_result PoseOut;       // E, R, t (double) + n_inliers, n_pose_good, iters_run, n_points, n_models
 
+// vis_batch_track's keyframe snapshot: one frame in the layout of a gradient-set frame (vis_grad_frame_elems elements per array),
+// level 0 of gray dense (w x h); valid = the pair to the carried keyframe may read it (set per call, not stored)
+struct TrackSnapshot { uint8_t* gray = nullptr; int16_t* gx = nullptr; int16_t* gy = nullptr; bool valid = false; };
+// the trajectory chain's device state: final_poseCam, the last residual Track composed and whether there is one (two frames saved)
+struct TrackState { vis_se3f pose; vis_se3f last; int32_t have_last; int32_t pad_; };
 struct Plan {
     int w = 0, h = 0, stride = 0, B = 0, L = 0;
     int fs_nch = VIS_FS_NCH;     // chunks (8 score rows) per k_fast segment of this plan: 8 for batches, fewer for a handful of frames (more, shorter waves)
@@ -139,6 +144,13 @@ struct Plan {
     int32_t* d_gq[VIS_BATCH_SETS] = {}; int32_t* d_kf_link[VIS_BATCH_SETS] = {};
     int32_t* d_kf_state = nullptr;
     hipEvent_t kf_reader[VIS_BATCH_SETS] = {};   // the last vis_batch_align that read d_kf_link[s] on the pose stream (nullptr: none pending)
+    // vis_batch_track (track.hip), allocated on first use: the snapshot of the last saved frame of the last tracked launch (the
+    // carried keyframe's images for the next launch's pair to it) and the trajectory state the chain kernel carries from launch to
+    // launch.  run_seq counts the vis_batch_run calls since plan / reset, track_seq the one the last vis_batch_track consumed.
+    int last_stages = 0, run_seq = 0, track_seq = 0;
+    TrackSnapshot snap{};
+    TrackState* d_track_state = nullptr;
+    vis_se3f track_init = {0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};   // vis_batch_track_init's pose: where vis_batch_reset restarts the chain
 };
 
 #define VIS_POSE_TABLE_M 64                  // the frame-at-a-time pose entry points take their RANSAC samples from the table for M <= 64 (root^2 = 49 in the reference)
@@ -333,7 +345,14 @@ int launch_keyframe_links(vis_ctx* ctx, Plan* pl, int set, int n);   // keyframe
 int reset_keyframe_state(vis_ctx* ctx, Plan* pl);                     // keyframe.hip: nothing saved, nothing carried
 int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int w, int h, int stride, int n,
                       const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy, const float* d_pts, const int32_t* d_npts,
-                      int max_pts, const int32_t* d_prev, const vis_se3f* d_init, vis_align_result* d_out);   // align.hip: vis_align_batch with pair i = (d_prev[i] -> i), nullptr = i-1
+                      int max_pts, const int32_t* d_prev, const TrackSnapshot* snap, const vis_se3f* d_init,
+                      vis_align_result* d_out);   // align.hip: vis_align_batch with pair i = (d_prev[i] -> i), nullptr = i-1; snap: vis_batch_track
+int ensure_track_buffers(vis_ctx* ctx, Plan* pl);                     // track.hip: the snapshot + chain state, allocated and initialised once per plan
+int reset_track_state(vis_ctx* ctx, Plan* pl, bool keep_last);        // track.hip: chain state = track_init (+ no last residual unless keep_last); synchronous
+int launch_track_snapshot(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
+                          const int32_t* links, int n);               // track.hip: the launch's last saved frame -> pl->snap (ctx->stream)
+int launch_track_chain(vis_ctx* ctx, Plan* pl, const int32_t* links, int n, const vis_align_result* d_align,
+                       vis_track_result* d_track);                    // track.hip: Track() over the launch (ctx->stream)
 int launch_half_pyramid(vis_ctx* ctx, const uint8_t* d_img, int w, int h, int stride, uint8_t* d_out[5]);
 // gradient.hip: Camera::Update / computeGradient / patch builders, batched
 size_t vis_grad_frame_elems(int w, int h);

@@ -76,6 +76,14 @@ class AlignResult(C.Structure):
                 ("iterations", C.c_int32 * 5), ("n_residuals", C.c_int32 * 5)]
 
 
+class TrackResult(C.Structure):
+    """vis_track_result: final_poseCam after a frame (VISystem::Track) and the pair whose residual was composed for it"""
+    _fields_ = [("pose", Se3f), ("composed", C.c_int32)]
+
+
+assert C.sizeof(TrackResult) == 32
+
+
 class PoseResult(C.Structure):
     _fields_ = [("E", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3), ("n_inliers", C.c_int32), ("n_pose_good", C.c_int32),
                 ("iters_run", C.c_int32), ("n_points", C.c_int32), ("n_models", C.c_int32), ("reserved_", C.c_int32)]
@@ -103,6 +111,7 @@ STAGE_DETECT, STAGE_MATCH, STAGE_POSE, STAGE_ALL = 1, 2, 4, 7
 STAGE_UPDATE, STAGE_FRAME = 8, 15          # Camera::Update's half pyramid at the head of the detect chain; FRAME = ALL | UPDATE
 STAGE_GRADIENT = 16                        # Camera::computeGradient into plan-owned buffers, beside the detect chain (implies UPDATE)
 KF_CARRIED, KF_NOT_SAVED, KF_FIRST = -1, -2, -3   # batch_get_keyframes(): no frame of this batch to match against
+TRACK_NONE = -4                                   # TrackResult.composed: Track did not run for the frame
 
 # every symbol include/vislam_hip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
@@ -119,6 +128,7 @@ ABI_SYMBOLS = [
     "vis_default_align_params", "vis_estimate_pose_features", "vis_align_batch", "vis_batch_align",
     "vis_synth_frame_parallax", "vis_synth_frames_device", "vis_batch_results_async", "vis_batch_half_pyramid", "vis_batch_gradients", "vis_batch_fast_thresholds",
     "vis_se3_exp", "vis_se3_mul", "vis_se3_from_rt", "vis_se3_matrix", "vis_batch_get_keyframes",
+    "vis_batch_track_init", "vis_batch_track",
 ]
 
 
@@ -167,6 +177,9 @@ def _load():
     lib.vis_batch_status.argtypes = [vp, ip]
     if hasattr(lib, "vis_batch_get_keyframes"):         # (absent from older A/B builds)
         lib.vis_batch_get_keyframes.argtypes = [vp, vp, ci, ip]
+    if hasattr(lib, "vis_batch_track"):                 # (absent from older A/B builds)
+        lib.vis_batch_track_init.argtypes = [vp, C.POINTER(Se3f)]
+        lib.vis_batch_track.argtypes = [vp, C.POINTER(AlignParams), vp, ci, vp, vp, vp]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -482,6 +495,17 @@ class Context:
         self._chk(lib.vis_batch_align(self._h, C.byref(ap), C.c_void_p(d_frames_ptr), n, nz(d_gray_ptr), nz(d_gx_ptr),
                                       nz(d_gy_ptr), nz(d_init_ptr), C.c_void_p(d_out_ptr)),
                   "vis_batch_align")
+
+    def batch_track_init(self, pose=None):
+        """final_poseCam the chain continues from (a Se3f, or None = identity); batch_reset() restarts there.  Synchronises."""
+        self._chk(lib.vis_batch_track_init(self._h, C.byref(pose) if pose is not None else None), "vis_batch_track_init")
+
+    def batch_track(self, ap, d_frames_ptr, n, d_init_ptr, d_align_ptr, d_track_ptr):
+        """alignment of every frame's keyframe pair of the last batch_run (n AlignResult at d_align_ptr, the pair to the carried
+        keyframe included) and VISystem::Track over the frames (n TrackResult at d_track_ptr); device pointers, asynchronous on the
+        pose stream like batch_align.  d_init_ptr: n Se3f or 0."""
+        self._chk(lib.vis_batch_track(self._h, C.byref(ap), C.c_void_p(d_frames_ptr), n, C.c_void_p(d_init_ptr) if d_init_ptr else None,
+                                      C.c_void_p(d_align_ptr), C.c_void_p(d_track_ptr)), "vis_batch_track")
 
     # -- CameraGPU::detectAndComputeGPUFeatures ---------------------------------------------------------
     def orb_detect_compute(self, img, slot=0, cap=None):
