@@ -439,6 +439,42 @@ int  vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redon
 /* device-side error/overflow flags of the last batch (0 = clean) */
 int  vis_batch_status(vis_ctx* ctx, int* flags);
 
+/* ---- rectification (vi::CameraModel, src/CameraModel.cpp:84-105; VISystem::CalculateROI, src/VISystem.cpp:162-205) -------------
+ * Opt-in: nothing else in this header remaps a frame (the reference's GPU main hands frames on un-remapped, src/VISystemGPU.cpp:137-146).
+ * Restatements of OpenCV 3.2 written from the published algorithm; parity with real OpenCV is UNPINNED.
+ * K = (fx, fy, cx, cy), dist = (k1, k2, p1, p2); sizes 1 ... 4095; fx, fy (and fx', fy') finite and > 0, else VIS_E_INVALID. */
+/* cv::getOptimalNewCameraMatrix(K, dist, Size(in_w, in_h), alpha = 1, Size(out_w, out_h)) -> Knew = (fx', fy', cx', cy').  Host only. */
+int  vis_optimal_new_camera_matrix(const float K[4], const float dist[4], int in_w, int in_h, int out_w, int out_h, float Knew[4]);
+/* cv::initUndistortRectifyMap(K, dist, R = I, Knew, Size(out_w, out_h), CV_16SC2, map1, map2).  Host only.
+ * map1: out_h x out_w x 2 int16 (source pixel x, y = floor(32 u) >> 5), map2: out_h x out_w uint16 ((v & 31) * 32 + (u & 31) in 1/32 px). */
+int  vis_undistort_rectify_map(const float K[4], const float dist[4], const float Knew[4], int out_w, int out_h,
+                               int16_t* map1, uint16_t* map2);
+/* Device tables of one calibration: built once on the host (vis_undistort_rectify_map) and uploaded.  A vis_rectify belongs to its
+ * context and is destroyed before it.  VIS_E_NODEVICE without a GPU (no context can exist then). */
+typedef struct vis_rectify vis_rectify;
+int  vis_rectify_create(vis_ctx* ctx, const float K[4], const float dist[4], const float Knew[4], int in_w, int in_h,
+                        int out_w, int out_h, vis_rectify** out);
+void vis_rectify_destroy(vis_rectify* r);
+/* the tables, copied to the host (either pointer may be NULL); equal to vis_undistort_rectify_map's.  Synchronises. */
+int  vis_rectify_maps(vis_rectify* r, int16_t* map1, uint16_t* map2);
+/* remap(INTER_LINEAR, BORDER_CONSTANT, 0) of n frames, bit-exact to OpenCV 3.2's fixed-point 8U path with these tables: per output
+ * pixel (sx, sy) = map1, a = map2 & 1023, fractions i = a >> 5 (y), j = a & 31 (x), D = (S00 32(32-i)(32-j) + S01 32(32-i)j +
+ * S10 32 i(32-j) + S11 32 i j + 16384) >> 15, a tap outside the in_w x in_h source reading 0.
+ *   d_in: n dense frames of in_h rows x in_stride bytes (in_stride >= in_w).  d_out: the window (x0, y0, w, h) of the rectified
+ *   out_w x out_h image (remap, then crop: VISystem::CalculateROI's frame without a copy), n frames of h rows x out_stride bytes
+ *   (out_stride >= w; the frame stride is out_stride * h -- a vis_batch_plan(ctx, w, h, out_stride, n) reads it as it is).
+ *   Asynchronous on the context's detect stream (the stream of vis_set_stream / its own): a vis_batch_run on d_out that follows is
+ *   ordered behind it, and a vis_feeder_release after that run also covers this read of the feeder's buffer.  d_out follows the
+ *   reuse rules of vis_batch_run's d_frames for whatever call reads it last: vis_batch_align / vis_batch_track read their frames
+ *   on the pose stream until vis_batch_sync.  This call orders itself behind the alignment that read d_out's range (the detect stream
+ *   waits for it, as vis_feeder_submit's copy does), so rewriting d_out is safe; a pipelined caller double-buffers d_out (alternates
+ *   two buffers) so that the wait is for the alignment of two steps back, not the last one. */
+int  vis_rectify_batch(vis_rectify* r, const uint8_t* d_in, int in_stride, int n, int x0, int y0, int w, int h,
+                       uint8_t* d_out, int out_stride);
+/* one host frame (in_h rows x in_stride bytes) -> the full out_w x out_h rectified frame (out_stride >= out_w): CameraModel::Undistort
+ * (src/CameraModel.cpp:103-105).  Through the context's staging block like the other single-frame entry points; blocks once. */
+int  vis_rectify_host(vis_rectify* r, const uint8_t* img, int in_stride, uint8_t* out, int out_stride);
+
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */
 int  vis_synth_canvas(uint8_t* canvas, int canvas_dim, uint64_t seed);

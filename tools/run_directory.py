@@ -13,6 +13,14 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --track out.csv: the camera trajectory as the reference's GPU main writes it (src/main_vi_slamGPU.cpp:137-144, its first seven
              columns): one row per frame, positionCam x, y, z, qOrientationCam x, y, z, w -- vis_batch_track after every batch (the
              GPU main's keyframe rule, keyframe_min_points = 1; alignment with the intrinsics of --K fx,fy,cx,cy), from the identity.
+  --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
+             calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
+             raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
+             (VISystem::CalculateROI's rectangle, e.g. 29,54,711,426 for EuRoC) -> vis_batch_run.  K' replaces the intrinsics of
+             vis_params and of --track, with its principal point moved into the processed window (cx' - x1, cy' - y1): the frames
+             are cropped at (x1, y1), so that is where the rectified camera's centre lies in them; --check runs the oracle on the
+             rectified frames the device produced.  (The frames go up through torch, not the feeder: the feeder's frames must
+             have the plan's size.)
 """
 import argparse
 import json
@@ -28,6 +36,26 @@ import torch  # noqa: E402,F401  (the process's HIP runtime: before the library)
 import vislam  # noqa: E402
 
 
+def read_calibration(path):
+    """the fields of a reference-format calibration XML (cv::FileStorage; calibration/calibrationEUROC.xml) that the rectification reads,
+    as vi::CameraModel::GetCameraModel reads them (src/CameraModel.cpp:25-68, relative intrinsics scaled by the input size)"""
+    import xml.etree.ElementTree as ET
+    root = ET.parse(path).getroot()
+
+    def nums(tag):
+        el = root.find(tag)
+        if el is None:
+            raise SystemExit(f"{path}: no <{tag}>")
+        data = el.find("data")
+        return [float(v) for v in (data if data is not None else el).text.split()]
+    c = {t: int(nums(t)[0]) for t in ("in_width", "in_height", "out_width", "out_height")}
+    K, dist = nums("calibration_values")[:4], (nums("rectification") + [0.0] * 4)[:4]
+    if K[2] < 1 and K[3] < 1:
+        K = [K[0] * c["in_width"], K[1] * c["in_height"], K[2] * c["in_width"], K[3] * c["in_height"]]
+    c["K"], c["dist"] = tuple(float(v) for v in K), tuple(dist)
+    return c
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("directory")
@@ -39,7 +67,11 @@ def main():
     ap.add_argument("--raw-size", default=None, help="WxH of headerless .raw files")
     ap.add_argument("--track", default=None, metavar="CSV", help="write the per-frame camera pose (positionCam, qOrientationCam) here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
+    ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
+    ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
     a = ap.parse_args()
+    if a.roi and not a.rectify:
+        raise SystemExit("--roi needs --rectify")
 
     names = vislam.image_list(a.directory)[:a.frames]
     if len(names) < 2:
@@ -50,24 +82,48 @@ def main():
     else:
         h, w = vislam.image_read(paths[0]).shape
     stamps = [vislam.image_time(n) for n in names]
+    in_w, in_h, window, Kn, Kw = w, h, None, None, None
+    if a.rectify:
+        cal = read_calibration(a.rectify)
+        if (cal["in_width"], cal["in_height"]) != (w, h):
+            raise SystemExit(f"{a.rectify}: in_width x in_height {cal['in_width']} x {cal['in_height']}, the images are {w} x {h}")
+        if cal["dist"][0] == 0:
+            raise SystemExit(f"{a.rectify}: no distortion coefficients (the reference does not rectify then: src/CameraModel.cpp:78-83)")
+        Kn = vislam.optimal_new_camera_matrix(cal["K"], cal["dist"], (w, h), (cal["out_width"], cal["out_height"]))
+        window = (0, 0, cal["out_width"], cal["out_height"])
+        if a.roi:
+            x1, y1, x2, y2 = (int(v) for v in a.roi.split(","))
+            window = (x1, y1, x2 - x1, y2 - y1)
+        w, h = window[2], window[3]
+        Kw = (float(Kn[0]), float(Kn[1]), float(Kn[2]) - window[0], float(Kn[3]) - window[1])   # K' in the window's pixel coordinates
+    stride = (w + 3) // 4 * 4 if a.rectify else w
     p = vislam.default_params()
     p.nfeatures, p.w_size, p.h_size = a.nfeatures, w, h
-    p.fy = p.fx
+    if Kw is not None:
+        p.fx, p.cx, p.cy = Kw[0], Kw[2], Kw[3]
+    p.fy = p.fx                                              # (the pose stage's one focal length, findEssentialMat(focal = fx))
     stages = vislam.STAGE_FRAME
     if a.track:
         import ctypes as C
         p.keyframe_min_points = 1                            # CameraGPU::addGPUKeyframe's rule
         stages |= vislam.STAGE_GRADIENT
         tap = vislam.default_align_params()
-        tap.fx, tap.fy, tap.cx, tap.cy = (float(x) for x in a.K.split(","))
+        tap.fx, tap.fy, tap.cx, tap.cy = (float(x) for x in (Kw if Kw is not None else a.K.split(",")))
         d_align = torch.empty(a.batch * C.sizeof(vislam.AlignResult), dtype=torch.uint8, device="cuda")
         d_track = torch.empty(a.batch * C.sizeof(vislam.TrackResult), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         poses = []
     ctx = vislam.Context(0, p)
     B = min(a.batch, len(paths))
-    ctx.batch_plan(w, h, w, B)
-    feed = vislam.Feeder(ctx, w, h, B)
+    ctx.batch_plan(w, h, stride, B)
+    if a.rectify:
+        feed = None
+        rect = ctx.rectify(cal["K"], cal["dist"], Kn, (in_w, in_h), (cal["out_width"], cal["out_height"]))
+        stage = np.empty((B, in_h, in_w), np.uint8)
+        d_rect = [torch.empty(B * h * stride, dtype=torch.uint8, device="cuda") for _ in range(2)]   # double-buffered (--track reads them)
+        torch.cuda.synchronize()
+    else:
+        feed = vislam.Feeder(ctx, w, h, B)
     n = len(paths)
     host = np.empty((n, h, w), np.uint8) if (a.check or a.cpu_seconds > 0) else None
     t_decode = 0.0
@@ -75,22 +131,31 @@ def main():
     t0 = time.perf_counter()
     for bi, first in enumerate(range(0, n, B)):
         k, nb = bi & 1, min(B, n - first)
-        buf = feed.host_buffer(k)                            # waits until the previous copy out of this buffer is done
+        buf = feed.host_buffer(k) if feed else stage         # (the feeder's waits until the previous copy out of this buffer is done)
         td = time.perf_counter()
         for i in range(nb):
-            buf[i] = vislam.image_read(paths[first + i], w, h)
-            if host is not None:
+            buf[i] = vislam.image_read(paths[first + i], in_w, in_h)
+            if host is not None and not a.rectify:
                 host[first + i] = buf[i]
         t_decode += time.perf_counter() - td
-        d = feed.submit(k, nb)
+        if feed:
+            d = feed.submit(k, nb)
+        else:
+            d_batch = torch.from_numpy(buf[:nb]).to("cuda")
+            torch.cuda.synchronize()                         # (torch's copy and the library's streams are not ordered)
+            d = d_rect[k].data_ptr()
+            rect.batch(d_batch.data_ptr(), in_w, nb, d, stride, window)
         ctx.batch_run(d, nb, stages)
         if a.track:
             ctx.batch_track(tap, d, nb, 0, d_align.data_ptr(), d_track.data_ptr())
-        feed.release(k)
+        if feed:
+            feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
+        if a.rectify and host is not None:                   # --check: the oracle reads the frames the device rectified
+            host[first:first + nb] = d_rect[k][:nb * h * stride].cpu().numpy().reshape(nb, h, stride)[:, :, :w]
         if a.track:
-            raw = d_track[:nb * C.sizeof(vislam.TrackResult)].cpu().numpy().tobytes()
-            poses += [vislam.TrackResult.from_buffer_copy(raw, i * C.sizeof(vislam.TrackResult)).pose for i in range(nb)]
+            track_bytes = d_track[:nb * C.sizeof(vislam.TrackResult)].cpu().numpy().tobytes()
+            poses += [vislam.TrackResult.from_buffer_copy(track_bytes, i * C.sizeof(vislam.TrackResult)).pose for i in range(nb)]
         if ctx.batch_status() != 0:
             raise SystemExit("device capacity flag set")
         for i in range(nb):
@@ -99,6 +164,7 @@ def main():
             results.append((kp, ds, g, nsym, ctx.batch_pose(i)))
     dt = time.perf_counter() - t0
     out = {"directory": a.directory, "frames": n, "width": w, "height": h, "nfeatures": a.nfeatures, "first_timestamp": stamps[0],
+           "rectified": None if not a.rectify else {"calibration": a.rectify, "window": list(window), "K_new": [float(v) for v in Kn], "K_window": list(Kw)},
            "median_frame_interval_ns": int(np.median(np.diff(stamps))) if n > 1 else None,
            "frames_per_s_incl_decode_and_downloads": n / dt, "host_decode_s": t_decode, "frames_per_s_host_decode_alone": n / t_decode if t_decode > 0 else None,
            "keypoints_mean": float(np.mean([len(r[0]) for r in results])), "good_matches_mean": float(np.mean([len(r[2]) for r in results[1:]])),
@@ -136,7 +202,10 @@ def main():
             for e in poses:
                 f.write(",".join("%.9g" % v for v in (e.tx, e.ty, e.tz, e.qx, e.qy, e.qz, e.qw)) + "\n")
         out["track_csv"] = a.track
-    feed.close()
+    if feed:
+        feed.close()
+    else:
+        rect.close()
     ctx.close()
     print(json.dumps(out, allow_nan=False))
     return 1 if out.get("frames_differing_from_the_oracle") else 0

@@ -532,6 +532,8 @@ static int batch_align_stream(vis_ctx* ctx, const vis_align_params* ap, const ui
     ctx->align_k ^= 1;
     ctx->ev_align_done = ctx->ev_align_done2[ctx->align_k];                           // (two events in turn: the one before stays valid for the set it guards)
     HIPCHK(ctx, hipEventRecord(ctx->ev_align_done, sP));
+    ctx->align_frames[ctx->align_k] = d_frames;                                      // (what vis_rectify_batch must not overwrite before it)
+    ctx->align_frames_end[ctx->align_k] = d_frames + (size_t)pl->stride * pl->h * n;
     ctx->align_pending = true;
     // the side stream refills a gradient set two steps on: it waits for the last alignment that read THAT set.  Decided by pointer
     // identity, not by how the caller got the pointers: the ones vis_batch_gradients() / vis_batch_half_pyramid() hand out are the

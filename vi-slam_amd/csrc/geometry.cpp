@@ -1,12 +1,13 @@
 // geometry.cpp -- host-side tables of the detector: pyramid level geometry, per-level feature
 // quotas, grid-filter band limits, and the
-// integer-only synthetic stream generator.  Plain C++ (no device code).
+// integer-only synthetic stream generator, the rectification tables.  Plain C++ (no device code).
 //
 // Follows what cv::ORB / cv::resize derive for the reference call site
 // /root/reference/src/Camera.cpp:87 (cv::ORB::detectAndCompute) -- see SURVEY.md Appendix A.1
 // items 2-3 -- and Matcher::bestMatchesFilter's window arithmetic (/root/reference/src/Matcher.cpp:171-216).
 #include "vis_internal.h"
 #include "synth_core.h"
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 
@@ -155,4 +156,103 @@ extern "C" int vis_synth_frame(const uint8_t* canvas, int dim, uint64_t seed, in
 extern "C" int vis_synth_frame_parallax(const uint8_t* canvas, int dim, uint64_t seed, int t,
                                         int w, int h, uint8_t* out, int out_stride) {
     return synth_frame_mode(canvas, dim, seed, t, w, h, out, out_stride, 1);
+}
+
+// ---- rectification (vi::CameraModel, src/CameraModel.cpp:84-90): the new camera matrix and the CV_16SC2 + CV_16UC1 tables ----------
+// Both restate OpenCV 3.2 from the published algorithm (the source is not part of this project): PARITY UNPINNED, like every other
+// OpenCV restatement here.  -ffp-contract=off (Makefile): no product is fused into a sum.
+static bool rect_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= 4095 && h <= 4095; }
+static bool rect_focal_ok(const float K[4]) { return std::isfinite(K[0]) && std::isfinite(K[1]) && K[0] > 0.f && K[1] > 0.f; }
+
+// cv::getOptimalNewCameraMatrix(alpha = 1, centerPrincipalPoint = false) as calib3d 3.2 computes it (calibration.cpp:
+// cvGetOptimalNewCameraMatrix -> icvGetRectangles -> cvUndistortPoints):
+//   1. a 9 x 9 grid of pixel positions (x * w / 8, y * h / 8), stored as float;
+//   2. each is undistorted into normalised coordinates by 5 fixed-point iterations of the inverse Brown model (double);
+//   3. outer = bounding box of the 81 results (float); with alpha = 1 the new projection maps it onto the output viewport:
+//      fx' = (out_w - 1) / outer.width, cx' = -fx' * outer.x (same for y).
+extern "C" int vis_optimal_new_camera_matrix(const float K[4], const float dist[4], int in_w, int in_h, int out_w, int out_h, float Knew[4]) {
+    if (!K || !dist || !Knew || !rect_size_ok(in_w, in_h) || !rect_size_ok(out_w, out_h) || !rect_focal_ok(K)) return VIS_E_INVALID;
+    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3];
+    float oX0 = FLT_MAX, oX1 = -FLT_MAX, oY0 = FLT_MAX, oY1 = -FLT_MAX;
+    const int N = 9;
+    for (int y = 0; y < N; y++)
+        for (int x = 0; x < N; x++) {
+            const float u = (float)x * in_w / (N - 1), v = (float)y * in_h / (N - 1);
+            double xn = ((double)u - cx) * (1.0 / fx), yn = ((double)v - cy) * (1.0 / fy);
+            const double x0 = xn, y0 = yn;
+            for (int j = 0; j < 5; j++) {
+                const double r2 = xn * xn + yn * yn;
+                const double icdist = 1.0 / (1 + (k2 * r2 + k1) * r2);
+                const double dX = 2 * p1 * xn * yn + p2 * (r2 + 2 * xn * xn);
+                const double dY = p1 * (r2 + 2 * yn * yn) + 2 * p2 * xn * yn;
+                xn = (x0 - dX) * icdist; yn = (y0 - dY) * icdist;
+            }
+            const float px = (float)xn, py = (float)yn;
+            oX0 = std::min(oX0, px); oX1 = std::max(oX1, px); oY0 = std::min(oY0, py); oY1 = std::max(oY1, py);
+        }
+    const float ow = oX1 - oX0, oh = oY1 - oY0;                                       // cv::Rect_<float>(oX0, oY0, oX1 - oX0, oY1 - oY0)
+    const double fx1 = (out_w - 1) / (double)ow, fy1 = (out_h - 1) / (double)oh;
+    const double cx1 = -fx1 * oX0, cy1 = -fy1 * oY0;
+    Knew[0] = (float)fx1; Knew[1] = (float)fy1; Knew[2] = (float)cx1; Knew[3] = (float)cy1;
+    return VIS_OK;
+}
+
+// cvRound(double) on x86-64 (cvtsd2si): round half to even; NaN and results outside int32 give INT_MIN -- what saturate_cast<int>
+// (double) is in OpenCV 3.2
+static inline int rect_cvround(double v) {
+    const double r = std::nearbyint(v);
+    if (!(r >= -2147483648.0 && r < 2147483648.0)) return INT32_MIN;
+    return (int)r;
+}
+
+// cv::initUndistortRectifyMap(K, dist, R = I, K', size, CV_16SC2, map1, map2) as imgproc 3.2 (undistort.cpp) computes it.  Everything in
+// double; dist = (k1, k2, p1, p2), k3 ... k6, s1 ... s4 and the tilt are 0 (the tilt matrix is the identity).
+//   iR = (K' R)^-1 by cv::invert(DECOMP_LU)'s closed form for a 3 x 3 double matrix (1 / det3, adjugate times it);
+//   row i: _x = i ir[1] + ir[2], _y = i ir[4] + ir[5], _w = i ir[7] + ir[8]; column j: the three ACCUMULATE ir[0], ir[3], ir[6];
+//   w = 1 / _w, x = _x w, y = _y w, r2 = x^2 + y^2, kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2),
+//   xd = x kr + p1 2xy + p2 (r2 + 2x^2) + s1 r2 + s2 r2^2, yd likewise, tilt (xd, yd, 1) -> (xd', yd', z'), u = fx / z' xd' + u0;
+//   iu = saturate_cast<int>(u * 32): map1 = (short)(iu >> 5), (short)(iv >> 5); map2 = (iv & 31) * 32 + (iu & 31).
+extern "C" int vis_undistort_rectify_map(const float K[4], const float dist[4], const float Knew[4], int out_w, int out_h,
+                                         int16_t* map1, uint16_t* map2) {
+    if (!K || !dist || !Knew || !map1 || !map2 || !rect_size_ok(out_w, out_h) || !rect_focal_ok(K) || !rect_focal_ok(Knew)) return VIS_E_INVALID;
+    const double A[9] = {(double)K[0], 0, (double)K[2], 0, (double)K[1], (double)K[3], 0, 0, 1};
+    const double Ar[9] = {(double)Knew[0], 0, (double)Knew[2], 0, (double)Knew[1], (double)Knew[3], 0, 0, 1};
+    const double I[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    double S[9];                                                                      // Ar.colRange(0, 3) * R
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) S[3 * r + c] = Ar[3 * r] * I[c] + Ar[3 * r + 1] * I[3 + c] + Ar[3 * r + 2] * I[6 + c];
+    auto m = [&](int r, int c) { return S[3 * r + c]; };
+    double d = m(0, 0) * (m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1)) - m(0, 1) * (m(1, 0) * m(2, 2) - m(1, 2) * m(2, 0)) +
+               m(0, 2) * (m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0));
+    if (d == 0.) return VIS_E_INVALID;                                                // (cv::invert leaves a zero matrix; K' > 0 cannot get here)
+    d = 1. / d;
+    const double ir[9] = {
+        (m(1, 1) * m(2, 2) - m(1, 2) * m(2, 1)) * d, (m(0, 2) * m(2, 1) - m(0, 1) * m(2, 2)) * d, (m(0, 1) * m(1, 2) - m(0, 2) * m(1, 1)) * d,
+        (m(1, 2) * m(2, 0) - m(1, 0) * m(2, 2)) * d, (m(0, 0) * m(2, 2) - m(0, 2) * m(2, 0)) * d, (m(0, 2) * m(1, 0) - m(0, 0) * m(1, 2)) * d,
+        (m(1, 0) * m(2, 1) - m(1, 1) * m(2, 0)) * d, (m(0, 1) * m(2, 0) - m(0, 0) * m(2, 1)) * d, (m(0, 0) * m(1, 1) - m(0, 1) * m(1, 0)) * d};
+    const double u0 = A[2], v0 = A[5], fx = A[0], fy = A[4];
+    const double k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3];
+    const double k3 = 0., k4 = 0., k5 = 0., k6 = 0., s1 = 0., s2 = 0., s3 = 0., s4 = 0.;
+    const double T[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};                                  // computeTiltProjectionMatrix(tauX = 0, tauY = 0)
+    for (int i = 0; i < out_h; i++) {
+        int16_t* m1 = map1 + (size_t)i * out_w * 2;
+        uint16_t* m2 = map2 + (size_t)i * out_w;
+        double _x = i * ir[1] + ir[2], _y = i * ir[4] + ir[5], _w = i * ir[7] + ir[8];
+        for (int j = 0; j < out_w; j++, _x += ir[0], _y += ir[3], _w += ir[6]) {
+            const double w = 1. / _w, x = _x * w, y = _y * w;
+            const double x2 = x * x, y2 = y * y;
+            const double r2 = x2 + y2, _2xy = 2 * x * y;
+            const double kr = (1 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1 + ((k6 * r2 + k5) * r2 + k4) * r2);
+            const double xd = (x * kr + p1 * _2xy + p2 * (r2 + 2 * x2) + s1 * r2 + s2 * r2 * r2);
+            const double yd = (y * kr + p1 * (r2 + 2 * y2) + p2 * _2xy + s3 * r2 + s4 * r2 * r2);
+            const double vt0 = T[0] * xd + T[1] * yd + T[2] * 1, vt1 = T[3] * xd + T[4] * yd + T[5] * 1, vt2 = T[6] * xd + T[7] * yd + T[8] * 1;
+            const double invProj = vt2 ? 1. / vt2 : 1;
+            const double u = fx * invProj * vt0 + u0, v = fy * invProj * vt1 + v0;
+            const int iu = rect_cvround(u * 32), iv = rect_cvround(v * 32);               // INTER_TAB_SIZE = 32, INTER_BITS = 5
+            m1[j * 2] = (int16_t)(iu >> 5);
+            m1[j * 2 + 1] = (int16_t)(iv >> 5);
+            m2[j] = (uint16_t)((iv & 31) * 32 + (iu & 31));
+        }
+    }
+    return VIS_OK;
 }

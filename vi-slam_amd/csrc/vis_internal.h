@@ -168,6 +168,9 @@ struct vis_ctx {
     // vis_batch_align runs on the pose stream (beside the next batch's detect chain): what may not overtake it waits for this event
     // (ev_align_done = the event of the LAST alignment, one of ev_align_done2[] used in turn, so that a gradient set can wait for its own reader)
     hipEvent_t ev_align_fork = nullptr, ev_align_done = nullptr, ev_align_done2[2] = {nullptr, nullptr}; int align_k = 0; bool align_pending = false;
+    // the frames the alignment behind ev_align_done2[k] reads ([begin, end) bytes): vis_rectify_batch, which rewrites caller frame buffers on
+    // the detect stream, waits for the alignment that read its output range (nullptr: none recorded)
+    const uint8_t* align_frames[2] = {nullptr, nullptr}; const uint8_t* align_frames_end[2] = {nullptr, nullptr};
     bool pose_attr_set = false;              // > 64 KiB LDS opt-in of the RANSAC solver kernels done on this context's device
     bool pose_grids_set = false; int pose_grid[4] = {0, 0, 0, 0};   // resident-workgroup grids of the work-list pose kernels on this device (pose.hip pose_grids)
     hipEvent_t ev_pose_done_set[2] = {nullptr, nullptr}, ev_results_done_set[2] = {nullptr, nullptr};   // per match-output set (Plan::mo_set)

@@ -35,26 +35,38 @@ struct DMatch { int queryIdx, trainIdx, imgIdx; float distance;
                 DMatch(int q, int t, float d) : queryIdx(q), trainIdx(t), imgIdx(-1), distance(d) {}
                 bool operator<(const DMatch& m) const { return distance < m.distance; } };
 static_assert(sizeof(KeyPoint) == 28 && sizeof(DMatch) == 16, "layout must match the C ABI");
-enum { CV_8U = 0, CV_16S = 3, CV_32F = 5, CV_8UC1 = 0, CV_16SC1 = 3, CV_32FC1 = 5 };               // OpenCV depth codes
-// minimal single-channel matrix with shared storage (enough for grayImage / descriptors / gradients / point lists / K)
+enum { CV_8U = 0, CV_16U = 2, CV_16S = 3, CV_32F = 5, CV_8UC1 = 0, CV_16UC1 = 2, CV_16SC1 = 3, CV_32FC1 = 5,     // OpenCV type codes:
+       CV_16SC2 = 3 + (1 << 3) };                                                                        // depth + ((channels - 1) << 3)
+// minimal matrix with shared storage (enough for grayImage / descriptors / gradients / point lists / K, and the CV_16SC2 rectification map):
+// `depth` holds the depth code, `cn` the channels
 struct Mat {
-    int rows = 0, cols = 0, depth = CV_8U; size_t step = 0; uint8_t* data = nullptr;
+    int rows = 0, cols = 0, depth = CV_8U, cn = 1; size_t step = 0; uint8_t* data = nullptr;
     std::shared_ptr<std::vector<uint8_t>> store;
     Mat() {}
     Mat(int r, int c, int type) { create(r, c, type); }
-    static size_t esz(int type) { return type == CV_16S ? 2 : (type == CV_32F ? 4 : 1); }
-    size_t elemSize() const { return esz(depth); }
-    void create(int r, int c, int type) { rows = r; cols = c; depth = type; step = (size_t)c * esz(type); store = std::make_shared<std::vector<uint8_t>>((size_t)r * step); data = store->data(); }
+    static size_t esz(int depth) { return (depth == CV_16S || depth == CV_16U) ? 2 : (depth == CV_32F ? 4 : 1); }
+    size_t elemSize() const { return esz(depth) * cn; }
+    int type() const { return depth + ((cn - 1) << 3); }
+    int channels() const { return cn; }
+    void create(int r, int c, int type) { rows = r; cols = c; depth = type & 7; cn = 1 + (type >> 3); step = (size_t)c * elemSize(); store = std::make_shared<std::vector<uint8_t>>((size_t)r * step); data = store->data(); }
     static Mat zeros(int r, int c, int type) { return Mat(r, c, type); }
     static Mat eye(int r, int c, int type) { Mat m(r, c, type); if (type == CV_32F) for (int i = 0; i < r && i < c; i++) m.at<float>(i, i) = 1.f; return m; }
     bool empty() const { return rows == 0 || cols == 0; }
     void release() { rows = cols = 0; step = 0; data = nullptr; store.reset(); }
-    Mat clone() const { Mat m; if (!empty()) { m.create(rows, cols, depth); for (int y = 0; y < rows; y++) std::memcpy(m.data + (size_t)y * m.step, data + (size_t)y * step, (size_t)cols * esz(depth)); } return m; }
+    Mat clone() const { Mat m; if (!empty()) { m.create(rows, cols, type()); for (int y = 0; y < rows; y++) std::memcpy(m.data + (size_t)y * m.step, data + (size_t)y * step, (size_t)cols * elemSize()); } return m; }
     void copyTo(Mat& m) const { m = clone(); }
     Mat rowRange(int a, int b) const { Mat m = *this; m.data = data + (size_t)a * step; m.rows = b - a; return m; }
     template <class T> T& at(int y, int x) { return *reinterpret_cast<T*>(data + (size_t)y * step + (size_t)x * sizeof(T)); }
     template <class T> const T& at(int y, int x) const { return *reinterpret_cast<const T*>(data + (size_t)y * step + (size_t)x * sizeof(T)); }
 };
+// cv::OutputArray stand-in: a function that fills an output Mat takes it by this reference (cv::_OutputArray::create / getMatRef)
+struct _OutputArray {
+    Mat* m;
+    _OutputArray(Mat& x) : m(&x) {}
+    void create(int r, int c, int type) const { if (m->rows != r || m->cols != c || m->type() != type || !m->data) m->create(r, c, type); }
+    Mat& getMatRef() const { return *m; }
+};
+typedef const _OutputArray& OutputArray;
 // cv::Matx33f: 3x3 float value matrix, row-major `val`
 struct Matx33f {
     float val[9];

@@ -402,9 +402,10 @@ static vector<double> xml_numbers(const string& doc, const string& tag) {
     while (is >> x) v.push_back(x);
     return v;
 }
-Mat optimal_new_camera_matrix_alpha1(const float K[4], const float dist[4], int in_w, int in_h, int out_w, int out_h);
 void CameraModel::GetCameraModel(string _calibration_path) {                          // src/CameraModel.cpp:16-101
     valid_ = true;
+    rectify_.reset();                                                                 // (Undistort's device tables belong to the last calibration)
+    map1_.release(); map2_.release();
     std::ifstream f(_calibration_path.c_str());
     if (!f.is_open()) {
         cout << " ... not found" << endl << "Cannot operate without calibration" << endl << "Exiting..." << endl;
@@ -439,44 +440,42 @@ void CameraModel::GetCameraModel(string _calibration_path) {                    
     } else {
         // :84-88: K_ = getOptimalNewCameraMatrix(K, dist, Size(in), alpha = 1.0, Size(out), nullptr, false).  The reference never
         // remaps the frames of the GPU main (VISystemGPU::AddFrameGPU hands the raw image on), but every intrinsic it uses
-        // afterwards -- InitializePyramid, EstimatePoseFeatures, findEssentialMat -- is this matrix, so it is restated here.
+        // afterwards -- InitializePyramid, EstimatePoseFeatures, findEssentialMat -- is this matrix.
+        // :89-90: initUndistortRectifyMap(K, dist, I, K_, Size(out), CV_16SC2, map1_, map2_).  Both are the library's host restatements,
+        // which refuse what they cannot tabulate -- an output size outside 1 ... 4095 or fx, fy <= 0 / not finite -- and so does this
+        // reader then (VisDevice::fail, the adapters' cout + exit), where it used to hand on a meaningless K_.
         cout << "Distortion coefficients found ... rectifying" << endl;
-        output_intrinsic_camera_ = optimal_new_camera_matrix_alpha1(input_calibration_, dist_coeffs_, in_width_, in_height_, out_width_, out_height_);
+        float Kn[4];
+        int rc = vis_optimal_new_camera_matrix(input_calibration_, dist_coeffs_, in_width_, in_height_, out_width_, out_height_, Kn);
+        if (rc) VisDevice::fail(rc, "CameraModel::GetCameraModel (getOptimalNewCameraMatrix)");
+        output_intrinsic_camera_ = Mat::zeros(3, 3, CV_32FC1);
+        output_intrinsic_camera_.at<float>(0, 0) = Kn[0]; output_intrinsic_camera_.at<float>(1, 1) = Kn[1];
+        output_intrinsic_camera_.at<float>(0, 2) = Kn[2]; output_intrinsic_camera_.at<float>(1, 2) = Kn[3]; output_intrinsic_camera_.at<float>(2, 2) = 1;
+        map1_.create(out_height_, out_width_, CV_16SC2);
+        map2_.create(out_height_, out_width_, CV_16UC1);
+        rc = vis_undistort_rectify_map(input_calibration_, dist_coeffs_, Kn, out_width_, out_height_, reinterpret_cast<int16_t*>(map1_.data),
+                                       reinterpret_cast<uint16_t*>(map2_.data));
+        if (rc) VisDevice::fail(rc, "CameraModel::GetCameraModel (initUndistortRectifyMap)");
     }
 }
 
-// cv::getOptimalNewCameraMatrix(alpha = 1, centerPrincipalPoint = false) as calib3d 3.2 computes it (calibration.cpp:
-// cvGetOptimalNewCameraMatrix -> icvGetRectangles -> cvUndistortPoints) -- written from the published algorithm, OpenCV is not
-// available here: PARITY UNPINNED like the rest of the OpenCV-owned arithmetic.
-//   1. a 9 x 9 grid of pixel positions (x * w / 8, y * h / 8), stored as float;
-//   2. each is undistorted into normalised coordinates by 5 fixed-point iterations of the inverse Brown model (double);
-//   3. outer = bounding box of the 81 results (float); with alpha = 1 the new projection maps it onto the output viewport:
-//      fx' = (out_w - 1) / outer.width, cx' = -fx' * outer.x (same for y).
-Mat optimal_new_camera_matrix_alpha1(const float K[4], const float dist[4], int in_w, int in_h, int out_w, int out_h) {
-    const double fx = K[0], fy = K[1], cx = K[2], cy = K[3], k1 = dist[0], k2 = dist[1], p1 = dist[2], p2 = dist[3];
-    float oX0 = FLT_MAX, oX1 = -FLT_MAX, oY0 = FLT_MAX, oY1 = -FLT_MAX;
-    const int N = 9;
-    for (int y = 0; y < N; y++)
-        for (int x = 0; x < N; x++) {
-            const float u = (float)x * in_w / (N - 1), v = (float)y * in_h / (N - 1);
-            double xn = ((double)u - cx) * (1.0 / fx), yn = ((double)v - cy) * (1.0 / fy);
-            const double x0 = xn, y0 = yn;
-            for (int j = 0; j < 5; j++) {
-                const double r2 = xn * xn + yn * yn;
-                const double icdist = 1.0 / (1 + (k2 * r2 + k1) * r2);
-                const double dX = 2 * p1 * xn * yn + p2 * (r2 + 2 * xn * xn);
-                const double dY = p1 * (r2 + 2 * yn * yn) + 2 * p2 * xn * yn;
-                xn = (x0 - dX) * icdist; yn = (y0 - dY) * icdist;
-            }
-            const float px = (float)xn, py = (float)yn;
-            oX0 = std::min(oX0, px); oX1 = std::max(oX1, px); oY0 = std::min(oY0, py); oY1 = std::max(oY1, py);
-        }
-    const float ow = oX1 - oX0, oh = oY1 - oY0;                                       // cv::Rect_<float>(oX0, oY0, oX1 - oX0, oY1 - oY0)
-    const double fx1 = (out_w - 1) / (double)ow, fy1 = (out_h - 1) / (double)oh;
-    const double cx1 = -fx1 * oX0, cy1 = -fy1 * oY0;
-    Mat M = Mat::zeros(3, 3, CV_32FC1);
-    M.at<float>(0, 0) = (float)fx1; M.at<float>(1, 1) = (float)fy1; M.at<float>(0, 2) = (float)cx1; M.at<float>(1, 2) = (float)cy1; M.at<float>(2, 2) = 1;
-    return M;
+void CameraModel::Undistort(const Mat& _image, OutputArray _output) const {      // src/CameraModel.cpp:103-105
+    if (!valid_) VisDevice::fail(VIS_E_STATE, "CameraModel::Undistort (no rectification maps: the calibration has no distortion coefficients)");
+    if (_image.type() != CV_8UC1 || _image.cols != in_width_ || _image.rows != in_height_)
+        VisDevice::fail(VIS_E_INVALID, "CameraModel::Undistort (an 8-bit in_width x in_height image)");
+    if (!rectify_) {
+        vis_rectify* r = nullptr;
+        const float Kn[4] = {output_intrinsic_camera_.at<float>(0, 0), output_intrinsic_camera_.at<float>(1, 1), output_intrinsic_camera_.at<float>(0, 2),
+                             output_intrinsic_camera_.at<float>(1, 2)};
+        const int rc = vis_rectify_create(VisDevice::get(), input_calibration_, dist_coeffs_, Kn, in_width_, in_height_, out_width_, out_height_, &r);
+        if (rc) VisDevice::fail(rc, "CameraModel::Undistort (vis_rectify_create)");
+        rectify_.reset(r, vis_rectify_destroy);
+    }
+    Mat src = _image;                                                                  // (the output may be the input: remap into a new buffer)
+    Mat dst(out_height_, out_width_, CV_8UC1);
+    const int rc = vis_rectify_host(rectify_.get(), src.data, (int)src.step, dst.data, (int)dst.step);
+    if (rc) VisDevice::fail(rc, "CameraModel::Undistort");
+    _output.getMatRef() = dst;
 }
 
 // initUndistortRectifyMap(K, dist, Mat(), K', Size(out)) maps output pixel (u, v) to the source position

@@ -5,16 +5,17 @@
 //   Matcher            /root/reference/include/Matcher.hpp:25-69
 //   MatcherGPU         /root/reference/include/MatcherGPU.hpp:14-28
 //   CameraGPU          /root/reference/include/CameraGPU.hpp:15-34
-//   vi::CameraModel    /root/reference/include/CameraModel.hpp:27-146 (calibration XML fields, no undistortion)
+//   vi::CameraModel    /root/reference/include/CameraModel.hpp:27-146 (calibration XML fields, rectification tables, Undistort)
 //   vi::VISystem       /root/reference/include/VISystem.hpp:33-155  (the members the GPU path and its main touch)
 //   vi::VISystemGPU    /root/reference/include/VISystemGPU.hpp:14-36
 //   Quaterniond + toQuaternion / toRPY / rotationMatrix2RPY / RPY2rotationMatrix   /root/reference/include/Plus.hpp:9-33
 // so that the calls src/main_vi_slamGPU.cpp makes (:41-48, :64-65, :123-144) compile against this header unchanged
 // (vi-slam_amd/host/main_calls_gpu.cpp holds them verbatim).  Out of scope and therefore absent: the IMU core (ROS topics,
-// src/Imu.cpp), undistortion / ROI (calib3d), the CPU-only estimators, GUI calls.
+// src/Imu.cpp), the CPU-only estimators, GUI calls.
 #ifndef VISLAM_HOST_HPP_
 #define VISLAM_HOST_HPP_
 #include <iostream>
+#include <memory>
 #include <string>
 #include <vector>
 #include "compat/opencv2/cudafeatures2d.hpp"
@@ -179,11 +180,15 @@ private:
 namespace vi {
 class CameraModel {                                      // include/CameraModel.hpp:27-146, src/CameraModel.cpp:16-142
 public:
-    void GetCameraModel(string _calibrationPath);        // reads the cv::FileStorage XML fields of src/CameraModel.cpp:25-42
+    void GetCameraModel(string _calibrationPath);        // reads the cv::FileStorage XML fields of src/CameraModel.cpp:25-42; with distortion
+                                                         // coefficients, a size or focal length the library refuses ends the process
     const Mat& GetK() const { return output_intrinsic_camera_; }
     const Mat& GetOriginalK() const { return original_intrinsic_camera_; }
-    const Mat& GetMap1() const { return map1_; }
-    const Mat& GetMap2() const { return map2_; }
+    const Mat& GetMap1() const { return map1_; }          // CV_16SC2 (initUndistortRectifyMap, src/CameraModel.cpp:84-90); empty unless IsValid()
+    const Mat& GetMap2() const { return map2_; }          // CV_16UC1
+    // src/CameraModel.cpp:103-105: remap(_image, _output, map1_, map2_, INTER_LINEAR) -- vis_rectify_host on the VisDevice context, with
+    // device tables made on first use (the reference asserts inside remap when there are no maps: here that is VisDevice::fail)
+    void Undistort(const Mat& _image, OutputArray _output) const;
     int GetOutputWidth() const { return out_width_; }
     int GetOutputHeight() const { return out_height_; }
     int GetInputWidth() const { return in_width_; }
@@ -202,6 +207,7 @@ private:
     float input_calibration_[4] = {0, 0, 0, 0}, dist_coeffs_[4] = {0, 0, 0, 0};
     int in_width_ = 0, in_height_ = 0, out_width_ = 0, out_height_ = 0;
     bool valid_ = false;
+    mutable std::shared_ptr<vis_rectify> rectify_;      // Undistort's device tables (vis_rectify_destroy when the last copy goes)
 };
 
 class VISystem {                                         // include/VISystem.hpp:33-155 (what the GPU path and its main use)

@@ -129,6 +129,8 @@ ABI_SYMBOLS = [
     "vis_synth_frame_parallax", "vis_synth_frames_device", "vis_batch_results_async", "vis_batch_half_pyramid", "vis_batch_gradients", "vis_batch_fast_thresholds",
     "vis_se3_exp", "vis_se3_mul", "vis_se3_from_rt", "vis_se3_matrix", "vis_batch_get_keyframes",
     "vis_batch_track_init", "vis_batch_track",
+    "vis_optimal_new_camera_matrix", "vis_undistort_rectify_map", "vis_rectify_create", "vis_rectify_destroy", "vis_rectify_maps",
+    "vis_rectify_batch", "vis_rectify_host",
 ]
 
 
@@ -180,6 +182,15 @@ def _load():
     if hasattr(lib, "vis_batch_track"):                 # (absent from older A/B builds)
         lib.vis_batch_track_init.argtypes = [vp, C.POINTER(Se3f)]
         lib.vis_batch_track.argtypes = [vp, C.POINTER(AlignParams), vp, ci, vp, vp, vp]
+    if hasattr(lib, "vis_rectify_create"):              # (absent from older A/B builds)
+        lib.vis_optimal_new_camera_matrix.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+        lib.vis_undistort_rectify_map.argtypes = [vp, vp, vp, ci, ci, vp, vp]
+        lib.vis_rectify_create.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(C.c_void_p)]
+        lib.vis_rectify_destroy.argtypes = [vp]
+        lib.vis_rectify_destroy.restype = None
+        lib.vis_rectify_maps.argtypes = [vp, vp, vp]
+        lib.vis_rectify_batch.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
+        lib.vis_rectify_host.argtypes = [vp, vp, ci, vp, ci]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -329,6 +340,74 @@ def image_read(path, w=None, h=None):
     return out
 
 
+# -- vi::CameraModel's rectification (src/CameraModel.cpp:84-105): OpenCV 3.2 restatements, parity with OpenCV unpinned --------------
+def _f4(a):
+    return np.ascontiguousarray(np.asarray(a, np.float32).reshape(4))
+
+
+def optimal_new_camera_matrix(K, dist, in_size, out_size):
+    """cv::getOptimalNewCameraMatrix(K, dist, in_size, alpha = 1, out_size): K, dist = 4 floats each ((fx, fy, cx, cy), (k1, k2, p1, p2)),
+    sizes (w, h) -> K' as 4 float32"""
+    K, dist, Kn = _f4(K), _f4(dist), np.zeros(4, np.float32)
+    rc = lib.vis_optimal_new_camera_matrix(_ptr(K), _ptr(dist), in_size[0], in_size[1], out_size[0], out_size[1], _ptr(Kn))
+    if rc:
+        raise VisError(rc, "vis_optimal_new_camera_matrix")
+    return Kn
+
+
+def undistort_rectify_map(K, dist, Knew, out_size):
+    """cv::initUndistortRectifyMap(K, dist, I, K', out_size, CV_16SC2) -> (map1 (h, w, 2) int16, map2 (h, w) uint16)"""
+    w, h = out_size
+    m1 = np.zeros((max(h, 1), max(w, 1), 2), np.int16); m2 = np.zeros((max(h, 1), max(w, 1)), np.uint16)
+    rc = lib.vis_undistort_rectify_map(_ptr(_f4(K)), _ptr(_f4(dist)), _ptr(_f4(Knew)), w, h, _ptr(m1), _ptr(m2))
+    if rc:
+        raise VisError(rc, "vis_undistort_rectify_map")
+    return m1, m2
+
+
+class Rectify:
+    """device tables of one calibration (vis_rectify_*); made by Context.rectify.  The context closes it when it closes itself (a
+    vis_rectify may not outlive its context); close() before that frees the tables earlier."""
+
+    def __init__(self, ctx, K, dist, Knew, in_size, out_size):
+        self.ctx, self.in_size, self.out_size = ctx, tuple(in_size), tuple(out_size)
+        self._r = C.c_void_p()
+        ctx._chk(lib.vis_rectify_create(ctx._h, _ptr(_f4(K)), _ptr(_f4(dist)), _ptr(_f4(Knew)), in_size[0], in_size[1], out_size[0],
+                                        out_size[1], C.byref(self._r)), "vis_rectify_create")
+        ctx._rectifiers.append(self)
+
+    def batch(self, d_in_ptr, in_stride, n, d_out_ptr, out_stride, window=None):
+        """n frames (in_h x in_stride each, device) -> the window (x0, y0, w, h) of the rectified frames (h x out_stride each, device);
+        window None = the whole out_w x out_h image.  Asynchronous on the context's detect stream."""
+        x0, y0, w, h = window if window is not None else (0, 0) + self.out_size
+        self.ctx._chk(lib.vis_rectify_batch(self._r, C.c_void_p(d_in_ptr), in_stride, n, x0, y0, w, h, C.c_void_p(d_out_ptr), out_stride),
+                      "vis_rectify_batch")
+
+    def host(self, img):
+        """one host frame -> the rectified out_h x out_w frame (CameraModel::Undistort)"""
+        img = np.asarray(img, np.uint8)
+        if img.strides[1] != 1:
+            img = np.ascontiguousarray(img)
+        assert img.shape == (self.in_size[1], self.in_size[0]), img.shape
+        out = np.empty((self.out_size[1], self.out_size[0]), np.uint8)
+        self.ctx._chk(lib.vis_rectify_host(self._r, _ptr(img), img.strides[0], _ptr(out), out.strides[0]), "vis_rectify_host")
+        return out
+
+    def maps(self):
+        """the device tables, downloaded: (map1 (h, w, 2) int16, map2 (h, w) uint16)"""
+        w, h = self.out_size
+        m1 = np.zeros((h, w, 2), np.int16); m2 = np.zeros((h, w), np.uint16)
+        self.ctx._chk(lib.vis_rectify_maps(self._r, _ptr(m1), _ptr(m2)), "vis_rectify_maps")
+        return m1, m2
+
+    def close(self):
+        if self._r:
+            lib.vis_rectify_destroy(self._r)             # (while the context lives: Context.close closes its rectifiers first)
+            self._r = C.c_void_p()
+        if self in self.ctx._rectifiers:
+            self.ctx._rectifiers.remove(self)
+
+
 class Feeder:
     """pinned-host double-buffered H2D feeder (vis_feeder_*)"""
 
@@ -379,6 +458,7 @@ class Context:
 
     def __init__(self, device=0, params=None):
         self._h = C.c_void_p()
+        self._rectifiers = []                                # open Rectify objects: closed before the context
         rc = lib.vis_create(int(device), C.byref(self._h))
         if rc:
             self._h = None
@@ -388,6 +468,8 @@ class Context:
             self.set_params(params)
 
     def close(self):
+        for r in list(getattr(self, "_rectifiers", ())):
+            r.close()
         if getattr(self, "_h", None):
             lib.vis_destroy(self._h)
             self._h = None
@@ -410,6 +492,11 @@ class Context:
         """frames t0 .. t0+n-1 of the synthetic stream straight into device memory (asynchronous)"""
         self._chk(lib.vis_synth_frames_device(self._h, C.c_void_p(d_canvas_ptr), dim, C.c_uint64(seed), t0, n, w, h, stride,
                                               1 if parallax else 0, C.c_void_p(d_out_ptr)), "vis_synth_frames_device")
+
+    def rectify(self, K, dist, Knew, in_size, out_size):
+        """vis_rectify_create: the rectification tables of (K, dist) onto K' for in_size -> out_size ((w, h)); close() before the
+        context"""
+        return Rectify(self, K, dist, Knew, in_size, out_size)
 
     def set_stream(self, raw_stream):
         self._chk(lib.vis_set_stream(self._h, C.c_void_p(raw_stream)), "vis_set_stream")
