@@ -487,11 +487,11 @@ static int batch_align_stream(vis_ctx* ctx, const vis_align_params* ap, const ui
     Plan* pl = ctx->batch;
     if (!pl || pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
     if (ctx->p.pose_input != VIS_POSE_GOOD) return VIS_E_STATE;                       // needs the grid-filtered matches in d_p1
-    bool plan_set = false;
     if (!d_gray && !d_gx && !d_gy) {                                                   // the plan's own gradients (VIS_STAGE_GRADIENT of the last vis_batch_run)
         if (!pl->grad_valid) { ctx->err = d_track ? "vis_batch_track: the last vis_batch_run had no VIS_STAGE_GRADIENT"
                                                   : "vis_batch_align: no gradient buffers given and the last vis_batch_run had no VIS_STAGE_GRADIENT"; return VIS_E_STATE; }
-        d_gray = pl->d_half; d_gx = pl->d_gx; d_gy = pl->d_gy; plan_set = true;
+        const Plan::GradSet& G = pl->grad[pl->grad_set];
+        d_gray = G.half; d_gx = G.gx; d_gy = G.gy;
     }
     if (d_track) {
         if (!d_frames || !d_out) return VIS_E_INVALID;
@@ -509,41 +509,40 @@ static int batch_align_stream(vis_ctx* ctx, const vis_align_params* ap, const ui
     // One persistent workgroup per pair, a chain of dependent iterations: latency-bound work that fits beside the next batch's
     // detect chain.  It runs on the pose stream, behind (a) everything queued on the context's stream so far -- the gradients of
     // these frames -- and (b) the matcher of the last batch; what may not overtake it (the next filter rewriting the matched
-    // points, the next vis_gradient_batch, the feeder's next copy into these frames) waits for ev_align_done.
+    // points, the next vis_gradient_batch, the feeder's next copy into these frames) waits for the reader events noted below.
     (void)hipSetDevice(ctx->device);
     hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
+    Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
     HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, sA));
     HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
-    if (pl->match_pending[pl->last_base / pl->rec_per_set]) HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_match_done[pl->last_base / pl->rec_per_set], 0));
+    HIPCHK(ctx, rs.matcher.wait(sP));                                                  // (the set's one reader is the matcher: that is the wait for it)
     // d_p1 = the matched keypoints of the query frame of every pair (getGoodMatches, src/Matcher.cpp:295-303): pair i = (frame i-1, frame i),
     // or with the keyframe gate (frame link[i], frame i); links to the carried record (VIS_KF_CARRIED < 0) are skipped like pair 0 --
     // except by vis_batch_track, which aligns them against the snapshot of that keyframe (its matched points are in d_p1 like any other)
     ctx->stream = sP;
-    const int32_t* links = pl->kf_min ? pl->d_kf_link[pl->last_base / pl->rec_per_set] : nullptr;
+    const int32_t* links = pl->kf_min ? rs.kf_link : nullptr;
     TrackSnapshot snap{};
     if (d_track) { snap = pl->snap; snap.valid = pl->kf_min ? pl->track_seq > 0 : pl->pair0_valid; }   // (gate on: only a link says whether it is used)
-    int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->d_p1, pl->d_ngood, pl->root * pl->root,
+    int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->out().p1, pl->out().ngood, pl->root * pl->root,
                                links, d_track ? &snap : nullptr, d_init, d_out);
     if (!rc && d_track) rc = launch_track_snapshot(ctx, pl, d_frames, d_gray, d_gx, d_gy, links, n);
     if (!rc && d_track) rc = launch_track_chain(ctx, pl, links, n, d_out, d_track);
     ctx->stream = sA;
     if (rc) return rc;
     if (d_track) pl->track_seq = pl->run_seq;
-    ctx->align_k ^= 1;
-    ctx->ev_align_done = ctx->ev_align_done2[ctx->align_k];                           // (two events in turn: the one before stays valid for the set it guards)
-    HIPCHK(ctx, hipEventRecord(ctx->ev_align_done, sP));
-    ctx->align_frames[ctx->align_k] = d_frames;                                      // (what vis_rectify_batch must not overwrite before it)
-    ctx->align_frames_end[ctx->align_k] = d_frames + (size_t)pl->stride * pl->h * n;
-    ctx->align_pending = true;
+    // two events in turn: the one before stays valid for the sets and the frames it guards
+    const int k = ctx->align_last ^ 1;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_align_done[k], sP));
+    const hipEvent_t ev = ctx->ev_align_done[k];
+    ctx->align_last = k;
+    ctx->align[k] = {ev, d_frames, d_frames + (size_t)pl->stride * pl->h * n};      // (what vis_rectify_batch must not overwrite before it)
     // the side stream refills a gradient set two steps on: it waits for the last alignment that read THAT set.  Decided by pointer
     // identity, not by how the caller got the pointers: the ones vis_batch_gradients() / vis_batch_half_pyramid() hand out are the
     // plan's sets too (valid until the next vis_batch_run), and a caller passing them explicitly needs the same ordering
-    (void)plan_set;
-    for (int s_ = 0; s_ < 2; s_++)
-        if ((pl->d_half_set[s_] && d_gray == pl->d_half_set[s_]) || (pl->d_gx_set[s_] && d_gx == pl->d_gx_set[s_]) || (pl->d_gy_set[s_] && d_gy == pl->d_gy_set[s_]))
-            pl->grad_reader[s_] = ctx->ev_align_done;
-    pl->mo_align[pl->last_cur] = ctx->ev_align_done;                                 // it read the matched points of the last step's matcher-output set
-    if (links) pl->kf_reader[pl->last_base / pl->rec_per_set] = ctx->ev_align_done;  // and the links the next gate kernel of that record set rewrites
+    for (Plan::GradSet& G : pl->grad)
+        if ((G.half && d_gray == G.half) || (G.gx && d_gx == G.gx) || (G.gy && d_gy == G.gy)) G.readers.note(sP, ev);
+    pl->out().readers.note(sP, ev);                                                  // it read the matched points of the last step's matcher-output set
+    if (links) rs.links.note(sP, ev);                                                // and the links the next gate kernel of that record set rewrites
     return VIS_OK;
 }
 

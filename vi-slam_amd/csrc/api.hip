@@ -71,6 +71,15 @@ static int validate_params(const vis_params& p) {
     return VIS_OK;
 }
 
+// the context's ordering events (vis_internal.h, vis_ctx) and their flags: vis_create and vis_destroy walk this one list
+template <class F> static void ordering_events(vis_ctx* ctx, F f) {
+    const unsigned dt = hipEventDisableTiming;
+    f(ctx->ev_filter_done, dt); f(ctx->ev_detect_done, dt); f(ctx->ev_update_fork, dt); f(ctx->ev_update_done, dt); f(ctx->ev_align_fork, dt);
+    f(ctx->ev_pose_done, hipEventDefault); f(ctx->ev_pose_start, hipEventDefault); f(ctx->ev_match_start, hipEventDefault);   // (also time the stages)
+    for (int i = 0; i < VIS_BATCH_SETS; i++) f(ctx->ev_match_done[i], dt);
+    for (int i = 0; i < 2; i++) { f(ctx->ev_pose_done_set[i], dt); f(ctx->ev_results_done_set[i], dt); f(ctx->ev_align_done[i], dt); }
+}
+
 extern "C" int vis_create(int device, vis_ctx** out) {
     if (!out) return VIS_E_INVALID;
     *out = nullptr;
@@ -93,27 +102,11 @@ extern "C" int vis_create(int device, vis_ctx** out) {
     if (hipStreamCreateWithPriority(&ctx->own_stream, hipStreamNonBlocking, prio_hi) != hipSuccess) { delete ctx; return VIS_E_HIP; }
     ctx->stream = ctx->own_stream;
     const int prio_pose = prio_hi, prio_match = prio_hi;
-    if (hipStreamCreateWithPriority(&ctx->pose_stream, hipStreamNonBlocking, prio_pose) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_filter_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_pose_done, hipEventDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_pose_start, hipEventDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_results_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_pose_done_set[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_pose_done_set[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_results_done_set[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_results_done_set[1], hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithPriority(&ctx->match_stream, hipStreamNonBlocking, prio_match) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_detect_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_match_start, hipEventDefault) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_match_done[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_match_done[1], hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithPriority(&ctx->update_stream, hipStreamNonBlocking, prio_lo) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_update_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_update_done, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_align_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_align_done2[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&ctx->ev_align_done2[1], hipEventDisableTiming) != hipSuccess) { delete ctx; return VIS_E_HIP; }
-    ctx->ev_align_done = ctx->ev_align_done2[0];
+    bool ok = hipStreamCreateWithPriority(&ctx->pose_stream, hipStreamNonBlocking, prio_pose) == hipSuccess &&
+              hipStreamCreateWithPriority(&ctx->match_stream, hipStreamNonBlocking, prio_match) == hipSuccess &&
+              hipStreamCreateWithPriority(&ctx->update_stream, hipStreamNonBlocking, prio_lo) == hipSuccess;
+    ordering_events(ctx, [&](hipEvent_t& e, unsigned flags) { ok = ok && hipEventCreateWithFlags(&e, flags) == hipSuccess; });
+    if (!ok) { delete ctx; return VIS_E_HIP; }
     ctx->ev_ok = true;
     for (int i = 0; i < 12; i++) if (hipEventCreate(&ctx->ev[i]) != hipSuccess) ctx->ev_ok = false;
     *out = ctx;
@@ -131,23 +124,22 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
-    if (ctx->pose_stream) { (void)hipStreamSynchronize(ctx->pose_stream); (void)hipStreamDestroy(ctx->pose_stream); }
-    if (ctx->ev_filter_done) (void)hipEventDestroy(ctx->ev_filter_done);
-    if (ctx->ev_pose_done) (void)hipEventDestroy(ctx->ev_pose_done);
-    if (ctx->ev_pose_start) (void)hipEventDestroy(ctx->ev_pose_start);
-    if (ctx->ev_results_done) (void)hipEventDestroy(ctx->ev_results_done);
-    for (int i = 0; i < 2; i++) { if (ctx->ev_pose_done_set[i]) (void)hipEventDestroy(ctx->ev_pose_done_set[i]); if (ctx->ev_results_done_set[i]) (void)hipEventDestroy(ctx->ev_results_done_set[i]); }
-    if (ctx->ev_align_fork) (void)hipEventDestroy(ctx->ev_align_fork);
-    for (int i = 0; i < 2; i++) if (ctx->ev_align_done2[i]) (void)hipEventDestroy(ctx->ev_align_done2[i]);
-    if (ctx->match_stream) { (void)hipStreamSynchronize(ctx->match_stream); (void)hipStreamDestroy(ctx->match_stream); }
-    if (ctx->ev_detect_done) (void)hipEventDestroy(ctx->ev_detect_done);
-    if (ctx->ev_match_start) (void)hipEventDestroy(ctx->ev_match_start);
-    for (int i = 0; i < VIS_BATCH_SETS; i++) if (ctx->ev_match_done[i]) (void)hipEventDestroy(ctx->ev_match_done[i]);
-    if (ctx->update_stream) { (void)hipStreamSynchronize(ctx->update_stream); (void)hipStreamDestroy(ctx->update_stream); }
-    if (ctx->ev_update_fork) (void)hipEventDestroy(ctx->ev_update_fork);
-    if (ctx->ev_update_done) (void)hipEventDestroy(ctx->ev_update_done);
+    for (hipStream_t st : {ctx->pose_stream, ctx->match_stream, ctx->update_stream})
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
+    ordering_events(ctx, [](hipEvent_t& e, unsigned) { if (e) (void)hipEventDestroy(e); });
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
+}
+
+// every stream of the context has been synchronised: no reader of any buffer set is pending any more
+static void clear_pending(vis_ctx* ctx) {
+    ctx->pose_pending = false;
+    ctx->align[0] = ctx->align[1] = vis_ctx::AlignRead{};
+    if (Plan* pl = ctx->batch) {
+        for (Plan::RecordSet& r : pl->rec) { r.matcher.clear(); r.links.clear(); }
+        for (Plan::GradSet& g : pl->grad) g.readers.clear();
+        for (Plan::MatchOut& o : pl->mo) o.readers.clear();
+    }
 }
 
 static void sync_all(vis_ctx* ctx) {
@@ -155,9 +147,7 @@ static void sync_all(vis_ctx* ctx) {
     if (ctx->update_stream) (void)hipStreamSynchronize(ctx->update_stream);      // (joined by the detect stream in vis_batch_run -- unless that call failed half way, or the caller swapped ctx->stream since)
     if (ctx->match_stream) (void)hipStreamSynchronize(ctx->match_stream);
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
-    ctx->pose_pending = false; ctx->results_pending = false; ctx->align_pending = false;
-    if (ctx->batch) { for (int i = 0; i < VIS_BATCH_SETS; i++) ctx->batch->match_pending[i] = false; ctx->batch->grad_reader[0] = ctx->batch->grad_reader[1] = nullptr; ctx->batch->kf_reader[0] = ctx->batch->kf_reader[1] = nullptr;
-                      for (int i = 0; i < 2; i++) ctx->batch->mo_pose[i] = ctx->batch->mo_results[i] = ctx->batch->mo_align[i] = nullptr; }
+    clear_pending(ctx);
 }
 
 extern "C" const char* vis_last_error(vis_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -249,7 +239,7 @@ template <class T> static int dalloc(vis_ctx* ctx, T** p, size_t count) {
     HIPCHK(ctx, hipMalloc((void**)p, count * sizeof(T)));
     return VIS_OK;
 }
-#define DALLOC(ptr, count) do { int rc_ = dalloc(ctx, &(ptr), (count)); if (rc_) { plan_destroy(pl); return rc_; } } while (0)
+#define DALLOC(ptr, count) do { int rc_ = dalloc(ctx, &(ptr), (count)); if (rc_) return rc_; } while (0)
 
 void plan_destroy(Plan* pl) {
     if (!pl) return;
@@ -259,24 +249,20 @@ void plan_destroy(Plan* pl) {
         F(pl->d_pyr[l]); F(pl->d_rs_tab[l]);
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
-    F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (int i = 0; i < 2; i++) { F(pl->d_half_set[i]); F(pl->d_gx_set[i]); F(pl->d_gy_set[i]); F(pl->d_g_set[i]); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
+    F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
     F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx);
-    for (int i = 0; i < VIS_BATCH_SETS; i++) { F(pl->d_pq[i]); F(pl->d_pt[i]); F(pl->d_pqn[i]); F(pl->d_gq[i]); F(pl->d_kf_link[i]); }
+    for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
     F(pl->d_knn12); F(pl->d_knn21);
-    if (pl->mo_set[0][0] || pl->mo_set[1][0]) { for (int s_ = 0; s_ < 2; s_++) for (int k = 0; k < 6; k++) F(pl->mo_set[s_][k]); }    // (d_sym ... d_p2 alias one of the sets)
-    else { F(pl->d_sym); F(pl->d_nsym); F(pl->d_good); F(pl->d_ngood); F(pl->d_p1); F(pl->d_p2); }                                  // a plan that failed before the sets were registered
+    for (Plan::MatchOut& o : pl->mo) { F(o.sym); F(o.nsym); F(o.good); F(o.ngood); F(o.p1); F(o.p2); }
     F(pl->d_hf); F(pl->d_wf);
     F(pl->d_n1); F(pl->d_n2); F(pl->d_mask); F(pl->d_samples); F(pl->d_models); F(pl->d_counts); F(pl->d_rstate); F(pl->d_pose); F(pl->d_worklist); F(pl->d_hyp);
     delete pl;
 }
 
-int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npairs, Plan** out, int nsets) {
-    *out = nullptr;
-    if (B < 1 || nrec < 1 || npairs < 1 || stride < w || (stride & 3)) return VIS_E_INVALID;
-    Plan* pl = new (std::nothrow) Plan();
-    if (!pl) return VIS_E_NOMEM;
+// plan_create's body: any failure returns, and plan_create frees whatever was allocated
+static int plan_fill(vis_ctx* ctx, Plan* pl, int w, int h, int stride, int B, int nrec, int npairs, int nsets) {
     pl->w = w; pl->h = h; pl->stride = stride; pl->B = B; pl->L = ctx->p.nlevels; pl->npairs = npairs;
     pl->nsets = nsets; pl->rec_per_set = nrec; nrec *= nsets; pl->nrec = nrec;
     // k_fast segment height: a wave marches 8 fs_nch - 2 emitting rows.  Long segments amortise the prologue and the halo rows of a wave --
@@ -284,17 +270,17 @@ int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npa
     // latency is a wave's lifetime, so the single-frame plan (and small batches) cut the same frame into more, shorter waves
     pl->fs_nch = B >= 32 ? VIS_FS_NCH : (B >= 8 ? 4 : 2);
     int rc = vis_compute_levels(ctx->p, w, h, stride, pl->lv, pl->fs_nch);
-    if (rc) { delete pl; return rc; }
+    if (rc) return rc;
     const int L = pl->L;
     int kcap = 0; for (int l = 0; l < L; l++) kcap += pl->lv[l].quota + pl->lv[l].quota / 8 + 32;      // default: every level's own slack
     kcap = std::max(kcap, ctx->p.keypoint_capacity);             // (the levels' keep_cap share whatever the caller asked for beyond it)
-    if (kcap > 65535) { delete pl; return VIS_E_INVALID; }       // packed 16-bit indices in the matcher
+    if (kcap > 65535) return VIS_E_INVALID;                      // packed 16-bit indices in the matcher
     pl->kcap = kcap;
     std::vector<float> hf, wf; vis_grid_limits(ctx->p, &pl->root, hf, wf);
     const int ncell = pl->root * pl->root;
     // correspondences per pair the pose stage sees: the grid-filtered good matches (reference pipeline) or every symmetric match
     const int mcap = ctx->p.pose_input == VIS_POSE_SYM ? kcap : ncell;
-    if (mcap > VIS_RANSAC_MAX_M) { delete pl; return VIS_E_INVALID; }
+    if (mcap > VIS_RANSAC_MAX_M) return VIS_E_INVALID;
     pl->pose_mcap = mcap;
     pl->max_iters = ctx->p.ransac_max_iters;
     DALLOC(pl->d_stage, (size_t)stride * h);
@@ -308,8 +294,9 @@ int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npa
     }
     pl->total_tiles = pl->lv[L - 1].tile_base + pl->lv[L - 1].tiles_x * pl->lv[L - 1].tiles_y;
     DALLOC(pl->d_tile_cnt, (size_t)B * pl->total_tiles); DALLOC(pl->d_seg_cnt, (size_t)B * L + VIS_MAX_LEVELS);   // + padding: k_describe reads VIS_MAX_LEVELS counts per frame
-    if (pl->total_tiles > 65535) { plan_destroy(pl); return VIS_E_INVALID; }        // k_fast: gridDim.y
-    { int rc2 = build_fast_tiles(ctx, pl); if (rc2) { plan_destroy(pl); return rc2; } }
+    if (pl->total_tiles > 65535) return VIS_E_INVALID;          // k_fast: gridDim.y
+    rc = build_fast_tiles(ctx, pl);
+    if (rc) return rc;
     if (nsets > 1) {                                               // batched stream plans predict the FAST threshold from batch to batch
         pl->speculate = true;
         DALLOC(pl->d_tau, L); DALLOC(pl->d_seg_cut, (size_t)B * L); DALLOC(pl->d_fix, (size_t)B * L + 1);
@@ -324,34 +311,42 @@ int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npa
     HIPCHK(ctx, hipMemset(pl->d_desc, 0, (size_t)nrec * kcap * 32));
     DALLOC(pl->d_descx, (size_t)nrec * kcap * 128);
     for (int sidx = 0; sidx < nsets; sidx++) {
-        DALLOC(pl->d_pq[sidx], npairs); DALLOC(pl->d_pt[sidx], npairs); DALLOC(pl->d_pqn[sidx], npairs);
+        Plan::RecordSet& r = pl->rec[sidx];
+        DALLOC(r.pq, npairs); DALLOC(r.pt, npairs); DALLOC(r.pqn, npairs);
         const int base = sidx * pl->rec_per_set;
         std::vector<int32_t> q(npairs), t(npairs), qn(npairs);
         for (int i = 0; i < npairs; i++) { q[i] = base + i; t[i] = base + i + 1; qn[i] = i == 0 ? -1 : base + i; }
-        HIPCHK(ctx, hipMemcpy(pl->d_pq[sidx], q.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(pl->d_pt[sidx], t.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
-        HIPCHK(ctx, hipMemcpy(pl->d_pqn[sidx], qn.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(r.pq, q.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(r.pt, t.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(r.pqn, qn.data(), (size_t)npairs * 4, hipMemcpyHostToDevice));
     }
-    pl->d_pair_q = pl->d_pq[0]; pl->d_pair_t = pl->d_pt[0]; pl->d_pair_q_noprev = pl->d_pqn[0];
+    pl->d_pair_q = pl->rec[0].pq; pl->d_pair_t = pl->rec[0].pt;
     if (nsets > 1 && ctx->p.keyframe_min_points > 0) {             // keyframe gate of a batched stream (keyframe.hip): tables written on the device
         pl->kf_min = ctx->p.keyframe_min_points;
         for (int sidx = 0; sidx < nsets; sidx++) {
-            DALLOC(pl->d_gq[sidx], npairs); DALLOC(pl->d_kf_link[sidx], npairs);
-            HIPCHK(ctx, hipMemset(pl->d_gq[sidx], 0xFF, (size_t)npairs * 4));       // -1: no pair until a run has written the set
-            HIPCHK(ctx, hipMemset(pl->d_kf_link[sidx], 0xFF, (size_t)npairs * 4));
+            Plan::RecordSet& r = pl->rec[sidx];
+            DALLOC(r.gq, npairs); DALLOC(r.kf_link, npairs);
+            HIPCHK(ctx, hipMemset(r.gq, 0xFF, (size_t)npairs * 4));       // -1: no pair until a run has written the set
+            HIPCHK(ctx, hipMemset(r.kf_link, 0xFF, (size_t)npairs * 4));
         }
         DALLOC(pl->d_kf_state, 2);
-        { int rc2 = reset_keyframe_state(ctx, pl); if (rc2) { plan_destroy(pl); return rc2; } }
+        rc = reset_keyframe_state(ctx, pl);
+        if (rc) return rc;
     }
     DALLOC(pl->d_knn12, (size_t)npairs * kcap * 2); DALLOC(pl->d_knn21, (size_t)npairs * kcap * 2);
-    DALLOC(pl->d_sym, (size_t)npairs * kcap); DALLOC(pl->d_nsym, npairs);
-    DALLOC(pl->d_good, (size_t)npairs * ncell); DALLOC(pl->d_ngood, npairs);
-    DALLOC(pl->d_p1, (size_t)npairs * mcap * 2); DALLOC(pl->d_p2, (size_t)npairs * mcap * 2);
+    for (int s_ = 0; s_ < (nsets > 1 ? 2 : 1); s_++) {              // the matcher-output sets (vis_internal.h): two for plans that pipeline steps
+        Plan::MatchOut& o = pl->mo[s_];
+        DALLOC(o.sym, (size_t)npairs * kcap); DALLOC(o.nsym, npairs);
+        DALLOC(o.good, (size_t)npairs * ncell); DALLOC(o.ngood, npairs);
+        DALLOC(o.p1, (size_t)npairs * mcap * 2); DALLOC(o.p2, (size_t)npairs * mcap * 2);
+        HIPCHK(ctx, hipMemset(o.nsym, 0, (size_t)npairs * 4));
+        HIPCHK(ctx, hipMemset(o.ngood, 0, (size_t)npairs * 4));
+        HIPCHK(ctx, hipMemset(o.p1, 0, (size_t)npairs * mcap * 2 * sizeof(float)));
+        HIPCHK(ctx, hipMemset(o.p2, 0, (size_t)npairs * mcap * 2 * sizeof(float)));
+    }
     DALLOC(pl->d_hf, pl->root); DALLOC(pl->d_wf, pl->root);
     HIPCHK(ctx, hipMemcpy(pl->d_hf, hf.data(), (size_t)pl->root * 4, hipMemcpyHostToDevice));
     HIPCHK(ctx, hipMemcpy(pl->d_wf, wf.data(), (size_t)pl->root * 4, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemset(pl->d_nsym, 0, (size_t)npairs * 4));
-    HIPCHK(ctx, hipMemset(pl->d_ngood, 0, (size_t)npairs * 4));
     DALLOC(pl->d_n1, (size_t)npairs * mcap * 2); DALLOC(pl->d_n2, (size_t)npairs * mcap * 2);
     DALLOC(pl->d_mask, (size_t)npairs * mcap);
     DALLOC(pl->d_samples, (size_t)npairs * pl->max_iters * 5);
@@ -369,31 +364,18 @@ int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npa
     HIPCHK(ctx, hipMemset(pl->d_worklist, 0, ((size_t)npairs + 2) * sizeof(int32_t)));
     HIPCHK(ctx, hipMemset(pl->d_knn12, 0xFF, (size_t)npairs * kcap * 2 * sizeof(uint32_t)));
     HIPCHK(ctx, hipMemset(pl->d_knn21, 0xFF, (size_t)npairs * kcap * 2 * sizeof(uint32_t)));
-    HIPCHK(ctx, hipMemset(pl->d_p1, 0, (size_t)npairs * mcap * 2 * sizeof(float)));
-    HIPCHK(ctx, hipMemset(pl->d_p2, 0, (size_t)npairs * mcap * 2 * sizeof(float)));
-    {   // the matcher-output sets (vis_internal.h): set 0 = the arrays above; a second one for plans that pipeline steps (nsets > 1)
-        void* s0[6] = {pl->d_sym, pl->d_nsym, pl->d_good, pl->d_ngood, pl->d_p1, pl->d_p2};
-        for (int k = 0; k < 6; k++) pl->mo_set[0][k] = s0[k];
-#ifndef VIS_MO_SETS
-#define VIS_MO_SETS 2
-#endif
-        if (pl->nsets > 1 && VIS_MO_SETS > 1) {
-            vis_dmatch* sym2 = nullptr; int32_t* nsym2 = nullptr; vis_dmatch* good2 = nullptr; int32_t* ngood2 = nullptr; float* p12 = nullptr; float* p22 = nullptr;
-            DALLOC(sym2, (size_t)npairs * kcap); pl->mo_set[1][0] = sym2;
-            DALLOC(nsym2, npairs); pl->mo_set[1][1] = nsym2;
-            DALLOC(good2, (size_t)npairs * ncell); pl->mo_set[1][2] = good2;
-            DALLOC(ngood2, npairs); pl->mo_set[1][3] = ngood2;
-            DALLOC(p12, (size_t)npairs * mcap * 2); pl->mo_set[1][4] = p12;
-            DALLOC(p22, (size_t)npairs * mcap * 2); pl->mo_set[1][5] = p22;
-            HIPCHK(ctx, hipMemset(nsym2, 0, (size_t)npairs * 4));
-            HIPCHK(ctx, hipMemset(ngood2, 0, (size_t)npairs * 4));
-            HIPCHK(ctx, hipMemset(p12, 0, (size_t)npairs * mcap * 2 * sizeof(float)));
-            HIPCHK(ctx, hipMemset(p22, 0, (size_t)npairs * mcap * 2 * sizeof(float)));
-        }
-    }
     HIPCHK(ctx, hipMemset(pl->d_pose, 0, (size_t)npairs * sizeof(PoseOut)));
     // cv::RNG sample tables only for small M (the reference pipeline: M <= root^2); larger M replays the stream on the device
-    { int rc2 = vis_build_sample_table(ctx, std::min(mcap, 8192)); if (rc2) { plan_destroy(pl); return rc2; } }
+    return vis_build_sample_table(ctx, std::min(mcap, 8192));
+}
+
+int plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npairs, Plan** out, int nsets) {
+    *out = nullptr;
+    if (B < 1 || nrec < 1 || npairs < 1 || stride < w || (stride & 3)) return VIS_E_INVALID;
+    Plan* pl = new (std::nothrow) Plan();
+    if (!pl) return VIS_E_NOMEM;
+    const int rc = plan_fill(ctx, pl, w, h, stride, B, nrec, npairs, nsets);
+    if (rc) { plan_destroy(pl); return rc; }
     *out = pl;
     return VIS_OK;
 }
@@ -435,8 +417,8 @@ int vis_build_sample_table(vis_ctx* ctx, int max_m) {
 
 int launch_pose(vis_ctx* ctx, Plan* pl, int npairs) {
     if (npairs <= 0) return VIS_OK;
-    return pose_run(ctx, npairs, pl->pose_mcap, pl->max_iters, pl->d_p1, pl->d_p2,
-                    ctx->p.pose_input == VIS_POSE_SYM ? pl->d_nsym : pl->d_ngood, pl->d_n1, pl->d_n2,
+    return pose_run(ctx, npairs, pl->pose_mcap, pl->max_iters, pl->out().p1, pl->out().p2,
+                    ctx->p.pose_input == VIS_POSE_SYM ? pl->out().nsym : pl->out().ngood, pl->d_n1, pl->d_n2,
                     pl->d_samples, pl->d_models, pl->d_counts, pl->d_rstate, nullptr, pl->d_mask, pl->d_pose, 1, 1, pl->d_worklist, pl->d_hyp);
 }
 
@@ -589,7 +571,7 @@ extern "C" int vis_gradient_batch(vis_ctx* ctx, const uint8_t* d_frames, int w, 
     if (((uintptr_t)d_gx | (uintptr_t)d_gy | (uintptr_t)d_g | (uintptr_t)d_gray) & 15) { ctx->err = "vis_gradient_batch: output buffers must be 16-byte aligned"; return VIS_E_INVALID; }
     (void)hipSetDevice(ctx->device);
     // a vis_batch_align still in flight on the pose stream reads the previous gradients (usually these very buffers)
-    if (ctx->align_pending) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_align_done, 0));
+    HIPCHK(ctx, wait_align_readers(ctx, ctx->stream));
     const size_t frame_bytes = (size_t)stride * h;
     int rc = launch_half_pyramid_batch(ctx, d_frames, w, h, stride, frame_bytes, n, d_gray);
     if (rc) return rc;
@@ -837,12 +819,12 @@ extern "C" int vis_bf_knn2_hamming_host(vis_ctx* ctx, const uint8_t* desc_q, int
 struct MatchFetch { const int32_t* ng; const int32_t* ns; const void* good; const void* sym; size_t ngood_cap, nsym_cap; };
 static MatchFetch fetch_matches(HostStage& hs, Plan* pl, int pair, bool want_good, int cap, bool want_sym, int sym_cap) {
     MatchFetch f = {};
-    f.ng = (const int32_t*)hs.down(pl->d_ngood + pair, 4);
-    f.ns = (const int32_t*)hs.down(pl->d_nsym + pair, 4);
+    f.ng = (const int32_t*)hs.down(pl->out().ngood + pair, 4);
+    f.ns = (const int32_t*)hs.down(pl->out().nsym + pair, 4);
     f.ngood_cap = (size_t)std::max(0, std::min(cap, pl->root * pl->root));
     f.nsym_cap = (size_t)std::max(0, std::min(sym_cap, pl->kcap));
-    if (want_good && f.ngood_cap) f.good = hs.down(pl->d_good + (size_t)pair * pl->root * pl->root, f.ngood_cap * sizeof(vis_dmatch));
-    if (want_sym && f.nsym_cap) f.sym = hs.down(pl->d_sym + (size_t)pair * pl->kcap, f.nsym_cap * sizeof(vis_dmatch));
+    if (want_good && f.ngood_cap) f.good = hs.down(pl->out().good + (size_t)pair * pl->root * pl->root, f.ngood_cap * sizeof(vis_dmatch));
+    if (want_sym && f.nsym_cap) f.sym = hs.down(pl->out().sym + (size_t)pair * pl->kcap, f.nsym_cap * sizeof(vis_dmatch));
     return f;
 }
 static int deliver_matches(const MatchFetch& f, vis_dmatch* good, int cap, int* n_good, vis_dmatch* sym_out, int sym_cap, int* n_sym) {
@@ -910,9 +892,10 @@ extern "C" int vis_good_matches_host(vis_ctx* ctx, const vis_keypoint* kps1, int
     tp.d_kps = cv.take<vis_keypoint>((size_t)kcap * 2);
     tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
     tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
-    tp.d_sym = cv.take<vis_dmatch>(kcap); tp.d_nsym = cv.take<int32_t>(1);
-    tp.d_good = cv.take<vis_dmatch>(ncell); tp.d_ngood = cv.take<int32_t>(1);
-    tp.d_p1 = cv.take<float>((size_t)ncell * 2); tp.d_p2 = cv.take<float>((size_t)ncell * 2);
+    Plan::MatchOut& o = tp.out();
+    o.sym = cv.take<vis_dmatch>(kcap); o.nsym = cv.take<int32_t>(1);
+    o.good = cv.take<vis_dmatch>(ncell); o.ngood = cv.take<int32_t>(1);
+    o.p1 = cv.take<float>((size_t)ncell * 2); o.p2 = cv.take<float>((size_t)ncell * 2);
     tp.d_hf = cv.take<float>(root); tp.d_wf = cv.take<float>(root);
     std::vector<uint32_t> k12(2 * (size_t)kcap, 0xFFFFFFFFu), k21(2 * (size_t)kcap, 0xFFFFFFFFu);
     for (int i = 0; i < 2 * n1; i++) k12[i] = dmatch_to_key(knn12[i]);
@@ -1057,17 +1040,17 @@ static int download_knn(vis_ctx* ctx, const uint32_t* d_keys, int n, vis_dmatch*
 static int download_matches(vis_ctx* ctx, Plan* pl, int pair, vis_dmatch* good, int cap, int* n_good,
                             vis_dmatch* sym_out, int sym_cap, int* n_sym) {
     int32_t ng = 0, ns = 0;
-    HIPCHK(ctx, hipMemcpy(&ng, pl->d_ngood + pair, 4, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(&ns, pl->d_nsym + pair, 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&ng, pl->out().ngood + pair, 4, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(&ns, pl->out().nsym + pair, 4, hipMemcpyDeviceToHost));
     if (n_good) *n_good = ng;
     if (n_sym) *n_sym = ns;
     if (good) {
         if (ng > cap) return VIS_E_CAPACITY;
-        if (ng) HIPCHK(ctx, hipMemcpy(good, pl->d_good + (size_t)pair * pl->root * pl->root, (size_t)ng * sizeof(vis_dmatch), hipMemcpyDeviceToHost));
+        if (ng) HIPCHK(ctx, hipMemcpy(good, pl->out().good + (size_t)pair * pl->root * pl->root, (size_t)ng * sizeof(vis_dmatch), hipMemcpyDeviceToHost));
     }
     if (sym_out) {
         if (ns > sym_cap) return VIS_E_CAPACITY;
-        if (ns) HIPCHK(ctx, hipMemcpy(sym_out, pl->d_sym + (size_t)pair * pl->kcap, (size_t)ns * sizeof(vis_dmatch), hipMemcpyDeviceToHost));
+        if (ns) HIPCHK(ctx, hipMemcpy(sym_out, pl->out().sym + (size_t)pair * pl->kcap, (size_t)ns * sizeof(vis_dmatch), hipMemcpyDeviceToHost));
     }
     return VIS_OK;
 }
@@ -1095,10 +1078,10 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     return VIS_OK;
 }
 
-// Three streams per context: A = detect chain (caller's / own stream), M = expand + knn + filters,
-// P = RANSAC + recoverPose.  Batch i+1's detect chain overlaps batch i's matcher (MFMA + LDS, little VALU)
-// and pose (latency-bound FP64): the records (keypoints, descriptors, expanded descriptors) are double
-// buffered, everything else is single buffered and ordered with events.
+// Four streams per context: A = detect chain (caller's / own stream), U = Camera::Update / gradients, M = expand + knn + filters,
+// P = RANSAC + recoverPose (and vis_batch_align / _track).  Batch i+1's detect chain overlaps batch i's matcher (MFMA + LDS, little
+// VALU) and pose (latency-bound FP64): the record, gradient and matcher-output sets are used in turn, and the writer of a set waits
+// for the readers of its last use (ReaderGuard, vis_internal.h).
 extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int stages) {
     if (!ctx || !d_frames) return VIS_E_INVALID;
     Plan* pl = ctx->batch;
@@ -1119,14 +1102,14 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     // Camera::Update (src/Camera.cpp:63-72): the half pyramid of every frame of the batch.  Nothing of the detect chain reads it
     // and it is pure streaming work, so it runs on a stream of its own beside the (vector-ALU bound) detect kernels; the detect
     // stream joins it at the end of its chain, so "the detect stream is done" still means "d_frames may be reused".
+    Plan::RecordSet& rs = pl->rec[cur];
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[0], sA);
     // keyframe gate on: the carried record is the last SAVED one, known only on the device -- k_keyframe_links copies it, behind the
-    // records of this batch (it reads their counts) and launch_detect's wait for the matcher that last read this set
+    // records of this batch (it reads their counts), launch_detect's wait for the matcher that last read this set and the alignments
+    // that still read its links
     if (detect) { VisRange r_("vis: ORB detect + describe"); rc = launch_detect(ctx, pl, d_frames, n, base + 1, (pl->carry_from > 0 && !pl->kf_min) ? pl->carry_from : -1,
-                                                                             (stages & (VIS_STAGE_UPDATE | VIS_STAGE_GRADIENT)) ? ctx->ev_update_fork : nullptr,
-                                                                             pl->match_pending[cur] ? ctx->ev_match_done[cur] : nullptr);
-                  if (!rc && pl->kf_min && pl->kf_reader[cur] && hipStreamWaitEvent(sA, pl->kf_reader[cur], 0) != hipSuccess) rc = VIS_E_HIP;   // (an alignment still reading the links)
-                  if (!rc && pl->kf_min) rc = launch_keyframe_links(ctx, pl, cur, n);
+                                                                             (stages & (VIS_STAGE_UPDATE | VIS_STAGE_GRADIENT)) ? ctx->ev_update_fork : nullptr, &rs.matcher);
+                  if (!rc && pl->kf_min) rc = rs.links.wait(sA) == hipSuccess ? launch_keyframe_links(ctx, pl, cur, n) : VIS_E_HIP;
                   if (rc) return rc; }
     else if (ctx->ev_ok) for (int i = 1; i <= 4; i++) (void)hipEventRecord(ctx->ev[i], sA);
     hipStream_t sU = ctx->update_stream;
@@ -1134,14 +1117,15 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     bool update_queued = false;
     if (stages & (VIS_STAGE_UPDATE | VIS_STAGE_GRADIENT)) {
         VisRange r_("vis: Camera::Update half pyramid");
-        // this step's half pyramid / gradient set: the one the step before last used.  The plan's view of it (grad_set, d_half ... d_g) is
-        // switched only once every launch of the stage has been queued; a failure leaves the last step's set and pointers in place
+        // this step's half pyramid / gradient set: the one the step before last used.  The plan's view of it (grad_set) is switched only
+        // once every launch of the stage has been queued; a failure leaves the last step's set in place
         const int gs = pl->grad_set ^ 1;
+        Plan::GradSet& G = pl->grad[gs];
         const size_t fe = vis_grad_frame_elems(pl->w, pl->h);
-        if (!pl->d_half_set[gs]) HIPCHK(ctx, hipMalloc((void**)&pl->d_half_set[gs], (size_t)pl->B * fe));
-        if ((stages & VIS_STAGE_GRADIENT) && !pl->d_gx_set[gs]) {
-            HIPCHK(ctx, hipMalloc((void**)&pl->d_gx_set[gs], (size_t)pl->B * fe * 2)); HIPCHK(ctx, hipMalloc((void**)&pl->d_gy_set[gs], (size_t)pl->B * fe * 2));
-            HIPCHK(ctx, hipMalloc((void**)&pl->d_g_set[gs], (size_t)pl->B * fe));
+        if (!G.half) HIPCHK(ctx, hipMalloc((void**)&G.half, (size_t)pl->B * fe));
+        if ((stages & VIS_STAGE_GRADIENT) && !G.gx) {
+            HIPCHK(ctx, hipMalloc((void**)&G.gx, (size_t)pl->B * fe * 2)); HIPCHK(ctx, hipMalloc((void**)&G.gy, (size_t)pl->B * fe * 2));
+            HIPCHK(ctx, hipMalloc((void**)&G.g, (size_t)pl->B * fe));
         }
         // the frames were produced on the detect stream (or before the call): the side stream is ordered behind it -- behind the
         // PYRAMID launches of this batch's detect chain (launch_detect recorded the event there): the resize chain streams at HBM
@@ -1149,13 +1133,13 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
         if (!detect) HIPCHK(ctx, hipEventRecord(ctx->ev_update_fork, sA));
         HIPCHK(ctx, hipStreamWaitEvent(sU, ctx->ev_update_fork, 0));
         // an alignment two steps back (vis_batch_align on the pose stream) may still read THIS set's half pyramid / gradients
-        if (pl->grad_reader[gs]) HIPCHK(ctx, hipStreamWaitEvent(sU, pl->grad_reader[gs], 0));
+        HIPCHK(ctx, G.readers.wait(sU));
         if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[10], sU);
         ctx->stream = sU;
-        rc = launch_half_pyramid_batch(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, pl->d_half_set[gs]);
+        rc = launch_half_pyramid_batch(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, G.half);
         if (!rc && (stages & VIS_STAGE_GRADIENT))
-            rc = launch_gradient(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, pl->d_half_set[gs], 3 /* the reference's Scharr scale, src/Camera.cpp:172 */,
-                                 pl->d_gx_set[gs], pl->d_gy_set[gs], pl->d_g_set[gs]);
+            rc = launch_gradient(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, G.half, 3 /* the reference's Scharr scale, src/Camera.cpp:172 */,
+                                 G.gx, G.gy, G.g);
         ctx->stream = sA;
         if (rc) {
             // whatever was queued on the side stream before the failure still reads d_frames / writes set gs: the detect stream joins
@@ -1163,8 +1147,8 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
             if (hipEventRecord(ctx->ev_update_done, sU) == hipSuccess) (void)hipStreamWaitEvent(sA, ctx->ev_update_done, 0);
             return rc;
         }
-        pl->grad_set = gs; pl->d_half = pl->d_half_set[gs];
-        if (stages & VIS_STAGE_GRADIENT) { pl->d_gx = pl->d_gx_set[gs]; pl->d_gy = pl->d_gy_set[gs]; pl->d_g = pl->d_g_set[gs]; pl->grad_valid = true; }
+        pl->grad_set = gs;
+        pl->grad_valid = (stages & VIS_STAGE_GRADIENT) != 0;
         if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[11], sU);
         HIPCHK(ctx, hipEventRecord(ctx->ev_update_done, sU));
         update_queued = true;
@@ -1178,15 +1162,12 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev_match_start, sM);
     // pair i: query = record base+i (frame i-1, or the carried frame for i = 0), train = record base+i+1 (frame i); keyframe gate on:
     // query = the record of the last saved frame before i (or -1: no pair), from the table k_keyframe_links wrote for this set
-    pl->d_pair_q = pl->kf_min ? pl->d_gq[cur] : (have_prev ? pl->d_pq[cur] : pl->d_pqn[cur]);
-    pl->d_pair_t = pl->d_pt[cur];
+    pl->d_pair_q = pl->kf_min ? rs.gq : (have_prev ? rs.pq : rs.pqn);
+    pl->d_pair_t = rs.pt;
     // the matcher-output set of this step: a step that runs the matcher takes the next one, a pose-only step reads the last one
-    const int mo = pl->mo_set[1][0] ? ((stages & VIS_STAGE_MATCH) ? (pl->last_cur ^ 1) : pl->last_cur) : 0;
-    auto use_mo = [&](int s_) {
-        pl->d_sym = (vis_dmatch*)pl->mo_set[s_][0]; pl->d_nsym = (int32_t*)pl->mo_set[s_][1]; pl->d_good = (vis_dmatch*)pl->mo_set[s_][2];
-        pl->d_ngood = (int32_t*)pl->mo_set[s_][3]; pl->d_p1 = (float*)pl->mo_set[s_][4]; pl->d_p2 = (float*)pl->mo_set[s_][5];
-    };
-    use_mo(mo);
+    const int last_mo = pl->mo_cur, mo = pl->mo[1].sym ? ((stages & VIS_STAGE_MATCH) ? (last_mo ^ 1) : last_mo) : 0;
+    pl->mo_cur = mo;
+    Plan::MatchOut& O = pl->out();
     ctx->stream = sM;
     if (stages & VIS_STAGE_MATCH) {
         VisRange r_("vis: knn + match filters");
@@ -1196,13 +1177,10 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
             if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[5], sM);
             // the filter writes matcher-output set `mo` (sets in turn, like the records): wait for what still reads THAT set -- the pose
             // stage, the alignment and the results download of the step before last; those of the last step read the other set
-            if (pl->mo_pose[mo]) { hipError_t e = hipStreamWaitEvent(sM, pl->mo_pose[mo], 0); if (e != hipSuccess) rc = VIS_E_HIP; }
-            if (!rc && pl->mo_align[mo]) { hipError_t e = hipStreamWaitEvent(sM, pl->mo_align[mo], 0); if (e != hipSuccess) rc = VIS_E_HIP; }
-            if (!rc && pl->mo_results[mo]) { hipError_t e = hipStreamWaitEvent(sM, pl->mo_results[mo], 0); if (e != hipSuccess) rc = VIS_E_HIP; }
-            if (!rc) rc = launch_filter(ctx, pl, n);
+            rc = O.readers.wait(sM) == hipSuccess ? launch_filter(ctx, pl, n) : VIS_E_HIP;
         }
         if (!rc && ctx->ev_ok) (void)hipEventRecord(ctx->ev[6], sM);
-        if (!rc) { (void)hipEventRecord(ctx->ev_match_done[cur], sM); pl->match_pending[cur] = true; }
+        if (!rc) { (void)hipEventRecord(ctx->ev_match_done[cur], sM); rs.matcher.note(sM, ctx->ev_match_done[cur]); }
     } else if (ctx->ev_ok) { (void)hipEventRecord(ctx->ev[5], sM); (void)hipEventRecord(ctx->ev[6], sM); }
     if (!rc && (stages & VIS_STAGE_POSE)) {
         (void)hipEventRecord(ctx->ev_filter_done, sM);
@@ -1213,14 +1191,14 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
         rc = launch_pose(ctx, pl, n);
         (void)hipEventRecord(ctx->ev_pose_done, sP);
         ctx->pose_pending = true;
-        if (hipEventRecord(ctx->ev_pose_done_set[mo], sP) == hipSuccess) pl->mo_pose[mo] = ctx->ev_pose_done_set[mo];
+        if (hipEventRecord(ctx->ev_pose_done_set[mo], sP) == hipSuccess) O.readers.note(sP, ctx->ev_pose_done_set[mo]);
     }
     ctx->stream = sA;
-    if (rc) { use_mo(pl->last_cur); pl->half_valid = pl->grad_valid = false; return rc; }   // nothing of the stream state (carried frame, record set, matcher-output set) has been committed
+    if (rc) { pl->mo_cur = last_mo; pl->half_valid = pl->grad_valid = false; return rc; }   // nothing of the stream state (carried frame, record set, matcher-output set) has been committed
     pl->have_prev = have_prev; pl->pair0_valid = have_prev;
     if (detect) { pl->run_count++; pl->carry_from = base + n; }
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[8], sA);
-    pl->last_n = n; pl->last_base = base; pl->last_cur = mo;
+    pl->last_n = n; pl->last_base = base;
     pl->last_stages = stages; pl->run_seq++;                      // (what vis_batch_track checks)
     return VIS_OK;
 }
@@ -1242,9 +1220,7 @@ extern "C" int vis_batch_sync(vis_ctx* ctx) {
     if (ctx->match_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->match_stream));
     const bool had_pose = ctx->pose_pending;
     if (ctx->pose_stream) HIPCHK(ctx, hipStreamSynchronize(ctx->pose_stream));
-    ctx->pose_pending = false; ctx->results_pending = false; ctx->align_pending = false;
-    if (ctx->batch) { for (int i = 0; i < VIS_BATCH_SETS; i++) ctx->batch->match_pending[i] = false; ctx->batch->grad_reader[0] = ctx->batch->grad_reader[1] = nullptr; ctx->batch->kf_reader[0] = ctx->batch->kf_reader[1] = nullptr;
-                      for (int i = 0; i < 2; i++) ctx->batch->mo_pose[i] = ctx->batch->mo_results[i] = ctx->batch->mo_align[i] = nullptr; }
+    clear_pending(ctx);
     if (ctx->ev_ok) {
         collect_detect_timings(ctx);
         float a = 0;
@@ -1266,8 +1242,8 @@ extern "C" int vis_batch_sync(vis_ctx* ctx) {
 extern "C" int vis_batch_half_pyramid(vis_ctx* ctx, const uint8_t** d_half, size_t* frame_elems) {
     if (!ctx || !ctx->batch || !d_half) return VIS_E_STATE;
     Plan* pl = ctx->batch;
-    if (!pl->half_valid || !pl->d_half) return VIS_E_STATE;
-    *d_half = pl->d_half;
+    if (!pl->half_valid) return VIS_E_STATE;
+    *d_half = pl->grad[pl->grad_set].half;
     if (frame_elems) *frame_elems = vis_grad_frame_elems(pl->w, pl->h);
     return VIS_OK;
 }
@@ -1275,11 +1251,12 @@ extern "C" int vis_batch_half_pyramid(vis_ctx* ctx, const uint8_t** d_half, size
 extern "C" int vis_batch_gradients(vis_ctx* ctx, const uint8_t** d_gray, const int16_t** d_gx, const int16_t** d_gy, const uint8_t** d_g, size_t* frame_elems) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     Plan* pl = ctx->batch;
-    if (!pl->grad_valid || !pl->d_gx) return VIS_E_STATE;
-    if (d_gray) *d_gray = pl->d_half;
-    if (d_gx) *d_gx = pl->d_gx;
-    if (d_gy) *d_gy = pl->d_gy;
-    if (d_g) *d_g = pl->d_g;
+    if (!pl->grad_valid) return VIS_E_STATE;
+    const Plan::GradSet& G = pl->grad[pl->grad_set];
+    if (d_gray) *d_gray = G.half;
+    if (d_gx) *d_gx = G.gx;
+    if (d_gy) *d_gy = G.gy;
+    if (d_g) *d_g = G.g;
     if (frame_elems) *frame_elems = vis_grad_frame_elems(pl->w, pl->h);
     return VIS_OK;
 }
@@ -1309,18 +1286,16 @@ extern "C" int vis_batch_results_async(vis_ctx* ctx, vis_pose_result* h_pose, vi
         srcs[nj] = d; bytes[nj] = b; nj++;
     };
     add(h_pose, pl->d_pose, (size_t)n * sizeof(vis_pose_result));
-    add(h_good, pl->d_good, (size_t)n * ncell * sizeof(vis_dmatch));
-    add(h_ngood, pl->d_ngood, (size_t)n * sizeof(int32_t));
+    add(h_good, pl->out().good, (size_t)n * ncell * sizeof(vis_dmatch));
+    add(h_ngood, pl->out().ngood, (size_t)n * sizeof(int32_t));
     if (nj && mapped) { const int rc = launch_copy_jobs(ctx, s, nj, dsts, srcs, bytes); if (rc) return rc; ctx->n_copies++; }
     else {
         if (h_pose) HIPCHK(ctx, hipMemcpyAsync(h_pose, pl->d_pose, (size_t)n * sizeof(vis_pose_result), hipMemcpyDeviceToHost, s));
-        if (h_good) HIPCHK(ctx, hipMemcpyAsync(h_good, pl->d_good, (size_t)n * ncell * sizeof(vis_dmatch), hipMemcpyDeviceToHost, s));
-        if (h_ngood) HIPCHK(ctx, hipMemcpyAsync(h_ngood, pl->d_ngood, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (h_good) HIPCHK(ctx, hipMemcpyAsync(h_good, pl->out().good, (size_t)n * ncell * sizeof(vis_dmatch), hipMemcpyDeviceToHost, s));
+        if (h_ngood) HIPCHK(ctx, hipMemcpyAsync(h_ngood, pl->out().ngood, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     }
-    HIPCHK(ctx, hipEventRecord(ctx->ev_results_done, s));
-    ctx->results_pending = true;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_results_done_set[pl->last_cur], s));
-    pl->mo_results[pl->last_cur] = ctx->ev_results_done_set[pl->last_cur];
+    HIPCHK(ctx, hipEventRecord(ctx->ev_results_done_set[pl->mo_cur], s));
+    pl->out().readers.note(s, ctx->ev_results_done_set[pl->mo_cur]);
     return VIS_OK;
 }
 
@@ -1365,7 +1340,7 @@ extern "C" int vis_batch_get_knn(vis_ctx* ctx, int frame, vis_dmatch* out12, int
     if (frame < 0 || frame >= pl->last_n) return VIS_E_INVALID;
     sync_all(ctx);
     int32_t nq = 0, nt = 0, q = pl->last_base + frame;
-    if (pl->kf_min) HIPCHK(ctx, hipMemcpy(&q, pl->d_gq[pl->last_base / pl->rec_per_set] + frame, 4, hipMemcpyDeviceToHost));   // keyframe gate: the query record of the pair, -1 = none
+    if (pl->kf_min) HIPCHK(ctx, hipMemcpy(&q, pl->rec[pl->last_base / pl->rec_per_set].gq + frame, 4, hipMemcpyDeviceToHost));   // keyframe gate: the query record of the pair, -1 = none
     if (q >= 0) HIPCHK(ctx, hipMemcpy(&nq, pl->d_nkp + q, 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(&nt, pl->d_nkp + pl->last_base + frame + 1, 4, hipMemcpyDeviceToHost));
     if (q < 0 || (!pl->kf_min && frame == 0 && !pl->pair0_valid)) { nq = 0; nt = 0; }      // no pair: the first frame of a stream, or a frame the gate did not save
@@ -1411,7 +1386,7 @@ extern "C" int vis_batch_get_keyframes(vis_ctx* ctx, int32_t* prev, int cap, int
     if (!prev) return VIS_OK;
     if (cap < n) return VIS_E_CAPACITY;
     sync_all(ctx);
-    if (pl->kf_min) { HIPCHK(ctx, hipMemcpy(prev, pl->d_kf_link[pl->last_base / pl->rec_per_set], (size_t)n * 4, hipMemcpyDeviceToHost)); return VIS_OK; }
+    if (pl->kf_min) { HIPCHK(ctx, hipMemcpy(prev, pl->rec[pl->last_base / pl->rec_per_set].kf_link, (size_t)n * 4, hipMemcpyDeviceToHost)); return VIS_OK; }
     for (int i = 0; i < n; i++) prev[i] = i - 1;
     prev[0] = pl->pair0_valid ? VIS_KF_CARRIED : VIS_KF_FIRST;
     return VIS_OK;

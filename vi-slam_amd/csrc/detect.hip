@@ -1436,7 +1436,7 @@ int launch_copy_jobs(vis_ctx* ctx, hipStream_t st, int njobs, void* const* dst, 
     return VIS_OK;
 }
 
-int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int rec0, int carry_rec, hipEvent_t after_resize, hipEvent_t records_free) {
+int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int rec0, int carry_rec, hipEvent_t after_resize, const ReaderGuard* records_free) {
     hipStream_t st = ctx->stream;
     const int L = pl->L;
     {
@@ -1521,7 +1521,7 @@ int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int re
     // of the chain that touches the record set the matcher of an earlier batch may still be reading: the detect stream waits for that
     // matcher HERE, not at the start of the chain (round 5 timeline: a quarter of a millisecond of idle detect stream per step) -- the
     // resize chain, k_fast and k_select of this batch run meanwhile.
-    if (records_free) HIPCHK(ctx, hipStreamWaitEvent(st, records_free, 0));
+    if (records_free) HIPCHK(ctx, records_free->wait(st));
     if (carry_rec >= 0) {              // the previous batch's last frame -> the record in front of this batch's first (rec0 - 1)
         SmallOps J = {}; uint32_t e = 0; int k = 0;
         auto job = [&](void* d, const void* s, size_t bytes) { J.dst[k] = (uint32_t*)d; J.src[k] = (const uint32_t*)s; e += (uint32_t)(bytes / 4); J.end[k] = e; k++; };

@@ -97,7 +97,7 @@ int launch_keyframe_links(vis_ctx* ctx, Plan* pl, int set, int n) {
     const int base = set * pl->rec_per_set;
     // 16 waves whatever n is: the carried record (up to kcap x 60 bytes) is copied by the whole workgroup; the gate needs a multiple of 64
     hipLaunchKernelGGL(k_keyframe_links, dim3(1), dim3(64 * KF_MAX_WAVES), 0, ctx->stream, pl->d_nkp, pl->d_kps,
-                       pl->d_desc, pl->kcap, base, n, pl->kf_min, pl->d_kf_state, pl->d_gq[set], pl->d_kf_link[set]);
+                       pl->d_desc, pl->kcap, base, n, pl->kf_min, pl->d_kf_state, pl->rec[set].gq, pl->rec[set].kf_link);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

@@ -441,10 +441,10 @@ int launch_filter(vis_ctx* ctx, Plan* pl, int npairs) {
     if (lds > 160 * 1024) { ctx->err = "the match filters sort up to 16384 keypoints per frame in LDS: keypoint capacity " + std::to_string(pl->kcap) + " is beyond that"; return VIS_E_CAPACITY; }
     auto kern = nt == 1024 ? k_filter<1024> : k_filter<256>;
     if (lds > 65536) HIPCHK(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const Plan::MatchOut& o = pl->out();
     hipLaunchKernelGGL(kern, dim3(npairs), dim3(nt), lds, ctx->stream, pl->d_kps, pl->d_nkp, pl->kcap,
                        pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, (double)ctx->p.ratio, ctx->p.sym_mode,
-                       pl->root, pl->d_hf, pl->d_wf, pl->d_sym, pl->d_nsym, pl->d_good, pl->d_ngood,
-                       pl->d_p1, pl->d_p2, keys_cap, pl->pose_mcap ? pl->pose_mcap : pl->root * pl->root,
+                       pl->root, pl->d_hf, pl->d_wf, o.sym, o.nsym, o.good, o.ngood, o.p1, o.p2, keys_cap, pl->pose_mcap ? pl->pose_mcap : pl->root * pl->root,
                        (pl->pose_mcap && ctx->p.pose_input == VIS_POSE_SYM) ? 1 : 0);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;

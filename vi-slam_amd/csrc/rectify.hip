@@ -160,15 +160,8 @@ extern "C" int vis_rectify_batch(vis_rectify* r, const uint8_t* d_in, int in_str
     }
     (void)hipSetDevice(ctx->device);
     // d_out is a caller frame buffer: a vis_batch_align / vis_batch_track still running on the pose stream may read it (the frames of an
-    // earlier step).  Wait for the alignment that read this range -- the latest one if it did, else the one before it, which also stands
-    // for every older one (the pose stream runs them in order).  vis_feeder_submit orders its copies the same way.
-    if (ctx->align_pending) {
-        const uint8_t* b = d_out; const uint8_t* e = d_out + (size_t)out_stride * h * n;
-        const int last = ctx->align_k, older = last ^ 1;
-        const bool hit_last = ctx->align_frames[last] && b < ctx->align_frames_end[last] && ctx->align_frames[last] < e;
-        const int k = hit_last ? last : (ctx->align_frames[older] ? older : -1);
-        if (k >= 0) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_align_done2[k], 0));
-    }
+    // earlier step).  Wait for the alignment that read this range (align_reader, vis_internal.h).
+    HIPCHK(ctx, wait_align_readers(ctx, ctx->stream, d_out, d_out + (size_t)out_stride * h * n));
     return launch_remap(r, ctx->stream, d_in, in_stride, n, x0, y0, w, h, d_out, out_stride);
 }
 

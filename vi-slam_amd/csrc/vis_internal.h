@@ -39,6 +39,21 @@ struct LevelInfo {
 // device-resident compact kNN entry: key = (dist << 16) | trainIdx, 0xFFFFFFFF = none
 typedef vis_pose_result PoseOut;       // E, R, t (double) + n_inliers, n_pose_good, iters_run, n_points, n_models
 
+// The pending readers of one buffer set of the batch path (sets used in turn: the writer of a set waits for the readers of its last use).
+// Per stream, one slot per stream of a context (A, U, M, P): the event behind the LAST reader queued there, which stands for every earlier
+// one (a stream runs in order).  note() and clear() are bookkeeping only (host/stage_selftest.cpp drives them on the CPU); wait() makes
+// the HIP calls.  A held event that is recorded again stands for a later point: a false dependency at worst (vis_ctx), never a missed one.
+struct ReaderGuard {
+    hipStream_t stream[4] = {};
+    hipEvent_t event[4] = {};
+    void note(hipStream_t s, hipEvent_t e) { int i = 0; while (i < 3 && stream[i] && stream[i] != s) i++; stream[i] = s; event[i] = e; }
+    hipError_t wait(hipStream_t writer) const {
+        for (int i = 0; i < 4 && stream[i]; i++) { const hipError_t e = hipStreamWaitEvent(writer, event[i], 0); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    }
+    void clear() { *this = ReaderGuard(); }
+};
+
 // vis_batch_track's keyframe snapshot: one frame in the layout of a gradient-set frame (vis_grad_frame_elems elements per array),
 // level 0 of gray dense (w x h); valid = the pair to the carried keyframe may read it (set per call, not stored)
 struct TrackSnapshot { uint8_t* gray = nullptr; int16_t* gx = nullptr; int16_t* gy = nullptr; bool valid = false; };
@@ -76,14 +91,11 @@ struct Plan {
     // (Camera::computeGradient) beside the detect chain.  Plan-owned, allocated on first use, TWO sets used in turn: vis_batch_align of
     // step i reads set i & 1 on the pose stream while the side stream of step i + 1 fills the other one (with one set the alignment, the
     // next step's gradients and -- through the detect stream's join -- the next matcher formed a serial chain as long as the step).
-    // d_half / d_gx / d_gy / d_g = the set the last vis_batch_run wrote (not owned); grad_reader[s] = the event of the last alignment
-    // that read set s (nullptr: none pending).
-    uint8_t* d_half_set[2] = {nullptr, nullptr}; int16_t* d_gx_set[2] = {nullptr, nullptr}; int16_t* d_gy_set[2] = {nullptr, nullptr}; uint8_t* d_g_set[2] = {nullptr, nullptr};
+    // grad[grad_set] = the set the last vis_batch_run wrote; readers = the alignments that read the set (matched by pointer identity).
+    struct GradSet { uint8_t* half = nullptr; int16_t* gx = nullptr; int16_t* gy = nullptr; uint8_t* g = nullptr; ReaderGuard readers; };
+    GradSet grad[2];
     int grad_set = 0;
-    hipEvent_t grad_reader[2] = {nullptr, nullptr};
-    uint8_t* d_half = nullptr;
     bool half_valid = false;
-    int16_t* d_gx = nullptr; int16_t* d_gy = nullptr; uint8_t* d_g = nullptr;
     bool grad_valid = false;
     // records
     vis_keypoint* d_kps = nullptr;           // nrec x kcap
@@ -95,28 +107,22 @@ struct Plan {
     int32_t* d_pair_t = nullptr;
     uint32_t* d_knn12 = nullptr;             // npairs x kcap x 2 keys
     uint32_t* d_knn21 = nullptr;
-    vis_dmatch* d_sym = nullptr;             // npairs x kcap
-    int32_t* d_nsym = nullptr;
-    vis_dmatch* d_good = nullptr;            // npairs x root^2
-    int32_t* d_ngood = nullptr;
-    float* d_p1 = nullptr;                   // npairs x root^2 x 2
-    float* d_p2 = nullptr;
-    // The six arrays above are what k_filter writes and the pose stage / vis_batch_align / the results download read.  A batch plan
-    // owns TWO sets of them, used in turn like the record sets: with one set the filter of step i + 1 had to wait for the pose stage and
-    // the download of step i, and the pose stage of step i + 1 for that filter -- a serial loop (pose chain + download + filter) that
-    // set the step's period as soon as it grew longer than the detect chain (results download: - 8 %).  d_sym ... d_p2 = the set of
-    // the last vis_batch_run (not owned); mo_set[s] = {sym, nsym, good, ngood, p1, p2} of set s (set 0 only for single-frame plans);
-    // mo_pose / mo_results / mo_align[s] = the event behind the last reader of set s on the pose stream (nullptr: none pending).
-    void* mo_set[2][6] = {{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};
-    hipEvent_t mo_pose[2] = {nullptr, nullptr}, mo_results[2] = {nullptr, nullptr}, mo_align[2] = {nullptr, nullptr};
-    int last_cur = 0;
+    // What k_filter writes (sym, good: npairs x kcap / root^2 matches, counts; p1, p2: npairs x pose_mcap x 2 points) and the pose stage
+    // / vis_batch_align / the results download read.  A batch plan owns TWO sets, used in turn like the record sets: with one set the filter
+    // of step i + 1 had to wait for the pose stage and the download of step i, and the pose stage of step i + 1 for that filter -- a serial
+    // loop (pose chain + download + filter) that set the step's period as soon as it grew longer than the detect chain (results download:
+    // - 8 %).  Single-frame plans have set 0 only.  out() = the set of the last vis_batch_run (or of the one queueing its launches).
+    struct MatchOut { vis_dmatch* sym = nullptr; int32_t* nsym = nullptr; vis_dmatch* good = nullptr; int32_t* ngood = nullptr;
+                      float* p1 = nullptr; float* p2 = nullptr; ReaderGuard readers; };
+    MatchOut mo[2];
+    int mo_cur = 0;
+    MatchOut& out() { return mo[mo_cur]; }
     float* d_hf = nullptr;                   // root band limits (float accumulation on host)
     float* d_wf = nullptr;
     // pose
     double* d_n1 = nullptr;                  // npairs x root^2 x 2 normalised points
     double* d_n2 = nullptr;
     uint8_t* d_mask = nullptr;               // npairs x root^2 inlier mask of the winning E
-    int32_t* d_pair_q_noprev = nullptr;      // same as d_pair_q with pair 0 disabled
     int32_t* d_samples = nullptr;            // npairs x max_iters x 5
     double* d_models = nullptr;              // npairs x max_iters x 10 x 9
     int32_t* d_counts = nullptr;             // npairs x max_iters x 10  (-1 = no model)
@@ -133,17 +139,18 @@ struct Plan {
     // low-priority matcher / pose streams progress only as fast as the detect chain leaves them room, and the detect stream ends up waiting
     // for them however far ahead it may run: 393.4 k frames/s with three sets against 395-400 k with two, same build.)
     int nsets = 1, rec_per_set = 0, run_count = 0, last_base = 0;
-    int32_t* d_pq[VIS_BATCH_SETS] = {}; int32_t* d_pt[VIS_BATCH_SETS] = {}; int32_t* d_pqn[VIS_BATCH_SETS] = {};
-    bool match_pending[VIS_BATCH_SETS] = {};
     bool pair0_valid = false;                // last run: frame 0 had a predecessor
-    // keyframe gate of a batch plan (vis_params.keyframe_min_points at vis_batch_plan; 0 = off, none of the buffers exist).  Per
-    // record set: the gated query table the matcher reads instead of d_pq / d_pqn (train table unchanged) and the link table
-    // (vis_batch_get_keyframes' prev[], the alignment's previous frames).  d_kf_state = {last saved record (absolute, -1 = none),
-    // a frame has been saved since reset}: written by k_keyframe_links, read by the next one (keyframe.hip) on the detect stream.
+    // Per record set: the pair tables (query / train record; pqn = pq with pair 0 disabled) and, with the keyframe gate
+    // (vis_params.keyframe_min_points at vis_batch_plan; 0 = off, gq and kf_link do not exist), the gated query table the matcher reads
+    // instead of pq / pqn and the link table (vis_batch_get_keyframes' prev[], the alignment's previous frames).  matcher: waited for
+    // where launch_detect first writes the set; links (the alignments that read kf_link): waited for before k_keyframe_links.
+    // d_kf_state = {last saved record (absolute, -1 = none), a frame has been saved since reset}: written by k_keyframe_links, read by
+    // the next one (keyframe.hip) on the detect stream.
+    struct RecordSet { int32_t* pq = nullptr; int32_t* pt = nullptr; int32_t* pqn = nullptr; int32_t* gq = nullptr; int32_t* kf_link = nullptr;
+                       ReaderGuard matcher, links; };
+    RecordSet rec[VIS_BATCH_SETS];
     int kf_min = 0;
-    int32_t* d_gq[VIS_BATCH_SETS] = {}; int32_t* d_kf_link[VIS_BATCH_SETS] = {};
     int32_t* d_kf_state = nullptr;
-    hipEvent_t kf_reader[VIS_BATCH_SETS] = {};   // the last vis_batch_align that read d_kf_link[s] on the pose stream (nullptr: none pending)
     // vis_batch_track (track.hip), allocated on first use: the snapshot of the last saved frame of the last tracked launch (the
     // carried keyframe's images for the next launch's pair to it) and the trajectory state the chain kernel carries from launch to
     // launch.  run_seq counts the vis_batch_run calls since plan / reset, track_seq the one the last vis_batch_track consumed.
@@ -159,22 +166,21 @@ struct vis_ctx {
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
     hipStream_t pose_stream = nullptr;       // RANSAC/pose of batch i overlaps detect/match of batch i+1
-    hipEvent_t ev_filter_done = nullptr, ev_pose_done = nullptr, ev_pose_start = nullptr;
     hipStream_t match_stream = nullptr;      // knn + filters of batch i overlap the detect chain of batch i+1
-    hipEvent_t ev_detect_done = nullptr, ev_match_start = nullptr, ev_match_done[VIS_BATCH_SETS] = {};
     hipStream_t update_stream = nullptr;     // VIS_STAGE_UPDATE (Camera::Update): streaming work beside the VALU-bound detect chain
-    hipEvent_t ev_update_fork = nullptr, ev_update_done = nullptr;
+    // Ordering events (api.hip ordering_events).  Forks / joins: ev_update_fork A -> U, ev_update_done U -> A, ev_detect_done A -> M,
+    // ev_filter_done M -> P, ev_align_fork A -> P; ev_pose_done / _start and ev_match_start also time.  Reader events (ReaderGuard):
+    // ev_match_done[record set], ev_pose_done_set / ev_results_done_set[matcher-output set], ev_align_done[] in turn.  Each is recorded
+    // again only by the next reader of its kind -- normally of the same set two steps on, after that set's writer queued its wait.
+    hipEvent_t ev_filter_done = nullptr, ev_pose_done = nullptr, ev_pose_start = nullptr, ev_detect_done = nullptr, ev_match_start = nullptr;
+    hipEvent_t ev_update_fork = nullptr, ev_update_done = nullptr, ev_align_fork = nullptr;
+    hipEvent_t ev_match_done[VIS_BATCH_SETS] = {}, ev_pose_done_set[2] = {}, ev_results_done_set[2] = {}, ev_align_done[2] = {};
     bool pose_pending = false;
-    // vis_batch_align runs on the pose stream (beside the next batch's detect chain): what may not overtake it waits for this event
-    // (ev_align_done = the event of the LAST alignment, one of ev_align_done2[] used in turn, so that a gradient set can wait for its own reader)
-    hipEvent_t ev_align_fork = nullptr, ev_align_done = nullptr, ev_align_done2[2] = {nullptr, nullptr}; int align_k = 0; bool align_pending = false;
-    // the frames the alignment behind ev_align_done2[k] reads ([begin, end) bytes): vis_rectify_batch, which rewrites caller frame buffers on
-    // the detect stream, waits for the alignment that read its output range (nullptr: none recorded)
-    const uint8_t* align_frames[2] = {nullptr, nullptr}; const uint8_t* align_frames_end[2] = {nullptr, nullptr};
+    // the last two vis_batch_align / vis_batch_track (align[align_last] the latest) and the caller frames each read: align_reader()
+    struct AlignRead { hipEvent_t event = nullptr; const uint8_t* begin = nullptr; const uint8_t* end = nullptr; };
+    AlignRead align[2]; int align_last = 0;
     bool pose_attr_set = false;              // > 64 KiB LDS opt-in of the RANSAC solver kernels done on this context's device
     bool pose_grids_set = false; int pose_grid[4] = {0, 0, 0, 0};   // resident-workgroup grids of the work-list pose kernels on this device (pose.hip pose_grids)
-    hipEvent_t ev_pose_done_set[2] = {nullptr, nullptr}, ev_results_done_set[2] = {nullptr, nullptr};   // per match-output set (Plan::mo_set)
-    hipEvent_t ev_results_done = nullptr; bool results_pending = false;   // D2H of the last batch's results (vis_batch_results_async)
     vis_params p;
     std::string err;
     Plan* single = nullptr;
@@ -194,6 +200,19 @@ struct vis_ctx {
     // cv::RNG sample tables for M in [6, sample_max_m], built on the host for (seed, max_iters)
     int32_t* d_sample_table = nullptr; int sample_max_m = 0; int sample_iters = 0; unsigned long long sample_seed = 0;
 };
+
+// The alignment still queued on the pose stream that a write of caller memory [b, e) waits for: the latest if it read the range or the
+// range is not known (b == nullptr: gradient buffers, feeder copies), else the one before it, which also stands for every older one (the
+// pose stream runs them in order).  nullptr: none pending.
+inline hipEvent_t align_reader(const vis_ctx* ctx, const void* b, const void* e) {
+    const vis_ctx::AlignRead& last = ctx->align[ctx->align_last];
+    if (!last.event || !b || (last.begin < (const uint8_t*)e && (const uint8_t*)b < last.end)) return last.event;
+    return ctx->align[ctx->align_last ^ 1].event;
+}
+inline hipError_t wait_align_readers(const vis_ctx* ctx, hipStream_t s, const void* b = nullptr, const void* e = nullptr) {
+    const hipEvent_t ev = align_reader(ctx, b, e);
+    return ev ? hipStreamWaitEvent(s, ev, 0) : hipSuccess;
+}
 
 // roctx ranges around the stage families of a batched step (readable rocprofv3 --marker-trace timelines); compiled in only by
 // `make ROCTX=1` (-DVIS_HAVE_ROCTX -lrocprofiler-sdk-roctx: a diagnostic build), otherwise no-ops
@@ -338,7 +357,7 @@ void plan_destroy(Plan* pl);
 
 // ---- kernel launchers (each enqueues on ctx->stream) ----
 int launch_copy_jobs(vis_ctx* ctx, hipStream_t st, int njobs, void* const* dst, const void* const* src, const size_t* bytes);   // detect.hip: <= 6 dword-granular copies in one launch
-int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int rec0, int carry_rec = -1, hipEvent_t after_resize = nullptr, hipEvent_t records_free = nullptr);   // carry_rec >= 0: copy that record to rec0 - 1 before k_describe; after_resize: recorded behind the pyramid launches; records_free: waited for before the chain's first write to the record set
+int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int rec0, int carry_rec = -1, hipEvent_t after_resize = nullptr, const ReaderGuard* records_free = nullptr);   // carry_rec >= 0: copy that record to rec0 - 1 before k_describe; after_resize: recorded behind the pyramid launches; records_free: waited for before the chain's first write to the record set
 int build_fast_tiles(vis_ctx* ctx, Plan* pl);
 int launch_expand(vis_ctx* ctx, Plan* pl, int rec_first, int rec_count);
 int launch_match(vis_ctx* ctx, Plan* pl, int npairs);

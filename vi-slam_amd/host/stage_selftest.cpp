@@ -1,6 +1,8 @@
-// stage_selftest -- the two refusals of the frame-at-a-time staging block, driven on the CPU (no device, no HIP call is reached):
+// stage_selftest -- host-side bookkeeping of the library, driven on the CPU (no device, no HIP call is reached):
 //   1. HostStage::take() beyond the pinned block -> nullptr, and the call's wait() answers VIS_E_NOMEM instead of copying past the block
 //   2. vis_ensure_pin() asked to grow (= free + re-allocate) the block while a HostStage is alive -> VIS_E_STATE, block untouched
+//   3. ReaderGuard (the batch path's buffer sets): which reader events a writer would wait for, and align_reader(): which alignment a
+//      write of caller memory waits for
 // (round 5's host SIGSEGV, gpurun_out/r5r_gdb.log: a stage that kept the address of a block a later vis_ensure_pin had freed; see
 // csrc/vis_internal.h at HostStage).  Compiled by `make -C vi-slam_amd/csrc selftest` with hipcc as host code against the library;
 // tests/test_abi.py runs it.  Prints one line per check and exits non-zero on the first failure.
@@ -40,6 +42,35 @@ int main() {
         CHECK(hs.up_n == 0 && e.n_copies == 0);
     }
     c.h_pin = nullptr; c.h_pin_bytes = 0;              // (the vector owns the memory)
+    {
+        // stand-in handles: only compared, never passed to the runtime
+        const hipStream_t sM = (hipStream_t)0x10, sP = (hipStream_t)0x20;
+        const hipEvent_t e1 = (hipEvent_t)0x100, e2 = (hipEvent_t)0x200, e3 = (hipEvent_t)0x300;
+        ReaderGuard g;
+        CHECK(!g.stream[0] && !g.event[0]);                                   // nothing to wait for
+        g.note(sP, e1); g.note(sP, e2);                                       // a later reader on the same stream stands for the earlier one
+        CHECK(g.stream[0] == sP && g.event[0] == e2 && !g.stream[1]);
+        g.note(sM, e3);                                                       // readers on two streams: both waited for
+        CHECK(g.stream[0] == sP && g.event[0] == e2 && g.stream[1] == sM && g.event[1] == e3 && !g.stream[2]);
+        g.note(sP, e1);                                                       // (each stream keeps its own slot)
+        CHECK(g.event[0] == e1 && g.event[1] == e3 && !g.stream[2]);
+        g.clear();
+        CHECK(!g.stream[0] && !g.event[0] && !g.stream[1] && !g.event[1]);
+        // caller memory and the alignments on the pose stream
+        vis_ctx a;
+        uint8_t frames[5][64];                                                // (frames 0-3; frames[4] = one past frame 3)
+        CHECK(align_reader(&a, nullptr, nullptr) == nullptr);                 // no alignment at all
+        CHECK(align_reader(&a, frames[0], frames[1]) == nullptr);
+        a.align[1] = {e1, frames[0], frames[2]}; a.align_last = 1;           // one alignment, of frames 0-1
+        CHECK(align_reader(&a, frames[1], frames[2]) == e1);                  // a range it read
+        CHECK(align_reader(&a, frames[2], frames[4]) == nullptr);             // a range it did not read, no older alignment
+        CHECK(align_reader(&a, nullptr, nullptr) == e1);                      // range not known: the latest
+        a.align[0] = {e2, frames[2], frames[4]}; a.align_last = 0;           // a later one, of frames 2-3
+        CHECK(align_reader(&a, frames[3], frames[4]) == e2);                  // a range the last alignment read
+        CHECK(align_reader(&a, frames[0], frames[1]) == e1);                  // one it did not read while an older one is pending
+        CHECK(align_reader(&a, frames[1], frames[3]) == e2);                  // overlapping both: the latest stands for the older
+        CHECK(align_reader(&a, nullptr, nullptr) == e2);
+    }
     std::printf(fails ? "stage_selftest FAILED (%d)\n" : "stage_selftest passed\n", fails);
     return fails ? 1 : 0;
 }
