@@ -65,9 +65,7 @@ __device__ __forceinline__ void resize_coef(int d, double scale, int slen, int& 
     c1 = __float2int_rn(fx * 2048.f);
 }
 
-#ifndef RS_ROWS
 #define RS_ROWS 5            // destination rows per thread (10: 110 VGPRs = 4 waves per SIMD and 0.49 ms for the pyramid of 1024 frames; 5: 63 VGPRs = 8 waves, 0.455 ms)
-#endif
 typedef uint32_t u32x3_a4 __attribute__((ext_vector_type(3), aligned(4)));
 typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 
@@ -195,11 +193,7 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src,
         const uint32_t sel[4] = {s4.x, s4.y, s4.z, s4.w}, coef[4] = {c4.x, c4.y, c4.z, c4.w};
         const uint32_t wb = m4.x, keep = m4.y, asel = m4.z;
         uint8_t* dbase = dst + (size_t)f * dframe + dx4;
-#ifdef VIS_TIMING_RESIZE_SRC_CACHED     // timing experiment (results wrong): every frame reads the source of frames 0 .. 7 -- the chain as if its sources were on chip
-        const uint8_t* fbase = src + (size_t)(sw < 752 ? (f & 7) : f) * sframe;
-#else
         const uint8_t* fbase = src + (size_t)f * sframe;
-#endif
         const uint4* yrow = yc + (dy0 - row_first);
         uint32_t YX[RS_ROWS], YY[RS_ROWS];
 #pragma unroll
@@ -208,16 +202,11 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src,
         uint32_t share = 0;
 #pragma unroll
         for (int r = 1; r < RS_ROWS; r++) share |= (__builtin_amdgcn_ballot_w64(YX[r] != YY[r - 1]) == 0 ? 1u : 0u) << r;
-        // At scale 1.2 the source row advances by two once every five rows (at row p of a group of five; ten rows: at p and p + 5).
+        // At scale 1.2 the source row advances by two once every five rows (at row p of a group of five).
         // Any pattern that is a SUBSET of the wave's is exact (an unshared row is simply loaded); the second list covers waves that
         // straddle two row groups whose phase differs by one, so that only waves at a clamped border or of another scale load every row.
 #define RS_CASE(M) if ((M & ~share) == 0u) { resize_rows<M>(fbase, wb, asel, YX, YY, yrow, sel, coef, dbase, dstride, dy0, dh, keep); return; }
-#if RS_ROWS == 10
-        RS_CASE(0x3DEu) RS_CASE(0x3BCu) RS_CASE(0x37Au) RS_CASE(0x2F6u) RS_CASE(0x1EEu)
-        RS_CASE(0x39Cu) RS_CASE(0x338u) RS_CASE(0x272u) RS_CASE(0x0E6u) RS_CASE(0x1CEu)
-#elif RS_ROWS == 5
         RS_CASE(0x1Eu) RS_CASE(0x1Cu) RS_CASE(0x1Au) RS_CASE(0x16u) RS_CASE(0x0Eu) RS_CASE(0x18u) RS_CASE(0x12u) RS_CASE(0x06u)
-#endif
 #undef RS_CASE
         resize_rows<0u>(fbase, wb, asel, YX, YY, yrow, sel, coef, dbase, dstride, dy0, dh, keep);
         return;
@@ -303,10 +292,7 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src,
 #define FS_SC_BYTES (FS_SCR * FS_ROWB)
 #define FS_Q_BYTES ((FS_QCAP + 64) * 2)          // + one scratch entry per lane (branch-free append)
 #define FS_CAR_BYTES (2 * 256)                   // two carry lists (ping-pong) of one byte per entry (4 lane + j): the scored passers of one score row
-#ifndef FS_PAD
-#define FS_PAD 0                                 // occupancy experiments: extra LDS bytes per wave
-#endif
-#define FS_WAVE_LDS (FS_PX_BYTES + FS_SC_BYTES + FS_Q_BYTES + FS_CAR_BYTES + FS_PAD)
+#define FS_WAVE_LDS (FS_PX_BYTES + FS_SC_BYTES + FS_Q_BYTES + FS_CAR_BYTES)
 #define TILE_CAND_CAP VIS_TILE_CAND_CAP
 static_assert(FS_LANES * 4 - 8 == VIS_FS_EMIT_W, "strip geometry (geometry.cpp)");
 static_assert(2 * 2 * 4 * FS_LANES <= FS_QCAP, "the passers of one row (both polarities) fit the queue");
@@ -639,33 +625,6 @@ __device__ __forceinline__ void fast_wave(const FastWave& V, const uint8_t* __re
                     const unsigned long long mine = half ? b1 : b0;
                     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
                     const uint32_t o = (half ? V.tile[1] : V.tile[0]) * TILE_CAND_CAP + (uint32_t)((half ? cnt1 : cnt0) + rank);
-#ifdef VIS_TIMING_HARRIS_IN_FAST         // timing experiment: the Harris response of every emitted candidate from the wave's own pixel ring (9 x 9 bytes around
-                    if (em) {                            // the centre, one lane per candidate); kept alive, stored nowhere
-                        const uint8_t* hb = pxb + (((q + 1) & (FS_RING - 1)) * FS_ROWB + xl - 4);
-                        int ha = 0, hbb = 0, hc = 0;
-                        uint32_t hw[9][3];
-#pragma unroll
-                        for (int i = 0; i < 9; i++) {
-                            const uint8_t* pr = hb + (i < 6 ? i : i) * FS_ROWB;       // (rows 0 .. 21 of the ring + mirror: no wrap inside a 9-row window starting below row 13)
-                            hw[i][0] = (uint32_t)pr[0] | ((uint32_t)pr[1] << 8) | ((uint32_t)pr[2] << 16) | ((uint32_t)pr[3] << 24);
-                            hw[i][1] = (uint32_t)pr[4] | ((uint32_t)pr[5] << 8) | ((uint32_t)pr[6] << 16) | ((uint32_t)pr[7] << 24);
-                            hw[i][2] = (uint32_t)pr[8];
-                        }
-#define HPXL(i, j) ((int)((hw[i][(j) >> 2] >> (8 * ((j) & 3))) & 0xFFu))
-#pragma unroll
-                        for (int i = 1; i <= 7; i++)
-#pragma unroll
-                            for (int j = 1; j <= 7; j++) {
-                                const int Ix = (HPXL(i, j + 1) - HPXL(i, j - 1)) * 2 + (HPXL(i - 1, j + 1) - HPXL(i - 1, j - 1)) + (HPXL(i + 1, j + 1) - HPXL(i + 1, j - 1));
-                                const int Iy = (HPXL(i + 1, j) - HPXL(i - 1, j)) * 2 + (HPXL(i + 1, j - 1) - HPXL(i - 1, j - 1)) + (HPXL(i + 1, j + 1) - HPXL(i - 1, j + 1));
-                                ha += Ix * Ix; hbb += Iy * Iy; hc += Ix * Iy;
-                            }
-#undef HPXL
-                        const float fa = (float)ha, fb = (float)hbb, fc = (float)hc, fs = fa + fb;
-                        float hr = fa * fb - fc * fc - 0.04f * fs * fs;
-                        asm volatile("" :: "v"(hr));
-                    }
-#endif
                     if (em) *(__attribute__((address_space(1))) uint32_t*)(uintptr_t)(candf + o) = ((uint32_t)s << 24) | ((uint32_t)gy << 12) | (uint32_t)gx;   // global, not flat
                     cnt0 += __popcll(b0); cnt1 += __popcll(b1);
                 }
@@ -703,9 +662,7 @@ __device__ __forceinline__ void fast_wave(const FastWave& V, const uint8_t* __re
     }
 }
 
-#ifndef FS_WPB
 #define FS_WPB 1                 // waves per workgroup (the waves of a workgroup share nothing)
-#endif
 // ONE launch for all pyramid levels of all frames.  Grid (8, waves / FS_WPB, ceil(frames / 8)): blockIdx.x is the XCD the workgroup
 // lands on (workgroups are dealt to the 8 XCDs round-robin in x-fastest order), so all work of frame 8 z + x meets in one L2
 // -- the same placement as xcd_frame_map() without its integer divisions.
@@ -758,9 +715,6 @@ __device__ __forceinline__ float funmap(uint32_t m) {
 
 // HarrisResponses(blockSize 7, k 0.04) at integer (x,y) of one level
 __device__ __forceinline__ float harris7(const uint8_t* __restrict__ img, int stride, int x, int y) {
-#ifdef VIS_TIMING_NOHARRIS               // timing experiment (results wrong): k_select as if the Harris response came with the candidate for free
-    return (float)(x * 7 + y) * 1e-6f;
-#endif
     int a = 0, b = 0, c = 0;
     const uint8_t* p0 = img + (size_t)(y - 4) * stride + (x - 4);
     // 9 x 9 neighbourhood as 9 x 3 unaligned dwords (27 loads instead of 81 byte loads); every kept
@@ -855,11 +809,7 @@ __global__ __launch_bounds__(256) void k_tau_update(const int32_t* __restrict__ 
 // k_describe: one wave per keypoint
 #define PR 21                 // raw patch radius: 18 (max rotated sample offset) + 3 (blur taps)
 #define PW 43
-#ifdef VIS_DESC_VALU_HPASS     // A/B build: the round-3 horizontal pass on the vector ALU
-#define PS 44                 // raw patch LDS row stride
-#else
 #define PS 48                 // raw patch LDS row stride: 16-byte rows, the MFMA A operand of the row pass is one aligned ds_read_b128
-#endif
 #define HW 40                 // horizontally blurred columns stored (patch cols 3..42; samples use 3..39)
 #define HTS 46                // the row-blurred patch is stored TRANSPOSED: hbT[col][row], 46 u16 per column (odd dword
                               // stride): the 7 vertical taps of a sample are then 4 consecutive dwords
@@ -876,7 +826,6 @@ struct DescArgs {
     int kq[7];                // 7-tap Gaussian, Q8
     uint32_t k0, k1;          // the same taps packed as bytes for v_dot4_u32_u8: (k0..k3), (k4..k6, 0)
     uint32_t kp[4];           // and as u16 pairs for v_dot2_u32_u16: (k0,k1) (k2,k3) (k4,k5) (k6,0)
-    uint32_t kw[4][3];        // the 7 byte taps placed at byte offset j = 0..3 of a 12-byte window (three dot4 operands)
     const uint32_t* angle_tab; // [31 rows][9 dwords][2]: byte weights (u+16 inside the disc, else 0) and byte mask (1/0)
     float rad_per_deg;        // (float)(CV_PI/180.f)
     int patch_size;
@@ -967,12 +916,7 @@ __device__ __forceinline__ void wave_sum3(int& a, int& b, int& c) {
 // (v_readfirstlane), so per-lane addresses are 32-bit offsets from scalar bases; lane -> (row, column)
 // mappings are fixed per phase, so the unrolled loops only add constants.
 // (at most 96 SGPRs: from 97 on the hardware admits one workgroup fewer per CU than the 7 that LDS and VGPRs allow)
-#ifdef VIS_TIMING_COLPASS
-#define DESC_WAVES_PER_EU amdgpu_waves_per_eu(6, 8)          // (the column pass's planes and accumulators do not fit 72 registers without spilling)
-#else
-#define DESC_WAVES_PER_EU amdgpu_waves_per_eu(7, 8)
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), DESC_WAVES_PER_EU)) void k_describe(DetLevels D, DescArgs G, const int32_t* __restrict__ seg_cnt,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(7, 8))) void k_describe(DetLevels D, DescArgs G, const int32_t* __restrict__ seg_cnt,
                                                   vis_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
                                                   int32_t* __restrict__ nkp, int kcap, int rec0,
                                                   int32_t* __restrict__ flags, int nframes) {
@@ -1006,10 +950,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), DESC_WAVES
             run += l < D.L ? SC.c[l] : 0;
         }
     }
-#ifdef VIS_DESC_VALU_HPASS
-#define PATCH_BIAS 0u
-#define PATCH_DOT4(p, w) ((int)__builtin_amdgcn_udot4((p), (w), 0u, false))
-#else
     // The patch is kept in LDS as SIGNED bytes (pixel - 128: the i8 matrix instruction has no unsigned form).  The IC moments do not
     // notice: sum u (I - 128) = sum u I and sum v (I - 128) = sum v I over the symmetric disc, in exact integers.
 #define PATCH_BIAS 0x80808080u
@@ -1029,7 +969,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), DESC_WAVES
         hp_b = v4i_t0{(int)bq[0], (int)bq[1], (int)bq[2], (int)bq[3]};
     }
     const int hp_c0 = 128 * (G.kq[0] + G.kq[1] + G.kq[2] + G.kq[3] + G.kq[4] + G.kq[5] + G.kq[6]);
-#endif
     const int lrs = (lane * 47) >> 9, lc = lane - lrs * 11;          // patch map: lane = (row % 5 [+ spare rows], dword); lane / 11
     uint8_t* const lw = raw + lrs * PS + 4 * lc;
     const uint2* const ic_tb = reinterpret_cast<const uint2*>(G.angle_tab) + min(lane, 62);
@@ -1108,35 +1047,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), DESC_WAVES
     wave_sum3(sA, sB, sC);
     const int m10 = sA - 16 * sB, m01 = sC;
     const float angle = fast_atan2_deg((float)m01, (float)m10);
-#ifdef VIS_DESC_VALU_HPASS
-    // horizontal 7-tap pass over all rows, patch columns 3..42.  One task = (row pair, group of 4 outputs):
-    // 2 x 3 dword reads, byte windows by v_alignbyte, 2 x v_dot4_u32_u8 per output; the two rows of a column are
-    // one dword of the transposed buffer (hbT[col][row], 23 dwords per column).  lane = (pair % 6, group).
-    if (lane < 60) {
-        const int rs = (lane * 52) >> 9, g4 = lane - rs * 10;         // lane / 10
-        const uint8_t* rb = raw + 2 * rs * PS + 4 * g4;
-        uint32_t* wb = hb32 + 4 * g4 * (HTS / 2) + rs;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (k < 3 || rs < 4) {                                     // row pairs 0 .. 21
-                const uint32_t* r0 = reinterpret_cast<const uint32_t*>(rb + k * 12 * PS);
-                const uint32_t* r1 = reinterpret_cast<const uint32_t*>(rb + k * 12 * PS + PS);   // row 43 of the last pair is
-                const uint32_t a0 = r0[0], a1 = r0[1], a2 = r0[2];                               // never sampled with weight != 0
-                const uint32_t b0 = r1[0], b1 = r1[1], b2 = r1[2];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    // the 7 taps start at byte j of the 12-byte window: instead of shifting the pixels (two v_alignbyte per
-                    // row and output) the byte weights are shifted -- G.kw[j] = the kernel placed at byte offset j of three
-                    // dwords -- so an output is a chain of 2 (j < 2) or 3 v_dot4_u32_u8
-                    uint32_t oa = __builtin_amdgcn_udot4(a1, G.kw[j][1], __builtin_amdgcn_udot4(a0, G.kw[j][0], 0u, false), false);
-                    uint32_t ob = __builtin_amdgcn_udot4(b1, G.kw[j][1], __builtin_amdgcn_udot4(b0, G.kw[j][0], 0u, false), false);
-                    if (j >= 2) { oa = __builtin_amdgcn_udot4(a2, G.kw[j][2], oa, false); ob = __builtin_amdgcn_udot4(b2, G.kw[j][2], ob, false); }
-                    wb[j * (HTS / 2) + 6 * k] = oa | (ob << 16);       // <= 255*257 = 65535 per output
-                }
-            }
-        }
-    }
-#else
     // Horizontal 7-tap pass on the MATRIX pipe: H = (patch - 128) x T + 128 * sum(w) with the banded constant T[k][c] = w[k - c],
     // exact in the i32 accumulators of v_mfma_i32_16x16x64_i8.  Tile (t, n) = rows 16t .. 16t+15, blur columns 16n .. 16n+15: the A
     // operand of lane (g, i) is the 16 patch bytes of row 16t + i from column 16n + 16g (one aligned ds_read_b128; only the first
@@ -1174,58 +1084,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), DESC_WAVES
                 if (n < 2 || c2) { w[0] = lo; w[1] = hi; }
             }
         };
-#ifdef VIS_TIMING_COLPASS
-        // TIMING experiment (descriptors wrong on purpose; VERDICT r5 #7a): the WHOLE 2D blur on the matrix pipe.  Column tile by column
-        // tile: the three row tiles' accumulators (rows 16 t + 4 g .. + 3 of column 16 n + j) become the two i8 planes of the column
-        // pass's B operand without leaving the lane (2 v_perm + 2 v_perm + 2 v_xor per tile), then per output row tile T two matrix
-        // instructions (high / low plane against a banded constant -- the row pass's own constant stands in for it), the combine
-        // (acc_hi << 8) + acc_lo, rounding shift, saturation, byte packing, ONE dword store into a transposed byte buffer (48-byte
-        // columns); no u16 buffer at all.  The sample phase then needs one byte gather per sample.
-        (void)row_tiles; (void)wbase; (void)c2;
-        WAVE_SYNC();
-        {
-            unsigned char* ob = reinterpret_cast<unsigned char*>(hb32) + hi_ * 48 + 4 * hg;
-#pragma unroll
-            for (int n = 0; n < 3; n++) {
-                v4i_t av[3], d[3];
-#pragma unroll
-                for (int t = 0; t < 3; t++) av[t] = *reinterpret_cast<const v4i_t*>(abase + t * 16 * PS + 16 * n);
-#pragma unroll
-                for (int t = 0; t < 3; t++) d[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(av[t], hp_b, cin, 0, 0, 0);
-                uint32_t ph[3], pl[3];
-#pragma unroll
-                for (int t = 0; t < 3; t++) {
-                    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)d[t].y, (uint32_t)d[t].x, 0x05040100u);
-                    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)d[t].w, (uint32_t)d[t].z, 0x05040100u);
-                    pl[t] = __builtin_amdgcn_perm(hi, lo, 0x06040200u) ^ 0x80808080u;
-                    ph[t] = __builtin_amdgcn_perm(hi, lo, 0x07050301u) ^ 0x80808080u;
-                }
-                const v4i_t bh = {(int)ph[0], (int)ph[1], (int)ph[2], (int)0x80808080};
-                const v4i_t bl = {(int)pl[0], (int)pl[1], (int)pl[2], (int)0x80808080};
-#pragma unroll
-                for (int T = 0; T < 3; T++) {
-                    v4i_t ca = hp_b; ca.x += T;                             // (three band constants in the real thing)
-                    const v4i_t ah = __builtin_amdgcn_mfma_i32_16x16x64_i8(ca, bh, cin, 0, 0, 0);
-                    const v4i_t al = __builtin_amdgcn_mfma_i32_16x16x64_i8(ca, bl, cin, 0, 0, 0);
-                    uint32_t o[4];
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const uint32_t v = ((uint32_t)ah[q] << 8) + (uint32_t)al[q];
-                        o[q] = min((v + (1u << 15)) >> 16, 255u);
-                    }
-                    const uint32_t pk = __builtin_amdgcn_perm(__builtin_amdgcn_perm(o[3], o[2], 0x0c0c0400u), __builtin_amdgcn_perm(o[1], o[0], 0x0c0c0400u), 0x05040100u);
-                    if (n < 2 || c2) *reinterpret_cast<uint32_t*>(ob + n * 16 * 48 + T * 16) = pk;
-                }
-            }
-        }
-#else
         row_tiles(2);
         WAVE_SYNC();
         row_tiles(1);
         row_tiles(0);
-#endif
     }
-#endif
     // the patch has left LDS: request the next keypoint's (and the record of the one after it)
     rec = rec_next;
     patch_request(rec, min(g + gstride, total - 1));
@@ -1256,22 +1119,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), DESC_WAVES
             const float rx = rintf(fx), ry = rintf(fy);
             const uint32_t ab = (uint32_t)(int)__fmaf_rn(rx, (float)(HTS * 2), __fmaf_rn(ry, 2.f, tap0_f));
             const uint32_t* cw = (const uint32_t*)(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)(ab & ~3u);
-            (void)cw;
             const uint32_t sh = ab;                                  // v_alignbyte_b32 shifts by bits [1:0] of its third operand (0 or 2 here: the address is even)
-#if defined(VIS_TIMING_NOCONFLICT)       // timing experiment (results wrong): every lane gathers at its own bank
-            cw = (const uint32_t*)(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)((uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)reinterpret_cast<unsigned char*>(hb32) + 16u * (uint32_t)lane + (ab & 0x800u));
-#endif
-#if defined(VIS_TIMING_COLPASS)          // timing experiment (results wrong): one BYTE gather per sample from the fully blurred patch (48-byte columns)
-            {
-                const uint32_t abb = (uint32_t)(int)__fmaf_rn(rx, 48.f, __fmaf_rn(ry, 1.f, tap0_f));
-                val[e] = *(const uint8_t*)(const __attribute__((address_space(3))) uint8_t*)(uintptr_t)abb;
-                continue;
-            }
-#endif
-#if defined(VIS_TIMING_ONEREAD)          // timing experiment (results wrong): one 16-bit gather per sample, no vertical taps
-            val[e] = *(const uint16_t*)(const __attribute__((address_space(3))) uint16_t*)(uintptr_t)(ab & ~1u);
-            continue;
-#endif
             const uint32_t w0 = cw[0], w1 = cw[1], w2 = cw[2], w3 = cw[3];
             typedef unsigned short us2 __attribute__((ext_vector_type(2)));
             const uint32_t t0 = __builtin_amdgcn_alignbyte(w1, w0, sh), t1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
@@ -1348,11 +1196,6 @@ static void fill_desc_args(const vis_params& p, DescArgs& G, std::vector<uint32_
     G.k1 = (uint32_t)G.kq[4] | ((uint32_t)G.kq[5] << 8) | ((uint32_t)G.kq[6] << 16);
     G.kp[0] = (uint32_t)G.kq[0] | ((uint32_t)G.kq[1] << 16); G.kp[1] = (uint32_t)G.kq[2] | ((uint32_t)G.kq[3] << 16);
     G.kp[2] = (uint32_t)G.kq[4] | ((uint32_t)G.kq[5] << 16); G.kp[3] = (uint32_t)G.kq[6];
-    for (int j = 0; j < 4; j++) {
-        uint8_t wbytes[12] = {0};
-        for (int i = 0; i < 7; i++) wbytes[j + i] = (uint8_t)G.kq[i];
-        for (int d = 0; d < 3; d++) G.kw[j][d] = (uint32_t)wbytes[4 * d] | ((uint32_t)wbytes[4 * d + 1] << 8) | ((uint32_t)wbytes[4 * d + 2] << 16) | ((uint32_t)wbytes[4 * d + 3] << 24);
-    }
     G.rad_per_deg = (float)(M_PI / 180.f);
     G.patch_size = p.patch_size;
     G.angle_tab = nullptr;

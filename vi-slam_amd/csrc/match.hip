@@ -10,7 +10,6 @@
 //          reference's O(N1*N2) iterator scan.
 // Bit-exact against oracle/match.cpp (tests/test_match_gpu.py).
 #include "vis_internal.h"
-#include <cstdlib>
 
 // One lane = one query row; the train descriptor of the current iteration is wave-uniform, so the
 // compiler keeps it in SGPRs (s_load_dwordx8) and the inner loop is 8 x (v_xor, v_bcnt accumulate)
@@ -403,24 +402,12 @@ int launch_expand(vis_ctx* ctx, Plan* pl, int rec_first, int rec_count) {
 
 int launch_match(vis_ctx* ctx, Plan* pl, int npairs) {
     if (npairs <= 0) return VIS_OK;
-    // A/B knobs exist only in the diagnostic build (make EXTRA=-DVIS_AB_KNOBS): the shipped library reads no environment variable
-#ifdef VIS_AB_KNOBS
-    static const bool force_popcount = getenv("VIS_KNN_POPCOUNT") != nullptr;
-    static const int nc = getenv("VIS_KNN_NC") ? atoi(getenv("VIS_KNN_NC")) : 2;
-#else
-    const bool force_popcount = false;
-    const int nc = 2;
-#endif
-    if (pl->d_descx && pl->kcap <= 16384 && !force_popcount) {
-        const int per_wg = 128 * (nc == 1 ? 1 : 2);
+    if (pl->d_descx && pl->kcap <= 16384) {
+        const int per_wg = 128 * 2;          // k_knn_mfma<2>: 128 * NC fixed descriptors per workgroup
         const int nchunks = (pl->kcap + per_wg - 1) / per_wg;
         dim3 grid(8 * ((npairs + 7) / 8) * 2 * nchunks);
-        if (nc == 1)
-            hipLaunchKernelGGL(k_knn_mfma<1>, grid, dim3(256), 0, ctx->stream, pl->d_descx, pl->d_nkp, pl->kcap,
-                               pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, npairs, nchunks);
-        else
-            hipLaunchKernelGGL(k_knn_mfma<2>, grid, dim3(256), 0, ctx->stream, pl->d_descx, pl->d_nkp, pl->kcap,
-                               pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, npairs, nchunks);
+        hipLaunchKernelGGL(k_knn_mfma<2>, grid, dim3(256), 0, ctx->stream, pl->d_descx, pl->d_nkp, pl->kcap,
+                           pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, npairs, nchunks);
         HIPCHK(ctx, hipGetLastError());
         return VIS_OK;
     }

@@ -24,7 +24,6 @@
 #include "vis_internal.h"
 #include <type_traits>
 #include <cfloat>
-#include <cstdlib>
 
 #define DEV __device__ __forceinline__
 
@@ -1064,9 +1063,7 @@ __global__ __launch_bounds__(256) void k_hyp_score(PoseParams P, int h0, int h_e
         __syncthreads();
         if (tid == 0) {
             int t = 0; for (int k = 0; k < 16; k++) { sBase[k] = t; t += sCnt[k]; } sTotal = t;
-#ifndef VIS_SCORE_COUNT_UNDECIDED                                  // diagnostic build: n_models reports the undecided (model, point) decisions instead
             if (t) atomicAdd(rstate + (size_t)pair * RS + 8, t);   // point evaluations = models x M
-#endif
         }
         __syncthreads();
         const double* mbase = models + ((size_t)pair * P.max_iters + hbase) * 90;
@@ -1197,9 +1194,6 @@ __global__ __launch_bounds__(256) void k_hyp_score(PoseParams P, int h0, int h_e
             }
             __syncthreads();
             const int na = sNamb;
-#ifdef VIS_SCORE_COUNT_UNDECIDED
-            if (tid == 0) atomicAdd(rstate + (size_t)pair * RS + 8, na);
-#endif
             if (__builtin_expect(na <= AMB_CAP, 1)) {
                 for (int a = tid; a < na; a += 256) {
                     const uint32_t code = sAmb[a];
@@ -1590,17 +1584,11 @@ int pose_run(vis_ctx* ctx, int npairs, int mcap, int max_iters, const float* d_p
         // per chunk of hypotheses: (A) minimal solver up to the degree-10 polynomial, four lanes per hypothesis, 14.5 KB LDS per wave;
         // (B) its real roots, 16 lanes per hypothesis; (C) models + inlier counts, 256 threads per 16 hypotheses;
         // then the sequential accept/adaptive-bound rule is replayed by k_ransac_scan.
-#ifdef VIS_AB_KNOBS       // diagnostic build only (make EXTRA=-DVIS_AB_KNOBS): the shipped library reads no environment variable
-        static const int first_chunk = getenv("VIS_RANSAC_FIRST") ? std::max(4, std::min(16, atoi(getenv("VIS_RANSAC_FIRST")) & ~3)) : 16;
-        static const bool roots16 = getenv("VIS_ROOTS_16LANE") != nullptr;      // the 16-lanes-per-polynomial kernel for every chunk
-#else
         // 16: the headline's degenerate pairs stop within 4 hypotheses and would be as fast with 8 or 4, but S-752P's pairs need 8.7 on
         // average and every pair past the first chunk costs a whole 64-hypothesis item of the list kernels (same-box A/B 16 / 8 / 4,
-        // tools/r5_first.sh: S-752 404 / 406 / 405 k frames/s, S-752P 386 / 342 / 298 k).  One value for every batch size: n_models (the
+        // DESIGN_history.md: S-752 404 / 406 / 405 k frames/s, S-752P 386 / 342 / 298 k).  One value for every batch size: n_models (the
         // work counter of the pose record) depends on it, and a stream's records must not depend on how it is cut into batches.
         const int first_chunk = 16;
-        const bool roots16 = false;
-#endif
         // adaptive runs: the first chunk of hypotheses of every pair, then only the pairs whose bound is still above it (work list): the
         // sequential accept / adaptive-bound rule is replayed over the same hypothesis sequence, so the chunking never changes a result.
         // With the adaptive stop off every pair needs every hypothesis: no first chunk, the first scan (hi = 0) only builds the work list.
@@ -1634,14 +1622,10 @@ int pose_run(vis_ctx* ctx, int npairs, int mcap, int max_iters, const float* d_p
             const int nsub = (int)std::min<long long>(ctx->p.ransac_adaptive ? 2 * G.score : (1 << 20), (long long)npairs * chunks * 4);   // one workgroup per sub-item (a fixed grid of 2048 walking them: config 3 + 0.17 ms)
             hipLaunchKernelGGL(k_ransac_hyp_list, dim3(nb), dim3(64), HYP_LDS_BYTES, st, P, first, max_iters,
                                npairs, d_n1, d_n2, d_samples, d_rstate, d_hyp, S, (const int32_t*)d_worklist, chunks);
-            if (roots16)
-                hipLaunchKernelGGL(k_hyp_roots, dim3(nsub), dim3(256), 0, st, P, first, max_iters, npairs, d_rstate, d_hyp, S,
-                                   (const int32_t*)d_worklist, chunks);
-            else           // one hypothesis per lane
-                // one workgroup (wave) per 64-hypothesis item: the items differ in their numbers of real roots, a fixed grid walking
-                // them in strides left a quarter of the chip idle at the end (2.0 -> 1.5 ms per 1.02 M polynomials)
-                hipLaunchKernelGGL(k_hyp_roots_packed, dim3(std::min(G.roots, npairs * chunks)), dim3(64), 0, st, P, first, max_iters, npairs, d_rstate,
-                                   d_hyp, S, (const int32_t*)d_worklist, chunks);
+            // one hypothesis per lane, one workgroup (wave) per 64-hypothesis item: the items differ in their numbers of real roots, a fixed
+            // grid walking them in strides left a quarter of the chip idle at the end (2.0 -> 1.5 ms per 1.02 M polynomials)
+            hipLaunchKernelGGL(k_hyp_roots_packed, dim3(std::min(G.roots, npairs * chunks)), dim3(64), 0, st, P, first, max_iters, npairs, d_rstate,
+                               d_hyp, S, (const int32_t*)d_worklist, chunks);
             hipLaunchKernelGGL(k_hyp_models, dim3(std::min(G.models, (npairs * chunks + 3) / 4)), dim3(256), 0, st, P, first, max_iters, npairs, d_rstate,
                                d_hyp, S, d_models, (const int32_t*)d_worklist, chunks);
             hipLaunchKernelGGL(k_hyp_score, dim3(nsub), dim3(256), 0, st, P, first, max_iters, npairs, d_rstate, d_n1, d_n2, d_hyp, S,

@@ -351,7 +351,7 @@ void vis_grid_limits(const vis_params& p, int* root, std::vector<float>& hf, std
 struct SynthOrigin;
 int  vis_synth_origin(int dim, uint64_t seed, int t, int w, int h, SynthOrigin* o);
 
-// ---- plan management (plan.hip) ----
+// ---- plan management (api.hip) ----
 int  plan_create(vis_ctx* ctx, int w, int h, int stride, int B, int nrec, int npairs, Plan** out, int nsets = 1);
 void plan_destroy(Plan* pl);
 
