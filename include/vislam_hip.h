@@ -439,6 +439,45 @@ int  vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redon
 /* device-side error/overflow flags of the last batch (0 = clean) */
 int  vis_batch_status(vis_ctx* ctx, int* flags);
 
+/* ---- map points: VISystem::Triangulate (src/VISystem.cpp:862-923) and VISystem::Disparity (:422-471) --------------------------------
+ * The 3-D points of matched keypoints under a known relative pose (x2 = R x1 + t, as vis_pose_result holds it), per correspondence i:
+ *   X            DLT triangulation in the pose stage's normalised coordinates ((double)p - c) * (1 / fx) -- the single focal of
+ *                findEssentialMat(focal, pp) -- by the device code of recoverPose's cheirality vote (4 x 4 Jacobi eigen-decomposition of
+ *                A^T A, eigenvector of the smallest eigenvalue): the point in the FIRST camera's frame, in units of the baseline (|t| = 1).
+ *   VIS_MP_FRONT the cheirality test of recoverPose, the vote's own expression: for a pair of the batch the number of FRONT points under
+ *                the record's (R, t) equals n_pose_good exactly.
+ *   VIS_MP_INLIER  the mask byte of findEssentialMat when a mask is given, else set.
+ *   reproj_px    |(u1, v1) - (fx X[0] / X[2] + cx, fx X[1] / X[2] + cy)| in double, rounded to float once (:913-915, with the focal the
+ *                point was triangulated with).
+ *   parallax_px  Disparity's per-point term (:440-462) in its own single precision and operation order with RotationResCam = (float)R^T:
+ *                a = (u2 - cx) / fx, b = (v2 - cy) / fy, o = Rres (a, b, 1), |(u1, v1) - (fx o.x / o.z + cx, fy o.y / o.z + cy)|.
+ *   VIS_MP_REPROJ_OK = reproj_px <= max_reproj_px, VIS_MP_PARALLAX_OK = parallax_px >= min_parallax_px, VIS_MP_KEPT = all four.
+ *   inliers_only != 0: a correspondence whose mask byte is 0 is not decomposed; its record and flags are zero.
+ * Summary per pair: the counts and mean_parallax_px = Disparity's return value, the float sum of parallax_px over all n_points in index
+ * order divided by (float)n_points.  A pair without correspondences or without a pose (R all zero: what the pose stage leaves where
+ * RANSAC found no model, for frame 0 after vis_batch_reset and for VIS_KF_NOT_SAVED / VIS_KF_FIRST frames) gets a zero summary and
+ * its rows are left untouched.  A metric scale is the caller's multiplication. */
+enum { VIS_MP_INLIER = 1, VIS_MP_FRONT = 2, VIS_MP_REPROJ_OK = 4, VIS_MP_PARALLAX_OK = 8, VIS_MP_KEPT = 16 };
+typedef struct vis_tri_params { float max_reproj_px, min_parallax_px; int32_t inliers_only, reserved_; } vis_tri_params;   /* 16 bytes */
+typedef struct vis_map_point { double X[3]; float reproj_px, parallax_px; } vis_map_point;                                /* 32 bytes */
+typedef struct vis_tri_summary { int32_t n_points, n_front, n_kept; float mean_parallax_px; } vis_tri_summary;            /* 16 bytes */
+/* 2.0 px, 0 px, 0.  These are THIS LIBRARY's defaults: the reference has no such constants (Triangulate only draws its points, and the
+ * 22 px disparity threshold of its keyframe decision is commented out, src/VISystem.cpp:322). */
+void vis_default_tri_params(vis_tri_params* tp);
+/* One pair, HOST pointers; blocks once like the other single-frame entry points.  p1xy / p2xy: m x 2 floats (pixels); mask (m bytes) may
+ * be NULL; points / flags receive m entries.  m = 0: a zero summary. */
+int  vis_triangulate(vis_ctx* ctx, const vis_tri_params* tp, const double R[9], const double t[3],
+                     const float* p1xy, const float* p2xy, int m, const uint8_t* mask,
+                     vis_map_point* points, uint8_t* flags, vis_tri_summary* summary);
+/* Every pair of the last vis_batch_run (which must have included VIS_STAGE_POSE; n = its frames), DEVICE pointers: d_points / d_flags hold
+ * n rows of row_cap entries (d_points 16-byte aligned), d_summary n records.  Pair i is the pose stage's: its correspondences in the order
+ * the stage saw them (vis_batch_get_inlier_mask), its mask, its (R, t).  Asynchronous on the POSE stream behind that pose stage, and it
+ * overlaps the next vis_batch_run like vis_batch_align: the caller's buffers are in use until vis_batch_sync.  VIS_E_STATE without
+ * context / plan / pose stage or when n differs; VIS_E_CAPACITY when row_cap is smaller than the plan's correspondences per pair
+ * (root^2, or the keypoint capacity with VIS_POSE_SYM); VIS_E_INVALID for NULL or misaligned outputs. */
+int  vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int n, int row_cap,
+                           vis_map_point* d_points, uint8_t* d_flags, vis_tri_summary* d_summary);
+
 /* ---- rectification (vi::CameraModel, src/CameraModel.cpp:84-105; VISystem::CalculateROI, src/VISystem.cpp:162-205) -------------
  * Opt-in: nothing else in this header remaps a frame (the reference's GPU main hands frames on un-remapped, src/VISystemGPU.cpp:137-146).
  * Restatements of OpenCV 3.2 written from the published algorithm; parity with real OpenCV is UNPINNED.

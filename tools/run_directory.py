@@ -13,6 +13,9 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --track out.csv: the camera trajectory as the reference's GPU main writes it (src/main_vi_slamGPU.cpp:137-144, its first seven
              columns): one row per frame, positionCam x, y, z, qOrientationCam x, y, z, w -- vis_batch_track after every batch (the
              GPU main's keyframe rule, keyframe_min_points = 1; alignment with the intrinsics of --K fx,fy,cx,cy), from the identity.
+  --points out.csv: the map points of every frame's pair (vis_batch_triangulate behind every batch, default thresholds): one row per
+             correspondence of a pair with a pose -- frame index, timestamp, correspondence index, X, Y, Z (first camera's frame, units
+             of the baseline), reproj_px, parallax_px, flags (VIS_MP_*); the JSON line carries the totals.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -66,6 +69,7 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=0.0)
     ap.add_argument("--raw-size", default=None, help="WxH of headerless .raw files")
     ap.add_argument("--track", default=None, metavar="CSV", help="write the per-frame camera pose (positionCam, qOrientationCam) here")
+    ap.add_argument("--points", default=None, metavar="CSV", help="write the triangulated map points of every pair here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -116,6 +120,13 @@ def main():
     ctx = vislam.Context(0, p)
     B = min(a.batch, len(paths))
     ctx.batch_plan(w, h, stride, B)
+    if a.points:
+        row_cap = int(np.floor(np.sqrt(p.n_cells))) ** 2      # the grid-filtered good matches of a pair
+        d_mp = torch.empty(B * row_cap * vislam.MAP_POINT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_mf = torch.empty(B * row_cap, dtype=torch.uint8, device="cuda")
+        d_ms = torch.empty(B * vislam.TRI_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        point_rows, tri_totals = [], np.zeros(3, np.int64)
     if a.rectify:
         feed = None
         rect = ctx.rectify(cal["K"], cal["dist"], Kn, (in_w, in_h), (cal["out_width"], cal["out_height"]))
@@ -148,6 +159,8 @@ def main():
         ctx.batch_run(d, nb, stages)
         if a.track:
             ctx.batch_track(tap, d, nb, 0, d_align.data_ptr(), d_track.data_ptr())
+        if a.points:
+            ctx.batch_triangulate(nb, row_cap, d_mp.data_ptr(), d_mf.data_ptr(), d_ms.data_ptr())
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -156,6 +169,13 @@ def main():
         if a.track:
             track_bytes = d_track[:nb * C.sizeof(vislam.TrackResult)].cpu().numpy().tobytes()
             poses += [vislam.TrackResult.from_buffer_copy(track_bytes, i * C.sizeof(vislam.TrackResult)).pose for i in range(nb)]
+        if a.points:
+            mp = d_mp.cpu().numpy().view(vislam.MAP_POINT_DTYPE).reshape(B, row_cap)
+            mf, ms = d_mf.cpu().numpy().reshape(B, row_cap), d_ms.cpu().numpy().view(vislam.TRI_SUMMARY_DTYPE)
+            for i in range(nb):
+                tri_totals += (int(ms[i]["n_points"]), int(ms[i]["n_front"]), int(ms[i]["n_kept"]))
+                point_rows += [(first + i, stamps[first + i], j, *mp[i, j]["X"], mp[i, j]["reproj_px"], mp[i, j]["parallax_px"], int(mf[i, j]))
+                               for j in range(int(ms[i]["n_points"]))]
         if ctx.batch_status() != 0:
             raise SystemExit("device capacity flag set")
         for i in range(nb):
@@ -202,6 +222,12 @@ def main():
             for e in poses:
                 f.write(",".join("%.9g" % v for v in (e.tx, e.ty, e.tz, e.qx, e.qy, e.qz, e.qw)) + "\n")
         out["track_csv"] = a.track
+    if a.points:
+        with open(a.points, "w") as f:
+            for r in point_rows:
+                f.write("%d,%d,%d,%.17g,%.17g,%.17g,%.9g,%.9g,%d\n" % r)
+        out["points_csv"] = a.points
+        out["map_points"] = {"triangulated": int(tri_totals[0]), "front": int(tri_totals[1]), "kept": int(tri_totals[2])}
     if feed:
         feed.close()
     else:

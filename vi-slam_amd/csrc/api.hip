@@ -77,7 +77,7 @@ template <class F> static void ordering_events(vis_ctx* ctx, F f) {
     f(ctx->ev_filter_done, dt); f(ctx->ev_detect_done, dt); f(ctx->ev_update_fork, dt); f(ctx->ev_update_done, dt); f(ctx->ev_align_fork, dt);
     f(ctx->ev_pose_done, hipEventDefault); f(ctx->ev_pose_start, hipEventDefault); f(ctx->ev_match_start, hipEventDefault);   // (also time the stages)
     for (int i = 0; i < VIS_BATCH_SETS; i++) f(ctx->ev_match_done[i], dt);
-    for (int i = 0; i < 2; i++) { f(ctx->ev_pose_done_set[i], dt); f(ctx->ev_results_done_set[i], dt); f(ctx->ev_align_done[i], dt); }
+    for (int i = 0; i < 2; i++) { f(ctx->ev_pose_done_set[i], dt); f(ctx->ev_results_done_set[i], dt); f(ctx->ev_align_done[i], dt); f(ctx->ev_tri_done[i], dt); }
 }
 
 extern "C" int vis_create(int device, vis_ctx** out) {
@@ -1296,6 +1296,77 @@ extern "C" int vis_batch_results_async(vis_ctx* ctx, vis_pose_result* h_pose, vi
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev_results_done_set[pl->mo_cur], s));
     pl->out().readers.note(s, ctx->ev_results_done_set[pl->mo_cur]);
+    return VIS_OK;
+}
+
+// ---- map points (VISystem::Triangulate / Disparity): pose.hip k_triangulate
+extern "C" void vis_default_tri_params(vis_tri_params* tp) {
+    if (!tp) return;
+    tp->max_reproj_px = 2.0f; tp->min_parallax_px = 0.0f; tp->inliers_only = 0; tp->reserved_ = 0;
+}
+
+extern "C" int vis_triangulate(vis_ctx* ctx, const vis_tri_params* tp, const double R[9], const double t[3],
+                               const float* p1xy, const float* p2xy, int m, const uint8_t* mask,
+                               vis_map_point* points, uint8_t* flags, vis_tri_summary* summary) {
+    if (!ctx || !tp || !R || !t || !summary || m < 0 || (m && (!p1xy || !p2xy || !points || !flags))) return VIS_E_INVALID;
+    std::memset(summary, 0, sizeof(*summary));
+    if (m == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    int rc = ensure_scratch(ctx, (size_t)m * (8 + 8 + 1 + sizeof(vis_map_point) + 1) + sizeof(PoseOut) + sizeof(vis_tri_summary) + 4096);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0};
+    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
+    uint8_t* d_mask = cv.take<uint8_t>(m);
+    PoseOut* d_pose = cv.take<PoseOut>(1);
+    vis_map_point* d_points = cv.take<vis_map_point>(m);
+    uint8_t* d_flags = cv.take<uint8_t>(((size_t)m + 3) & ~(size_t)3);
+    vis_tri_summary* d_summary = cv.take<vis_tri_summary>(1);
+    rc = vis_ensure_pin(ctx, (size_t)m * (8 + 8 + 1 + sizeof(vis_map_point) + 1) + sizeof(PoseOut) + sizeof(vis_tri_summary) + 4096);
+    if (rc) return rc;
+    PoseOut o;
+    std::memset(&o, 0, sizeof(o));
+    std::memcpy(o.R, R, 72); std::memcpy(o.t, t, 24);
+    o.n_points = m;
+    HostStage hs(ctx);
+    hs.up(d_p1, p1xy, (size_t)m * 8);
+    hs.up(d_p2, p2xy, (size_t)m * 8);
+    if (mask) hs.up(d_mask, mask, (size_t)m);
+    hs.up(d_pose, &o, sizeof(o));
+    hs.flush_ups();
+    // (a pair without a pose leaves its rows untouched: the caller's buffers are then not written either, summary.n_points == 0 below)
+    rc = triangulate_run(ctx, tp, 1, m, m, d_pose, d_p1, d_p2, mask ? d_mask : nullptr, d_points, d_flags, d_summary);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const void* h_sum = hs.down(d_summary, sizeof(vis_tri_summary));
+    const void* h_pts = hs.down(d_points, (size_t)m * sizeof(vis_map_point));
+    const void* h_fl = hs.down(d_flags, ((size_t)m + 3) & ~(size_t)3);
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(summary, h_sum, sizeof(*summary));
+    if (summary->n_points > 0) { std::memcpy(points, h_pts, (size_t)m * sizeof(vis_map_point)); std::memcpy(flags, h_fl, (size_t)m); }
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int n, int row_cap,
+                                     vis_map_point* d_points, uint8_t* d_flags, vis_tri_summary* d_summary) {
+    if (!tp || !d_points || !d_flags || !d_summary || ((uintptr_t)d_points & 15) || ((uintptr_t)d_summary & 3)) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_triangulate: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (row_cap < pl->pose_mcap) { ctx->err = "vis_batch_triangulate: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    // On the pose stream, behind the pose stage that wrote d_mask / d_pose (single-buffered, written on that stream only: the next
+    // pose stage is queued behind this call) and that itself waited for the filter that wrote p1 / p2.  Those belong to the matcher-output
+    // set of the last step, which the filter two steps on rewrites: it waits for the reader event noted here.
+    hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
+    Plan::MatchOut& O = pl->out();
+    ctx->stream = sP;
+    const int rc = triangulate_run(ctx, tp, n, pl->pose_mcap, row_cap, pl->d_pose, O.p1, O.p2, pl->d_mask, d_points, d_flags, d_summary);
+    ctx->stream = sA;
+    if (rc) return rc;
+    ctx->pose_pending = true;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_tri_done[pl->mo_cur], sP));
+    O.readers.note(sP, ctx->ev_tri_done[pl->mo_cur]);
     return VIS_OK;
 }
 

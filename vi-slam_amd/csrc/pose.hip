@@ -1500,6 +1500,116 @@ __global__ __launch_bounds__(256) void k_pose_final(PoseParams P, const double* 
     }
 }
 
+// ---- VISystem::Triangulate (src/VISystem.cpp:862-923) + the per-point term of VISystem::Disparity (:440-462): the map points of the
+// correspondences under a KNOWN (R, t) -- the points recoverPose voted on, which k_pose_final reduces to one bit each.  ONE
+// CORRESPONDENCE PER LANE.  A workgroup covers up to TRI_MAX_PB whole pairs when their rows fit (49 correspondences at the headline: five pairs,
+// 245 of 256 lanes), else a 256-correspondence piece of one pair's row (config 3: M ~ 3100 spreads over 13 workgroups per pair); the
+// 21 doubles of a pair's pose go through LDS once per workgroup.  The decomposition is cheirality() itself: VIS_MP_FRONT is the vote's
+// own expression on the vote's own inputs, so its count under the record's (R, t) equals n_pose_good bit for bit.
+#define TRI_THREADS 256
+#define TRI_MAX_PB 8
+static inline int tri_pairs_per_block(int row) { return row >= TRI_THREADS ? 1 : std::min(TRI_MAX_PB, TRI_THREADS / std::max(row, 1)); }
+struct TriArgs {
+    double fx, fx_inv, cx, cy;                                     // the pose stage's normalisation (single focal) and the reprojection
+    float fxf, fyf, cxf, cyf;                                      // Disparity's own floats (fx AND fy)
+    float max_reproj_px, min_parallax_px;
+    int inliers_only, npairs, in_stride, row_cap, pb, pieces;      // in_stride: row length of p1 / p2 / mask; pieces: workgroups per row (pb == 1)
+};
+// a pair has a pose when its record holds correspondences and a rotation (k_pose_final leaves R = 0 where RANSAC found no model)
+DEV bool tri_has_pose(const PoseOut* __restrict__ o) {
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 9; k++) any = any || (o->R[k] != 0.0);
+    return any && o->n_points > 0;
+}
+__global__ __launch_bounds__(TRI_THREADS) void k_triangulate(TriArgs T, const PoseOut* __restrict__ pose, const float* __restrict__ p1,
+                                                             const float* __restrict__ p2, const uint8_t* __restrict__ mask,
+                                                             vis_map_point* __restrict__ points, uint8_t* __restrict__ flags) {
+    __shared__ double sRt[TRI_MAX_PB][12];
+    __shared__ int sN[TRI_MAX_PB];
+    const int tid = threadIdx.x;
+    int pl, i, pair0;                                              // pair slot of the workgroup, correspondence
+    if (T.pb > 1) { pair0 = blockIdx.x * T.pb; pl = tid / T.in_stride; i = tid - pl * T.in_stride; }
+    else { pair0 = blockIdx.x / T.pieces; pl = 0; i = (blockIdx.x - pair0 * T.pieces) * TRI_THREADS + tid; }
+    if (tid < T.pb * 13) {                                         // 9 + 3 doubles and the count of every pair of the workgroup
+        const int s = tid / 13, k = tid - s * 13, pr = pair0 + s;
+        if (pr < T.npairs) {
+            const PoseOut* o = pose + pr;
+            if (k < 9) sRt[s][k] = o->R[k];
+            else if (k < 12) sRt[s][k] = o->t[k - 9];
+            else sN[s] = tri_has_pose(o) ? min(o->n_points, T.in_stride) : 0;
+        } else if (k == 12) sN[s] = 0;
+    }
+    __syncthreads();
+    if (pl >= T.pb || i >= sN[pl]) return;                         // rows of pairs without a pose are left untouched
+    const int pair = pair0 + pl;
+    const size_t in = (size_t)pair * T.in_stride + i, out = (size_t)pair * T.row_cap + i;
+    const float2 a = reinterpret_cast<const float2*>(p1)[in], b = reinterpret_cast<const float2*>(p2)[in];
+    const bool inl = mask ? mask[in] != 0 : true;
+    uint4 w0 = {0, 0, 0, 0}, w1 = {0, 0, 0, 0};
+    unsigned f = 0;
+    if (inl || !T.inliers_only) {
+        const double* R = sRt[pl];
+        const double x1 = ((double)a.x - T.cx) * T.fx_inv, y1 = ((double)a.y - T.cy) * T.fx_inv;       // k_pose_prep's expression
+        const double x2 = ((double)b.x - T.cx) * T.fx_inv, y2 = ((double)b.y - T.cy) * T.fx_inv;
+        double Xh[4];
+        const bool front = cheirality(R, R + 9, x1, y1, x2, y2, Xh, nullptr);
+        const double X[3] = {Xh[0] / Xh[3], Xh[1] / Xh[3], Xh[2] / Xh[3]};
+        // reprojection into the first image with the focal the point was triangulated with (:913-915)
+        const double du = (double)a.x - (T.fx * (X[0] / X[2]) + T.cx), dv = (double)a.y - (T.fx * (X[1] / X[2]) + T.cy);
+        const float reproj = (float)sqrt(du * du + dv * dv);
+        // Disparity's term: the second ray rotated into the first camera, RotationResCam = (float)R^T, single precision throughout
+        const float ra = (b.x - T.cxf) / T.fxf, rb = (b.y - T.cyf) / T.fyf;
+        const float ox = ((float)R[0] * ra + (float)R[3] * rb) + (float)R[6] * 1.0f;
+        const float oy = ((float)R[1] * ra + (float)R[4] * rb) + (float)R[7] * 1.0f;
+        const float oz = ((float)R[2] * ra + (float)R[5] * rb) + (float)R[8] * 1.0f;
+        const float pu = T.fxf * ox / oz + T.cxf, pv = T.fyf * oy / oz + T.cyf;
+        const float eu = a.x - pu, ev = a.y - pv;
+        const float parallax = sqrtf(eu * eu + ev * ev);
+        f = (inl ? VIS_MP_INLIER : 0) | (front ? VIS_MP_FRONT : 0) | (reproj <= T.max_reproj_px ? VIS_MP_REPROJ_OK : 0) |
+            (parallax >= T.min_parallax_px ? VIS_MP_PARALLAX_OK : 0);
+        if (f == (VIS_MP_INLIER | VIS_MP_FRONT | VIS_MP_REPROJ_OK | VIS_MP_PARALLAX_OK)) f |= VIS_MP_KEPT;
+        const unsigned long long u0 = __builtin_bit_cast(unsigned long long, X[0]), u1 = __builtin_bit_cast(unsigned long long, X[1]),
+                                 u2 = __builtin_bit_cast(unsigned long long, X[2]);
+        w0 = {(unsigned)u0, (unsigned)(u0 >> 32), (unsigned)u1, (unsigned)(u1 >> 32)};
+        w1 = {(unsigned)u2, (unsigned)(u2 >> 32), __builtin_bit_cast(unsigned, reproj), __builtin_bit_cast(unsigned, parallax)};
+    }
+    uint4* rec = reinterpret_cast<uint4*>(points + out);           // 32-byte records, 16-byte aligned rows: two dwordx4 stores
+    rec[0] = w0; rec[1] = w1;
+    flags[out] = (uint8_t)f;
+}
+
+// the summary of every pair: one wave per pair walks the row in index order.  Disparity's return value is a float sum over the points
+// in the order of the loop (:440-466); a tree reduction is a different number, so lane 0's accumulator takes the 64 values of a
+// piece one by one (readlane), and the counts are ballots.
+__global__ __launch_bounds__(64) void k_tri_summary(int row_cap, int in_stride, const PoseOut* __restrict__ pose,
+                                                    const vis_map_point* __restrict__ points, const uint8_t* __restrict__ flags,
+                                                    vis_tri_summary* __restrict__ summary) {
+    const int pair = blockIdx.x, lane = threadIdx.x;
+    const PoseOut* o = pose + pair;
+    const int n = tri_has_pose(o) ? min(o->n_points, in_stride) : 0;
+    float sum = 0.f; int n_front = 0, n_kept = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const size_t at = (size_t)pair * row_cap + i;
+        const float v = i < n ? points[at].parallax_px : 0.f;
+        const unsigned fl = i < n ? flags[at] : 0u;
+        n_front += __popcll(__builtin_amdgcn_ballot_w64((fl & VIS_MP_FRONT) != 0));
+        n_kept += __popcll(__builtin_amdgcn_ballot_w64((fl & VIS_MP_KEPT) != 0));
+        // all 64 lanes with constant lane numbers (a loop over the valid ones pays a branch and a scalar-register hazard per point: config 3's
+        // 3000 points per pair took as long here as in k_triangulate).  The lanes past the row hold +0: the sum is a sum of square roots
+        // -- never -0 -- and x + 0 == x, NaN included, so the value is that of the loop over the valid points.
+#pragma unroll
+        for (int j = 0; j < 64; j++) sum += __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), j));
+    }
+    if (lane == 0) {
+        vis_tri_summary s;
+        s.n_points = n; s.n_front = n_front; s.n_kept = n_kept;
+        s.mean_parallax_px = n > 0 ? sum / (float)n : 0.f;
+        summary[pair] = s;
+    }
+}
+
 // ---- F2FRansac (src/VISystem.cpp:612-769): lane per iteration, shared normal vectors
 __global__ __launch_bounds__(256) void k_f2f(const vis_keypoint* __restrict__ pts1, const vis_keypoint* __restrict__ pts2, int m,
                                              float fx, float fy, float cx, float cy, const float* __restrict__ rot,
@@ -1636,6 +1746,26 @@ int pose_run(vis_ctx* ctx, int npairs, int mcap, int max_iters, const float* d_p
     const int nsplit = std::max(1, std::min(32, (4 * mcap + 4095) / 4096));       // ~16 triangulations per thread
     if (do_pose) hipLaunchKernelGGL(k_pose_svd, dim3((npairs + 63) / 64), dim3(64), 0, st, P, (const double*)d_models, (const int32_t*)d_rstate, d_E_in, d_hyp, npairs);
     hipLaunchKernelGGL(k_pose_final, dim3(npairs, nsplit), dim3(256), 0, st, P, d_n1, d_n2, d_models, d_rstate, d_E_in, d_mask, d_pose, do_pose, (const double*)d_hyp);
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+// d_pose: npairs records (R, t, n_points); d_p1 / d_p2 / d_mask (may be null): rows of in_stride correspondences; outputs: rows of row_cap
+int triangulate_run(vis_ctx* ctx, const vis_tri_params* tp, int npairs, int in_stride, int row_cap, const PoseOut* d_pose,
+                    const float* d_p1, const float* d_p2, const uint8_t* d_mask, vis_map_point* d_points, uint8_t* d_flags,
+                    vis_tri_summary* d_summary) {
+    if (npairs <= 0) return VIS_OK;
+    hipStream_t st = ctx->stream;
+    TriArgs T;
+    T.fx = ctx->p.fx; T.fx_inv = 1. / ctx->p.fx; T.cx = ctx->p.cx; T.cy = ctx->p.cy;
+    T.fxf = (float)ctx->p.fx; T.fyf = (float)ctx->p.fy; T.cxf = (float)ctx->p.cx; T.cyf = (float)ctx->p.cy;
+    T.max_reproj_px = tp->max_reproj_px; T.min_parallax_px = tp->min_parallax_px; T.inliers_only = tp->inliers_only;
+    T.npairs = npairs; T.in_stride = in_stride; T.row_cap = row_cap;
+    T.pb = tri_pairs_per_block(in_stride); T.pieces = (in_stride + TRI_THREADS - 1) / TRI_THREADS;
+    const long long blocks = T.pb > 1 ? (npairs + T.pb - 1) / T.pb : (long long)npairs * T.pieces;
+    if (blocks > 0x7fffffffLL) return VIS_E_CAPACITY;
+    hipLaunchKernelGGL(k_triangulate, dim3((unsigned)blocks), dim3(TRI_THREADS), 0, st, T, d_pose, d_p1, d_p2, d_mask, d_points, d_flags);
+    hipLaunchKernelGGL(k_tri_summary, dim3(npairs), dim3(64), 0, st, row_cap, in_stride, d_pose, (const vis_map_point*)d_points, (const uint8_t*)d_flags, d_summary);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

@@ -28,6 +28,7 @@ template <class T> inline Point3_<T> operator-(const Point3_<T>& a, const Point3
 template <class T> inline Point3_<T> operator-(const Point3_<T>& a) { return Point3_<T>(-a.x, -a.y, -a.z); }
 template <class T> inline Point3_<T> operator*(const Point3_<T>& a, double s) { return Point3_<T>((T)(a.x * s), (T)(a.y * s), (T)(a.z * s)); }
 typedef Point3_<float> Point3f; typedef Point3_<double> Point3d;
+typedef unsigned char uchar;
 struct KeyPoint { Point2f pt; float size, angle, response; int octave, class_id;
                   KeyPoint() : size(0), angle(-1), response(0), octave(0), class_id(-1) {} };
 struct DMatch { int queryIdx, trainIdx, imgIdx; float distance;

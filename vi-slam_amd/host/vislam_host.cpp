@@ -537,6 +537,63 @@ void VISystem::setGtRes(Mat TranslationResGT, Mat RotationResGT) {              
     Matx33f R; for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R(r, c) = RotationResGT.at<float>(r, c);
     RotationResidual = RPY2rotationMatrix(rotationMatrix2RPY(R));
 }
+float VISystem::Disparity(vector<KeyPoint> keyPoints, vector<KeyPoint> inPoints) {     // :422-471
+    const float fx0 = fx_[0], fy0 = fy_[0], cx0 = cx_[0], cy0 = cy_[0];
+    const int numkeypoints = (int)std::min(keyPoints.size(), inPoints.size());
+    float disparitySum = 0;
+    for (int index = 0; index < numkeypoints; index++) {
+        const float u2 = inPoints[index].pt.x, v2 = inPoints[index].pt.y, uk1 = keyPoints[index].pt.x, vk1 = keyPoints[index].pt.y;
+        const float a = (u2 - cx0) / fx0, b = (v2 - cy0) / fy0;
+        const Matx33f& Rr = RotationResCam;                                            // Matx33f * Point3f: every row summed left to right
+        const float ox = (Rr(0, 0) * a + Rr(0, 1) * b) + Rr(0, 2) * 1.0f;
+        const float oy = (Rr(1, 0) * a + Rr(1, 1) * b) + Rr(1, 2) * 1.0f;
+        const float oz = (Rr(2, 0) * a + Rr(2, 1) * b) + Rr(2, 2) * 1.0f;
+        const float u1 = fx0 * ox / oz + cx0, v1 = fy0 * oy / oz + cy0;
+        disparitySum = disparitySum + std::sqrt((uk1 - u1) * (uk1 - u1) + (vk1 - v1) * (vk1 - v1));
+    }
+    return numkeypoints > 0 ? disparitySum / (float)numkeypoints : 0.f;
+}
+Mat VISystem::getProjectionMat(Mat cameraMat, Mat rotationMat, Mat translationMat) {   // :1872-1880
+    Mat P = Mat::zeros(3, 4, CV_32FC1);
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) {
+            float s = 0;
+            for (int k = 0; k < 3; k++) s += cameraMat.at<float>(r, k) * (c < 3 ? rotationMat.at<float>(k, c) : translationMat.at<float>(k, 0));
+            P.at<float>(r, c) = s;
+        }
+    return P;
+}
+void VISystem::Triangulate(vector<KeyPoint> inPoints1, vector<KeyPoint> inPoints2) {  // :862-923
+    const int m = (int)std::min(inPoints1.size(), inPoints2.size());
+    mapPoints.assign(m, Point3f(0, 0, 0)); mapPointFlags.assign(m, 0);
+    lastTriangulation = vis_tri_summary{0, 0, 0, 0.f};
+    if (m == 0) return;                                                                // :883
+    // [R | t] of P2 (:872): rotation RotationResidual^T, translation (-RotationResidual^T) * TranslationResidual, in float like the Mats
+    double R2[9], t2[3];
+    for (int r = 0; r < 3; r++) {
+        const float n0 = -RotationResidual(0, r), n1 = -RotationResidual(1, r), n2 = -RotationResidual(2, r);
+        for (int c = 0; c < 3; c++) R2[3 * r + c] = (double)RotationResidual(c, r);
+        t2[r] = (double)((n0 * TranslationResidual.at<float>(0, 0) + n1 * TranslationResidual.at<float>(1, 0)) + n2 * TranslationResidual.at<float>(2, 0));
+    }
+    vis_ctx* ctx = VisDevice::get();
+    vis_params p; vis_get_params(ctx, &p);
+    if (p.fx != (double)fx_[0] || p.fy != (double)fy_[0] || p.cx != (double)cx_[0] || p.cy != (double)cy_[0]) {
+        p.fx = fx_[0]; p.fy = fy_[0]; p.cx = cx_[0]; p.cy = cy_[0];
+        const int rc = vis_set_params(ctx, &p);
+        if (rc) VisDevice::fail(rc, "Triangulate");
+    }
+    vector<float> p1(2 * (size_t)m), p2(2 * (size_t)m);
+    for (int i = 0; i < m; i++) {                                                     // KeyPoint::convert, :876-877
+        p1[2 * i] = inPoints1[i].pt.x; p1[2 * i + 1] = inPoints1[i].pt.y;
+        p2[2 * i] = inPoints2[i].pt.x; p2[2 * i + 1] = inPoints2[i].pt.y;
+    }
+    vis_tri_params tp; vis_default_tri_params(&tp);
+    vector<vis_map_point> pts(m);
+    const int rc = vis_triangulate(ctx, &tp, R2, t2, p1.data(), p2.data(), m, nullptr, pts.data(), mapPointFlags.data(), &lastTriangulation);
+    if (rc) VisDevice::fail(rc, "Triangulate");
+    if (lastTriangulation.n_points == 0) return;                                       // no pose (a zero rotation): nothing was written
+    for (int i = 0; i < m; i++) mapPoints[i] = Point3f((float)pts[i].X[0], (float)pts[i].X[1], (float)pts[i].X[2]);
+}
 // Gauss-Newton photometric alignment of the previous keyframe's candidate points to the current frame, :1113-1448.
 // Options (:1115-1121) are the defaults of vis_align_params.  The reference seeds the pose with the IMU's residual rotation and
 // the ground-truth translation residual (:1133-1166); the IMU core is outside this build (identity), the translation seed is

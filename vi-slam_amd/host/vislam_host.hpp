@@ -221,6 +221,14 @@ public:
     int EstimatePoseFeaturesRansac(Frame* _previous_frame, Frame* _current_frame);
     void Track();                                                                  // :1567-1635
     void setGtRes(Mat TranslationResGT, Mat RotationGT);                            // :406 (ground-truth seed of the alignment)
+    // mean rotation-compensated parallax of matched keypoints (keyframe, current frame) under RotationResCam, :422-471: the host float
+    // loop; equals vis_tri_summary::mean_parallax_px when RotationResCam == (float)R^T.  No points: 0.
+    float Disparity(vector<KeyPoint> keyPoints, vector<KeyPoint> inPoints);
+    // :862-923 on the device (vis_triangulate) with P2 = [R^T | -R^T t] from RotationResidual / TranslationResidual (:872); what the
+    // reference only draws on its debug image is left in mapPoints / mapPointFlags.  Triangulated in the pose stage's normalised
+    // coordinates with the single focal fx_[0].
+    void Triangulate(vector<KeyPoint> inPoints1, vector<KeyPoint> inPoints2);
+    Mat getProjectionMat(Mat cameraMat, Mat rotationMat, Mat translationMat);        // :1872-1880: cameraMat * [rotation | translation], CV_32F
     bool initialized = false, distortion_valid = false, depth_available = false;
     int num_keyframes = 0, num_max_keyframes = 0, min_features = 0, start_index = 0;
     Mat map1, map2;
@@ -251,6 +259,8 @@ public:
     // results of the last pose estimates
     vis_align_result lastAlignment;                                                // EstimatePoseFeatures
     float ransacR[9], ransacT[3]; int lastInliers = 0, lastPoseGood = 0;            // EstimatePoseFeaturesRansac
+    std::vector<Point3f> mapPoints; std::vector<uchar> mapPointFlags;               // Triangulate: (float)X and the VIS_MP_* flags per point
+    vis_tri_summary lastTriangulation = {0, 0, 0, 0.f};
 };
 
 class VISystemGPU : public VISystem {                    // include/VISystemGPU.hpp:14-36

@@ -94,6 +94,26 @@ POSE_RESULT_DTYPE = np.dtype([("E", "<f8", (9,)), ("R", "<f8", (9,)), ("t", "<f8
 assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult) == 192
 
 
+class TriParams(C.Structure):
+    """vis_tri_params: the thresholds of the map-point flags (vis_default_tri_params: 2.0 px, 0 px, 0)"""
+    _fields_ = [("max_reproj_px", C.c_float), ("min_parallax_px", C.c_float), ("inliers_only", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class MapPoint(C.Structure):
+    """vis_map_point: the triangulated point (first camera's frame, units of the baseline) and its two per-point errors"""
+    _fields_ = [("X", C.c_double * 3), ("reproj_px", C.c_float), ("parallax_px", C.c_float)]
+
+
+class TriSummary(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_front", C.c_int32), ("n_kept", C.c_int32), ("mean_parallax_px", C.c_float)]
+
+
+MAP_POINT_DTYPE = np.dtype([("X", "<f8", (3,)), ("reproj_px", "<f4"), ("parallax_px", "<f4")])
+TRI_SUMMARY_DTYPE = np.dtype([("n_points", "<i4"), ("n_front", "<i4"), ("n_kept", "<i4"), ("mean_parallax_px", "<f4")])
+assert C.sizeof(TriParams) == 16 and MAP_POINT_DTYPE.itemsize == C.sizeof(MapPoint) == 32 and TRI_SUMMARY_DTYPE.itemsize == C.sizeof(TriSummary) == 16
+MP_INLIER, MP_FRONT, MP_REPROJ_OK, MP_PARALLAX_OK, MP_KEPT = 1, 2, 4, 8, 16
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -131,6 +151,7 @@ ABI_SYMBOLS = [
     "vis_batch_track_init", "vis_batch_track",
     "vis_optimal_new_camera_matrix", "vis_undistort_rectify_map", "vis_rectify_create", "vis_rectify_destroy", "vis_rectify_maps",
     "vis_rectify_batch", "vis_rectify_host",
+    "vis_default_tri_params", "vis_triangulate", "vis_batch_triangulate",
 ]
 
 
@@ -191,6 +212,11 @@ def _load():
         lib.vis_rectify_maps.argtypes = [vp, vp, vp]
         lib.vis_rectify_batch.argtypes = [vp, vp, ci, ci, ci, ci, ci, ci, vp, ci]
         lib.vis_rectify_host.argtypes = [vp, vp, ci, vp, ci]
+    if hasattr(lib, "vis_triangulate"):                 # (absent from older A/B builds)
+        lib.vis_default_tri_params.argtypes = [C.POINTER(TriParams)]
+        lib.vis_default_tri_params.restype = None
+        lib.vis_triangulate.argtypes = [vp, C.POINTER(TriParams), vp, vp, vp, vp, ci, vp, vp, vp, C.POINTER(TriSummary)]
+        lib.vis_batch_triangulate.argtypes = [vp, C.POINTER(TriParams), ci, ci, vp, vp, vp]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -269,6 +295,12 @@ def default_align_params():
     ap = AlignParams()
     lib.vis_default_align_params(C.byref(ap))
     return ap
+
+
+def default_tri_params():
+    tp = TriParams()
+    lib.vis_default_tri_params(C.byref(tp))
+    return tp
 
 
 def se3_exp(a):
@@ -667,6 +699,32 @@ class Context:
         self._chk(lib.vis_recover_pose(self._h, _ptr(E), _ptr(p1), _ptr(p2), len(p1), _ptr(R), _ptr(t), C.byref(ng)),
                   "vis_recover_pose")
         return R.reshape(3, 3), t, ng.value
+
+    # -- VISystem::Triangulate / Disparity ------------------------------------------------------------------
+    def triangulate(self, R, t, p1, p2, mask=None, tp=None):
+        """(points MAP_POINT_DTYPE[m], flags uint8[m], TriSummary) of m correspondences under x2 = R x1 + t"""
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        m = len(p1)
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+            assert len(mask) == m
+        tp = default_tri_params() if tp is None else tp
+        pts = np.zeros(max(m, 1), MAP_POINT_DTYPE)
+        fl = np.zeros(max(m, 1), np.uint8)
+        sm = TriSummary()
+        self._chk(lib.vis_triangulate(self._h, C.byref(tp), _ptr(R), _ptr(t), _ptr(p1), _ptr(p2), m, _ptr(mask), _ptr(pts), _ptr(fl),
+                                      C.byref(sm)), "vis_triangulate")
+        return pts[:m], fl[:m], sm
+
+    def batch_triangulate(self, n, row_cap, d_points_ptr, d_flags_ptr, d_summary_ptr, tp=None):
+        """queue the triangulation of every pair of the last batch_run(... | STAGE_POSE) on the pose stream (raw DEVICE pointers: n rows of
+        row_cap MapPoint / flag bytes, n TriSummary); the buffers are in use until batch_sync()"""
+        tp = default_tri_params() if tp is None else tp
+        self._chk(lib.vis_batch_triangulate(self._h, C.byref(tp), n, row_cap, C.c_void_p(d_points_ptr), C.c_void_p(d_flags_ptr),
+                                            C.c_void_p(d_summary_ptr)), "vis_batch_triangulate")
 
     def f2f_ransac(self, pts1, pts2, rot, sample_idx, scale):
         pts1 = np.ascontiguousarray(pts1, KEYPOINT_DTYPE)
