@@ -367,7 +367,8 @@ int  vis_batch_get_matches(vis_ctx* ctx, int frame, vis_dmatch* good, int cap, i
 int  vis_batch_get_pose(vis_ctx* ctx, int frame, double E[9], double R[9], double t[3],
                         int* n_inliers, int* n_pose_good, int* iters_run);
 /* diagnostics: out[0] = kernel launches of this process so far, out[1] = times a single-frame entry point of this context blocked on the
- * device, out[2] = asynchronous copies those entry points queued, out[3] = 0.  (bench.py `single_frame_api`: per-frame differences.) */
+ * device, out[2] = asynchronous copies those entry points queued (bench.py `single_frame_api`: per-frame differences), out[3] = the largest
+ * vis_pose_result::undecided_max of any vis_essential_ransac call of this context. */
 int  vis_debug_counters(vis_ctx* ctx, unsigned long long out[4]);
 /* the inlier mask of findEssentialMat (src/VISystem.cpp:1680, the `mask` argument) for pair `frame` of the last batch: one byte per
  * correspondence the pose stage saw, in the order it saw them (good matches, or the symmetric matches with VIS_POSE_SYM).
@@ -416,7 +417,9 @@ typedef struct vis_pose_result {
     int32_t n_inliers, n_pose_good, iters_run, n_points;
     int32_t n_models;          /* candidate essential matrices scored against the n_points correspondences (SURVEY 8(d):
                                   point evaluations = n_models x n_points) */
-    int32_t reserved_;
+    int32_t undecided_max;     /* diagnostic: the most (model, point) inlier decisions that single precision left open in any group of 16
+                                  hypotheses of this problem (settled in double precision: up to 4096 from a list, beyond that by
+                                  recounting the group); 0 for up to 256 correspondences, which never use that form */
 } vis_pose_result;
 /* Queue the device-to-host copy of the last batch's results -- n pose records, the good matches (n x root^2, dense
  * rows) and their counts, one entry per frame of the batch: the pair (vis_batch_get_keyframes' prev[i] -> frame i); a frame

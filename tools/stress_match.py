@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """tools/stress_match.py [SECONDS] [SEED] -- randomised parity of the host-pointer matcher entry points and VISystem::F2FRansac on the
-GPU box: vis_bf_knn2_hamming_host on random descriptor sets (1 ... 9000 rows each side, with duplicated rows, all-zero / all-one rows
-and near-duplicates so that ties and the ends of the distance range occur), vis_good_matches_host on random keypoints with those
-tables, vis_f2f_ransac on random two-view problems -- 2-NN tables, symmetric / good matches and the winning count bit for bit, the
-translation within 1e-6.  Exit code 1 on any failure.  Not part of the test suite (unbounded run time)."""
+GPU box: vis_bf_knn2_hamming_host on random descriptor sets (1 ... 20000 rows on one side -- 16384 is the last size of the MFMA kernel,
+above it the popcount kernel runs -- and 1 ... 8000 on the other, with duplicated rows, all-zero / all-one rows and near-duplicates so
+that ties and the ends of the distance range occur), vis_good_matches_host on random keypoints with those tables, vis_f2f_ransac on
+random two-view problems -- 2-NN tables, symmetric / good matches and the winning count bit for bit, the translation within 1e-6.
+Exit code 1 on any failure.  Not part of the test suite (unbounded run time)."""
 import os
 import sys
 import time
@@ -45,7 +46,7 @@ while time.time() < t_end and (max_cases is None or runs < max_cases):
     what = "?"
     try:
         if kind == 0:
-            n1 = int(rng.choice([1, 2, 3, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1000, 1000, 1023, 1025, 4000, 8000, 9000]))
+            n1 = int(rng.choice([1, 2, 3, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1000, 1000, 1023, 1025, 4000, 8000, 9000, 16384, 16385, 20000]))
             n2 = int(rng.choice([1, 2, 7, 31, 33, 64, 65, 129, 500, 1000, 1000, 1024, 4000, 8000]))
             if n1 * n2 > 40_000_000:
                 n2 = 1000

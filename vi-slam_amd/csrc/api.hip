@@ -456,10 +456,11 @@ int vis_ensure_pin(vis_ctx* ctx, size_t bytes) {
     return VIS_OK;
 }
 // diagnostics: out[0] = kernel launches of this process, out[1] = times a single-frame entry point of this context blocked on the device,
-// out[2] = asynchronous copies it queued (bench.py `single_frame_api`: launches and round trips per frame)
+// out[2] = asynchronous copies it queued (bench.py `single_frame_api`: launches and round trips per frame), out[3] = largest undecided
+// list of any pose call of this context (k_hyp_score)
 extern "C" int vis_debug_counters(vis_ctx* ctx, unsigned long long out[4]) {
     if (!ctx || !out) return VIS_E_INVALID;
-    out[0] = vis_g_launches.load(std::memory_order_relaxed); out[1] = ctx->n_host_waits; out[2] = ctx->n_copies; out[3] = 0;
+    out[0] = vis_g_launches.load(std::memory_order_relaxed); out[1] = ctx->n_host_waits; out[2] = ctx->n_copies; out[3] = ctx->undecided_max;
     return VIS_OK;
 }
 
@@ -970,6 +971,7 @@ static int pose_host(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m, 
     if (rc) return rc;
     { float a = 0; if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[6], ctx->ev[7])) ctx->tm.ms_pose = a; }
     std::memcpy(out, h_pose, sizeof(PoseOut));
+    if (out->undecided_max > 0) ctx->undecided_max = std::max(ctx->undecided_max, (unsigned long long)out->undecided_max);
     if (h_mask) std::memcpy(mask, h_mask, (size_t)m);
     return VIS_OK;
 }

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void k_knn2(const uint8_t* __restrict__ desc, 
 // the bit patterns: non-negative floats order like integers) per distance instead of 19.
 // Columns (lane & 31) = the 32 descriptors whose neighbours this wave tracks (B operand, in registers); rows = the swept set,
 // staged through LDS 32 descriptors at a time (row stride 144 B: conflict-free ds_read_b128).  Results are bit-identical to
-// k_knn2 (same key order): tests/test_match_gpu.py.
+// k_knn2 (same key order): tests/test_limits_gpu.py test_mfma_and_popcount_matchers_agree runs both on the same 16384 x 16384 rows.
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v16f __attribute__((ext_vector_type(16)));

@@ -199,7 +199,8 @@ struct PoseParams {
 
 // rstate: [0] niters, [1] maxGood, [2] best hypothesis index (-1 none), [3] best model, [4] next iteration to scan,
 //         [5] special (1 = M==5 shortcut, 2 = M<5), [6] M, [7] iterations run, [8] candidate models scored (all chunks),
-//         [9..12] cheirality votes of the four (R, t) candidates, [14] finished workgroups (k_pose_final)
+//         [9..12] cheirality votes of the four (R, t) candidates, [13] largest undecided list of any sub-item (k_hyp_score's
+//         many-correspondences form; diagnostic, handed out as vis_pose_result::undecided_max), [14] finished workgroups (k_pose_final)
 #define RS VIS_RSTATE_WORDS
 
 // getSubset (ptsetreg.cpp): 5 distinct indices in [0,M), redraw on duplicates, from the running cv::RNG
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(256) void k_pose_prep(PoseParams P, const float* __
     int32_t* sm = samples + (size_t)pair * P.max_iters * 5;
     if (tid == 0) {
         rs[1] = 0; rs[2] = -1; rs[3] = 0; rs[4] = 0; rs[6] = M; rs[7] = 0; rs[8] = 0;
-        for (int k = 9; k < 15; k++) rs[k] = 0;
+        for (int k = 9; k < 15; k++) rs[k] = 0;                  // (votes, the undecided-list mark [13], the ticket)
         if (M < 5) { rs[0] = 0; rs[5] = 2; }
         else if (M == 5) { rs[0] = 1; rs[5] = 1; for (int k = 0; k < 5; k++) sm[k] = k; }
         else { rs[0] = max(P.max_iters, 1); rs[5] = 0; }
@@ -1194,6 +1195,7 @@ __global__ __launch_bounds__(256) void k_hyp_score(PoseParams P, int h0, int h_e
             }
             __syncthreads();
             const int na = sNamb;
+            if (tid == 0 && na > 0) atomicMax(rstate + (size_t)pair * RS + 13, na);      // diagnostic: a maximum is order independent
             if (__builtin_expect(na <= AMB_CAP, 1)) {
                 for (int a = tid; a < na; a += 256) {
                     const uint32_t code = sAmb[a];
@@ -1203,8 +1205,8 @@ __global__ __launch_bounds__(256) void k_hyp_score(PoseParams P, int h0, int h_e
                         atomicAdd(&sGood[t], 1);
                 }
             } else {
-                // the list overflowed (not seen: it holds 2 % of the decisions of 67 models x 3100 points, about 0.1 % are
-                // undecided): every count of the sub-item again, in double
+                // the list overflowed (it holds 2 % of the decisions of 67 models x 3100 points; tests/test_limits_gpu.py measures how many
+                // stay undecided): every count of the sub-item again, in double
                 __syncthreads();
                 for (int t = tid; t < T; t += 256) sGood[t] = 0;
                 __syncthreads();
@@ -1483,7 +1485,7 @@ __global__ __launch_bounds__(256) void k_pose_final(PoseParams P, const double* 
             for (int i = 0; i < 9; i++) { o.E[i] = sE[i]; o.R[i] = 0; }
             o.t[0] = o.t[1] = o.t[2] = 0;
             o.n_inliers = E_in ? 0 : (have ? (rs[5] == 1 ? 5 : rs[1]) : 0);
-            o.iters_run = rs[7]; o.n_points = M; o.n_pose_good = 0; o.n_models = rs[8]; o.reserved_ = 0;
+            o.iters_run = rs[7]; o.n_points = M; o.n_pose_good = 0; o.n_models = rs[8]; o.undecided_max = rs[13];
             if (do_pose && have) {
                 const int* g = sgood;
                 int sel;

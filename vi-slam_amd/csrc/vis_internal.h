@@ -37,7 +37,7 @@ struct LevelInfo {
 };
 
 // device-resident compact kNN entry: key = (dist << 16) | trainIdx, 0xFFFFFFFF = none
-typedef vis_pose_result PoseOut;       // E, R, t (double) + n_inliers, n_pose_good, iters_run, n_points, n_models
+typedef vis_pose_result PoseOut;       // E, R, t (double) + n_inliers, n_pose_good, iters_run, n_points, n_models, undecided_max
 
 // The pending readers of one buffer set of the batch path (sets used in turn: the writer of a set waits for the readers of its last use).
 // Per stream, one slot per stream of a context (A, U, M, P): the event behind the LAST reader queued there, which stands for every earlier
@@ -196,6 +196,7 @@ struct vis_ctx {
     int stage_live = 0;                      // HostStage objects alive on this context: vis_ensure_pin refuses to replace the block under one (VIS_E_STATE)
     // diagnostics of the single-frame path (vis_debug_counters): times the host blocked on the device / copies queued since the context was made
     unsigned long long n_host_waits = 0, n_copies = 0;
+    unsigned long long undecided_max = 0;    // largest vis_pose_result::undecided_max a pose call of this context downloaded
     int slot_valid[VIS_NSLOTS];
     // cv::RNG sample tables for M in [6, sample_max_m], built on the host for (seed, max_iters)
     int32_t* d_sample_table = nullptr; int sample_max_m = 0; int sample_iters = 0; unsigned long long sample_seed = 0;

@@ -86,11 +86,11 @@ assert C.sizeof(TrackResult) == 32
 
 class PoseResult(C.Structure):
     _fields_ = [("E", C.c_double * 9), ("R", C.c_double * 9), ("t", C.c_double * 3), ("n_inliers", C.c_int32), ("n_pose_good", C.c_int32),
-                ("iters_run", C.c_int32), ("n_points", C.c_int32), ("n_models", C.c_int32), ("reserved_", C.c_int32)]
+                ("iters_run", C.c_int32), ("n_points", C.c_int32), ("n_models", C.c_int32), ("undecided_max", C.c_int32)]
 
 
 POSE_RESULT_DTYPE = np.dtype([("E", "<f8", (9,)), ("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n_inliers", "<i4"), ("n_pose_good", "<i4"),
-                              ("iters_run", "<i4"), ("n_points", "<i4"), ("n_models", "<i4"), ("reserved_", "<i4")])
+                              ("iters_run", "<i4"), ("n_points", "<i4"), ("n_models", "<i4"), ("undecided_max", "<i4")])
 assert POSE_RESULT_DTYPE.itemsize == C.sizeof(PoseResult) == 192
 
 
@@ -819,6 +819,12 @@ class Context:
         out = (C.c_ulonglong * 4)()
         self._chk(lib.vis_debug_counters(self._h, out), "vis_debug_counters")
         return int(out[0]), int(out[1]), int(out[2])
+
+    def undecided_max(self):
+        """largest undecided list (vis_pose_result.undecided_max) of any essential_ransac call of this context so far"""
+        out = (C.c_ulonglong * 4)()
+        self._chk(lib.vis_debug_counters(self._h, out), "vis_debug_counters")
+        return int(out[3])
 
     def batch_inlier_mask(self, frame, cap=16384):
         mask = np.zeros(cap, np.uint8)
