@@ -290,6 +290,29 @@ int  vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_
 int  vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
                      const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
                      const vis_se3f* d_init, vis_align_result* d_out);
+/* The weighting of the Gauss-Newton step (src/VISystem.cpp:1342-1344): the reference wrote two, IdentityWeights (live) and
+ * TukeyFunctionWeights (:1797-1870, commented out at the call site).  Context state like vis_params, IDENTITY by default; read when
+ * an alignment is enqueued (vis_estimate_pose_features, vis_align_batch, vis_batch_align, vis_batch_track -- the pair against the
+ * carried keyframe included) and passed to it by value: a later vis_set_align_weights does not touch work already queued.
+ * Per iteration, over the n valid residuals r (integers -255 ... 255):  med = MedianMat(r);  MAD = mad_scale * MedianMat(|r - med|),
+ * 0 -> 1;  x = r / MAD;  w = (1 - x^2 / b^2)^2 for |x| <= b, else 0.  The step solves (WJ)^T (WJ) delta = -(WJ)^T (W r) and the error
+ * is mean(r * W r) over all n (weight-0 residuals count in n), :1346-1409.  MedianMat takes the first bin whose running count exceeds
+ * n / 2 -- after converting to CV_8U, which turns every negative residual into 0 and every deviation above 255 into 255:
+ * VIS_W_TUKEY keeps that, VIS_W_TUKEY_SIGNED takes both medians over the values themselves (cf. VIS_SYM_*). */
+enum { VIS_W_IDENTITY = 0,       /* IdentityWeights, :1343 */
+       VIS_W_TUKEY = 1,          /* TukeyFunctionWeights exactly as written, MedianMat's 8-bit saturation included */
+       VIS_W_TUKEY_SIGNED = 2 }; /* the same with medians over the signed residuals (what MedianMat evidently meant) */
+typedef struct vis_align_weights {
+    int32_t mode;                /* VIS_W_* */
+    float   tukey_b;             /* 4.6851f :1800 */
+    float   mad_scale;           /* 1.4826f :1831 */
+    int32_t reserved_;           /* 0 */
+} vis_align_weights;
+void vis_default_align_weights(vis_align_weights* aw);
+/* aw == NULL: the defaults.  VIS_E_INVALID (the setting stays as it was): mode outside VIS_W_*, tukey_b or mad_scale not finite and > 0,
+ * reserved_ != 0, ctx == NULL. */
+int  vis_set_align_weights(vis_ctx* ctx, const vis_align_weights* aw);
+int  vis_get_align_weights(vis_ctx* ctx, vis_align_weights* aw);
 
 /* ---- frame ingest (src/ImageReader.cpp) ------------------------------------- */
 /* ImageReader::searchImages (src/ImageReader.cpp:49-74): the .pgm / .raw / .png files of `dir` in byte order, names

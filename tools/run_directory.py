@@ -13,6 +13,8 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --track out.csv: the camera trajectory as the reference's GPU main writes it (src/main_vi_slamGPU.cpp:137-144, its first seven
              columns): one row per frame, positionCam x, y, z, qOrientationCam x, y, z, w -- vis_batch_track after every batch (the
              GPU main's keyframe rule, keyframe_min_points = 1; alignment with the intrinsics of --K fx,fy,cx,cy), from the identity.
+  --weights tukey|tukey-signed: with --track, the alignment under the reference's TukeyFunctionWeights (vis_set_align_weights:
+             VIS_W_TUKEY as written, VIS_W_TUKEY_SIGNED with signed medians) instead of IdentityWeights.
   --points out.csv: the map points of every frame's pair (vis_batch_triangulate behind every batch, default thresholds): one row per
              correspondence of a pair with a pose -- frame index, timestamp, correspondence index, X, Y, Z (first camera's frame, units
              of the baseline), reproj_px, parallax_px, flags (VIS_MP_*); the JSON line carries the totals.
@@ -69,6 +71,8 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=0.0)
     ap.add_argument("--raw-size", default=None, help="WxH of headerless .raw files")
     ap.add_argument("--track", default=None, metavar="CSV", help="write the per-frame camera pose (positionCam, qOrientationCam) here")
+    ap.add_argument("--weights", choices=("identity", "tukey", "tukey-signed"), default="identity",
+                    help="--track: the weighting of the alignment's Gauss-Newton step (vis_set_align_weights); identity = the reference's live call")
     ap.add_argument("--points", default=None, metavar="CSV", help="write the triangulated map points of every pair here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
@@ -120,6 +124,10 @@ def main():
     ctx = vislam.Context(0, p)
     B = min(a.batch, len(paths))
     ctx.batch_plan(w, h, stride, B)
+    if a.weights != "identity":
+        aw = vislam.default_align_weights()
+        aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
+        ctx.set_align_weights(aw)
     if a.points:
         row_cap = int(np.floor(np.sqrt(p.n_cells))) ** 2      # the grid-filtered good matches of a pair
         d_mp = torch.empty(B * row_cap * vislam.MAP_POINT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")

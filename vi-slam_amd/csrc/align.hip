@@ -21,6 +21,7 @@
 // bit-identical to it (tests/test_align_gpu.py).
 #include "vis_internal.h"
 #include <cfloat>
+#include <cmath>
 #include <cstring>
 
 #define DEV __device__ __forceinline__
@@ -46,6 +47,7 @@ struct AlignArgs {
     // vis_batch_track: image 1 of a pair whose previous frame is VIS_KF_CARRIED (an earlier launch) is the plan's keyframe snapshot,
     // one frame in the layout of a gradient set with a dense level 0 (track.hip); nullptr: such a pair is skipped like any link < 0
     const uint8_t* c_gray; const int16_t* c_gx; const int16_t* c_gy;
+    int wmode; float tukey_b, mad_scale;                  // vis_align_weights of the context when the call was made (k_align<*, true> reads them)
 };
 
 #include "se3_core.h"
@@ -113,9 +115,41 @@ DEV unsigned long long wave_tree_sum_u64(unsigned long long v) {
     return v;
 }
 
+// k_align<*, true>, statistics pass: WarpFunctionSE3 and the validity tests of one candidate exactly as the accumulation loop of
+// k_align runs them (the same operations in the same order: both passes of an iteration must see the same residual list) -> the
+// offsets of its two intensities; false = the candidate is skipped.  M = rows 0..2 of pose.matrix().
+template <bool GEN>
+DEV bool warp_offsets(const AlignLevel& V, const uint32_t* plist, int i, const double M[12], int rs1, size_t& o1, size_t& o2) {
+    float x1, y1, z1, w1;
+    if (GEN) { const uint32_t pw = plist[i]; x1 = (float)(pw & 0xFFFFu); y1 = (float)(pw >> 16); z1 = 1.f; w1 = 1.f; }
+    else { const float4 c = reinterpret_cast<const float4*>(V.cand)[i]; x1 = c.x; y1 = c.y; z1 = c.z; w1 = c.w; }
+    const float X = ((x1 - V.cx) * V.invfx) * z1, Y = ((y1 - V.cy) * V.invfy) * z1;
+    const float P0 = (float)(((M[0] * (double)X + M[1] * (double)Y) + M[2] * (double)z1) + M[3] * (double)w1);
+    const float P1 = (float)(((M[4] * (double)X + M[5] * (double)Y) + M[6] * (double)z1) + M[7] * (double)w1);
+    const float P2 = (float)(((M[8] * (double)X + M[9] * (double)Y) + M[10] * (double)z1) + M[11] * (double)w1);
+    const float P3 = (float)(((0.0 * (double)X + 0.0 * (double)Y) + 0.0 * (double)z1) + 1.0 * (double)w1);
+    float x2 = P0 * V.fx; x2 = x2 / P2; x2 = x2 + V.cx;
+    float y2 = P1 * V.fy; y2 = y2 / P2; y2 = y2 + V.cy;
+    x2 = x2 * P3; y2 = y2 * P3;
+    const int ix1 = (int)x1, iy1 = (int)y1;
+    if (!((y2 > 0 && y2 < V.arows && x2 > 0 && x2 < V.acols) && (P2 != 0))) return false;
+    if (ix1 < 0 || ix1 >= V.cols || iy1 < 0 || iy1 >= V.rows) return false;
+    int rx = (int)roundf(x2), ry = (int)roundf(y2);
+    if (rx > V.acols - 1) rx = V.acols - 1;
+    if (ry > V.arows - 1) ry = V.arows - 1;
+    o1 = (size_t)iy1 * rs1 + ix1; o2 = (size_t)ry * V.rowstride + rx;
+    return true;
+}
+
+#define AL_WBINS 512                     // residuals are intensity2 - intensity1 = -255 ... 255: bin r + 255 (bin 511 stays empty)
+
 // One workgroup per frame pair; GEN = candidate pixels generated from the matched keypoints (batched path),
 // otherwise read from an explicit (x, y, z, w) list (single-pair entry point: Frame::candidatePoints as the caller holds it).
-template <bool GEN>
+// WT = VISystem::TukeyFunctionWeights (src/VISystem.cpp:1797-1870) instead of IdentityWeights in the Gauss-Newton step
+// (:1342-1409): every iteration first counts the residuals of its candidates (one warp pass, a 511-bin histogram per wave), takes
+// both medians of MedianAbsoluteDeviation from the counts, and tabulates the weight of every possible residual; the accumulation
+// pass that follows is the identity one with a table lookup per residual.  The identity instantiations hold none of this.
+template <bool GEN, bool WT>
 __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint32_t* plist = reinterpret_cast<uint32_t*>(smem);                 // GEN: packed candidate pixels of the level
@@ -201,10 +235,80 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
             const double m00 = R[0], m01 = R[1], m02 = R[2], m03 = pose.t[0];
             const double m10 = R[3], m11 = R[4], m12 = R[5], m13 = pose.t[1];
             const double m20 = R[6], m21 = R[7], m22 = R[8], m23 = pose.t[2];
-            double S[27];
+            constexpr int NS = WT ? 28 : 27;                                        // WT: + the weighted squared error (not a sum of integers any more)
+            double S[NS];
 #pragma unroll
-            for (int s = 0; s < 27; s++) S[s] = 0.0;
+            for (int s = 0; s < NS; s++) S[s] = 0.0;
             unsigned long long sumsq = 0; int cnt = 0;
+            [[maybe_unused]] const float* wtab = nullptr;
+            if constexpr (WT) {
+                __shared__ int s_hist[4][AL_WBINS];                                 // one histogram per wave: residuals pile up around 0
+                __shared__ int s_cum[AL_WBINS];                                     // s_cum[j] = residuals <= j - 255
+                __shared__ float s_wtab[AL_WBINS];
+                __shared__ int s_wsum[4], s_stat[2];
+                for (int j = tid; j < 4 * AL_WBINS; j += AL_THREADS) (&s_hist[0][0])[j] = 0;
+                if (tid == 0) { s_stat[0] = 0; s_stat[1] = 0; }
+                __syncthreads();
+                const double M[12] = {m00, m01, m02, m03, m10, m11, m12, m13, m20, m21, m22, m23};
+#pragma unroll 1
+                for (int i0 = tid; i0 < N; i0 += 4 * AL_THREADS) {                  // four candidates per round, like the accumulation
+                    bool ok[4]; int a1[4], a2[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        const int i = i0 + u * AL_THREADS;
+                        size_t o1 = 0, o2 = 0;
+                        ok[u] = i < N && warp_offsets<GEN>(V, plist, i, M, rs1, o1, o2);
+                        a1[u] = I1[o1]; a2[u] = I2[o2];
+                    }
+#pragma unroll
+                    for (int u = 0; u < 4; u++) if (ok[u]) atomicAdd(&s_hist[wv][a2[u] - a1[u] + 255], 1);
+                }
+                __syncthreads();
+                {   // the four histograms added and their running count (thread = two bins; wave scan + the wave totals)
+                    const int h0 = (s_hist[0][2 * tid] + s_hist[1][2 * tid]) + (s_hist[2][2 * tid] + s_hist[3][2 * tid]);
+                    const int h1 = (s_hist[0][2 * tid + 1] + s_hist[1][2 * tid + 1]) + (s_hist[2][2 * tid + 1] + s_hist[3][2 * tid + 1]);
+                    int v = h0 + h1;
+#pragma unroll
+                    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
+                    if (lane == 63) s_wsum[wv] = v;
+                    __syncthreads();
+                    for (int w = 0; w < wv; w++) v += s_wsum[w];
+                    s_cum[2 * tid] = v - h1; s_cum[2 * tid + 1] = v;
+                    __syncthreads();
+                }
+                // MedianMat (:1846-1870): the first bin whose running count exceeds (float)(n / 2) -- counts are < 2^24, so the float
+                // comparison is the integer one.  The running count rises with the bin: exactly one bin sees the crossing.
+                const int half = s_cum[AL_WBINS - 1] / 2;
+                const bool as_written = G.wmode == VIS_W_TUKEY;                     // CV_8U saturation of both MedianMat calls
+#pragma unroll
+                for (int j = 2 * tid; j < 2 * tid + 2; j++)
+                    if (s_cum[j] > half && (j == 0 || s_cum[j - 1] <= half)) s_stat[0] = j - 255;
+                __syncthreads();
+                // as written every negative residual counts in bin 0: the median of max(r, 0) = max(signed median, 0)
+                const int med = as_written ? max(s_stat[0], 0) : s_stat[0];
+                // |r - med| <= d  <=>  med - d <= r <= med + d: the running count of the deviations from the one of the residuals
+                auto dev_count = [&](int d) {
+                    const int hi = min(med + d, 255) + 255, lo = max(med - d, -255) + 255;
+                    return s_cum[hi] - (lo > 0 ? s_cum[lo - 1] : 0);
+                };
+#pragma unroll
+                for (int d = 2 * tid; d < 2 * tid + 2; d++)
+                    if (d <= 510 && dev_count(d) > half && (d == 0 || dev_count(d - 1) <= half)) s_stat[1] = d;
+                __syncthreads();
+                const int dev = as_written ? min(s_stat[1], 255) : s_stat[1];       // (deviations of 256 ... 510 saturate to 255)
+                float MAD = G.mad_scale * (float)dev;
+                if (MAD == 0) MAD = 1;
+                const float b = G.tukey_b;
+                const float inv_MAD = (float)(1.0 / MAD), inv_b2 = (float)(1.0 / (b * b));
+                for (int j = tid; j < AL_WBINS; j += AL_THREADS) {
+                    const float x = (float)(j - 255) * inv_MAD;
+                    float w = 0.f;
+                    if (fabsf(x) <= b) { const float t = (float)(1.0 - (double)((x * x) * inv_b2)); w = t * t; }
+                    s_wtab[j] = w;
+                }
+                __syncthreads();
+                wtab = s_wtab;
+            }
             // Four candidates per thread per round: first the warp of all four and their image / gradient loads (clamped
             // addresses for the ones that will be skipped), then the accumulation in the original order i, i + T, i + 2T,
             // i + 3T -- the per-thread sums see the same operations in the same order, but a round costs one memory round
@@ -268,28 +372,38 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
                     double J[6];
 #pragma unroll
                     for (int c = 0; c < 6; c++) J[c] = (double)(float)((double)jl0 * (double)Jw0[c] + (double)jl1 * (double)Jw1[c]);
+                    float rhs = resf;
+                    if constexpr (WT) {                                             // W enters the row and the residual (:1346-1409)
+                        const float wgt = wtab[ri + 255];
+#pragma unroll
+                        for (int c = 0; c < 6; c++) J[c] = (double)(wgt * (float)J[c]);
+                        rhs = resf * wgt;
+                        S[27] += (double)resf * (double)rhs;
+                    }
                     int s = 0;
 #pragma unroll
                     for (int a = 0; a < 6; a++)
 #pragma unroll
                         for (int b = a; b < 6; b++) S[s++] += J[a] * J[b];
 #pragma unroll
-                    for (int a = 0; a < 6; a++) S[21 + a] += J[a] * (double)resf;
-                    sumsq += (unsigned long long)(ri * ri);
+                    for (int a = 0; a < 6; a++) S[21 + a] += J[a] * (double)rhs;
+                    if constexpr (!WT) sumsq += (unsigned long long)(ri * ri);
                     cnt++;
                 }
             }
             // reduction in the oracle's order: inside a wave strides 32..1, then (W0 + W1) + (W2 + W3)
 #pragma unroll
-            for (int s = 0; s < 27; s++) { const double v = wave_tree_sum(S[s]); if (lane == 0) s_red[wv][s] = v; }
-            { const unsigned long long q = wave_tree_sum_u64(sumsq); if (lane == 0) s_sq[wv] = q; }
+            for (int s = 0; s < NS; s++) { const double v = wave_tree_sum(S[s]); if (lane == 0) s_red[wv][s] = v; }
+            if constexpr (!WT) { const unsigned long long q = wave_tree_sum_u64(sumsq); if (lane == 0) s_sq[wv] = q; }
             { int c = cnt; for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64); if (lane == 0) s_cnt[wv] = c; }
             __syncthreads();
             nres = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
-            const unsigned long long tsq = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
+            unsigned long long tsq = 0;
+            if constexpr (!WT) tsq = (s_sq[0] + s_sq[1]) + (s_sq[2] + s_sq[3]);
             if (nres == 0) { __syncthreads(); break; }
             const float inv_num = (float)(1.0 / nres);
-            error = (float)((double)inv_num * (double)tsq);
+            if constexpr (WT) error = (float)((double)inv_num * ((s_red[0][27] + s_red[1][27]) + (s_red[2][27] + s_red[3][27])));
+            else error = (float)((double)inv_num * (double)tsq);
             if (k == 0) initial_error = error;
             if (error >= last_error || k == G.max_it - 1 || fabsf(error - last_error) < G.eps) { __syncthreads(); break; }
             last_error = error;
@@ -366,6 +480,30 @@ static void fill_level_intrinsics(const vis_align_params& ap, AlignArgs& G) {
     G.first = ap.first_level; G.last = ap.last_level; G.max_it = ap.max_iterations; G.eps = ap.epsilon; G.zf = ap.z_factor;
 }
 
+// ---- vis_align_weights: context state, read where an alignment is enqueued and passed to the kernel by value
+extern "C" void vis_default_align_weights(vis_align_weights* aw) {
+    if (!aw) return;
+    aw->mode = VIS_W_IDENTITY; aw->tukey_b = 4.6851f; aw->mad_scale = 1.4826f; aw->reserved_ = 0;   // src/VISystem.cpp:1343,1800,1831
+}
+extern "C" int vis_set_align_weights(vis_ctx* ctx, const vis_align_weights* aw) {
+    if (!ctx) return VIS_E_INVALID;
+    vis_align_weights v;
+    if (aw) v = *aw; else vis_default_align_weights(&v);
+    if (v.mode < VIS_W_IDENTITY || v.mode > VIS_W_TUKEY_SIGNED) { ctx->err = "vis_set_align_weights: mode is VIS_W_IDENTITY, VIS_W_TUKEY or VIS_W_TUKEY_SIGNED"; return VIS_E_INVALID; }
+    if (!std::isfinite(v.tukey_b) || !(v.tukey_b > 0) || !std::isfinite(v.mad_scale) || !(v.mad_scale > 0)) {
+        ctx->err = "vis_set_align_weights: tukey_b and mad_scale must be finite and > 0"; return VIS_E_INVALID;
+    }
+    if (v.reserved_ != 0) { ctx->err = "vis_set_align_weights: reserved_ must be 0"; return VIS_E_INVALID; }
+    ctx->aw = v;
+    return VIS_OK;
+}
+extern "C" int vis_get_align_weights(vis_ctx* ctx, vis_align_weights* aw) {
+    if (!ctx || !aw) return VIS_E_INVALID;
+    *aw = ctx->aw;
+    return VIS_OK;
+}
+static void fill_weights(const vis_ctx* ctx, AlignArgs& G) { G.wmode = ctx->aw.mode; G.tukey_b = ctx->aw.tukey_b; G.mad_scale = ctx->aw.mad_scale; }
+
 extern "C" int vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* ap, int w, int h,
                                           const uint8_t* const gray1[5], const uint8_t* const gray2[5],
                                           const int16_t* const gx1[5], const int16_t* const gy1[5],
@@ -412,7 +550,9 @@ extern "C" int vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* 
     hs.flush_ups();
     vis_align_result* d_out = cv.take<vis_align_result>(1);
     G.init = d_init; G.out = d_out; G.f1_off = 0; G.f2_off = 0; G.out_off = 0;
-    hipLaunchKernelGGL(k_align<false>, dim3(1), dim3(AL_THREADS), 0, st, G);
+    fill_weights(ctx, G);
+    if (G.wmode == VIS_W_IDENTITY) hipLaunchKernelGGL((k_align<false, false>), dim3(1), dim3(AL_THREADS), 0, st, G);
+    else hipLaunchKernelGGL((k_align<false, true>), dim3(1), dim3(AL_THREADS), 0, st, G);
     HIPCHK(ctx, hipGetLastError());
     const void* h_out = hs.down(d_out, sizeof(vis_align_result));
     rc = hs.wait();
@@ -472,8 +612,14 @@ int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d
     }
     const int used = std::min(max_pts, AL_MAXKP);
     const size_t lds = (size_t)used * 121 * 4;                                       // largest patch: (2*5+1)^2 pixels per keypoint
-    if (lds > 65536 - 4096) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_align<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_align<true>, dim3(pairs), dim3(AL_THREADS), lds, st, G);
+    fill_weights(ctx, G);
+    if (G.wmode == VIS_W_IDENTITY) {
+        if (lds > 65536 - 4096) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_align<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_align<true, false>), dim3(pairs), dim3(AL_THREADS), lds, st, G);
+    } else {                                                                          // (+ 12.3 KB of histograms and tables beside the list: 109 KB of 160)
+        if (lds > 65536 - 16384) HIPCHK(ctx, hipFuncSetAttribute((const void*)k_align<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((k_align<true, true>), dim3(pairs), dim3(AL_THREADS), lds, st, G);
+    }
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

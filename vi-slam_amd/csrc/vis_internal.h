@@ -182,6 +182,7 @@ struct vis_ctx {
     bool pose_attr_set = false;              // > 64 KiB LDS opt-in of the RANSAC solver kernels done on this context's device
     bool pose_grids_set = false; int pose_grid[4] = {0, 0, 0, 0};   // resident-workgroup grids of the work-list pose kernels on this device (pose.hip pose_grids)
     vis_params p;
+    vis_align_weights aw = {VIS_W_IDENTITY, 4.6851f, 1.4826f, 0};   // vis_set_align_weights: read where an alignment is enqueued
     std::string err;
     Plan* single = nullptr;
     Plan* batch = nullptr;

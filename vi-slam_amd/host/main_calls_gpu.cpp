@@ -46,7 +46,7 @@ int main( int argc, char** argv ){
         std::printf("\n");
         return 0;
     }
-    if (argc < 4) { cout << "usage: vislam_main_gpu <calibration.xml> <frames> <output.csv> [parallax]" << endl; return 2; }
+    if (argc < 4) { cout << "usage: vislam_main_gpu <calibration.xml> <frames> <output.csv> [parallax] [identity|tukey|tukey-signed]" << endl; return 2; }
     // BEGIN verbatim src/main_vi_slamGPU.cpp:40-48
     cout << "===================================================" << endl;
     int n_cuda_devices = cuda::getCudaEnabledDeviceCount();
@@ -75,6 +75,12 @@ int main( int argc, char** argv ){
     Quaterniond qinit = toQuaternion(Data.gtRPY[0].x, Data.gtRPY[0].y, Data.gtRPY[0].z);
     // END verbatim
     (void)qinit;
+    if (argc > 5) {                                                                    // the weighting the reference keeps behind a comment (src/VISystem.cpp:1344)
+        const string wname = argv[5];
+        if (wname == "tukey") visystem.alignmentWeights.mode = VIS_W_TUKEY;
+        else if (wname == "tukey-signed") visystem.alignmentWeights.mode = VIS_W_TUKEY_SIGNED;
+        else if (wname != "identity") { cout << "unknown weighting " << wname << endl; return 2; }
+    }
     {
         const float ini7[7] = {visystem.final_poseCam.v.qx, visystem.final_poseCam.v.qy, visystem.final_poseCam.v.qz, visystem.final_poseCam.v.qw,
                                visystem.final_poseCam.v.tx, visystem.final_poseCam.v.ty, visystem.final_poseCam.v.tz};

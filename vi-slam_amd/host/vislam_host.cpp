@@ -625,7 +625,8 @@ void VISystem::EstimatePoseFeatures(Frame* _previous_frame, Frame* _current_fram
     }
     const float sx = TranslationResidual.at<float>(0, 0), sy = TranslationResidual.at<float>(1, 0), sz = TranslationResidual.at<float>(2, 0);
     const SE3 current_pose(Matx33f::eye(), SE3::Point(-sx, -sy, -sz));                 // :1159
-    int rc = vis_estimate_pose_features(VisDevice::get(), &ap, w_[0], h_[0], g1, g2, gx, gy, cd, n, &current_pose.v, &lastAlignment);
+    int rc = vis_set_align_weights(VisDevice::get(), &alignmentWeights);              // :1343-1344
+    if (!rc) rc = vis_estimate_pose_features(VisDevice::get(), &ap, w_[0], h_[0], g1, g2, gx, gy, cd, n, &current_pose.v, &lastAlignment);
     if (rc) VisDevice::fail(rc, "EstimatePoseFeatures");
     _previous_frame->rigid_transformation_.v = lastAlignment.pose;                     // :1445
 }

@@ -258,6 +258,9 @@ public:
     Point3f translationResEst;
     // results of the last pose estimates
     vis_align_result lastAlignment;                                                // EstimatePoseFeatures
+    // the weighting of EstimatePoseFeatures' Gauss-Newton step, :1342-1344: IdentityWeights as the reference calls it, or the
+    // TukeyFunctionWeights it keeps behind a comment (VIS_W_TUKEY / VIS_W_TUKEY_SIGNED); set on the device context before every call
+    vis_align_weights alignmentWeights = {VIS_W_IDENTITY, 4.6851f, 1.4826f, 0};
     float ransacR[9], ransacT[3]; int lastInliers = 0, lastPoseGood = 0;            // EstimatePoseFeaturesRansac
     std::vector<Point3f> mapPoints; std::vector<uchar> mapPointFlags;               // Triangulate: (float)X and the VIS_MP_* flags per point
     vis_tri_summary lastTriangulation = {0, 0, 0, 0.f};

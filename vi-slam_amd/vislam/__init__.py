@@ -76,6 +76,15 @@ class AlignResult(C.Structure):
                 ("iterations", C.c_int32 * 5), ("n_residuals", C.c_int32 * 5)]
 
 
+class AlignWeights(C.Structure):
+    """vis_align_weights: the weighting of the alignment's Gauss-Newton step (vis_default_align_weights: W_IDENTITY, 4.6851, 1.4826)"""
+    _fields_ = [("mode", C.c_int32), ("tukey_b", C.c_float), ("mad_scale", C.c_float), ("reserved_", C.c_int32)]
+
+
+assert C.sizeof(AlignWeights) == 16
+W_IDENTITY, W_TUKEY, W_TUKEY_SIGNED = 0, 1, 2
+
+
 class TrackResult(C.Structure):
     """vis_track_result: final_poseCam after a frame (VISystem::Track) and the pair whose residual was composed for it"""
     _fields_ = [("pose", Se3f), ("composed", C.c_int32)]
@@ -152,6 +161,7 @@ ABI_SYMBOLS = [
     "vis_optimal_new_camera_matrix", "vis_undistort_rectify_map", "vis_rectify_create", "vis_rectify_destroy", "vis_rectify_maps",
     "vis_rectify_batch", "vis_rectify_host",
     "vis_default_tri_params", "vis_triangulate", "vis_batch_triangulate",
+    "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
 ]
 
 
@@ -217,6 +227,11 @@ def _load():
         lib.vis_default_tri_params.restype = None
         lib.vis_triangulate.argtypes = [vp, C.POINTER(TriParams), vp, vp, vp, vp, ci, vp, vp, vp, C.POINTER(TriSummary)]
         lib.vis_batch_triangulate.argtypes = [vp, C.POINTER(TriParams), ci, ci, vp, vp, vp]
+    if hasattr(lib, "vis_set_align_weights"):           # (absent from older A/B builds)
+        lib.vis_default_align_weights.argtypes = [C.POINTER(AlignWeights)]
+        lib.vis_default_align_weights.restype = None
+        lib.vis_set_align_weights.argtypes = [vp, C.POINTER(AlignWeights)]
+        lib.vis_get_align_weights.argtypes = [vp, C.POINTER(AlignWeights)]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -295,6 +310,12 @@ def default_align_params():
     ap = AlignParams()
     lib.vis_default_align_params(C.byref(ap))
     return ap
+
+
+def default_align_weights():
+    aw = AlignWeights()
+    lib.vis_default_align_weights(C.byref(aw))
+    return aw
 
 
 def default_tri_params():
@@ -519,6 +540,15 @@ class Context:
     def set_params(self, p):
         self._chk(lib.vis_set_params(self._h, C.byref(p)), "vis_set_params")
         self.params = p.copy()
+
+    def set_align_weights(self, aw=None):
+        """the weighting every alignment enqueued from now on takes (an AlignWeights; None = the defaults: identity)"""
+        self._chk(lib.vis_set_align_weights(self._h, None if aw is None else C.byref(aw)), "vis_set_align_weights")
+
+    def get_align_weights(self):
+        aw = AlignWeights()
+        self._chk(lib.vis_get_align_weights(self._h, C.byref(aw)), "vis_get_align_weights")
+        return aw
 
     def synth_frames_device(self, d_canvas_ptr, dim, seed, t0, n, w, h, stride, d_out_ptr, parallax=False):
         """frames t0 .. t0+n-1 of the synthetic stream straight into device memory (asynchronous)"""
