@@ -393,6 +393,13 @@ int  vis_batch_get_pose(vis_ctx* ctx, int frame, double E[9], double R[9], doubl
  * device, out[2] = asynchronous copies those entry points queued (bench.py `single_frame_api`: per-frame differences), out[3] = the largest
  * vis_pose_result::undecided_max of any vis_essential_ransac call of this context. */
 int  vis_debug_counters(vis_ctx* ctx, unsigned long long out[4]);
+/* diagnostic (tests read the pyramid with it; no product path needs it): copy level `level` >= 1 of frame `frame` of the last
+ * detection -- of the single-frame plan (batch == 0: vis_orb_detect_compute, frame 0) or of the batch plan (batch != 0: the last
+ * vis_batch_run with VIS_STAGE_DETECT) -- to `out`, h_level rows of w_level bytes (vis_level_geometry) at out_stride >= w_level.
+ * Read only: it launches nothing and changes nothing.  Synchronises the context's stream.  VIS_E_STATE if that plan has not
+ * detected yet (also after vis_set_params / vis_batch_plan / vis_batch_reset); VIS_E_INVALID for level 0 (the caller's own
+ * frame), a level >= nlevels or a frame outside the last detection. */
+int  vis_debug_pyramid_level(vis_ctx* ctx, int batch, int frame, int level, uint8_t* out, int out_stride);
 /* the inlier mask of findEssentialMat (src/VISystem.cpp:1680, the `mask` argument) for pair `frame` of the last batch: one byte per
  * correspondence the pose stage saw, in the order it saw them (good matches, or the symmetric matches with VIS_POSE_SYM).
  * VIS_E_CAPACITY if cap < *n_points (which is still returned). */

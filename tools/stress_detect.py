@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """tools/stress_detect.py [SECONDS] [SEED] -- randomised parity of detect + describe + match + Camera::Update on the GPU box: random
 image sizes (any size, not only multiples of 16), contents (stream crops, crops at reduced contrast, uniform noise, blurred noise,
-checkerboards, flat patches pasted in), ORB parameters (nfeatures 20 ... 3000, 1 ... 8 levels, scale factor, FAST / edge
-thresholds) through the single-frame C ABI against the CPU oracle: keypoints, descriptors, 2-NN tables, symmetric / good matches and
-the half pyramid, all bit for bit.  Prints one line per failure and a summary; exit code 1 on any failure.  Not part of the test
+checkerboards, flat patches pasted in), ORB parameters (nfeatures 20 ... 3000, 1 ... 8 levels, scale factor 1.01 ... 3.0, FAST
+threshold 1 ... 254, edge threshold 22 ... 255: the whole range vis_set_params accepts) through the single-frame C ABI against the
+CPU oracle: keypoints, descriptors, 2-NN tables, symmetric / good matches and the half pyramid, all bit for bit.  Prints one line per failure and a summary; exit code 1 on any failure.  Not part of the test
 suite (unbounded run time); tests/test_detect_gpu.py, test_match_gpu.py, test_edge_cases_gpu.py hold the fixed cases."""
 import os
 import sys
@@ -63,14 +63,16 @@ while time.time() < t_end and (max_cases is None or runs < max_cases):
     p.w_size, p.h_size = w, h
     p.nfeatures = int(rng.choice([20, 100, 300, 500, 1000, 1000, 3000]))
     p.nlevels = int(rng.choice([1, 2, 3, 5, 8, 8]))
-    p.scale_factor = float(rng.choice([1.2, 1.2, 1.1, 1.5, 2.0]))
-    p.fast_threshold = int(rng.choice([5, 10, 20, 20, 40]))
-    p.edge_threshold = int(rng.choice([22, 31, 31, 40]))
+    p.scale_factor = float(rng.choice([1.2, 1.2, 1.1, 1.5, 2.0, 1.01, 2.2, 2.5, 3.0]))
+    p.fast_threshold = int(rng.choice([5, 10, 20, 20, 40, 1, 2, 4, 120, 200, 254]))
+    p.edge_threshold = int(rng.choice([22, 31, 31, 40, 31, 64, 120, 255]))
     p.sym_mode = int(rng.integers(0, 2))
-    # the smallest level must still hold the border twice over (the reference's own requirement on its inputs)
-    sc = p.scale_factor ** (p.nlevels - 1)
-    if min(w, h) / sc < 2 * p.edge_threshold + 8:
+    # what the library itself asks of a configuration: level 0 holds the border twice over and every level is at least 8 x 8 (upper
+    # levels smaller than the border are valid input: they emit nothing).  The level count is lowered until the draw is feasible.
+    if min(w, h) < 2 * p.edge_threshold + 8:
         continue
+    while p.nlevels > 1 and min(w, h) / p.scale_factor ** (p.nlevels - 1) < 8.5:
+        p.nlevels -= 1
     a, b = content(w, h)
     what = "set_params"
     try:

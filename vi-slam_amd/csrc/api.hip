@@ -464,6 +464,22 @@ extern "C" int vis_debug_counters(vis_ctx* ctx, unsigned long long out[4]) {
     return VIS_OK;
 }
 
+// diagnostic: level `level` >= 1 of frame `frame` as the last detection of the chosen plan left it in the plan's pyramid (read only: no
+// launch, nothing of the plan changes).  The rows are copied without their stride padding.
+extern "C" int vis_debug_pyramid_level(vis_ctx* ctx, int batch, int frame, int level, uint8_t* out, int out_stride) {
+    if (!ctx || !out) return VIS_E_INVALID;
+    const Plan* pl = batch ? ctx->batch : ctx->single;
+    if (!pl || pl->pyr_frames < 1) return VIS_E_STATE;
+    if (level < 1 || level >= pl->L || frame < 0 || frame >= pl->pyr_frames) return VIS_E_INVALID;     // (level 0 is the caller's own frame)
+    const LevelInfo& V = pl->lv[level];
+    if (out_stride < V.w) return VIS_E_INVALID;
+    (void)hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy2D(out, (size_t)out_stride, pl->d_pyr[level] + (size_t)frame * V.frame_bytes, (size_t)V.stride, (size_t)V.w, (size_t)V.h,
+                            hipMemcpyDeviceToHost));
+    return VIS_OK;
+}
+
 __global__ void k_set_pair(int32_t* q, int32_t* t, int32_t vq, int32_t vt) { *q = vq; *t = vt; }
 
 static int ensure_single(vis_ctx* ctx, int w, int h) {
@@ -1069,7 +1085,7 @@ extern "C" int vis_batch_plan(vis_ctx* ctx, int w, int h, int stride, int max_fr
 extern "C" int vis_batch_reset(vis_ctx* ctx) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     sync_all(ctx);
-    ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
+    ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->pyr_frames = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }

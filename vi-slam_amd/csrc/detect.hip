@@ -1383,6 +1383,7 @@ int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int re
     ctx->tm.launches_fast = nfast;
     ctx->tm.launches_total = (L - 1) + 1 + 2;
     HIPCHK(ctx, hipGetLastError());
+    pl->pyr_frames = n;                 // (vis_debug_pyramid_level: the frames whose levels this chain writes)
     return VIS_OK;
 }
 

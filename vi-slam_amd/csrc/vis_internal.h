@@ -133,6 +133,7 @@ struct Plan {
     int max_iters = 0;
     bool have_prev = false;                  // batch: record 0 holds the previous batch's last frame
     int last_n = 0;                          // frames in the last batch
+    int pyr_frames = 0;                      // frames whose levels >= 1 the last launch_detect of this plan wrote into d_pyr (0: it has not run)
     int carry_from = 0;                      // absolute record to copy into the next set's record 0 (0 = none)
     // batch plans keep VIS_BATCH_SETS sets of records (keypoints, descriptors, expanded descriptors) and walk them round-robin: the detect
     // chain of batch i + SETS waits for the matcher of batch i.  (Round 5: three sets instead of two change nothing -- in steady state the

@@ -162,6 +162,7 @@ ABI_SYMBOLS = [
     "vis_rectify_batch", "vis_rectify_host",
     "vis_default_tri_params", "vis_triangulate", "vis_batch_triangulate",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
+    "vis_debug_pyramid_level",
 ]
 
 
@@ -232,6 +233,8 @@ def _load():
         lib.vis_default_align_weights.restype = None
         lib.vis_set_align_weights.argtypes = [vp, C.POINTER(AlignWeights)]
         lib.vis_get_align_weights.argtypes = [vp, C.POINTER(AlignWeights)]
+    if hasattr(lib, "vis_debug_pyramid_level"):         # (absent from older A/B builds)
+        lib.vis_debug_pyramid_level.argtypes = [vp, ci, ci, ci, vp, ci]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -574,6 +577,16 @@ class Context:
         sc = np.zeros(L, np.float32)
         self._chk(lib.vis_level_geometry(self._h, w, h, _ptr(ws), _ptr(hs), _ptr(sc), _ptr(q)), "vis_level_geometry")
         return ws, hs, sc, q
+
+    def pyramid_level(self, level, frame=0, batch=False, w=None, h=None):
+        """diagnostic: level `level` >= 1 of frame `frame` as the last detection left it -- of the single-frame plan, or of the batch
+        plan with batch=True -- as an (h_level, w_level) array without the stride padding.  (w, h) = the frame size of that plan;
+        default: the parameters' w_size x h_size"""
+        ws, hs, _, _ = self.level_geometry(self.params.w_size if w is None else w, self.params.h_size if h is None else h)
+        ok = 0 <= level < len(ws)                                  # (a level the plan does not have: the library refuses it)
+        out = np.empty((int(hs[level]), int(ws[level])) if ok else (1, 1), np.uint8)
+        self._chk(lib.vis_debug_pyramid_level(self._h, 1 if batch else 0, frame, level, _ptr(out), out.strides[0]), "vis_debug_pyramid_level")
+        return out
 
     # -- Camera::Update --------------------------------------------------------------------------------
     def camera_update(self, img):
