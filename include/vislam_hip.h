@@ -165,7 +165,8 @@ void vis_half_pyramid_dims(int w, int h, int32_t lw[5], int32_t lh[5]);
  * out_levels[l] (l=1..4) receives lw[l]*lh[l] bytes (vis_half_pyramid_dims), tightly packed; out_levels[0] may be NULL.
  * With scale exactly 2 cv::resize(INTER_LINEAR) runs its area-fast path: (a+b+c+d+2)>>2 over every complete 2x2 block; where a
  * level is one larger than half of an odd source size, the last column / row averages the pixels that exist
- * (saturate_cast<uchar>((float)sum / count), round half to even).  w, h >= 16. */
+ * (saturate_cast<uchar>((float)sum / count), round half to even).  16 <= w, h <= 4095 (a level may be one pixel wide or high:
+ * 16 -> 8 -> 4 -> 2 -> 1); outside that VIS_E_INVALID, with a text in vis_last_error. */
 int  vis_camera_update(vis_ctx* ctx, const uint8_t* img, int w, int h, int stride,
                        uint8_t* const out_levels[5]);
 /* replaces frameGPU.upload + cuda::ORB::detectAndCompute + descriptorsGPU.download,
@@ -216,12 +217,16 @@ int  vis_f2f_ransac(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keypoint* 
  * passes scale = 3, delta = 0), and gradient = addWeighted(|dx| sat u8, 0.5, |dy| sat u8, 0.5, 0).
  * All outputs are caller-owned DEVICE buffers of n * vis_gradient_frame_elems(w, h) elements: inside a frame the
  * levels are dense and back to back (level l starts at sum_{k<l} lw[k] lh[k]); d_gray receives levels 1..4 of
- * the half pyramid (its level-0 part is left untouched: level 0 is the frame itself).  w, h >= 16,
- * stride % 4 == 0, 1 <= scale <= 8 (int16 cannot overflow), buffers 16-byte aligned. */
+ * the half pyramid (its level-0 part is left untouched: level 0 is the frame itself).  16 <= w, h <= 4095 (the limit of the
+ * alignment that reads these buffers; vis_gradient_frame_elems returns 0 outside it), stride >= w and stride % 4 == 0,
+ * 1 <= scale <= 8 (int16 cannot overflow), output buffers 16-byte aligned (d_frames needs no alignment).  A level that is one pixel
+ * wide or high (every side of 16 ... 21 ends in one) is a level like any other: BORDER_REFLECT_101 of a single pixel repeats it, so
+ * the response across it is 0. */
 size_t vis_gradient_frame_elems(int w, int h);
 int  vis_gradient_batch(vis_ctx* ctx, const uint8_t* d_frames, int w, int h, int stride, int n, int scale,
                         uint8_t* d_gray, int16_t* d_gx, int16_t* d_gy, uint8_t* d_g);
-/* one host frame; out pointers per level may be NULL; each receives (w>>l)*(h>>l) elements */
+/* one host frame; out pointers per level may be NULL; level l receives lw[l]*lh[l] elements (vis_half_pyramid_dims -- NOT (w>>l)*(h>>l):
+ * 150 x 110 has a 38 x 28 level 2).  16 <= w, h <= 4095, stride >= w, 1 <= scale <= 8. */
 int  vis_compute_gradient(vis_ctx* ctx, const uint8_t* img, int w, int h, int stride, int scale,
                           int16_t* const gx[5], int16_t* const gy[5], uint8_t* const g[5]);
 /* Camera::ObtainPatchesPointsPreviousFrame (src/Camera.cpp:358-410) and ObtainDebugPointsPreviousFrame
@@ -261,7 +266,8 @@ void vis_se3_exp(const float a[6], vis_se3f* out);
 void vis_se3_mul(const vis_se3f* a, const vis_se3f* b, vis_se3f* out);
 void vis_se3_from_rt(const float R[9], const float t[3], vis_se3f* out);
 void vis_se3_matrix(const vis_se3f* a, float M[16]);
-/* One pair, HOST pointers.  Level l images are dense (w>>l) x (h>>l): gray1/gx1/gy1 of the previous keyframe
+/* One pair, HOST pointers.  Level l images are dense lw[l] x lh[l] (vis_half_pyramid_dims: what vis_camera_update and
+ * vis_compute_gradient write; up to one row / column more than (w>>l) x (h>>l)); 16 <= w, h <= 4095: gray1/gx1/gy1 of the previous keyframe
  * (Frame::grayImage / gradientX / gradientY), gray2 of the current frame, cand1[l] = n_cand[l] rows (x, y, z, 1) as
  * Frame::candidatePoints[l] holds them.  Levels outside [last_level, first_level] may be NULL.  init may be NULL
  * (identity); the reference seeds it from the IMU rotation residual and the ground-truth translation (:1133-1166). */
@@ -273,8 +279,9 @@ int  vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* ap, int w,
 /* Batched, DEVICE pointers: n consecutive frames resident in HBM and the outputs of vis_gradient_batch for the same
  * frames (d_gray levels 1..4, d_gx, d_gy).  Pair i = (frame i-1 -> frame i), i = 1..n-1; d_out[0] is zeroed.  The
  * candidate points of pair i are generated on the fly from d_pts: max_pts (x, y) floats per pair = the matched
- * keypoints of frame i-1 (Frame::nextGoodMatches, at most 200 are used like the reference), d_npts[i] of them valid.
- * d_init: n poses or NULL.  Asynchronous on the context's stream.  w, h >= 16. */
+ * keypoints of frame i-1 (Frame::nextGoodMatches, at most 200 are used like the reference), d_npts[i] of them valid; a d_npts[i]
+ * above max_pts is clamped to max_pts (below 1: no candidates, the record of a pair without residuals).
+ * d_init: n poses or NULL.  Asynchronous on the context's stream.  16 <= w, h <= 4095, stride >= w (any alignment). */
 int  vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int w, int h, int stride, int n,
                      const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
                      const float* d_pts, const int32_t* d_npts, int max_pts,

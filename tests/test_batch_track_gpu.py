@@ -74,9 +74,9 @@ def _residual(orc, pose):
 
 
 class _Oracle:
-    """EstimatePoseFeatures (prev -> cur) on the matched keypoints of prev, cached by pair and points"""
-    def __init__(self, orc, frames):
-        self.orc, self.frames, self.lv, self.cache = orc, frames, {}, {}
+    """EstimatePoseFeatures (prev -> cur) on the matched keypoints of prev, cached by pair and points; frames of w x h"""
+    def __init__(self, orc, frames, w=W, h=H):
+        self.orc, self.frames, self.lv, self.cache, self.w, self.h = orc, frames, {}, {}, w, h
 
     def levels(self, g):
         if g not in self.lv:
@@ -92,8 +92,8 @@ class _Oracle:
         key = (j, g, prev_kp.tobytes())
         if key not in self.cache:
             (p0, gx, gy), (p1, _, _) = self.levels(j), self.levels(g)
-            cand = [self.orc.patch_points(prev_kp, W, H, l) for l in range(5)]
-            self.cache[key] = self.orc.estimate_pose_features(self.orc.default_align_params(), W, H, p0, p1, gx, gy, cand)
+            cand = [self.orc.patch_points(prev_kp, self.w, self.h, l) for l in range(5)]
+            self.cache[key] = self.orc.estimate_pose_features(self.orc.default_align_params(), self.w, self.h, p0, p1, gx, gy, cand)
         return self.cache[key]
 
 

@@ -457,9 +457,13 @@ extern "C" void vis_default_align_params(vis_align_params* ap) {
     ap->epsilon = 0.001f; ap->z_factor = 0.002f;                                      // :1115,1121
 }
 
-static int check_align_params(const vis_align_params* ap, int w, int h) {
-    if (!ap || ap->first_level < ap->last_level || ap->first_level > 4 || ap->last_level < 0 || ap->max_iterations < 1) return VIS_E_INVALID;
-    if (w < 16 || h < 16 || w > 4095 || h > 4095 || !(ap->fx > 0) || !(ap->fy > 0)) return VIS_E_INVALID;
+static int check_align_params(vis_ctx* ctx, const vis_align_params* ap, int w, int h) {
+    if (!ap || ap->first_level < ap->last_level || ap->first_level > 4 || ap->last_level < 0 || ap->max_iterations < 1) {
+        ctx->err = "alignment: 0 <= last_level <= first_level <= 4, max_iterations >= 1"; return VIS_E_INVALID;
+    }
+    if (w < 16 || h < 16 || w > VIS_MAX_SIDE || h > VIS_MAX_SIDE || !(ap->fx > 0) || !(ap->fy > 0)) {
+        ctx->err = "alignment: 16 <= w, h <= 4095, fx, fy > 0"; return VIS_E_INVALID;
+    }
     return VIS_OK;
 }
 
@@ -510,7 +514,7 @@ extern "C" int vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* 
                                           const float* const cand1[5], const int32_t n_cand[5],
                                           const vis_se3f* init, vis_align_result* out) {
     if (!ctx || !out || !gray1 || !gray2 || !gx1 || !gy1 || !cand1 || !n_cand) return VIS_E_INVALID;
-    int rc = check_align_params(ap, w, h);
+    int rc = check_align_params(ctx, ap, w, h);
     if (rc) return rc;
     (void)hipSetDevice(ctx->device);
     size_t need = 4096;
@@ -576,7 +580,7 @@ int align_batch_links(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d
                       const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy, const float* d_pts, const int32_t* d_npts,
                       int max_pts, const int32_t* d_prev, const TrackSnapshot* snap, const vis_se3f* d_init, vis_align_result* d_out) {
     if (!ctx || !d_frames || !d_gray || !d_gx || !d_gy || !d_pts || !d_npts || !d_out) return VIS_E_INVALID;
-    int rc = check_align_params(ap, w, h);
+    int rc = check_align_params(ctx, ap, w, h);
     if (rc) return rc;
     if (stride < w || n < 1 || max_pts < 1) { ctx->err = "vis_align_batch: stride >= w, n >= 1, max_pts >= 1"; return VIS_E_INVALID; }
     (void)hipSetDevice(ctx->device);

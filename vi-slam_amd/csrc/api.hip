@@ -551,7 +551,10 @@ static int check_flags(vis_ctx* ctx, Plan* pl) {
 
 // ------------------------------------------------------------------------------------------------ single-frame API
 extern "C" int vis_camera_update(vis_ctx* ctx, const uint8_t* img, int w, int h, int stride, uint8_t* const out_levels[5]) {
-    if (!ctx || !img || !out_levels || w < 16 || h < 16 || stride < w) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_INVALID;
+    if (!img || !out_levels || w < 16 || h < 16 || w > VIS_MAX_SIDE || h > VIS_MAX_SIDE || stride < w) {
+        ctx->err = "vis_camera_update: img and out_levels not NULL, 16 <= w, h <= 4095, stride >= w"; return VIS_E_INVALID;
+    }
     (void)hipSetDevice(ctx->device);
     int lw[5], lh[5]; vis_half_dims(w, h, lw, lh);
     size_t lvl_bytes[5]; size_t total = (size_t)w * h;
@@ -576,14 +579,14 @@ extern "C" int vis_camera_update(vis_ctx* ctx, const uint8_t* img, int w, int h,
     return VIS_OK;
 }
 
-extern "C" size_t vis_gradient_frame_elems(int w, int h) { return (w < 16 || h < 16) ? 0 : vis_grad_frame_elems(w, h); }
+extern "C" size_t vis_gradient_frame_elems(int w, int h) { return (w < 16 || h < 16 || w > VIS_MAX_SIDE || h > VIS_MAX_SIDE) ? 0 : vis_grad_frame_elems(w, h); }
 extern "C" void vis_half_pyramid_dims(int w, int h, int32_t lw[5], int32_t lh[5]) { if (lw && lh) vis_half_dims(w, h, lw, lh); }
 
 extern "C" int vis_gradient_batch(vis_ctx* ctx, const uint8_t* d_frames, int w, int h, int stride, int n, int scale,
                                   uint8_t* d_gray, int16_t* d_gx, int16_t* d_gy, uint8_t* d_g) {
     if (!ctx || !d_frames || !d_gray || !d_gx || !d_gy || !d_g) return VIS_E_INVALID;
-    if (w < 16 || h < 16 || stride < w || (stride & 3) || n < 1 || scale < 1 || scale > 8) {
-        ctx->err = "vis_gradient_batch: w, h >= 16, stride >= w and % 4 == 0, n >= 1, 1 <= scale <= 8"; return VIS_E_INVALID;
+    if (w < 16 || h < 16 || w > VIS_MAX_SIDE || h > VIS_MAX_SIDE || stride < w || (stride & 3) || n < 1 || scale < 1 || scale > 8) {
+        ctx->err = "vis_gradient_batch: 16 <= w, h <= 4095, stride >= w and % 4 == 0, n >= 1, 1 <= scale <= 8"; return VIS_E_INVALID;
     }
     if (((uintptr_t)d_gx | (uintptr_t)d_gy | (uintptr_t)d_g | (uintptr_t)d_gray) & 15) { ctx->err = "vis_gradient_batch: output buffers must be 16-byte aligned"; return VIS_E_INVALID; }
     (void)hipSetDevice(ctx->device);
@@ -597,7 +600,10 @@ extern "C" int vis_gradient_batch(vis_ctx* ctx, const uint8_t* d_frames, int w, 
 
 extern "C" int vis_compute_gradient(vis_ctx* ctx, const uint8_t* img, int w, int h, int stride, int scale,
                                     int16_t* const gx[5], int16_t* const gy[5], uint8_t* const g[5]) {
-    if (!ctx || !img || !gx || !gy || !g || w < 16 || h < 16 || stride < w || scale < 1 || scale > 8) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_INVALID;
+    if (!img || !gx || !gy || !g || w < 16 || h < 16 || w > VIS_MAX_SIDE || h > VIS_MAX_SIDE || stride < w || scale < 1 || scale > 8) {
+        ctx->err = "vis_compute_gradient: img, gx, gy and g not NULL, 16 <= w, h <= 4095, stride >= w, 1 <= scale <= 8"; return VIS_E_INVALID;
+    }
     (void)hipSetDevice(ctx->device);
     const size_t fe = vis_grad_frame_elems(w, h);
     const int ws = (w + 15) & ~15;                              // device row stride of the copy (the batched entry wants % 4 == 0)

@@ -346,7 +346,7 @@ int launch_half_pyramid_batch(vis_ctx* ctx, const uint8_t* d_frames, int w, int 
     if (row0 < h)
         for (int l = 1; l < 5; l++) {
             const int sw = lw[l - 1], sh = lh[l - 1], dw = lw[l], dh = lh[l];
-            if (dw < 1 || dh < 1) return VIS_E_INVALID;
+            if (dw < 1 || dh < 1) { ctx->err = "half pyramid: a level is empty (w, h >= 16)"; return VIS_E_INVALID; }
             const int sr0 = row0 >> (l - 1), dr0 = row0 >> l;                // first source / destination row still to do (row0 is a multiple of 16)
             if (dr0 >= dh) continue;
             const uint8_t* src = (l == 1 ? d_frames : d_pyr + loff[l - 1]) + (size_t)sr0 * (l == 1 ? stride : sw);
@@ -369,7 +369,9 @@ int launch_gradient(vis_ctx* ctx, const uint8_t* d_frames, int w, int h, int str
     for (int l = 0; l < 5; l++) {
         GradLevel& L = G.lv[l];
         L.w = lw[l]; L.h = lh[l]; L.off = off;
-        if (L.w < 2 || L.h < 2) return VIS_E_INVALID;
+        // a level one pixel wide or high is a valid one (16 -> 8 -> 4 -> 2 -> 1): reflect101 sends every neighbour of its only column / row
+        // to index 0, so the response across it is 0, and k_gradient's slow row path and its tail store touch nothing outside it
+        if (L.w < 1 || L.h < 1) { ctx->err = "gradient: a level is empty (w, h >= 16)"; return VIS_E_INVALID; }
         L.items_x = (L.w + 7) / 8;
         L.items = L.items_x * ((L.h + GR_ROWS - 1) / GR_ROWS);
         L.base_blocks = blocks;

@@ -14,6 +14,7 @@
 #define VIS_NSLOTS 32            // device keyframe slots of the single-frame API (Camera::frameList)
 #define VIS_RANSAC_MAX_M 8192    // max correspondences per RANSAC problem
 #define VIS_MAX_MODELS 10
+#define VIS_MAX_SIDE 4095        // largest frame side of the half pyramid, the gradients and the alignment (rectify.hip's too)
 // k_fast (detect.hip) works on ITEMS: a strip of 32 lanes x 4 pixels = 128 pixel columns (120 of them emit; 1 score halo + 3 ring
 // columns on either side) marched down 8 score rows at a time, at most VIS_FS_NCH chunks = 8 * NCH - 2 emitting rows.  An item owns a
 // candidate slot sized by the 3x3-NMS bound of its emit region (60 x 31 = 1860 <= 2048): a slot cannot overflow.
