@@ -518,6 +518,51 @@ int  vis_triangulate(vis_ctx* ctx, const vis_tri_params* tp, const double R[9], 
 int  vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int n, int row_cap,
                            vis_map_point* d_points, uint8_t* d_flags, vis_tri_summary* d_summary);
 
+/* ---- IMU-aided translation and epipolar keypoint filter: VISystem::F2FRansac (src/VISystem.cpp:612-769) and VISystem::FilterKeypoints
+ * (:542-610) for the pairs of a batch -- the pose steps of the ground-truth main's AddFrame (:358-359, :523-527).  The rotation of every
+ * pair is an INPUT (the reference integrates the IMU for it; that is outside this library).  Both use one test per correspondence:
+ *     -1000 / log10(|dir . normal|) < threshold,   normal = bearing1 x (R bearing2),  bearings ((u - cx) / fx, (v - cy) / fy, 1) normalised
+ * with dir = a RANSAC hypothesis (F2FRansac) or the given translation's direction (FilterKeypoints).  The device decides it by two compares
+ * and evaluates the expression itself only in a narrow band around 10^(-1000 / threshold): the result is that of the expression for every input
+ * (DESIGN.md).  Rows: d_p1 / d_p2 hold n rows of max_pts (x, y) float points (8-byte aligned), d_npts[i] of them valid (clamped to max_pts).
+ * F2FRansac per pair with m correspondences: iteration j of params.f2f_iters samples i1 = (d_draws[2j] & 0x7fffffff) % (m - 1) and i2 likewise from
+ * d_draws[2j + 1] (rand() % (sizeNewGroup - 1), :712-713; ONE table of f2f_iters x 2 draws serves every pair, so a stream's records do not depend on
+ * how it is cut into batches), d = normalize(n_i1 x n_i2), a zero cross product is skipped (:716), the count runs over all m correspondences with
+ * params.f2f_threshold, and the first iteration with the largest count > 0 wins (:737-741).  t = scale * (float)d; with a reference translation g
+ * (d_tref, 3 floats per pair; the ground-truth translation of :524-527 and :639-642) scale = |g| in float and t is negated when t . g < 0; without
+ * (NULL): scale 1, no flip.  m < 2, f2f_iters == 0 or a frame without a pair: a zero record with best_iter = -1. */
+enum { VIS_F2F_TILE = 512 };   /* correspondences per LDS tile of the kernel: rows longer than this are walked in several tiles */
+typedef struct vis_f2f_result {          /* 32 bytes */
+    float   t[3];                        /* scale * direction, sign-fixed; 0 when no hypothesis won */
+    int32_t count_max, n_points;
+    int32_t best_iter;                   /* -1: none */
+    int32_t n_degenerate;                /* iterations skipped for a zero cross product, :716 */
+    int32_t flipped;
+} vis_f2f_result;
+/* DEVICE pointers; d_rot: n x 9 floats (row-major 3x3 per pair), d_out: n records.  Asynchronous on the context's stream.  VIS_E_INVALID for a NULL
+ * or misaligned argument (d_tref may be NULL) or n, max_pts < 0; VIS_E_STATE without a context. */
+int  vis_f2f_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
+                   const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out);
+/* The same on the pairs of the last vis_batch_run (which must have included VIS_STAGE_MATCH; VIS_STAGE_POSE is not needed; n = its frames): the
+ * correspondences the pose stage would see, in the order of vis_batch_get_inlier_mask (the good matches, or the symmetric matches with
+ * VIS_POSE_SYM), with vis_batch_get_keyframes' pairing, the pair to the carried frame included; frame i's rotation is d_rot[9 i].  Asynchronous
+ * on the POSE stream behind the match filter (and behind what is queued on the context's stream so far), overlapping the next vis_batch_run like
+ * vis_batch_align: the caller's buffers are in use until vis_batch_sync.  VIS_E_STATE without context / plan / match stage or when n differs;
+ * VIS_E_INVALID for NULL d_rot, d_draws or d_out. */
+int  vis_batch_f2f(vis_ctx* ctx, int n, const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out);
+/* FilterKeypoints: d_keep[i * row_cap + k] = 1 when correspondence k of pair i passes the test with dir = d_t[3 i ..] / |d_t[3 i ..]| (the three
+ * floats widened to double, :565-568) under the rotation d_rot[9 i ..] (RotationResidual, :594), else 0; bytes beyond the pair's correspondences
+ * are left untouched; d_nkeep[i] = the number kept.  A zero translation makes every dot product NaN: nothing is kept, as in the reference.  The
+ * reference passes threshold 500.0 at its only call site (:358).  Asynchronous like vis_f2f_batch / vis_batch_f2f.  VIS_E_CAPACITY when row_cap is
+ * smaller than max_pts (the plan's correspondences per pair); VIS_E_INVALID when threshold is not finite. */
+int  vis_filter_keypoints_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
+                                const float* d_rot, const float* d_t, double threshold, int row_cap, uint8_t* d_keep, int32_t* d_nkeep);
+int  vis_batch_filter_keypoints(vis_ctx* ctx, int n, const float* d_rot, const float* d_t, double threshold, int row_cap,
+                                uint8_t* d_keep, int32_t* d_nkeep);
+/* One pair, HOST pointers (vis_keypoint arrays like vis_f2f_ransac); blocks once.  keep receives m bytes; m = 0: *n_keep = 0. */
+int  vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keypoint* pts2, int m, const float rot[9], const float t[3],
+                          double threshold, uint8_t* keep, int* n_keep);
+
 /* ---- rectification (vi::CameraModel, src/CameraModel.cpp:84-105; VISystem::CalculateROI, src/VISystem.cpp:162-205) -------------
  * Opt-in: nothing else in this header remaps a frame (the reference's GPU main hands frames on un-remapped, src/VISystemGPU.cpp:137-146).
  * Restatements of OpenCV 3.2 written from the published algorithm; parity with real OpenCV is UNPINNED.

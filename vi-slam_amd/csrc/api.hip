@@ -77,7 +77,7 @@ template <class F> static void ordering_events(vis_ctx* ctx, F f) {
     f(ctx->ev_filter_done, dt); f(ctx->ev_detect_done, dt); f(ctx->ev_update_fork, dt); f(ctx->ev_update_done, dt); f(ctx->ev_align_fork, dt);
     f(ctx->ev_pose_done, hipEventDefault); f(ctx->ev_pose_start, hipEventDefault); f(ctx->ev_match_start, hipEventDefault);   // (also time the stages)
     for (int i = 0; i < VIS_BATCH_SETS; i++) f(ctx->ev_match_done[i], dt);
-    for (int i = 0; i < 2; i++) { f(ctx->ev_pose_done_set[i], dt); f(ctx->ev_results_done_set[i], dt); f(ctx->ev_align_done[i], dt); f(ctx->ev_tri_done[i], dt); }
+    for (int i = 0; i < 2; i++) { f(ctx->ev_pose_done_set[i], dt); f(ctx->ev_results_done_set[i], dt); f(ctx->ev_align_done[i], dt); f(ctx->ev_tri_done[i], dt); f(ctx->ev_epi_done[i], dt); }
 }
 
 extern "C" int vis_create(int device, vis_ctx** out) {
@@ -1391,6 +1391,105 @@ extern "C" int vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int
     ctx->pose_pending = true;
     HIPCHK(ctx, hipEventRecord(ctx->ev_tri_done[pl->mo_cur], sP));
     O.readers.note(sP, ctx->ev_tri_done[pl->mo_cur]);
+    return VIS_OK;
+}
+
+// ---- F2FRansac / FilterKeypoints for the pairs of a batch: pose.hip k_f2f_batch, k_epi_filter
+extern "C" int vis_f2f_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
+                             const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
+    if (n < 0 || max_pts < 0 || !d_npts || !d_rot || !d_draws || !d_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
+    if (((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 3)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    return f2f_batch_run(ctx, n, max_pts, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
+}
+
+extern "C" int vis_filter_keypoints_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
+                                          const float* d_rot, const float* d_t, double threshold, int row_cap, uint8_t* d_keep, int32_t* d_nkeep) {
+    if (n < 0 || max_pts < 0 || !d_npts || !d_rot || !d_t || !d_keep || !d_nkeep || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
+    if (((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_nkeep & 3) || !std::isfinite(threshold)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (row_cap < max_pts) { ctx->err = "vis_filter_keypoints_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return epi_filter_run(ctx, n, max_pts, d_p1, d_p2, d_npts, d_rot, d_t, threshold, row_cap, d_keep, d_nkeep);
+}
+
+// The plan's pairs: the rows k_filter wrote for the pose stage (p1 / p2 of the last step's matcher-output set, ngood or nsym).  On the pose
+// stream, behind the matcher of that step (the record set's matcher event, recorded behind the filter: what vis_batch_align waits for) and
+// behind the context's stream, where the caller's inputs may have been produced.  The filter two steps on rewrites the set: it waits for
+// the reader event noted here.
+template <class F> static int batch_epi(vis_ctx* ctx, int n, const char* who, F run) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = std::string(who) + ": the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    (void)hipSetDevice(ctx->device);
+    hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
+    Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
+    Plan::MatchOut& O = pl->out();
+    HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, sA));
+    HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
+    HIPCHK(ctx, rs.matcher.wait(sP));
+    ctx->stream = sP;
+    const int rc = run(pl, O, ctx->p.pose_input == VIS_POSE_SYM ? O.nsym : O.ngood);
+    ctx->stream = sA;
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_epi_done[pl->mo_cur], sP));
+    O.readers.note(sP, ctx->ev_epi_done[pl->mo_cur]);
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_f2f(vis_ctx* ctx, int n, const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
+    if (!d_rot || !d_draws || !d_out || ((uintptr_t)d_out & 3)) return VIS_E_INVALID;
+    return batch_epi(ctx, n, "vis_batch_f2f", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        return f2f_batch_run(ctx, n, pl->pose_mcap, O.p1, O.p2, d_npts, d_rot, d_tref, d_draws, d_out);
+    });
+}
+
+extern "C" int vis_batch_filter_keypoints(vis_ctx* ctx, int n, const float* d_rot, const float* d_t, double threshold, int row_cap,
+                                          uint8_t* d_keep, int32_t* d_nkeep) {
+    if (!d_rot || !d_t || !d_keep || !d_nkeep || ((uintptr_t)d_nkeep & 3) || !std::isfinite(threshold)) return VIS_E_INVALID;
+    if (ctx && ctx->batch && row_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_filter_keypoints: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    return batch_epi(ctx, n, "vis_batch_filter_keypoints", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        return epi_filter_run(ctx, n, pl->pose_mcap, O.p1, O.p2, d_npts, d_rot, d_t, threshold, row_cap, d_keep, d_nkeep);
+    });
+}
+
+extern "C" int vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keypoint* pts2, int m, const float rot[9], const float t[3],
+                                    double threshold, uint8_t* keep, int* n_keep) {
+    if (m < 0 || !rot || !t || !n_keep || (m && (!pts1 || !pts2 || !keep)) || !std::isfinite(threshold)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    *n_keep = 0;
+    if (m == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t mk = ((size_t)m + 3) & ~(size_t)3;
+    const size_t need = (size_t)m * 16 + 2 * mk + 64 + 16 * 256 + 4096;
+    int rc = ensure_scratch(ctx, need);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0};
+    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
+    float* d_rt = cv.take<float>(12); int32_t* d_cnt = cv.take<int32_t>(2);       // rot, t | m, count
+    uint8_t* d_keep = cv.take<uint8_t>(mk);
+    rc = vis_ensure_pin(ctx, need);
+    if (rc) return rc;
+    std::vector<float> xy((size_t)m * 4);
+    for (int i = 0; i < m; i++) { xy[2 * (size_t)i] = pts1[i].x; xy[2 * (size_t)i + 1] = pts1[i].y; xy[2 * ((size_t)m + i)] = pts2[i].x; xy[2 * ((size_t)m + i) + 1] = pts2[i].y; }
+    float rt[12]; std::memcpy(rt, rot, 36); std::memcpy(rt + 9, t, 12);
+    const int32_t cnt[2] = {m, 0};
+    HostStage hs(ctx);
+    hs.up(d_p1, xy.data(), (size_t)m * 8);
+    hs.up(d_p2, xy.data() + (size_t)m * 2, (size_t)m * 8);
+    hs.up(d_rt, rt, sizeof(rt));
+    hs.up(d_cnt, cnt, sizeof(cnt));
+    hs.flush_ups();
+    rc = epi_filter_run(ctx, 1, m, d_p1, d_p2, d_cnt, d_rt, d_rt + 9, threshold, (int)mk, d_keep, d_cnt + 1);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const void* h_cnt = hs.down(d_cnt, sizeof(cnt));
+    const void* h_keep = hs.down(d_keep, mk);
+    rc = hs.wait();
+    if (rc) return rc;
+    *n_keep = ((const int32_t*)h_cnt)[1];
+    std::memcpy(keep, h_keep, (size_t)m);
     return VIS_OK;
 }
 

@@ -172,11 +172,11 @@ struct vis_ctx {
     hipStream_t update_stream = nullptr;     // VIS_STAGE_UPDATE (Camera::Update): streaming work beside the VALU-bound detect chain
     // Ordering events (api.hip ordering_events).  Forks / joins: ev_update_fork A -> U, ev_update_done U -> A, ev_detect_done A -> M,
     // ev_filter_done M -> P, ev_align_fork A -> P; ev_pose_done / _start and ev_match_start also time.  Reader events (ReaderGuard):
-    // ev_match_done[record set], ev_pose_done_set / ev_results_done_set / ev_tri_done[matcher-output set], ev_align_done[] in turn.  Each is recorded
+    // ev_match_done[record set], ev_pose_done_set / ev_results_done_set / ev_tri_done / ev_epi_done[matcher-output set], ev_align_done[] in turn.  Each is recorded
     // again only by the next reader of its kind -- normally of the same set two steps on, after that set's writer queued its wait.
     hipEvent_t ev_filter_done = nullptr, ev_pose_done = nullptr, ev_pose_start = nullptr, ev_detect_done = nullptr, ev_match_start = nullptr;
     hipEvent_t ev_update_fork = nullptr, ev_update_done = nullptr, ev_align_fork = nullptr;
-    hipEvent_t ev_match_done[VIS_BATCH_SETS] = {}, ev_pose_done_set[2] = {}, ev_results_done_set[2] = {}, ev_align_done[2] = {}, ev_tri_done[2] = {};
+    hipEvent_t ev_match_done[VIS_BATCH_SETS] = {}, ev_pose_done_set[2] = {}, ev_results_done_set[2] = {}, ev_align_done[2] = {}, ev_tri_done[2] = {}, ev_epi_done[2] = {};
     bool pose_pending = false;
     // the last two vis_batch_align / vis_batch_track (align[align_last] the latest) and the caller frames each read: align_reader()
     struct AlignRead { hipEvent_t event = nullptr; const uint8_t* begin = nullptr; const uint8_t* end = nullptr; };
@@ -405,6 +405,11 @@ int triangulate_run(vis_ctx* ctx, const vis_tri_params* tp, int npairs, int in_s
 int  vis_build_sample_table(vis_ctx* ctx, int max_m);
 int f2f_run(vis_ctx* ctx, const vis_keypoint* d_pts1, const vis_keypoint* d_pts2, int m, const float* d_rot,
             const int32_t* d_idx, int iters, double* d_nv, float* d_counts);
+// pose.hip: k_f2f_batch / k_epi_filter on ctx->stream over npairs rows of in_stride (x, y) points (d_npts valid, clamped); d_keep: rows of row_cap >= in_stride
+int f2f_batch_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
+                  const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out);
+int epi_filter_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
+                   const float* d_rot, const float* d_t, double threshold, int row_cap, uint8_t* d_keep, int32_t* d_nkeep);
 #define VIS_RSTATE_WORDS 16
 
 #endif

@@ -8,6 +8,8 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.good_matches         <-> Matcher::computeBestMatches             (src/Matcher.cpp:353-367)
   Context.essential_ransac / recover_pose <-> VISystem::EstimatePoseFeaturesRansac (src/VISystem.cpp:1679-1701)
   Context.f2f_ransac           <-> VISystem::F2FRansac                      (src/VISystem.cpp:612-769)
+  Context.f2f_batch / batch_f2f                       <-> the same for every pair of a batch
+  Context.filter_keypoints (_batch, batch_...)        <-> VISystem::FilterKeypoints  (src/VISystem.cpp:542-610)
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises.
 """
@@ -123,6 +125,18 @@ assert C.sizeof(TriParams) == 16 and MAP_POINT_DTYPE.itemsize == C.sizeof(MapPoi
 MP_INLIER, MP_FRONT, MP_REPROJ_OK, MP_PARALLAX_OK, MP_KEPT = 1, 2, 4, 8, 16
 
 
+class F2fResult(C.Structure):
+    """vis_f2f_result: the translation F2FRansac gives one pair (scale * direction, sign-fixed) and how it was won"""
+    _fields_ = [("t", C.c_float * 3), ("count_max", C.c_int32), ("n_points", C.c_int32), ("best_iter", C.c_int32),
+                ("n_degenerate", C.c_int32), ("flipped", C.c_int32)]
+
+
+F2F_RESULT_DTYPE = np.dtype([("t", "<f4", (3,)), ("count_max", "<i4"), ("n_points", "<i4"), ("best_iter", "<i4"), ("n_degenerate", "<i4"),
+                             ("flipped", "<i4")])
+assert F2F_RESULT_DTYPE.itemsize == C.sizeof(F2fResult) == 32
+F2F_TILE = 512                                    # VIS_F2F_TILE: correspondences per LDS tile of the batched F2FRansac kernel
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -161,6 +175,7 @@ ABI_SYMBOLS = [
     "vis_optimal_new_camera_matrix", "vis_undistort_rectify_map", "vis_rectify_create", "vis_rectify_destroy", "vis_rectify_maps",
     "vis_rectify_batch", "vis_rectify_host",
     "vis_default_tri_params", "vis_triangulate", "vis_batch_triangulate",
+    "vis_f2f_batch", "vis_batch_f2f", "vis_filter_keypoints_batch", "vis_batch_filter_keypoints", "vis_filter_keypoints",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
 ]
@@ -228,6 +243,13 @@ def _load():
         lib.vis_default_tri_params.restype = None
         lib.vis_triangulate.argtypes = [vp, C.POINTER(TriParams), vp, vp, vp, vp, ci, vp, vp, vp, C.POINTER(TriSummary)]
         lib.vis_batch_triangulate.argtypes = [vp, C.POINTER(TriParams), ci, ci, vp, vp, vp]
+    if hasattr(lib, "vis_batch_f2f"):                   # (absent from older A/B builds)
+        cd = C.c_double
+        lib.vis_f2f_batch.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp]
+        lib.vis_batch_f2f.argtypes = [vp, ci, vp, vp, vp, vp]
+        lib.vis_filter_keypoints_batch.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, cd, ci, vp, vp]
+        lib.vis_batch_filter_keypoints.argtypes = [vp, ci, vp, vp, cd, ci, vp, vp]
+        lib.vis_filter_keypoints.argtypes = [vp, vp, vp, ci, vp, vp, cd, vp, ip]
     if hasattr(lib, "vis_set_align_weights"):           # (absent from older A/B builds)
         lib.vis_default_align_weights.argtypes = [C.POINTER(AlignWeights)]
         lib.vis_default_align_weights.restype = None
@@ -779,6 +801,42 @@ class Context:
         self._chk(lib.vis_f2f_ransac(self._h, _ptr(pts1), _ptr(pts2), len(pts1), _ptr(rot), _ptr(idx), len(idx) // 2,
                                      C.c_float(scale), _ptr(out), C.byref(cm)), "vis_f2f_ransac")
         return out, cm.value
+
+    # -- VISystem::F2FRansac / FilterKeypoints for the pairs of a batch (raw DEVICE pointers; 0 / None = NULL) ---------------
+    def f2f_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, d_rot_ptr, d_tref_ptr, d_draws_ptr, d_out_ptr):
+        """queue F2FRansac of n rows of max_pts (x, y) correspondences on the context's stream: n F2fResult records"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_f2f_batch(self._h, n, v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, v(d_rot_ptr), v(d_tref_ptr), v(d_draws_ptr),
+                                    v(d_out_ptr)), "vis_f2f_batch")
+
+    def batch_f2f(self, n, d_rot_ptr, d_tref_ptr, d_draws_ptr, d_out_ptr):
+        """the same on the pairs of the last batch_run(... | STAGE_MATCH), on the pose stream; the buffers are in use until batch_sync()"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_f2f(self._h, n, v(d_rot_ptr), v(d_tref_ptr), v(d_draws_ptr), v(d_out_ptr)), "vis_batch_f2f")
+
+    def filter_keypoints_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, d_rot_ptr, d_t_ptr, threshold, row_cap, d_keep_ptr, d_nkeep_ptr):
+        """queue FilterKeypoints of n rows on the context's stream: n rows of row_cap keep bytes and n counts"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_filter_keypoints_batch(self._h, n, v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, v(d_rot_ptr), v(d_t_ptr),
+                                                 float(threshold), row_cap, v(d_keep_ptr), v(d_nkeep_ptr)), "vis_filter_keypoints_batch")
+
+    def batch_filter_keypoints(self, n, d_rot_ptr, d_t_ptr, threshold, row_cap, d_keep_ptr, d_nkeep_ptr):
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_filter_keypoints(self._h, n, v(d_rot_ptr), v(d_t_ptr), float(threshold), row_cap, v(d_keep_ptr), v(d_nkeep_ptr)),
+                  "vis_batch_filter_keypoints")
+
+    def filter_keypoints(self, pts1, pts2, rot, t, threshold=500.0):
+        """(keep uint8[m], count) of one pair: VISystem::FilterKeypoints with RotationResidual = rot, TranslationResidual = t"""
+        pts1 = np.ascontiguousarray(pts1, KEYPOINT_DTYPE)
+        pts2 = np.ascontiguousarray(pts2, KEYPOINT_DTYPE)
+        assert len(pts1) == len(pts2)
+        rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+        t = np.ascontiguousarray(t, np.float32).reshape(3)
+        keep = np.zeros(max(len(pts1), 1), np.uint8)
+        nk = C.c_int(0)
+        self._chk(lib.vis_filter_keypoints(self._h, _ptr(pts1), _ptr(pts2), len(pts1), _ptr(rot), _ptr(t), float(threshold), _ptr(keep),
+                                           C.byref(nk)), "vis_filter_keypoints")
+        return keep[:len(pts1)], nk.value
 
     # -- batched stream path ----------------------------------------------------------------------------------
     def batch_plan(self, w, h, stride, max_frames):
