@@ -563,6 +563,43 @@ int  vis_batch_filter_keypoints(vis_ctx* ctx, int n, const float* d_rot, const f
 int  vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keypoint* pts2, int m, const float rot[9], const float t[3],
                           double threshold, uint8_t* keep, int* n_keep);
 
+/* ---- rotation-guided matching ("search by projection"): the 2-NN search of the matcher restricted to a window around the position the
+ * pair's rotation predicts -- VISystem::WarpFunctionRT (src/VISystem.cpp:771-860; its call sites :500-504 are commented out in the reference)
+ * put in front of the matcher.  rot: row-major 3x3 f32, the matrix vis_batch_f2f takes (current-frame rays -> previous frame, :1031-1033).
+ * Prediction of a keypoint (u, v) of the CURRENT frame, with fx, fy, cx, cy = params narrowed to float once:
+ *     a = (u - cx) / fx, b = (v - cy) / fy                                     (float)
+ *     X_k = (float)((double)r_k0 a + (double)r_k1 b + (double)r_k2), k = 0..2  (summed left to right in double: OpenCV's float Mat * Mat,
+ *                                                                               restated from memory, UNPINNED -- DESIGN.md section 2)
+ *     x' = fx X_0 / X_2 + cx,  y' = fy X_1 / X_2 + cy                          (float, every operation rounded, in this order, no FMA)
+ * Deviation from the reference, which divides by whatever X_2 is: (x', y') = (NaN, NaN) when !(X_2 > 0).
+ * Window: previous keypoint i at (x_i, y_i) and current keypoint j may be matched iff
+ *     fabsf(x'_j - x_i) <= radius && fabsf(y'_j - y_i) <= radius               (square; false for a NaN; the same test in both directions)
+ * out12[i] = the two nearest admissible j (ascending distance, ties -> lower index), out21[j] likewise over admissible i; a row with fewer
+ * than two admissible candidates has trainIdx = -1 in the missing places, exactly what the unguided matcher returns when the other set has
+ * fewer than two rows, so the filters (fewer than 2 neighbours -> dropped, src/Matcher.cpp:162-165) apply unchanged.
+ * Every call: VIS_E_INVALID for a NULL rot / d_rot, a radius that is negative or not finite, a non-finite entry of a HOST rot (and what the
+ * unguided twin refuses); then VIS_E_STATE without a context or plan.  vis_timings.ms_knn of a guided call includes the prediction kernel. */
+/* predictions of one set of keypoints, HOST pointers: out_xy receives n x 2 floats.  Blocks once. */
+int  vis_warp_keypoints(vis_ctx* ctx, const vis_keypoint* kps, int n, const float rot[9], float* out_xy);
+/* vis_bf_knn2_hamming inside the window; slot_q = previous frame, slot_t = current frame */
+int  vis_bf_knn2_hamming_guided(vis_ctx* ctx, int slot_q, int slot_t, const float rot[9], float radius,
+                                vis_dmatch* out12, vis_dmatch* out21);
+/* vis_bf_knn2_hamming_host with the keypoints of both sets (q = previous, t = current).  The device rows are as long as the larger set, or
+ * as params.keypoint_capacity when that is larger (above 16384 the popcount kernel runs, as for slots of such a context). */
+int  vis_bf_knn2_hamming_guided_host(vis_ctx* ctx, const uint8_t* desc_q, const vis_keypoint* kps_q, int n_q,
+                                     const uint8_t* desc_t, const vis_keypoint* kps_t, int n_t, const float rot[9], float radius,
+                                     vis_dmatch* out12, vis_dmatch* out21);
+/* vis_good_matches on the windowed 2-NN */
+int  vis_good_matches_guided(vis_ctx* ctx, int slot_prev, int slot_cur, const float rot[9], float radius,
+                             vis_dmatch* good, int cap, int* n_good, vis_dmatch* sym_out, int sym_cap, int* n_sym);
+/* vis_batch_run whose match stage is windowed (stages without VIS_STAGE_MATCH: VIS_E_INVALID).  d_rot: DEVICE pointer, n_frames x 9 floats;
+ * frame i's pair -- in vis_batch_get_keyframes' pairing, keyframe gate off or on, the pair to the carried frame included -- uses d_rot[9 i]
+ * (vis_batch_f2f's convention).  d_rot is read on the match stream, behind what is queued on the context's stream so far, and is in use
+ * until vis_batch_sync.  Everything downstream (filters, pose, vis_batch_f2f, triangulation, tracking, vis_batch_results_async) consumes
+ * the matches as it does vis_batch_run's.  Nothing is remembered: a later vis_batch_run is unguided.  The prediction buffer (n_pairs x
+ * keypoint capacity x 8 bytes) is allocated by the first guided call of a plan. */
+int  vis_batch_run_guided(vis_ctx* ctx, const uint8_t* d_frames, int n_frames, int stages, const float* d_rot, float radius);
+
 /* ---- rectification (vi::CameraModel, src/CameraModel.cpp:84-105; VISystem::CalculateROI, src/VISystem.cpp:162-205) -------------
  * Opt-in: nothing else in this header remaps a frame (the reference's GPU main hands frames on un-remapped, src/VISystemGPU.cpp:137-146).
  * Restatements of OpenCV 3.2 written from the published algorithm; parity with real OpenCV is UNPINNED.

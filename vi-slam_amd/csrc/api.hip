@@ -250,7 +250,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -773,17 +773,44 @@ static void keys_to_dmatches(const uint32_t* k, int n, vis_dmatch* out) {
     for (int q = 0; q < n; q++) { key_to_dmatch(k[2 * q], q, out + 2 * q); key_to_dmatch(k[2 * q + 1], q, out + 2 * q + 1); }
 }
 
-extern "C" int vis_bf_knn2_hamming(vis_ctx* ctx, int slot_q, int slot_t, vis_dmatch* out12, vis_dmatch* out21) {
-    if (!ctx) return VIS_E_INVALID;
+// ---- guided matching: the window of the *_guided entry points (match.hip k_warp, window_admits) ----
+int ensure_warp(vis_ctx* ctx, Plan* pl) {
+    if (pl->d_warp) return VIS_OK;
+    HIPCHK(ctx, hipMalloc((void**)&pl->d_warp, ((size_t)pl->npairs * pl->kcap + 8) * sizeof(float2)));   // + 16 floats: a single-frame call's rotation
+    return VIS_OK;
+}
+// what every guided entry point refuses before it looks at its context; host_rot: rot is host memory, its entries must be finite
+static bool guide_args_ok(const float* rot, float radius, bool host_rot) {
+    if (!rot || !std::isfinite(radius) || radius < 0.f) return false;
+    if (host_rot) for (int i = 0; i < 9; i++) if (!std::isfinite(rot[i])) return false;
+    return true;
+}
+// the single-frame plan's guide: the caller's rotation goes behind the plan's predictions (through the staging block, sized by the caller)
+static int single_guide(vis_ctx* ctx, Plan* pl, const float* rot, float radius, MatchGuide* g) {
+    int rc = ensure_warp(ctx, pl);
+    if (rc) return rc;
+    float* d_rot = reinterpret_cast<float*>(pl->d_warp + (size_t)pl->npairs * pl->kcap);
+    HostStage up(ctx);
+    up.up(d_rot, rot, 36);
+    up.flush_ups();
+    if (up.overflow || up.err != hipSuccess) { ctx->err = "guided match: staging the rotation failed"; return VIS_E_HIP; }
+    g->d_rot = d_rot; g->radius = radius;
+    return VIS_OK;
+}
+
+// vis_bf_knn2_hamming (rot == nullptr) and vis_bf_knn2_hamming_guided
+static int knn2_slots(vis_ctx* ctx, int slot_q, int slot_t, const float* rot, float radius, vis_dmatch* out12, vis_dmatch* out21) {
     (void)hipSetDevice(ctx->device);
     Plan* pl = ctx->single;
     int rc = pl ? vis_ensure_pin(ctx, (size_t)pl->kcap * 16 + 4096) : VIS_E_STATE;
     if (!rc) rc = set_single_pair(ctx, pl, slot_q, slot_t);
+    MatchGuide g = {nullptr, 0.f};
+    if (!rc && rot) rc = single_guide(ctx, pl, rot, radius, &g);
     if (rc) return rc;
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[4], ctx->stream);
     rc = launch_expand(ctx, pl, slot_q, 1);
     if (!rc && slot_t != slot_q) rc = launch_expand(ctx, pl, slot_t, 1);
-    if (!rc) rc = launch_match(ctx, pl, 1);
+    if (!rc) rc = launch_match(ctx, pl, 1, rot ? &g : nullptr);
     if (rc) return rc;
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[5], ctx->stream);
     HostStage hs(ctx);
@@ -796,6 +823,100 @@ extern "C" int vis_bf_knn2_hamming(vis_ctx* ctx, int slot_q, int slot_t, vis_dma
     { float a = 0; if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[4], ctx->ev[5])) ctx->tm.ms_knn = a; }
     keys_to_dmatches(h12, std::min(*h_nq, pl->kcap), out12);
     keys_to_dmatches(h21, std::min(*h_nt, pl->kcap), out21);
+    return VIS_OK;
+}
+
+extern "C" int vis_bf_knn2_hamming(vis_ctx* ctx, int slot_q, int slot_t, vis_dmatch* out12, vis_dmatch* out21) {
+    if (!ctx) return VIS_E_INVALID;
+    return knn2_slots(ctx, slot_q, slot_t, nullptr, 0.f, out12, out21);
+}
+
+extern "C" int vis_bf_knn2_hamming_guided(vis_ctx* ctx, int slot_q, int slot_t, const float rot[9], float radius, vis_dmatch* out12, vis_dmatch* out21) {
+    if (!guide_args_ok(rot, radius, true)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    return knn2_slots(ctx, slot_q, slot_t, rot, radius, out12, out21);
+}
+
+// One set of keypoints, host pointers: out_xy[2 j ..] = the prediction of kps[j] (k_warp).  Blocks once.
+extern "C" int vis_warp_keypoints(vis_ctx* ctx, const vis_keypoint* kps, int n, const float rot[9], float* out_xy) {
+    if (n < 0 || !guide_args_ok(rot, 0.f, true) || (n && (!kps || !out_xy))) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t need = (size_t)n * (sizeof(vis_keypoint) + 8) + 4096;
+    int rc = ensure_scratch(ctx, need);
+    if (!rc) rc = vis_ensure_pin(ctx, need);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0};
+    Plan tp; tp.kcap = n;
+    tp.d_kps = cv.take<vis_keypoint>(n);
+    tp.d_nkp = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
+    float* d_rot = cv.take<float>(9);
+    float2* d_xy = cv.take<float2>(n);
+    const int32_t head[2] = {n, 0};                               // nkp[0] = n; pair 0's current record = 0
+    HostStage hs(ctx);
+    hs.up(tp.d_kps, kps, (size_t)n * sizeof(vis_keypoint));
+    hs.up(tp.d_nkp, head, 4); hs.up(tp.d_pair_t, head + 1, 4);
+    hs.up(d_rot, rot, 36);
+    hs.flush_ups();
+    rc = launch_warp(ctx, &tp, 1, d_rot, d_xy);
+    tp = Plan();       // scratch-owned pointers: nothing to free
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const void* h_xy = hs.down(d_xy, (size_t)n * 8);
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out_xy, h_xy, (size_t)n * 8);
+    return VIS_OK;
+}
+
+// vis_bf_knn2_hamming_host with the keypoints of both sets and a window.  The rows are as long as the larger set -- or as the context's
+// keypoint_capacity when that is larger, so a capacity above 16384 selects the popcount kernel here as it does for the slots.
+extern "C" int vis_bf_knn2_hamming_guided_host(vis_ctx* ctx, const uint8_t* desc_q, const vis_keypoint* kps_q, int n_q,
+                                               const uint8_t* desc_t, const vis_keypoint* kps_t, int n_t, const float rot[9], float radius,
+                                               vis_dmatch* out12, vis_dmatch* out21) {
+    if (n_q < 0 || n_t < 0 || (n_q && (!desc_q || !kps_q)) || (n_t && (!desc_t || !kps_t))) return VIS_E_INVALID;
+    if (n_q > 65535 || n_t > 65535 || !guide_args_ok(rot, radius, true)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    const int kcap = std::max(std::max(std::max(n_q, n_t), 1), std::min(ctx->p.keypoint_capacity, 65535));
+    const bool mfma = kcap <= 16384;
+    int rc = ensure_scratch(ctx, (size_t)kcap * ((32 + 8 + sizeof(vis_keypoint)) * 2 + 8 + (mfma ? 256 : 0)) + 8192);
+    if (!rc) rc = vis_ensure_pin(ctx, (size_t)std::max(std::max(n_q, n_t), 1) * ((32 + sizeof(vis_keypoint)) * 2 + 16) + 4096);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0};
+    Plan tp;
+    tp.kcap = kcap; tp.npairs = 1;
+    tp.d_desc = cv.take<uint8_t>((size_t)kcap * 64);
+    tp.d_kps = cv.take<vis_keypoint>((size_t)kcap * 2);
+    tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
+    tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
+    tp.d_warp = cv.take<float2>(kcap);
+    float* d_rot = cv.take<float>(9);
+    if (mfma) tp.d_descx = cv.take<int8_t>((size_t)kcap * 256);
+    const int32_t nk[2] = {n_q, n_t};
+    const MatchGuide g = {d_rot, radius};
+    HostStage hs(ctx);
+    hs.up(tp.d_desc, desc_q, (size_t)n_q * 32);
+    hs.up(tp.d_desc + (size_t)kcap * 32, desc_t, (size_t)n_t * 32);
+    hs.up(tp.d_kps, kps_q, (size_t)n_q * sizeof(vis_keypoint));
+    hs.up(tp.d_kps + kcap, kps_t, (size_t)n_t * sizeof(vis_keypoint));
+    hs.up(tp.d_nkp, nk, 8);
+    hs.up(d_rot, rot, 36);
+    hs.flush_ups();
+    hipLaunchKernelGGL(k_set_pair, dim3(1), dim3(1), 0, ctx->stream, tp.d_pair_q, tp.d_pair_t, 0, 1);
+    if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[4], ctx->stream);
+    rc = launch_expand(ctx, &tp, 0, 2);
+    if (!rc) rc = launch_match(ctx, &tp, 1, &g);
+    if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[5], ctx->stream);
+    const uint32_t* h12 = out12 && n_q ? (const uint32_t*)hs.down(tp.d_knn12, (size_t)n_q * 8) : nullptr;
+    const uint32_t* h21 = out21 && n_t ? (const uint32_t*)hs.down(tp.d_knn21, (size_t)n_t * 8) : nullptr;
+    tp = Plan();       // scratch-owned pointers: nothing to free
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    rc = hs.wait();
+    if (rc) return rc;
+    { float a = 0; if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[4], ctx->ev[5])) ctx->tm.ms_knn = a; }
+    if (h12) keys_to_dmatches(h12, n_q, out12);
+    if (h21) keys_to_dmatches(h21, n_t, out21);
     return VIS_OK;
 }
 
@@ -865,18 +986,20 @@ static int deliver_matches(const MatchFetch& f, vis_dmatch* good, int cap, int* 
     return VIS_OK;
 }
 
-extern "C" int vis_good_matches(vis_ctx* ctx, int slot_prev, int slot_cur, vis_dmatch* good, int cap, int* n_good,
-                                vis_dmatch* sym_out, int sym_cap, int* n_sym) {
-    if (!ctx) return VIS_E_INVALID;
+// vis_good_matches (rot == nullptr) and vis_good_matches_guided
+static int good_matches_slots(vis_ctx* ctx, int slot_prev, int slot_cur, const float* rot, float radius, vis_dmatch* good, int cap, int* n_good,
+                              vis_dmatch* sym_out, int sym_cap, int* n_sym) {
     (void)hipSetDevice(ctx->device);
     Plan* pl = ctx->single;
     int rc = pl ? vis_ensure_pin(ctx, ((size_t)pl->kcap + (size_t)pl->root * pl->root) * sizeof(vis_dmatch) + 4096) : VIS_E_STATE;
     if (!rc) rc = set_single_pair(ctx, pl, slot_prev, slot_cur);
+    MatchGuide g = {nullptr, 0.f};
+    if (!rc && rot) rc = single_guide(ctx, pl, rot, radius, &g);
     if (rc) return rc;
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[4], ctx->stream);
     rc = launch_expand(ctx, pl, slot_prev, 1);
     if (!rc && slot_cur != slot_prev) rc = launch_expand(ctx, pl, slot_cur, 1);
-    if (!rc) rc = launch_match(ctx, pl, 1);
+    if (!rc) rc = launch_match(ctx, pl, 1, rot ? &g : nullptr);
     if (rc) return rc;
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[5], ctx->stream);
     rc = launch_filter(ctx, pl, 1);
@@ -890,6 +1013,19 @@ extern "C" int vis_good_matches(vis_ctx* ctx, int slot_prev, int slot_cur, vis_d
       if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[4], ctx->ev[5])) ctx->tm.ms_knn = a;
       if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[5], ctx->ev[6])) ctx->tm.ms_filter = a; }
     return deliver_matches(f, good, cap, n_good, sym_out, sym_cap, n_sym);
+}
+
+extern "C" int vis_good_matches(vis_ctx* ctx, int slot_prev, int slot_cur, vis_dmatch* good, int cap, int* n_good,
+                                vis_dmatch* sym_out, int sym_cap, int* n_sym) {
+    if (!ctx) return VIS_E_INVALID;
+    return good_matches_slots(ctx, slot_prev, slot_cur, nullptr, 0.f, good, cap, n_good, sym_out, sym_cap, n_sym);
+}
+
+extern "C" int vis_good_matches_guided(vis_ctx* ctx, int slot_prev, int slot_cur, const float rot[9], float radius, vis_dmatch* good, int cap,
+                                       int* n_good, vis_dmatch* sym_out, int sym_cap, int* n_sym) {
+    if (!guide_args_ok(rot, radius, true)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    return good_matches_slots(ctx, slot_prev, slot_cur, rot, radius, good, cap, n_good, sym_out, sym_cap, n_sym);
 }
 
 static uint32_t dmatch_to_key(const vis_dmatch& m) {
@@ -1106,12 +1242,13 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
 // P = RANSAC + recoverPose (and vis_batch_align / _track).  Batch i+1's detect chain overlaps batch i's matcher (MFMA + LDS, little
 // VALU) and pose (latency-bound FP64): the record, gradient and matcher-output sets are used in turn, and the writer of a set waits
 // for the readers of its last use (ReaderGuard, vis_internal.h).
-extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int stages) {
-    if (!ctx || !d_frames) return VIS_E_INVALID;
+// guide != nullptr (vis_batch_run_guided): the match stage searches inside the window; nothing of it outlives the call
+static int batch_run_impl(vis_ctx* ctx, const uint8_t* d_frames, int n, int stages, const MatchGuide* guide) {
     Plan* pl = ctx->batch;
     if (!pl) return VIS_E_STATE;
     if (n < 1 || n > pl->B || ((uintptr_t)d_frames & 3)) return VIS_E_INVALID;
     (void)hipSetDevice(ctx->device);
+    if (guide) { const int rcw = ensure_warp(ctx, pl); if (rcw) return rcw; }
     hipStream_t sA = ctx->stream, sM = ctx->match_stream, sP = ctx->pose_stream;
     ctx->tm.launches_total = 0;
     const bool detect = (stages & VIS_STAGE_DETECT) != 0;
@@ -1196,7 +1333,7 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     if (stages & VIS_STAGE_MATCH) {
         VisRange r_("vis: knn + match filters");
         rc = launch_expand(ctx, pl, base, n + 1);
-        if (!rc) rc = launch_match(ctx, pl, n);
+        if (!rc) rc = launch_match(ctx, pl, n, guide);
         if (!rc) {
             if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[5], sM);
             // the filter writes matcher-output set `mo` (sets in turn, like the records): wait for what still reads THAT set -- the pose
@@ -1225,6 +1362,18 @@ extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int s
     pl->last_n = n; pl->last_base = base;
     pl->last_stages = stages; pl->run_seq++;                      // (what vis_batch_track checks)
     return VIS_OK;
+}
+
+extern "C" int vis_batch_run(vis_ctx* ctx, const uint8_t* d_frames, int n, int stages) {
+    if (!ctx || !d_frames) return VIS_E_INVALID;
+    return batch_run_impl(ctx, d_frames, n, stages, nullptr);
+}
+
+extern "C" int vis_batch_run_guided(vis_ctx* ctx, const uint8_t* d_frames, int n, int stages, const float* d_rot, float radius) {
+    if (!d_frames || !guide_args_ok(d_rot, radius, false) || !(stages & VIS_STAGE_MATCH)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    const MatchGuide g = {d_rot, radius};
+    return batch_run_impl(ctx, d_frames, n, stages, &g);
 }
 
 extern "C" int vis_batch_track_init(vis_ctx* ctx, const vis_se3f* pose) {

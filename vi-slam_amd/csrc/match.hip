@@ -11,13 +11,60 @@
 // Bit-exact against oracle/match.cpp (tests/test_match_gpu.py).
 #include "vis_internal.h"
 
+// ---- the window of the guided entry points (vis_bf_knn2_hamming_guided ...: "search by projection") ----------------------------------
+// VISystem::WarpFunctionRT (src/VISystem.cpp:771-860 of the reference) restated: where keypoint (u, v) of the CURRENT frame falls in the
+// PREVIOUS frame under the rotation `r` (row-major; the matrix vis_batch_f2f takes: current-frame rays -> previous frame, :1031-1033).
+// a, b and the projection in float, one rounding per operation (-ffp-contract=off); the three rows of r (a, b, 1) are summed left to right
+// in double and narrowed once, which is how OpenCV's single-precision Mat * Mat accumulates (written from memory and UNPINNED like the other
+// OpenCV restatements: DESIGN.md section 2).  Deviation: the reference divides by whatever X_2 is; here a point that does not lie in
+// front of the previous camera (!(X_2 > 0), NaN included) predicts (NaN, NaN) and so matches nothing.
+__device__ __forceinline__ float2 warp_point(float u, float v, const float* __restrict__ r, float fx, float fy, float cx, float cy) {
+    const float a = (u - cx) / fx, b = (v - cy) / fy;
+    float X[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) X[k] = (float)((double)r[3 * k] * (double)a + (double)r[3 * k + 1] * (double)b + (double)r[3 * k + 2]);
+    if (!(X[2] > 0.f)) { const float q = __int_as_float(0x7FC00000); return make_float2(q, q); }
+    return make_float2(fx * X[0] / X[2] + cx, fy * X[1] / X[2] + cy);
+}
+
+// one thread per keypoint of a pair's current record (pair_t): warp[pair * kcap + j] = its prediction under rot[9 pair ..]
+__global__ __launch_bounds__(256) void k_warp(const vis_keypoint* __restrict__ kps, const int32_t* __restrict__ nkp, int kcap,
+                                              const int32_t* __restrict__ pair_t, const float* __restrict__ rot,
+                                              float fx, float fy, float cx, float cy, float2* __restrict__ warp) {
+    const int pair = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+    const int rt = pair_t[pair];
+    if (rt < 0 || j >= min(nkp[rt], kcap)) return;
+    const vis_keypoint* k = kps + (size_t)rt * kcap + j;
+    warp[(size_t)pair * kcap + j] = warp_point(k->x, k->y, rot + 9 * (size_t)pair, fx, fy, cx, cy);
+}
+
+// Previous keypoint i at (x_i, y_i) and current keypoint j predicted at (x'_j, y'_j) may be matched iff this holds: a square window, false
+// for a NaN.  Both directions of a pair call it on the same two positions (one of them the row a lane keeps, the other the row it sweeps);
+// |a - b| and |b - a| are the same float, so the order of the two sets cannot change the answer and admissibility is symmetric.
+__device__ __forceinline__ bool window_admits(float sx, float sy, float fx, float fy, float radius) {
+    return (fabsf(sx - fx) <= radius) & (fabsf(sy - fy) <= radius);
+}
+// where the positions of one side of a pair are: the previous frame's record (x, y of its keypoints) or the current frame's predictions
+struct WinSide { const float* p; int stride; };
+__device__ __forceinline__ WinSide win_side(const vis_keypoint* kps, const float2* warp, int kcap, int pair, int rec, bool previous) {
+    static_assert(sizeof(vis_keypoint) == 28 && sizeof(float2) == 8, "strides in floats");
+    if (previous) return WinSide{&kps[(size_t)rec * kcap].x, 7};
+    return WinSide{reinterpret_cast<const float*>(warp + (size_t)pair * kcap), 2};
+}
+
 // One lane = one query row; the train descriptor of the current iteration is wave-uniform, so the
 // compiler keeps it in SGPRs (s_load_dwordx8) and the inner loop is 8 x (v_xor, v_bcnt accumulate)
 // + 3 ops of top-2 maintenance on the packed key (dist << 16 | trainIdx).  Keeping the two smallest
 // keys reproduces cv::batchDistance's order: ascending distance, ties -> lower train index first.
+//
+// WIN (the guided entry points): a (query, train) couple competes only when the window predicate holds (window_admits below).  The
+// train row's position is wave-uniform like its descriptor (scalar loads); an inadmissible couple's key becomes 0xFFFFFFFF, which the
+// min / max maintenance leaves where "no neighbour" already sits.  WIN = false is the kernel as it was.
+template <bool WIN>
 __global__ __launch_bounds__(256) void k_knn2(const uint8_t* __restrict__ desc, const int32_t* __restrict__ nkp, int kcap,
                                               const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_t,
-                                              uint32_t* __restrict__ knn12, uint32_t* __restrict__ knn21) {
+                                              uint32_t* __restrict__ knn12, uint32_t* __restrict__ knn21,
+                                              const vis_keypoint* __restrict__ kps, const float2* __restrict__ warp, float radius) {
     const int pair = blockIdx.y, dir = blockIdx.z;
     const int rq = dir == 0 ? pair_q[pair] : pair_t[pair];
     const int rt = dir == 0 ? pair_t[pair] : pair_q[pair];
@@ -33,6 +80,15 @@ __global__ __launch_bounds__(256) void k_knn2(const uint8_t* __restrict__ desc, 
     const uint4 qa = Q0[0], qb = Q0[1], ra = Q1[0], rb = Q1[1];
     const uint4* T = reinterpret_cast<const uint4*>(desc + (size_t)rt * kcap * 32);
     uint32_t k0 = 0xFFFFFFFFu, k1 = 0xFFFFFFFFu, j0 = 0xFFFFFFFFu, j1 = 0xFFFFFFFFu;
+    // window: positions of this lane's two query rows, and where the train rows' positions are read (floats, stride in floats)
+    float qx0 = 0.f, qy0 = 0.f, qx1 = 0.f, qy1 = 0.f;
+    const float* tpos = nullptr; int tstride = 0;
+    if constexpr (WIN) {
+        const WinSide qs = win_side(kps, warp, kcap, pair, rq, dir == 0), ts = win_side(kps, warp, kcap, pair, rt, dir != 0);
+        const size_t a = (size_t)min(q0i, nq - 1) * qs.stride, b = (size_t)min(q1i, nq - 1) * qs.stride;
+        qx0 = qs.p[a]; qy0 = qs.p[a + 1]; qx1 = qs.p[b]; qy1 = qs.p[b + 1];
+        tpos = ts.p; tstride = ts.stride;
+    }
 #define KNN_DIST(xa, xb, ta, tb, d_) do {                                                          \
         d_ = __popc((xa).x ^ (ta).x);                                                              \
         d_ += __popc((xa).y ^ (ta).y); d_ += __popc((xa).z ^ (ta).z); d_ += __popc((xa).w ^ (ta).w); \
@@ -41,7 +97,12 @@ __global__ __launch_bounds__(256) void k_knn2(const uint8_t* __restrict__ desc, 
 #define KNN_STEP(ta, tb, tt) do {                                                                   \
         uint32_t da_, db_;                                                                          \
         KNN_DIST(qa, qb, ta, tb, da_); KNN_DIST(ra, rb, ta, tb, db_);                               \
-        const uint32_t ka_ = (da_ << 16) | (uint32_t)(tt), kb_ = (db_ << 16) | (uint32_t)(tt);      \
+        uint32_t ka_ = (da_ << 16) | (uint32_t)(tt), kb_ = (db_ << 16) | (uint32_t)(tt);            \
+        if constexpr (WIN) {                                                                        \
+            const float tx_ = tpos[(size_t)(tt) * tstride], ty_ = tpos[(size_t)(tt) * tstride + 1]; \
+            if (!window_admits(tx_, ty_, qx0, qy0, radius)) ka_ = 0xFFFFFFFFu;                      \
+            if (!window_admits(tx_, ty_, qx1, qy1, radius)) kb_ = 0xFFFFFFFFu;                      \
+        }                                                                                           \
         k1 = min(k1, max(k0, ka_)); k0 = min(k0, ka_);                                              \
         j1 = min(j1, max(j0, kb_)); j0 = min(j0, kb_); } while (0)
     // the train descriptors are wave-uniform (SGPRs): groups of KNN_U rows are fetched with back-to-back
@@ -117,11 +178,18 @@ __device__ __forceinline__ int imed3(int a, int b, int c) {
 // NC = column groups of 32 fixed descriptors per wave.  NC = 2: every 16-byte LDS read of a swept row feeds two MFMA chains
 // (the LDS pipe and the staging traffic per MFMA halve, one barrier per 8 MFMAs instead of 4) at the price of 32 + 32
 // operand / accumulator registers per lane.
-template <int NC>
+// WIN (the guided entry points): the lane keeps the position of its fixed column(s) in registers, the positions of the 32 swept rows are
+// staged beside the descriptor tile (8 B per row behind the 32 descriptor rows of each buffer; a row past the end of the swept set is
+// staged as NaN), and an element whose couple fails window_admits becomes KNN_NONE before the merge.  Masked keys are equal, so every
+// tile is merged with the two-instruction form of the tail path (v_med3_i32, v_min_i32: right for any keys); the 1.5-instruction form
+// relies on distinct keys.  KNN_NONE is a float that 16 cannot change, so a masked key survives any number of ageings.  No tile is
+// skipped by position: keypoints are ordered by level and response.  WIN = false is the kernel as it was.
+template <int NC, bool WIN>
 __global__ __launch_bounds__(256) void k_knn_mfma(const int8_t* __restrict__ X, const int32_t* __restrict__ nkp, int kcap,
                                                   const int32_t* __restrict__ pair_q, const int32_t* __restrict__ pair_t,
-                                                  uint32_t* __restrict__ knn12, uint32_t* __restrict__ knn21, int npairs, int nchunks) {
-    __shared__ __attribute__((aligned(16))) uint4 tile[2][32 * KM_ROW];
+                                                  uint32_t* __restrict__ knn12, uint32_t* __restrict__ knn21, int npairs, int nchunks,
+                                                  const vis_keypoint* __restrict__ kps, const float2* __restrict__ warp, float radius) {
+    __shared__ __attribute__((aligned(16))) uint4 tile[2][32 * KM_ROW + (WIN ? 16 : 0)];
     // XCD-aware mapping: workgroups are dealt round-robin over the 8 XCDs (private L2 each).  All chunks and both
     // directions of one frame pair go to ONE XCD, so the pair's two descriptor sets are fetched into one L2 once
     // (rocprofv3 FETCH_SIZE was 2.3 GB per 512 pairs with a plain (chunk, pair, dir) grid: every chunk re-fetched the
@@ -153,14 +221,30 @@ __global__ __launch_bounds__(256) void k_knn_mfma(const int8_t* __restrict__ X, 
             bf[c][ks] = v8i{x[0] ^ (int)0x88888888, x[1] ^ (int)0x88888888, x[2] ^ (int)0x88888888, x[3] ^ (int)0x88888888, 0, 0, 0, 0};
         }
     }
+    // window: the position of each fixed column, and where the swept rows' positions are read
+    float fpx[NC], fpy[NC];
+    const float* spos = nullptr; int sstride = 0;
+    if constexpr (WIN) {
+        const WinSide fs = win_side(kps, warp, kcap, pair, rf, dir == 0), ss = win_side(kps, warp, kcap, pair, rs, dir != 0);
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            const size_t o = (size_t)min(fidx0 + 32 * c, nf - 1) * fs.stride;
+            fpx[c] = fs.p[o]; fpy[c] = fs.p[o + 1];
+        }
+        spos = ss.p; sstride = ss.stride;
+    }
     const int8_t* xs = X + (size_t)rs * kcap * 128;
     const int ntiles = (ns + 31) / 32;
     // staging of the next swept tile (32 rows x 128 B = one uint4 per thread): the global load is issued before the MFMA chain of
     // the current tile, the LDS write after it (the load latency is covered by the wave's own compute, not only by other waves)
     const int st_row = tid >> 3, st_c = tid & 7;
     uint4 pre;
-#define STAGE_LOAD(t_) do { pre = *reinterpret_cast<const uint4*>(xs + (size_t)min((t_) * 32 + st_row, ns - 1) * 128 + 16 * st_c); } while (0)
-#define STAGE_STORE(buf_) do { tile[buf_][st_row * KM_ROW + st_c] = pre; } while (0)
+    float2 ppre;                 // WIN: the position of swept row st_row of the next tile (the thread with st_c == 0 stages it)
+#define STAGE_LOAD(t_) do { pre = *reinterpret_cast<const uint4*>(xs + (size_t)min((t_) * 32 + st_row, ns - 1) * 128 + 16 * st_c);      \
+        if constexpr (WIN) { if (st_c == 0) { const int r_ = (t_) * 32 + st_row; const float q_ = __int_as_float(0x7FC00000);              \
+            ppre = r_ < ns ? make_float2(spos[(size_t)r_ * sstride], spos[(size_t)r_ * sstride + 1]) : make_float2(q_, q_); } } } while (0)
+#define STAGE_STORE(buf_) do { tile[buf_][st_row * KM_ROW + st_c] = pre;                                                                \
+        if constexpr (WIN) { if (st_c == 0) reinterpret_cast<float2*>(&tile[buf_][32 * KM_ROW])[st_row] = ppre; } } while (0)
     // The dot products are multiples of 8192 after the 2^20 offset, so the 13 low bits of an accumulator are free: every chain STARTS
     // from 2^20 + 8192 + accumulator register, and the finished accumulator IS the key 8192 * (Hamming + 1) + register of a row of the
     // CURRENT tile -- no per-element key construction.  The tile index is carried by AGE instead of by the start values (round 6: 16
@@ -198,7 +282,23 @@ __global__ __launch_bounds__(256) void k_knn_mfma(const int8_t* __restrict__ X, 
             k0[c] = __float_as_int(__int_as_float(k0[c]) - 16.f);
             k1[c] = __float_as_int(__int_as_float(k1[c]) - 16.f);
         }
-        if (t * 32 + 32 <= ns) {
+        if constexpr (WIN) {
+            // register r of a lane is row 4 h + (r & 3) + 8 (r >> 2) of the tile: four consecutive rows = two float4 of positions
+            const float4* pp = reinterpret_cast<const float4*>(&tile[t & 1][32 * KM_ROW]) + 2 * h;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const float4 pa = pp[4 * g], pb = pp[4 * g + 1];
+                const float sx[4] = {pa.x, pa.z, pb.x, pb.z}, sy[4] = {pa.y, pa.w, pb.y, pb.w};
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+#pragma unroll
+                    for (int c = 0; c < NC; c++) {
+                        const int key = window_admits(sx[i], sy[i], fpx[c], fpy[c], radius) ? __float_as_int(acc[c][4 * g + i]) : KNN_NONE;
+                        k1[c] = imed3(k0[c], k1[c], key);
+                        k0[c] = min(k0[c], key);
+                    }
+            }
+        } else if (t * 32 + 32 <= ns) {
             // two keys per step, three instructions (1.5 per key instead of 2): the second smallest of {k0, k1, x, y} is k1 or the
             // second smallest of {k0, x, y} (k1 >= k0 >= the smallest of those three); all keys are distinct (they carry their tile
             // and register), so the order in which they are merged cannot change the result
@@ -400,22 +500,45 @@ int launch_expand(vis_ctx* ctx, Plan* pl, int rec_first, int rec_count) {
     return VIS_OK;
 }
 
-int launch_match(vis_ctx* ctx, Plan* pl, int npairs) {
+// k_warp over the current record of every pair (pl->d_pair_t) into d_warp (npairs x pl->kcap); d_rot: 9 floats per pair
+int launch_warp(vis_ctx* ctx, Plan* pl, int npairs, const float* d_rot, float2* d_warp) {
     if (npairs <= 0) return VIS_OK;
+    hipLaunchKernelGGL(k_warp, dim3((pl->kcap + 255) / 256, npairs), dim3(256), 0, ctx->stream, pl->d_kps, pl->d_nkp, pl->kcap, pl->d_pair_t,
+                       d_rot, (float)ctx->p.fx, (float)ctx->p.fy, (float)ctx->p.cx, (float)ctx->p.cy, d_warp);
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+// guide != nullptr: the windowed 2-NN of the guided entry points -- k_warp, then the same choice of kernel with the window predicate
+int launch_match(vis_ctx* ctx, Plan* pl, int npairs, const MatchGuide* guide) {
+    if (npairs <= 0) return VIS_OK;
+    if (guide) {
+        if (!pl->d_warp || !pl->d_kps) { ctx->err = "guided match without a prediction buffer (internal)"; return VIS_E_STATE; }
+        const int rc = launch_warp(ctx, pl, npairs, guide->d_rot, pl->d_warp);
+        if (rc) return rc;
+    }
     if (pl->d_descx && pl->kcap <= 16384) {
         const int per_wg = 128 * 2;          // k_knn_mfma<2>: 128 * NC fixed descriptors per workgroup
         const int nchunks = (pl->kcap + per_wg - 1) / per_wg;
         dim3 grid(8 * ((npairs + 7) / 8) * 2 * nchunks);
-        hipLaunchKernelGGL(k_knn_mfma<2>, grid, dim3(256), 0, ctx->stream, pl->d_descx, pl->d_nkp, pl->kcap,
-                           pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, npairs, nchunks);
+        if (guide)
+            hipLaunchKernelGGL((k_knn_mfma<2, true>), grid, dim3(256), 0, ctx->stream, pl->d_descx, pl->d_nkp, pl->kcap,
+                               pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, npairs, nchunks, pl->d_kps, pl->d_warp, guide->radius);
+        else
+            hipLaunchKernelGGL((k_knn_mfma<2, false>), grid, dim3(256), 0, ctx->stream, pl->d_descx, pl->d_nkp, pl->kcap,
+                               pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, npairs, nchunks, nullptr, nullptr, 0.f);
         HIPCHK(ctx, hipGetLastError());
         return VIS_OK;
     }
     // small problems: one wave per block so a single pair still spreads over many CUs
     const int bs = (npairs * ((pl->kcap + 255) / 256) * 2 >= 512) ? 256 : 64;
     dim3 grid((pl->kcap + 2 * bs - 1) / (2 * bs), npairs, 2);
-    hipLaunchKernelGGL(k_knn2, grid, dim3(bs), 0, ctx->stream, pl->d_desc, pl->d_nkp, pl->kcap,
-                       pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21);
+    if (guide)
+        hipLaunchKernelGGL(k_knn2<true>, grid, dim3(bs), 0, ctx->stream, pl->d_desc, pl->d_nkp, pl->kcap,
+                           pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, pl->d_kps, pl->d_warp, guide->radius);
+    else
+        hipLaunchKernelGGL(k_knn2<false>, grid, dim3(bs), 0, ctx->stream, pl->d_desc, pl->d_nkp, pl->kcap,
+                           pl->d_pair_q, pl->d_pair_t, pl->d_knn12, pl->d_knn21, nullptr, nullptr, 0.f);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

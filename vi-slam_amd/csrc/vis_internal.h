@@ -103,6 +103,9 @@ struct Plan {
     uint8_t* d_desc = nullptr;               // nrec x kcap x 32
     int32_t* d_nkp = nullptr;                // nrec
     int8_t* d_descx = nullptr;               // nrec x kcap x 128: descriptor bits as FP4 (e2m1) +1/-1, two per byte (MFMA matcher operand)
+    // guided matching (match.hip k_warp): npairs x kcap predictions + 16 floats (the rotation of a single-frame call); allocated by the
+    // first guided call of the plan (ensure_warp), so a context that never asks for a window has the footprint it always had
+    float2* d_warp = nullptr;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -364,7 +367,10 @@ int launch_copy_jobs(vis_ctx* ctx, hipStream_t st, int njobs, void* const* dst, 
 int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int rec0, int carry_rec = -1, hipEvent_t after_resize = nullptr, const ReaderGuard* records_free = nullptr);   // carry_rec >= 0: copy that record to rec0 - 1 before k_describe; after_resize: recorded behind the pyramid launches; records_free: waited for before the chain's first write to the record set
 int build_fast_tiles(vis_ctx* ctx, Plan* pl);
 int launch_expand(vis_ctx* ctx, Plan* pl, int rec_first, int rec_count);
-int launch_match(vis_ctx* ctx, Plan* pl, int npairs);
+struct MatchGuide { const float* d_rot; float radius; };             // 9 floats per pair (row-major), window half-side in pixels
+int ensure_warp(vis_ctx* ctx, Plan* pl);                              // api.hip: pl->d_warp, allocated once per plan
+int launch_warp(vis_ctx* ctx, Plan* pl, int npairs, const float* d_rot, float2* d_warp);
+int launch_match(vis_ctx* ctx, Plan* pl, int npairs, const MatchGuide* guide = nullptr);   // guide: the windowed 2-NN (k_warp first; needs pl->d_warp)
 int launch_filter(vis_ctx* ctx, Plan* pl, int npairs);
 int launch_pose(vis_ctx* ctx, Plan* pl, int npairs);
 int launch_keyframe_links(vis_ctx* ctx, Plan* pl, int set, int n);   // keyframe.hip: carry the last saved record into the set, gate + link the batch

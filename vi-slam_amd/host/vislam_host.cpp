@@ -105,8 +105,15 @@ void Matcher::computeMatches() {                                                
     const int n1 = descriptors_1.rows, n2 = descriptors_2.rows;
     vector<vis_dmatch> o12(2 * (size_t)std::max(n1, 1)), o21(2 * (size_t)std::max(n2, 1));
     clock_t begin = clock();
-    int rc = (slot1 >= 0 && slot2 >= 0) ? vis_bf_knn2_hamming(ctx, slot1, slot2, o12.data(), o21.data())
+    int rc;
+    if (!guideOn)
+        rc = (slot1 >= 0 && slot2 >= 0) ? vis_bf_knn2_hamming(ctx, slot1, slot2, o12.data(), o21.data())
                                         : vis_bf_knn2_hamming_host(ctx, descriptors_1.data, n1, descriptors_2.data, n2, o12.data(), o21.data());
+    else if (slot1 >= 0 && slot2 >= 0) rc = vis_bf_knn2_hamming_guided(ctx, slot1, slot2, guideRot, guideRadius, o12.data(), o21.data());
+    else if ((int)keypoints_1.size() != n1 || (int)keypoints_2.size() != n2) rc = VIS_E_INVALID;   // the window needs one keypoint per descriptor
+    else rc = vis_bf_knn2_hamming_guided_host(ctx, descriptors_1.data, reinterpret_cast<const vis_keypoint*>(keypoints_1.data()), n1,
+                                              descriptors_2.data, reinterpret_cast<const vis_keypoint*>(keypoints_2.data()), n2,
+                                              guideRot, guideRadius, o12.data(), o21.data());
     if (rc) VisDevice::fail(rc, "computeMatches");
     clock_t knn2 = clock();
     unpack_knn(o12, n1, aux_matches1); unpack_knn(o21, n2, aux_matches2);
@@ -127,8 +134,10 @@ void Matcher::computeBestMatches(int n_cells) {                                 
     vector<vis_dmatch> good(1024), sym((size_t)std::max(n1, 1));
     int ng = 0, ns = 0, rc;
     clock_t begin = clock();
-    if (slot1 >= 0 && slot2 >= 0) rc = vis_good_matches(ctx, slot1, slot2, good.data(), 1024, &ng, sym.data(), (int)sym.size(), &ns);
-    else {
+    if (slot1 >= 0 && slot2 >= 0)
+        rc = guideOn ? vis_good_matches_guided(ctx, slot1, slot2, guideRot, guideRadius, good.data(), 1024, &ng, sym.data(), (int)sym.size(), &ns)
+                     : vis_good_matches(ctx, slot1, slot2, good.data(), 1024, &ng, sym.data(), (int)sym.size(), &ns);
+    else {                                                // (the lists of computeMatches: already windowed when the guide is on)
         vector<vis_dmatch> k12(2 * (size_t)std::max(n1, 1)), k21(2 * (size_t)std::max(n2, 1));
         auto pack = [](const vector<vector<DMatch> >& a, vector<vis_dmatch>& o) {
             for (size_t q = 0; q < a.size(); q++) for (int k = 0; k < 2; k++) {
@@ -173,6 +182,11 @@ void MatcherGPU::setGPUMatcher(int _matcher) {                                  
     else if (_matcher == USE_BRUTE_FORCE_GPU) { cout << "L2 brute force is outside the hot path; using Hamming" << endl; useGPU = true; }
     else { useGPU = false; setMatcher(_matcher); }
 }
+void MatcherGPU::setRotationGuide(const Matx33f& rotation, float radius) {
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) guideRot[3 * r + c] = rotation(r, c);
+    guideRadius = radius; guideOn = true;
+}
+void MatcherGPU::clearRotationGuide() { guideOn = false; }
 void MatcherGPU::computeGPUMatches() {                                            // :44-66
     descriptorsGPU[0].release(); descriptorsGPU[1].release();
     descriptorsGPU[0].slot = slot1; descriptorsGPU[1].slot = slot2;               // "upload": descriptors are already resident
@@ -562,6 +576,23 @@ Mat VISystem::getProjectionMat(Mat cameraMat, Mat rotationMat, Mat translationMa
             P.at<float>(r, c) = s;
         }
     return P;
+}
+void VISystem::WarpFunctionRT(vector<KeyPoint> inPoints, Mat rotationMat, Mat, vector<KeyPoint>& outPoints) {   // :771-860
+    const int n = (int)inPoints.size();
+    if (n == 0) return;
+    vis_ctx* ctx = VisDevice::get();
+    vis_params p; vis_get_params(ctx, &p);
+    if (p.fx != (double)fx_[0] || p.fy != (double)fy_[0] || p.cx != (double)cx_[0] || p.cy != (double)cy_[0]) {
+        p.fx = fx_[0]; p.fy = fy_[0]; p.cx = cx_[0]; p.cy = cy_[0];
+        const int rc = vis_set_params(ctx, &p);
+        if (rc) VisDevice::fail(rc, "WarpFunctionRT");
+    }
+    float rot[9];
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) rot[3 * r + c] = rotationMat.at<float>(r, c);
+    vector<float> xy(2 * (size_t)n);
+    const int rc = vis_warp_keypoints(ctx, reinterpret_cast<const vis_keypoint*>(inPoints.data()), n, rot, xy.data());
+    if (rc) VisDevice::fail(rc, "WarpFunctionRT");
+    for (int i = 0; i < n; i++) { KeyPoint k; k.pt.x = xy[2 * (size_t)i]; k.pt.y = xy[2 * (size_t)i + 1]; outPoints.push_back(k); }   // :830-843
 }
 void VISystem::Triangulate(vector<KeyPoint> inPoints1, vector<KeyPoint> inPoints2) {  // :862-923
     const int m = (int)std::min(inPoints1.size(), inPoints2.size());

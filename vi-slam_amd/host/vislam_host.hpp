@@ -100,6 +100,8 @@ public:
     double elapsed_knn1 = 0, elapsed_knn2 = 0, elapsed_symMatches = 0, elapsed_sortMatches = 0, elapsed_bestMatches = 0;
 protected:
     int slot1 = -1, slot2 = -1;                          // set by CameraGPU when both descriptor sets are device resident
+    // rotation guide (MatcherGPU::setRotationGuide): off unless set; computeMatches / computeBestMatches then search inside the window
+    bool guideOn = false; float guideRot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}; float guideRadius = 0.f;
     friend class CameraGPU;
 };
 
@@ -109,6 +111,11 @@ public:
     void setGPUFrames(Mat _frame1, Mat _frame2);         // declared at :20, never defined in the reference: defined here (keeps the images)
     void computeGPUMatches();
     void setGPUMatcher(int _matcher);
+    // Not in the reference: search for neighbours only inside a square window of `radius` pixels around the position that `rotation`
+    // (current-frame rays -> previous frame, the matrix of F2FRansac) predicts for a keypoint of the second set in the first
+    // (vis_bf_knn2_hamming_guided; VISystem::WarpFunctionRT is the prediction).  Off by default and after clearRotationGuide().
+    void setRotationGuide(const Matx33f& rotation, float radius);
+    void clearRotationGuide();
     bool useGPU = false;
     int matcherType = 0;
     Ptr<cuda::DescriptorMatcher> matcherGPU;             // :23 -- handle of the device matcher (createBFMatcher(NORM_HAMMING))
@@ -229,6 +236,9 @@ public:
     // coordinates with the single focal fx_[0].
     void Triangulate(vector<KeyPoint> inPoints1, vector<KeyPoint> inPoints2);
     Mat getProjectionMat(Mat cameraMat, Mat rotationMat, Mat translationMat);        // :1872-1880: cameraMat * [rotation | translation], CV_32F
+    // :771-860 on the device (vis_warp_keypoints): where the keypoints fall under rotationMat (3x3 CV_32F) with the level-0 intrinsics;
+    // translationMat is ignored, as the reference's live lines ignore it.  A point with X_2 <= 0 comes back as (NaN, NaN).
+    void WarpFunctionRT(vector<KeyPoint> inPoints, Mat rotationMat, Mat translationMat, vector<KeyPoint>& outPoints);
     bool initialized = false, distortion_valid = false, depth_available = false;
     int num_keyframes = 0, num_max_keyframes = 0, min_features = 0, start_index = 0;
     Mat map1, map2;

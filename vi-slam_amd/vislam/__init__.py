@@ -178,6 +178,7 @@ ABI_SYMBOLS = [
     "vis_f2f_batch", "vis_batch_f2f", "vis_filter_keypoints_batch", "vis_batch_filter_keypoints", "vis_filter_keypoints",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
+    "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
 ]
 
 
@@ -257,6 +258,13 @@ def _load():
         lib.vis_get_align_weights.argtypes = [vp, C.POINTER(AlignWeights)]
     if hasattr(lib, "vis_debug_pyramid_level"):         # (absent from older A/B builds)
         lib.vis_debug_pyramid_level.argtypes = [vp, ci, ci, ci, vp, ci]
+    if hasattr(lib, "vis_batch_run_guided"):            # (absent from older A/B builds)
+        cf = C.c_float
+        lib.vis_warp_keypoints.argtypes = [vp, vp, ci, vp, vp]
+        lib.vis_bf_knn2_hamming_guided.argtypes = [vp, ci, ci, vp, cf, vp, vp]
+        lib.vis_bf_knn2_hamming_guided_host.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, cf, vp, vp]
+        lib.vis_good_matches_guided.argtypes = [vp, ci, ci, vp, cf, vp, ci, ip, vp, ci, ip]
+        lib.vis_batch_run_guided.argtypes = [vp, vp, ci, ci, vp, cf]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -720,6 +728,45 @@ class Context:
                   "vis_bf_knn2_hamming_host")
         return o12, o21
 
+    # -- rotation-guided matching: the 2-NN inside the window a rotation predicts (VISystem::WarpFunctionRT + the matcher) --
+    def warp_keypoints(self, kps, rot):
+        kps = np.ascontiguousarray(kps, KEYPOINT_DTYPE)
+        rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+        out = np.zeros((len(kps), 2), np.float32)
+        self._chk(lib.vis_warp_keypoints(self._h, _ptr(kps), len(kps), _ptr(rot), _ptr(out)), "vis_warp_keypoints")
+        return out
+
+    def bf_knn2_hamming_guided(self, slot_q, slot_t, nq, nt, rot, radius):
+        rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+        o12 = np.zeros((nq, 2), DMATCH_DTYPE)
+        o21 = np.zeros((nt, 2), DMATCH_DTYPE)
+        self._chk(lib.vis_bf_knn2_hamming_guided(self._h, slot_q, slot_t, _ptr(rot), radius, _ptr(o12), _ptr(o21)), "vis_bf_knn2_hamming_guided")
+        return o12, o21
+
+    def bf_knn2_hamming_guided_host(self, d1, k1, d2, k2, rot, radius):
+        d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 32)
+        d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 32)
+        k1 = np.ascontiguousarray(k1, KEYPOINT_DTYPE)
+        k2 = np.ascontiguousarray(k2, KEYPOINT_DTYPE)
+        if len(k1) != len(d1) or len(k2) != len(d2):
+            raise ValueError("one keypoint per descriptor")
+        rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+        o12 = np.zeros((len(d1), 2), DMATCH_DTYPE)
+        o21 = np.zeros((len(d2), 2), DMATCH_DTYPE)
+        self._chk(lib.vis_bf_knn2_hamming_guided_host(self._h, _ptr(d1), _ptr(k1), len(d1), _ptr(d2), _ptr(k2), len(d2), _ptr(rot), radius,
+                                                      _ptr(o12), _ptr(o21)), "vis_bf_knn2_hamming_guided_host")
+        return o12, o21
+
+    def good_matches_guided(self, slot_prev, slot_cur, rot, radius, sym_cap=65536):
+        rot = np.ascontiguousarray(rot, np.float32).reshape(9)
+        root2 = 1024
+        good = np.zeros(root2, DMATCH_DTYPE)
+        sym = np.zeros(sym_cap, DMATCH_DTYPE)
+        ng, ns = C.c_int(0), C.c_int(0)
+        self._chk(lib.vis_good_matches_guided(self._h, slot_prev, slot_cur, _ptr(rot), radius, _ptr(good), root2, C.byref(ng), _ptr(sym),
+                                              sym_cap, C.byref(ns)), "vis_good_matches_guided")
+        return good[:ng.value].copy(), sym[:ns.value].copy()
+
     # -- Matcher::computeBestMatches ----------------------------------------------------------------------
     def good_matches(self, slot_prev, slot_cur, sym_cap=65536):
         root2 = 1024
@@ -847,6 +894,10 @@ class Context:
 
     def batch_run(self, dev_ptr, n_frames, stages=STAGE_ALL):
         self._chk(lib.vis_batch_run(self._h, C.c_void_p(dev_ptr), n_frames, stages), "vis_batch_run")
+
+    def batch_run_guided(self, dev_ptr, n_frames, d_rot_ptr, radius, stages=STAGE_ALL):
+        """batch_run whose match stage searches inside the window: d_rot_ptr = n_frames x 9 floats in device memory, in use until batch_sync"""
+        self._chk(lib.vis_batch_run_guided(self._h, C.c_void_p(dev_ptr), n_frames, stages, C.c_void_p(d_rot_ptr), radius), "vis_batch_run_guided")
 
     def batch_sync(self):
         self._chk(lib.vis_batch_sync(self._h), "vis_batch_sync")
