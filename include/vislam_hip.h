@@ -200,7 +200,9 @@ int  vis_good_matches_host(vis_ctx* ctx, const vis_keypoint* kps1, int n1,
  * p1xy/p2xy: m x 2 floats (pixels).  E row-major. mask may be NULL. */
 int  vis_essential_ransac(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m,
                           double E[9], uint8_t* mask, int* n_inliers, int* iters_run);
-/* replaces cv::recoverPose(E,p1,p2,R,t,focal,pp), src/VISystem.cpp:1701 */
+/* replaces cv::recoverPose(E,p1,p2,R,t,focal,pp), src/VISystem.cpp:1701.
+ * A zero or rank-1 E -- such as the E vis_essential_ransac returns when it finds no model -- yields
+ * NaN R, NaN t and n_good = 0 (the return code is still VIS_OK). */
 int  vis_recover_pose(vis_ctx* ctx, const double E[9], const float* p1xy, const float* p2xy,
                       int m, double R[9], double t[3], int* n_good);
 /* VISystem::F2FRansac, src/VISystem.cpp:612-769.  rot: 3x3 row-major f32 (IMU rotation),
