@@ -565,6 +565,73 @@ int  vis_batch_filter_keypoints(vis_ctx* ctx, int n, const float* d_rot, const f
 int  vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keypoint* pts2, int m, const float rot[9], const float t[3],
                           double threshold, uint8_t* keep, int* n_keep);
 
+/* ---- homography RANSAC and the H-or-E model choice: the other half of a two-view initialiser (Mur-Artal, Montiel, Tardos: ORB-SLAM, 2015,
+ * section IV; the reference has neither).  For a standing or purely rotating camera, a planar scene or points at infinity the essential
+ * matrix of the pose stage is not determined by the correspondences; a homography explains such a pair, and
+ * comparing the two models' scores flags it.  Acting on the flag is the caller's business.
+ * Coordinates: the pose stage's, x = ((double)u - cx) * (1 / fx), y = ((double)v - cy) * (1 / fx) with the single focal of findEssentialMat,
+ * so H is the Euclidean homography R + t n^T / d up to scale.  Thresholds, once on the host in double: s2 = (sigma_px * (1 / fx))^2,
+ * t_h = chi2_h * s2, t_e = chi2_e * s2.  No multiply-add is contracted; dot products are summed left to right.
+ * Hypothesis j of hp.iters samples i_k = (d_draws[4 j + k] & 0x7fffffff) % m, k = 0 ... 3 (ONE table of iters x 4 draws serves every pair, so a
+ * stream's records do not depend on how it is cut into batches).  Minimal solver, closed form over projective bases: with p_k = (x_k, y_k, 1)
+ * the four source points, l0 = (p1 x p2) . p3, l1 = (p2 x p0) . p3, l2 = (p0 x p1) . p3, A = [l0 p0 | l1 p1 | l2 p2], B likewise from the
+ * target points, H = B adj(A) (adj: rows c1 x c2, c2 x c0, c0 x c1 of the columns).  The iteration is skipped and counted in n_degenerate
+ * when two indices are equal, when an l or (p0 x p1) . p2 of either side is zero or not finite, or when H does not reproduce its own
+ * sample: one of the eight transfer tests below of the four sample points fails at t_h * 2^-20.
+ * Per-point test, division-free: (U, V, w) = H (x1, y1, 1), e12 = (U - x2 w)^2 + (V - y2 w)^2, forward iff e12 <= t_h (w w); backward the
+ * same with G = adj(H) on (x2, y2, 1) against (x1, y1); an inlier passes both; a NaN fails.  The first iteration with the largest count > 0
+ * wins.  mask receives the winner's inlier bytes (zeros when no iteration won); bytes beyond the pair's correspondences are left untouched.
+ * Scores of the winner -- ORB-SLAM's CheckHomography / CheckFundamental, restated from the paper, not from its code: with d = e12 / (w w),
+ * score_h = sum over the points and both directions of (d <= t_h ? chi2_h - d / s2 : 0).  With an E: l2 = E x1, l1 = E^T x2, r = x2 . l2;
+ * each direction adds chi2_h - d / s2, d = r^2 / (l_a^2 + l_b^2), when l_a^2 + l_b^2 > 0 and r^2 <= t_e (l_a^2 + l_b^2); n_inliers_e counts
+ * the points that pass both; a zero or NaN E scores 0.  E is scored whether or not an H won.  Both sums are taken in one fixed order (64
+ * partial sums over i mod 64 in rising i, then a fixed tree), without floating-point atomics: two runs are byte-identical.
+ * Decision: H is offered when n_inliers >= min_inliers, E when it is given and n_inliers_e >= min_inliers; model = VIS_MODEL_HOMOGRAPHY when H
+ * is offered and either E is not or score_h > h_ratio (score_h + score_e); else VIS_MODEL_ESSENTIAL when E is offered; else VIS_MODEL_NONE.
+ * H is normalised last (unit Frobenius norm, negated when its determinant is negative; a determinant of exactly 0 keeps the sign): everything
+ * above is computed from the unnormalised winner.  m < 4 or iters == 0: a zero record with best_iter = -1 (mask bytes of the pair zero). */
+enum { VIS_MODEL_NONE = 0, VIS_MODEL_HOMOGRAPHY = 1, VIS_MODEL_ESSENTIAL = 2 };
+enum { VIS_H_TILE = 512 };               /* correspondences per LDS tile of the kernel: rows longer than this are walked in several tiles */
+typedef struct vis_homography_params {   /* 40 bytes */
+    int32_t iters;                       /* 200    hypotheses per pair */
+    int32_t min_inliers;                 /* 8      below it a model is not offered */
+    double  chi2_h;                      /* 5.991  two-sided transfer error, 2 degrees of freedom, 95 % */
+    double  chi2_e;                      /* 3.841  point-to-epipolar-line distance, 1 degree of freedom, 95 % */
+    double  sigma_px;                    /* 1.0 */
+    double  h_ratio;                     /* 0.40   ORB-SLAM2's value (the paper's 0.45 does not separate the test scenes: DESIGN.md section 4.10) */
+} vis_homography_params;
+typedef struct vis_homography_result {   /* 112 bytes */
+    double  H[9];                        /* row-major, x2 ~ H x1; unit Frobenius norm, det >= 0; zeros when no iteration won */
+    double  score_h, score_e;
+    int32_t n_inliers, n_points;
+    int32_t best_iter;                   /* -1: none */
+    int32_t n_degenerate;
+    int32_t n_inliers_e;
+    int32_t model;                       /* VIS_MODEL_* */
+} vis_homography_result;
+void vis_default_homography_params(vis_homography_params* hp);
+/* One pair, HOST pointers; blocks once like the other single-frame entry points.  p1xy / p2xy: m x 2 floats (pixels); draws: hp.iters x 4;
+ * E: 9 doubles row-major or NULL; mask: m bytes or NULL. */
+int  vis_find_homography(vis_ctx* ctx, const vis_homography_params* hp, const float* p1xy, const float* p2xy, int m,
+                         const int32_t* draws, const double* E, uint8_t* mask, vis_homography_result* out);
+/* DEVICE pointers, asynchronous on the context's stream.  d_p1 / d_p2: n rows of max_pts (x, y) float points, d_npts[i] of them valid
+ * (clamped to max_pts); d_E: n x 9 doubles or NULL; d_mask: n rows of row_cap bytes or NULL; d_out: n records. */
+int  vis_homography_batch(vis_ctx* ctx, const vis_homography_params* hp, int n, const float* d_p1, const float* d_p2,
+                          const int32_t* d_npts, int max_pts, const int32_t* d_draws, const double* d_E,
+                          int row_cap, uint8_t* d_mask, vis_homography_result* d_out);
+/* The same on the pairs of the last vis_batch_run (which must have included VIS_STAGE_MATCH; n = its frames): the correspondences the pose
+ * stage would see, in the order of vis_batch_get_inlier_mask, with vis_batch_get_keyframes' pairing, the pair to the carried frame
+ * included.  E is the pair's pose record's when that run included VIS_STAGE_POSE; otherwise there is none.  A frame without a pair gets the
+ * zero record.  Asynchronous on the POSE stream behind the pose stage, overlapping the next vis_batch_run like vis_batch_f2f: the caller's
+ * buffers are in use until vis_batch_sync.
+ * Refusals of the three calls, in this order.  VIS_E_INVALID: a NULL or misaligned pointer (8 bytes for points, E and records; E and the
+ * mask may be NULL), a negative size, hp.iters < 0, hp.min_inliers < 4, a chi2 or sigma_px that is not finite and positive, h_ratio outside
+ * (0, 1).  vis_homography_batch: VIS_E_STATE without a context, then VIS_E_CAPACITY when a mask is given and row_cap < max_pts.
+ * vis_batch_homography: VIS_E_CAPACITY when a mask is given and row_cap is below the plan's correspondences per pair, then VIS_E_STATE
+ * without context / plan / match stage or when n differs. */
+int  vis_batch_homography(vis_ctx* ctx, const vis_homography_params* hp, int n, const int32_t* d_draws,
+                          int row_cap, uint8_t* d_mask, vis_homography_result* d_out);
+
 /* ---- rotation-guided matching ("search by projection"): the 2-NN search of the matcher restricted to a window around the position the
  * pair's rotation predicts -- VISystem::WarpFunctionRT (src/VISystem.cpp:771-860; its call sites :500-504 are commented out in the reference)
  * put in front of the matcher.  rot: row-major 3x3 f32, the matrix vis_batch_f2f takes (current-frame rays -> previous frame, :1031-1033).

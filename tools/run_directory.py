@@ -18,6 +18,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --points out.csv: the map points of every frame's pair (vis_batch_triangulate behind every batch, default thresholds): one row per
              correspondence of a pair with a pose -- frame index, timestamp, correspondence index, X, Y, Z (first camera's frame, units
              of the baseline), reproj_px, parallax_px, flags (VIS_MP_*); the JSON line carries the totals.
+  --models out.csv: which two-view model explains every frame's pair (vis_batch_homography behind every batch, default parameters, 200
+             draws of default_rng(7)): one row per pair -- frame index, timestamp, model (none / homography / essential), n_points,
+             n_inliers (H), n_inliers_e, score_h, score_e, best_iter, n_degenerate, H (nine entries, row-major, normalised
+             coordinates); the JSON line carries the count of each model.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -74,6 +78,7 @@ def main():
     ap.add_argument("--weights", choices=("identity", "tukey", "tukey-signed"), default="identity",
                     help="--track: the weighting of the alignment's Gauss-Newton step (vis_set_align_weights); identity = the reference's live call")
     ap.add_argument("--points", default=None, metavar="CSV", help="write the triangulated map points of every pair here")
+    ap.add_argument("--models", default=None, metavar="CSV", help="write the H-or-E model choice of every pair here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -135,6 +140,12 @@ def main():
         d_ms = torch.empty(B * vislam.TRI_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         point_rows, tri_totals = [], np.zeros(3, np.int64)
+    if a.models:
+        hp = vislam.default_homography_params()
+        d_hdraws = torch.from_numpy(np.random.default_rng(7).integers(0, 2 ** 31, (hp.iters, 4)).astype(np.int32)).cuda()
+        d_hrec = torch.empty(B * vislam.HOMOGRAPHY_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        model_rows, model_totals = [], [0, 0, 0]
     if a.rectify:
         feed = None
         rect = ctx.rectify(cal["K"], cal["dist"], Kn, (in_w, in_h), (cal["out_width"], cal["out_height"]))
@@ -169,6 +180,8 @@ def main():
             ctx.batch_track(tap, d, nb, 0, d_align.data_ptr(), d_track.data_ptr())
         if a.points:
             ctx.batch_triangulate(nb, row_cap, d_mp.data_ptr(), d_mf.data_ptr(), d_ms.data_ptr())
+        if a.models:
+            ctx.batch_homography(nb, d_hdraws.data_ptr(), 0, 0, d_hrec.data_ptr(), hp)
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -184,6 +197,12 @@ def main():
                 tri_totals += (int(ms[i]["n_points"]), int(ms[i]["n_front"]), int(ms[i]["n_kept"]))
                 point_rows += [(first + i, stamps[first + i], j, *mp[i, j]["X"], mp[i, j]["reproj_px"], mp[i, j]["parallax_px"], int(mf[i, j]))
                                for j in range(int(ms[i]["n_points"]))]
+        if a.models:
+            hrec = d_hrec.cpu().numpy().view(vislam.HOMOGRAPHY_RESULT_DTYPE)
+            for i in range(nb):
+                if int(hrec[i]["n_points"]) > 0:
+                    model_totals[int(hrec[i]["model"])] += 1
+                    model_rows.append((first + i, stamps[first + i], hrec[i].copy()))
         if ctx.batch_status() != 0:
             raise SystemExit("device capacity flag set")
         for i in range(nb):
@@ -236,6 +255,14 @@ def main():
                 f.write("%d,%d,%d,%.17g,%.17g,%.17g,%.9g,%.9g,%d\n" % r)
         out["points_csv"] = a.points
         out["map_points"] = {"triangulated": int(tri_totals[0]), "front": int(tri_totals[1]), "kept": int(tri_totals[2])}
+    if a.models:
+        with open(a.models, "w") as f:
+            for fi, ts, r in model_rows:
+                f.write("%d,%d,%s,%d,%d,%d,%.17g,%.17g,%d,%d," % (fi, ts, vislam.MODEL_NAMES[int(r["model"])], r["n_points"], r["n_inliers"], r["n_inliers_e"],
+                                                                   r["score_h"], r["score_e"], r["best_iter"], r["n_degenerate"])
+                        + ",".join("%.17g" % v for v in r["H"]) + "\n")
+        out["models_csv"] = a.models
+        out["models"] = dict(zip(vislam.MODEL_NAMES, model_totals))
     if feed:
         feed.close()
     else:

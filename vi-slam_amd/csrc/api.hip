@@ -1642,6 +1642,84 @@ extern "C" int vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, cons
     return VIS_OK;
 }
 
+// ---- homography RANSAC and the H-or-E model choice: homography.hip k_homography_batch
+extern "C" void vis_default_homography_params(vis_homography_params* hp) {
+    if (!hp) return;
+    hp->iters = 200; hp->min_inliers = 8;
+    hp->chi2_h = 5.991; hp->chi2_e = 3.841; hp->sigma_px = 1.0; hp->h_ratio = 0.40;
+}
+
+static bool homography_params_ok(const vis_homography_params* hp) {
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    return hp && hp->iters >= 0 && hp->min_inliers >= 4 && pos(hp->chi2_h) && pos(hp->chi2_e) && pos(hp->sigma_px) &&
+           hp->h_ratio > 0.0 && hp->h_ratio < 1.0;
+}
+
+static void homography_zero_record(vis_homography_result* r) { std::memset(r, 0, sizeof(*r)); r->best_iter = -1; }
+
+extern "C" int vis_find_homography(vis_ctx* ctx, const vis_homography_params* hp, const float* p1xy, const float* p2xy, int m,
+                                   const int32_t* draws, const double* E, uint8_t* mask, vis_homography_result* out) {
+    if (!out || m < 0 || (m && (!p1xy || !p2xy)) || !homography_params_ok(hp) || (m && hp->iters && !draws)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    homography_zero_record(out);
+    if (m == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t mk = ((size_t)m + 3) & ~(size_t)3, nd = (size_t)hp->iters * 4;
+    const size_t need = (size_t)m * 16 + mk + nd * 4 + 72 + sizeof(vis_homography_result) + 64 + 16 * 256 + 4096;
+    int rc = ensure_scratch(ctx, need);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0};
+    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
+    int32_t* d_draws = cv.take<int32_t>(nd ? nd : 4); int32_t* d_n = cv.take<int32_t>(1);
+    double* d_E = cv.take<double>(9);
+    uint8_t* d_mask = cv.take<uint8_t>(mk);
+    vis_homography_result* d_out = cv.take<vis_homography_result>(1);
+    rc = vis_ensure_pin(ctx, need);
+    if (rc) return rc;
+    const int32_t n1 = m;
+    HostStage hs(ctx);
+    hs.up(d_p1, p1xy, (size_t)m * 8);
+    hs.up(d_p2, p2xy, (size_t)m * 8);
+    if (nd) hs.up(d_draws, draws, nd * 4);
+    hs.up(d_n, &n1, 4);
+    if (E) hs.up(d_E, E, 72);
+    hs.flush_ups();
+    rc = homography_batch_run(ctx, hp, 1, m, d_p1, d_p2, d_n, d_draws, E ? d_E : nullptr, 9, (int)mk, d_mask, d_out);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const void* h_out = hs.down(d_out, sizeof(vis_homography_result));
+    const void* h_mask = hs.down(d_mask, mk);
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out, h_out, sizeof(*out));
+    if (mask) std::memcpy(mask, h_mask, (size_t)m);
+    return VIS_OK;
+}
+
+extern "C" int vis_homography_batch(vis_ctx* ctx, const vis_homography_params* hp, int n, const float* d_p1, const float* d_p2,
+                                    const int32_t* d_npts, int max_pts, const int32_t* d_draws, const double* d_E,
+                                    int row_cap, uint8_t* d_mask, vis_homography_result* d_out) {
+    if (n < 0 || max_pts < 0 || row_cap < 0 || !d_npts || !d_draws || !d_out || (max_pts && (!d_p1 || !d_p2)) || !homography_params_ok(hp)) return VIS_E_INVALID;
+    if (((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_E & 7) || ((uintptr_t)d_out & 7)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (d_mask && row_cap < max_pts) { ctx->err = "vis_homography_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return homography_batch_run(ctx, hp, n, max_pts, d_p1, d_p2, d_npts, d_draws, d_E, 9, row_cap, d_mask, d_out);
+}
+
+extern "C" int vis_batch_homography(vis_ctx* ctx, const vis_homography_params* hp, int n, const int32_t* d_draws,
+                                    int row_cap, uint8_t* d_mask, vis_homography_result* d_out) {
+    if (n < 0 || row_cap < 0 || !d_draws || !d_out || ((uintptr_t)d_out & 7) || !homography_params_ok(hp)) return VIS_E_INVALID;
+    if (ctx && ctx->batch && d_mask && row_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_homography: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    // behind the pose stage of the last run on the pose stream (batch_epi queues there): its records are single-buffered and written on that
+    // stream only, and the next pose stage is queued behind this call
+    return batch_epi(ctx, n, "vis_batch_homography", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        const bool have_E = (pl->last_stages & VIS_STAGE_POSE) != 0;
+        static_assert(sizeof(PoseOut) % 8 == 0 && offsetof(PoseOut, E) == 0, "the pose record begins with E");
+        return homography_batch_run(ctx, hp, n, pl->pose_mcap, O.p1, O.p2, d_npts, d_draws, have_E ? (const double*)pl->d_pose : nullptr,
+                                    (int)(sizeof(PoseOut) / 8), row_cap, d_mask, d_out);
+    });
+}
+
 extern "C" int vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redone) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     Plan* pl = ctx->batch;

@@ -416,6 +416,11 @@ int f2f_batch_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, co
                   const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out);
 int epi_filter_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
                    const float* d_rot, const float* d_t, double threshold, int row_cap, uint8_t* d_keep, int32_t* d_nkeep);
+// homography.hip: k_homography_batch on ctx->stream over npairs rows of in_stride (x, y) points; hp validated by the caller; d_E: records of e_stride
+// doubles that begin with E, or null; d_mask: rows of row_cap >= in_stride bytes, or null
+int homography_batch_run(vis_ctx* ctx, const vis_homography_params* hp, int npairs, int in_stride, const float* d_p1, const float* d_p2,
+                         const int32_t* d_npts, const int32_t* d_draws, const double* d_E, int e_stride, int row_cap, uint8_t* d_mask,
+                         vis_homography_result* d_out);
 #define VIS_RSTATE_WORDS 16
 
 #endif

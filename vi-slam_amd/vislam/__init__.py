@@ -9,6 +9,7 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.essential_ransac / recover_pose <-> VISystem::EstimatePoseFeaturesRansac (src/VISystem.cpp:1679-1701)
   Context.f2f_ransac           <-> VISystem::F2FRansac                      (src/VISystem.cpp:612-769)
   Context.f2f_batch / batch_f2f                       <-> the same for every pair of a batch
+  Context.find_homography / homography_batch / batch_homography   homography RANSAC and the H-or-E model choice (beyond the reference)
   Context.filter_keypoints (_batch, batch_...)        <-> VISystem::FilterKeypoints  (src/VISystem.cpp:542-610)
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises.
@@ -137,6 +138,27 @@ assert F2F_RESULT_DTYPE.itemsize == C.sizeof(F2fResult) == 32
 F2F_TILE = 512                                    # VIS_F2F_TILE: correspondences per LDS tile of the batched F2FRansac kernel
 
 
+class HomographyParams(C.Structure):
+    """vis_homography_params: the knobs of the homography RANSAC and of the H-or-E decision (vis_default_homography_params: 200, 8, 5.991,
+    3.841, 1.0, 0.40)"""
+    _fields_ = [("iters", C.c_int32), ("min_inliers", C.c_int32), ("chi2_h", C.c_double), ("chi2_e", C.c_double), ("sigma_px", C.c_double),
+                ("h_ratio", C.c_double)]
+
+
+class HomographyResult(C.Structure):
+    """vis_homography_result: the winning homography of one pair (normalised coordinates, unit norm, det >= 0), both models' scores and the choice"""
+    _fields_ = [("H", C.c_double * 9), ("score_h", C.c_double), ("score_e", C.c_double), ("n_inliers", C.c_int32), ("n_points", C.c_int32),
+                ("best_iter", C.c_int32), ("n_degenerate", C.c_int32), ("n_inliers_e", C.c_int32), ("model", C.c_int32)]
+
+
+HOMOGRAPHY_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("score_h", "<f8"), ("score_e", "<f8"), ("n_inliers", "<i4"), ("n_points", "<i4"),
+                                    ("best_iter", "<i4"), ("n_degenerate", "<i4"), ("n_inliers_e", "<i4"), ("model", "<i4")])
+assert C.sizeof(HomographyParams) == 40 and HOMOGRAPHY_RESULT_DTYPE.itemsize == C.sizeof(HomographyResult) == 112
+H_TILE = 512                                      # VIS_H_TILE: correspondences per LDS tile of the homography kernel
+MODEL_NONE, MODEL_HOMOGRAPHY, MODEL_ESSENTIAL = 0, 1, 2
+MODEL_NAMES = ("none", "homography", "essential")
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -176,6 +198,7 @@ ABI_SYMBOLS = [
     "vis_rectify_batch", "vis_rectify_host",
     "vis_default_tri_params", "vis_triangulate", "vis_batch_triangulate",
     "vis_f2f_batch", "vis_batch_f2f", "vis_filter_keypoints_batch", "vis_batch_filter_keypoints", "vis_filter_keypoints",
+    "vis_default_homography_params", "vis_find_homography", "vis_homography_batch", "vis_batch_homography",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
@@ -251,6 +274,13 @@ def _load():
         lib.vis_filter_keypoints_batch.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, cd, ci, vp, vp]
         lib.vis_batch_filter_keypoints.argtypes = [vp, ci, vp, vp, cd, ci, vp, vp]
         lib.vis_filter_keypoints.argtypes = [vp, vp, vp, ci, vp, vp, cd, vp, ip]
+    if hasattr(lib, "vis_batch_homography"):            # (absent from older A/B builds)
+        hpp = C.POINTER(HomographyParams)
+        lib.vis_default_homography_params.argtypes = [hpp]
+        lib.vis_default_homography_params.restype = None
+        lib.vis_find_homography.argtypes = [vp, hpp, vp, vp, ci, vp, vp, vp, vp]
+        lib.vis_homography_batch.argtypes = [vp, hpp, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
+        lib.vis_batch_homography.argtypes = [vp, hpp, ci, vp, ci, vp, vp]
     if hasattr(lib, "vis_set_align_weights"):           # (absent from older A/B builds)
         lib.vis_default_align_weights.argtypes = [C.POINTER(AlignWeights)]
         lib.vis_default_align_weights.restype = None
@@ -355,6 +385,12 @@ def default_tri_params():
     tp = TriParams()
     lib.vis_default_tri_params(C.byref(tp))
     return tp
+
+
+def default_homography_params():
+    hp = HomographyParams()
+    lib.vis_default_homography_params(C.byref(hp))
+    return hp
 
 
 def se3_exp(a):
@@ -884,6 +920,38 @@ class Context:
         self._chk(lib.vis_filter_keypoints(self._h, _ptr(pts1), _ptr(pts2), len(pts1), _ptr(rot), _ptr(t), float(threshold), _ptr(keep),
                                            C.byref(nk)), "vis_filter_keypoints")
         return keep[:len(pts1)], nk.value
+
+    # -- homography RANSAC and the H-or-E model choice -----------------------------------------------------------
+    def find_homography(self, p1, p2, draws, E=None, hp=None):
+        """(record, mask uint8[m]) of one pair: p1 / p2 m x 2 float pixels, draws iters x 4 int32, E 3 x 3 or None; the record is one
+        HOMOGRAPHY_RESULT_DTYPE element"""
+        hp = default_homography_params() if hp is None else hp
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        assert len(p1) == len(p2)
+        draws = np.ascontiguousarray(draws, np.int32).reshape(-1)
+        assert len(draws) >= 4 * hp.iters
+        E = None if E is None else np.ascontiguousarray(E, np.float64).reshape(9)
+        mask = np.zeros(max(len(p1), 1), np.uint8)
+        out = np.zeros(1, HOMOGRAPHY_RESULT_DTYPE)
+        self._chk(lib.vis_find_homography(self._h, C.byref(hp), _ptr(p1), _ptr(p2), len(p1), _ptr(draws), _ptr(E), _ptr(mask), _ptr(out)),
+                  "vis_find_homography")
+        return out[0], mask[:len(p1)]
+
+    def homography_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, d_draws_ptr, d_E_ptr, row_cap, d_mask_ptr, d_out_ptr, hp=None):
+        """queue the homography RANSAC of n rows of max_pts (x, y) correspondences on the context's stream (raw DEVICE pointers; 0 / None =
+        NULL for d_E and d_mask): n HomographyResult records, n rows of row_cap mask bytes"""
+        hp = default_homography_params() if hp is None else hp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_homography_batch(self._h, C.byref(hp), n, v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, v(d_draws_ptr), v(d_E_ptr),
+                                           row_cap, v(d_mask_ptr), v(d_out_ptr)), "vis_homography_batch")
+
+    def batch_homography(self, n, d_draws_ptr, row_cap, d_mask_ptr, d_out_ptr, hp=None):
+        """the same on the pairs of the last batch_run(... | STAGE_MATCH), on the pose stream, with the pose records' E when that run had
+        STAGE_POSE; the buffers are in use until batch_sync()"""
+        hp = default_homography_params() if hp is None else hp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_homography(self._h, C.byref(hp), n, v(d_draws_ptr), row_cap, v(d_mask_ptr), v(d_out_ptr)), "vis_batch_homography")
 
     # -- batched stream path ----------------------------------------------------------------------------------
     def batch_plan(self, w, h, stride, max_frames):
