@@ -568,7 +568,7 @@ int  vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keyp
 /* ---- homography RANSAC and the H-or-E model choice: the other half of a two-view initialiser (Mur-Artal, Montiel, Tardos: ORB-SLAM, 2015,
  * section IV; the reference has neither).  For a standing or purely rotating camera, a planar scene or points at infinity the essential
  * matrix of the pose stage is not determined by the correspondences; a homography explains such a pair, and
- * comparing the two models' scores flags it.  Acting on the flag is the caller's business.
+ * comparing the two models' scores flags it; the section after this one turns a flagged pair's H into a pose.
  * Coordinates: the pose stage's, x = ((double)u - cx) * (1 / fx), y = ((double)v - cy) * (1 / fx) with the single focal of findEssentialMat,
  * so H is the Euclidean homography R + t n^T / d up to scale.  Thresholds, once on the host in double: s2 = (sigma_px * (1 / fx))^2,
  * t_h = chi2_h * s2, t_e = chi2_e * s2.  No multiply-add is contracted; dot products are summed left to right.
@@ -631,6 +631,79 @@ int  vis_homography_batch(vis_ctx* ctx, const vis_homography_params* hp, int n, 
  * without context / plan / match stage or when n differs. */
 int  vis_batch_homography(vis_ctx* ctx, const vis_homography_params* hp, int n, const int32_t* d_draws,
                           int row_cap, uint8_t* d_mask, vis_homography_result* d_out);
+
+/* ---- the pose of a homography: the second half of that two-view initialiser (Faugeras & Lustman, "Motion and structure from motion in a
+ * piecewise planar environment", 1988; ORB-SLAM section IV's ReconstructH -- both restated from the papers; the reference has neither).  For a
+ * pair flagged VIS_MODEL_HOMOGRAPHY the (R, t) of vis_pose_result is undetermined; this turns the pair's H into (R, t / d, n): x2 = R x1 + t
+ * for points of the plane n . X = d of the first camera, t in units of d -- NOT of unit norm like vis_pose_result's.  Accuracy is that of the
+ * unrefitted four-point H of vis_*_homography.
+ * All arithmetic is double, nothing is contracted, the only operations are + - * / sqrt; dot3(a, b) = a0 b0 + a1 b1 + a2 b2 and every sum of a
+ * 3 x 3 product run left to right from 0 (tests/homography_pose_ref.py restates every step in this order, bit for bit).
+ * Input: the record's H and best_iter, the pair's correspondences in pixels, an optional mask (the one vis_*_homography wrote; NULL = every
+ * correspondence votes) and an optional rotation hint.  best_iter < 0, an H entry that is not finite, m < 1, or a t_norm (below) that is
+ * not finite (a rank-deficient H: d2 == 0): the zero record with kind = VIS_HP_NONE, solution = second = -1.
+ * Singular values: H = U diag(d1, d2, d3) V^T by the pose stage's Jacobi path (eigenvectors v0, v1 of H^T H by descending eigenvalue, v2 = v0 x
+ * v1; u0 = H v0 / |H v0|, u1 = H v1 made orthogonal to u0 and normalised, u2 = u0 x u1: U and V are proper rotations, and det H >= 0 makes
+ * d3 >= 0); sv[k] = d_k = sqrt(dot3(w, w)) with w = H v_k.  t_norm = (d1 - d3) / d2 = |t| / d.  q_k = d_k d_k, den = q1 - q3.
+ * VIS_HP_ROTATION when t_norm <= min_t_over_d, den == 0 or den is not finite: R = U V^T, t = n = 0, no vote, solution = 0, second = -1.
+ * Otherwise VIS_HP_PLANE, with the branch d' = +d2 only (det H >= 0: both cameras on one side of the plane):
+ *   x1 = sqrt(max((q1 - q2) / den, 0)), x3 = sqrt(max((q2 - q3) / den, 0)), dd = (d1 + d3) d2,
+ *   S = sqrt(max((q1 - q2) (q2 - q3), 0)) / dd, c = (q2 + d1 d3) / dd;   rotation 0: s = S, x3' = x3;  rotation 1: s = -S, x3' = -x3;
+ *   R' = [[c, 0, -s], [0, 1, 0], [s, 0, c]], R = (U R') V^T, t' = ((d1 - d3) x1, 0, (d1 - d3) (-x3')), t_i = dot3(row i of U, t') / d2,
+ *   n_i = (V_i0 x1 + V_i1 0) + V_i2 x3'.
+ * Candidates k = 0 ... 3 for (e1, e3) = (+,+), (+,-), (-,+), (-,-): 0 = rotation 0, 1 = rotation 1, 2 = candidate 1 with -t, -n, 3 = candidate 0
+ * with -t, -n (exactly).
+ * Vote: a voting correspondence, in the pose stage's coordinates ((double)u - cx) * (1 / fx), votes for candidate k when the DLT triangulation
+ * and depth test of recoverPose (the one behind n_pose_good and VIS_MP_FRONT) passes under (R_k, t_k) -> n_good[k]; a passing voter counts in
+ * candidate k's parallax count when, with X its triangulated point, r1 = X, r2 = X + R_k^T t_k ((R^T t)_j = (R_0j t_0 + R_1j t_1) + R_2j t_2),
+ * dot3(r1, r2) < max_cos_parallax * sqrt(dot3(r1, r1) * dot3(r2, r2)).  Integer sums: the order does not matter.  n_tested = the voters.
+ * Choice: candidates ordered by (n_good descending, index ascending); best = the first; rivals = the others with (double)n_good[k] >=
+ * ambiguity_ratio * (double)n_good[best].  Without a hint solution = best.  With a hint rot (9 floats row-major, the matrix vis_batch_f2f
+ * takes: current-frame rays -> previous frame, i.e. ~ R^T) solution = the one of best and rivals, walked in that order, with the largest
+ * trace(R_k (double)rot) = sum over i, j in row order of R_ij * rot_ji from 0; the first wins ties.  second = the first of the order that
+ * is not solution.  The record carries both; whether to trust it is the caller's decision, as with `model`.
+ * Flags: AMBIGUOUS = a rival and no hint; HINTED = a hint chose among two or more; FEW = (double)n_good[solution] < max((double)min_good,
+ * good_share * (double)n_tested); LOW_PARALLAX = (double)n_parallax < parallax_share * (double)n_good[solution], n_parallax = the parallax
+ * count of solution.  Two runs are byte-identical (no floating-point atomics). */
+enum { VIS_HP_NONE = 0, VIS_HP_ROTATION = 1, VIS_HP_PLANE = 2 };
+enum { VIS_HPF_AMBIGUOUS = 1, VIS_HPF_HINTED = 2, VIS_HPF_FEW = 4, VIS_HPF_LOW_PARALLAX = 8 };
+typedef struct vis_hpose_params {        /* 48 bytes */
+    double  min_t_over_d;                /* 0.05   below it the pair is a rotation (the measured separation of the test scenes) */
+    double  max_cos_parallax;            /* 0.9998476951563913 = cos 1 deg, the paper's value */
+    double  ambiguity_ratio;             /* 0.75   the paper's */
+    double  good_share;                  /* 0.9    the paper's */
+    double  parallax_share;              /* 0.5    this library's */
+    int32_t min_good;                    /* 8      = vis_homography_params.min_inliers */
+    int32_t reserved_;
+} vis_hpose_params;
+typedef struct vis_hpose_result {        /* 320 bytes */
+    double  R[9], t[3], n[3];            /* the chosen candidate: x2 = R x1 + t, t in units of d, |n| = 1 */
+    double  R2[9], t2[3], n2[3];         /* `second`; zeros when there is none */
+    double  sv[3], t_norm;               /* d1, d2, d3; (d1 - d3) / d2 */
+    int32_t n_good[4];                   /* votes of the four candidates */
+    int32_t kind, flags, solution, second;   /* VIS_HP_*, VIS_HPF_*, candidate indices (-1: none) */
+    int32_t n_tested, n_parallax, n_points, reserved_;
+} vis_hpose_result;
+void vis_default_hpose_params(vis_hpose_params* hq);
+/* One pair, HOST pointers; blocks once.  h: the pair's homography record; p1xy / p2xy: m x 2 floats (pixels); mask: m bytes or NULL;
+ * rot_hint: 9 floats or NULL. */
+int  vis_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, const vis_homography_result* h, const float* p1xy, const float* p2xy, int m,
+                         const uint8_t* mask, const float* rot_hint, vis_hpose_result* out);
+/* DEVICE pointers, asynchronous on the context's stream, rows like vis_homography_batch's.  d_h: n homography records; d_mask: n rows of
+ * row_cap bytes or NULL; d_rot: n x 9 floats or NULL; d_out: n records (a PLANE pair's record is the kernels' workspace until the call has
+ * run: no scratch memory is taken). */
+int  vis_homography_pose_batch(vis_ctx* ctx, const vis_hpose_params* hq, int n, const vis_homography_result* d_h, const float* d_p1,
+                               const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask, const float* d_rot,
+                               vis_hpose_result* d_out);
+/* The same on the pairs of the last vis_batch_run, with d_h and d_mask as vis_batch_homography wrote them: on the POSE stream behind that call,
+ * overlapping the next vis_batch_run like it; the caller's buffers are in use until vis_batch_sync.
+ * Refusals of the three calls, in this order.  VIS_E_INVALID: a NULL pointer (the mask and the hint may be NULL), on the two device-pointer
+ * calls a misaligned one (8 bytes for records and points, 4 for d_npts and d_rot; host pointers are copied and need none), a negative size, a parameter that is not finite, min_t_over_d < 0, max_cos_parallax, ambiguity_ratio, good_share or
+ * parallax_share outside (0, 1], min_good < 1.  vis_homography_pose_batch: VIS_E_STATE without a context, then VIS_E_CAPACITY when a mask is
+ * given and row_cap < max_pts or when max_pts > 2^29.  vis_batch_homography_pose: VIS_E_CAPACITY when a mask is given and row_cap is below the
+ * plan's correspondences per pair, then VIS_E_STATE without context / plan / match stage or when n differs. */
+int  vis_batch_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, int n, const vis_homography_result* d_h, int row_cap,
+                               const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out);
 
 /* ---- rotation-guided matching ("search by projection"): the 2-NN search of the matcher restricted to a window around the position the
  * pair's rotation predicts -- VISystem::WarpFunctionRT (src/VISystem.cpp:771-860; its call sites :500-504 are commented out in the reference)

@@ -22,6 +22,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              draws of default_rng(7)): one row per pair -- frame index, timestamp, model (none / homography / essential), n_points,
              n_inliers (H), n_inliers_e, score_h, score_e, best_iter, n_degenerate, H (nine entries, row-major, normalised
              coordinates); the JSON line carries the count of each model.
+  --hposes out.csv: the pose of every pair's homography (vis_batch_homography with its mask, then vis_batch_homography_pose without a rotation
+             hint, default parameters, the draws of --models): one row per pair -- frame index, timestamp, kind (none / rotation / plane), flags
+             (VIS_HPF_*), solution, second, n_points, n_tested, n_parallax, n_good (four), d1, d2, d3, t_norm, then R (nine, row-major), t (in
+             units of the plane distance), n of the chosen candidate and R, t, n of the second; the JSON line carries the count of each kind.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -79,6 +83,7 @@ def main():
                     help="--track: the weighting of the alignment's Gauss-Newton step (vis_set_align_weights); identity = the reference's live call")
     ap.add_argument("--points", default=None, metavar="CSV", help="write the triangulated map points of every pair here")
     ap.add_argument("--models", default=None, metavar="CSV", help="write the H-or-E model choice of every pair here")
+    ap.add_argument("--hposes", default=None, metavar="CSV", help="write the pose of every pair's homography (chosen and second candidate) here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -140,12 +145,19 @@ def main():
         d_ms = torch.empty(B * vislam.TRI_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         point_rows, tri_totals = [], np.zeros(3, np.int64)
-    if a.models:
+    if a.models or a.hposes:                                  # one homography RANSAC per batch serves both (the mask does not change the records)
         hp = vislam.default_homography_params()
         d_hdraws = torch.from_numpy(np.random.default_rng(7).integers(0, 2 ** 31, (hp.iters, 4)).astype(np.int32)).cuda()
         d_hrec = torch.empty(B * vislam.HOMOGRAPHY_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
+        hcap, d_hmask = 0, None
         model_rows, model_totals = [], [0, 0, 0]
+    if a.hposes:
+        hq = vislam.default_hpose_params()
+        hcap = max(int(np.floor(np.sqrt(p.n_cells))) ** 2, 1)  # the grid-filtered good matches of a pair
+        d_hmask = torch.empty(B * hcap, dtype=torch.uint8, device="cuda")
+        d_hpose = torch.empty(B * vislam.HPOSE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        hpose_rows, hpose_totals = [], [0, 0, 0]
+    torch.cuda.synchronize()
     if a.rectify:
         feed = None
         rect = ctx.rectify(cal["K"], cal["dist"], Kn, (in_w, in_h), (cal["out_width"], cal["out_height"]))
@@ -180,8 +192,10 @@ def main():
             ctx.batch_track(tap, d, nb, 0, d_align.data_ptr(), d_track.data_ptr())
         if a.points:
             ctx.batch_triangulate(nb, row_cap, d_mp.data_ptr(), d_mf.data_ptr(), d_ms.data_ptr())
-        if a.models:
-            ctx.batch_homography(nb, d_hdraws.data_ptr(), 0, 0, d_hrec.data_ptr(), hp)
+        if a.models or a.hposes:
+            ctx.batch_homography(nb, d_hdraws.data_ptr(), hcap, d_hmask.data_ptr() if a.hposes else 0, d_hrec.data_ptr(), hp)
+        if a.hposes:
+            ctx.batch_homography_pose(nb, d_hrec.data_ptr(), hcap, d_hmask.data_ptr(), 0, d_hpose.data_ptr(), hq)
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -203,6 +217,12 @@ def main():
                 if int(hrec[i]["n_points"]) > 0:
                     model_totals[int(hrec[i]["model"])] += 1
                     model_rows.append((first + i, stamps[first + i], hrec[i].copy()))
+        if a.hposes:
+            hpose = d_hpose.cpu().numpy().view(vislam.HPOSE_RESULT_DTYPE)
+            for i in range(nb):
+                if int(hpose[i]["kind"]) != vislam.HP_NONE:
+                    hpose_totals[int(hpose[i]["kind"])] += 1
+                    hpose_rows.append((first + i, stamps[first + i], hpose[i].copy()))
         if ctx.batch_status() != 0:
             raise SystemExit("device capacity flag set")
         for i in range(nb):
@@ -263,6 +283,15 @@ def main():
                         + ",".join("%.17g" % v for v in r["H"]) + "\n")
         out["models_csv"] = a.models
         out["models"] = dict(zip(vislam.MODEL_NAMES, model_totals))
+    if a.hposes:
+        with open(a.hposes, "w") as f:
+            for fi, ts, r in hpose_rows:
+                ints = [r[k] for k in ("flags", "solution", "second", "n_points", "n_tested", "n_parallax")] + list(r["n_good"])
+                dbl = list(r["sv"]) + [r["t_norm"]] + [v for k in ("R", "t", "n", "R2", "t2", "n2") for v in r[k]]
+                f.write("%d,%d,%s," % (fi, ts, vislam.HP_KIND_NAMES[int(r["kind"])]) + ",".join("%d" % v for v in ints) + "," +
+                        ",".join("%.17g" % v for v in dbl) + "\n")
+        out["hposes_csv"] = a.hposes
+        out["hposes"] = dict(zip(vislam.HP_KIND_NAMES, hpose_totals))
     if feed:
         feed.close()
     else:

@@ -1720,6 +1720,78 @@ extern "C" int vis_batch_homography(vis_ctx* ctx, const vis_homography_params* h
     });
 }
 
+// ---- the pose of a homography: pose.hip k_hpose_svd + k_hpose_vote
+extern "C" void vis_default_hpose_params(vis_hpose_params* hq) {
+    if (!hq) return;
+    hq->min_t_over_d = 0.05; hq->max_cos_parallax = 0.9998476951563913; hq->ambiguity_ratio = 0.75;
+    hq->good_share = 0.9; hq->parallax_share = 0.5; hq->min_good = 8; hq->reserved_ = 0;
+}
+
+static bool hpose_params_ok(const vis_hpose_params* hq) {
+    auto share = [](double v) { return std::isfinite(v) && v > 0.0 && v <= 1.0; };
+    return hq && std::isfinite(hq->min_t_over_d) && hq->min_t_over_d >= 0.0 && share(hq->max_cos_parallax) && share(hq->ambiguity_ratio) &&
+           share(hq->good_share) && share(hq->parallax_share) && hq->min_good >= 1;
+}
+
+extern "C" int vis_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, const vis_homography_result* h, const float* p1xy, const float* p2xy,
+                                   int m, const uint8_t* mask, const float* rot_hint, vis_hpose_result* out) {
+    if (!out || !h || m < 0 || (m && (!p1xy || !p2xy)) || !hpose_params_ok(hq)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    std::memset(out, 0, sizeof(*out)); out->solution = out->second = -1;
+    if (m == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t mk = ((size_t)m + 3) & ~(size_t)3;
+    const size_t need = (size_t)m * 16 + mk + sizeof(vis_homography_result) + sizeof(vis_hpose_result) + 36 + 4 + 64 + 16 * 256 + 4096;
+    int rc = ensure_scratch(ctx, need);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0};
+    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
+    int32_t* d_n = cv.take<int32_t>(1);
+    float* d_rot = cv.take<float>(9);
+    vis_homography_result* d_h = cv.take<vis_homography_result>(1);
+    uint8_t* d_mask = cv.take<uint8_t>(mk);
+    vis_hpose_result* d_out = cv.take<vis_hpose_result>(1);
+    rc = vis_ensure_pin(ctx, need);
+    if (rc) return rc;
+    const int32_t n1 = m;
+    HostStage hs(ctx);
+    hs.up(d_p1, p1xy, (size_t)m * 8);
+    hs.up(d_p2, p2xy, (size_t)m * 8);
+    hs.up(d_n, &n1, 4);
+    hs.up(d_h, h, sizeof(*h));
+    if (rot_hint) hs.up(d_rot, rot_hint, 36);
+    if (mask) hs.up(d_mask, mask, (size_t)m);
+    hs.flush_ups();
+    rc = hpose_run(ctx, hq, 1, m, d_h, d_p1, d_p2, d_n, (int)mk, mask ? d_mask : nullptr, rot_hint ? d_rot : nullptr, d_out);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    const void* h_out = hs.down(d_out, sizeof(vis_hpose_result));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out, h_out, sizeof(*out));
+    return VIS_OK;
+}
+
+extern "C" int vis_homography_pose_batch(vis_ctx* ctx, const vis_hpose_params* hq, int n, const vis_homography_result* d_h, const float* d_p1,
+                                         const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask,
+                                         const float* d_rot, vis_hpose_result* d_out) {
+    if (n < 0 || max_pts < 0 || row_cap < 0 || !d_h || !d_npts || !d_out || (max_pts && (!d_p1 || !d_p2)) || !hpose_params_ok(hq)) return VIS_E_INVALID;
+    if (((uintptr_t)d_h & 7) || ((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_npts & 3) || ((uintptr_t)d_rot & 3)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (d_mask && row_cap < max_pts) { ctx->err = "vis_homography_pose_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return hpose_run(ctx, hq, n, max_pts, d_h, d_p1, d_p2, d_npts, row_cap, d_mask, d_rot, d_out);
+}
+
+extern "C" int vis_batch_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, int n, const vis_homography_result* d_h, int row_cap,
+                                         const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out) {
+    if (n < 0 || row_cap < 0 || !d_h || !d_out || ((uintptr_t)d_h & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_rot & 3) || !hpose_params_ok(hq)) return VIS_E_INVALID;
+    if (ctx && ctx->batch && d_mask && row_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_homography_pose: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    // on the pose stream behind vis_batch_homography of the same run (batch_epi queues there): d_h and d_mask are complete when the kernels read them
+    return batch_epi(ctx, n, "vis_batch_homography_pose", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        return hpose_run(ctx, hq, n, pl->pose_mcap, d_h, O.p1, O.p2, d_npts, row_cap, d_mask, d_rot, d_out);
+    });
+}
+
 extern "C" int vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redone) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     Plan* pl = ctx->batch;

@@ -1856,6 +1856,203 @@ __global__ __launch_bounds__(256) void k_epi_filter(F2fArgs A, int row_cap, cons
     if (tid == 0) nkeep[pair] = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
 }
 
+// ---- the pose of a homography (Faugeras & Lustman 1988; ORB-SLAM 2015 section IV, both restated from the papers): H = U diag(d1, d2, d3) V^T
+// -> two rotations, each with +-(t / d, n), a cheirality vote over the pair's correspondences, and both survivors in the record.  Two kernels
+// in the shape of k_pose_svd / k_pose_final.  Until k_hpose_vote's last workgroup has written it, a PLANE pair's record is the workspace:
+//   R, t, n = rotation 0 with candidate 0's (t, n);  R2, t2, n2 = rotation 1 with candidate 1's;  n_good[4] = the votes;
+//   flags, solution, second, n_parallax = the parallax counts of candidates 0 ... 3;  n_tested = the voters;  reserved_ = the ticket.
+struct HpArgs {
+    double fx_inv, cx, cy, min_t_over_d, max_cos, ratio, good_share, par_share;
+    int min_good, in_stride, row_cap, npairs;
+};
+
+// part 1, ONE PAIR PER LANE (the note at k_pose_svd): singular values, kind, and for a plane the two rotations with their (t, n).
+// Every expression is restated by tests/homography_pose_ref.py decompose() in the same order.
+__global__ __launch_bounds__(64) void k_hpose_svd(HpArgs A, const vis_homography_result* __restrict__ h, const int32_t* __restrict__ npts,
+                                                  vis_hpose_result* __restrict__ out) {
+    const int pair = blockIdx.x * 64 + threadIdx.x;
+    if (pair >= A.npairs) return;
+    const int m = min(max(npts[pair], 0), A.in_stride);
+    double H[9];
+    bool finite = true;
+#pragma unroll
+    for (int i = 0; i < 9; i++) { H[i] = h[pair].H[i]; finite = finite && (fabs(H[i]) <= 1.7976931348623157e308); }
+    vis_hpose_result o;
+#pragma unroll
+    for (int i = 0; i < 9; i++) o.R[i] = o.R2[i] = 0;
+#pragma unroll
+    for (int i = 0; i < 3; i++) o.t[i] = o.n[i] = o.t2[i] = o.n2[i] = o.sv[i] = 0;
+    o.t_norm = 0;
+    o.n_good[0] = o.n_good[1] = o.n_good[2] = o.n_good[3] = 0;
+    o.kind = VIS_HP_NONE; o.flags = 0; o.solution = o.second = -1;
+    o.n_tested = o.n_parallax = o.n_points = o.reserved_ = 0;
+    if (h[pair].best_iter >= 0 && finite && m >= 1) {
+        double U[9], Vt[9]; svd3_decompose(H, U, Vt);
+#pragma unroll
+        for (int k = 0; k < 3; k++) {                              // d_k = |H v_k|
+            const double w[3] = {dot3(H, Vt + 3 * k), dot3(H + 3, Vt + 3 * k), dot3(H + 6, Vt + 3 * k)};
+            o.sv[k] = sqrt(dot3(w, w));
+        }
+        const double d1 = o.sv[0], d2 = o.sv[1], d3 = o.sv[2];
+        o.t_norm = (d1 - d3) / d2;
+        const double q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3, den = q1 - q3;
+        o.n_points = m;
+        if (!(fabs(o.t_norm) <= 1.7976931348623157e308)) {         // a rank-deficient H (d2 == 0) or an overflow: no pose, the zero record
+            o.sv[0] = o.sv[1] = o.sv[2] = 0; o.t_norm = 0; o.n_points = 0;
+        } else if (o.t_norm <= A.min_t_over_d || den == 0.0 || !(fabs(den) <= 1.7976931348623157e308)) {
+            o.kind = VIS_HP_ROTATION; o.solution = 0;
+            mat3_mul(U, Vt, o.R);
+        } else {
+            o.kind = VIS_HP_PLANE; o.solution = 0; o.second = 0;   // (parallax counters until the vote has written the record)
+            const double a = (q1 - q2) / den, b = (q2 - q3) / den, rad = (q1 - q2) * (q2 - q3);
+            const double x1 = sqrt(a > 0.0 ? a : 0.0), x3 = sqrt(b > 0.0 ? b : 0.0);
+            const double dd = (d1 + d3) * d2;
+            const double S = sqrt(rad > 0.0 ? rad : 0.0) / dd, c = (q2 + d1 * d3) / dd, base = d1 - d3;
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const double s = r ? -S : S, x3p = r ? -x3 : x3;
+                const double Rp[9] = {c, 0.0, -s, 0.0, 1.0, 0.0, s, 0.0, c};
+                const double tp[3] = {base * x1, 0.0, base * -x3p};
+                double T[9];
+                mat3_mul(U, Rp, T); mat3_mul(T, Vt, r ? o.R2 : o.R);
+                double* tt = r ? o.t2 : o.t; double* nn = r ? o.n2 : o.n;
+#pragma unroll
+                for (int i = 0; i < 3; i++) {
+                    tt[i] = dot3(U + 3 * i, tp) / d2;
+                    nn[i] = (Vt[i] * x1 + Vt[3 + i] * 0.0) + Vt[6 + i] * x3p;
+                }
+            }
+        }
+    }
+    out[pair] = o;
+}
+
+// the parallax term of a triangulated point X under a candidate with ct = R^T t: the angle between the rays r1 = X and r2 = X + ct
+DEV bool hp_parallax(const double* X, const double* ct, double max_cos) {
+    const double r2[3] = {X[0] + ct[0], X[1] + ct[1], X[2] + ct[2]};
+    return dot3(X, r2) < max_cos * sqrt(dot3(X, X) * dot3(r2, r2));
+}
+
+// cheirality_pair with the point kept for the parallax term.  Under [R | -t] the point is -X and R^T (-t) = -ct, both exactly, so the
+// second candidate's term runs on the first decomposition too; the zero-theta fallback decomposes it on its own, as cheirality_pair does.
+__device__ __forceinline__ void cheirality_pair_par(const double* R, const double* t, const double* ct, double max_cos, double x1, double y1,
+                                                    double x2, double y2, bool& ok_pos, bool& ok_neg, bool& par_pos, bool& par_neg) {
+    double tt[3] = {t[0], t[1], t[2]}, cc[3] = {ct[0], ct[1], ct[2]};
+    ok_pos = ok_neg = par_pos = par_neg = false;
+#pragma nounroll
+    for (int pass = 0; pass < 2; pass++) {
+        double X[4]; bool zt = false;
+        const bool ok = cheirality(R, tt, x1, y1, x2, y2, X, &zt);
+        const double Xn[3] = {X[0] / X[3], X[1] / X[3], X[2] / X[3]};
+        const bool par = ok && hp_parallax(Xn, cc, max_cos);
+#pragma unroll
+        for (int k = 0; k < 3; k++) { tt[k] = -tt[k]; cc[k] = -cc[k]; }
+        if (pass == 1) { ok_neg = ok; par_neg = par; break; }
+        ok_pos = ok; par_pos = par;
+        if (!__any(zt)) {
+            const double X3 = -X[3];
+            bool o = (X[2] * X3) > 0;
+            const double Xm[3] = {X[0] / X3, X[1] / X3, X[2] / X3};
+            o = o && (Xm[2] < 50.0);
+            const double z2 = ((R[6] * Xm[0] + R[7] * Xm[1]) + R[8] * Xm[2]) + tt[2];
+            ok_neg = o && (z2 > 0) && (z2 < 50.0);
+            par_neg = ok_neg && hp_parallax(Xm, cc, max_cos);
+            break;
+        }
+    }
+}
+
+// part 2, grid (pairs, nsplit) like k_pose_final: the 2 M (rotation, correspondence) items of a PLANE pair in strides, integer votes in
+// LDS, one global atomic per counter per workgroup; the workgroup that takes the last ticket chooses and writes the record.
+__global__ __launch_bounds__(256) void k_hpose_vote(HpArgs A, const float* __restrict__ p1, const float* __restrict__ p2,
+                                                    const uint8_t* __restrict__ mask, const float* __restrict__ rot, vis_hpose_result* out) {
+    __shared__ double sR[2][9], sT[2][3], sN[2][3], sC[2][3];
+    __shared__ int sgood[4], spar[4], stested;
+    const int pair = blockIdx.x, tid = threadIdx.x, nsplit = gridDim.y, part = blockIdx.y;
+    vis_hpose_result* o = out + pair;
+    if (o->kind != VIS_HP_PLANE) return;                           // (uniform: the kind is k_hpose_svd's and the last workgroup writes the same value)
+    const int M = o->n_points;
+    if (tid < 18) sR[tid / 9][tid % 9] = tid < 9 ? o->R[tid] : o->R2[tid - 9];
+    else if (tid < 24) { const int k = tid - 18; sT[k / 3][k % 3] = k < 3 ? o->t[k] : o->t2[k - 3]; }
+    else if (tid < 30) { const int k = tid - 24; sN[k / 3][k % 3] = k < 3 ? o->n[k] : o->n2[k - 3]; }
+    else if (tid < 38) { if (tid < 34) sgood[tid - 30] = 0; else spar[tid - 34] = 0; }
+    else if (tid == 38) stested = 0;
+    __syncthreads();
+    if (tid < 6) {                                                 // R^T t of both rotations, each entry summed left to right
+        const int r = tid / 3, j = tid - 3 * r;
+        sC[r][j] = (sR[r][j] * sT[r][0] + sR[r][3 + j] * sT[r][1]) + sR[r][6 + j] * sT[r][2];
+    }
+    __syncthreads();
+    const float* a = p1 + (size_t)pair * A.in_stride * 2;
+    const float* b = p2 + (size_t)pair * A.in_stride * 2;
+    const uint8_t* mrow = mask ? mask + (size_t)pair * A.row_cap : nullptr;
+    for (int w = part * 256 + tid; w < 2 * M; w += 256 * nsplit) { // (rotation c, point i): votes for candidate c and for its twin with -t, -n
+        const int c = w / M, i = w - c * M;
+        if (mrow && !mrow[i]) continue;
+        if (c == 0) atomicAdd(&stested, 1);
+        const float2 u = reinterpret_cast<const float2*>(a)[i], v = reinterpret_cast<const float2*>(b)[i];
+        const double x1 = ((double)u.x - A.cx) * A.fx_inv, y1 = ((double)u.y - A.cy) * A.fx_inv;
+        const double x2 = ((double)v.x - A.cx) * A.fx_inv, y2 = ((double)v.y - A.cy) * A.fx_inv;
+        bool okp, okn, pp, pn;
+        cheirality_pair_par(sR[c], sT[c], sC[c], A.max_cos, x1, y1, x2, y2, okp, okn, pp, pn);
+        if (okp) atomicAdd(&sgood[c], 1);
+        if (okn) atomicAdd(&sgood[3 - c], 1);
+        if (pp) atomicAdd(&spar[c], 1);
+        if (pn) atomicAdd(&spar[3 - c], 1);
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    if (nsplit > 1) {
+        int* const gpar[4] = {&o->flags, &o->solution, &o->second, &o->n_parallax};
+        for (int c = 0; c < 4; c++) {
+            if (sgood[c]) atomicAdd(&o->n_good[c], sgood[c]);
+            if (spar[c]) atomicAdd(gpar[c], spar[c]);
+        }
+        if (stested) atomicAdd(&o->n_tested, stested);
+        __threadfence();                                           // the sums are visible before the ticket
+        if (atomicAdd(&o->reserved_, 1) != nsplit - 1) return;
+        __threadfence();
+        for (int c = 0; c < 4; c++) { sgood[c] = atomicAdd(&o->n_good[c], 0); spar[c] = atomicAdd(gpar[c], 0); }
+        stested = atomicAdd(&o->n_tested, 0);
+    }
+    // the choice: candidates by (votes descending, index ascending); rivals reach ambiguity_ratio of the best; a hint picks among them
+    int ord[4] = {0, 1, 2, 3};
+    for (int i = 0; i < 4; i++) for (int j = i + 1; j < 4; j++)
+        if (sgood[ord[j]] > sgood[ord[i]] || (sgood[ord[j]] == sgood[ord[i]] && ord[j] < ord[i])) { const int t_ = ord[i]; ord[i] = ord[j]; ord[j] = t_; }
+    const int best = ord[0];
+    int sol = best, flags = 0;
+    bool rival = false;
+    double top = 0;
+    for (int q = 0; q < 4; q++) {
+        const int k = ord[q];
+        if (q > 0 && !((double)sgood[k] >= A.ratio * (double)sgood[best])) continue;
+        if (q > 0) rival = true;
+        if (!rot) continue;
+        const double* R = sR[(k == 0 || k == 3) ? 0 : 1];
+        double s = 0;
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) s = s + R[3 * i + j] * (double)rot[(size_t)pair * 9 + 3 * j + i];
+        if (q == 0 || s > top) { top = s; sol = k; }
+    }
+    if (rival) flags |= rot ? VIS_HPF_HINTED : VIS_HPF_AMBIGUOUS;
+    const int second = ord[0] != sol ? ord[0] : ord[1];
+    const double few_a = (double)A.min_good, few_b = A.good_share * (double)stested;
+    if ((double)sgood[sol] < (few_a > few_b ? few_a : few_b)) flags |= VIS_HPF_FEW;
+    if ((double)spar[sol] < A.par_share * (double)sgood[sol]) flags |= VIS_HPF_LOW_PARALLAX;
+    vis_hpose_result r;
+    for (int half = 0; half < 2; half++) {
+        const int k = half ? second : sol, rr = (k == 0 || k == 3) ? 0 : 1;
+        double* R = half ? r.R2 : r.R; double* t = half ? r.t2 : r.t; double* n = half ? r.n2 : r.n;
+        for (int i = 0; i < 9; i++) R[i] = sR[rr][i];
+        for (int i = 0; i < 3; i++) { t[i] = k < 2 ? sT[rr][i] : -sT[rr][i]; n[i] = k < 2 ? sN[rr][i] : -sN[rr][i]; }
+    }
+    for (int i = 0; i < 3; i++) r.sv[i] = o->sv[i];
+    r.t_norm = o->t_norm;
+    for (int c = 0; c < 4; c++) r.n_good[c] = sgood[c];
+    r.kind = VIS_HP_PLANE; r.flags = flags; r.solution = sol; r.second = second;
+    r.n_tested = stested; r.n_parallax = spar[sol]; r.n_points = M; r.reserved_ = 0;
+    *o = r;
+}
+
 // ------------------------------------------------------------------------------------------------
 static PoseParams make_pose_params(const vis_ctx* ctx, int max_iters, int mcap) {
     PoseParams P;
@@ -2018,6 +2215,24 @@ int epi_filter_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, c
     if (npairs <= 0) return VIS_OK;
     const F2fArgs A = epi_args(ctx, threshold, 0, in_stride);
     hipLaunchKernelGGL(k_epi_filter, dim3(npairs), dim3(256), 0, ctx->stream, A, row_cap, d_p1, d_p2, d_npts, d_rot, d_t, d_keep, d_nkeep);
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+// hq has been validated by the entry point.  d_h: npairs homography records; d_p1 / d_p2: rows of in_stride (x, y) points, d_npts of them valid
+// (clamped); d_mask: rows of row_cap >= in_stride bytes, or null; d_rot: npairs x 9 floats, or null; d_out: npairs records.  On ctx->stream.
+int hpose_run(vis_ctx* ctx, const vis_hpose_params* hq, int npairs, int in_stride, const vis_homography_result* d_h, const float* d_p1,
+              const float* d_p2, const int32_t* d_npts, int row_cap, const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out) {
+    if (npairs <= 0) return VIS_OK;
+    if (in_stride > (1 << 29)) { ctx->err = "homography pose: more than 2^29 correspondences per row"; return VIS_E_CAPACITY; }   // 2 M work items in an int
+    HpArgs A;
+    A.fx_inv = 1. / ctx->p.fx; A.cx = ctx->p.cx; A.cy = ctx->p.cy;
+    A.min_t_over_d = hq->min_t_over_d; A.max_cos = hq->max_cos_parallax; A.ratio = hq->ambiguity_ratio;
+    A.good_share = hq->good_share; A.par_share = hq->parallax_share;
+    A.min_good = hq->min_good; A.in_stride = in_stride; A.row_cap = row_cap; A.npairs = npairs;
+    const int nsplit = (int)std::max<long long>(1, std::min<long long>(32, (4LL * in_stride + 4095) / 4096));  // k_pose_final's: ~16 triangulations per thread
+    hipLaunchKernelGGL(k_hpose_svd, dim3((npairs + 63) / 64), dim3(64), 0, ctx->stream, A, d_h, d_npts, d_out);
+    hipLaunchKernelGGL(k_hpose_vote, dim3(npairs, nsplit), dim3(256), 0, ctx->stream, A, d_p1, d_p2, d_mask, d_rot, d_out);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

@@ -421,6 +421,10 @@ int epi_filter_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, c
 int homography_batch_run(vis_ctx* ctx, const vis_homography_params* hp, int npairs, int in_stride, const float* d_p1, const float* d_p2,
                          const int32_t* d_npts, const int32_t* d_draws, const double* d_E, int e_stride, int row_cap, uint8_t* d_mask,
                          vis_homography_result* d_out);
+// pose.hip: k_hpose_svd + k_hpose_vote on ctx->stream; hq validated by the caller; d_mask: rows of row_cap >= in_stride bytes, or null; d_rot: npairs x 9
+// floats, or null
+int hpose_run(vis_ctx* ctx, const vis_hpose_params* hq, int npairs, int in_stride, const vis_homography_result* d_h, const float* d_p1,
+              const float* d_p2, const int32_t* d_npts, int row_cap, const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out);
 #define VIS_RSTATE_WORDS 16
 
 #endif

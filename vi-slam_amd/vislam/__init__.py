@@ -10,6 +10,7 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.f2f_ransac           <-> VISystem::F2FRansac                      (src/VISystem.cpp:612-769)
   Context.f2f_batch / batch_f2f                       <-> the same for every pair of a batch
   Context.find_homography / homography_batch / batch_homography   homography RANSAC and the H-or-E model choice (beyond the reference)
+  Context.homography_pose / homography_pose_batch / batch_homography_pose   (R, t / d, n) of a pair's homography, both survivors of the vote
   Context.filter_keypoints (_batch, batch_...)        <-> VISystem::FilterKeypoints  (src/VISystem.cpp:542-610)
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises.
@@ -159,6 +160,29 @@ MODEL_NONE, MODEL_HOMOGRAPHY, MODEL_ESSENTIAL = 0, 1, 2
 MODEL_NAMES = ("none", "homography", "essential")
 
 
+class HposeParams(C.Structure):
+    """vis_hpose_params: the knobs of the homography pose (vis_default_hpose_params: 0.05, cos 1 deg, 0.75, 0.9, 0.5, 8)"""
+    _fields_ = [("min_t_over_d", C.c_double), ("max_cos_parallax", C.c_double), ("ambiguity_ratio", C.c_double), ("good_share", C.c_double),
+                ("parallax_share", C.c_double), ("min_good", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class HposeResult(C.Structure):
+    """vis_hpose_result: the chosen and the second candidate (R, t / d, n) of one pair's homography, the votes and the flags"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("n", C.c_double * 3), ("R2", C.c_double * 9), ("t2", C.c_double * 3),
+                ("n2", C.c_double * 3), ("sv", C.c_double * 3), ("t_norm", C.c_double), ("n_good", C.c_int32 * 4), ("kind", C.c_int32),
+                ("flags", C.c_int32), ("solution", C.c_int32), ("second", C.c_int32), ("n_tested", C.c_int32), ("n_parallax", C.c_int32),
+                ("n_points", C.c_int32), ("reserved_", C.c_int32)]
+
+
+HPOSE_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("n", "<f8", (3,)), ("R2", "<f8", (9,)), ("t2", "<f8", (3,)), ("n2", "<f8", (3,)),
+                               ("sv", "<f8", (3,)), ("t_norm", "<f8"), ("n_good", "<i4", (4,)), ("kind", "<i4"), ("flags", "<i4"), ("solution", "<i4"),
+                               ("second", "<i4"), ("n_tested", "<i4"), ("n_parallax", "<i4"), ("n_points", "<i4"), ("reserved_", "<i4")])
+assert C.sizeof(HposeParams) == 48 and HPOSE_RESULT_DTYPE.itemsize == C.sizeof(HposeResult) == 320
+HP_NONE, HP_ROTATION, HP_PLANE = 0, 1, 2
+HPF_AMBIGUOUS, HPF_HINTED, HPF_FEW, HPF_LOW_PARALLAX = 1, 2, 4, 8
+HP_KIND_NAMES = ("none", "rotation", "plane")
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -199,6 +223,7 @@ ABI_SYMBOLS = [
     "vis_default_tri_params", "vis_triangulate", "vis_batch_triangulate",
     "vis_f2f_batch", "vis_batch_f2f", "vis_filter_keypoints_batch", "vis_batch_filter_keypoints", "vis_filter_keypoints",
     "vis_default_homography_params", "vis_find_homography", "vis_homography_batch", "vis_batch_homography",
+    "vis_default_hpose_params", "vis_homography_pose", "vis_homography_pose_batch", "vis_batch_homography_pose",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
@@ -281,6 +306,13 @@ def _load():
         lib.vis_find_homography.argtypes = [vp, hpp, vp, vp, ci, vp, vp, vp, vp]
         lib.vis_homography_batch.argtypes = [vp, hpp, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
         lib.vis_batch_homography.argtypes = [vp, hpp, ci, vp, ci, vp, vp]
+    if hasattr(lib, "vis_batch_homography_pose"):       # (absent from older A/B builds)
+        hqp = C.POINTER(HposeParams)
+        lib.vis_default_hpose_params.argtypes = [hqp]
+        lib.vis_default_hpose_params.restype = None
+        lib.vis_homography_pose.argtypes = [vp, hqp, vp, vp, vp, ci, vp, vp, vp]
+        lib.vis_homography_pose_batch.argtypes = [vp, hqp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp]
+        lib.vis_batch_homography_pose.argtypes = [vp, hqp, ci, vp, ci, vp, vp, vp]
     if hasattr(lib, "vis_set_align_weights"):           # (absent from older A/B builds)
         lib.vis_default_align_weights.argtypes = [C.POINTER(AlignWeights)]
         lib.vis_default_align_weights.restype = None
@@ -391,6 +423,12 @@ def default_homography_params():
     hp = HomographyParams()
     lib.vis_default_homography_params(C.byref(hp))
     return hp
+
+
+def default_hpose_params():
+    hq = HposeParams()
+    lib.vis_default_hpose_params(C.byref(hq))
+    return hq
 
 
 def se3_exp(a):
@@ -952,6 +990,41 @@ class Context:
         hp = default_homography_params() if hp is None else hp
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_homography(self._h, C.byref(hp), n, v(d_draws_ptr), row_cap, v(d_mask_ptr), v(d_out_ptr)), "vis_batch_homography")
+
+    # -- the pose of a homography ---------------------------------------------------------------------------------
+    def homography_pose(self, hrec, p1, p2, mask=None, rot_hint=None, hq=None):
+        """one HPOSE_RESULT_DTYPE element: (R, t / d, n) of the pair's homography record hrec (one HOMOGRAPHY_RESULT_DTYPE element), the
+        chosen and the second candidate; p1 / p2 m x 2 float pixels, mask m bytes or None (everyone votes), rot_hint 3 x 3 (current-frame rays
+        -> previous frame) or None"""
+        hq = default_hpose_params() if hq is None else hq
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        assert len(p1) == len(p2)
+        h = np.frombuffer(np.asarray(hrec).tobytes(), HOMOGRAPHY_RESULT_DTYPE).copy()
+        assert len(h) == 1
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert mask is None or len(mask) >= len(p1)
+        rot = None if rot_hint is None else np.ascontiguousarray(rot_hint, np.float32).reshape(9)
+        out = np.zeros(1, HPOSE_RESULT_DTYPE)
+        self._chk(lib.vis_homography_pose(self._h, C.byref(hq), _ptr(h), _ptr(p1), _ptr(p2), len(p1), _ptr(mask), _ptr(rot), _ptr(out)),
+                  "vis_homography_pose")
+        return out[0]
+
+    def homography_pose_batch(self, n, d_h_ptr, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_rot_ptr, d_out_ptr, hq=None):
+        """queue the homography pose of n rows of max_pts (x, y) correspondences on the context's stream (raw DEVICE pointers; 0 / None = NULL
+        for d_mask and d_rot): n HposeResult records from n HomographyResult records"""
+        hq = default_hpose_params() if hq is None else hq
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_homography_pose_batch(self._h, C.byref(hq), n, v(d_h_ptr), v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, row_cap,
+                                                v(d_mask_ptr), v(d_rot_ptr), v(d_out_ptr)), "vis_homography_pose_batch")
+
+    def batch_homography_pose(self, n, d_h_ptr, row_cap, d_mask_ptr, d_rot_ptr, d_out_ptr, hq=None):
+        """the same on the pairs of the last batch_run, from the records and mask rows batch_homography wrote, on the pose stream behind it;
+        the buffers are in use until batch_sync()"""
+        hq = default_hpose_params() if hq is None else hq
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_homography_pose(self._h, C.byref(hq), n, v(d_h_ptr), row_cap, v(d_mask_ptr), v(d_rot_ptr), v(d_out_ptr)),
+                  "vis_batch_homography_pose")
 
     # -- batched stream path ----------------------------------------------------------------------------------
     def batch_plan(self, w, h, stride, max_frames):
