@@ -3,7 +3,10 @@ vis_batch_filter_keypoints / vis_filter_keypoints; VISystem::F2FRansac, src/VISy
 
 Every F2F record is checked against the single call (ctx.f2f_ransac on the same pair with idx = draws % (m - 1) and the float scale: t
 byte-identical, equal count), against the oracle (orc.f2f_ransac: equal count, |dt| <= 1e-6, the project's own tolerance,
-tests/test_pose_gpu.py) and against tests/f2f_ref.py (best_iter, n_degenerate, flipped).  Filter masks and counts are compared byte for byte
+tests/test_pose_gpu.py) and against tests/f2f_ref.py (best_iter, n_degenerate, flipped).  The single call and the batch now run the same
+kernel template (k_f2f_batch: the single call is one pair of it with its indices taken as given, the batch reduces raw draws modulo
+m - 1), so the first comparison only shows that the two index forms, the two row layouts and the host's scale agree; the independent
+checks are the oracle and tests/f2f_ref.py, both asserted on every record below.  Filter masks and counts are compared byte for byte
 with the restatement.  The plan's pairs are rebuilt from the batch getters.
 
 The stream of the plan tests: vis_synth_frame_parallax, canvas 2048 / seed 0xE0C00001, 752 x 480, fy = fx, frames 0 ... 15; the oracle's
@@ -64,7 +67,7 @@ def _filled(torch, nbytes):
 
 
 def _check_record(vislam, orc, single, p, rec, a, b, rot, draws, tref, where):
-    """one record of a batch against the single call, the oracle and the restatement"""
+    """one record of a batch against the single call (the same kernel template), and -- independently -- the oracle and the restatement"""
     KP = vislam.KEYPOINT_DTYPE
     m, iters = len(a), int(p.f2f_iters)
     want = fr.f2f(p, a, b, rot, draws, tref)

@@ -517,47 +517,46 @@ extern "C" int vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* 
     int rc = check_align_params(ctx, ap, w, h);
     if (rc) return rc;
     (void)hipSetDevice(ctx->device);
-    size_t need = 4096;
     int alw[5], alh[5]; vis_half_dims(w, h, alw, alh);
     for (int l = ap->last_level; l <= ap->first_level; l++) {
         const int N = n_cand[l];
         if (N < 0 || N > (1 << 24)) return VIS_E_INVALID;
         if (N && (!gray1[l] || !gray2[l] || !gx1[l] || !gy1[l] || !cand1[l])) return VIS_E_INVALID;
-        const size_t px = (size_t)alw[l] * alh[l];
-        need += 6 * px + (size_t)N * 16 + 6 * 256;
     }
-    rc = vis_ensure_scratch(ctx, need + sizeof(vis_se3f) + sizeof(vis_align_result) + 1024);
-    if (!rc) rc = vis_ensure_pin(ctx, need + sizeof(vis_se3f) + sizeof(vis_align_result) + 4096);     // (the caller's arrays are pageable: through the pinned block, one wait per call)
-    if (rc) return rc;
-    HostStage hs(ctx);
-    Carver cv{(char*)ctx->d_scratch, 0};
     AlignArgs G; std::memset(&G, 0, sizeof(G));
     fill_level_intrinsics(*ap, G);
+    vis_se3f* d_init = nullptr; vis_align_result* d_out;
+    rc = vis_carve(ctx, [&](Carver& cv) {                          // (the caller's arrays are pageable: through the pinned block, one wait per call)
+        for (int l = ap->last_level; l <= ap->first_level; l++) {
+            const size_t px = (size_t)alw[l] * alh[l];
+            AlignLevel& V = G.lv[l];
+            V.cols = w >> l; V.rows = h >> l; V.acols = alw[l]; V.arows = alh[l]; V.rowstride = alw[l]; V.ncand = n_cand[l]; V.img_fstride = 0; V.grad_fstride = 0;
+            if (!V.ncand) continue;
+            V.i1 = cv.take<uint8_t>(px); V.i2 = cv.take<uint8_t>(px);
+            V.gx = cv.take<int16_t>(px); V.gy = cv.take<int16_t>(px);
+            V.cand = cv.take<float>((size_t)V.ncand * 4);
+        }
+        if (init) d_init = cv.take<vis_se3f>(1);
+        d_out = cv.take<vis_align_result>(1);
+    });
+    if (rc) return rc;
+    HostStage hs(ctx);
     hipStream_t st = ctx->stream;
     for (int l = ap->last_level; l <= ap->first_level; l++) {
-        const int N = n_cand[l];
-        const int cols = w >> l, rows = h >> l;
+        const AlignLevel& V = G.lv[l];
         const size_t px = (size_t)alw[l] * alh[l];
-        AlignLevel& V = G.lv[l];
-        V.cols = cols; V.rows = rows; V.acols = alw[l]; V.arows = alh[l]; V.rowstride = alw[l]; V.ncand = N; V.img_fstride = 0; V.grad_fstride = 0;
-        if (!N) continue;
-        uint8_t* d1 = cv.take<uint8_t>(px); uint8_t* d2 = cv.take<uint8_t>(px);
-        int16_t* dgx = cv.take<int16_t>(px); int16_t* dgy = cv.take<int16_t>(px);
-        float* dc = cv.take<float>((size_t)N * 4);
-        hs.up(d1, gray1[l], px); hs.up(d2, gray2[l], px);
-        hs.up(dgx, gx1[l], px * 2); hs.up(dgy, gy1[l], px * 2);
-        hs.up(dc, cand1[l], (size_t)N * 16);
-        V.i1 = d1; V.i2 = d2; V.gx = dgx; V.gy = dgy; V.cand = dc;
+        if (!V.ncand) continue;
+        hs.up((void*)V.i1, gray1[l], px); hs.up((void*)V.i2, gray2[l], px);
+        hs.up((void*)V.gx, gx1[l], px * 2); hs.up((void*)V.gy, gy1[l], px * 2);
+        hs.up((void*)V.cand, cand1[l], (size_t)V.ncand * 16);
     }
-    vis_se3f* d_init = nullptr;
-    if (init) { d_init = cv.take<vis_se3f>(1); hs.up(d_init, init, sizeof(vis_se3f)); }
+    if (init) hs.up(d_init, init, sizeof(vis_se3f));
     hs.flush_ups();
-    vis_align_result* d_out = cv.take<vis_align_result>(1);
     G.init = d_init; G.out = d_out; G.f1_off = 0; G.f2_off = 0; G.out_off = 0;
     fill_weights(ctx, G);
     if (G.wmode == VIS_W_IDENTITY) hipLaunchKernelGGL((k_align<false, false>), dim3(1), dim3(AL_THREADS), 0, st, G);
     else hipLaunchKernelGGL((k_align<false, true>), dim3(1), dim3(AL_THREADS), 0, st, G);
-    HIPCHK(ctx, hipGetLastError());
+    if (const hipError_t e = hipGetLastError()) { ctx->err = std::string("k_align launch: ") + hipGetErrorString(e); return vis_drain(ctx, VIS_E_HIP); }
     const void* h_out = hs.down(d_out, sizeof(vis_align_result));
     rc = hs.wait();
     if (rc) return rc;

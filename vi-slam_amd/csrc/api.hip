@@ -433,7 +433,6 @@ int vis_ensure_scratch(vis_ctx* ctx, size_t bytes) {
     ctx->scratch_bytes = bytes;
     return VIS_OK;
 }
-static inline int ensure_scratch(vis_ctx* ctx, size_t bytes) { return vis_ensure_scratch(ctx, bytes); }
 
 std::atomic<unsigned long long> vis_g_launches{0};
 
@@ -557,20 +556,16 @@ extern "C" int vis_camera_update(vis_ctx* ctx, const uint8_t* img, int w, int h,
     }
     (void)hipSetDevice(ctx->device);
     int lw[5], lh[5]; vis_half_dims(w, h, lw, lh);
-    size_t lvl_bytes[5]; size_t total = (size_t)w * h;
-    lvl_bytes[0] = (size_t)w * h;
-    for (int l = 1; l < 5; l++) { lvl_bytes[l] = (size_t)lw[l] * lh[l]; total += lvl_bytes[l] + 256; }
-    int rc = ensure_scratch(ctx, total + 1024);
-    if (!rc) rc = vis_ensure_pin(ctx, 2 * total + 4096);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
+    size_t lvl_bytes[5];
+    for (int l = 0; l < 5; l++) lvl_bytes[l] = (size_t)lw[l] * lh[l];
     uint8_t* d[5];
-    for (int l = 0; l < 5; l++) d[l] = cv.take<uint8_t>(lvl_bytes[l]);
+    int rc = vis_carve(ctx, [&](Carver& cv) { for (int l = 0; l < 5; l++) d[l] = cv.take<uint8_t>(lvl_bytes[l]); }, 2);   // (d[0] goes up and may come down)
+    if (rc) return rc;
     HostStage hs(ctx);
     hs.up2d(d[0], w, img, stride, w, h);
     hs.flush_ups();
     rc = launch_half_pyramid(ctx, d[0], w, h, w, d);
-    if (rc) return rc;
+    if (rc) return vis_drain(ctx, rc);
     const void* got[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     for (int l = 0; l < 5; l++) if (out_levels[l]) got[l] = hs.down(d[l], lvl_bytes[l]);
     rc = hs.wait();
@@ -607,20 +602,19 @@ extern "C" int vis_compute_gradient(vis_ctx* ctx, const uint8_t* img, int w, int
     (void)hipSetDevice(ctx->device);
     const size_t fe = vis_grad_frame_elems(w, h);
     const int ws = (w + 15) & ~15;                              // device row stride of the copy (the batched entry wants % 4 == 0)
-    int rc = ensure_scratch(ctx, (size_t)ws * h + fe * 6 + 4096);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    uint8_t* d_img = cv.take<uint8_t>((size_t)ws * h);
-    uint8_t* d_gray = cv.take<uint8_t>(fe);
-    int16_t* d_gx = cv.take<int16_t>(fe); int16_t* d_gy = cv.take<int16_t>(fe);
-    uint8_t* d_g = cv.take<uint8_t>(fe);
-    rc = vis_ensure_pin(ctx, (size_t)w * h + fe * 5 + 4096);
+    uint8_t *d_img, *d_gray, *d_g; int16_t *d_gx, *d_gy;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_img = cv.take<uint8_t>((size_t)ws * h);
+        d_gray = cv.take<uint8_t>(fe);
+        d_gx = cv.take<int16_t>(fe); d_gy = cv.take<int16_t>(fe);
+        d_g = cv.take<uint8_t>(fe);
+    });
     if (rc) return rc;
     HostStage hs(ctx);
     hs.up2d(d_img, ws, img, stride, w, h);
     hs.flush_ups();
     rc = vis_gradient_batch(ctx, d_img, w, h, ws, 1, scale, d_gray, d_gx, d_gy, d_g);
-    if (rc) return rc;
+    if (rc) return vis_drain(ctx, rc);
     int lw[5], lh[5]; vis_half_dims(w, h, lw, lh);
     // the three outputs are dense over the five levels: one copy each, cut into levels on the host
     const int16_t* h_gx = (const int16_t*)hs.down(d_gx, fe * 2);
@@ -644,20 +638,19 @@ extern "C" int vis_patch_points(vis_ctx* ctx, const vis_keypoint* good, int n, i
     if (!ctx || (n > 0 && !good) || n < 0 || cap < 0 || !patch || !debug || !n_patch || !n_debug) return VIS_E_INVALID;
     (void)hipSetDevice(ctx->device);
     const int m = std::min(n, 200);
-    int rc = ensure_scratch(ctx, (size_t)200 * sizeof(vis_keypoint) + (size_t)2 * 5 * std::max(cap, 1) * 16 + 4096);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    vis_keypoint* d_good = cv.take<vis_keypoint>(200);
-    float* d_patch = cv.take<float>((size_t)5 * std::max(cap, 1) * 4);
-    float* d_debug = cv.take<float>((size_t)5 * std::max(cap, 1) * 4);
-    int32_t* d_cnt = cv.take<int32_t>(10);
-    rc = vis_ensure_pin(ctx, (size_t)200 * sizeof(vis_keypoint) + (size_t)10 * std::max(cap, 1) * 16 + 4096);
+    vis_keypoint* d_good; float *d_patch, *d_debug; int32_t* d_cnt;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_good = cv.take<vis_keypoint>(200);
+        d_patch = cv.take<float>((size_t)5 * std::max(cap, 1) * 4);
+        d_debug = cv.take<float>((size_t)5 * std::max(cap, 1) * 4);
+        d_cnt = cv.take<int32_t>(10);
+    }, 2);                                                         // (the two lists come down in five pieces each, one per level)
     if (rc) return rc;
     HostStage hs(ctx);
     hs.up(d_good, good, (size_t)m * sizeof(vis_keypoint));
     hs.flush_ups();
     rc = launch_patch_points(ctx, d_good, m, ctx->p.w_size, ctx->p.h_size, d_patch, d_debug, cap, d_cnt);
-    if (rc) return rc;
+    if (rc) return vis_drain(ctx, rc);
     // counts and both point lists of all five levels behind the kernels.  The list lengths are not known before the wait, but their
     // bounds are: min(m, 200) keypoints x at most (2 sp + 2)^2 points of a level's window (sp = 5, 3, 2, 5, 5: k_patch_points) and one
     // debug point per keypoint -- that much of every level is fetched, not the caller's whole capacity (200 x 121 x 16 B x 5 levels x 2
@@ -843,16 +836,15 @@ extern "C" int vis_warp_keypoints(vis_ctx* ctx, const vis_keypoint* kps, int n, 
     if (!ctx) return VIS_E_STATE;
     if (n == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
-    const size_t need = (size_t)n * (sizeof(vis_keypoint) + 8) + 4096;
-    int rc = ensure_scratch(ctx, need);
-    if (!rc) rc = vis_ensure_pin(ctx, need);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
     Plan tp; tp.kcap = n;
-    tp.d_kps = cv.take<vis_keypoint>(n);
-    tp.d_nkp = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
-    float* d_rot = cv.take<float>(9);
-    float2* d_xy = cv.take<float2>(n);
+    float* d_rot; float2* d_xy;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        tp.d_kps = cv.take<vis_keypoint>(n);
+        tp.d_nkp = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
+        d_rot = cv.take<float>(9);
+        d_xy = cv.take<float2>(n);
+    });
+    if (rc) return rc;
     const int32_t head[2] = {n, 0};                               // nkp[0] = n; pair 0's current record = 0
     HostStage hs(ctx);
     hs.up(tp.d_kps, kps, (size_t)n * sizeof(vis_keypoint));
@@ -861,7 +853,7 @@ extern "C" int vis_warp_keypoints(vis_ctx* ctx, const vis_keypoint* kps, int n, 
     hs.flush_ups();
     rc = launch_warp(ctx, &tp, 1, d_rot, d_xy);
     tp = Plan();       // scratch-owned pointers: nothing to free
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     const void* h_xy = hs.down(d_xy, (size_t)n * 8);
     rc = hs.wait();
     if (rc) return rc;
@@ -880,19 +872,19 @@ extern "C" int vis_bf_knn2_hamming_guided_host(vis_ctx* ctx, const uint8_t* desc
     (void)hipSetDevice(ctx->device);
     const int kcap = std::max(std::max(std::max(n_q, n_t), 1), std::min(ctx->p.keypoint_capacity, 65535));
     const bool mfma = kcap <= 16384;
-    int rc = ensure_scratch(ctx, (size_t)kcap * ((32 + 8 + sizeof(vis_keypoint)) * 2 + 8 + (mfma ? 256 : 0)) + 8192);
-    if (!rc) rc = vis_ensure_pin(ctx, (size_t)std::max(std::max(n_q, n_t), 1) * ((32 + sizeof(vis_keypoint)) * 2 + 16) + 4096);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
     Plan tp;
     tp.kcap = kcap; tp.npairs = 1;
-    tp.d_desc = cv.take<uint8_t>((size_t)kcap * 64);
-    tp.d_kps = cv.take<vis_keypoint>((size_t)kcap * 2);
-    tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
-    tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
-    tp.d_warp = cv.take<float2>(kcap);
-    float* d_rot = cv.take<float>(9);
-    if (mfma) tp.d_descx = cv.take<int8_t>((size_t)kcap * 256);
+    float* d_rot;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        tp.d_desc = cv.take<uint8_t>((size_t)kcap * 64);
+        tp.d_kps = cv.take<vis_keypoint>((size_t)kcap * 2);
+        tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
+        tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
+        tp.d_warp = cv.take<float2>(kcap);
+        d_rot = cv.take<float>(9);
+        if (mfma) tp.d_descx = cv.take<int8_t>((size_t)kcap * 256);
+    });
+    if (rc) return rc;
     const int32_t nk[2] = {n_q, n_t};
     const MatchGuide g = {d_rot, radius};
     HostStage hs(ctx);
@@ -911,7 +903,7 @@ extern "C" int vis_bf_knn2_hamming_guided_host(vis_ctx* ctx, const uint8_t* desc
     const uint32_t* h12 = out12 && n_q ? (const uint32_t*)hs.down(tp.d_knn12, (size_t)n_q * 8) : nullptr;
     const uint32_t* h21 = out21 && n_t ? (const uint32_t*)hs.down(tp.d_knn21, (size_t)n_t * 8) : nullptr;
     tp = Plan();       // scratch-owned pointers: nothing to free
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     rc = hs.wait();
     if (rc) return rc;
     { float a = 0; if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[4], ctx->ev[5])) ctx->tm.ms_knn = a; }
@@ -926,16 +918,15 @@ extern "C" int vis_bf_knn2_hamming_host(vis_ctx* ctx, const uint8_t* desc_q, int
     if (n_q > 65535 || n_t > 65535) return VIS_E_INVALID;
     (void)hipSetDevice(ctx->device);
     const int kcap = std::max(std::max(n_q, n_t), 1);
-    int rc = ensure_scratch(ctx, (size_t)kcap * 32 * 2 + (size_t)kcap * 8 * 2 + (size_t)kcap * 256 + 8192);
-    if (!rc) rc = vis_ensure_pin(ctx, (size_t)kcap * (64 + 16) + 4096);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
     Plan tp;
     tp.kcap = kcap;
-    tp.d_desc = cv.take<uint8_t>((size_t)kcap * 64);
-    tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
-    tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
-    tp.d_descx = cv.take<int8_t>((size_t)kcap * 256);
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        tp.d_desc = cv.take<uint8_t>((size_t)kcap * 64);
+        tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
+        tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
+        tp.d_descx = cv.take<int8_t>((size_t)kcap * 256);
+    });
+    if (rc) return rc;
     const int32_t nk[2] = {n_q, n_t};
     HostStage hs(ctx);
     hs.up(tp.d_desc, desc_q, (size_t)n_q * 32);
@@ -950,7 +941,7 @@ extern "C" int vis_bf_knn2_hamming_host(vis_ctx* ctx, const uint8_t* desc_q, int
     const uint32_t* h12 = out12 && n_q ? (const uint32_t*)hs.down(tp.d_knn12, (size_t)n_q * 8) : nullptr;
     const uint32_t* h21 = out21 && n_t ? (const uint32_t*)hs.down(tp.d_knn21, (size_t)n_t * 8) : nullptr;
     tp = Plan();       // scratch-owned pointers: nothing to free
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     rc = hs.wait();
     if (rc) return rc;
     { float a = 0; if (ctx->ev_ok && ev_elapsed(&a, ctx->ev[4], ctx->ev[5])) ctx->tm.ms_knn = a; }
@@ -1043,25 +1034,22 @@ extern "C" int vis_good_matches_host(vis_ctx* ctx, const vis_keypoint* kps1, int
     const int kcap = std::max(std::max(n1, n2), 1);
     int root; std::vector<float> hf, wf; vis_grid_limits(ctx->p, &root, hf, wf);
     const int ncell = root * root;
-    size_t need = (size_t)kcap * (2 * sizeof(vis_keypoint) + 16 + sizeof(vis_dmatch)) + (size_t)ncell * (sizeof(vis_dmatch) + 16) + 16384;
-    int rc = ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
     Plan tp; tp.kcap = kcap; tp.root = root;
-    tp.d_kps = cv.take<vis_keypoint>((size_t)kcap * 2);
-    tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
-    tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
-    Plan::MatchOut& o = tp.out();
-    o.sym = cv.take<vis_dmatch>(kcap); o.nsym = cv.take<int32_t>(1);
-    o.good = cv.take<vis_dmatch>(ncell); o.ngood = cv.take<int32_t>(1);
-    o.p1 = cv.take<float>((size_t)ncell * 2); o.p2 = cv.take<float>((size_t)ncell * 2);
-    tp.d_hf = cv.take<float>(root); tp.d_wf = cv.take<float>(root);
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        tp.d_kps = cv.take<vis_keypoint>((size_t)kcap * 2);
+        tp.d_nkp = cv.take<int32_t>(2); tp.d_pair_q = cv.take<int32_t>(1); tp.d_pair_t = cv.take<int32_t>(1);
+        tp.d_knn12 = cv.take<uint32_t>((size_t)kcap * 2); tp.d_knn21 = cv.take<uint32_t>((size_t)kcap * 2);
+        Plan::MatchOut& o = tp.out();
+        o.sym = cv.take<vis_dmatch>(kcap); o.nsym = cv.take<int32_t>(1);
+        o.good = cv.take<vis_dmatch>(ncell); o.ngood = cv.take<int32_t>(1);
+        o.p1 = cv.take<float>((size_t)ncell * 2); o.p2 = cv.take<float>((size_t)ncell * 2);
+        tp.d_hf = cv.take<float>(root); tp.d_wf = cv.take<float>(root);
+    });
+    if (rc) return rc;
     std::vector<uint32_t> k12(2 * (size_t)kcap, 0xFFFFFFFFu), k21(2 * (size_t)kcap, 0xFFFFFFFFu);
     for (int i = 0; i < 2 * n1; i++) k12[i] = dmatch_to_key(knn12[i]);
     for (int i = 0; i < 2 * n2; i++) k21[i] = dmatch_to_key(knn21[i]);
     const int32_t nk[2] = {n1, n2};
-    rc = vis_ensure_pin(ctx, (size_t)kcap * (2 * sizeof(vis_keypoint) + 16 + sizeof(vis_dmatch)) + (size_t)ncell * sizeof(vis_dmatch) + (size_t)root * 8 + 8192);
-    if (rc) { tp = Plan(); return rc; }
     HostStage hs(ctx);
     hs.up(tp.d_kps, kps1, (size_t)n1 * sizeof(vis_keypoint));
     hs.up(tp.d_kps + kcap, kps2, (size_t)n2 * sizeof(vis_keypoint));
@@ -1074,7 +1062,7 @@ extern "C" int vis_good_matches_host(vis_ctx* ctx, const vis_keypoint* kps1, int
     hs.up(tp.d_wf, wf.data(), (size_t)root * 4);
     hs.flush_ups();
     rc = launch_filter(ctx, &tp, 1);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); tp = Plan(); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     const MatchFetch f = fetch_matches(hs, &tp, 0, good != nullptr, cap, sym_out != nullptr, sym_cap);
     tp = Plan();
     rc = hs.wait();
@@ -1091,23 +1079,23 @@ static int pose_host(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m, 
     const int iters = ctx->p.ransac_max_iters;
     // scratch sized for a power-of-two correspondence count >= 256: a stream whose match count creeps up does not re-allocate per call
     int mroom = 256; while (mroom < mcap) mroom <<= 1;
-    size_t need = (size_t)mroom * (16 + 32 + 1) + (size_t)iters * (20 + 720 + 40 + 8 * VIS_HYP_DOUBLES) + 65536;
-    int rc = ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    float* d_p1 = cv.take<float>((size_t)mcap * 2); float* d_p2 = cv.take<float>((size_t)mcap * 2);
-    int32_t* d_npts = cv.take<int32_t>(1);
-    double* d_n1 = cv.take<double>((size_t)mcap * 2); double* d_n2 = cv.take<double>((size_t)mcap * 2);
-    int32_t* d_samples = cv.take<int32_t>((size_t)iters * 5);
-    double* d_models = cv.take<double>((size_t)iters * 90);
-    int32_t* d_counts = cv.take<int32_t>((size_t)iters * 10);
-    int32_t* d_rstate = cv.take<int32_t>(VIS_RSTATE_WORDS);
-    double* d_E = cv.take<double>(9);
-    uint8_t* d_mask = cv.take<uint8_t>(mcap);
-    PoseOut* d_pose = cv.take<PoseOut>(1);
-    int32_t* d_worklist = cv.take<int32_t>(3);
-    double* d_hyp = cv.take<double>((size_t)iters * VIS_HYP_DOUBLES);
-    rc = vis_ensure_pin(ctx, (size_t)mcap * 17 + sizeof(PoseOut) + 4096);
+    float *d_p1, *d_p2; double *d_n1, *d_n2, *d_models, *d_E, *d_hyp; int32_t *d_npts, *d_samples, *d_counts, *d_rstate, *d_worklist;
+    uint8_t* d_mask; PoseOut* d_pose;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        const size_t mc = cv.base ? mcap : mroom;                  // measured with room, bound to what the call uses
+        d_p1 = cv.take<float>(mc * 2); d_p2 = cv.take<float>(mc * 2);
+        d_npts = cv.take<int32_t>(1);
+        d_n1 = cv.take<double>(mc * 2); d_n2 = cv.take<double>(mc * 2);
+        d_samples = cv.take<int32_t>((size_t)iters * 5);
+        d_models = cv.take<double>((size_t)iters * 90);
+        d_counts = cv.take<int32_t>((size_t)iters * 10);
+        d_rstate = cv.take<int32_t>(VIS_RSTATE_WORDS);
+        d_E = cv.take<double>(9);
+        d_mask = cv.take<uint8_t>(mc);
+        d_pose = cv.take<PoseOut>(1);
+        d_worklist = cv.take<int32_t>(3);
+        d_hyp = cv.take<double>((size_t)iters * VIS_HYP_DOUBLES);
+    });
     if (rc) return rc;
     HostStage hs(ctx);
     hs.up(d_p1, p1xy, (size_t)m * 8);
@@ -1117,11 +1105,11 @@ static int pose_host(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m, 
     if (E_in) hs.up(d_E, E_in, 72);
     hs.flush_ups();
     rc = vis_build_sample_table(ctx, VIS_POSE_TABLE_M);           // (already there since vis_set_params / the first call: never rebuilt because M grew)
-    if (rc) return rc;
+    if (rc) return vis_drain(ctx, rc);
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[6], ctx->stream);
     rc = pose_run(ctx, 1, mcap, iters, d_p1, d_p2, d_npts, d_n1, d_n2, d_samples, d_models, d_counts, d_rstate,
                   E_in ? d_E : nullptr, d_mask, d_pose, do_ransac, do_pose, d_worklist, d_hyp);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[7], ctx->stream);
     const void* h_pose = hs.down(d_pose, sizeof(PoseOut));
     const void* h_mask = mask && m ? hs.down(d_mask, (size_t)m) : nullptr;
@@ -1165,27 +1153,32 @@ extern "C" int vis_f2f_ransac(vis_ctx* ctx, const vis_keypoint* pts1, const vis_
     if (m < 2 || iters == 0) return VIS_OK;                       // SPEC: M < 2 -> zero vector
     for (int i = 0; i < 2 * iters; i++) if (sample_idx[i] < 0 || sample_idx[i] >= m) return VIS_E_INVALID;
     (void)hipSetDevice(ctx->device);
-    int rc = ensure_scratch(ctx, (size_t)m * (2 * sizeof(vis_keypoint) + 24) + (size_t)iters * 24 + 8192);
+    float *d_p1, *d_p2, *d_rot; int32_t *d_idx, *d_n; vis_f2f_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>((size_t)m * 2); d_p2 = cv.take<float>((size_t)m * 2);
+        d_rot = cv.take<float>(9); d_idx = cv.take<int32_t>((size_t)iters * 2); d_n = cv.take<int32_t>(1);
+        d_out = cv.take<vis_f2f_result>(1);
+    });
     if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    vis_keypoint* d1 = cv.take<vis_keypoint>(m); vis_keypoint* d2 = cv.take<vis_keypoint>(m);
-    float* d_rot = cv.take<float>(9); int32_t* d_idx = cv.take<int32_t>((size_t)iters * 2);
-    double* d_nv = cv.take<double>((size_t)m * 3); float* d_cnt = cv.take<float>((size_t)iters * 4);
-    HIPCHK(ctx, hipMemcpy(d1, pts1, (size_t)m * sizeof(vis_keypoint), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(d2, pts2, (size_t)m * sizeof(vis_keypoint), hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(d_rot, rot, 36, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(d_idx, sample_idx, (size_t)iters * 8, hipMemcpyHostToDevice));
-    rc = f2f_run(ctx, d1, d2, m, d_rot, d_idx, iters, d_nv, d_cnt);
+    std::vector<float> xy((size_t)m * 4);
+    for (int i = 0; i < m; i++) { xy[2 * (size_t)i] = pts1[i].x; xy[2 * (size_t)i + 1] = pts1[i].y; xy[2 * ((size_t)m + i)] = pts2[i].x; xy[2 * ((size_t)m + i) + 1] = pts2[i].y; }
+    const int32_t n1 = m;
+    HostStage hs(ctx);
+    hs.up(d_p1, xy.data(), (size_t)m * 8);
+    hs.up(d_p2, xy.data() + (size_t)m * 2, (size_t)m * 8);
+    hs.up(d_rot, rot, 36);
+    hs.up(d_idx, sample_idx, (size_t)iters * 8);
+    hs.up(d_n, &n1, 4);
+    hs.flush_ups();
+    // one pair of k_f2f_batch with the indices as given and no reference translation: the record's t is (float)d of the winner -- `if (count >
+    // countMax)`, the first strictly larger count in iteration order (src/VISystem.cpp:737-741), degenerate samples never -- or zero
+    rc = f2f_batch_run(ctx, 1, m, d_p1, d_p2, d_n, d_rot, nullptr, d_idx, iters, true, d_out);
+    if (rc) return vis_drain(ctx, rc);
+    const vis_f2f_result* r = (const vis_f2f_result*)hs.down(d_out, sizeof(vis_f2f_result));
+    rc = hs.wait();
     if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<float> c((size_t)iters * 4);
-    HIPCHK(ctx, hipMemcpy(c.data(), d_cnt, c.size() * 4, hipMemcpyDeviceToHost));
-    // `if (count > countMax)`: first strictly larger count wins, iterations in order (src/VISystem.cpp:737-741)
-    float countMax = 0; float best[3] = {0, 0, 0};
-    for (int i = 0; i < iters; i++)
-        if (c[4 * (size_t)i] > countMax) { countMax = c[4 * (size_t)i]; best[0] = c[4 * (size_t)i + 1]; best[1] = c[4 * (size_t)i + 2]; best[2] = c[4 * (size_t)i + 3]; }
-    for (int k = 0; k < 3; k++) out_t[k] = scale * best[k];
-    if (count_max) *count_max = (int)countMax;
+    for (int k = 0; k < 3; k++) out_t[k] = scale * r->t[k];
+    if (count_max) *count_max = r->count_max;
     return VIS_OK;
 }
 
@@ -1485,16 +1478,15 @@ extern "C" int vis_triangulate(vis_ctx* ctx, const vis_tri_params* tp, const dou
     std::memset(summary, 0, sizeof(*summary));
     if (m == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
-    int rc = ensure_scratch(ctx, (size_t)m * (8 + 8 + 1 + sizeof(vis_map_point) + 1) + sizeof(PoseOut) + sizeof(vis_tri_summary) + 4096);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
-    uint8_t* d_mask = cv.take<uint8_t>(m);
-    PoseOut* d_pose = cv.take<PoseOut>(1);
-    vis_map_point* d_points = cv.take<vis_map_point>(m);
-    uint8_t* d_flags = cv.take<uint8_t>(((size_t)m + 3) & ~(size_t)3);
-    vis_tri_summary* d_summary = cv.take<vis_tri_summary>(1);
-    rc = vis_ensure_pin(ctx, (size_t)m * (8 + 8 + 1 + sizeof(vis_map_point) + 1) + sizeof(PoseOut) + sizeof(vis_tri_summary) + 4096);
+    float *d_p1, *d_p2; uint8_t *d_mask, *d_flags; PoseOut* d_pose; vis_map_point* d_points; vis_tri_summary* d_summary;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>((size_t)m * 2); d_p2 = cv.take<float>((size_t)m * 2);
+        d_mask = cv.take<uint8_t>(m);
+        d_pose = cv.take<PoseOut>(1);
+        d_points = cv.take<vis_map_point>(m);
+        d_flags = cv.take<uint8_t>(((size_t)m + 3) & ~(size_t)3);
+        d_summary = cv.take<vis_tri_summary>(1);
+    });
     if (rc) return rc;
     PoseOut o;
     std::memset(&o, 0, sizeof(o));
@@ -1508,7 +1500,7 @@ extern "C" int vis_triangulate(vis_ctx* ctx, const vis_tri_params* tp, const dou
     hs.flush_ups();
     // (a pair without a pose leaves its rows untouched: the caller's buffers are then not written either, summary.n_points == 0 below)
     rc = triangulate_run(ctx, tp, 1, m, m, d_pose, d_p1, d_p2, mask ? d_mask : nullptr, d_points, d_flags, d_summary);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     const void* h_sum = hs.down(d_summary, sizeof(vis_tri_summary));
     const void* h_pts = hs.down(d_points, (size_t)m * sizeof(vis_map_point));
     const void* h_fl = hs.down(d_flags, ((size_t)m + 3) & ~(size_t)3);
@@ -1550,7 +1542,7 @@ extern "C" int vis_f2f_batch(vis_ctx* ctx, int n, const float* d_p1, const float
     if (((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 3)) return VIS_E_INVALID;
     if (!ctx) return VIS_E_STATE;
     (void)hipSetDevice(ctx->device);
-    return f2f_batch_run(ctx, n, max_pts, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
+    return f2f_batch_run(ctx, n, max_pts, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, ctx->p.f2f_iters, false, d_out);
 }
 
 extern "C" int vis_filter_keypoints_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
@@ -1591,7 +1583,7 @@ template <class F> static int batch_epi(vis_ctx* ctx, int n, const char* who, F 
 extern "C" int vis_batch_f2f(vis_ctx* ctx, int n, const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
     if (!d_rot || !d_draws || !d_out || ((uintptr_t)d_out & 3)) return VIS_E_INVALID;
     return batch_epi(ctx, n, "vis_batch_f2f", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
-        return f2f_batch_run(ctx, n, pl->pose_mcap, O.p1, O.p2, d_npts, d_rot, d_tref, d_draws, d_out);
+        return f2f_batch_run(ctx, n, pl->pose_mcap, O.p1, O.p2, d_npts, d_rot, d_tref, d_draws, ctx->p.f2f_iters, false, d_out);
     });
 }
 
@@ -1612,14 +1604,12 @@ extern "C" int vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, cons
     if (m == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
     const size_t mk = ((size_t)m + 3) & ~(size_t)3;
-    const size_t need = (size_t)m * 16 + 2 * mk + 64 + 16 * 256 + 4096;
-    int rc = ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
-    float* d_rt = cv.take<float>(12); int32_t* d_cnt = cv.take<int32_t>(2);       // rot, t | m, count
-    uint8_t* d_keep = cv.take<uint8_t>(mk);
-    rc = vis_ensure_pin(ctx, need);
+    float *d_p1, *d_p2, *d_rt; int32_t* d_cnt; uint8_t* d_keep;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>((size_t)m * 2); d_p2 = cv.take<float>((size_t)m * 2);
+        d_rt = cv.take<float>(12); d_cnt = cv.take<int32_t>(2);                   // rot, t | m, count
+        d_keep = cv.take<uint8_t>(mk);
+    }, 2);                                                         // (d_cnt goes up and comes down)
     if (rc) return rc;
     std::vector<float> xy((size_t)m * 4);
     for (int i = 0; i < m; i++) { xy[2 * (size_t)i] = pts1[i].x; xy[2 * (size_t)i + 1] = pts1[i].y; xy[2 * ((size_t)m + i)] = pts2[i].x; xy[2 * ((size_t)m + i) + 1] = pts2[i].y; }
@@ -1632,7 +1622,7 @@ extern "C" int vis_filter_keypoints(vis_ctx* ctx, const vis_keypoint* pts1, cons
     hs.up(d_cnt, cnt, sizeof(cnt));
     hs.flush_ups();
     rc = epi_filter_run(ctx, 1, m, d_p1, d_p2, d_cnt, d_rt, d_rt + 9, threshold, (int)mk, d_keep, d_cnt + 1);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     const void* h_cnt = hs.down(d_cnt, sizeof(cnt));
     const void* h_keep = hs.down(d_keep, mk);
     rc = hs.wait();
@@ -1665,16 +1655,14 @@ extern "C" int vis_find_homography(vis_ctx* ctx, const vis_homography_params* hp
     if (m == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
     const size_t mk = ((size_t)m + 3) & ~(size_t)3, nd = (size_t)hp->iters * 4;
-    const size_t need = (size_t)m * 16 + mk + nd * 4 + 72 + sizeof(vis_homography_result) + 64 + 16 * 256 + 4096;
-    int rc = ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
-    int32_t* d_draws = cv.take<int32_t>(nd ? nd : 4); int32_t* d_n = cv.take<int32_t>(1);
-    double* d_E = cv.take<double>(9);
-    uint8_t* d_mask = cv.take<uint8_t>(mk);
-    vis_homography_result* d_out = cv.take<vis_homography_result>(1);
-    rc = vis_ensure_pin(ctx, need);
+    float *d_p1, *d_p2; int32_t *d_draws, *d_n; double* d_E; uint8_t* d_mask; vis_homography_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>((size_t)m * 2); d_p2 = cv.take<float>((size_t)m * 2);
+        d_draws = cv.take<int32_t>(nd ? nd : 4); d_n = cv.take<int32_t>(1);
+        d_E = cv.take<double>(9);
+        d_mask = cv.take<uint8_t>(mk);
+        d_out = cv.take<vis_homography_result>(1);
+    });
     if (rc) return rc;
     const int32_t n1 = m;
     HostStage hs(ctx);
@@ -1685,7 +1673,7 @@ extern "C" int vis_find_homography(vis_ctx* ctx, const vis_homography_params* hp
     if (E) hs.up(d_E, E, 72);
     hs.flush_ups();
     rc = homography_batch_run(ctx, hp, 1, m, d_p1, d_p2, d_n, d_draws, E ? d_E : nullptr, 9, (int)mk, d_mask, d_out);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     const void* h_out = hs.down(d_out, sizeof(vis_homography_result));
     const void* h_mask = hs.down(d_mask, mk);
     rc = hs.wait();
@@ -1741,17 +1729,15 @@ extern "C" int vis_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, con
     if (m == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
     const size_t mk = ((size_t)m + 3) & ~(size_t)3;
-    const size_t need = (size_t)m * 16 + mk + sizeof(vis_homography_result) + sizeof(vis_hpose_result) + 36 + 4 + 64 + 16 * 256 + 4096;
-    int rc = ensure_scratch(ctx, need);
-    if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    float* d_p1 = cv.take<float>((size_t)m * 2); float* d_p2 = cv.take<float>((size_t)m * 2);
-    int32_t* d_n = cv.take<int32_t>(1);
-    float* d_rot = cv.take<float>(9);
-    vis_homography_result* d_h = cv.take<vis_homography_result>(1);
-    uint8_t* d_mask = cv.take<uint8_t>(mk);
-    vis_hpose_result* d_out = cv.take<vis_hpose_result>(1);
-    rc = vis_ensure_pin(ctx, need);
+    float *d_p1, *d_p2, *d_rot; int32_t* d_n; vis_homography_result* d_h; uint8_t* d_mask; vis_hpose_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>((size_t)m * 2); d_p2 = cv.take<float>((size_t)m * 2);
+        d_n = cv.take<int32_t>(1);
+        d_rot = cv.take<float>(9);
+        d_h = cv.take<vis_homography_result>(1);
+        d_mask = cv.take<uint8_t>(mk);
+        d_out = cv.take<vis_hpose_result>(1);
+    });
     if (rc) return rc;
     const int32_t n1 = m;
     HostStage hs(ctx);
@@ -1763,7 +1749,7 @@ extern "C" int vis_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, con
     if (mask) hs.up(d_mask, mask, (size_t)m);
     hs.flush_ups();
     rc = hpose_run(ctx, hq, 1, m, d_h, d_p1, d_p2, d_n, (int)mk, mask ? d_mask : nullptr, rot_hint ? d_rot : nullptr, d_out);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (rc) return vis_drain(ctx, rc);
     const void* h_out = hs.down(d_out, sizeof(vis_hpose_result));
     rc = hs.wait();
     if (rc) return rc;

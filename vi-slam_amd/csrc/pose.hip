@@ -1612,48 +1612,10 @@ __global__ __launch_bounds__(64) void k_tri_summary(int row_cap, int in_stride, 
     }
 }
 
-// ---- F2FRansac (src/VISystem.cpp:612-769): lane per iteration, shared normal vectors
-__global__ __launch_bounds__(256) void k_f2f(const vis_keypoint* __restrict__ pts1, const vis_keypoint* __restrict__ pts2, int m,
-                                             float fx, float fy, float cx, float cy, const float* __restrict__ rot,
-                                             const int32_t* __restrict__ sample_idx, int iters, double threshold,
-                                             double* __restrict__ nv, float* __restrict__ counts) {
-    // phase 1 (grid-stride over points) is done by a first launch with iters == 0
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (iters == 0) {
-        if (gid >= m) return;
-        const float u1 = pts1[gid].x, v1 = pts1[gid].y, u2 = pts2[gid].x, v2 = pts2[gid].y;
-        double a[3] = {(double)((u1 - cx) / fx), (double)((v1 - cy) / fy), 1.0};
-        double b[3] = {(double)((u2 - cx) / fx), (double)((v2 - cy) / fy), 1.0};
-        const double na = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-        const double nb = sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
-        for (int k = 0; k < 3; k++) { a[k] /= na; b[k] /= nb; }
-        double Rm[9]; for (int i = 0; i < 9; i++) Rm[i] = (double)rot[i];
-        const double rb[3] = {(Rm[0] * b[0] + Rm[1] * b[1]) + Rm[2] * b[2], (Rm[3] * b[0] + Rm[4] * b[1]) + Rm[5] * b[2],
-                              (Rm[6] * b[0] + Rm[7] * b[1]) + Rm[8] * b[2]};
-        cross3(a, rb, nv + 3 * (size_t)gid);
-        return;
-    }
-    if (gid >= iters) return;
-    const int i1 = sample_idx[2 * gid], i2 = sample_idx[2 * gid + 1];
-    double d[3]; cross3(nv + 3 * (size_t)i1, nv + 3 * (size_t)i2, d);
-    float count = -1.f;                                            // -1: degenerate sample (skipped by the reference)
-    if (d[0] != 0.0 || d[1] != 0.0 || d[2] != 0.0) {
-        const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-        for (int k = 0; k < 3; k++) d[k] /= dn;
-        count = 0.f;
-        for (int i = 0; i < m; i++) {
-            const double error = -1000.0 / log10(fabs(dot3(d, nv + 3 * (size_t)i)));
-            if (error < threshold) count += 1.f;
-        }
-    }
-    counts[4 * (size_t)gid] = count;
-    counts[4 * (size_t)gid + 1] = (float)d[0]; counts[4 * (size_t)gid + 2] = (float)d[1]; counts[4 * (size_t)gid + 3] = (float)d[2];
-}
-
 // ---- the epipolar-plane test F2FRansac (src/VISystem.cpp:729-731) and FilterKeypoints (:596-598) share:
 //          -1000.0 / log10(fabs(x)) < threshold,      x = a unit direction . an epipolar-plane normal
-// decided by two compares wherever the outcome cannot depend on rounding, and by the expression itself (exactly as k_f2f writes it)
-// inside a band c_lo <= |x| <= c_hi around c = 10^(-1000 / threshold).  The result equals the full expression for EVERY x.
+// decided by two compares wherever the outcome cannot depend on rounding, and by the expression itself (as src/VISystem.cpp:729-731
+// and oracle/pose.cpp:585-586 write it: -1000.0 / log10(fabs(x)) < threshold, all in double) inside a band c_lo <= |x| <= c_hi around c = 10^(-1000 / threshold).  The result equals the full expression for EVERY x.
 //
 // For threshold T > 0, in exact arithmetic E(a) = -1000 / log10(a) rises from +0 (a -> 0) to +inf (a -> 1-) and is negative for a > 1, so
 // E(a) < T  <=>  a < c  or  a >= 1.  The special values of the expression as the libms compute it agree with that: a = 0 gives -1000 / -inf
@@ -1687,7 +1649,9 @@ DEV bool epi_inlier(double x, double threshold, double c_lo, double c_hi) {
     return -1000.0 / log10(ax) < threshold;
 }
 
-// the normal of correspondence i's epipolar plane: k_f2f's first phase, expression for expression (:651-668)
+// the normal of correspondence i's epipolar plane (src/VISystem.cpp:651-668, oracle/pose.cpp:565-573), expression for expression: the
+// pixels to float camera coordinates ((u - cx) / fx, (v - cy) / fy, 1), widened to double, both normalised by the square root of
+// (x x + y y) + z z, the second rotated by R with each row summed as (r0 b0 + r1 b1) + r2 b2, and n = a x (R b)
 struct EpiCam { float fx, fy, cx, cy; };
 DEV void epi_normal(const float* __restrict__ q1, const float* __restrict__ q2, int i, const EpiCam& K, const double (&Rm)[9], double* nv) {
     const float2 pa = reinterpret_cast<const float2*>(q1)[i], pb = reinterpret_cast<const float2*>(q2)[i];
@@ -1710,16 +1674,19 @@ DEV void epi_normal(const float* __restrict__ q1, const float* __restrict__ q2, 
 // 256 lanes x 4 iterations for rows of up to one tile (the good matches: thousands of small pairs share the chip with the detect chain),
 // 512 x 2 for longer rows (VIS_POSE_SYM: tens of pairs of thousands of points, where a second wave per SIMD hides the LDS and
 // branch latency of the first) -- DESIGN.md section 4.7 has both shapes measured both ways.
+// vis_f2f_ransac is one pair of the same kernel with DIRECT indices (the same choice of shape).
 #define F2F_TILE VIS_F2F_TILE          // 512 normals = 16 KiB of LDS (public: the tests size their rows around it)
 struct F2fArgs { EpiCam K; double threshold, c_lo, c_hi; int iters, in_stride; };
 struct alignas(32) EpiNv { double x, y, z, pad_; };
 
-// hypothesis of iteration j: d = normalize(n_i1 x n_i2) with i = (draw & 0x7fffffff) % (m - 1) (rand() % (sizeNewGroup - 1), :712-713);
+// hypothesis of iteration j: d = normalize(n_i1 x n_i2) with i = (draw & 0x7fffffff) % (m - 1) (rand() % (sizeNewGroup - 1), :712-713) -- or,
+// DIRECT, with i = the draw as it stands (vis_f2f_ransac's sample_idx, validated to [0, m): m - 1 included, which the modulo cannot give);
 // false: the cross product is zero and the iteration is skipped (:716)
+template <bool DIRECT>
 DEV bool f2f_hypothesis(const int32_t* __restrict__ draws, int j, int m, const EpiNv* s_nv, bool from_lds, const float* q1, const float* q2,
                         const EpiCam& K, const double (&Rm)[9], double* d) {
-    const int i1 = (int)((unsigned)(draws[2 * j] & 0x7fffffff) % (unsigned)(m - 1));
-    const int i2 = (int)((unsigned)(draws[2 * j + 1] & 0x7fffffff) % (unsigned)(m - 1));
+    const int i1 = DIRECT ? draws[2 * j] : (int)((unsigned)(draws[2 * j] & 0x7fffffff) % (unsigned)(m - 1));
+    const int i2 = DIRECT ? draws[2 * j + 1] : (int)((unsigned)(draws[2 * j + 1] & 0x7fffffff) % (unsigned)(m - 1));
     double n1[3], n2[3];
     if (from_lds) { n1[0] = s_nv[i1].x; n1[1] = s_nv[i1].y; n1[2] = s_nv[i1].z; n2[0] = s_nv[i2].x; n2[1] = s_nv[i2].y; n2[2] = s_nv[i2].z; }
     else { epi_normal(q1, q2, i1, K, Rm, n1); epi_normal(q1, q2, i2, K, Rm, n2); }
@@ -1743,14 +1710,16 @@ DEV void f2f_count_tile(const EpiNv* s_nv, int nt, const double (&d)[IPL][3], in
     }
 }
 
-// the count over one tile for the first `nslots` of a lane's IPL iterations (a uniform number: slots beyond it hold no iteration on any lane)
-template <int NS, int IPL>
+// the count over one tile for the first `nslots` of a lane's IPL iterations (a uniform number: slots beyond it hold no iteration on any lane).
+// DIRECT is not used here: it gives k_f2f_batch<.., true> a dispatch chain of its own, without which the compiler inlines the shared one in
+// another order and schedules the counting loop of the <.., false> kernels differently (same instructions, four scalar adds moved).
+template <int NS, int IPL, bool DIRECT>
 DEV void f2f_count_slots(int nslots, const EpiNv* s_nv, int nt, const double (&d)[IPL][3], int (&cnt)[IPL], const F2fArgs& A) {
-    if constexpr (NS < IPL) { if (nslots > NS) { f2f_count_slots<NS + 1, IPL>(nslots, s_nv, nt, d, cnt, A); return; } }
+    if constexpr (NS < IPL) { if (nslots > NS) { f2f_count_slots<NS + 1, IPL, DIRECT>(nslots, s_nv, nt, d, cnt, A); return; } }
     f2f_count_tile<NS, IPL>(s_nv, nt, d, cnt, A);
 }
 
-template <int NT, int IPL>
+template <int NT, int IPL, bool DIRECT = false>
 __global__ __launch_bounds__(NT) void k_f2f_batch(F2fArgs A, const float* __restrict__ p1, const float* __restrict__ p2,
                                                   const int32_t* __restrict__ npts, const float* __restrict__ rot,
                                                   const float* __restrict__ tref, const int32_t* __restrict__ draws,
@@ -1781,7 +1750,7 @@ __global__ __launch_bounds__(NT) void k_f2f_batch(F2fArgs A, const float* __rest
             const int j = j0 + s * NT + tid;
             cnt[s] = 0; d[s][0] = d[s][1] = d[s][2] = 0.0;
             live[s] = j < A.iters;
-            if (live[s]) { live[s] = f2f_hypothesis(draws, j, m, s_nv, single, q1, q2, A.K, Rm, d[s]); if (!live[s]) { ndeg++; d[s][0] = d[s][1] = d[s][2] = 0.0; } }
+            if (live[s]) { live[s] = f2f_hypothesis<DIRECT>(draws, j, m, s_nv, single, q1, q2, A.K, Rm, d[s]); if (!live[s]) { ndeg++; d[s][0] = d[s][1] = d[s][2] = 0.0; } }
         }
         const int nslots = min(IPL, (A.iters - j0 + NT - 1) / NT);      // slots that hold an iteration on any lane
         const bool wave_live = j0 + (tid & ~63) < A.iters;          // (wave-uniform) a wave whose lanes hold no iteration only keeps the barriers
@@ -1793,7 +1762,7 @@ __global__ __launch_bounds__(NT) void k_f2f_batch(F2fArgs A, const float* __rest
                 __syncthreads();
             }
             if (wave_live) {
-                f2f_count_slots<1, IPL>(nslots, s_nv, nt, d, cnt, A);
+                f2f_count_slots<1, IPL, DIRECT>(nslots, s_nv, nt, d, cnt, A);
             }
         }
 #pragma unroll
@@ -1816,7 +1785,7 @@ __global__ __launch_bounds__(NT) void k_f2f_batch(F2fArgs A, const float* __rest
     if (best != 0) {
         const int it = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
         double d[3];
-        (void)f2f_hypothesis(draws, it, m, s_nv, false, q1, q2, A.K, Rm, d);        // the same expression: the same bits as the lane that counted it
+        (void)f2f_hypothesis<DIRECT>(draws, it, m, s_nv, false, q1, q2, A.K, Rm, d);        // the same expression: the same bits as the lane that counted it
         float scale = 1.0f, g[3] = {0.f, 0.f, 0.f};
         if (tref) { for (int k = 0; k < 3; k++) g[k] = tref[3 * (size_t)pair + k]; scale = sqrtf((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]); }   // :639-642
         float t[3] = {scale * (float)d[0], scale * (float)d[1], scale * (float)d[2]};
@@ -2175,19 +2144,6 @@ int triangulate_run(vis_ctx* ctx, const vis_tri_params* tp, int npairs, int in_s
     return VIS_OK;
 }
 
-int f2f_run(vis_ctx* ctx, const vis_keypoint* d_pts1, const vis_keypoint* d_pts2, int m, const float* d_rot,
-            const int32_t* d_idx, int iters, double* d_nv, float* d_counts) {
-    hipStream_t st = ctx->stream;
-    const float fx = (float)ctx->p.fx, fy = (float)ctx->p.fy, cx = (float)ctx->p.cx, cy = (float)ctx->p.cy;
-    hipLaunchKernelGGL(k_f2f, dim3((m + 255) / 256), dim3(256), 0, st, d_pts1, d_pts2, m, fx, fy, cx, cy, d_rot, d_idx, 0,
-                       ctx->p.f2f_threshold, d_nv, d_counts);
-    if (iters > 0)
-        hipLaunchKernelGGL(k_f2f, dim3((iters + 255) / 256), dim3(256), 0, st, d_pts1, d_pts2, m, fx, fy, cx, cy, d_rot, d_idx, iters,
-                           ctx->p.f2f_threshold, d_nv, d_counts);
-    HIPCHK(ctx, hipGetLastError());
-    return VIS_OK;
-}
-
 static F2fArgs epi_args(const vis_ctx* ctx, double threshold, int iters, int in_stride) {
     F2fArgs A;
     A.K = {(float)ctx->p.fx, (float)ctx->p.fy, (float)ctx->p.cx, (float)ctx->p.cy};
@@ -2198,13 +2154,19 @@ static F2fArgs epi_args(const vis_ctx* ctx, double threshold, int iters, int in_
 }
 
 // d_p1 / d_p2: npairs rows of in_stride (x, y) points, d_npts of them valid (clamped to in_stride); d_rot: npairs x 9; d_tref: npairs x 3 or
-// null; d_draws: f2f_iters x 2; d_out: npairs records.  On ctx->stream.
+// null; d_draws: iters x 2 (direct: point indices in [0, m), see f2f_hypothesis); d_out: npairs records.  On ctx->stream.
+template <bool DIRECT>
+static void f2f_launch(vis_ctx* ctx, const F2fArgs& A, int npairs, const float* d_p1, const float* d_p2, const int32_t* d_npts,
+                       const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
+    if (A.in_stride > F2F_TILE) hipLaunchKernelGGL((k_f2f_batch<512, 2, DIRECT>), dim3(npairs), dim3(512), 0, ctx->stream, A, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
+    else hipLaunchKernelGGL((k_f2f_batch<256, 4, DIRECT>), dim3(npairs), dim3(256), 0, ctx->stream, A, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
+}
 int f2f_batch_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
-                  const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
+                  const float* d_rot, const float* d_tref, const int32_t* d_draws, int iters, bool direct, vis_f2f_result* d_out) {
     if (npairs <= 0) return VIS_OK;
-    const F2fArgs A = epi_args(ctx, ctx->p.f2f_threshold, ctx->p.f2f_iters, in_stride);
-    if (in_stride > F2F_TILE) hipLaunchKernelGGL((k_f2f_batch<512, 2>), dim3(npairs), dim3(512), 0, ctx->stream, A, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
-    else hipLaunchKernelGGL((k_f2f_batch<256, 4>), dim3(npairs), dim3(256), 0, ctx->stream, A, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
+    const F2fArgs A = epi_args(ctx, ctx->p.f2f_threshold, iters, in_stride);
+    if (direct) f2f_launch<true>(ctx, A, npairs, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
+    else f2f_launch<false>(ctx, A, npairs, d_p1, d_p2, d_npts, d_rot, d_tref, d_draws, d_out);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

@@ -173,17 +173,14 @@ extern "C" int vis_rectify_host(vis_rectify* r, const uint8_t* img, int in_strid
     }
     (void)hipSetDevice(ctx->device);
     const size_t in_bytes = (size_t)r->in_w * r->in_h, out_bytes = (size_t)r->out_w * r->out_h;
-    int rc = vis_ensure_scratch(ctx, in_bytes + out_bytes + 1024);
-    if (!rc) rc = vis_ensure_pin(ctx, in_bytes + out_bytes + 4096);
+    uint8_t *d_in, *d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) { d_in = cv.take<uint8_t>(in_bytes); d_out = cv.take<uint8_t>(out_bytes); });
     if (rc) return rc;
-    Carver cv{(char*)ctx->d_scratch, 0};
-    uint8_t* d_in = cv.take<uint8_t>(in_bytes);
-    uint8_t* d_out = cv.take<uint8_t>(out_bytes);
     HostStage hs(ctx);
     hs.up2d(d_in, r->in_w, img, in_stride, r->in_w, r->in_h);
     hs.flush_ups();
     rc = launch_remap(r, ctx->stream, d_in, r->in_w, 1, 0, 0, r->out_w, r->out_h, d_out, r->out_w);
-    if (rc) return rc;
+    if (rc) return vis_drain(ctx, rc);
     const uint8_t* got = (const uint8_t*)hs.down(d_out, out_bytes);
     rc = hs.wait();
     if (rc) return rc;

@@ -243,10 +243,21 @@ extern std::atomic<unsigned long long> vis_g_launches;
          if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
                                  return VIS_E_HIP; } } while (0)
 
-// carve typed, 256-byte aligned pieces out of the context scratch block
+// Carve typed, 256-byte aligned pieces out of the context scratch block.  With a null base the carver MEASURES: it hands out nullptr and
+// only advances `off`, through the same offsets a bound carver walks.  A take that would end beyond `limit` sets `overflow` and hands out
+// nullptr, and so does every take after it (HostStage::overflow's twin: vis_carve refuses the call before anything is queued).
 struct Carver {
-    char* base; size_t off;
-    template <class T> T* take(size_t count) { off = (off + 255) & ~(size_t)255; T* p = (T*)(base + off); off += count * sizeof(T); return p; }
+    char* base; size_t off; size_t limit;
+    int n = 0; bool overflow = false;
+    template <class T> T* take(size_t count) {
+        const size_t at = (off + 255) & ~(size_t)255, bytes = count * sizeof(T);
+        if (overflow || at > limit || bytes > limit - at) { overflow = true; return nullptr; }
+        off = at + bytes; n++;
+        return base ? (T*)(base + at) : nullptr;
+    }
+    // What a HostStage needs to pass every carved buffer through the pinned block once per direction, `ways` directions: a stage take is
+    // 64-byte aligned and at least 4 bytes long, so the 256 bytes per buffer cover a buffer staged in up to three pieces.
+    size_t pin_bound(int ways) const { return (size_t)ways * (off + (size_t)n * 256); }
 };
 int vis_ensure_scratch(vis_ctx* ctx, size_t bytes);
 
@@ -350,6 +361,23 @@ struct HostStage {
     }
 };
 
+// The buffers of one host-pointer call, declared ONCE: layout(Carver&) assigns the call's d_* pointers.  It runs twice -- measuring, which
+// sizes the scratch block and, from the same list, the pinned block (Carver::pin_bound; ways = 2 where a buffer is staged up AND down or in
+// many pieces), then bound to ctx->d_scratch.  Both blocks have their final size when this returns: build the HostStage after it.
+template <class Layout> int vis_carve(vis_ctx* ctx, Layout&& layout, int ways = 1) {
+    Carver measure{nullptr, 0, SIZE_MAX};
+    layout(measure);
+    int rc = vis_ensure_scratch(ctx, measure.off);
+    if (!rc) rc = vis_ensure_pin(ctx, measure.pin_bound(ways));
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_scratch, 0, ctx->scratch_bytes};
+    layout(cv);
+    if (cv.overflow) { ctx->err = "device scratch block too small (internal)"; return VIS_E_NOMEM; }
+    return VIS_OK;
+}
+// a launch failed behind queued uploads: drain the stream (they read the pinned block, which the next call may refill), then report
+inline int vis_drain(vis_ctx* ctx, int rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+
 
 // ---- host-side geometry / tables (geometry.cpp) ----
 int  vis_compute_levels(const vis_params& p, int w, int h, int stride0, LevelInfo* lv, int fs_nch = VIS_FS_NCH);
@@ -409,11 +437,10 @@ int triangulate_run(vis_ctx* ctx, const vis_tri_params* tp, int npairs, int in_s
                     const float* d_p1, const float* d_p2, const uint8_t* d_mask, vis_map_point* d_points, uint8_t* d_flags,
                     vis_tri_summary* d_summary);
 int  vis_build_sample_table(vis_ctx* ctx, int max_m);
-int f2f_run(vis_ctx* ctx, const vis_keypoint* d_pts1, const vis_keypoint* d_pts2, int m, const float* d_rot,
-            const int32_t* d_idx, int iters, double* d_nv, float* d_counts);
-// pose.hip: k_f2f_batch / k_epi_filter on ctx->stream over npairs rows of in_stride (x, y) points (d_npts valid, clamped); d_keep: rows of row_cap >= in_stride
+// pose.hip: k_f2f_batch / k_epi_filter on ctx->stream over npairs rows of in_stride (x, y) points (d_npts valid, clamped); d_keep: rows of row_cap >= in_stride.
+// d_draws: iters x 2 words -- point indices in [0, m) as they stand with `direct`, else raw draws reduced modulo m - 1
 int f2f_batch_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
-                  const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out);
+                  const float* d_rot, const float* d_tref, const int32_t* d_draws, int iters, bool direct, vis_f2f_result* d_out);
 int epi_filter_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
                    const float* d_rot, const float* d_t, double threshold, int row_cap, uint8_t* d_keep, int32_t* d_nkeep);
 // homography.hip: k_homography_batch on ctx->stream over npairs rows of in_stride (x, y) points; hp validated by the caller; d_E: records of e_stride

@@ -3,6 +3,8 @@
 //   2. vis_ensure_pin() asked to grow (= free + re-allocate) the block while a HostStage is alive -> VIS_E_STATE, block untouched
 //   3. ReaderGuard (the batch path's buffer sets): which reader events a writer would wait for, and align_reader(): which alignment a
 //      write of caller memory waits for
+//   4. Carver / the one buffer list of a host-pointer call (vis_carve): the measuring and the binding pass walk the same offsets, a take
+//      beyond the block is refused, and the pinned bound derived from the list holds a stage that passes every buffer up and down
 // (round 5's host SIGSEGV, gpurun_out/r5r_gdb.log: a stage that kept the address of a block a later vis_ensure_pin had freed; see
 // csrc/vis_internal.h at HostStage).  Compiled by `make -C vi-slam_amd/csrc selftest` with hipcc as host code against the library;
 // tests/test_abi.py runs it.  Prints one line per check and exits non-zero on the first failure.
@@ -70,6 +72,36 @@ int main() {
         CHECK(align_reader(&a, frames[0], frames[1]) == e1);                  // one it did not read while an older one is pending
         CHECK(align_reader(&a, frames[1], frames[3]) == e2);                  // overlapping both: the latest stands for the older
         CHECK(align_reader(&a, nullptr, nullptr) == e2);
+    }
+    {
+        // one buffer list, as an entry point writes it (odd sizes: every take pays its alignment); d[2] goes up and comes down
+        const size_t sizes[4] = {1000, 7, 300, 4097};
+        void* d[4];
+        auto layout = [&](Carver& cv) { for (int i = 0; i < 4; i++) d[i] = cv.take<char>(sizes[i]); };
+        Carver measure{nullptr, 0, SIZE_MAX};
+        layout(measure);
+        CHECK(!measure.overflow && measure.n == 4 && !d[0] && !d[3]);          // measuring hands out no address
+        CHECK(measure.off == 1792 + 4097);                                    // 0, 1024, 1280, 1792: 256-byte aligned offsets
+        std::vector<char> dev(measure.off + 1);
+        Carver bound{dev.data(), 0, measure.off};                             // bound at exactly the measured size
+        layout(bound);
+        CHECK(!bound.overflow && bound.off == measure.off);                   // the measured size is what a bound pass consumes
+        CHECK(d[0] == dev.data() && d[1] == dev.data() + 1024 && d[2] == dev.data() + 1280 && d[3] == dev.data() + 1792);   // identical offsets
+        Carver tight{dev.data(), 0, measure.off - 1};                         // one byte short: the last take ends beyond the block
+        layout(tight);
+        CHECK(tight.overflow && d[2] == dev.data() + 1280 && d[3] == nullptr && tight.off == 1280 + 300);
+        CHECK(tight.take<char>(1) == nullptr && tight.off == 1280 + 300);     // nothing is handed out after an overflow
+        // the pinned bound of the list, two ways: a stage that uploads and downloads every buffer once fits
+        std::vector<char> pin(measure.pin_bound(2)), src(4097);
+        vis_ctx p;
+        p.h_pin = pin.data(); p.h_pin_bytes = pin.size(); p.h_pin_dev = nullptr;
+        {
+            HostStage hs(&p);
+            for (int i = 0; i < 4; i++) CHECK(hs.take(sizes[i]) != nullptr);                              // (up(): take + memcpy + a queued copy)
+            for (int i = 0; i < 4; i++) CHECK(hs.take(std::max(sizes[i], (size_t)4)) != nullptr);         // (down(): take + a queued copy)
+            CHECK(!hs.overflow && hs.off <= pin.size());
+        }
+        p.h_pin = nullptr; p.h_pin_bytes = 0;
     }
     std::printf(fails ? "stage_selftest FAILED (%d)\n" : "stage_selftest passed\n", fails);
     return fails ? 1 : 0;
