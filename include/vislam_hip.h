@@ -705,6 +705,113 @@ int  vis_homography_pose_batch(vis_ctx* ctx, const vis_hpose_params* hq, int n, 
 int  vis_batch_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, int n, const vis_homography_result* d_h, int row_cap,
                                const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out);
 
+/* ---- PnP: the pose of a frame against map points, P3P RANSAC and Gauss-Newton refinement (Grunert 1841 as restated by Haralick, Lee,
+ * Ottenberg, Noelle: "Review and analysis of solutions of the three point perspective pose estimation problem", 1994; the reference has
+ * none).  A pose is (R, t) with x_cam = R X + t, X in the map's frame and units -- for the rows of vis_triangulate / vis_batch_triangulate,
+ * the first camera of the pair in units of its baseline -- so t, unlike every two-view result above, has a scale.
+ * Coordinates: the pose stage's, x = ((double)u - cx) * (1 / fx), y = ((double)v - cy) * (1 / fx) with the single focal the map points live in;
+ * thr2 = (threshold_px * (1 / fx))^2 once on the host.  All arithmetic is double, nothing is contracted, the only operations are + - * / sqrt;
+ * dot3(a, b) = a0 b0 + a1 b1 + a2 b2 and every sum of a 3 x 3 product run left to right (tests/pnp_ref.py restates every step in this order, bit
+ * for bit).
+ * Sample j of pp.iters takes i_k = (d_draws[3 j + k] & 0x7fffffff) % m, k = 0 ... 2 (ONE table of iters x 3 draws serves every problem).
+ * Minimal solver.  Bearings f_k = (x / n, y / n, 1 / n), n = sqrt((x x + y y) + 1); world points P_k; p01 = P1 - P0, p02 = P2 - P0, p12 = P2 - P1;
+ *   c2 = |p01|^2, b2 = |p02|^2, a2 = |p12|^2; ca = f1 . f2, cb = f0 . f2, cg = f0 . f1; p = (a2 - c2) / b2, q = (a2 + c2) / b2;
+ *   A4 = (p - 1)^2 - 4 (c2 / b2) ca^2
+ *   A3 = 4 [p (1 - p) cb - (1 - q) ca cg + 2 (c2 / b2) ca^2 cb]
+ *   A2 = 2 [p^2 - 1 + 2 p^2 cb^2 + 2 ((b2 - c2) / b2) ca^2 - 4 q ca cb cg + 2 ((b2 - a2) / b2) cg^2]
+ *   A1 = 4 [-p (1 + p) cb + 2 (a2 / b2) cg^2 cb - (1 - q) ca cg]
+ *   A0 = (1 + p)^2 - 4 (a2 / b2) cg^2
+ * (each bracket summed left to right, each product left to right).  Real roots v of A0 + ... + A4 v^4 in (0, B), B = 1 + max_k |A_k / A4|, by
+ * derivative interlacing: the roots of the third, second and first derivative, found in turn, cut (0, B) into intervals with at most one
+ * root each; an interval whose end values differ in sign (f < 0 against f >= 0) is halved, 40 times for a derivative and 100 times for the
+ * quartic, an interval whose midpoint is not strictly inside staying as it is; the root is the last midpoint.  Ascending, at most four; the
+ * root's place r is its slot.  For a root: den = 2 (cg - v ca); u = ((((p - 1) v^2 - 2 p cb v) + 1) + p) / den; w = (1 + v^2) - 2 v cb;
+ * s0 = sqrt(b2 / w), s1 = u s0, s2 = v s0, Q_k = s_k f_k.  Rotation from two orthonormal triads: e1 = p01 / |p01|, e3 = (p01 x p02) / |p01 x p02|,
+ * e2 = e3 x e1, g1, g2, g3 the same from Q1 - Q0 and Q2 - Q0; R_ij = (g1_i e1_j + g2_i e2_j) + g3_i e3_j; t = Q0 - R P0.
+ * A sample is skipped and counted in n_degenerate when two of its indices are equal, when b2 is zero, when a coefficient is not finite or A4 is
+ * zero, when |p01 x p02|^2 <= 2^-40 |p01|^2 |p02|^2, when B is not finite, or when no root yields a pose.  A root is dropped (its slot stays
+ * empty) when den is zero or not finite, when v, u or w is not > 0, or when the camera triad fails the same collinearity test.  n_solutions
+ * counts the poses of all samples.
+ * Per-point test, division-free: (U, V, W) = R X + t (each row ((R_i0 X0 + R_i1 X1) + R_i2 X2) + t_i); an inlier iff W > 0 and
+ * (U - x W)^2 + (V - y W)^2 <= thr2 (W W); a NaN fails.  Hypothesis h = 4 j + r: the largest count > 0 wins, ties go to the smallest h.  mask
+ * receives the winner's inlier bytes (zeros when nothing won); bytes beyond the problem's points are left untouched.
+ * Refinement: when refine_iters > 0 and n_inliers >= min_inliers, refine_iters Gauss-Newton steps over the winner's inliers (the set is
+ * fixed).  Per point, with (U, V, W) under the current pose: iw = 1 / W, un = U / W, vn = V / W, residual (un - x, vn - y), j02 = -(un iw),
+ * j12 = -(vn iw), Jacobian rows (rotation, then translation; the update is applied on the camera side)
+ *   J0 = (j02 V, iw W - j02 U, -(iw V), iw, 0, j02),   J1 = (j12 V - iw W, -(j12 U), iw U, 0, iw, j12).
+ * The 21 sums of J0_a J0_b + J1_a J1_b (a <= b), the 6 of J0_a rx + J1_a ry and the cost rx^2 + ry^2 are each taken in ONE fixed order (64 partial
+ * sums over i mod 64 in rising i, a point outside the set adding 0, then the tree v = v + v[lane ^ off], off = 32 ... 1), without floating-point
+ * atomics.  The step d = -(J^T J)^-1 J^T r by LDL^T without pivoting (D_j = A_jj - sum_c (L_jc L_jc) D_c, L_ij = (A_ij - sum_c (L_ic L_jc) D_c) / D_j,
+ * c rising; z_i = -g_i - sum_c L_ic z_c; d_i = z_i / D_i - sum_{c > i} L_ci d_c, c rising); a pivot that is not > 0 or not finite ends the
+ * refinement.  Update with the Cayley map: h = d_0..2 / 2, hh = h . h, s = 2 / (1 + hh), C_ij = delta_ij + s ([h]x_ij + (h_i h_j - delta_ij hh)),
+ * R <- C R, t <- C t + d_3..5.  cost0 / cost1: the cost over the set under the winner and under the last pose reached (equal when no
+ * refinement ran).  The refined pose is reported with VIS_PNP_REFINED iff cost1 is finite, cost1 <= cost0 and no pivot failed; otherwise the
+ * winner with VIS_PNP_REFINE_REJECTED.  VIS_PNP_FEW: a winner below min_inliers, reported unrefined.  n_inliers_refined: the per-point test
+ * under the reported pose over all points.  m < 4 or iters == 0: a zero record with best_iter = -1 (mask bytes of the problem zero).
+ * Two runs are byte-identical. */
+enum { VIS_PNP_REFINED = 1, VIS_PNP_REFINE_REJECTED = 2, VIS_PNP_FEW = 4 };
+enum { VIS_PNP_TILE = 512 };             /* points per LDS tile of the kernel: rows longer than this are walked in several tiles */
+typedef struct vis_pnp_params {          /* 24 bytes; the defaults are this library's own */
+    int32_t iters;                       /* 200    three-point samples per problem (at most 2^29) */
+    int32_t min_inliers;                 /* 8      below it the winner is not refined; refused below 4 */
+    double  threshold_px;                /* 2.0    vis_default_tri_params' reprojection bound */
+    int32_t refine_iters;                /* 5      Gauss-Newton steps; 0 = none */
+    int32_t reserved_;
+} vis_pnp_params;
+typedef struct vis_pnp_result {          /* 240 bytes */
+    double  R[9], t[3];                  /* the reported pose: x_cam = R X + t */
+    double  R_ransac[9], t_ransac[3];    /* the winning P3P pose, always; zeros when nothing won */
+    double  cost0, cost1;                /* sum of squared residuals (normalised coordinates) over the mask, before and after */
+    int32_t n_inliers, n_points;
+    int32_t best_iter, best_root;        /* the winning sample (-1: none) and its root's place */
+    int32_t n_degenerate, n_solutions;
+    int32_t n_inliers_refined;
+    int32_t flags;                       /* VIS_PNP_* */
+} vis_pnp_result;
+void vis_default_pnp_params(vis_pnp_params* pp);
+/* One problem, HOST pointers; blocks once like the other single-frame entry points.  X: m x 3 doubles; xy: m x 2 floats (pixels); draws:
+ * pp.iters x 3; mask: m bytes or NULL. */
+int  vis_pnp_ransac(vis_ctx* ctx, const vis_pnp_params* pp, const double* X, const float* xy, int m, const int32_t* draws, uint8_t* mask,
+                    vis_pnp_result* out);
+/* DEVICE pointers, asynchronous on the context's stream.  d_X: n rows of max_pts points, x_stride doubles from one point to the next (>= 3; 4
+ * reads a row of vis_map_point in place); d_xy: n rows of max_pts (x, y) float pixels; d_npts[i] of them valid (clamped to max_pts); d_mask: n
+ * rows of row_cap bytes or NULL; d_out: n records.
+ * Refusals of these two calls, in this order.  VIS_E_INVALID: a NULL pointer (the mask may be NULL), on the device-pointer call a misaligned one
+ * (8 bytes for d_X, d_xy and records, 4 for d_npts and d_draws), a negative size, x_stride < 3, pp.iters < 0 or > 2^29, pp.min_inliers < 4,
+ * pp.refine_iters < 0, a threshold_px that is not finite and positive.  Then VIS_E_STATE without a context.  Then, vis_pnp_batch only,
+ * VIS_E_CAPACITY when a mask is given and row_cap < max_pts. */
+int  vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, const double* d_X, int x_stride, const float* d_xy, const int32_t* d_npts,
+                   int max_pts, const int32_t* d_draws, int row_cap, uint8_t* d_mask, vis_pnp_result* d_out);
+
+/* The same for every frame of the last vis_batch_run (which must have included VIS_STAGE_MATCH and VIS_STAGE_POSE; n = its frames) against the map
+ * points vis_batch_triangulate wrote for that run: d_points / d_flags are its rows of row_cap entries.  For frame i, with q its keyframe
+ * (vis_batch_get_keyframes) and p the keyframe of q: correspondence c of pair (q -> i) is linked to the FIRST correspondence k of pair (p -> q)
+ * whose keypoint in frame q is the same (vis_dmatch.trainIdx of k == vis_dmatch.queryIdx of c, the lists the pose stage saw) and whose flags
+ * contain every bit of `require` (VIS_MP_KEPT is the usual choice; 0 links every triangulated row).  The problem is X = d_points[q][k].X against
+ * c's pixel in frame i, in rising c, solved like a row of vis_pnp_batch with the same d_draws for every frame: d_out[i] is the pose of frame i in
+ * the frame of p, in units of the baseline p -> q; d_mask (rows of mask_cap bytes, or NULL) receives the inlier bytes of the n_linked rows.
+ * d_link[i] always carries n_linked and q and p as vis_batch_get_keyframes numbers them (VIS_KF_* where there is none; p = q when q is no frame
+ * of this launch), and where d_out[i] has a winner the motion q -> i in the same units: R_rel = R R_pq^T ((R_i0 Rpq_j0 + R_i1 Rpq_j1) + R_i2 Rpq_j2),
+ * t_rel = t - R_rel t_pq, scale = sqrt(dot3(t_rel, t_rel)) -- this pair's baseline in units of the previous one -- with (R_pq, t_pq) the pose
+ * record of pair q; zeros otherwise.  There is no problem (n_linked = 0, d_out[i] the zero record) when the frame has no pair, when q's pair has
+ * no pose (R all zero), or when q lies in an earlier launch (frame 0, and whatever else the gate carries): the last case sets VIS_PNPL_NO_MAP --
+ * joining across launches needs the carried pair's match list, which the plan does not keep.  Asynchronous on the POSE stream behind
+ * vis_batch_triangulate of the same run, overlapping the next vis_batch_run like it; the caller's buffers are in use until vis_batch_sync.  The
+ * workspace (a keypoint table and the linked rows per frame) is allocated by the first call of a plan.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_pnp_batch refuses of pp, a NULL d_draws / d_points / d_flags / d_out / d_link, d_points not
+ * 16-byte or records not 8-byte aligned, a negative size, require outside 0 ... 255.  VIS_E_CAPACITY: row_cap, or with a mask mask_cap, below
+ * the plan's correspondences per pair.  VIS_E_STATE: no context / plan / match stage / pose stage, or n differs. */
+enum { VIS_PNPL_NO_MAP = 1 };
+typedef struct vis_pnp_link {            /* 120 bytes */
+    double  R_rel[9], t_rel[3];          /* frame q -> frame i: x_i = R_rel x_q + t_rel */
+    double  scale;                       /* |t_rel|: the baseline q -> i in units of the baseline p -> q */
+    int32_t n_linked;
+    int32_t q, p;                        /* frame indices of this launch, or VIS_KF_* */
+    int32_t flags;                       /* VIS_PNPL_* */
+} vis_pnp_link;
+int  vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d_draws, const vis_map_point* d_points, const uint8_t* d_flags,
+                   int row_cap, int require, int mask_cap, uint8_t* d_mask, vis_pnp_result* d_out, vis_pnp_link* d_link);
+
 /* ---- rotation-guided matching ("search by projection"): the 2-NN search of the matcher restricted to a window around the position the
  * pair's rotation predicts -- VISystem::WarpFunctionRT (src/VISystem.cpp:771-860; its call sites :500-504 are commented out in the reference)
  * put in front of the matcher.  rot: row-major 3x3 f32, the matrix vis_batch_f2f takes (current-frame rays -> previous frame, :1031-1033).

@@ -26,6 +26,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              hint, default parameters, the draws of --models): one row per pair -- frame index, timestamp, kind (none / rotation / plane), flags
              (VIS_HPF_*), solution, second, n_points, n_tested, n_parallax, n_good (four), d1, d2, d3, t_norm, then R (nine, row-major), t (in
              units of the plane distance), n of the chosen candidate and R, t, n of the second; the JSON line carries the count of each kind.
+  --pnp out.csv: the pose of every frame against the map points of its keyframe's own pair (vis_batch_triangulate, then vis_batch_pnp with
+             VIS_MP_KEPT, default parameters, 200 x 3 draws of default_rng(7)): one row per frame -- frame index, timestamp, q, p, n_linked,
+             link flags (VIS_PNPL_*), scale, then n_inliers, n_inliers_refined, best_iter, best_root, flags (VIS_PNP_*), cost0, cost1, R (nine,
+             row-major), t (units of the baseline p -> q), R_rel, t_rel; the JSON line carries the counts.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -84,6 +88,7 @@ def main():
     ap.add_argument("--points", default=None, metavar="CSV", help="write the triangulated map points of every pair here")
     ap.add_argument("--models", default=None, metavar="CSV", help="write the H-or-E model choice of every pair here")
     ap.add_argument("--hposes", default=None, metavar="CSV", help="write the pose of every pair's homography (chosen and second candidate) here")
+    ap.add_argument("--pnp", default=None, metavar="CSV", help="write every frame's pose against its keyframe's map points here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -138,13 +143,19 @@ def main():
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
         ctx.set_align_weights(aw)
-    if a.points:
+    if a.points or a.pnp:
         row_cap = int(np.floor(np.sqrt(p.n_cells))) ** 2      # the grid-filtered good matches of a pair
         d_mp = torch.empty(B * row_cap * vislam.MAP_POINT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         d_mf = torch.empty(B * row_cap, dtype=torch.uint8, device="cuda")
         d_ms = torch.empty(B * vislam.TRI_SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         point_rows, tri_totals = [], np.zeros(3, np.int64)
+    if a.pnp:
+        pp = vislam.default_pnp_params()
+        d_pdraws = torch.from_numpy(np.random.default_rng(7).integers(0, 2 ** 31, (pp.iters, 3)).astype(np.int32)).cuda()
+        d_prec = torch.empty(B * vislam.PNP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_plink = torch.empty(B * vislam.PNP_LINK_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        pnp_rows, pnp_totals = [], dict(linked=0, posed=0, refined=0, no_map=0)
     if a.models or a.hposes:                                  # one homography RANSAC per batch serves both (the mask does not change the records)
         hp = vislam.default_homography_params()
         d_hdraws = torch.from_numpy(np.random.default_rng(7).integers(0, 2 ** 31, (hp.iters, 4)).astype(np.int32)).cuda()
@@ -190,8 +201,10 @@ def main():
         ctx.batch_run(d, nb, stages)
         if a.track:
             ctx.batch_track(tap, d, nb, 0, d_align.data_ptr(), d_track.data_ptr())
-        if a.points:
+        if a.points or a.pnp:
             ctx.batch_triangulate(nb, row_cap, d_mp.data_ptr(), d_mf.data_ptr(), d_ms.data_ptr())
+        if a.pnp:
+            ctx.batch_pnp(nb, d_pdraws.data_ptr(), d_mp.data_ptr(), d_mf.data_ptr(), row_cap, d_prec.data_ptr(), d_plink.data_ptr(), vislam.MP_KEPT, 0, 0, pp)
         if a.models or a.hposes:
             ctx.batch_homography(nb, d_hdraws.data_ptr(), hcap, d_hmask.data_ptr() if a.hposes else 0, d_hrec.data_ptr(), hp)
         if a.hposes:
@@ -211,6 +224,14 @@ def main():
                 tri_totals += (int(ms[i]["n_points"]), int(ms[i]["n_front"]), int(ms[i]["n_kept"]))
                 point_rows += [(first + i, stamps[first + i], j, *mp[i, j]["X"], mp[i, j]["reproj_px"], mp[i, j]["parallax_px"], int(mf[i, j]))
                                for j in range(int(ms[i]["n_points"]))]
+        if a.pnp:
+            prec, plink = d_prec.cpu().numpy().view(vislam.PNP_RESULT_DTYPE), d_plink.cpu().numpy().view(vislam.PNP_LINK_DTYPE)
+            for i in range(nb):
+                pnp_totals["linked"] += int(plink[i]["n_linked"] >= 4)
+                pnp_totals["posed"] += int(prec[i]["best_iter"] >= 0)
+                pnp_totals["refined"] += int(bool(prec[i]["flags"] & vislam.PNP_REFINED))
+                pnp_totals["no_map"] += int(bool(plink[i]["flags"] & vislam.PNPL_NO_MAP))
+                pnp_rows.append((first + i, stamps[first + i], prec[i].copy(), plink[i].copy()))
         if a.models:
             hrec = d_hrec.cpu().numpy().view(vislam.HOMOGRAPHY_RESULT_DTYPE)
             for i in range(nb):
@@ -275,6 +296,16 @@ def main():
                 f.write("%d,%d,%d,%.17g,%.17g,%.17g,%.9g,%.9g,%d\n" % r)
         out["points_csv"] = a.points
         out["map_points"] = {"triangulated": int(tri_totals[0]), "front": int(tri_totals[1]), "kept": int(tri_totals[2])}
+    if a.pnp:
+        with open(a.pnp, "w") as f:
+            for fi, ts, r, l in pnp_rows:
+                ints = [l["q"], l["p"], l["n_linked"], l["flags"]]
+                ints2 = [r[k] for k in ("n_inliers", "n_inliers_refined", "best_iter", "best_root", "flags")]
+                dbl = [r["cost0"], r["cost1"]] + list(r["R"]) + list(r["t"]) + list(l["R_rel"]) + list(l["t_rel"])
+                f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + ",%.17g," % l["scale"] + ",".join("%d" % v for v in ints2) + "," +
+                        ",".join("%.17g" % v for v in dbl) + "\n")
+        out["pnp_csv"] = a.pnp
+        out["pnp"] = pnp_totals
     if a.models:
         with open(a.models, "w") as f:
             for fi, ts, r in model_rows:

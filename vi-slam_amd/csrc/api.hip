@@ -250,7 +250,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1776,6 +1776,108 @@ extern "C" int vis_batch_homography_pose(vis_ctx* ctx, const vis_hpose_params* h
     return batch_epi(ctx, n, "vis_batch_homography_pose", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
         return hpose_run(ctx, hq, n, pl->pose_mcap, d_h, O.p1, O.p2, d_npts, row_cap, d_mask, d_rot, d_out);
     });
+}
+
+// ---- PnP: pnp.hip k_pnp_batch + k_pnp_refine
+extern "C" void vis_default_pnp_params(vis_pnp_params* pp) {
+    if (!pp) return;
+    pp->iters = 200; pp->min_inliers = 8; pp->threshold_px = 2.0; pp->refine_iters = 5; pp->reserved_ = 0;
+}
+
+static bool pnp_params_ok(const vis_pnp_params* pp) {
+    return pp && pp->iters >= 0 && pp->iters <= (1 << 29) && pp->min_inliers >= 4 && pp->refine_iters >= 0 &&
+           std::isfinite(pp->threshold_px) && pp->threshold_px > 0.0;
+}
+
+extern "C" int vis_pnp_ransac(vis_ctx* ctx, const vis_pnp_params* pp, const double* X, const float* xy, int m, const int32_t* draws,
+                              uint8_t* mask, vis_pnp_result* out) {
+    if (!out || m < 0 || (m && (!X || !xy)) || !pnp_params_ok(pp) || (m && pp->iters && !draws)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    std::memset(out, 0, sizeof(*out)); out->best_iter = -1;
+    if (m == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const size_t mk = ((size_t)m + 3) & ~(size_t)3, nd = (size_t)pp->iters * 3;
+    double* d_X; float* d_xy; int32_t *d_draws, *d_n; uint8_t* d_mask; vis_pnp_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_X = cv.take<double>((size_t)m * 3); d_xy = cv.take<float>((size_t)m * 2);
+        d_draws = cv.take<int32_t>(nd ? nd : 3); d_n = cv.take<int32_t>(1);
+        d_mask = cv.take<uint8_t>(mk);
+        d_out = cv.take<vis_pnp_result>(1);
+    });
+    if (rc) return rc;
+    const int32_t n1 = m;
+    HostStage hs(ctx);
+    hs.up(d_X, X, (size_t)m * 24);
+    hs.up(d_xy, xy, (size_t)m * 8);
+    if (nd) hs.up(d_draws, draws, nd * 4);
+    hs.up(d_n, &n1, 4);
+    hs.flush_ups();
+    rc = pnp_batch_run(ctx, pp, 1, m, d_X, 3, d_xy, d_n, d_draws, (int)mk, d_mask, d_out);
+    if (rc) return vis_drain(ctx, rc);
+    const void* h_out = hs.down(d_out, sizeof(vis_pnp_result));
+    const void* h_mask = hs.down(d_mask, mk);
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out, h_out, sizeof(*out));
+    if (mask) std::memcpy(mask, h_mask, (size_t)m);
+    return VIS_OK;
+}
+
+extern "C" int vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, const double* d_X, int x_stride, const float* d_xy,
+                             const int32_t* d_npts, int max_pts, const int32_t* d_draws, int row_cap, uint8_t* d_mask, vis_pnp_result* d_out) {
+    if (n < 0 || max_pts < 0 || row_cap < 0 || x_stride < 3 || !d_npts || !d_draws || !d_out || (max_pts && (!d_X || !d_xy)) || !pnp_params_ok(pp)) return VIS_E_INVALID;
+    if (((uintptr_t)d_X & 7) || ((uintptr_t)d_xy & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_npts & 3) || ((uintptr_t)d_draws & 3)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (d_mask && row_cap < max_pts) { ctx->err = "vis_pnp_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return pnp_batch_run(ctx, pp, n, max_pts, d_X, x_stride, d_xy, d_npts, d_draws, row_cap, d_mask, d_out);
+}
+
+static int ensure_pnp(vis_ctx* ctx, Plan* pl) {
+    if (pl->d_pnp_tab && pl->d_pnp_X && pl->d_pnp_xy && pl->d_pnp_n) return VIS_OK;
+    auto drop = [&]() {                                            // all four or none: a failed call leaves nothing behind for the next one to overwrite
+        (void)hipFree(pl->d_pnp_tab); (void)hipFree(pl->d_pnp_X); (void)hipFree(pl->d_pnp_xy); (void)hipFree(pl->d_pnp_n);
+        pl->d_pnp_tab = nullptr; pl->d_pnp_X = nullptr; pl->d_pnp_xy = nullptr; pl->d_pnp_n = nullptr;
+    };
+    drop();
+    const bool ok = hipMalloc((void**)&pl->d_pnp_tab, (size_t)pl->npairs * pl->kcap * sizeof(int32_t)) == hipSuccess &&
+                    hipMalloc((void**)&pl->d_pnp_X, (size_t)pl->npairs * pl->pose_mcap * 3 * sizeof(double)) == hipSuccess &&
+                    hipMalloc((void**)&pl->d_pnp_xy, (size_t)pl->npairs * pl->pose_mcap * 2 * sizeof(float)) == hipSuccess &&
+                    hipMalloc((void**)&pl->d_pnp_n, (size_t)pl->npairs * sizeof(int32_t)) == hipSuccess;
+    if (!ok) { drop(); (void)hipGetLastError(); ctx->err = "vis_batch_pnp: out of device memory for the plan's workspace"; return VIS_E_NOMEM; }
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d_draws, const vis_map_point* d_points,
+                             const uint8_t* d_flags, int row_cap, int require, int mask_cap, uint8_t* d_mask, vis_pnp_result* d_out,
+                             vis_pnp_link* d_link) {
+    if (n < 0 || row_cap < 0 || mask_cap < 0 || require < 0 || require > 255 || !d_draws || !d_points || !d_flags || !d_out || !d_link ||
+        !pnp_params_ok(pp)) return VIS_E_INVALID;
+    if (((uintptr_t)d_points & 15) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_link & 7) || ((uintptr_t)d_draws & 3)) return VIS_E_INVALID;
+    if (ctx && ctx->batch && row_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_pnp: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    if (ctx && ctx->batch && d_mask && mask_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_pnp: mask_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    if (!(ctx->batch->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_pnp: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    {
+        Plan* pl = ctx->batch;
+        if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;    // (before the workspace is allocated)
+        (void)hipSetDevice(ctx->device);
+        const int rc = ensure_pnp(ctx, pl);
+        if (rc) return rc;
+    }
+    // on the pose stream (batch_epi queues there) behind the pose stage that wrote the pose records and behind vis_batch_triangulate of the same
+    // run, which wrote d_points / d_flags on that stream; the link table is read there too: the next gate kernel of the record set waits for it
+    const int rc = batch_epi(ctx, n, "vis_batch_pnp", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        const bool sym = ctx->p.pose_input == VIS_POSE_SYM;
+        Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
+        return pnp_link_run(ctx, pp, n, pl->kf_min ? rs.kf_link : nullptr, pl->pair0_valid ? 1 : 0, pl->pose_mcap, sym ? pl->kcap : pl->root * pl->root,
+                            pl->kcap, sym ? O.sym : O.good, d_npts, O.p2, pl->d_pose, d_points, d_flags, row_cap, require, pl->d_pnp_tab, pl->d_pnp_X,
+                            pl->d_pnp_xy, pl->d_pnp_n, d_draws, mask_cap, d_mask, d_out, d_link);
+    });
+    if (rc) return rc;
+    Plan* pl = ctx->batch;
+    if (pl->kf_min) pl->rec[pl->last_base / pl->rec_per_set].links.note(ctx->pose_stream, ctx->ev_epi_done[pl->mo_cur]);
+    return VIS_OK;
 }
 
 extern "C" int vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redone) {

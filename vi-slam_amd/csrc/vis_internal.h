@@ -106,6 +106,9 @@ struct Plan {
     // guided matching (match.hip k_warp): npairs x kcap predictions + 16 floats (the rotation of a single-frame call); allocated by the
     // first guided call of the plan (ensure_warp), so a context that never asks for a window has the footprint it always had
     float2* d_warp = nullptr;
+    // vis_batch_pnp (pnp.hip k_pnp_link), allocated by the first call of the plan (ensure_pnp): per frame the keypoint table of its keyframe's
+    // pair (npairs x kcap), the linked rows (npairs x pose_mcap map points and pixels) and their counts
+    int32_t* d_pnp_tab = nullptr; double* d_pnp_X = nullptr; float* d_pnp_xy = nullptr; int32_t* d_pnp_n = nullptr;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -452,6 +455,15 @@ int homography_batch_run(vis_ctx* ctx, const vis_homography_params* hp, int npai
 // floats, or null
 int hpose_run(vis_ctx* ctx, const vis_hpose_params* hq, int npairs, int in_stride, const vis_homography_result* d_h, const float* d_p1,
               const float* d_p2, const int32_t* d_npts, int row_cap, const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out);
+// pnp.hip: k_pnp_batch + k_pnp_refine on ctx->stream over n rows of in_stride points (d_X: x_stride doubles apart; d_xy: pixels); pp validated by the
+// caller; d_mask: rows of row_cap >= in_stride bytes, or null
+int pnp_batch_run(vis_ctx* ctx, const vis_pnp_params* pp, int n, int in_stride, const double* d_X, int x_stride, const float* d_xy,
+                  const int32_t* d_npts, const int32_t* d_draws, int row_cap, uint8_t* d_mask, vis_pnp_result* d_out);
+// k_pnp_link + pnp_batch_run + k_pnp_rel on ctx->stream: vis_batch_pnp's body (api.hip has the arguments' origin)
+int pnp_link_run(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d_links, int pair0_valid, int mcap, int mstride, int kcap,
+                 const vis_dmatch* d_matches, const int32_t* d_npts, const float* d_p2, const PoseOut* d_pose, const vis_map_point* d_points,
+                 const uint8_t* d_flags, int row_cap, int require, int32_t* d_table, double* d_X, float* d_xy, int32_t* d_cnt,
+                 const int32_t* d_draws, int mask_cap, uint8_t* d_mask, vis_pnp_result* d_out, vis_pnp_link* d_link);
 #define VIS_RSTATE_WORDS 16
 
 #endif

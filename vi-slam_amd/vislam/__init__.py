@@ -11,6 +11,7 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.f2f_batch / batch_f2f                       <-> the same for every pair of a batch
   Context.find_homography / homography_batch / batch_homography   homography RANSAC and the H-or-E model choice (beyond the reference)
   Context.homography_pose / homography_pose_batch / batch_homography_pose   (R, t / d, n) of a pair's homography, both survivors of the vote
+  Context.pnp_ransac / pnp_batch / batch_pnp   the pose of a frame against map points: P3P RANSAC + Gauss-Newton refinement (beyond the reference)
   Context.filter_keypoints (_batch, batch_...)        <-> VISystem::FilterKeypoints  (src/VISystem.cpp:542-610)
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises.
@@ -183,6 +184,38 @@ HPF_AMBIGUOUS, HPF_HINTED, HPF_FEW, HPF_LOW_PARALLAX = 1, 2, 4, 8
 HP_KIND_NAMES = ("none", "rotation", "plane")
 
 
+class PnpParams(C.Structure):
+    """vis_pnp_params: the knobs of the P3P RANSAC and its refinement (vis_default_pnp_params: 200, 8, 2.0, 5)"""
+    _fields_ = [("iters", C.c_int32), ("min_inliers", C.c_int32), ("threshold_px", C.c_double), ("refine_iters", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class PnpResult(C.Structure):
+    """vis_pnp_result: the reported pose (x_cam = R X + t), the winning P3P pose, the refinement's costs and the counts of one problem"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("R_ransac", C.c_double * 9), ("t_ransac", C.c_double * 3), ("cost0", C.c_double),
+                ("cost1", C.c_double), ("n_inliers", C.c_int32), ("n_points", C.c_int32), ("best_iter", C.c_int32), ("best_root", C.c_int32),
+                ("n_degenerate", C.c_int32), ("n_solutions", C.c_int32), ("n_inliers_refined", C.c_int32), ("flags", C.c_int32)]
+
+
+PNP_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("R_ransac", "<f8", (9,)), ("t_ransac", "<f8", (3,)), ("cost0", "<f8"),
+                             ("cost1", "<f8"), ("n_inliers", "<i4"), ("n_points", "<i4"), ("best_iter", "<i4"), ("best_root", "<i4"),
+                             ("n_degenerate", "<i4"), ("n_solutions", "<i4"), ("n_inliers_refined", "<i4"), ("flags", "<i4")])
+assert C.sizeof(PnpParams) == 24 and PNP_RESULT_DTYPE.itemsize == C.sizeof(PnpResult) == 240
+
+
+class PnpLink(C.Structure):
+    """vis_pnp_link: what vis_batch_pnp joined for one frame and the relative motion keyframe -> frame in units of the keyframe's own baseline"""
+    _fields_ = [("R_rel", C.c_double * 9), ("t_rel", C.c_double * 3), ("scale", C.c_double), ("n_linked", C.c_int32), ("q", C.c_int32),
+                ("p", C.c_int32), ("flags", C.c_int32)]
+
+
+PNP_LINK_DTYPE = np.dtype([("R_rel", "<f8", (9,)), ("t_rel", "<f8", (3,)), ("scale", "<f8"), ("n_linked", "<i4"), ("q", "<i4"), ("p", "<i4"),
+                           ("flags", "<i4")])
+assert PNP_LINK_DTYPE.itemsize == C.sizeof(PnpLink) == 120
+PNPL_NO_MAP = 1
+PNP_TILE = 512                                    # VIS_PNP_TILE: points per LDS tile of the PnP kernel
+PNP_REFINED, PNP_REFINE_REJECTED, PNP_FEW = 1, 2, 4
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -224,6 +257,7 @@ ABI_SYMBOLS = [
     "vis_f2f_batch", "vis_batch_f2f", "vis_filter_keypoints_batch", "vis_batch_filter_keypoints", "vis_filter_keypoints",
     "vis_default_homography_params", "vis_find_homography", "vis_homography_batch", "vis_batch_homography",
     "vis_default_hpose_params", "vis_homography_pose", "vis_homography_pose_batch", "vis_batch_homography_pose",
+    "vis_default_pnp_params", "vis_pnp_ransac", "vis_pnp_batch", "vis_batch_pnp",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
@@ -306,6 +340,13 @@ def _load():
         lib.vis_find_homography.argtypes = [vp, hpp, vp, vp, ci, vp, vp, vp, vp]
         lib.vis_homography_batch.argtypes = [vp, hpp, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp]
         lib.vis_batch_homography.argtypes = [vp, hpp, ci, vp, ci, vp, vp]
+    if hasattr(lib, "vis_pnp_batch"):                   # (absent from older A/B builds)
+        ppp = C.POINTER(PnpParams)
+        lib.vis_default_pnp_params.argtypes = [ppp]
+        lib.vis_default_pnp_params.restype = None
+        lib.vis_pnp_ransac.argtypes = [vp, ppp, vp, vp, ci, vp, vp, vp]
+        lib.vis_pnp_batch.argtypes = [vp, ppp, ci, vp, ci, vp, vp, ci, vp, ci, vp, vp]
+        lib.vis_batch_pnp.argtypes = [vp, ppp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp]
     if hasattr(lib, "vis_batch_homography_pose"):       # (absent from older A/B builds)
         hqp = C.POINTER(HposeParams)
         lib.vis_default_hpose_params.argtypes = [hqp]
@@ -423,6 +464,12 @@ def default_homography_params():
     hp = HomographyParams()
     lib.vis_default_homography_params(C.byref(hp))
     return hp
+
+
+def default_pnp_params():
+    pp = PnpParams()
+    lib.vis_default_pnp_params(C.byref(pp))
+    return pp
 
 
 def default_hpose_params():
@@ -1025,6 +1072,38 @@ class Context:
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_homography_pose(self._h, C.byref(hq), n, v(d_h_ptr), row_cap, v(d_mask_ptr), v(d_rot_ptr), v(d_out_ptr)),
                   "vis_batch_homography_pose")
+
+    # -- PnP: the pose of a frame against map points ---------------------------------------------------------------
+    def pnp_ransac(self, X, xy, draws, pp=None):
+        """(record, mask uint8[m]) of one problem: X m x 3 double map points, xy m x 2 float pixels, draws iters x 3 int32; the record is one
+        PNP_RESULT_DTYPE element"""
+        pp = default_pnp_params() if pp is None else pp
+        X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+        assert len(X) == len(xy)
+        draws = np.ascontiguousarray(draws, np.int32).reshape(-1)
+        assert len(draws) >= 3 * pp.iters
+        mask = np.zeros(max(len(X), 1), np.uint8)
+        out = np.zeros(1, PNP_RESULT_DTYPE)
+        self._chk(lib.vis_pnp_ransac(self._h, C.byref(pp), _ptr(X), _ptr(xy), len(X), _ptr(draws), _ptr(mask), _ptr(out)), "vis_pnp_ransac")
+        return out[0], mask[:len(X)]
+
+    def pnp_batch(self, n, d_X_ptr, x_stride, d_xy_ptr, d_npts_ptr, max_pts, d_draws_ptr, row_cap, d_mask_ptr, d_out_ptr, pp=None):
+        """queue the PnP of n rows of max_pts map points (x_stride doubles apart) and pixels on the context's stream (raw DEVICE pointers; 0 /
+        None = NULL for d_mask): n PnpResult records, n rows of row_cap mask bytes"""
+        pp = default_pnp_params() if pp is None else pp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_pnp_batch(self._h, C.byref(pp), n, v(d_X_ptr), x_stride, v(d_xy_ptr), v(d_npts_ptr), max_pts, v(d_draws_ptr), row_cap,
+                                    v(d_mask_ptr), v(d_out_ptr)), "vis_pnp_batch")
+
+    def batch_pnp(self, n, d_draws_ptr, d_points_ptr, d_flags_ptr, row_cap, d_out_ptr, d_link_ptr, require=16, mask_cap=0, d_mask_ptr=0, pp=None):
+        """every frame of the last batch_run(STAGE_ALL) against the map points batch_triangulate wrote for it (d_points / d_flags rows of
+        row_cap), on the pose stream behind that call: n PnpResult and n PnpLink records; require = the flag bits a map point must have
+        (16 = MP_KEPT); the buffers are in use until batch_sync()"""
+        pp = default_pnp_params() if pp is None else pp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_pnp(self._h, C.byref(pp), n, v(d_draws_ptr), v(d_points_ptr), v(d_flags_ptr), row_cap, require, mask_cap,
+                                    v(d_mask_ptr), v(d_out_ptr), v(d_link_ptr)), "vis_batch_pnp")
 
     # -- batched stream path ----------------------------------------------------------------------------------
     def batch_plan(self, w, h, stride, max_frames):
