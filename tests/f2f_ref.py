@@ -7,7 +7,7 @@ double, sqrt((a0^2 + a1^2) + a2^2), rows of R summed left to right, cross produc
 (x x' + y y') + z z'.  numpy's element-wise double arithmetic is IEEE without fused multiply-adds, so these are the same operations.
 
 The inlier test is the full expression -1000 / log10(|x|) < threshold here (`inlier_full`); `inlier_banded` restates the device helper's two
-compares + band (csrc/pose.hip epi_inlier / epi_band) so that the reasoning behind it can be checked on the CPU."""
+compares + band (csrc/epipolar.hip epi_inlier / epi_band) so that the reasoning behind it can be checked on the CPU."""
 import math
 import struct
 
@@ -66,6 +66,25 @@ def batch_cases(tile):
     return out
 
 
+def edge_rows(tile):
+    """the two rows of the iteration-count and tie tests, one per workgroup shape of the kernel: 40 correspondences and one more than a tile"""
+    return [pair_inputs(40, 211, 0.1, 1.5), pair_inputs(tile + 1, 212, 0.1, 1.5)]
+
+
+TIE_ITERS = 1100                                                   # a second round of either workgroup shape (1024 iterations per round)
+TIE_FIRSTS = (0, 70, 300, 1030)                                    # the first live iteration: lane 0, a second wave, a second slot, the second round
+TIE_PAIR, TIE_SKIP = (3, 17), 5                                    # below 39: the same reduced indices for both rows
+
+
+def tie_draws(first, iters=TIE_ITERS):
+    """every iteration draws TIE_PAIR, so every live count is equal; the first `first` draw (TIE_SKIP, TIE_SKIP), whose cross product
+    n x n is exactly zero (a b - b a of the same two doubles), so they are skipped"""
+    d = np.empty((iters, 2), np.int32)
+    d[:] = TIE_PAIR
+    d[:first] = TIE_SKIP
+    return d
+
+
 # ---------------------------------------------------------------------------------------------- the predicate
 def inlier_full(x, thr):
     """-1000.0 / log10(fabs(x)) < threshold, element-wise (x = 0: -1000 / -inf = +0; |x| = 1: -1000 / +0 = -inf; NaN: False)"""
@@ -74,7 +93,7 @@ def inlier_full(x, thr):
 
 
 def band(thr):
-    """(c_lo, c_hi) of csrc/pose.hip epi_band; (0, inf) = the full expression for every x"""
+    """(c_lo, c_hi) of csrc/epipolar.hip epi_band; (0, inf) = the full expression for every x"""
     if not (thr > 0.0) or not math.isfinite(thr):
         return 0.0, math.inf
     c = math.pow(10.0, -1000.0 / thr)

@@ -159,6 +159,69 @@ def test_device_rows_against_single_call_oracle_and_restatement(vislam, orc, syn
     single.close()
 
 
+class _EdgeRows:
+    """fr.edge_rows, each a one-pair batch of its own row length (40: the workgroup shape of short rows; F2F_TILE + 1: the other one)"""
+    def __init__(self, vislam, torch):
+        self.pairs = fr.edge_rows(vislam.F2F_TILE)
+        assert [len(a) for a, _, _, _ in self.pairs] == [40, vislam.F2F_TILE + 1]
+        self.dev = [(_dev(torch, a), _dev(torch, b), _dev(torch, np.array([len(a)], np.int32)), _dev(torch, rot), _dev(torch, t))
+                    for a, b, rot, t in self.pairs]
+
+    def run(self, vislam, torch, c, k, draws):
+        d_p1, d_p2, d_n, d_rot, d_tref = self.dev[k]
+        d_draws, out = _dev(torch, draws), _filled(torch, 2 * 32)
+        c.f2f_batch(1, d_p1.data_ptr(), d_p2.data_ptr(), d_n.data_ptr(), len(self.pairs[k][0]), d_rot.data_ptr(), d_tref.data_ptr(),
+                    d_draws.data_ptr(), out.data_ptr())
+        c.batch_sync()
+        raw = out.cpu().numpy()
+        assert (raw[32:] == FILL).all()
+        return raw[:32].view(vislam.F2F_RESULT_DTYPE)[0]
+
+
+def test_iteration_counts_at_slot_and_round_edges(vislam, orc):
+    """iteration counts at the edges of a lane's slots, a wave, a workgroup and a round (256 x 4 and 512 x 2 lanes x slots: 1024 iterations
+    per round): one lane, one wave, one more; one slot of the short shape, one more; inside the third slot; one round, one more; inside
+    the second round's second slot"""
+    import torch
+    p = _params(vislam)
+    c = vislam.Context(0, p)
+    rows = _EdgeRows(vislam, torch)
+    for iters in (1, 64, 65, 256, 257, 600, 1024, 1025, 1300):
+        p.f2f_iters = iters
+        c.set_params(p)
+        draws = _draws(900 + iters, iters)
+        for k, (a, b, rot, t) in enumerate(rows.pairs):
+            rec = rows.run(vislam, torch, c, k, draws)
+            _check_record(vislam, orc, c, p, rec, a, b, rot, draws, t, (iters, len(a)))
+            assert int(rec["best_iter"]) >= 0, (iters, len(a))
+    c.close()
+
+
+def test_tie_goes_to_the_first_live_iteration(vislam):
+    """every live iteration has the same count: the winner is the first of them, wherever it sits -- lane 0, a second wave, a later slot
+    of a lane, the second round (tests/test_f2f_batch_ref.py checks the inputs against the restatement on the CPU)"""
+    import torch
+    p = _params(vislam)
+    c = vislam.Context(0, p)
+    rows = _EdgeRows(vislam, torch)
+    for k, (a, b, rot, t) in enumerate(rows.pairs):
+        p.f2f_iters = 1
+        c.set_params(p)
+        alone = rows.run(vislam, torch, c, k, fr.tie_draws(0, 1))
+        assert int(alone["best_iter"]) == 0 and int(alone["count_max"]) > 0
+        assert fr.record_tuple(alone) == fr.record_tuple(fr.f2f(p, a, b, rot, fr.tie_draws(0, 1), t))
+        p.f2f_iters = fr.TIE_ITERS
+        c.set_params(p)
+        for first in fr.TIE_FIRSTS:
+            draws = fr.tie_draws(first)
+            rec = rows.run(vislam, torch, c, k, draws)
+            where = (len(a), first)
+            assert int(rec["best_iter"]) == first and int(rec["n_degenerate"]) == first, (where, rec)
+            assert int(rec["count_max"]) == int(alone["count_max"]), (where, rec, alone)
+            assert fr.record_tuple(rec) == fr.record_tuple(fr.f2f(p, a, b, rot, draws, t)), where
+    c.close()
+
+
 def test_counts_at_the_boundary_of_the_predicate(vislam, orc):
     """thresholds set exactly ON the error of a correspondence (and its two neighbours), where the band of the device helper is entered:
     count and winner must be the oracle's"""

@@ -1,6 +1,6 @@
 """CPU: tests/f2f_ref.py -- the numpy restatement of F2FRansac / FilterKeypoints that the GPU tests compare the batched kernels with --
 against the oracle (orc.f2f_ransac), against a second restatement in plain Python floats, and the reasoning behind the device's
-two-compare form of the inlier test (csrc/pose.hip epi_inlier) against the full expression.  Tolerance: the project's own for F2FRansac
+two-compare form of the inlier test (csrc/epipolar.hip epi_inlier) against the full expression.  Tolerance: the project's own for F2FRansac
 (tests/test_pose_gpu.py): equal count_max, |dt| <= 1e-6."""
 import numpy as np
 import pytest
@@ -49,6 +49,23 @@ def test_zero_records(vislam):
     a, b, rot, t = fr.pair_inputs(40, 3, 0.0, 0.1)
     assert fr.record_tuple(fr.f2f(p, a, b, rot, draws[:0], iters=0)) == zero
     assert zero[3] == -1
+
+
+def test_tie_inputs_give_the_first_live_iteration(vislam):
+    """the inputs of tests/test_f2f_batch_gpu.py test_tie_goes_to_the_first_live_iteration: under the restatement the (c, c) draws are
+    skipped, every other iteration has the count of the hypothesis run alone, which is > 0, and the winner is the first of them"""
+    p = vislam.default_params()
+    p.fy = p.fx
+    for a, b, rot, t in fr.edge_rows(vislam.F2F_TILE):
+        idx = fr.reduce_draws(fr.tie_draws(1), len(a))
+        assert tuple(idx[1]) == fr.TIE_PAIR and tuple(idx[0]) == (fr.TIE_SKIP, fr.TIE_SKIP)
+        alone = fr.f2f(p, a, b, rot, fr.tie_draws(0, 1), t, iters=1)
+        assert alone["best_iter"] == 0 and alone["n_degenerate"] == 0 and 0 < alone["count_max"] < len(a)
+        for first in fr.TIE_FIRSTS:
+            rec, (d, cnt, deg, nv) = fr.f2f(p, a, b, rot, fr.tie_draws(first), t, iters=fr.TIE_ITERS, detail=True)
+            assert deg[:first].all() and not deg[first:].any() and (cnt[first:] == alone["count_max"]).all()
+            assert (rec["best_iter"], rec["n_degenerate"], rec["count_max"]) == (first, first, alone["count_max"])
+            assert rec["t"].tobytes() == alone["t"].tobytes() and rec["flipped"] == alone["flipped"]
 
 
 def test_filter_two_ways(vislam):

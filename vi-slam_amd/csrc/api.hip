@@ -1,6 +1,6 @@
 // api.hip -- the C ABI of libvislam_hip.so (include/vislam_hip.h): context, plans, single-frame
 // entry points (one per OpenCV-CUDA call site of the reference) and the batched stream path.
-// Host code only; kernels live in detect.hip / match.hip / pose.hip.
+// Host code only; kernels live in detect.hip / match.hip / pose.hip / epipolar.hip / homography.hip / pnp.hip.
 #include "vis_internal.h"
 #include <algorithm>
 #include <cfloat>
@@ -1535,7 +1535,7 @@ extern "C" int vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int
     return VIS_OK;
 }
 
-// ---- F2FRansac / FilterKeypoints for the pairs of a batch: pose.hip k_f2f_batch, k_epi_filter
+// ---- F2FRansac / FilterKeypoints for the pairs of a batch: epipolar.hip k_f2f_batch, k_epi_filter
 extern "C" int vis_f2f_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
                              const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
     if (n < 0 || max_pts < 0 || !d_npts || !d_rot || !d_draws || !d_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;

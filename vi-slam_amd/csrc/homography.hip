@@ -6,19 +6,18 @@
 // restated operation for operation in tests/homography_ref.py; this file must keep every product and sum parenthesised as written
 // there (the library is built with -ffp-contract=off).
 //
-// k_homography_batch has k_f2f_batch's shape: one workgroup per pair, the hypotheses spread over the lanes (IPL per lane), the
-// correspondences walked in LDS tiles of VIS_H_TILE normalised (x1, y1, x2, y2) -- every lane reads the same point, a broadcast -- and
-// the winner taken as the maximum of the integer key (count << 32 | ~iteration) over the workgroup, which does not depend on the order
-// it is taken in.  A lane holds H and adj(H) of its hypotheses in registers, 18 doubles per slot; the solver is a closed form whose
+// k_homography_batch has the shape of ransac_lanes.h: one workgroup per pair, the hypotheses spread over the lanes (IPL per lane), the
+// correspondences walked in LDS tiles of VIS_H_TILE normalised (x1, y1, x2, y2), the winner the maximum key over the workgroup (a slot
+// is an iteration).  A lane holds H and adj(H) of its hypotheses in registers, 18 doubles per slot; the solver is a closed form whose
 // every index is a constant (pose.hip's comment on jacobi_eig has the reason: a run-time index puts the matrices into scratch memory).
 // The first wave then recomputes the winner from its draws -- the same expressions, so the same bits as the lane that counted it -- and
 // computes mask, scores and the decision; the sums run over 64 partial sums (i mod 64, rising i) and a fixed butterfly, whatever <NT, IPL>
 // the launch has, so the record does not depend on the shape.
 #include "vis_internal.h"
+#include "ransac_lanes.h"
 #include <cmath>
 #include <cfloat>
 
-#define DEV __device__ __forceinline__
 #define H_TILE VIS_H_TILE              // 512 points = 16 KiB of LDS (public: the tests size their rows around it)
 
 struct HArgs {
@@ -29,12 +28,6 @@ struct HArgs {
 };
 struct alignas(32) HPt { double x1, y1, x2, y2; };
 
-DEV double h_dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-DEV void h_cross3(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
 DEV bool h_bad(double v) { return !(v != 0.0) || !(fabs(v) <= DBL_MAX); }      // zero, NaN or infinite
 
 DEV HPt h_point(const float* __restrict__ q1, const float* __restrict__ q2, int i, const HArgs& A) {
@@ -49,7 +42,7 @@ DEV HPt h_point(const float* __restrict__ q1, const float* __restrict__ q2, int 
 DEV void h_adj(const double (&M)[9], double (&G)[9]) {
     const double c0[3] = {M[0], M[3], M[6]}, c1[3] = {M[1], M[4], M[7]}, c2[3] = {M[2], M[5], M[8]};
     double r0[3], r1[3], r2[3];
-    h_cross3(c1, c2, r0); h_cross3(c2, c0, r1); h_cross3(c0, c1, r2);
+    cross3(c1, c2, r0); cross3(c2, c0, r1); cross3(c0, c1, r2);
     G[0] = r0[0]; G[1] = r0[1]; G[2] = r0[2]; G[3] = r1[0]; G[4] = r1[1]; G[5] = r1[2]; G[6] = r2[0]; G[7] = r2[1]; G[8] = r2[2];
 }
 
@@ -57,8 +50,8 @@ DEV void h_adj(const double (&M)[9], double (&G)[9]) {
 DEV bool h_basis(const double (&x)[4], const double (&y)[4], double (&M)[9]) {
     const double p0[3] = {x[0], y[0], 1.0}, p1[3] = {x[1], y[1], 1.0}, p2[3] = {x[2], y[2], 1.0}, p3[3] = {x[3], y[3], 1.0};
     double c12[3], c20[3], c01[3];
-    h_cross3(p1, p2, c12); h_cross3(p2, p0, c20); h_cross3(p0, p1, c01);
-    const double l0 = h_dot3(c12, p3), l1 = h_dot3(c20, p3), l2 = h_dot3(c01, p3), det = h_dot3(c01, p2);
+    cross3(p1, p2, c12); cross3(p2, p0, c20); cross3(p0, p1, c01);
+    const double l0 = dot3(c12, p3), l1 = dot3(c20, p3), l2 = dot3(c01, p3), det = dot3(c01, p2);
     M[0] = l0 * p0[0]; M[1] = l1 * p1[0]; M[2] = l2 * p2[0];
     M[3] = l0 * p0[1]; M[4] = l1 * p1[1]; M[5] = l2 * p2[1];
     M[6] = l0 * p0[2]; M[7] = l1 * p1[2]; M[8] = l2 * p2[2];
@@ -116,17 +109,6 @@ DEV void h_count_tile(const HPt* s_pt, int nt, const double (&H)[IPL][9], const 
         for (int s = 0; s < NS; s++) cnt[s] += h_inlier(H[s], G[s], p, t_h) ? 1 : 0;
     }
 }
-// the count over one tile for the first `nslots` of a lane's IPL iterations (a uniform number: slots beyond it hold no iteration on any lane)
-template <int NS, int IPL>
-DEV void h_count_slots(int nslots, const HPt* s_pt, int nt, const double (&H)[IPL][9], const double (&G)[IPL][9], int (&cnt)[IPL], double t_h) {
-    if constexpr (NS < IPL) { if (nslots > NS) { h_count_slots<NS + 1, IPL>(nslots, s_pt, nt, H, G, cnt, t_h); return; } }
-    h_count_tile<NS, IPL>(s_pt, nt, H, G, cnt, t_h);
-}
-
-DEV double h_wave_sum(double v) {                                  // the fixed tree: every lane ends with the same sum
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
 
 template <int NT, int IPL>
 __global__ __launch_bounds__(NT) void k_homography_batch(HArgs A, const float* __restrict__ p1, const float* __restrict__ p2,
@@ -134,8 +116,6 @@ __global__ __launch_bounds__(NT) void k_homography_batch(HArgs A, const float* _
                                                          const double* __restrict__ Ein, uint8_t* __restrict__ mask,
                                                          vis_homography_result* __restrict__ out) {
     __shared__ HPt s_pt[H_TILE];
-    __shared__ unsigned long long s_key[NT / 64];
-    __shared__ int s_deg[NT / 64];
     const int pair = blockIdx.x, tid = threadIdx.x;
     const int m = min(max(npts[pair], 0), A.in_stride);
     uint8_t* mrow = mask ? mask + (size_t)pair * A.row_cap : nullptr;
@@ -150,11 +130,8 @@ __global__ __launch_bounds__(NT) void k_homography_batch(HArgs A, const float* _
     }
     const float* q1 = p1 + (size_t)pair * A.in_stride * 2;
     const float* q2 = p2 + (size_t)pair * A.in_stride * 2;
-    const bool single = m <= H_TILE;                               // one tile: filled once
-    if (single) {
-        for (int i = tid; i < m; i += NT) s_pt[i] = h_point(q1, q2, i, A);
-        __syncthreads();
-    }
+    const auto fill = [&](int i) { return h_point(q1, q2, i, A); };
+    const bool single = rl_first_tile<H_TILE, NT>(s_pt, m, fill);
     unsigned long long best = 0;                                   // 0: no iteration with a count > 0 yet
     int ndeg = 0;
     for (int j0 = 0; j0 < A.iters; j0 += NT * IPL) {
@@ -170,35 +147,17 @@ __global__ __launch_bounds__(NT) void k_homography_batch(HArgs A, const float* _
                 for (int k = 0; k < 9; k++) H[s][k] = G[s][k] = 0.0;
             }
         }
-        const int nslots = min(IPL, (A.iters - j0 + NT - 1) / NT);       // slots that hold an iteration on any lane
-        const bool wave_live = j0 + (tid & ~63) < A.iters;          // (wave-uniform) a wave whose lanes hold no iteration only keeps the barriers
-        for (int t0 = 0; t0 < m; t0 += H_TILE) {
-            const int nt = min(H_TILE, m - t0);
-            if (!single) {
-                __syncthreads();                                   // the tile before has been read by every wave
-                for (int i = tid; i < nt; i += NT) s_pt[i] = h_point(q1, q2, t0 + i, A);
-                __syncthreads();
-            }
-            if (wave_live) h_count_slots<1, IPL>(nslots, s_pt, nt, H, G, cnt, A.t_h);
-        }
+        const int nslots = rl_round_slots<NT, IPL>(j0, A.iters);
+        rl_walk_tiles<H_TILE, NT>(s_pt, m, single, rl_wave_live(j0, A.iters), fill, [&](const HPt* tile, int nt) {
+            rl_for_slots<1, IPL>(nslots, [&](auto ns) { h_count_tile<decltype(ns)::value, IPL>(tile, nt, H, G, cnt, A.t_h); });
+        });
 #pragma unroll
-        for (int s = 0; s < IPL; s++) {                            // a lane's iterations in rising order
-            const int j = j0 + s * NT + tid;
-            const unsigned long long key = ((unsigned long long)(unsigned)cnt[s] << 32) | (unsigned)(0x7fffffff - j);
-            if (live[s] && cnt[s] > 0 && key > best) best = key;
-        }
+        for (int s = 0; s < IPL; s++) (void)rl_offer(best, live[s], cnt[s], j0 + s * NT + tid);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-        ndeg += __shfl_xor(ndeg, off);
-    }
-    if ((tid & 63) == 0) { s_key[tid >> 6] = best; s_deg[tid >> 6] = ndeg; }
-    __syncthreads();
+    int sums[1] = {ndeg};
+    rl_block_reduce<NT>(best, sums);
     if (tid >= 64) return;
-    best = s_key[0]; ndeg = s_deg[0];
-    for (int w = 1; w < NT / 64; w++) { best = s_key[w] > best ? s_key[w] : best; ndeg += s_deg[w]; }
-    r.n_points = m; r.n_degenerate = ndeg;
+    r.n_points = m; r.n_degenerate = sums[0];
     // ---- the first wave: the winner again from its draws, then mask, scores and decision over the points in strides of 64
     double H[9], G[9];
 #pragma unroll
@@ -206,7 +165,7 @@ __global__ __launch_bounds__(NT) void k_homography_batch(HArgs A, const float* _
     const bool won = best != 0;
     int it = -1;
     if (won) {
-        it = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+        it = rl_key_slot(best);
         (void)h_hypothesis(draws, it, m, q1, q2, A, H, G);
     }
     double E[9];
@@ -240,7 +199,7 @@ __global__ __launch_bounds__(NT) void k_homography_batch(HArgs A, const float* _
             nine += (i2 && i1) ? 1 : 0;
         }
     }
-    sh = h_wave_sum(sh); se = h_wave_sum(se);
+    sh = wave_sum(sh); se = wave_sum(se);
     for (int off = 32; off > 0; off >>= 1) { nin += __shfl_xor(nin, off); nine += __shfl_xor(nine, off); }
     if (tid != 0) return;
     r.score_h = sh; r.score_e = se; r.n_inliers = nin; r.n_inliers_e = nine; r.best_iter = it;

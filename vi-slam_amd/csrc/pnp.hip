@@ -5,11 +5,10 @@
 // summation order -- is stated in include/vislam_hip.h and restated operation for operation in tests/pnp_ref.py; this file must keep every
 // product and sum parenthesised as written there (the library is built with -ffp-contract=off).
 //
-// k_pnp_batch has k_homography_batch's shape: one workgroup per problem, one three-point sample per lane with its up to four poses in
+// k_pnp_batch has the shape of ransac_lanes.h: one workgroup per problem, one three-point sample per lane with its up to four poses in
 // registers (48 doubles; DESIGN.md section 4.12 has the resource table that decided against four lanes per sample: the root finder runs in
 // lock step over a wave either way, so a lane per root only quarters the samples a wave's solver pass serves), the correspondences walked
-// in LDS tiles of VIS_PNP_TILE (X, x, y) -- every lane reads the same point, a broadcast -- and the winner taken as the maximum of the
-// integer key (count << 32 | 0x7fffffff - (4 sample + root)) over the workgroup, which does not depend on the order it is taken in.  Every
+// in LDS tiles of VIS_PNP_TILE (X, x, y), the winner the maximum key over the workgroup (a slot is 4 sample + root).  Every
 // index into a pose, a root list or a matrix is a compile-time constant (pose.hip's comment on jacobi_eig has the reason).  A lane keeps
 // the pose behind its own best key in LDS and the first wave reads the one of the lane that holds the workgroup's (solving the winner a second time,
 // as k_homography_batch does, would double the kernel: the solver, not the test, is what a short row costs); the first wave then
@@ -17,10 +16,10 @@
 // k_pnp_refine: one wave per problem; every sum over 64 partial sums (i mod 64, rising i) and a fixed butterfly; the 6 x 6 solve on every
 // lane alike (they hold the same sums), which is the one-lane solve without a broadcast.
 #include "vis_internal.h"
+#include "ransac_lanes.h"
 #include <cmath>
 #include <cfloat>
 
-#define DEV __device__ __forceinline__
 #define P_TILE VIS_PNP_TILE            // 512 points = 24 KiB of LDS (public: the tests size their rows around it)
 #define P_INNER 40                     // halvings that separate the roots of a derivative
 #define P_FINAL 100                    // halvings of the quartic itself: the interval stops shrinking long before
@@ -31,12 +30,6 @@ struct PArgs {
 };
 struct alignas(16) PPt { double X[3], x, y, pad_; };               // 48 bytes: the broadcast read is three aligned 16-byte loads
 
-DEV double p_dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-DEV void p_cross3(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
 DEV bool p_finite(double v) { return fabs(v) <= DBL_MAX; }         // false for a NaN
 
 DEV PPt p_point(const double* __restrict__ Xr, const float* __restrict__ xyr, int i, const PArgs& A) {
@@ -135,13 +128,13 @@ DEV bool p_solution(const PSample& S, double v, double (&P)[12]) {
     const double q01[3] = {s1 * S.f1[0] - Q0[0], s1 * S.f1[1] - Q0[1], s1 * S.f1[2] - Q0[2]};
     const double q02[3] = {s2 * S.f2[0] - Q0[0], s2 * S.f2[1] - Q0[1], s2 * S.f2[2] - Q0[2]};
     double nq[3];
-    p_cross3(q01, q02, nq);
-    const double l1 = p_dot3(q01, q01), l2 = p_dot3(q02, q02), nn = p_dot3(nq, nq);
+    cross3(q01, q02, nq);
+    const double l1 = dot3(q01, q01), l2 = dot3(q02, q02), nn = dot3(nq, nq);
     if (!(nn > (0x1p-40 * l1) * l2)) return false;
     const double n1 = sqrt(l1), n3 = sqrt(nn);
     const double g1[3] = {q01[0] / n1, q01[1] / n1, q01[2] / n1}, g3[3] = {nq[0] / n3, nq[1] / n3, nq[2] / n3};
     double g2[3];
-    p_cross3(g3, g1, g2);
+    cross3(g3, g1, g2);
 #pragma unroll
     for (int r = 0; r < 3; r++) {
 #pragma unroll
@@ -171,9 +164,9 @@ DEV int p_hypothesis(const int32_t* __restrict__ draws, int j, int m, const doub
     const double p01[3] = {s1.X[0] - s0.X[0], s1.X[1] - s0.X[1], s1.X[2] - s0.X[2]};
     const double p02[3] = {s2.X[0] - s0.X[0], s2.X[1] - s0.X[1], s2.X[2] - s0.X[2]};
     const double p12[3] = {s2.X[0] - s1.X[0], s2.X[1] - s1.X[1], s2.X[2] - s1.X[2]};
-    const double c2 = p_dot3(p01, p01), b2 = p_dot3(p02, p02), a2 = p_dot3(p12, p12);
+    const double c2 = dot3(p01, p01), b2 = dot3(p02, p02), a2 = dot3(p12, p12);
     if (!(b2 != 0.0)) return 0;
-    const double ca = p_dot3(S.f1, S.f2), cb = p_dot3(S.f0, S.f2), cg = p_dot3(S.f0, S.f1);
+    const double ca = dot3(S.f1, S.f2), cb = dot3(S.f0, S.f2), cg = dot3(S.f0, S.f1);
     const double p = (a2 - c2) / b2, q = (a2 + c2) / b2, ra = a2 / b2, rc = c2 / b2, rbc = (b2 - c2) / b2, rba = (b2 - a2) / b2;
     const double ca2 = ca * ca, cb2 = cb * cb, cg2 = cg * cg, pm1 = p - 1.0, pp1 = 1.0 + p, omq = 1.0 - q, p2 = p * p;
     double c[5];
@@ -184,8 +177,8 @@ DEV int p_hypothesis(const int32_t* __restrict__ draws, int j, int m, const doub
     c[0] = pp1 * pp1 - (4.0 * ra) * cg2;
     if (!(p_finite(c[0]) && p_finite(c[1]) && p_finite(c[2]) && p_finite(c[3]) && p_finite(c[4])) || !(c[4] != 0.0)) return 0;
     double nw[3];
-    p_cross3(p01, p02, nw);
-    const double nnw = p_dot3(nw, nw);
+    cross3(p01, p02, nw);
+    const double nnw = dot3(nw, nw);
     if (!(nnw > (0x1p-40 * c2) * b2)) return 0;
     double B = fabs(c[0] / c[4]);
 #pragma unroll
@@ -197,7 +190,7 @@ DEV int p_hypothesis(const int32_t* __restrict__ draws, int j, int m, const doub
     const double lc = sqrt(c2), lw = sqrt(nnw);
 #pragma unroll
     for (int k = 0; k < 3; k++) { S.P0[k] = s0.X[k]; S.e1[k] = p01[k] / lc; S.e3[k] = nw[k] / lw; }
-    p_cross3(S.e3, S.e1, S.e2);
+    cross3(S.e3, S.e1, S.e2);
     S.b2 = b2; S.p = p; S.pm1 = pm1; S.ca = ca; S.cb = cb; S.cg = cg;
     int nsol = 0;
 #pragma unroll
@@ -227,8 +220,6 @@ __global__ __launch_bounds__(NT) void k_pnp_batch(PArgs A, const double* __restr
                                                   const int32_t* __restrict__ npts, const int32_t* __restrict__ draws,
                                                   uint8_t* __restrict__ mask, vis_pnp_result* __restrict__ out) {
     __shared__ PPt s_pt[P_TILE];
-    __shared__ unsigned long long s_key[NT / 64];
-    __shared__ int s_deg[NT / 64], s_sol[NT / 64];
     __shared__ double s_bp[12][NT];                                // per lane, the pose behind its best key (registers are what bounds the occupancy)
     __shared__ int s_wt;
     const int row = blockIdx.x, tid = threadIdx.x;
@@ -246,11 +237,8 @@ __global__ __launch_bounds__(NT) void k_pnp_batch(PArgs A, const double* __restr
     }
     const double* Xr = X + (size_t)row * A.in_stride * A.x_stride;
     const float* xyr = xy + (size_t)row * A.in_stride * 2;
-    const bool single = m <= P_TILE;                               // one tile: filled once
-    if (single) {
-        for (int i = tid; i < m; i += NT) s_pt[i] = p_point(Xr, xyr, i, A);
-        __syncthreads();
-    }
+    const auto fill = [&](int i) { return p_point(Xr, xyr, i, A); };
+    const bool single = rl_first_tile<P_TILE, NT>(s_pt, m, fill);
     unsigned long long best = 0;                                   // 0: no pose with a count > 0 yet
     int ndeg = 0, nsol = 0;
     for (int j0 = 0; j0 < A.iters; j0 += NT) {
@@ -268,37 +256,19 @@ __global__ __launch_bounds__(NT) void k_pnp_batch(PArgs A, const double* __restr
                 for (int k = 0; k < 12; k++) PR[r][k] = 0.0;
             }
         }
-        const bool wave_live = j0 + (tid & ~63) < A.iters;          // (wave-uniform) a wave whose lanes hold no sample only keeps the barriers
-        for (int t0 = 0; t0 < m; t0 += P_TILE) {
-            const int nt = min(P_TILE, m - t0);
-            if (!single) {
-                __syncthreads();                                   // the tile before has been read by every wave
-                for (int i = tid; i < nt; i += NT) s_pt[i] = p_point(Xr, xyr, t0 + i, A);
-                __syncthreads();
-            }
-            if (wave_live) p_count_tile(s_pt, nt, PR, cnt, A.thr2);
-        }
+        rl_walk_tiles<P_TILE, NT>(s_pt, m, single, rl_wave_live(j0, A.iters), fill,
+                                  [&](const PPt* tile, int nt) { p_count_tile(tile, nt, PR, cnt, A.thr2); });
 #pragma unroll
-        for (int r = 0; r < 4; r++) {                              // a lane's slots in rising order
-            const unsigned long long key = ((unsigned long long)(unsigned)cnt[r] << 32) | (unsigned)(0x7fffffff - (4 * j + r));
-            if (live[r] && cnt[r] > 0 && key > best) {
-                best = key;
+        for (int r = 0; r < 4; r++) {
+            if (rl_offer(best, live[r], cnt[r], 4 * j + r)) {
 #pragma unroll
                 for (int k = 0; k < 12; k++) s_bp[k][tid] = PR[r][k];
             }
         }
     }
     const unsigned long long mine = best;
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(best, off);
-        best = o > best ? o : best;
-        ndeg += __shfl_xor(ndeg, off);
-        nsol += __shfl_xor(nsol, off);
-    }
-    if ((tid & 63) == 0) { s_key[tid >> 6] = best; s_deg[tid >> 6] = ndeg; s_sol[tid >> 6] = nsol; }
-    __syncthreads();
-    best = s_key[0]; ndeg = s_deg[0]; nsol = s_sol[0];
-    for (int w = 1; w < NT / 64; w++) { best = s_key[w] > best ? s_key[w] : best; ndeg += s_deg[w]; nsol += s_sol[w]; }
+    int sums[2] = {ndeg, nsol};
+    rl_block_reduce<NT>(best, sums);
     const bool won = best != 0;
     if (won && mine == best) s_wt = tid;                           // one lane: a key names its slot
     __syncthreads();
@@ -309,7 +279,7 @@ __global__ __launch_bounds__(NT) void k_pnp_batch(PArgs A, const double* __restr
     for (int k = 0; k < 12; k++) Pw[k] = won ? s_bp[k][s_wt] : 0.0;
     int it = -1, root = 0;
     if (won) {
-        const int h = 0x7fffffff - (int)(unsigned)(best & 0xffffffffull);
+        const int h = rl_key_slot(best);
         it = h >> 2; root = h & 3;
     }
     int nin = 0;
@@ -326,17 +296,13 @@ __global__ __launch_bounds__(NT) void k_pnp_batch(PArgs A, const double* __restr
 #pragma unroll
     for (int k = 0; k < 3; k++) r.t[k] = r.t_ransac[k] = Pw[9 + k];
     r.cost0 = r.cost1 = 0.0;
-    r.n_inliers = nin; r.n_points = m; r.best_iter = it; r.best_root = root; r.n_degenerate = ndeg; r.n_solutions = nsol;
+    r.n_inliers = nin; r.n_points = m; r.best_iter = it; r.best_root = root; r.n_degenerate = sums[0]; r.n_solutions = sums[1];
     r.n_inliers_refined = nin;
     r.flags = won && nin < A.min_inliers ? VIS_PNP_FEW : 0;
     out[row] = r;
 }
 
 // ---- the refinement
-DEV double p_wave_sum(double v) {                                  // the fixed tree: every lane ends with the same sum
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_xor(v, off);
-    return v;
-}
 
 // one pass over the points at pose P: S[0..20] = the upper triangle of sum J^T J in row order, S[21..26] = sum J^T r, S[27] = sum |r|^2, over the
 // inliers of the winner P0; returns the number of points that pass the per-point test under P
@@ -367,7 +333,7 @@ DEV int p_pass(const double (&P0)[12], const double (&P)[12], const double* __re
         S[27] = S[27] + (in ? e : 0.0);
     }
 #pragma unroll
-    for (int k = 0; k < 28; k++) S[k] = p_wave_sum(S[k]);
+    for (int k = 0; k < 28; k++) S[k] = wave_sum(S[k]);
     for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
     return n;
 }
@@ -416,7 +382,7 @@ DEV bool p_solve6(const double (&S)[28], double (&d)[6]) {
 // R <- C(w) R, t <- C(w) t + dt with the Cayley map C = I + 2 / (1 + |h|^2) ([h]x + [h]x^2), h = w / 2
 DEV void p_update(double (&P)[12], const double (&d)[6]) {
     const double h[3] = {0.5 * d[0], 0.5 * d[1], 0.5 * d[2]};
-    const double hh = p_dot3(h, h), s = 2.0 / (1.0 + hh);
+    const double hh = dot3(h, h), s = 2.0 / (1.0 + hh);
     const double K[9] = {0.0, -h[2], h[1], h[2], 0.0, -h[0], -h[1], h[0], 0.0};
     double Cm[9];
 #pragma unroll
@@ -569,7 +535,7 @@ __global__ void k_pnp_rel(int n, const vis_pnp_result* __restrict__ rec, const P
     for (int k = 0; k < 9; k++) link[i].R_rel[k] = Rr[k];
 #pragma unroll
     for (int k = 0; k < 3; k++) link[i].t_rel[k] = tr[k];
-    link[i].scale = sqrt(p_dot3(tr, tr));
+    link[i].scale = sqrt(dot3(tr, tr));
 }
 
 // vis_batch_pnp's body on ctx->stream: links (null: gate off), the pose stage's match list (mstride entries per pair) and counts, its p2 rows, the

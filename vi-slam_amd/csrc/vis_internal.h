@@ -440,7 +440,7 @@ int triangulate_run(vis_ctx* ctx, const vis_tri_params* tp, int npairs, int in_s
                     const float* d_p1, const float* d_p2, const uint8_t* d_mask, vis_map_point* d_points, uint8_t* d_flags,
                     vis_tri_summary* d_summary);
 int  vis_build_sample_table(vis_ctx* ctx, int max_m);
-// pose.hip: k_f2f_batch / k_epi_filter on ctx->stream over npairs rows of in_stride (x, y) points (d_npts valid, clamped); d_keep: rows of row_cap >= in_stride.
+// epipolar.hip: k_f2f_batch / k_epi_filter on ctx->stream over npairs rows of in_stride (x, y) points (d_npts valid, clamped); d_keep: rows of row_cap >= in_stride.
 // d_draws: iters x 2 words -- point indices in [0, m) as they stand with `direct`, else raw draws reduced modulo m - 1
 int f2f_batch_run(vis_ctx* ctx, int npairs, int in_stride, const float* d_p1, const float* d_p2, const int32_t* d_npts,
                   const float* d_rot, const float* d_tref, const int32_t* d_draws, int iters, bool direct, vis_f2f_result* d_out);
