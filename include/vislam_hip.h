@@ -849,6 +849,101 @@ int  vis_good_matches_guided(vis_ctx* ctx, int slot_prev, int slot_cur, const fl
  * keypoint capacity x 8 bytes) is allocated by the first guided call of a plan. */
 int  vis_batch_run_guided(vis_ctx* ctx, const uint8_t* d_frames, int n_frames, int stages, const float* d_rot, float radius);
 
+/* ---- pyramidal KLT: follow keypoints from one frame into the next by their image patch (Lucas-Kanade, coarse to fine) -----------------
+ * Beyond the reference, off unless called.  Reads what the gradient stage leaves on the device: the half pyramid (vis_half_pyramid_dims) and
+ * its Scharr gx / gy (int16, made with OpenCV's `scale` = scharr_scale).  The arithmetic is part of the contract (tests/klt_ref.py restates it
+ * and the device reproduces it byte for byte): every inner sum is an integer, everything else is double arithmetic with + - * / sqrt in the
+ * order written here, never contracted.
+ *   Level geometry.  A level-0 position maps to level l as x_l = (x_0 + 0.5) / 2^l - 0.5 (pixel i of level l+1 is the mean of pixels 2i, 2i+1).
+ *   Window fit.  With r = win_radius and n = (2r+1)^2, a window fits at (x, y) on a level of lw x lh pixels iff x, y are finite,
+ *     floor(x) - r >= 0, floor(y) - r >= 0, floor(x) + r + 1 <= lw - 1, floor(y) + r + 1 <= lh - 1 -- tested in double before any
+ *     conversion to an integer.  Nothing outside a level's lw x lh pixels is ever read; there is no border mode.
+ *   Sampling.  X = floor(x), Y = floor(y), a = x - X, b = y - Y; w00 = rint(((1-a)(1-b)) 16384.0), w01 = rint((a (1-b)) 16384.0),
+ *     w10 = rint(((1-a) b) 16384.0), w11 = 16384 - w00 - w01 - w10 (rint: half to even; w11 may be -1).  For window offset (i, j) in [-r, r]^2:
+ *     S = w00 img[Y+j][X+i] + w01 img[Y+j][X+i+1] + w10 img[Y+j+1][X+i] + w11 img[Y+j+1][X+i+1];
+ *     intensities T, J = (S + 256) >> 9 (1/32 grey level); gradients D = (S + 8192) >> 14 (int16 Scharr units); arithmetic shifts.
+ *   One pass (template frame A, target frame B, start p0 in double, optional guess g).  d = 0, or (g - p0) / 2^first_level when both
+ *   components of g are finite.  For l = first_level ... last_level: d <- 2 d when l < first_level; p_l = the level position of p0;
+ *     (a) the template window at p_l does not fit: the level is skipped; at last_level the point is lost, VIS_KLT_OOB;
+ *     (b) T, Dx, Dy from A's level l; Gxx = sum Dx^2, Gxy = sum Dx Dy, Gyy = sum Dy^2 (int64) -> doubles fxx, fxy, fyy;
+ *         det = fxx fyy - fxy fxy;  lam = ((fxx + fyy) - sqrt((fxx - fyy)(fxx - fyy) + 4.0 (fxy fxy))) / (((2.0 n)(32.0 s))(32.0 s));
+ *         !(det > 0 && lam >= min_eig): the level is skipped; at last_level the point is lost, VIS_KLT_FLAT;
+ *     (c) up to max_iters times: the window at p_l + d does not fit in B: the level ends; at last_level the point is lost, VIS_KLT_OOB.
+ *         Else J from B, e = J - T, bx = sum Dx e, by = sum Dy e (int64), ux = -(s (fyy bx - fxy by)) / det, uy = -(s (fxx by - fxy bx)) / det,
+ *         d += u, one iteration counted; stop when ux ux + uy uy <= epsilon epsilon.
+ *   Behind last_level: one more sample of B at p_last + d (same fit rule, VIS_KLT_OOB), sad = sum |J - T|; the pass ends at
+ *   p0 + d 2^last_level.
+ *   A point.  p0 = the float input widened; a non-finite input gives VIS_KLT_INVALID, reads no image and leaves a zero record otherwise.
+ *     Forward pass A = frame 1, B = frame 2.  A lost point reports x, y = its input; else x, y = (float)(p0 + d 2^last_level), and VIS_KLT_ERR
+ *     is set when max_err > 0 and (double)sad > (max_err 32.0) n.  Forward-backward, when fb_max_px > 0 and no flag is set so far: the same
+ *     pass with the frames swapped from the float result, with p0 as its guess, ending at q: dx, dy = q - p0 in double,
+ *     fb = (float)sqrt(dx dx + dy dy), VIS_KLT_FB when dx dx + dy dy > fb_max_px fb_max_px; a lost backward pass gives fb = -1 and VIS_KLT_FB.
+ *     VIS_KLT_TRACKED is set iff no other flag is.  min_eig = (float)lam of last_level when (b) was reached there; iters = the forward
+ *     pass's iterations over all levels; levels = bit l for every level that reached (c) in the forward pass. */
+enum { VIS_KLT_TRACKED = 1, VIS_KLT_OOB = 2, VIS_KLT_FLAT = 4, VIS_KLT_ERR = 8, VIS_KLT_FB = 16, VIS_KLT_INVALID = 32 };
+enum { VIS_KLT_NO_PAIR = 1 };
+typedef struct vis_klt_params {          /* 56 bytes */
+    int32_t win_radius;                  /* 7     2 ... 10: the window is (2r+1)^2 pixels */
+    int32_t first_level;                 /* 3     last_level ... 4 */
+    int32_t last_level;                  /* 0     0 ... first_level */
+    int32_t max_iters;                   /* 10    1 ... 30, per level */
+    double  epsilon;                     /* 0.01  px, finite and >= 0; 0 = never stop early */
+    double  min_eig;                     /* 0.1   grey^2 / px^2 per pixel, finite and >= 0 (the order of OpenCV's 1e-4 in these units) */
+    double  max_err;                     /* 0     mean absolute grey-level residual, finite and >= 0; 0 = off */
+    double  fb_max_px;                   /* 0     forward-backward bound in px, finite and >= 0; 0 = off */
+    int32_t scharr_scale;                /* 3     1 ... 8: what the gradients were made with (the plan's stage always uses 3) */
+    int32_t reserved_;                   /* 0 */
+} vis_klt_params;
+typedef struct vis_klt_point {           /* 32 bytes */
+    float    x, y;                       /* the point in frame 2 (a lost point: its input) */
+    float    fb;                         /* forward-backward distance in px; 0 when it did not run, -1 when the backward pass was lost */
+    float    min_eig;
+    int32_t  sad;
+    int32_t  flags;                      /* VIS_KLT_* */
+    uint16_t iters;
+    uint8_t  levels;
+    uint8_t  pad_[5];                    /* 0 */
+} vis_klt_point;
+typedef struct vis_klt_pair {            /* 32 bytes */
+    int32_t n_points, n_tracked, n_oob, n_flat, n_err, n_fb, n_invalid;
+    int32_t flags;                       /* VIS_KLT_NO_PAIR */
+} vis_klt_pair;
+void vis_default_klt_params(vis_klt_params* kp);
+/* Refusals of the three calls that need no device, in this order.  VIS_E_INVALID: a NULL pointer that is not optional; a negative size;
+ * a parameter outside the ranges above or reserved_ != 0; w, h outside 16 ... 4095 or stride < w; on the device-pointer calls a record
+ * pointer that is not 8-byte or a point / count pointer that is not 4-byte aligned.  Then VIS_E_STATE without a context (vis_batch_klt:
+ * or without a plan, a run, its DETECT and GRADIENT stages, or with another n).
+ * One pair, HOST pointers, shaped like vis_estimate_pose_features: level l images are dense lw[l] x lh[l]; levels outside
+ * [last_level, first_level] may be NULL; gx2 / gy2 (or their level pointers) may be NULL when fb_max_px == 0.  pts: m x 2 floats;
+ * guess: m x 2 floats or NULL; out: m records; pair: one record (n_points = m).  Blocks once. */
+int  vis_klt_track(vis_ctx* ctx, const vis_klt_params* kp, int w, int h,
+                   const uint8_t* const gray1[5], const int16_t* const gx1[5], const int16_t* const gy1[5],
+                   const uint8_t* const gray2[5], const int16_t* const gx2[5], const int16_t* const gy2[5],
+                   const float* pts, const float* guess, int m, vis_klt_point* out, vis_klt_pair* pair);
+/* DEVICE pointers, shaped like vis_align_batch: n frames and the outputs of vis_gradient_batch for them.  Pair i = (frame i-1 -> frame i),
+ * i = 1 ... n-1, tracks the first d_npts[i] (clamped to 0 ... max_pts) of d_pts' row i (max_pts x 2 floats per pair); d_guess: rows like
+ * d_pts or NULL.  d_out: n rows of max_pts records, of which the pair's n_points are written; d_pair: n records.  Row 0 has no pair: its
+ * max_pts records are zeroed and its pair record is zero but for VIS_KLT_NO_PAIR.  d_p1 / d_p2 / d_ntracked (all three or none): per pair the
+ * VIS_KLT_TRACKED points in rising index, frame-1 input and frame-2 result, as rows of max_pts x 2 floats -- the layout vis_homography_batch,
+ * vis_f2f_batch, vis_filter_keypoints_batch and vis_pnp_batch read -- and their count (0 for row 0); places behind the count are left alone.
+ * Any stride >= w; a level too small for any window is skipped by the fit rule, not refused.  Asynchronous on the context's stream. */
+int  vis_klt_batch(vis_ctx* ctx, const vis_klt_params* kp, const uint8_t* d_frames, int w, int h, int stride, int n,
+                   const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
+                   const float* d_pts, const int32_t* d_npts, int max_pts, const float* d_guess,
+                   vis_klt_point* d_out, vis_klt_pair* d_pair, float* d_p1, float* d_p2, int32_t* d_ntracked);
+/* The same on the pairs of the last vis_batch_run, whose stages must have included DETECT and GRADIENT (n = its frames; kp->scharr_scale must
+ * be 3): the points of pair i are ALL keypoints of frame prev[i], in vis_batch_get_keyframes' pairing with the gate off or on, tracked into
+ * frame i.  Rows have the plan's keypoint capacity (row_cap >= it, else VIS_E_CAPACITY): d_out n x row_cap records, d_guess / d_p1 / d_p2
+ * n x row_cap x 2 floats.  A frame without a pair, and a pair to the carried frame (whose gradients are not in this launch's set: what
+ * vis_batch_align does with pair 0), gets the records of its row zeroed (the plan's keypoint capacity of them), n_tracked 0 and a pair record
+ * that is zero but for VIS_KLT_NO_PAIR.
+ * Runs on the context's POSE stream with vis_batch_align's ordering and buffer-lifetime rules: behind everything queued on the context's
+ * stream so far (the gradients, the detection), overlapping the next vis_batch_run; d_frames, the plan's gradients and keypoints and the
+ * caller's buffers are in use until vis_batch_sync -- or until the later vis_batch_run / vis_gradient_batch / vis_feeder_submit /
+ * vis_rectify_batch that would overwrite them, which wait for it. */
+int  vis_batch_klt(vis_ctx* ctx, const vis_klt_params* kp, const uint8_t* d_frames, int n, const float* d_guess, int row_cap,
+                   vis_klt_point* d_out, vis_klt_pair* d_pair, float* d_p1, float* d_p2, int32_t* d_ntracked);
+
 /* ---- rectification (vi::CameraModel, src/CameraModel.cpp:84-105; VISystem::CalculateROI, src/VISystem.cpp:162-205) -------------
  * Opt-in: nothing else in this header remaps a frame (the reference's GPU main hands frames on un-remapped, src/VISystemGPU.cpp:137-146).
  * Restatements of OpenCV 3.2 written from the published algorithm; parity with real OpenCV is UNPINNED.

@@ -30,6 +30,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              VIS_MP_KEPT, default parameters, 200 x 3 draws of default_rng(7)): one row per frame -- frame index, timestamp, q, p, n_linked,
              link flags (VIS_PNPL_*), scale, then n_inliers, n_inliers_refined, best_iter, best_root, flags (VIS_PNP_*), cost0, cost1, R (nine,
              row-major), t (units of the baseline p -> q), R_rel, t_rel; the JSON line carries the counts.
+  --klt out.csv: every keypoint of each pair's previous frame followed into the pair's frame by its image patch (vis_batch_klt behind every
+             batch, default parameters with a forward-backward bound of 1 px; adds VIS_STAGE_GRADIENT): one row per point -- frame index,
+             timestamp, point index (the keypoint's place in the previous frame's list), x1, y1, x2, y2, flags (VIS_KLT_*), fb, min_eig, sad,
+             iters, levels; the JSON line carries the counts.  The pair to a frame of the batch before has no rows (VIS_KLT_NO_PAIR).
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -89,6 +93,7 @@ def main():
     ap.add_argument("--models", default=None, metavar="CSV", help="write the H-or-E model choice of every pair here")
     ap.add_argument("--hposes", default=None, metavar="CSV", help="write the pose of every pair's homography (chosen and second candidate) here")
     ap.add_argument("--pnp", default=None, metavar="CSV", help="write every frame's pose against its keyframe's map points here")
+    ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -136,9 +141,18 @@ def main():
         d_track = torch.empty(a.batch * C.sizeof(vislam.TrackResult), dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         poses = []
+    if a.klt:
+        stages |= vislam.STAGE_GRADIENT
     ctx = vislam.Context(0, p)
     B = min(a.batch, len(paths))
     ctx.batch_plan(w, h, stride, B)
+    if a.klt:
+        kltp = vislam.default_klt_params()
+        kltp.fb_max_px = 1.0
+        kcap = ctx.keypoint_capacity(w, h)
+        d_krec = torch.empty(B * kcap * vislam.KLT_POINT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_kpair = torch.empty(B * vislam.KLT_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        klt_rows, klt_totals = [], dict(pairs=0, points=0, tracked=0, oob=0, flat=0, fb=0)
     if a.weights != "identity":
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
@@ -209,6 +223,8 @@ def main():
             ctx.batch_homography(nb, d_hdraws.data_ptr(), hcap, d_hmask.data_ptr() if a.hposes else 0, d_hrec.data_ptr(), hp)
         if a.hposes:
             ctx.batch_homography_pose(nb, d_hrec.data_ptr(), hcap, d_hmask.data_ptr(), 0, d_hpose.data_ptr(), hq)
+        if a.klt:
+            ctx.batch_klt(d, nb, kcap, d_krec.data_ptr(), d_kpair.data_ptr(), kp=kltp)
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -244,6 +260,18 @@ def main():
                 if int(hpose[i]["kind"]) != vislam.HP_NONE:
                     hpose_totals[int(hpose[i]["kind"])] += 1
                     hpose_rows.append((first + i, stamps[first + i], hpose[i].copy()))
+        if a.klt:
+            krec = d_krec.cpu().numpy().view(vislam.KLT_POINT_DTYPE).reshape(B, kcap)
+            kpair, klinks = d_kpair.cpu().numpy().view(vislam.KLT_PAIR_DTYPE), ctx.batch_get_keyframes()
+            for i in range(nb):
+                if int(kpair[i]["flags"]) & vislam.KLT_NO_PAIR:
+                    continue
+                src_kp = ctx.batch_keypoints(int(klinks[i]))[0]
+                m = int(kpair[i]["n_points"])
+                klt_totals["pairs"] += 1
+                for key, name in (("points", "n_points"), ("tracked", "n_tracked"), ("oob", "n_oob"), ("flat", "n_flat"), ("fb", "n_fb")):
+                    klt_totals[key] += int(kpair[i][name])
+                klt_rows += [(first + i, stamps[first + i], j, src_kp["x"][j], src_kp["y"][j], krec[i, j].copy()) for j in range(m)]
         if ctx.batch_status() != 0:
             raise SystemExit("device capacity flag set")
         for i in range(nb):
@@ -314,6 +342,13 @@ def main():
                         + ",".join("%.17g" % v for v in r["H"]) + "\n")
         out["models_csv"] = a.models
         out["models"] = dict(zip(vislam.MODEL_NAMES, model_totals))
+    if a.klt:
+        with open(a.klt, "w") as f:
+            for fi, ts, j, x1, y1, r in klt_rows:
+                f.write("%d,%d,%d,%.9g,%.9g,%.9g,%.9g,%d,%.9g,%.9g,%d,%d,%d\n" % (fi, ts, j, x1, y1, r["x"], r["y"], r["flags"], r["fb"], r["min_eig"],
+                                                                                   r["sad"], r["iters"], r["levels"]))
+        out["klt_csv"] = a.klt
+        out["klt"] = klt_totals
     if a.hposes:
         with open(a.hposes, "w") as f:
             for fi, ts, r in hpose_rows:

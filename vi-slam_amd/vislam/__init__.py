@@ -216,6 +216,22 @@ PNP_TILE = 512                                    # VIS_PNP_TILE: points per LDS
 PNP_REFINED, PNP_REFINE_REJECTED, PNP_FEW = 1, 2, 4
 
 
+class KltParams(C.Structure):
+    """vis_klt_params: the knobs of the pyramidal KLT tracker (vis_default_klt_params: 7, 3, 0, 10, 0.01, 0.1, 0, 0, 3)"""
+    _fields_ = [("win_radius", C.c_int32), ("first_level", C.c_int32), ("last_level", C.c_int32), ("max_iters", C.c_int32),
+                ("epsilon", C.c_double), ("min_eig", C.c_double), ("max_err", C.c_double), ("fb_max_px", C.c_double),
+                ("scharr_scale", C.c_int32), ("reserved_", C.c_int32)]
+
+
+KLT_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("fb", "<f4"), ("min_eig", "<f4"), ("sad", "<i4"), ("flags", "<i4"), ("iters", "<u2"),
+                            ("levels", "u1"), ("pad_", "u1", (5,))])
+KLT_PAIR_DTYPE = np.dtype([("n_points", "<i4"), ("n_tracked", "<i4"), ("n_oob", "<i4"), ("n_flat", "<i4"), ("n_err", "<i4"), ("n_fb", "<i4"),
+                           ("n_invalid", "<i4"), ("flags", "<i4")])
+assert C.sizeof(KltParams) == 56 and KLT_POINT_DTYPE.itemsize == 32 and KLT_PAIR_DTYPE.itemsize == 32
+KLT_TRACKED, KLT_OOB, KLT_FLAT, KLT_ERR, KLT_FB, KLT_INVALID = 1, 2, 4, 8, 16, 32
+KLT_NO_PAIR = 1
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -261,6 +277,7 @@ ABI_SYMBOLS = [
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
+    "vis_default_klt_params", "vis_klt_track", "vis_klt_batch", "vis_batch_klt",
 ]
 
 
@@ -368,6 +385,13 @@ def _load():
         lib.vis_bf_knn2_hamming_guided_host.argtypes = [vp, vp, vp, ci, vp, vp, ci, vp, cf, vp, vp]
         lib.vis_good_matches_guided.argtypes = [vp, ci, ci, vp, cf, vp, ci, ip, vp, ci, ip]
         lib.vis_batch_run_guided.argtypes = [vp, vp, ci, ci, vp, cf]
+    if hasattr(lib, "vis_batch_klt"):                   # (absent from older A/B builds)
+        kpp, pv5 = C.POINTER(KltParams), C.POINTER(C.c_void_p)
+        lib.vis_default_klt_params.argtypes = [kpp]
+        lib.vis_default_klt_params.restype = None
+        lib.vis_klt_track.argtypes = [vp, kpp, ci, ci, pv5, pv5, pv5, pv5, pv5, pv5, vp, vp, ci, vp, vp]
+        lib.vis_klt_batch.argtypes = [vp, kpp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_klt.argtypes = [vp, kpp, vp, ci, vp, ci, vp, vp, vp, vp, vp]
     lib.vis_synth_canvas.argtypes = [vp, ci, C.c_uint64]
     lib.vis_synth_frame.argtypes = [vp, ci, C.c_uint64, ci, ci, ci, vp, ci]
     lib.vis_gradient_frame_elems.argtypes = [ci, ci]
@@ -470,6 +494,12 @@ def default_pnp_params():
     pp = PnpParams()
     lib.vis_default_pnp_params(C.byref(pp))
     return pp
+
+
+def default_klt_params():
+    kp = KltParams()
+    lib.vis_default_klt_params(C.byref(kp))
+    return kp
 
 
 def default_hpose_params():
@@ -729,6 +759,11 @@ class Context:
         self._chk(lib.vis_level_geometry(self._h, w, h, _ptr(ws), _ptr(hs), _ptr(sc), _ptr(q)), "vis_level_geometry")
         return ws, hs, sc, q
 
+    def keypoint_capacity(self, w, h):
+        """keypoints per frame a plan for w x h frames holds (vis_params.keypoint_capacity): the row length of batch_klt's buffers"""
+        q = self.level_geometry(w, h)[3]
+        return max(int(sum(int(v) + int(v) // 8 + 32 for v in q)), int(self.params.keypoint_capacity))
+
     def pyramid_level(self, level, frame=0, batch=False, w=None, h=None):
         """diagnostic: level `level` >= 1 of frame `frame` as the last detection left it -- of the single-frame plan, or of the batch
         plan with batch=True -- as an (h_level, w_level) array without the stride padding.  (w, h) = the frame size of that plan;
@@ -819,6 +854,43 @@ class Context:
         pose stream like batch_align.  d_init_ptr: n Se3f or 0."""
         self._chk(lib.vis_batch_track(self._h, C.byref(ap), C.c_void_p(d_frames_ptr), n, C.c_void_p(d_init_ptr) if d_init_ptr else None,
                                       C.c_void_p(d_align_ptr), C.c_void_p(d_track_ptr)), "vis_batch_track")
+
+    # -- pyramidal KLT (beyond the reference) -------------------------------------------------------------
+    def klt_track(self, w, h, gray1, gx1, gy1, gray2, pts, gx2=None, gy2=None, guess=None, kp=None):
+        """one pair, host arrays: per-level lists (None for unused levels; gx2 / gy2 only for forward-backward), pts m x 2 floats
+        -> (m records of KLT_POINT_DTYPE, one record of KLT_PAIR_DTYPE)"""
+        kp = kp or default_klt_params()
+
+        def lv(arrs, dt):
+            if arrs is None:
+                return None, None
+            keep = [None if a is None else np.ascontiguousarray(a, dt) for a in arrs]
+            keep += [None] * (5 - len(keep))
+            return keep, (C.c_void_p * 5)(*[None if a is None else a.ctypes.data for a in keep])
+        keep = [lv(gray1, np.uint8), lv(gx1, np.int16), lv(gy1, np.int16), lv(gray2, np.uint8), lv(gx2, np.int16), lv(gy2, np.int16)]
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        guess = None if guess is None else np.ascontiguousarray(guess, np.float32).reshape(len(pts), 2)
+        out, pair = np.zeros(len(pts), KLT_POINT_DTYPE), np.zeros(1, KLT_PAIR_DTYPE)
+        self._chk(lib.vis_klt_track(self._h, C.byref(kp), w, h, *[k[1] for k in keep], _ptr(pts), _ptr(guess), len(pts), _ptr(out), _ptr(pair)),
+                  "vis_klt_track")
+        return out, pair[0]
+
+    def klt_batch(self, d_frames_ptr, w, h, stride, n, d_gray_ptr, d_gx_ptr, d_gy_ptr, d_pts_ptr, d_npts_ptr, max_pts, d_out_ptr, d_pair_ptr,
+                  d_guess_ptr=0, d_p1_ptr=0, d_p2_ptr=0, d_ntracked_ptr=0, kp=None):
+        """device pointers (0 = NULL for the optional ones); asynchronous on the context's stream"""
+        kp = kp or default_klt_params()
+        nz = lambda q: C.c_void_p(q) if q else None
+        self._chk(lib.vis_klt_batch(self._h, C.byref(kp), C.c_void_p(d_frames_ptr), w, h, stride, n, C.c_void_p(d_gray_ptr), C.c_void_p(d_gx_ptr),
+                                    C.c_void_p(d_gy_ptr), nz(d_pts_ptr), C.c_void_p(d_npts_ptr), max_pts, nz(d_guess_ptr), nz(d_out_ptr),
+                                    C.c_void_p(d_pair_ptr), nz(d_p1_ptr), nz(d_p2_ptr), nz(d_ntracked_ptr)), "vis_klt_batch")
+
+    def batch_klt(self, d_frames_ptr, n, row_cap, d_out_ptr, d_pair_ptr, d_guess_ptr=0, d_p1_ptr=0, d_p2_ptr=0, d_ntracked_ptr=0, kp=None):
+        """every keypoint of each pair's previous frame of the last batch_run(DETECT | GRADIENT) tracked into the pair's frame; rows of
+        row_cap >= the plan's keypoint capacity; asynchronous on the pose stream like batch_align"""
+        kp = kp or default_klt_params()
+        nz = lambda q: C.c_void_p(q) if q else None
+        self._chk(lib.vis_batch_klt(self._h, C.byref(kp), C.c_void_p(d_frames_ptr), n, nz(d_guess_ptr), row_cap, C.c_void_p(d_out_ptr),
+                                    C.c_void_p(d_pair_ptr), nz(d_p1_ptr), nz(d_p2_ptr), nz(d_ntracked_ptr)), "vis_batch_klt")
 
     # -- CameraGPU::detectAndComputeGPUFeatures ---------------------------------------------------------
     def orb_detect_compute(self, img, slot=0, cap=None):
