@@ -659,40 +659,26 @@ static int batch_align_stream(vis_ctx* ctx, const vis_align_params* ap, const ui
     // detect chain.  It runs on the pose stream, behind (a) everything queued on the context's stream so far -- the gradients of
     // these frames -- and (b) the matcher of the last batch; what may not overtake it (the next filter rewriting the matched
     // points, the next vis_gradient_batch, the feeder's next copy into these frames) waits for the reader events noted below.
-    (void)hipSetDevice(ctx->device);
-    hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
-    Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
-    HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, sA));
-    HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
-    HIPCHK(ctx, rs.matcher.wait(sP));                                                  // (the set's one reader is the matcher: that is the wait for it)
+    Plan::RecordSet& rs = pl->last_set();
     // d_p1 = the matched keypoints of the query frame of every pair (getGoodMatches, src/Matcher.cpp:295-303): pair i = (frame i-1, frame i),
     // or with the keyframe gate (frame link[i], frame i); links to the carried record (VIS_KF_CARRIED < 0) are skipped like pair 0 --
     // except by vis_batch_track, which aligns them against the snapshot of that keyframe (its matched points are in d_p1 like any other)
-    ctx->stream = sP;
     const int32_t* links = pl->kf_min ? rs.kf_link : nullptr;
-    TrackSnapshot snap{};
-    if (d_track) { snap = pl->snap; snap.valid = pl->kf_min ? pl->track_seq > 0 : pl->pair0_valid; }   // (gate on: only a link says whether it is used)
-    int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->out().p1, pl->out().ngood, pl->root * pl->root,
-                               links, d_track ? &snap : nullptr, d_init, d_out);
-    if (!rc && d_track) rc = launch_track_snapshot(ctx, pl, d_frames, d_gray, d_gx, d_gy, links, n);
-    if (!rc && d_track) rc = launch_track_chain(ctx, pl, links, n, d_out, d_track);
-    ctx->stream = sA;
-    if (rc) return rc;
-    if (d_track) pl->track_seq = pl->run_seq;
-    // two events in turn: the one before stays valid for the sets and the frames it guards
-    const int k = ctx->align_last ^ 1;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_align_done[k], sP));
-    const hipEvent_t ev = ctx->ev_align_done[k];
-    ctx->align_last = k;
-    ctx->align[k] = {ev, d_frames, d_frames + (size_t)pl->stride * pl->h * n};      // (what vis_rectify_batch must not overwrite before it)
     // the side stream refills a gradient set two steps on: it waits for the last alignment that read THAT set.  Decided by pointer
     // identity, not by how the caller got the pointers: the ones vis_batch_gradients() / vis_batch_half_pyramid() hand out are the
-    // plan's sets too (valid until the next vis_batch_run), and a caller passing them explicitly needs the same ordering
-    for (Plan::GradSet& G : pl->grad)
-        if ((G.half && d_gray == G.half) || (G.gx && d_gx == G.gx) || (G.gy && d_gy == G.gy)) G.readers.note(sP, ev);
-    pl->out().readers.note(sP, ev);                                                  // it read the matched points of the last step's matcher-output set
-    if (links) rs.links.note(sP, ev);                                                // and the links the next gate kernel of that record set rewrites
-    return VIS_OK;
+    // plan's sets too (valid until the next vis_batch_run), and a caller passing them explicitly needs the same ordering.  Noted too: the
+    // matcher-output set of the last step (the matched points) and the links, which the next gate kernel of that record set rewrites
+    auto read = [&](Plan::GradSet& G) { return (G.half && d_gray == G.half) || (G.gx && d_gx == G.gx) || (G.gy && d_gy == G.gy) ? &G.readers : nullptr; };
+    return on_pose_stream(ctx, {FU_FORK | FU_MATCHER, nullptr, d_frames, d_frames + (size_t)pl->stride * pl->h * n}, [&] {
+        TrackSnapshot snap{};
+        if (d_track) { snap = pl->snap; snap.valid = pl->kf_min ? pl->track_seq > 0 : pl->pair0_valid; }   // (gate on: only a link says whether it is used)
+        int rc = align_batch_links(ctx, ap, d_frames, pl->w, pl->h, pl->stride, n, d_gray, d_gx, d_gy, pl->out().p1, pl->out().ngood, pl->root * pl->root,
+                                   links, d_track ? &snap : nullptr, d_init, d_out);
+        if (!rc && d_track) rc = launch_track_snapshot(ctx, pl, d_frames, d_gray, d_gx, d_gy, links, n);
+        if (!rc && d_track) rc = launch_track_chain(ctx, pl, links, n, d_out, d_track);
+        if (!rc && d_track) pl->track_seq = pl->run_seq;
+        return rc;
+    }, {read(pl->grad[0]), read(pl->grad[1]), &pl->out().readers, links ? &rs.links : nullptr});
 }
 
 extern "C" int vis_batch_align(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,

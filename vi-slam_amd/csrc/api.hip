@@ -1289,12 +1289,11 @@ static int batch_run_impl(vis_ctx* ctx, const uint8_t* d_frames, int n, int stag
         // an alignment two steps back (vis_batch_align on the pose stream) may still read THIS set's half pyramid / gradients
         HIPCHK(ctx, G.readers.wait(sU));
         if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[10], sU);
-        ctx->stream = sU;
-        rc = launch_half_pyramid_batch(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, G.half);
-        if (!rc && (stages & VIS_STAGE_GRADIENT))
-            rc = launch_gradient(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, G.half, 3 /* the reference's Scharr scale, src/Camera.cpp:172 */,
-                                 G.gx, G.gy, G.g);
-        ctx->stream = sA;
+        { StreamScope on(ctx, sU);
+          rc = launch_half_pyramid_batch(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, G.half);
+          if (!rc && (stages & VIS_STAGE_GRADIENT))
+              rc = launch_gradient(ctx, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, n, G.half, 3 /* the reference's Scharr scale, src/Camera.cpp:172 */,
+                                   G.gx, G.gy, G.g); }
         if (rc) {
             // whatever was queued on the side stream before the failure still reads d_frames / writes set gs: the detect stream joins
             // it before this call returns, so "ctx->stream is done" keeps meaning "the batch's buffers are free"
@@ -1322,9 +1321,9 @@ static int batch_run_impl(vis_ctx* ctx, const uint8_t* d_frames, int n, int stag
     const int last_mo = pl->mo_cur, mo = pl->mo[1].sym ? ((stages & VIS_STAGE_MATCH) ? (last_mo ^ 1) : last_mo) : 0;
     pl->mo_cur = mo;
     Plan::MatchOut& O = pl->out();
-    ctx->stream = sM;
     if (stages & VIS_STAGE_MATCH) {
         VisRange r_("vis: knn + match filters");
+        StreamScope on(ctx, sM);
         rc = launch_expand(ctx, pl, base, n + 1);
         if (!rc) rc = launch_match(ctx, pl, n, guide);
         if (!rc) {
@@ -1339,7 +1338,7 @@ static int batch_run_impl(vis_ctx* ctx, const uint8_t* d_frames, int n, int stag
     if (!rc && (stages & VIS_STAGE_POSE)) {
         (void)hipEventRecord(ctx->ev_filter_done, sM);
         (void)hipStreamWaitEvent(sP, ctx->ev_filter_done, 0);
-        ctx->stream = sP;
+        StreamScope on(ctx, sP);
         (void)hipEventRecord(ctx->ev_pose_start, sP);
         VisRange r_("vis: essential RANSAC + recoverPose");
         rc = launch_pose(ctx, pl, n);
@@ -1347,7 +1346,6 @@ static int batch_run_impl(vis_ctx* ctx, const uint8_t* d_frames, int n, int stag
         ctx->pose_pending = true;
         if (hipEventRecord(ctx->ev_pose_done_set[mo], sP) == hipSuccess) O.readers.note(sP, ctx->ev_pose_done_set[mo]);
     }
-    ctx->stream = sA;
     if (rc) { pl->mo_cur = last_mo; pl->half_valid = pl->grad_valid = false; return rc; }   // nothing of the stream state (carried frame, record set, matcher-output set) has been committed
     pl->have_prev = have_prev; pl->pair0_valid = have_prev;
     if (detect) { pl->run_count++; pl->carry_from = base + n; }
@@ -1519,20 +1517,16 @@ extern "C" int vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int
     if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
     if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_triangulate: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
     if (row_cap < pl->pose_mcap) { ctx->err = "vis_batch_triangulate: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
-    (void)hipSetDevice(ctx->device);
     // On the pose stream, behind the pose stage that wrote d_mask / d_pose (single-buffered, written on that stream only: the next
     // pose stage is queued behind this call) and that itself waited for the filter that wrote p1 / p2.  Those belong to the matcher-output
-    // set of the last step, which the filter two steps on rewrites: it waits for the reader event noted here.
-    hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
+    // set of the last step, which the filter two steps on rewrites: it waits for the reader event noted here.  (No fork: that would order
+    // the call behind the side stream's gradients, which the detect stream joins.)
     Plan::MatchOut& O = pl->out();
-    ctx->stream = sP;
-    const int rc = triangulate_run(ctx, tp, n, pl->pose_mcap, row_cap, pl->d_pose, O.p1, O.p2, pl->d_mask, d_points, d_flags, d_summary);
-    ctx->stream = sA;
-    if (rc) return rc;
-    ctx->pose_pending = true;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_tri_done[pl->mo_cur], sP));
-    O.readers.note(sP, ctx->ev_tri_done[pl->mo_cur]);
-    return VIS_OK;
+    return on_pose_stream(ctx, {0, ctx->ev_tri_done[pl->mo_cur]}, [&] {
+        const int rc = triangulate_run(ctx, tp, n, pl->pose_mcap, row_cap, pl->d_pose, O.p1, O.p2, pl->d_mask, d_points, d_flags, d_summary);
+        if (!rc) ctx->pose_pending = true;
+        return rc;
+    }, {&O.readers});
 }
 
 // ---- F2FRansac / FilterKeypoints for the pairs of a batch: epipolar.hip k_f2f_batch, k_epi_filter
@@ -1558,26 +1552,16 @@ extern "C" int vis_filter_keypoints_batch(vis_ctx* ctx, int n, const float* d_p1
 // The plan's pairs: the rows k_filter wrote for the pose stage (p1 / p2 of the last step's matcher-output set, ngood or nsym).  On the pose
 // stream, behind the matcher of that step (the record set's matcher event, recorded behind the filter: what vis_batch_align waits for) and
 // behind the context's stream, where the caller's inputs may have been produced.  The filter two steps on rewrites the set: it waits for
-// the reader event noted here.
-template <class F> static int batch_epi(vis_ctx* ctx, int n, const char* who, F run) {
+// the reader event noted here; so does, with `links` (the call read the link table of the keyframe gate), the next gate kernel of the record set.
+template <class F> static int batch_epi(vis_ctx* ctx, int n, const char* who, F run, bool links = false) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     Plan* pl = ctx->batch;
     if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
     if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = std::string(who) + ": the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
-    (void)hipSetDevice(ctx->device);
-    hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
-    Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
     Plan::MatchOut& O = pl->out();
-    HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, sA));
-    HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
-    HIPCHK(ctx, rs.matcher.wait(sP));
-    ctx->stream = sP;
-    const int rc = run(pl, O, ctx->p.pose_input == VIS_POSE_SYM ? O.nsym : O.ngood);
-    ctx->stream = sA;
-    if (rc) return rc;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_epi_done[pl->mo_cur], sP));
-    O.readers.note(sP, ctx->ev_epi_done[pl->mo_cur]);
-    return VIS_OK;
+    return on_pose_stream(ctx, {FU_FORK | FU_MATCHER, ctx->ev_epi_done[pl->mo_cur]},
+                          [&] { return run(pl, O, ctx->p.pose_input == VIS_POSE_SYM ? O.nsym : O.ngood); },
+                          {&O.readers, links && pl->kf_min ? &pl->last_set().links : nullptr});
 }
 
 extern "C" int vis_batch_f2f(vis_ctx* ctx, int n, const float* d_rot, const float* d_tref, const int32_t* d_draws, vis_f2f_result* d_out) {
@@ -1867,17 +1851,12 @@ extern "C" int vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     }
     // on the pose stream (batch_epi queues there) behind the pose stage that wrote the pose records and behind vis_batch_triangulate of the same
     // run, which wrote d_points / d_flags on that stream; the link table is read there too: the next gate kernel of the record set waits for it
-    const int rc = batch_epi(ctx, n, "vis_batch_pnp", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+    return batch_epi(ctx, n, "vis_batch_pnp", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
         const bool sym = ctx->p.pose_input == VIS_POSE_SYM;
-        Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
-        return pnp_link_run(ctx, pp, n, pl->kf_min ? rs.kf_link : nullptr, pl->pair0_valid ? 1 : 0, pl->pose_mcap, sym ? pl->kcap : pl->root * pl->root,
+        return pnp_link_run(ctx, pp, n, pl->kf_min ? pl->last_set().kf_link : nullptr, pl->pair0_valid ? 1 : 0, pl->pose_mcap, sym ? pl->kcap : pl->root * pl->root,
                             pl->kcap, sym ? O.sym : O.good, d_npts, O.p2, pl->d_pose, d_points, d_flags, row_cap, require, pl->d_pnp_tab, pl->d_pnp_X,
                             pl->d_pnp_xy, pl->d_pnp_n, d_draws, mask_cap, d_mask, d_out, d_link);
-    });
-    if (rc) return rc;
-    Plan* pl = ctx->batch;
-    if (pl->kf_min) pl->rec[pl->last_base / pl->rec_per_set].links.note(ctx->pose_stream, ctx->ev_epi_done[pl->mo_cur]);
-    return VIS_OK;
+    }, true);
 }
 
 extern "C" int vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redone) {
@@ -1921,7 +1900,7 @@ extern "C" int vis_batch_get_knn(vis_ctx* ctx, int frame, vis_dmatch* out12, int
     if (frame < 0 || frame >= pl->last_n) return VIS_E_INVALID;
     sync_all(ctx);
     int32_t nq = 0, nt = 0, q = pl->last_base + frame;
-    if (pl->kf_min) HIPCHK(ctx, hipMemcpy(&q, pl->rec[pl->last_base / pl->rec_per_set].gq + frame, 4, hipMemcpyDeviceToHost));   // keyframe gate: the query record of the pair, -1 = none
+    if (pl->kf_min) HIPCHK(ctx, hipMemcpy(&q, pl->last_set().gq + frame, 4, hipMemcpyDeviceToHost));   // keyframe gate: the query record of the pair, -1 = none
     if (q >= 0) HIPCHK(ctx, hipMemcpy(&nq, pl->d_nkp + q, 4, hipMemcpyDeviceToHost));
     HIPCHK(ctx, hipMemcpy(&nt, pl->d_nkp + pl->last_base + frame + 1, 4, hipMemcpyDeviceToHost));
     if (q < 0 || (!pl->kf_min && frame == 0 && !pl->pair0_valid)) { nq = 0; nt = 0; }      // no pair: the first frame of a stream, or a frame the gate did not save
@@ -1967,7 +1946,7 @@ extern "C" int vis_batch_get_keyframes(vis_ctx* ctx, int32_t* prev, int cap, int
     if (!prev) return VIS_OK;
     if (cap < n) return VIS_E_CAPACITY;
     sync_all(ctx);
-    if (pl->kf_min) { HIPCHK(ctx, hipMemcpy(prev, pl->rec[pl->last_base / pl->rec_per_set].kf_link, (size_t)n * 4, hipMemcpyDeviceToHost)); return VIS_OK; }
+    if (pl->kf_min) { HIPCHK(ctx, hipMemcpy(prev, pl->last_set().kf_link, (size_t)n * 4, hipMemcpyDeviceToHost)); return VIS_OK; }
     for (int i = 0; i < n; i++) prev[i] = i - 1;
     prev[0] = pl->pair0_valid ? VIS_KF_CARRIED : VIS_KF_FIRST;
     return VIS_OK;

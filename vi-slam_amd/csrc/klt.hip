@@ -404,15 +404,11 @@ extern "C" int vis_batch_klt(vis_ctx* ctx, const vis_klt_params* kp, const uint8
     if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
     if (!(pl->last_stages & VIS_STAGE_DETECT) || !pl->grad_valid) { ctx->err = "vis_batch_klt: the last vis_batch_run had no VIS_STAGE_DETECT | VIS_STAGE_GRADIENT"; return VIS_E_STATE; }
     if (row_cap < pl->kcap) { ctx->err = "vis_batch_klt: row_cap is smaller than the plan's keypoint capacity"; return VIS_E_CAPACITY; }
-    (void)hipSetDevice(ctx->device);
     // On the pose stream like vis_batch_align (align.hip batch_align_stream): behind everything queued on the context's stream so far -- the
     // detect chain that wrote the keypoints and the links, joined by the side stream that wrote the gradients.  What may not overtake it
     // waits for the reader events noted below.
-    hipStream_t sA = ctx->stream, sP = ctx->pose_stream;
-    Plan::RecordSet& rs = pl->rec[pl->last_base / pl->rec_per_set];
+    Plan::RecordSet& rs = pl->last_set();
     Plan::GradSet& GS = pl->grad[pl->grad_set];
-    HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, sA));
-    HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0));
     KltArgs G; std::memset(&G, 0, sizeof(G));
     klt_fill_params(*kp, G);
     klt_fill_levels(G, d_frames, pl->w, pl->h, pl->stride, (size_t)pl->stride * pl->h, GS.half, GS.gx, GS.gy);
@@ -425,18 +421,8 @@ extern "C" int vis_batch_klt(vis_ctx* ctx, const vis_klt_params* kp, const uint8
     G.prev = links;
     G.max_pts = pl->kcap; G.out_row = (size_t)row_cap; G.out = d_out; G.pair = d_pair;
     G.p1 = d_p1; G.p2 = d_p2; G.ntracked = d_ntracked;
-    ctx->stream = sP;
-    const int rc = klt_run(ctx, G, n);
-    ctx->stream = sA;
-    if (rc) return rc;
-    // the reader event: the alignments' ring (two events in turn), so that every writer that waits for an alignment waits for this call too
-    const int k = ctx->align_last ^ 1;
-    HIPCHK(ctx, hipEventRecord(ctx->ev_align_done[k], sP));
-    const hipEvent_t ev = ctx->ev_align_done[k];
-    ctx->align_last = k;
-    ctx->align[k] = {ev, d_frames, d_frames + (size_t)pl->stride * pl->h * n};
-    GS.readers.note(sP, ev);                                       // the gradient set two steps on is refilled behind it
-    rs.matcher.note(sP, ev);                                       // and so is the record set (launch_detect waits for this guard)
-    if (links) rs.links.note(sP, ev);
-    return VIS_OK;
+    // the reader event: the alignments' ring, so that every writer that waits for an alignment waits for this call too.  The gradient set
+    // two steps on is refilled behind it, and so is the record set (launch_detect waits for the matcher guard)
+    return on_pose_stream(ctx, {FU_FORK, nullptr, d_frames, d_frames + (size_t)pl->stride * pl->h * n}, [&] { return klt_run(ctx, G, n); },
+                          {&GS.readers, &rs.matcher, links ? &rs.links : nullptr});
 }

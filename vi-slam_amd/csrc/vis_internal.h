@@ -5,6 +5,7 @@
 
 #include <atomic>
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -157,6 +158,7 @@ struct Plan {
     struct RecordSet { int32_t* pq = nullptr; int32_t* pt = nullptr; int32_t* pqn = nullptr; int32_t* gq = nullptr; int32_t* kf_link = nullptr;
                        ReaderGuard matcher, links; };
     RecordSet rec[VIS_BATCH_SETS];
+    RecordSet& last_set() { return rec[last_base / rec_per_set]; }   // the record set of the last vis_batch_run
     int kf_min = 0;
     int32_t* d_kf_state = nullptr;
     // vis_batch_track (track.hip), allocated on first use: the snapshot of the last saved frame of the last tracked launch (the
@@ -180,6 +182,7 @@ struct vis_ctx {
     // ev_filter_done M -> P, ev_align_fork A -> P; ev_pose_done / _start and ev_match_start also time.  Reader events (ReaderGuard):
     // ev_match_done[record set], ev_pose_done_set / ev_results_done_set / ev_tri_done / ev_epi_done[matcher-output set], ev_align_done[] in turn.  Each is recorded
     // again only by the next reader of its kind -- normally of the same set two steps on, after that set's writer queued its wait.
+    // The reader events of the follow-ups of a batch step (ev_tri_done, ev_epi_done, ev_align_done) are recorded in ONE place: on_pose_stream().
     hipEvent_t ev_filter_done = nullptr, ev_pose_done = nullptr, ev_pose_start = nullptr, ev_detect_done = nullptr, ev_match_start = nullptr;
     hipEvent_t ev_update_fork = nullptr, ev_update_done = nullptr, ev_align_fork = nullptr;
     hipEvent_t ev_match_done[VIS_BATCH_SETS] = {}, ev_pose_done_set[2] = {}, ev_results_done_set[2] = {}, ev_align_done[2] = {}, ev_tri_done[2] = {}, ev_epi_done[2] = {};
@@ -245,6 +248,45 @@ extern std::atomic<unsigned long long> vis_g_launches;
     do { hipError_t e_ = (call);                                                   \
          if (e_ != hipSuccess) { (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_); \
                                  return VIS_E_HIP; } } while (0)
+
+// Every launcher enqueues on ctx->stream: the batch path points it at one of the context's other streams for the length of a block.
+// Restored however the block is left, so a failure between the launches cannot leave the context enqueueing on the wrong stream.
+struct StreamScope {
+    vis_ctx* ctx; hipStream_t saved;
+    StreamScope(vis_ctx* c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
+    ~StreamScope() { ctx->stream = saved; }
+    StreamScope(const StreamScope&) = delete; StreamScope& operator=(const StreamScope&) = delete;
+};
+
+// The alignments' ring (vis_ctx::align): two reader events in turn, so the one before stays valid for the sets and the caller frames it
+// guards.  next = the event the next alignment records; commit, once that record succeeded = it is the latest and read frames [b, e)
+// (what vis_rectify_batch must not overwrite before it).  Bookkeeping only, like ReaderGuard::note.
+inline hipEvent_t align_ring_next(const vis_ctx* ctx) { return ctx->ev_align_done[ctx->align_last ^ 1]; }
+inline void align_ring_commit(vis_ctx* ctx, const uint8_t* b, const uint8_t* e) {
+    ctx->align_last ^= 1;
+    ctx->align[ctx->align_last] = {ctx->ev_align_done[ctx->align_last], b, e};
+}
+inline void note_readers(std::initializer_list<ReaderGuard*> readers, hipStream_t s, hipEvent_t e) { for (ReaderGuard* g : readers) if (g) g->note(s, e); }
+
+// A follow-up of the last vis_batch_run, queued on the pose stream (DESIGN.md has the table of what each entry point orders and notes):
+// optionally behind the context's stream (FU_FORK: where the caller's inputs, the detect chain and the joined gradients were queued) and
+// behind the matcher of the last record set (FU_MATCHER); run() launches under a StreamScope of the pose stream; then the reader event --
+// `done`, or the next of the alignments' ring with the caller frames [frames, frames_end) -- is recorded behind it and noted on every
+// guard of `readers` that is not null: the buffers the call read, whose next writer waits for it.  A failing run() records and notes nothing.
+enum { FU_FORK = 1, FU_MATCHER = 2 };
+struct FollowUp { unsigned order; hipEvent_t done; const uint8_t* frames = nullptr; const uint8_t* frames_end = nullptr; };
+template <class Run> int on_pose_stream(vis_ctx* ctx, const FollowUp& fu, Run run, std::initializer_list<ReaderGuard*> readers) {
+    (void)hipSetDevice(ctx->device);
+    const hipStream_t sP = ctx->pose_stream;
+    if (fu.order & FU_FORK) { HIPCHK(ctx, hipEventRecord(ctx->ev_align_fork, ctx->stream)); HIPCHK(ctx, hipStreamWaitEvent(sP, ctx->ev_align_fork, 0)); }
+    if (fu.order & FU_MATCHER) HIPCHK(ctx, ctx->batch->last_set().matcher.wait(sP));
+    { StreamScope on(ctx, sP); const int rc = run(); if (rc) return rc; }
+    const hipEvent_t ev = fu.done ? fu.done : align_ring_next(ctx);
+    HIPCHK(ctx, hipEventRecord(ev, sP));
+    if (!fu.done) align_ring_commit(ctx, fu.frames, fu.frames_end);
+    note_readers(readers, sP, ev);
+    return VIS_OK;
+}
 
 // Carve typed, 256-byte aligned pieces out of the context scratch block.  With a null base the carver MEASURES: it hands out nullptr and
 // only advances `off`, through the same offsets a bound carver walks.  A take that would end beyond `limit` sets `overflow` and hands out

@@ -2,7 +2,7 @@
 //   1. HostStage::take() beyond the pinned block -> nullptr, and the call's wait() answers VIS_E_NOMEM instead of copying past the block
 //   2. vis_ensure_pin() asked to grow (= free + re-allocate) the block while a HostStage is alive -> VIS_E_STATE, block untouched
 //   3. ReaderGuard (the batch path's buffer sets): which reader events a writer would wait for, and align_reader(): which alignment a
-//      write of caller memory waits for
+//      write of caller memory waits for; StreamScope, the alignments' ring and note_readers(): the bookkeeping of on_pose_stream()
 //   4. Carver / the one buffer list of a host-pointer call (vis_carve): the measuring and the binding pass walk the same offsets, a take
 //      beyond the block is refused, and the pinned bound derived from the list holds a stage that passes every buffer up and down
 // (round 5's host SIGSEGV, gpurun_out/r5r_gdb.log: a stage that kept the address of a block a later vis_ensure_pin had freed; see
@@ -72,6 +72,33 @@ int main() {
         CHECK(align_reader(&a, frames[0], frames[1]) == e1);                  // one it did not read while an older one is pending
         CHECK(align_reader(&a, frames[1], frames[3]) == e2);                  // overlapping both: the latest stands for the older
         CHECK(align_reader(&a, nullptr, nullptr) == e2);
+        // the stream switch of the batch path: restored when the block is left by an early return, nested scopes in order
+        const hipStream_t sA = (hipStream_t)0x30;
+        vis_ctx f;
+        f.stream = sA;
+        const int rc = [&]() -> int { StreamScope on(&f, sP); if (f.stream == sP) return VIS_E_HIP; return VIS_OK; }();
+        CHECK(rc == VIS_E_HIP && f.stream == sA);
+        {
+            StreamScope onM(&f, sM);
+            { StreamScope onP(&f, sP); CHECK(f.stream == sP); }
+            CHECK(f.stream == sM);
+        }
+        CHECK(f.stream == sA);
+        // the alignments' ring: two slots in turn; nothing changes before the commit
+        f.ev_align_done[0] = e1; f.ev_align_done[1] = e2;
+        CHECK(align_ring_next(&f) == e2 && align_ring_next(&f) == e2);          // "next" alone commits nothing
+        CHECK(f.align_last == 0 && align_reader(&f, nullptr, nullptr) == nullptr);
+        align_ring_commit(&f, frames[0], frames[2]);                          // frames 0-1
+        CHECK(f.align_last == 1 && align_reader(&f, frames[1], frames[2]) == e2 && align_reader(&f, frames[2], frames[4]) == nullptr);
+        CHECK(align_ring_next(&f) == e1);
+        align_ring_commit(&f, frames[2], frames[4]);                          // frames 2-3: the other slot
+        CHECK(f.align_last == 0 && align_ring_next(&f) == e2);
+        CHECK(align_reader(&f, frames[3], frames[4]) == e1);                  // overlapping the new one: the new event
+        CHECK(align_reader(&f, frames[0], frames[1]) == e2);                  // disjoint: the older one
+        // a guard list with a null entry: the event is noted on the others only
+        ReaderGuard g1, g2;
+        note_readers({&g1, nullptr, &g2}, sP, e3);
+        CHECK(g1.stream[0] == sP && g1.event[0] == e3 && !g1.stream[1] && g2.stream[0] == sP && g2.event[0] == e3 && !g2.stream[1]);
     }
     {
         // one buffer list, as an entry point writes it (odd sizes: every take pays its alignment); d[2] goes up and comes down
