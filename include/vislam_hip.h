@@ -812,6 +812,93 @@ typedef struct vis_pnp_link {            /* 120 bytes */
 int  vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d_draws, const vis_map_point* d_points, const uint8_t* d_flags,
                    int row_cap, int require, int mask_cap, uint8_t* d_mask, vis_pnp_result* d_out, vis_pnp_link* d_link);
 
+/* ---- the essential-matrix pose on device rows, and its refinement (the reference has neither: its findEssentialMat / recoverPose run once per
+ * frame on host vectors, src/VISystem.cpp:1679-1701, and the five-point winner is never touched again) ---- */
+/* The pose stage of vis_batch_run on caller-made rows: DEVICE pointers, asynchronous on the context's stream.  d_p1 / d_p2: n rows of max_pts
+ * (x, y) float pixels, d_npts[i] of them valid (clamped to max_pts); d_mask: n rows of row_cap bytes, or NULL; d_out: n records, the layout
+ * vis_batch_results_async writes.  Row i is what vis_essential_ransac followed by vis_recover_pose give for that row alone with the context's
+ * parameters -- the same sample stream from (ransac_seed, M), the same adaptive stop, mask, E, R, t and counts -- except that a row without a
+ * model (E all zero) has R = 0 and t = 0 as the batch path's records do, where vis_recover_pose on a zero E reports NaN.  Mask bytes beyond a
+ * row's correspondences are left untouched.  The workspace (what a single call carves for one pair, times n) belongs to the context, is sized by
+ * n, max_pts and ransac_max_iters and only grows: the first call, and any call that grows it, drains every stream of the context before the old
+ * block is freed, so such a call SYNCHRONISES; VIS_E_NOMEM when the block cannot be allocated.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL or misaligned pointer (8 bytes for points and records, 4 for counts; the mask may be NULL) or
+ * a negative size.  VIS_E_STATE without a context.  VIS_E_CAPACITY when max_pts > 8192 (the limit of every RANSAC problem), or when a mask is
+ * given and row_cap < max_pts. */
+int  vis_essential_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts,
+                         int row_cap, uint8_t* d_mask, vis_pose_result* d_out);
+
+/* Two-view refinement: Gauss-Newton on the Sampson distance over a fixed set of correspondences, from the (R, t) of a pose record.
+ * Coordinates: the pose stage's, x = ((double)u - cx) * (1 / fx), y = ((double)v - cy) * (1 / fx), x1 = (x, y, 1) of the first image and x2 of the
+ * second; thr = threshold_px / fx and thr2 = thr thr once on the host.  All arithmetic is double, nothing is contracted, the only operations are
+ * + - * / sqrt and comparisons; dot3(a, b) = a0 b0 + a1 b1 + a2 b2, cross3 the usual (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0), both left to right
+ * (tests/essential_refine_ref.py restates every step in this order, bit for bit).
+ * Start: the record's (R, t).  An all-zero R (what the pose stage leaves where there is no model or no pair), any entry of R or t that is not
+ * finite, or |t|^2 = dot3(t, t) that is not > 0 or not finite gives the ZERO record with flags = VIS_ER_NO_POSE.  Otherwise t <- t / sqrt(|t|^2).
+ * Set: the points i < m (m = the row's count clamped to 0 ... max_pts) whose mask byte is non-zero, every point when there is no mask; fixed for
+ * the whole refinement; n_used counts it.  refine_iters == 0 or n_used < min_inliers: no refinement; the start is reported with best_step = 0,
+ * steps_run = 0, cost1 = cost0, and VIS_ER_FEW when n_used < min_inliers.
+ * For a matrix M (row-major) and x1 = (a, b, 1), x2 = (c, d, 1):  l_k(M) = (M_k0 a + M_k1 b) + M_k2;  m_k(M) = (M_0k c + M_1k d) + M_2k;
+ * s(M) = (c l_0 + d l_1) + l_2.  "v x M" is the matrix whose column j is cross3(v, column j of M).
+ * Model: E = t x R.  Residual of a point: r = s / sd with s = s(E), den = ((l_0^2 + l_1^2) + m_0^2) + m_1^2 (l, m of E), sd = sqrt(den): the signed
+ * Sampson distance.  A point outside the set, or with den not > 0 or not finite, adds 0 to every sum below.
+ * Parameters: rotation w (3), applied on the left of R, and a move (d_0, d_1) in the tangent plane of t.  Tangent basis of t: e = the unit axis of
+ * t's smallest |component| (the lowest index on a tie), c = cross3(t, e), b1 = c / sqrt(dot3(c, c)), b2 = cross3(t, b1).  Derivative matrices
+ * G_a = t x (e_a x R), a = 0, 1, 2 (e_a x R written out: rows (0, -R_2, R_1), (R_2, 0, -R_0), (-R_1, R_0, 0) of R's rows), G_3 = b1 x R, G_4 = b2 x R.
+ * Jacobian, complete (the denominator is differentiated): with g = s(G_a), l', m' of G_a:  dd = 2 (((l_0 l'_0 + l_1 l'_1) + m_0 m'_0) + m_1 m'_1),
+ * J_a = g / sd - ((0.5 s) dd) / (den sd).
+ * Sums: the 15 of J_a J_b (a <= b, row order), the 5 of J_a r and the cost r r, each in ONE fixed order: 64 partial sums over i mod 64 in rising i, then
+ * the tree v = v + v[lane ^ off], off = 32 ... 1; no floating-point atomics.
+ * Step: (w, d) = -(J^T J)^-1 J^T r by LDL^T without pivoting, exactly the PnP refinement's solve above for five unknowns; a pivot that is not > 0 or
+ * not finite ends the iteration (the poses costed so far still compete).  Update: R <- C(w) R with the PnP refinement's Cayley map;
+ * v_k = (t_k + b1_k d_0) + b2_k d_1, t <- v / sqrt(dot3(v, v)) (b1, b2 of the t before the move).
+ * Iterates: pass k = 0 ... refine_iters costs the current pose (iterate k) and, for k < refine_iters, solves and updates.  THE REPORTED POSE IS THE
+ * ITERATE OF LEAST FINITE COST, the earliest on a tie (plain Gauss-Newton is not monotone here); iterate 0 is reported when no cost is finite.
+ * best_step = its index, steps_run = the updates applied; cost0 = iterate 0's cost, cost1 = the reported one's, so cost1 <= cost0.  When a refinement
+ * ran: VIS_ER_REFINED iff best_step > 0, else VIS_ER_REJECTED.  E = t x R of the reported pose.
+ * n_inliers0 / n_inliers_refined: the points of the WHOLE row (not only the set) with s s <= thr2 den under the start and under the reported pose
+ * (a NaN fails); reported, not used.  The input mask is never modified, and the set is not re-selected after the refinement.
+ * The refined pose is NOT written back: vis_batch_triangulate, vis_batch_pnp and vis_batch_track keep reading the pose stage's record.
+ * Two runs are byte-identical. */
+enum { VIS_ER_REFINED = 1, VIS_ER_REJECTED = 2, VIS_ER_FEW = 4, VIS_ER_NO_POSE = 8 };
+typedef struct vis_eref_params {         /* 16 bytes; the defaults are this library's own */
+    int32_t refine_iters;                /* 5      Gauss-Newton steps, 0 ... 64; 0 = none */
+    int32_t min_inliers;                 /* 8      a smaller set is not refined; refused below 6 */
+    double  threshold_px;                /* 1.0    of the reported inlier counts only (vis_params.ransac_threshold's default) */
+} vis_eref_params;
+typedef struct vis_eref_result {         /* 216 bytes, 8-byte aligned */
+    double  R[9], t[3];                  /* the reported pose, |t| = 1 */
+    double  E[9];                        /* t x R of the reported pose */
+    double  cost0, cost1;                /* sum of squared Sampson distances (normalised coordinates) over the set: iterate 0, reported iterate */
+    int32_t n_used, n_points;
+    int32_t n_inliers0, n_inliers_refined;
+    int32_t best_step, steps_run;
+    int32_t flags;                       /* VIS_ER_* */
+    int32_t reserved_;
+} vis_eref_result;
+void vis_default_eref_params(vis_eref_params* ep);
+/* One pair, HOST pointers; blocks once like the other single-frame entry points.  R: 9 doubles row-major, t: 3; p1xy / p2xy: m x 2 floats (pixels);
+ * mask: m bytes or NULL.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL out, R or t, m < 0, NULL points with m > 0, ep NULL, ep.refine_iters < 0 or > 64,
+ * ep.min_inliers < 6, a threshold_px that is not finite and positive.  Then VIS_E_STATE without a context. */
+int  vis_essential_refine(vis_ctx* ctx, const vis_eref_params* ep, const double R[9], const double t[3], const float* p1xy, const float* p2xy,
+                          int m, const uint8_t* mask, vis_eref_result* out);
+/* DEVICE pointers, asynchronous on the context's stream: exactly what vis_essential_batch writes and reads -- d_pose: n records; d_p1 / d_p2: n rows
+ * of max_pts (x, y) float pixels, d_npts[i] of them valid (clamped); d_mask: n rows of row_cap bytes or NULL; d_out: n records -- so that
+ * vis_batch_klt -> vis_essential_batch -> vis_essential_refine_batch runs without a host round trip.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_essential_refine refuses of ep, a NULL or misaligned pointer (8 bytes for records and points,
+ * 4 for counts; the mask may be NULL), a negative size.  Then VIS_E_STATE without a context.  Then VIS_E_CAPACITY when a mask is given and
+ * row_cap < max_pts. */
+int  vis_essential_refine_batch(vis_ctx* ctx, const vis_eref_params* ep, int n, const vis_pose_result* d_pose, const float* d_p1, const float* d_p2,
+                                const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask, vis_eref_result* d_out);
+/* The same on the pairs of the last vis_batch_run (which must have included VIS_STAGE_MATCH and VIS_STAGE_POSE; n = its frames): the correspondences
+ * the pose stage saw, its inlier mask (vis_batch_get_inlier_mask) and its pose records.  A frame without a pair gets the zero record with
+ * VIS_ER_NO_POSE.  Asynchronous on the POSE stream behind the pose stage, overlapping the next vis_batch_run like vis_batch_homography: d_out is in
+ * use until vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_essential_refine refuses of ep, a NULL or misaligned (8 bytes) d_out, n < 0.  Then VIS_E_STATE
+ * without context / plan / match stage / pose stage, or when n differs. */
+int  vis_batch_essential_refine(vis_ctx* ctx, const vis_eref_params* ep, int n, vis_eref_result* d_out);
+
 /* ---- rotation-guided matching ("search by projection"): the 2-NN search of the matcher restricted to a window around the position the
  * pair's rotation predicts -- VISystem::WarpFunctionRT (src/VISystem.cpp:771-860; its call sites :500-504 are commented out in the reference)
  * put in front of the matcher.  rot: row-major 3x3 f32, the matrix vis_batch_f2f takes (current-frame rays -> previous frame, :1031-1033).

@@ -30,6 +30,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              VIS_MP_KEPT, default parameters, 200 x 3 draws of default_rng(7)): one row per frame -- frame index, timestamp, q, p, n_linked,
              link flags (VIS_PNPL_*), scale, then n_inliers, n_inliers_refined, best_iter, best_root, flags (VIS_PNP_*), cost0, cost1, R (nine,
              row-major), t (units of the baseline p -> q), R_rel, t_rel; the JSON line carries the counts.
+  --refined out.csv: the pose stage's (R, t) of every frame's pair refined over its inlier mask (vis_batch_essential_refine behind every batch,
+             default parameters): one row per frame -- frame index, timestamp, flags (VIS_ER_*; 8 = no pair or no pose), n_used, n_points,
+             n_inliers0, n_inliers_refined, best_step, steps_run, cost0, cost1, R (nine, row-major), t (unit), E = [t]x R; the JSON line carries
+             the counts.
   --klt out.csv: every keypoint of each pair's previous frame followed into the pair's frame by its image patch (vis_batch_klt behind every
              batch, default parameters with a forward-backward bound of 1 px; adds VIS_STAGE_GRADIENT): one row per point -- frame index,
              timestamp, point index (the keypoint's place in the previous frame's list), x1, y1, x2, y2, flags (VIS_KLT_*), fb, min_eig, sad,
@@ -93,6 +97,7 @@ def main():
     ap.add_argument("--models", default=None, metavar="CSV", help="write the H-or-E model choice of every pair here")
     ap.add_argument("--hposes", default=None, metavar="CSV", help="write the pose of every pair's homography (chosen and second candidate) here")
     ap.add_argument("--pnp", default=None, metavar="CSV", help="write every frame's pose against its keyframe's map points here")
+    ap.add_argument("--refined", default=None, metavar="CSV", help="write every frame's refined two-view pose here")
     ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
@@ -170,6 +175,10 @@ def main():
         d_prec = torch.empty(B * vislam.PNP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         d_plink = torch.empty(B * vislam.PNP_LINK_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         pnp_rows, pnp_totals = [], dict(linked=0, posed=0, refined=0, no_map=0)
+    if a.refined:
+        erp = vislam.default_eref_params()
+        d_eref = torch.empty(B * vislam.EREF_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        eref_rows, eref_totals = [], dict(refined=0, rejected=0, few=0, no_pose=0)
     if a.models or a.hposes:                                  # one homography RANSAC per batch serves both (the mask does not change the records)
         hp = vislam.default_homography_params()
         d_hdraws = torch.from_numpy(np.random.default_rng(7).integers(0, 2 ** 31, (hp.iters, 4)).astype(np.int32)).cuda()
@@ -219,6 +228,8 @@ def main():
             ctx.batch_triangulate(nb, row_cap, d_mp.data_ptr(), d_mf.data_ptr(), d_ms.data_ptr())
         if a.pnp:
             ctx.batch_pnp(nb, d_pdraws.data_ptr(), d_mp.data_ptr(), d_mf.data_ptr(), row_cap, d_prec.data_ptr(), d_plink.data_ptr(), vislam.MP_KEPT, 0, 0, pp)
+        if a.refined:
+            ctx.batch_essential_refine(nb, d_eref.data_ptr(), erp)
         if a.models or a.hposes:
             ctx.batch_homography(nb, d_hdraws.data_ptr(), hcap, d_hmask.data_ptr() if a.hposes else 0, d_hrec.data_ptr(), hp)
         if a.hposes:
@@ -248,6 +259,12 @@ def main():
                 pnp_totals["refined"] += int(bool(prec[i]["flags"] & vislam.PNP_REFINED))
                 pnp_totals["no_map"] += int(bool(plink[i]["flags"] & vislam.PNPL_NO_MAP))
                 pnp_rows.append((first + i, stamps[first + i], prec[i].copy(), plink[i].copy()))
+        if a.refined:
+            erec = d_eref.cpu().numpy().view(vislam.EREF_RESULT_DTYPE)
+            for i in range(nb):
+                for key, bit in (("refined", vislam.ER_REFINED), ("rejected", vislam.ER_REJECTED), ("few", vislam.ER_FEW), ("no_pose", vislam.ER_NO_POSE)):
+                    eref_totals[key] += int(bool(int(erec[i]["flags"]) & bit))
+                eref_rows.append((first + i, stamps[first + i], erec[i].copy()))
         if a.models:
             hrec = d_hrec.cpu().numpy().view(vislam.HOMOGRAPHY_RESULT_DTYPE)
             for i in range(nb):
@@ -334,6 +351,14 @@ def main():
                         ",".join("%.17g" % v for v in dbl) + "\n")
         out["pnp_csv"] = a.pnp
         out["pnp"] = pnp_totals
+    if a.refined:
+        with open(a.refined, "w") as f:
+            for fi, ts, r in eref_rows:
+                ints = [r[k] for k in ("flags", "n_used", "n_points", "n_inliers0", "n_inliers_refined", "best_step", "steps_run")]
+                dbl = [r["cost0"], r["cost1"]] + list(r["R"]) + list(r["t"]) + list(r["E"])
+                f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + "," + ",".join("%.17g" % v for v in dbl) + "\n")
+        out["refined_csv"] = a.refined
+        out["refined"] = eref_totals
     if a.models:
         with open(a.models, "w") as f:
             for fi, ts, r in model_rows:

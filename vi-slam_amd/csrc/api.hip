@@ -121,6 +121,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
     plan_destroy(ctx->single); plan_destroy(ctx->batch);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
+    if (ctx->d_ess_ws) (void)hipFree(ctx->d_ess_ws);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -1070,6 +1071,22 @@ extern "C" int vis_good_matches_host(vis_ctx* ctx, const vis_keypoint* kps1, int
     return deliver_matches(f, good, cap, n_good, sym_out, sym_cap, n_sym);
 }
 
+// The pose stage's working buffers (pose_run's arguments) for n rows of mc correspondences and `iters` hypotheses, declared ONCE: pose_host carves
+// them from the scratch block for one pair, vis_essential_batch from the context's own workspace for n.
+struct PoseWork {
+    double *n1, *n2, *models, *hyp; int32_t *samples, *counts, *rstate, *worklist; uint8_t* mask;
+    void layout(Carver& cv, size_t n, size_t mc, size_t iters) {
+        n1 = cv.take<double>(n * mc * 2); n2 = cv.take<double>(n * mc * 2);
+        samples = cv.take<int32_t>(n * iters * 5);
+        models = cv.take<double>(n * iters * 90);
+        counts = cv.take<int32_t>(n * iters * 10);
+        rstate = cv.take<int32_t>(n * VIS_RSTATE_WORDS);
+        mask = cv.take<uint8_t>(n * mc);
+        worklist = cv.take<int32_t>(2 + n);
+        hyp = cv.take<double>(n * iters * VIS_HYP_DOUBLES);
+    }
+};
+
 // shared by vis_essential_ransac / vis_recover_pose
 static int pose_host(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m, const double* E_in,
                      int do_ransac, int do_pose, uint8_t* mask, PoseOut* out) {
@@ -1079,24 +1096,18 @@ static int pose_host(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m, 
     const int iters = ctx->p.ransac_max_iters;
     // scratch sized for a power-of-two correspondence count >= 256: a stream whose match count creeps up does not re-allocate per call
     int mroom = 256; while (mroom < mcap) mroom <<= 1;
-    float *d_p1, *d_p2; double *d_n1, *d_n2, *d_models, *d_E, *d_hyp; int32_t *d_npts, *d_samples, *d_counts, *d_rstate, *d_worklist;
-    uint8_t* d_mask; PoseOut* d_pose;
+    float *d_p1, *d_p2; double* d_E; int32_t* d_npts; PoseOut* d_pose; PoseWork W;
     int rc = vis_carve(ctx, [&](Carver& cv) {
         const size_t mc = cv.base ? mcap : mroom;                  // measured with room, bound to what the call uses
         d_p1 = cv.take<float>(mc * 2); d_p2 = cv.take<float>(mc * 2);
         d_npts = cv.take<int32_t>(1);
-        d_n1 = cv.take<double>(mc * 2); d_n2 = cv.take<double>(mc * 2);
-        d_samples = cv.take<int32_t>((size_t)iters * 5);
-        d_models = cv.take<double>((size_t)iters * 90);
-        d_counts = cv.take<int32_t>((size_t)iters * 10);
-        d_rstate = cv.take<int32_t>(VIS_RSTATE_WORDS);
         d_E = cv.take<double>(9);
-        d_mask = cv.take<uint8_t>(mc);
         d_pose = cv.take<PoseOut>(1);
-        d_worklist = cv.take<int32_t>(3);
-        d_hyp = cv.take<double>((size_t)iters * VIS_HYP_DOUBLES);
+        W.layout(cv, 1, mc, (size_t)iters);
     });
     if (rc) return rc;
+    double *d_n1 = W.n1, *d_n2 = W.n2, *d_models = W.models, *d_hyp = W.hyp; int32_t *d_samples = W.samples, *d_counts = W.counts, *d_rstate = W.rstate, *d_worklist = W.worklist;
+    uint8_t* d_mask = W.mask;
     HostStage hs(ctx);
     hs.up(d_p1, p1xy, (size_t)m * 8);
     hs.up(d_p2, p2xy, (size_t)m * 8);
@@ -1857,6 +1868,125 @@ extern "C" int vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
                             pl->kcap, sym ? O.sym : O.good, d_npts, O.p2, pl->d_pose, d_points, d_flags, row_cap, require, pl->d_pnp_tab, pl->d_pnp_X,
                             pl->d_pnp_xy, pl->d_pnp_n, d_draws, mask_cap, d_mask, d_out, d_link);
     }, true);
+}
+
+// ---- the pose stage on device rows: pose_run on a workspace of the context's own
+static int ensure_essential_workspace(vis_ctx* ctx, size_t bytes) {
+    if (bytes <= ctx->ess_ws_bytes) return VIS_OK;
+    sync_all(ctx);                                                 // work queued on any stream may still use the old block
+    if (ctx->d_ess_ws) (void)hipFree(ctx->d_ess_ws);
+    ctx->d_ess_ws = nullptr; ctx->ess_ws_bytes = 0;
+    if (hipMalloc(&ctx->d_ess_ws, bytes) != hipSuccess) {
+        (void)hipGetLastError(); ctx->d_ess_ws = nullptr;
+        ctx->err = "vis_essential_batch: out of device memory for the workspace"; return VIS_E_NOMEM;
+    }
+    ctx->ess_ws_bytes = bytes;
+    // defence in depth, as plan_fill's: nothing reads these buffers before it writes them, but fresh memory must never hold an index.  On the
+    // context's stream, in front of the kernels the caller queues next: that stream does not wait for the null stream (hipStreamNonBlocking), so a
+    // plain hipMemset could still be clearing the block under them
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_ess_ws, 0, bytes, ctx->stream));
+    return VIS_OK;
+}
+
+extern "C" int vis_essential_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap,
+                                   uint8_t* d_mask, vis_pose_result* d_out) {
+    if (n < 0 || max_pts < 0 || row_cap < 0 || !d_npts || !d_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
+    if (((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_npts & 3)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (max_pts > VIS_RANSAC_MAX_M) { ctx->err = "vis_essential_batch: max_pts exceeds the limit of a RANSAC problem"; return VIS_E_CAPACITY; }
+    if (d_mask && row_cap < max_pts) { ctx->err = "vis_essential_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    if (max_pts == 0) {                                            // rows without room for a point: the record of zero correspondences, which is all zeros
+        HIPCHK(ctx, hipMemsetAsync(d_out, 0, (size_t)n * sizeof(vis_pose_result), ctx->stream));
+        return VIS_OK;
+    }
+    const int iters = ctx->p.ransac_max_iters, mcap = max_pts;
+    PoseWork W;
+    Carver measure{nullptr, 0, SIZE_MAX};
+    W.layout(measure, (size_t)n, (size_t)mcap, (size_t)iters);
+    if (measure.overflow) return VIS_E_NOMEM;
+    int rc = ensure_essential_workspace(ctx, measure.off);
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_ess_ws, 0, ctx->ess_ws_bytes};
+    W.layout(cv, (size_t)n, (size_t)mcap, (size_t)iters);
+    if (cv.overflow) { ctx->err = "vis_essential_batch: workspace too small (internal)"; return VIS_E_NOMEM; }
+    rc = vis_build_sample_table(ctx, VIS_POSE_TABLE_M);            // (already there since vis_set_params: the single calls' table, the same sample stream)
+    if (rc) return rc;
+    rc = pose_run(ctx, n, mcap, iters, d_p1, d_p2, d_npts, W.n1, W.n2, W.samples, W.models, W.counts, W.rstate, nullptr, W.mask, d_out, 1, 1,
+                  W.worklist, W.hyp);
+    if (rc) return rc;
+    static_assert(sizeof(PoseOut) == sizeof(vis_pose_result), "the pose stage writes the public record: nothing to convert");
+    return d_mask ? mask_rows_run(ctx, n, mcap, row_cap, d_npts, W.mask, d_mask) : VIS_OK;
+}
+
+// ---- two-view refinement: refine.hip k_essential_refine
+extern "C" void vis_default_eref_params(vis_eref_params* ep) {
+    if (!ep) return;
+    ep->refine_iters = 5; ep->min_inliers = 8; ep->threshold_px = 1.0;
+}
+
+static bool eref_params_ok(const vis_eref_params* ep) {
+    return ep && ep->refine_iters >= 0 && ep->refine_iters <= 64 && ep->min_inliers >= 6 && std::isfinite(ep->threshold_px) && ep->threshold_px > 0.0;
+}
+
+extern "C" int vis_essential_refine(vis_ctx* ctx, const vis_eref_params* ep, const double R[9], const double t[3], const float* p1xy,
+                                    const float* p2xy, int m, const uint8_t* mask, vis_eref_result* out) {
+    if (!out || !R || !t || m < 0 || (m && (!p1xy || !p2xy)) || !eref_params_ok(ep)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    const size_t mc = (size_t)std::max(m, 1), mk = (mc + 3) & ~(size_t)3;
+    float *d_p1, *d_p2; double* d_rt; int32_t* d_n; uint8_t* d_mask; vis_eref_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>(mc * 2); d_p2 = cv.take<float>(mc * 2);
+        d_rt = cv.take<double>(12); d_n = cv.take<int32_t>(1);
+        d_mask = cv.take<uint8_t>(mk);
+        d_out = cv.take<vis_eref_result>(1);
+    });
+    if (rc) return rc;
+    double rt[12]; std::memcpy(rt, R, 72); std::memcpy(rt + 9, t, 24);
+    const int32_t n1 = m;
+    std::vector<uint8_t> mpad;
+    if (mask && m) { mpad.assign(mk, 0); std::memcpy(mpad.data(), mask, (size_t)m); }
+    HostStage hs(ctx);
+    hs.up(d_p1, p1xy, (size_t)m * 8);
+    hs.up(d_p2, p2xy, (size_t)m * 8);
+    hs.up(d_rt, rt, sizeof(rt));
+    hs.up(d_n, &n1, 4);
+    if (!mpad.empty()) hs.up(d_mask, mpad.data(), mk);
+    hs.flush_ups();
+    rc = essential_refine_run(ctx, ep, 1, (int)mc, d_rt, 12, 0, 9, d_p1, d_p2, d_n, (int)mk, mask ? d_mask : nullptr, d_out);
+    if (rc) return vis_drain(ctx, rc);
+    const void* h_out = hs.down(d_out, sizeof(vis_eref_result));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out, h_out, sizeof(*out));
+    return VIS_OK;
+}
+
+static_assert(sizeof(PoseOut) % 8 == 0 && offsetof(PoseOut, R) == 72 && offsetof(PoseOut, t) == 144, "where k_essential_refine finds R and t in a pose record");
+
+extern "C" int vis_essential_refine_batch(vis_ctx* ctx, const vis_eref_params* ep, int n, const vis_pose_result* d_pose, const float* d_p1,
+                                          const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask,
+                                          vis_eref_result* d_out) {
+    if (!eref_params_ok(ep) || n < 0 || max_pts < 0 || row_cap < 0 || !d_pose || !d_npts || !d_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
+    if (((uintptr_t)d_pose & 7) || ((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_npts & 3)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (d_mask && row_cap < max_pts) { ctx->err = "vis_essential_refine_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return essential_refine_run(ctx, ep, n, max_pts, (const double*)d_pose, (int)(sizeof(PoseOut) / 8), 9, 18, d_p1, d_p2, d_npts, row_cap, d_mask, d_out);
+}
+
+extern "C" int vis_batch_essential_refine(vis_ctx* ctx, const vis_eref_params* ep, int n, vis_eref_result* d_out) {
+    if (!eref_params_ok(ep) || n < 0 || !d_out || ((uintptr_t)d_out & 7)) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    if (!(ctx->batch->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_essential_refine: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    // on the pose stream (batch_epi queues there) behind the pose stage of the last run: its mask and records are single-buffered and written on
+    // that stream only, and the next pose stage is queued behind this call
+    return batch_epi(ctx, n, "vis_batch_essential_refine", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        return essential_refine_run(ctx, ep, n, pl->pose_mcap, (const double*)pl->d_pose, (int)(sizeof(PoseOut) / 8), 9, 18, O.p1, O.p2, d_npts,
+                                    pl->pose_mcap, pl->d_mask, d_out);
+    });
 }
 
 extern "C" int vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redone) {

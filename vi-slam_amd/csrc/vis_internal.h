@@ -202,6 +202,9 @@ struct vis_ctx {
     bool ev_ok = false;
     // grow-only scratch for the *_host entry points
     void* d_scratch = nullptr; size_t scratch_bytes = 0;
+    // grow-only workspace of vis_essential_batch (api.hip PoseWork: the pose stage's buffers for n rows), apart from the scratch block so that a
+    // host-pointer call between two batches cannot move it
+    void* d_ess_ws = nullptr; size_t ess_ws_bytes = 0;
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)
@@ -506,6 +509,12 @@ int pnp_link_run(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d
                  const vis_dmatch* d_matches, const int32_t* d_npts, const float* d_p2, const PoseOut* d_pose, const vis_map_point* d_points,
                  const uint8_t* d_flags, int row_cap, int require, int32_t* d_table, double* d_X, float* d_xy, int32_t* d_cnt,
                  const int32_t* d_draws, int mask_cap, uint8_t* d_mask, vis_pnp_result* d_out, vis_pnp_link* d_link);
+// refine.hip: k_essential_refine on ctx->stream over n rows of in_stride (x, y) points; ep validated by the caller; d_start: n records of rec_stride
+// doubles with R at r_off and t at t_off; d_mask: rows of row_cap >= in_stride bytes, or null
+int essential_refine_run(vis_ctx* ctx, const vis_eref_params* ep, int n, int in_stride, const double* d_start, int rec_stride, int r_off, int t_off,
+                         const float* d_p1, const float* d_p2, const int32_t* d_npts, int row_cap, const uint8_t* d_mask, vis_eref_result* d_out);
+// refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
+int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16
 
 #endif

@@ -12,6 +12,8 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.find_homography / homography_batch / batch_homography   homography RANSAC and the H-or-E model choice (beyond the reference)
   Context.homography_pose / homography_pose_batch / batch_homography_pose   (R, t / d, n) of a pair's homography, both survivors of the vote
   Context.pnp_ransac / pnp_batch / batch_pnp   the pose of a frame against map points: P3P RANSAC + Gauss-Newton refinement (beyond the reference)
+  Context.essential_batch                             <-> essential RANSAC + recoverPose on rows that already sit in device memory
+  Context.essential_refine / essential_refine_batch / batch_essential_refine   Gauss-Newton refinement of the two-view pose (beyond the reference)
   Context.filter_keypoints (_batch, batch_...)        <-> VISystem::FilterKeypoints  (src/VISystem.cpp:542-610)
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises.
@@ -216,6 +218,25 @@ PNP_TILE = 512                                    # VIS_PNP_TILE: points per LDS
 PNP_REFINED, PNP_REFINE_REJECTED, PNP_FEW = 1, 2, 4
 
 
+class EssentialRefineParams(C.Structure):
+    """vis_eref_params: the knobs of the two-view refinement (vis_default_eref_params: 5, 8, 1.0)"""
+    _fields_ = [("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("threshold_px", C.c_double)]
+
+
+class EssentialRefineResult(C.Structure):
+    """vis_eref_result: the reported pose (|t| = 1), its E = [t]x R, the costs of the start and of the reported iterate, and the counts"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("E", C.c_double * 9), ("cost0", C.c_double), ("cost1", C.c_double),
+                ("n_used", C.c_int32), ("n_points", C.c_int32), ("n_inliers0", C.c_int32), ("n_inliers_refined", C.c_int32),
+                ("best_step", C.c_int32), ("steps_run", C.c_int32), ("flags", C.c_int32), ("reserved_", C.c_int32)]
+
+
+EREF_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,)), ("cost0", "<f8"), ("cost1", "<f8"), ("n_used", "<i4"),
+                              ("n_points", "<i4"), ("n_inliers0", "<i4"), ("n_inliers_refined", "<i4"), ("best_step", "<i4"), ("steps_run", "<i4"),
+                              ("flags", "<i4"), ("reserved_", "<i4")])
+assert C.sizeof(EssentialRefineParams) == 16 and EREF_RESULT_DTYPE.itemsize == C.sizeof(EssentialRefineResult) == 216
+ER_REFINED, ER_REJECTED, ER_FEW, ER_NO_POSE = 1, 2, 4, 8
+
+
 class KltParams(C.Structure):
     """vis_klt_params: the knobs of the pyramidal KLT tracker (vis_default_klt_params: 7, 3, 0, 10, 0.01, 0.1, 0, 0, 3)"""
     _fields_ = [("win_radius", C.c_int32), ("first_level", C.c_int32), ("last_level", C.c_int32), ("max_iters", C.c_int32),
@@ -274,6 +295,7 @@ ABI_SYMBOLS = [
     "vis_default_homography_params", "vis_find_homography", "vis_homography_batch", "vis_batch_homography",
     "vis_default_hpose_params", "vis_homography_pose", "vis_homography_pose_batch", "vis_batch_homography_pose",
     "vis_default_pnp_params", "vis_pnp_ransac", "vis_pnp_batch", "vis_batch_pnp",
+    "vis_essential_batch", "vis_default_eref_params", "vis_essential_refine", "vis_essential_refine_batch", "vis_batch_essential_refine",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
@@ -364,6 +386,14 @@ def _load():
         lib.vis_pnp_ransac.argtypes = [vp, ppp, vp, vp, ci, vp, vp, vp]
         lib.vis_pnp_batch.argtypes = [vp, ppp, ci, vp, ci, vp, vp, ci, vp, ci, vp, vp]
         lib.vis_batch_pnp.argtypes = [vp, ppp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    if hasattr(lib, "vis_essential_refine_batch"):      # (absent from older A/B builds)
+        epp = C.POINTER(EssentialRefineParams)
+        lib.vis_default_eref_params.argtypes = [epp]
+        lib.vis_default_eref_params.restype = None
+        lib.vis_essential_batch.argtypes = [vp, ci, vp, vp, vp, ci, ci, vp, vp]
+        lib.vis_essential_refine.argtypes = [vp, epp, vp, vp, vp, vp, ci, vp, vp]
+        lib.vis_essential_refine_batch.argtypes = [vp, epp, ci, vp, vp, vp, vp, ci, ci, vp, vp]
+        lib.vis_batch_essential_refine.argtypes = [vp, epp, ci, vp]
     if hasattr(lib, "vis_batch_homography_pose"):       # (absent from older A/B builds)
         hqp = C.POINTER(HposeParams)
         lib.vis_default_hpose_params.argtypes = [hqp]
@@ -494,6 +524,12 @@ def default_pnp_params():
     pp = PnpParams()
     lib.vis_default_pnp_params(C.byref(pp))
     return pp
+
+
+def default_eref_params():
+    ep = EssentialRefineParams()
+    lib.vis_default_eref_params(C.byref(ep))
+    return ep
 
 
 def default_klt_params():
@@ -1176,6 +1212,45 @@ class Context:
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_pnp(self._h, C.byref(pp), n, v(d_draws_ptr), v(d_points_ptr), v(d_flags_ptr), row_cap, require, mask_cap,
                                     v(d_mask_ptr), v(d_out_ptr), v(d_link_ptr)), "vis_batch_pnp")
+
+    # -- the essential-matrix pose on device rows, and its refinement ----------------------------------------------
+    def essential_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr):
+        """queue essential RANSAC + recoverPose of n rows of max_pts (x, y) correspondences on the context's stream (raw DEVICE pointers; 0 /
+        None = NULL for d_mask): n POSE_RESULT_DTYPE records, n rows of row_cap mask bytes.  The first call, and any call that needs a larger
+        workspace, synchronises"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_essential_batch(self._h, n, v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, row_cap, v(d_mask_ptr), v(d_out_ptr)),
+                  "vis_essential_batch")
+
+    def essential_refine(self, R, t, p1, p2, mask=None, ep=None):
+        """one EREF_RESULT_DTYPE element: the Gauss-Newton refinement of (R, t) on the Sampson distance over the correspondences p1 / p2 (m x 2
+        float pixels) whose mask byte is non-zero (None: all)"""
+        ep = default_eref_params() if ep is None else ep
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        assert len(p1) == len(p2)
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert mask is None or len(mask) >= len(p1)
+        out = np.zeros(1, EREF_RESULT_DTYPE)
+        self._chk(lib.vis_essential_refine(self._h, C.byref(ep), _ptr(R), _ptr(t), _ptr(p1), _ptr(p2), len(p1), _ptr(mask), _ptr(out)),
+                  "vis_essential_refine")
+        return out[0]
+
+    def essential_refine_batch(self, n, d_pose_ptr, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr, ep=None):
+        """queue the refinement of n pose records on the context's stream (raw DEVICE pointers; 0 / None = NULL for d_mask): exactly the
+        buffers essential_batch wrote and read; n EREF_RESULT_DTYPE records"""
+        ep = default_eref_params() if ep is None else ep
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_essential_refine_batch(self._h, C.byref(ep), n, v(d_pose_ptr), v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, row_cap,
+                                                 v(d_mask_ptr), v(d_out_ptr)), "vis_essential_refine_batch")
+
+    def batch_essential_refine(self, n, d_out_ptr, ep=None):
+        """the same on the pairs of the last batch_run(STAGE_ALL), from the pose stage's records and inlier mask, on the pose stream behind it;
+        d_out is in use until batch_sync().  The refined pose is not written back into the plan"""
+        ep = default_eref_params() if ep is None else ep
+        self._chk(lib.vis_batch_essential_refine(self._h, C.byref(ep), n, C.c_void_p(d_out_ptr) if d_out_ptr else None), "vis_batch_essential_refine")
 
     # -- batched stream path ----------------------------------------------------------------------------------
     def batch_plan(self, w, h, stride, max_frames):
