@@ -197,7 +197,10 @@ int  vis_good_matches_host(vis_ctx* ctx, const vis_keypoint* kps1, int n1,
                            vis_dmatch* good, int cap, int* n_good,
                            vis_dmatch* sym_out, int sym_cap, int* n_sym);
 /* replaces cv::findEssentialMat(p1,p2,focal,pp,RANSAC,0.999,1.0), src/VISystem.cpp:1679-1680.
- * p1xy/p2xy: m x 2 floats (pixels).  E row-major. mask may be NULL. */
+ * p1xy/p2xy: m x 2 floats (pixels).  E row-major. mask may be NULL.
+ * Per-point test: (float)(s s / den) <= (float)thr^2 (s = x2^T E x1, den the Sampson denominator).  A correspondence with a NaN or an infinite
+ * coordinate is no inlier of any model (s s / den is NaN: a NaN fails; the kernel's division-free shortcut asks for a finite right-hand side,
+ * so inf <= inf does not pass); rows made of such correspondences alone give no model: E all zero, n_inliers 0, iters_run = the cap. */
 int  vis_essential_ransac(vis_ctx* ctx, const float* p1xy, const float* p2xy, int m,
                           double E[9], uint8_t* mask, int* n_inliers, int* iters_run);
 /* replaces cv::recoverPose(E,p1,p2,R,t,focal,pp), src/VISystem.cpp:1701.
@@ -732,8 +735,9 @@ int  vis_batch_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, int n, 
  * zero, when |p01 x p02|^2 <= 2^-40 |p01|^2 |p02|^2, when B is not finite, or when no root yields a pose.  A root is dropped (its slot stays
  * empty) when den is zero or not finite, when v, u or w is not > 0, or when the camera triad fails the same collinearity test.  n_solutions
  * counts the poses of all samples.
- * Per-point test, division-free: (U, V, W) = R X + t (each row ((R_i0 X0 + R_i1 X1) + R_i2 X2) + t_i); an inlier iff W > 0 and
- * (U - x W)^2 + (V - y W)^2 <= thr2 (W W); a NaN fails.  Hypothesis h = 4 j + r: the largest count > 0 wins, ties go to the smallest h.  mask
+ * Per-point test, division-free: (U, V, W) = R X + t (each row ((R_i0 X0 + R_i1 X1) + R_i2 X2) + t_i); an inlier iff W > 0, thr2 (W W) is
+ * finite and (U - x W)^2 + (V - y W)^2 <= thr2 (W W); a NaN fails, and so does a point whose W W overflows or is infinite (inf <= inf would
+ * otherwise pass under every pose).  Hypothesis h = 4 j + r: the largest count > 0 wins, ties go to the smallest h.  mask
  * receives the winner's inlier bytes (zeros when nothing won); bytes beyond the problem's points are left untouched.
  * Refinement: when refine_iters > 0 and n_inliers >= min_inliers, refine_iters Gauss-Newton steps over the winner's inliers (the set is
  * fixed).  Per point, with (U, V, W) under the current pose: iw = 1 / W, un = U / W, vn = V / W, residual (un - x, vn - y), j02 = -(un iw),
@@ -856,8 +860,8 @@ int  vis_essential_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_
  * ITERATE OF LEAST FINITE COST, the earliest on a tie (plain Gauss-Newton is not monotone here); iterate 0 is reported when no cost is finite.
  * best_step = its index, steps_run = the updates applied; cost0 = iterate 0's cost, cost1 = the reported one's, so cost1 <= cost0.  When a refinement
  * ran: VIS_ER_REFINED iff best_step > 0, else VIS_ER_REJECTED.  E = t x R of the reported pose.
- * n_inliers0 / n_inliers_refined: the points of the WHOLE row (not only the set) with s s <= thr2 den under the start and under the reported pose
- * (a NaN fails); reported, not used.  The input mask is never modified, and the set is not re-selected after the refinement.
+ * n_inliers0 / n_inliers_refined: the points of the WHOLE row (not only the set) with thr2 den finite and s s <= thr2 den under the start and under
+ * the reported pose (a NaN fails, and so does a point whose den is infinite: inf <= inf would pass); reported, not used.  The input mask is never modified, and the set is not re-selected after the refinement.
  * The refined pose is NOT written back: vis_batch_triangulate, vis_batch_pnp and vis_batch_track keep reading the pose stage's record.
  * Two runs are byte-identical. */
 enum { VIS_ER_REFINED = 1, VIS_ER_REJECTED = 2, VIS_ER_FEW = 4, VIS_ER_NO_POSE = 8 };

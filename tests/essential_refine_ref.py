@@ -129,7 +129,8 @@ def gn_pass(R, t, a, b, c, d, setmask, thr2):
         E, G = matrices(R, t)
         l0, l1, m0, m1, s = apply(E, a, b, c, d)
         den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1
-        n = int((s * s <= thr2 * den).sum())
+        rhs = thr2 * den
+        n = int(((np.abs(rhs) <= DBL_MAX) & (s * s <= rhs)).sum())
         inl = setmask & (den > 0.0) & (np.abs(den) <= DBL_MAX)
         sd = np.sqrt(den)
         r, hs, dsd = s / sd, 0.5 * s, den * sd

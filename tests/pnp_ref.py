@@ -251,7 +251,8 @@ def inliers(P, X, x, y, thr2):
     with np.errstate(all="ignore"):
         U, V, W = transform(P, X)
         du, dv = U - x * W, V - y * W
-        return (W > 0.0) & ((du * du + dv * dv) <= thr2 * (W * W))
+        rhs = thr2 * (W * W)
+        return (W > 0.0) & _finite(rhs) & ((du * du + dv * dv) <= rhs)
 
 
 def hypotheses(cam, pp, X, xy, draws, iters=None, count=True):

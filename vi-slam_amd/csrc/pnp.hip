@@ -52,7 +52,8 @@ DEV bool p_inlier(const double (&P)[12], const PPt& q, double thr2) {
     double U, V, W;
     p_transform(P, q.X, U, V, W);
     const double du = U - q.x * W, dv = V - q.y * W;
-    return W > 0.0 && (du * du + dv * dv) <= thr2 * (W * W);
+    const double rhs = thr2 * (W * W);                              // an overflowed rhs would let inf <= inf pass under every pose
+    return W > 0.0 && p_finite(rhs) && (du * du + dv * dv) <= rhs;
 }
 
 // ---- the real roots of a polynomial of degree D in (0, B): derivative interlacing (oracle/pose.cpp real_roots), one level

@@ -1000,8 +1000,10 @@ DEV int sampson_in_f64(const double* __restrict__ Em, double x1, double y1, doub
     const double a = Ex0 * Ex0, b = Ex1 * Ex1, c = Et0 * Et0, d = Et1 * Et1;
     const double num = x2tEx1 * x2tEx1, den = ((a + b) + c) + d;
     // division-free classification of (float)(num/den) <= thr2: num <= kLo*den is certainly an inlier, num >= kHi*den certainly an
-    // outlier (margins 2^-40 >> the 2^-53 rounding of the products), anything in between takes the exact division
-    if (den > 0 && num <= kLo * den) return 1;
+    // outlier (margins 2^-40 >> the 2^-53 rounding of the products), anything in between takes the exact division.  The first shortcut
+    // needs a finite right-hand side: with an infinite pixel num = den = +inf, where inf <= inf would pass and the division gives a NaN
+    const double lo = kLo * den;
+    if (den > 0 && lo <= DBL_MAX && num <= lo) return 1;
     if (num >= kHi * den) return 0;
     return (float)(num / den) <= thr2 ? 1 : 0;
 }

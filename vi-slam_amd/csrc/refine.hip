@@ -96,7 +96,8 @@ DEV int er_pass(const double (&R)[9], const double (&t)[3], const float* __restr
         double l0, l1, m0, m1, s;
         er_apply(E, a, b, c, d, l0, l1, m0, m1, s);
         const double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
-        n += (s * s <= A.thr2 * den) ? 1 : 0;
+        const double rhs = A.thr2 * den;                           // an infinite rhs would let inf <= inf pass
+        n += (er_finite(rhs) && s * s <= rhs) ? 1 : 0;
         const bool in = (mrow ? mrow[i] != 0 : true) && den > 0.0 && er_finite(den);
         const double sd = sqrt(den), r = s / sd, hs = 0.5 * s, dsd = den * sd;
         double J[5];
@@ -137,7 +138,8 @@ DEV int er_cost(const double (&R)[9], const double (&t)[3], const float* __restr
         double l0, l1, m0, m1, s;
         er_apply(E, a, b, c, d, l0, l1, m0, m1, s);
         const double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
-        n += (s * s <= A.thr2 * den) ? 1 : 0;
+        const double rhs = A.thr2 * den;                           // an infinite rhs would let inf <= inf pass
+        n += (er_finite(rhs) && s * s <= rhs) ? 1 : 0;
         const bool in = (mrow ? mrow[i] != 0 : true) && den > 0.0 && er_finite(den);
         const double r = s / sqrt(den), e2 = r * r;
         acc = acc + (in ? e2 : 0.0);
