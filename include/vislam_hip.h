@@ -903,6 +903,98 @@ int  vis_essential_refine_batch(vis_ctx* ctx, const vis_eref_params* ep, int n, 
  * without context / plan / match stage / pose stage, or when n differs. */
 int  vis_batch_essential_refine(vis_ctx* ctx, const vis_eref_params* ep, int n, vis_eref_result* d_out);
 
+/* Two-view polish: the refinement above with its set RE-SELECTED under the pose it reached, and the result in a pose record that
+ * vis_batch_triangulate_from reads (tests/essential_polish_ref.py restates every step on essential_refine_ref's functions, bit for bit).
+ * Everything the refinement's contract states holds here -- coordinates, residual, Jacobian, solve, updates -- except the order of the sums:
+ * Summation contract "T" (tiled), for each of the 21 sums:
+ *   partial sum j, j = 0 ... 255, adds the terms of the points i = j (mod 256) in rising i, starting from +0.0;
+ *   W_w, w = 0 ... 3, is the tree v = v + v[lane ^ off], off = 32 ... 1, over the partial sums 64 w ... 64 w + 63;
+ *   the sum is ((W_0 + W_1) + W_2) + W_3.  No floating-point atomics; every thread ends with the same bits; integer counts in any order.
+ * A partial sum is never -0.0 (it starts at +0.0), so neither is a W.  A row of at most 64 points has W_1 = W_2 = W_3 = +0.0 and its sum is W_0
+ * bit for bit: the one-wave contract of vis_essential_refine.  The device therefore runs one kernel in two shapes, chosen per LAUNCH and without
+ * effect on a bit: one wave per pair when max_pts <= 64, four waves (thread tid owns the residue tid, the wave totals added in rising w) otherwise.
+ * Start: vis_essential_refine's, from the record's (R, t): the same tests give the ZERO record with flags = VIS_EP_NO_POSE -- then the output mask row
+ * is left untouched and pose_out receives the input record unchanged -- and otherwise t <- t / sqrt(|t|^2), once.
+ * Set 0: the points i < m (m = the row's count clamped to 0 ... max_pts) whose input mask byte is non-zero, every point without a mask; it is written
+ * to the output mask row, bytes 0 / 1 for i < m, and the current set lives there from then on; n_set_first counts it.  thr = select_px / fx and
+ * thr2 = thr thr once on the host.
+ * n_set_first < min_inliers: VIS_EP_FEW; the start is reported with cost_first = cost0 = cost1 = its cost over set 0, n_set_last = n_set_first and
+ * rounds_run = steps_run = best_step = n_changed = 0.
+ * Otherwise round k = 0 ... rounds:
+ *   k >= 1: (1) the NEW set = the points of the whole row with thr2 den finite and s s <= thr2 den under the pose reported by round k - 1 (a NaN
+ *           fails, and so does a point whose den is infinite: inf <= inf would pass); n_changed = the bytes in which it differs from the current set.
+ *           (2) n_changed == 0: stop.  (3) the new set has fewer than min_inliers points: stop with VIS_EP_SHRANK; the current set and pose stay.
+ *           (4) otherwise the new set becomes the current one.
+ *   then vis_essential_refine's passes 0 ... refine_iters over the current set, from the pose reported by round k - 1 (round 0: from the start): the
+ *   round reports its iterate of least finite cost, the earliest on a tie.  Costs are compared within a round only -- two sets' costs do not compare.
+ * Record: the pose reported by the last round run and E = t x R of it; cost_first = iterate 0 of round 0; cost0 / cost1 / best_step = the last round
+ * run's iterate 0, reported iterate and its index, so cost1 <= cost0; n_set_last = the current set at the end; n_changed = of the last selection made
+ * (0 when none was); rounds_run = the rounds run, round 0 included; steps_run = the updates applied in all rounds.  VIS_EP_POLISHED iff some round
+ * reported an iterate other than its first (the pose moved), else VIS_EP_REJECTED.
+ * Output mask: the set the reported pose was fitted on (n_set_last bytes are 1); bytes beyond a row's points are left untouched.  The input mask is
+ * never modified.  pose_out (optional): the input record with E, R, t replaced by the reported pose and n_inliers by n_set_last.
+ * rounds = 0 on a row of at most 64 points: R, t, E, cost0, cost1, best_step are vis_essential_refine's, byte for byte.  Two runs are byte-identical.
+ * Nothing is written into a plan: vis_batch_track and vis_batch_pnp's links (vis_pnp_link) still read the pose stage's record. */
+enum { VIS_EP_POLISHED = 1, VIS_EP_REJECTED = 2, VIS_EP_FEW = 4, VIS_EP_NO_POSE = 8, VIS_EP_SHRANK = 16 };
+typedef struct vis_epolish_params {      /* 32 bytes; the defaults are this library's own */
+    int32_t rounds;                      /* 3      re-selections, 0 ... 8; 0 = the refinement over set 0 alone */
+    int32_t refine_iters;                /* 5      Gauss-Newton steps per round, 1 ... 64 */
+    int32_t min_inliers;                 /* 8      a smaller set is not refined; refused below 6 */
+    int32_t reserved_;                   /* 0 */
+    double  select_px;                   /* 2.0    the re-selection's threshold in pixels, finite and > 0 */
+    int32_t reserved2_[2];               /* 0 */
+} vis_epolish_params;
+typedef struct vis_epolish_result {      /* 224 bytes, 8-byte aligned, no implicit padding */
+    double  R[9], t[3];                  /* the reported pose, |t| = 1 */
+    double  E[9];                        /* t x R of the reported pose */
+    double  cost_first;                  /* iterate 0 of round 0: the start's cost over set 0 */
+    double  cost0, cost1;                /* of the last round run: its iterate 0 and its reported iterate, over that round's set */
+    int32_t n_points, n_set_first, n_set_last;
+    int32_t n_changed;
+    int32_t rounds_run, steps_run, best_step;
+    int32_t flags;                       /* VIS_EP_* */
+} vis_epolish_result;
+void vis_default_epolish_params(vis_epolish_params* ep);
+/* One pair, HOST pointers; blocks once like the other single-frame entry points.  R, t, p1xy, p2xy, m, mask as for vis_essential_refine; mask_out:
+ * m bytes; pose_out: one record or NULL -- its input record is all zero but for R, t and n_points = m.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL out, R or t, m < 0, NULL points or a NULL mask_out with m > 0, ep NULL, ep.rounds < 0 or > 8,
+ * ep.refine_iters < 1 or > 64, ep.min_inliers < 6, a select_px that is not finite and positive, a reserved field that is not 0.  Then VIS_E_STATE
+ * without a context.  A refused call writes nothing. */
+int  vis_essential_polish(vis_ctx* ctx, const vis_epolish_params* ep, const double R[9], const double t[3], const float* p1xy, const float* p2xy,
+                          int m, const uint8_t* mask, vis_epolish_result* out, uint8_t* mask_out, vis_pose_result* pose_out);
+/* DEVICE pointers, asynchronous on the context's stream: vis_essential_refine_batch's rows -- d_mask: n rows of row_cap bytes or NULL -- and
+ * d_mask_out: n rows of row_cap bytes (required), d_out: n records, d_pose_out: n records or NULL.  Rows may be as long as memory allows: the 8192
+ * of a RANSAC problem does not apply.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_essential_polish refuses of ep, a NULL or misaligned pointer (8 bytes for records and points,
+ * 4 for counts; d_mask and d_pose_out may be NULL), a negative size, d_mask_out overlapping d_mask or d_pose_out overlapping d_pose.  Then
+ * VIS_E_STATE without a context.  Then VIS_E_CAPACITY when row_cap < max_pts. */
+int  vis_essential_polish_batch(vis_ctx* ctx, const vis_epolish_params* ep, int n, const vis_pose_result* d_pose, const float* d_p1, const float* d_p2,
+                                const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask, uint8_t* d_mask_out,
+                                vis_epolish_result* d_out, vis_pose_result* d_pose_out);
+/* The same on the pairs of the last vis_batch_run (which must have included VIS_STAGE_MATCH and VIS_STAGE_POSE; n = its frames), as
+ * vis_batch_essential_refine: the pose stage's correspondences, mask (read, never written) and records.  d_mask_out: n rows of row_cap bytes with
+ * row_cap >= the plan's correspondences per pair (root^2, or the keypoint capacity with VIS_POSE_SYM).  A frame without a pair gets the NO_POSE
+ * record.  Asynchronous on the POSE stream behind the pose stage, overlapping the next vis_batch_run: the caller's buffers are in use until
+ * vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_essential_polish refuses of ep, a NULL d_mask_out or d_out, a misaligned (8 bytes) d_out or
+ * d_pose_out, n < 0 or row_cap < 0.  Then VIS_E_STATE without context / plan / match stage / pose stage, or when n differs.  Then VIS_E_CAPACITY
+ * when row_cap is below the plan's correspondences per pair. */
+int  vis_batch_essential_polish(vis_ctx* ctx, const vis_epolish_params* ep, int n, int row_cap, uint8_t* d_mask_out, vis_epolish_result* d_out,
+                                vis_pose_result* d_pose_out);
+/* vis_batch_triangulate with the pose records (R, t, n_points are read) and the mask rows taken from CALLER device buffers -- those
+ * vis_batch_essential_polish wrote for the same run -- instead of the plan's; the correspondences are still the plan's.  d_pose: n records, 8-byte
+ * aligned; d_mask: n rows EXACTLY the plan's correspondences per pair apart (mask_cap states the distance; the triangulation reads its mask at the
+ * row length of its points), or NULL for every point an inlier.  Fed the plan's own records and mask it gives vis_batch_triangulate's bytes.  Same
+ * stream, ordering and buffer lifetimes as vis_batch_triangulate, which is also what orders it behind a vis_batch_essential_polish queued before it.
+ * Records or mask rows that anything else wrote must be complete before the call: like vis_batch_triangulate it does not wait for the context's stream.
+ * vis_batch_pnp takes its points from the caller already, so polish -> triangulate_from -> pnp chains with nothing more; vis_batch_pnp's links
+ * (vis_pnp_link) and vis_batch_track still read the plan's record.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_batch_triangulate refuses, a NULL or misaligned d_pose, mask_cap < 0.  Then VIS_E_STATE as
+ * vis_batch_triangulate.  Then VIS_E_CAPACITY when row_cap is below the plan's correspondences per pair, or d_mask is given and mask_cap differs
+ * from it. */
+int  vis_batch_triangulate_from(vis_ctx* ctx, const vis_tri_params* tp, int n, const vis_pose_result* d_pose, int mask_cap, const uint8_t* d_mask,
+                                int row_cap, vis_map_point* d_points, uint8_t* d_flags, vis_tri_summary* d_summary);
+
 /* ---- rotation-guided matching ("search by projection"): the 2-NN search of the matcher restricted to a window around the position the
  * pair's rotation predicts -- VISystem::WarpFunctionRT (src/VISystem.cpp:771-860; its call sites :500-504 are commented out in the reference)
  * put in front of the matcher.  rot: row-major 3x3 f32, the matrix vis_batch_f2f takes (current-frame rays -> previous frame, :1031-1033).

@@ -34,6 +34,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              default parameters): one row per frame -- frame index, timestamp, flags (VIS_ER_*; 8 = no pair or no pose), n_used, n_points,
              n_inliers0, n_inliers_refined, best_step, steps_run, cost0, cost1, R (nine, row-major), t (unit), E = [t]x R; the JSON line carries
              the counts.
+  --polished out.csv: the same pose polished -- its inlier set re-selected at 2 px under the refined pose, up to three times
+             (vis_batch_essential_polish behind every batch, default parameters): one row per frame -- frame index, timestamp, flags (VIS_EP_*;
+             8 = no pair or no pose), n_points, n_set_first, n_set_last, n_changed, rounds_run, steps_run, best_step, cost_first, cost0, cost1,
+             R (nine, row-major), t (unit), E = [t]x R; the JSON line carries the counts.
   --klt out.csv: every keypoint of each pair's previous frame followed into the pair's frame by its image patch (vis_batch_klt behind every
              batch, default parameters with a forward-backward bound of 1 px; adds VIS_STAGE_GRADIENT): one row per point -- frame index,
              timestamp, point index (the keypoint's place in the previous frame's list), x1, y1, x2, y2, flags (VIS_KLT_*), fb, min_eig, sad,
@@ -98,6 +102,7 @@ def main():
     ap.add_argument("--hposes", default=None, metavar="CSV", help="write the pose of every pair's homography (chosen and second candidate) here")
     ap.add_argument("--pnp", default=None, metavar="CSV", help="write every frame's pose against its keyframe's map points here")
     ap.add_argument("--refined", default=None, metavar="CSV", help="write every frame's refined two-view pose here")
+    ap.add_argument("--polished", default=None, metavar="CSV", help="write every frame's polished two-view pose here")
     ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
@@ -179,6 +184,12 @@ def main():
         erp = vislam.default_eref_params()
         d_eref = torch.empty(B * vislam.EREF_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         eref_rows, eref_totals = [], dict(refined=0, rejected=0, few=0, no_pose=0)
+    if a.polished:
+        epp = vislam.default_epolish_params()
+        pcap = max(int(np.floor(np.sqrt(p.n_cells))) ** 2, 1)  # the grid-filtered good matches of a pair
+        d_epol = torch.empty(B * vislam.EPOLISH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_pmask = torch.empty(B * pcap, dtype=torch.uint8, device="cuda")
+        epol_rows, epol_totals = [], dict(polished=0, rejected=0, few=0, no_pose=0, shrank=0)
     if a.models or a.hposes:                                  # one homography RANSAC per batch serves both (the mask does not change the records)
         hp = vislam.default_homography_params()
         d_hdraws = torch.from_numpy(np.random.default_rng(7).integers(0, 2 ** 31, (hp.iters, 4)).astype(np.int32)).cuda()
@@ -230,6 +241,8 @@ def main():
             ctx.batch_pnp(nb, d_pdraws.data_ptr(), d_mp.data_ptr(), d_mf.data_ptr(), row_cap, d_prec.data_ptr(), d_plink.data_ptr(), vislam.MP_KEPT, 0, 0, pp)
         if a.refined:
             ctx.batch_essential_refine(nb, d_eref.data_ptr(), erp)
+        if a.polished:
+            ctx.batch_essential_polish(nb, pcap, d_pmask.data_ptr(), d_epol.data_ptr(), 0, epp)
         if a.models or a.hposes:
             ctx.batch_homography(nb, d_hdraws.data_ptr(), hcap, d_hmask.data_ptr() if a.hposes else 0, d_hrec.data_ptr(), hp)
         if a.hposes:
@@ -265,6 +278,13 @@ def main():
                 for key, bit in (("refined", vislam.ER_REFINED), ("rejected", vislam.ER_REJECTED), ("few", vislam.ER_FEW), ("no_pose", vislam.ER_NO_POSE)):
                     eref_totals[key] += int(bool(int(erec[i]["flags"]) & bit))
                 eref_rows.append((first + i, stamps[first + i], erec[i].copy()))
+        if a.polished:
+            prec_ = d_epol.cpu().numpy().view(vislam.EPOLISH_RESULT_DTYPE)
+            for i in range(nb):
+                for key, bit in (("polished", vislam.EP_POLISHED), ("rejected", vislam.EP_REJECTED), ("few", vislam.EP_FEW), ("no_pose", vislam.EP_NO_POSE),
+                                 ("shrank", vislam.EP_SHRANK)):
+                    epol_totals[key] += int(bool(int(prec_[i]["flags"]) & bit))
+                epol_rows.append((first + i, stamps[first + i], prec_[i].copy()))
         if a.models:
             hrec = d_hrec.cpu().numpy().view(vislam.HOMOGRAPHY_RESULT_DTYPE)
             for i in range(nb):
@@ -359,6 +379,14 @@ def main():
                 f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + "," + ",".join("%.17g" % v for v in dbl) + "\n")
         out["refined_csv"] = a.refined
         out["refined"] = eref_totals
+    if a.polished:
+        with open(a.polished, "w") as f:
+            for fi, ts, r in epol_rows:
+                ints = [r[k] for k in ("flags", "n_points", "n_set_first", "n_set_last", "n_changed", "rounds_run", "steps_run", "best_step")]
+                dbl = [r["cost_first"], r["cost0"], r["cost1"]] + list(r["R"]) + list(r["t"]) + list(r["E"])
+                f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + "," + ",".join("%.17g" % v for v in dbl) + "\n")
+        out["polished_csv"] = a.polished
+        out["polished"] = epol_totals
     if a.models:
         with open(a.models, "w") as f:
             for fi, ts, r in model_rows:

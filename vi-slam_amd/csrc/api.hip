@@ -1989,6 +1989,111 @@ extern "C" int vis_batch_essential_refine(vis_ctx* ctx, const vis_eref_params* e
     });
 }
 
+// ---- two-view polish: refine.hip k_essential_polish
+extern "C" void vis_default_epolish_params(vis_epolish_params* ep) {
+    if (!ep) return;
+    std::memset(ep, 0, sizeof(*ep));
+    ep->rounds = 3; ep->refine_iters = 5; ep->min_inliers = 8; ep->select_px = 2.0;
+}
+
+static bool epolish_params_ok(const vis_epolish_params* ep) {
+    return ep && ep->rounds >= 0 && ep->rounds <= 8 && ep->refine_iters >= 1 && ep->refine_iters <= 64 && ep->min_inliers >= 6 &&
+           std::isfinite(ep->select_px) && ep->select_px > 0.0 && !ep->reserved_ && !ep->reserved2_[0] && !ep->reserved2_[1];
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return a && b && pa < pb + nb && pb < pa + na;
+}
+
+extern "C" int vis_essential_polish(vis_ctx* ctx, const vis_epolish_params* ep, const double R[9], const double t[3], const float* p1xy,
+                                    const float* p2xy, int m, const uint8_t* mask, vis_epolish_result* out, uint8_t* mask_out,
+                                    vis_pose_result* pose_out) {
+    if (!out || !R || !t || m < 0 || (m && (!p1xy || !p2xy || !mask_out)) || !epolish_params_ok(ep)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    const size_t mc = (size_t)std::max(m, 1), mk = (mc + 3) & ~(size_t)3;
+    float *d_p1, *d_p2; int32_t* d_n; uint8_t *d_mask, *d_mask_out; PoseOut *d_pose, *d_pose_out; vis_epolish_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>(mc * 2); d_p2 = cv.take<float>(mc * 2);
+        d_pose = cv.take<PoseOut>(1); d_n = cv.take<int32_t>(1);
+        d_mask = cv.take<uint8_t>(mk); d_mask_out = cv.take<uint8_t>(mk);
+        d_out = cv.take<vis_epolish_result>(1); d_pose_out = cv.take<PoseOut>(1);
+    });
+    if (rc) return rc;
+    PoseOut o;
+    std::memset(&o, 0, sizeof(o));
+    std::memcpy(o.R, R, 72); std::memcpy(o.t, t, 24);
+    o.n_points = m;
+    const int32_t n1 = m;
+    std::vector<uint8_t> mpad;
+    if (mask && m) { mpad.assign(mk, 0); std::memcpy(mpad.data(), mask, (size_t)m); }
+    HostStage hs(ctx);
+    hs.up(d_p1, p1xy, (size_t)m * 8);
+    hs.up(d_p2, p2xy, (size_t)m * 8);
+    hs.up(d_pose, &o, sizeof(o));
+    hs.up(d_n, &n1, 4);
+    if (!mpad.empty()) hs.up(d_mask, mpad.data(), mk);
+    hs.flush_ups();
+    rc = essential_polish_run(ctx, ep, 1, (int)mc, d_pose, d_p1, d_p2, d_n, (int)mk, mask ? d_mask : nullptr, (int)mk, d_mask_out, d_out, d_pose_out);
+    if (rc) return vis_drain(ctx, rc);
+    const void* h_out = hs.down(d_out, sizeof(vis_epolish_result));
+    const void* h_mask = hs.down(d_mask_out, mk);
+    const void* h_pose = hs.down(d_pose_out, sizeof(PoseOut));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out, h_out, sizeof(*out));
+    if (m && !(out->flags & VIS_EP_NO_POSE)) std::memcpy(mask_out, h_mask, (size_t)m);    // (NO_POSE: the row is left untouched, the caller's too)
+    if (pose_out) std::memcpy(pose_out, h_pose, sizeof(*pose_out));
+    return VIS_OK;
+}
+
+extern "C" int vis_essential_polish_batch(vis_ctx* ctx, const vis_epolish_params* ep, int n, const vis_pose_result* d_pose, const float* d_p1,
+                                          const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask,
+                                          uint8_t* d_mask_out, vis_epolish_result* d_out, vis_pose_result* d_pose_out) {
+    if (!epolish_params_ok(ep) || n < 0 || max_pts < 0 || row_cap < 0 || !d_pose || !d_npts || !d_out || !d_mask_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
+    if (((uintptr_t)d_pose & 7) || ((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_pose_out & 7) || ((uintptr_t)d_npts & 3)) return VIS_E_INVALID;
+    if (ranges_overlap(d_mask, (size_t)n * row_cap, d_mask_out, (size_t)n * row_cap) ||
+        ranges_overlap(d_pose, (size_t)n * sizeof(PoseOut), d_pose_out, (size_t)n * sizeof(PoseOut))) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (row_cap < max_pts) { ctx->err = "vis_essential_polish_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return essential_polish_run(ctx, ep, n, max_pts, d_pose, d_p1, d_p2, d_npts, row_cap, d_mask, row_cap, d_mask_out, d_out, d_pose_out);
+}
+
+extern "C" int vis_batch_essential_polish(vis_ctx* ctx, const vis_epolish_params* ep, int n, int row_cap, uint8_t* d_mask_out, vis_epolish_result* d_out,
+                                          vis_pose_result* d_pose_out) {
+    if (!epolish_params_ok(ep) || !d_mask_out || !d_out || ((uintptr_t)d_out & 7) || ((uintptr_t)d_pose_out & 7) || n < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    if (!(ctx->batch->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_essential_polish: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (ctx->batch->last_n < 1 || n != ctx->batch->last_n || !(ctx->batch->last_stages & VIS_STAGE_MATCH)) return VIS_E_STATE;
+    if (row_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_essential_polish: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    // on the pose stream behind the pose stage of the last run, as vis_batch_essential_refine; the plan's mask and records are read only
+    return batch_epi(ctx, n, "vis_batch_essential_polish", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        return essential_polish_run(ctx, ep, n, pl->pose_mcap, pl->d_pose, O.p1, O.p2, d_npts, pl->pose_mcap, pl->d_mask, row_cap, d_mask_out, d_out, d_pose_out);
+    });
+}
+
+extern "C" int vis_batch_triangulate_from(vis_ctx* ctx, const vis_tri_params* tp, int n, const vis_pose_result* d_pose, int mask_cap,
+                                          const uint8_t* d_mask, int row_cap, vis_map_point* d_points, uint8_t* d_flags, vis_tri_summary* d_summary) {
+    if (!tp || !d_points || !d_flags || !d_summary || ((uintptr_t)d_points & 15) || ((uintptr_t)d_summary & 3)) return VIS_E_INVALID;
+    if (!d_pose || ((uintptr_t)d_pose & 7) || mask_cap < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_triangulate_from: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (row_cap < pl->pose_mcap) { ctx->err = "vis_batch_triangulate_from: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    if (d_mask && mask_cap != pl->pose_mcap) { ctx->err = "vis_batch_triangulate_from: mask rows must be the plan's correspondences per pair apart"; return VIS_E_CAPACITY; }
+    // vis_batch_triangulate's place on the pose stream and its reader event (it reads the same p1 / p2 of the last step's matcher-output set); the
+    // caller's records and mask were written on that stream (vis_batch_essential_polish) or are the caller's to order
+    Plan::MatchOut& O = pl->out();
+    return on_pose_stream(ctx, {0, ctx->ev_tri_done[pl->mo_cur]}, [&] {
+        const int rc = triangulate_run(ctx, tp, n, pl->pose_mcap, row_cap, d_pose, O.p1, O.p2, d_mask, d_points, d_flags, d_summary);
+        if (!rc) ctx->pose_pending = true;
+        return rc;
+    }, {&O.readers});
+}
+
 extern "C" int vis_batch_fast_thresholds(vis_ctx* ctx, int32_t* tau_next, int32_t* n_redone) {
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     Plan* pl = ctx->batch;

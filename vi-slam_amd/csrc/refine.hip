@@ -11,6 +11,9 @@
 // 5 x 5 solve on every lane alike (they hold the same sums), which is the one-lane solve without a broadcast; lane 0 writes.  Every index into a
 // matrix or a sum is a compile-time constant (pose.hip's comment on jacobi_eig has the reason).  The LDL^T solve and the Cayley map are p_solve6
 // and p_update of pnp.hip cut down to five unknowns and to the rotation: a second copy, so that pnp.o stays what it was.
+//
+// k_essential_polish (below k_essential_refine) runs the same passes in rounds, re-selecting the set under the pose each round reached, with one or
+// four waves per pair; it shares every er_* function, er_pass / er_cost through their thread count.
 #include "vis_internal.h"
 #include "ransac_lanes.h"
 #include <cmath>
@@ -81,7 +84,9 @@ DEV void er_move_t(double (&t)[3], double d0, double d1) {
 }
 
 // one pass over the row at pose (R, t): S[0..14] = the upper triangle of sum J^T J in row order, S[15..19] = sum J^T r, S[20] = sum r^2 over the
-// set; returns the number of points of the whole row that pass the inlier test under the pose
+// set; returns the number of points of the whole row that pass the inlier test under the pose.  NT threads walk the row (thread `lane` of them
+// the points i = lane mod NT): what comes back is the total of the caller's own WAVE, all there is for NT = 64
+template <int NT = 64>
 DEV int er_pass(const double (&R)[9], const double (&t)[3], const float* __restrict__ p1, const float* __restrict__ p2,
                 const uint8_t* __restrict__ mrow, int m, int lane, const ERArgs& A, double (&S)[21]) {
     double E[9], G[5][9];
@@ -89,7 +94,7 @@ DEV int er_pass(const double (&R)[9], const double (&t)[3], const float* __restr
 #pragma unroll
     for (int k = 0; k < 21; k++) S[k] = 0.0;
     int n = 0;
-    for (int i = lane; i < m; i += 64) {
+    for (int i = lane; i < m; i += NT) {
         const float2 q1 = reinterpret_cast<const float2*>(p1)[i], q2 = reinterpret_cast<const float2*>(p2)[i];
         const double a = ((double)q1.x - A.cx) * A.fx_inv, b = ((double)q1.y - A.cy) * A.fx_inv;
         const double c = ((double)q2.x - A.cx) * A.fx_inv, d = ((double)q2.y - A.cy) * A.fx_inv;
@@ -125,13 +130,14 @@ DEV int er_pass(const double (&R)[9], const double (&t)[3], const float* __restr
 }
 
 // the last pass: nothing is solved behind it, so only the cost and the count are taken -- the same operations on the same operands as er_pass
+template <int NT = 64>
 DEV int er_cost(const double (&R)[9], const double (&t)[3], const float* __restrict__ p1, const float* __restrict__ p2,
                 const uint8_t* __restrict__ mrow, int m, int lane, const ERArgs& A, double& cost) {
     double E[9];
     er_xmat(t, R, E);
     double acc = 0.0;
     int n = 0;
-    for (int i = lane; i < m; i += 64) {
+    for (int i = lane; i < m; i += NT) {
         const float2 q1 = reinterpret_cast<const float2*>(p1)[i], q2 = reinterpret_cast<const float2*>(p2)[i];
         const double a = ((double)q1.x - A.cx) * A.fx_inv, b = ((double)q1.y - A.cy) * A.fx_inv;
         const double c = ((double)q2.x - A.cx) * A.fx_inv, d = ((double)q2.y - A.cy) * A.fx_inv;
@@ -292,6 +298,213 @@ int essential_refine_run(vis_ctx* ctx, const vis_eref_params* ep, int n, int in_
     A.refine_iters = ep->refine_iters; A.min_inliers = ep->min_inliers; A.in_stride = in_stride; A.row_cap = row_cap;
     A.rec_stride = rec_stride; A.r_off = r_off; A.t_off = t_off;
     hipLaunchKernelGGL(k_essential_refine, dim3(n), dim3(64), 0, ctx->stream, A, d_start, d_p1, d_p2, d_npts, d_mask, d_out);
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+// ---- k_essential_polish: the refinement with its set re-selected under the pose it reached (include/vislam_hip.h states the algorithm and the
+// summation contract "T", tests/essential_polish_ref.py restates both).  NW waves walk a pair: thread tid of NT = 64 NW owns the points
+// i = tid mod NT, so er_pass<NT> / er_cost<NT> leave wave w with W_w, and ep_totals adds the wave totals in rising w on every thread: the same bits
+// everywhere, hence uniform control flow around the barriers.  NW = 1 is the one-wave kernel's order as it stands (W_1 = W_2 = W_3 = +0.0 and a
+// W is never -0.0); a row of at most 64 points gives the same bits under either NW.  The set lives in the caller's output mask row: byte i is
+// read and written by thread i mod NT alone, so no barrier guards it.
+struct EPArgs {
+    ERArgs er;                         // thr2 = (select_px / fx)^2; row_cap: of the input mask
+    int rounds, out_cap;               // out_cap: bytes between two rows of the output mask
+};
+
+// v[k] <- ((W_0 + W_1) + W_2) + W_3 of the wave totals v[k], n <- the sum of the waves' n, on every thread.  Two barriers: every thread of the
+// workgroup calls it, in uniform control flow
+template <int NW, int K>
+DEV void ep_totals(double (&v)[K], int& n) {
+    if constexpr (NW > 1) {
+        static_assert(NW == 4, "the contract names four wave totals");
+        __shared__ double s_w[NW][K];
+        __shared__ int s_n[NW];
+        const int tid = threadIdx.x;
+        if ((tid & 63) == 0) {
+#pragma unroll
+            for (int k = 0; k < K; k++) s_w[tid >> 6][k] = v[k];
+            s_n[tid >> 6] = n;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < K; k++) v[k] = ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k];
+        n = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
+        __syncthreads();                                           // read by every wave before the next call writes
+    }
+}
+// two integer counts of the workgroup, on every thread
+template <int NW>
+DEV void ep_counts(int& a, int& b) {
+    for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
+    if constexpr (NW > 1) {
+        __shared__ int s_c[NW][2];
+        const int tid = threadIdx.x;
+        if ((tid & 63) == 0) { s_c[tid >> 6][0] = a; s_c[tid >> 6][1] = b; }
+        __syncthreads();
+        a = 0; b = 0;
+#pragma unroll
+        for (int w = 0; w < NW; w++) { a += s_c[w][0]; b += s_c[w][1]; }
+        __syncthreads();
+    }
+}
+
+// the selection under the pose (R, t): bit 1 of byte i <- point i passes (thr2 den finite and s s <= thr2 den: er_pass's count, point for point);
+// bit 0 stays the current set.  nnew: the points that pass, nchg: the bytes the selection would flip (this thread's share of both)
+template <int NT>
+DEV void ep_select(const double (&R)[9], const double (&t)[3], const float* __restrict__ p1, const float* __restrict__ p2, uint8_t* srow, int m, int tid,
+                   const ERArgs& A, int& nnew, int& nchg) {
+    double E[9];
+    er_xmat(t, R, E);
+    nnew = 0; nchg = 0;
+    for (int i = tid; i < m; i += NT) {
+        const float2 q1 = reinterpret_cast<const float2*>(p1)[i], q2 = reinterpret_cast<const float2*>(p2)[i];
+        const double a = ((double)q1.x - A.cx) * A.fx_inv, b = ((double)q1.y - A.cy) * A.fx_inv;
+        const double c = ((double)q2.x - A.cx) * A.fx_inv, d = ((double)q2.y - A.cy) * A.fx_inv;
+        double l0, l1, m0, m1, s;
+        er_apply(E, a, b, c, d, l0, l1, m0, m1, s);
+        const double den = ((l0 * l0 + l1 * l1) + m0 * m0) + m1 * m1;
+        const double rhs = A.thr2 * den;                           // an infinite rhs would let inf <= inf pass
+        const int pass = (er_finite(rhs) && s * s <= rhs) ? 1 : 0;
+        const int cur = srow[i];
+        srow[i] = (uint8_t)(cur | (pass << 1));
+        nnew += pass; nchg += pass ^ cur;
+    }
+}
+
+static_assert(sizeof(vis_epolish_result) == 224 && offsetof(vis_epolish_result, flags) == 220, "28 words of 8 bytes, flags in the high half of the last");
+static_assert(sizeof(PoseOut) == 192 && offsetof(PoseOut, E) == 0 && offsetof(PoseOut, R) == 72 && offsetof(PoseOut, t) == 144 &&
+              offsetof(PoseOut, n_inliers) == 168, "the record k_essential_polish starts from and writes");
+
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_essential_polish(EPArgs P, const PoseOut* __restrict__ pose, const float* __restrict__ p1,
+                                                              const float* __restrict__ p2, const int32_t* __restrict__ npts,
+                                                              const uint8_t* __restrict__ mask, uint8_t* mask_out,
+                                                              vis_epolish_result* __restrict__ out, PoseOut* __restrict__ pose_out) {
+    constexpr int NT = 64 * NW;
+    const ERArgs& A = P.er;
+    const int row = blockIdx.x, tid = threadIdx.x;
+    const double* rec = reinterpret_cast<const double*>(pose + row);
+    double R[9], t[3];
+    bool any = false, fin = true;
+#pragma unroll
+    for (int k = 0; k < 9; k++) { R[k] = rec[9 + k]; any = any || R[k] != 0.0; fin = fin && er_finite(R[k]); }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { t[k] = rec[18 + k]; fin = fin && er_finite(t[k]); }
+    const double tt = dot3(t, t);
+    vis_epolish_result* o = out + row;
+    if (!any || !fin || !(tt > 0.0) || !er_finite(tt)) {           // (uniform) no pose to start from: the zero record, the input record as it is
+        if (tid < 28) reinterpret_cast<unsigned long long*>(o)[tid] = tid == 27 ? (unsigned long long)VIS_EP_NO_POSE << 32 : 0ull;
+        if (pose_out && tid < 24) reinterpret_cast<unsigned long long*>(pose_out + row)[tid] = reinterpret_cast<const unsigned long long*>(rec)[tid];
+        return;
+    }
+    const double nt = sqrt(tt);
+    t[0] = t[0] / nt; t[1] = t[1] / nt; t[2] = t[2] / nt;
+    const int m = min(max(npts[row], 0), A.in_stride);
+    const float* r1 = p1 + (size_t)row * A.in_stride * 2;
+    const float* r2 = p2 + (size_t)row * A.in_stride * 2;
+    const uint8_t* mrow = mask ? mask + (size_t)row * A.row_cap : nullptr;
+    uint8_t* srow = mask_out + (size_t)row * P.out_cap;
+    int nset = 0, nchg = 0;
+    for (int i = tid; i < m; i += NT) {                            // set 0
+        const int in = (mrow ? mrow[i] != 0 : true) ? 1 : 0;
+        srow[i] = (uint8_t)in;
+        nset += in;
+    }
+    ep_counts<NW>(nset, nchg);
+    const int nfirst = nset;
+    const bool run = nset >= A.min_inliers;
+    const int passes = run ? A.refine_iters : 0, rounds = run ? P.rounds : 0;
+    double Rb[9], tb[3], S[21];
+    double cost_first = 0.0, cost0 = 0.0, cost1 = 0.0;
+    int best = 0, steps = 0, rounds_run = 0;
+    bool shrank = false, moved = false;
+#pragma unroll
+    for (int k = 0; k < 9; k++) Rb[k] = R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) tb[k] = t[k];
+    for (int round = 0; round <= rounds; round++) {                // (uniform: every thread holds the same sums and counts)
+        if (round > 0) {
+            int nnew;
+            ep_select<NT>(Rb, tb, r1, r2, srow, m, tid, A, nnew, nchg);
+            ep_counts<NW>(nnew, nchg);
+            const bool adopt = nchg != 0 && nnew >= A.min_inliers;
+            for (int i = tid; i < m; i += NT) { const int v = srow[i]; srow[i] = (uint8_t)(adopt ? v >> 1 : v & 1); }
+            if (nchg == 0) break;
+            if (!adopt) { shrank = true; break; }
+            nset = nnew;
+#pragma unroll
+            for (int k = 0; k < 9; k++) R[k] = Rb[k];
+#pragma unroll
+            for (int k = 0; k < 3; k++) t[k] = tb[k];
+        }
+        for (int step = 0; step <= passes; step++) {               // k_essential_refine's passes over the current set
+            double cost[1];
+            int nin;
+            if (step == passes) { nin = er_cost<NT>(R, t, r1, r2, srow, m, tid, A, cost[0]); ep_totals<NW>(cost, nin); }
+            else { nin = er_pass<NT>(R, t, r1, r2, srow, m, tid, A, S); ep_totals<NW>(S, nin); cost[0] = S[20]; }
+            const bool take = step == 0 || (er_finite(cost[0]) && (!er_finite(cost1) || cost[0] < cost1));
+            if (step == 0) { cost0 = cost[0]; if (round == 0) cost_first = cost[0]; }
+            if (take) {
+                cost1 = cost[0]; best = step;
+#pragma unroll
+                for (int k = 0; k < 9; k++) Rb[k] = R[k];
+#pragma unroll
+                for (int k = 0; k < 3; k++) tb[k] = t[k];
+            }
+            if (step == passes) break;
+            double d[5];
+            if (!er_solve5(S, d)) break;
+            er_rotate(R, d[0], d[1], d[2]);
+            er_move_t(t, d[3], d[4]);
+            steps++;
+        }
+        rounds_run += run ? 1 : 0;
+        moved = moved || best > 0;
+    }
+    if (tid != 0) return;
+    vis_epolish_result r;
+    double Eb[9];
+    er_xmat(tb, Rb, Eb);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { r.R[k] = Rb[k]; r.E[k] = Eb[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; k++) r.t[k] = tb[k];
+    r.cost_first = cost_first; r.cost0 = cost0; r.cost1 = cost1;
+    r.n_points = m; r.n_set_first = nfirst; r.n_set_last = nset; r.n_changed = nchg;
+    r.rounds_run = rounds_run; r.steps_run = steps; r.best_step = best;
+    r.flags = (run ? (moved ? VIS_EP_POLISHED : VIS_EP_REJECTED) : VIS_EP_FEW) | (shrank ? VIS_EP_SHRANK : 0);
+    *o = r;
+    if (pose_out) {
+        PoseOut q = pose[row];
+#pragma unroll
+        for (int k = 0; k < 9; k++) { q.E[k] = Eb[k]; q.R[k] = Rb[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; k++) q.t[k] = tb[k];
+        q.n_inliers = nset;
+        pose_out[row] = q;
+    }
+}
+
+// ep has been validated by the entry point.  d_pose: n pose records; d_p1 / d_p2: n rows of in_stride (x, y) pixels, d_npts of them valid (clamped);
+// d_mask: rows of mask_cap >= in_stride bytes, or null; d_mask_out: rows of out_cap >= in_stride bytes; d_pose_out: n records or null.  On ctx->stream.
+int essential_polish_run(vis_ctx* ctx, const vis_epolish_params* ep, int n, int in_stride, const PoseOut* d_pose, const float* d_p1, const float* d_p2,
+                         const int32_t* d_npts, int mask_cap, const uint8_t* d_mask, int out_cap, uint8_t* d_mask_out, vis_epolish_result* d_out,
+                         PoseOut* d_pose_out) {
+    if (n <= 0) return VIS_OK;
+    EPArgs P;
+    ERArgs& A = P.er;
+    A.cx = ctx->p.cx; A.cy = ctx->p.cy; A.fx_inv = 1. / ctx->p.fx;
+    const double thr = ep->select_px / ctx->p.fx;
+    A.thr2 = thr * thr;
+    A.refine_iters = ep->refine_iters; A.min_inliers = ep->min_inliers; A.in_stride = in_stride; A.row_cap = mask_cap;
+    A.rec_stride = (int)(sizeof(PoseOut) / 8); A.r_off = 9; A.t_off = 18;
+    P.rounds = ep->rounds; P.out_cap = out_cap;
+    if (in_stride <= 64)
+        hipLaunchKernelGGL(k_essential_polish<1>, dim3(n), dim3(64), 0, ctx->stream, P, d_pose, d_p1, d_p2, d_npts, d_mask, d_mask_out, d_out, d_pose_out);
+    else
+        hipLaunchKernelGGL(k_essential_polish<4>, dim3(n), dim3(256), 0, ctx->stream, P, d_pose, d_p1, d_p2, d_npts, d_mask, d_mask_out, d_out, d_pose_out);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

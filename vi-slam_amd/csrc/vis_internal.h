@@ -513,6 +513,11 @@ int pnp_link_run(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d
 // doubles with R at r_off and t at t_off; d_mask: rows of row_cap >= in_stride bytes, or null
 int essential_refine_run(vis_ctx* ctx, const vis_eref_params* ep, int n, int in_stride, const double* d_start, int rec_stride, int r_off, int t_off,
                          const float* d_p1, const float* d_p2, const int32_t* d_npts, int row_cap, const uint8_t* d_mask, vis_eref_result* d_out);
+// refine.hip: k_essential_polish on ctx->stream (one wave per pair for in_stride <= 64, else four); ep validated by the caller; d_mask: rows of mask_cap
+// bytes or null; d_mask_out: rows of out_cap bytes; d_pose_out: n records or null
+int essential_polish_run(vis_ctx* ctx, const vis_epolish_params* ep, int n, int in_stride, const PoseOut* d_pose, const float* d_p1, const float* d_p2,
+                         const int32_t* d_npts, int mask_cap, const uint8_t* d_mask, int out_cap, uint8_t* d_mask_out, vis_epolish_result* d_out,
+                         PoseOut* d_pose_out);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

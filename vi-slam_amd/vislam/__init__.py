@@ -14,6 +14,8 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.pnp_ransac / pnp_batch / batch_pnp   the pose of a frame against map points: P3P RANSAC + Gauss-Newton refinement (beyond the reference)
   Context.essential_batch                             <-> essential RANSAC + recoverPose on rows that already sit in device memory
   Context.essential_refine / essential_refine_batch / batch_essential_refine   Gauss-Newton refinement of the two-view pose (beyond the reference)
+  Context.essential_polish / essential_polish_batch / batch_essential_polish   the refinement with its inlier set re-selected (beyond the reference)
+  Context.batch_triangulate_from                      batch_triangulate from caller pose records and mask rows (the polished ones)
   Context.filter_keypoints (_batch, batch_...)        <-> VISystem::FilterKeypoints  (src/VISystem.cpp:542-610)
 
 There is NO CPU fallback: if the HIP library is missing, importing this module raises.
@@ -237,6 +239,26 @@ assert C.sizeof(EssentialRefineParams) == 16 and EREF_RESULT_DTYPE.itemsize == C
 ER_REFINED, ER_REJECTED, ER_FEW, ER_NO_POSE = 1, 2, 4, 8
 
 
+class EssentialPolishParams(C.Structure):
+    """vis_epolish_params: the knobs of the two-view polish (vis_default_epolish_params: 3, 5, 8, 2.0)"""
+    _fields_ = [("rounds", C.c_int32), ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("reserved_", C.c_int32), ("select_px", C.c_double),
+                ("reserved2_", C.c_int32 * 2)]
+
+
+class EssentialPolishResult(C.Structure):
+    """vis_epolish_result: the reported pose (|t| = 1), its E = [t]x R, the start's cost, the last round's costs, the sets' sizes and the counts"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("E", C.c_double * 9), ("cost_first", C.c_double), ("cost0", C.c_double),
+                ("cost1", C.c_double), ("n_points", C.c_int32), ("n_set_first", C.c_int32), ("n_set_last", C.c_int32), ("n_changed", C.c_int32),
+                ("rounds_run", C.c_int32), ("steps_run", C.c_int32), ("best_step", C.c_int32), ("flags", C.c_int32)]
+
+
+EPOLISH_RESULT_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("E", "<f8", (9,)), ("cost_first", "<f8"), ("cost0", "<f8"), ("cost1", "<f8"),
+                                 ("n_points", "<i4"), ("n_set_first", "<i4"), ("n_set_last", "<i4"), ("n_changed", "<i4"), ("rounds_run", "<i4"),
+                                 ("steps_run", "<i4"), ("best_step", "<i4"), ("flags", "<i4")])
+assert C.sizeof(EssentialPolishParams) == 32 and EPOLISH_RESULT_DTYPE.itemsize == C.sizeof(EssentialPolishResult) == 224
+EP_POLISHED, EP_REJECTED, EP_FEW, EP_NO_POSE, EP_SHRANK = 1, 2, 4, 8, 16
+
+
 class KltParams(C.Structure):
     """vis_klt_params: the knobs of the pyramidal KLT tracker (vis_default_klt_params: 7, 3, 0, 10, 0.01, 0.1, 0, 0, 3)"""
     _fields_ = [("win_radius", C.c_int32), ("first_level", C.c_int32), ("last_level", C.c_int32), ("max_iters", C.c_int32),
@@ -296,6 +318,7 @@ ABI_SYMBOLS = [
     "vis_default_hpose_params", "vis_homography_pose", "vis_homography_pose_batch", "vis_batch_homography_pose",
     "vis_default_pnp_params", "vis_pnp_ransac", "vis_pnp_batch", "vis_batch_pnp",
     "vis_essential_batch", "vis_default_eref_params", "vis_essential_refine", "vis_essential_refine_batch", "vis_batch_essential_refine",
+    "vis_default_epolish_params", "vis_essential_polish", "vis_essential_polish_batch", "vis_batch_essential_polish", "vis_batch_triangulate_from",
     "vis_default_align_weights", "vis_set_align_weights", "vis_get_align_weights",
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
@@ -394,6 +417,14 @@ def _load():
         lib.vis_essential_refine.argtypes = [vp, epp, vp, vp, vp, vp, ci, vp, vp]
         lib.vis_essential_refine_batch.argtypes = [vp, epp, ci, vp, vp, vp, vp, ci, ci, vp, vp]
         lib.vis_batch_essential_refine.argtypes = [vp, epp, ci, vp]
+    if hasattr(lib, "vis_essential_polish_batch"):      # (absent from older A/B builds)
+        eqp = C.POINTER(EssentialPolishParams)
+        lib.vis_default_epolish_params.argtypes = [eqp]
+        lib.vis_default_epolish_params.restype = None
+        lib.vis_essential_polish.argtypes = [vp, eqp, vp, vp, vp, vp, ci, vp, vp, vp, vp]
+        lib.vis_essential_polish_batch.argtypes = [vp, eqp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]
+        lib.vis_batch_essential_polish.argtypes = [vp, eqp, ci, ci, vp, vp, vp]
+        lib.vis_batch_triangulate_from.argtypes = [vp, C.POINTER(TriParams), ci, vp, ci, vp, ci, vp, vp, vp]
     if hasattr(lib, "vis_batch_homography_pose"):       # (absent from older A/B builds)
         hqp = C.POINTER(HposeParams)
         lib.vis_default_hpose_params.argtypes = [hqp]
@@ -529,6 +560,12 @@ def default_pnp_params():
 def default_eref_params():
     ep = EssentialRefineParams()
     lib.vis_default_eref_params(C.byref(ep))
+    return ep
+
+
+def default_epolish_params():
+    ep = EssentialPolishParams()
+    lib.vis_default_epolish_params(C.byref(ep))
     return ep
 
 
@@ -1251,6 +1288,48 @@ class Context:
         d_out is in use until batch_sync().  The refined pose is not written back into the plan"""
         ep = default_eref_params() if ep is None else ep
         self._chk(lib.vis_batch_essential_refine(self._h, C.byref(ep), n, C.c_void_p(d_out_ptr) if d_out_ptr else None), "vis_batch_essential_refine")
+
+    def essential_polish(self, R, t, p1, p2, mask=None, ep=None):
+        """(EPOLISH_RESULT_DTYPE element, mask uint8[m], POSE_RESULT_DTYPE element): the refinement of (R, t) with its set re-selected under the
+        pose it reached, the set the reported pose was fitted on, and the pose as a record batch_triangulate_from reads"""
+        ep = default_epolish_params() if ep is None else ep
+        R = np.ascontiguousarray(R, np.float64).reshape(9)
+        t = np.ascontiguousarray(t, np.float64).reshape(3)
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        assert len(p1) == len(p2)
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert mask is None or len(mask) >= len(p1)
+        out, pose = np.zeros(1, EPOLISH_RESULT_DTYPE), np.zeros(1, POSE_RESULT_DTYPE)
+        mo = np.zeros(max(len(p1), 1), np.uint8)
+        self._chk(lib.vis_essential_polish(self._h, C.byref(ep), _ptr(R), _ptr(t), _ptr(p1), _ptr(p2), len(p1), _ptr(mask), _ptr(out), _ptr(mo),
+                                           _ptr(pose)), "vis_essential_polish")
+        return out[0], mo[:len(p1)], pose[0]
+
+    def essential_polish_batch(self, n, d_pose_ptr, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_mask_out_ptr, d_out_ptr,
+                               d_pose_out_ptr=0, ep=None):
+        """queue the polish of n pose records on the context's stream (raw DEVICE pointers; 0 / None = NULL for d_mask and d_pose_out):
+        essential_refine_batch's buffers, n rows of row_cap output mask bytes, n EPOLISH_RESULT_DTYPE and n POSE_RESULT_DTYPE records"""
+        ep = default_epolish_params() if ep is None else ep
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_essential_polish_batch(self._h, C.byref(ep), n, v(d_pose_ptr), v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, row_cap,
+                                                 v(d_mask_ptr), v(d_mask_out_ptr), v(d_out_ptr), v(d_pose_out_ptr)), "vis_essential_polish_batch")
+
+    def batch_essential_polish(self, n, row_cap, d_mask_out_ptr, d_out_ptr, d_pose_out_ptr=0, ep=None):
+        """the same on the pairs of the last batch_run(STAGE_ALL), from the pose stage's records and inlier mask (read only), on the pose stream
+        behind it; the buffers are in use until batch_sync().  Nothing is written into the plan: batch_triangulate_from reads the outputs"""
+        ep = default_epolish_params() if ep is None else ep
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_essential_polish(self._h, C.byref(ep), n, row_cap, v(d_mask_out_ptr), v(d_out_ptr), v(d_pose_out_ptr)),
+                  "vis_batch_essential_polish")
+
+    def batch_triangulate_from(self, n, d_pose_ptr, mask_cap, d_mask_ptr, row_cap, d_points_ptr, d_flags_ptr, d_summary_ptr, tp=None):
+        """batch_triangulate with the pose records and the mask rows (mask_cap = the plan's correspondences per pair; 0 / None = no mask) taken
+        from caller device buffers, e.g. what batch_essential_polish wrote"""
+        tp = default_tri_params() if tp is None else tp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_triangulate_from(self._h, C.byref(tp), n, v(d_pose_ptr), mask_cap, v(d_mask_ptr), row_cap, v(d_points_ptr),
+                                                 v(d_flags_ptr), v(d_summary_ptr)), "vis_batch_triangulate_from")
 
     # -- batched stream path ----------------------------------------------------------------------------------
     def batch_plan(self, w, h, stride, max_frames):
