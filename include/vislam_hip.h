@@ -639,7 +639,8 @@ int  vis_batch_homography(vis_ctx* ctx, const vis_homography_params* hp, int n, 
  * piecewise planar environment", 1988; ORB-SLAM section IV's ReconstructH -- both restated from the papers; the reference has neither).  For a
  * pair flagged VIS_MODEL_HOMOGRAPHY the (R, t) of vis_pose_result is undetermined; this turns the pair's H into (R, t / d, n): x2 = R x1 + t
  * for points of the plane n . X = d of the first camera, t in units of d -- NOT of unit norm like vis_pose_result's.  Accuracy is that of the
- * unrefitted four-point H of vis_*_homography.
+ * H it is given: the unrefitted four-point H of vis_*_homography, or that H refined over its inliers by vis_*_homography_polish (below), whose
+ * record and mask this call reads unchanged.
  * All arithmetic is double, nothing is contracted, the only operations are + - * / sqrt; dot3(a, b) = a0 b0 + a1 b1 + a2 b2 and every sum of a
  * 3 x 3 product run left to right from 0 (tests/homography_pose_ref.py restates every step in this order, bit for bit).
  * Input: the record's H and best_iter, the pair's correspondences in pixels, an optional mask (the one vis_*_homography wrote; NULL = every
@@ -707,6 +708,91 @@ int  vis_homography_pose_batch(vis_ctx* ctx, const vis_hpose_params* hq, int n, 
  * plan's correspondences per pair, then VIS_E_STATE without context / plan / match stage or when n differs. */
 int  vis_batch_homography_pose(vis_ctx* ctx, const vis_hpose_params* hq, int n, const vis_homography_result* d_h, int row_cap,
                                const uint8_t* d_mask, const float* d_rot, vis_hpose_result* d_out);
+
+/* ---- homography polish: the RANSAC winner refined over its inliers, the set RE-SELECTED under the H it reached (OpenCV's findHomography refines
+ * the same one-sided cost behind its RANSAC; the reference has no homography).  The call sits between vis_*_homography and vis_*_homography_pose:
+ * it reads the record and mask the first wrote and writes a record and a mask the second reads unchanged, so homography -> polish ->
+ * homography_pose chains on one stream with no host round trip (tests/homography_polish_ref.py restates every step, bit for bit).
+ * All arithmetic is double, nothing is contracted, the only operations are + - * / sqrt and comparisons; every sum written with parentheses runs
+ * in that order.  Coordinates: the pose stage's, x = ((double)u - cx) * (1 / fx), y likewise; (x, y) of the first image, (x2, y2) of the second.
+ * t_sel = select_chi2 * (sigma_px * (1 / fx))^2 once on the host: with the defaults it is vis_*_homography's t_h.
+ * Start: the record's H.  best_iter < 0, an entry that is not finite, or ss = H0 H0 + ... + H8 H8 (from k = 0, left to right) that is not > 0 or
+ * not finite gives the ZERO record with flags = VIS_HPOL_NO_MODEL -- then the output mask row is left untouched and h_out receives the input
+ * record unchanged.  Otherwise H <- H / sqrt(ss), entry by entry.
+ * Per point under the current H:  U = (H0 x + H1 y) + H2, V = (H3 x + H4 y) + H5, w = (H6 x + H7 y) + H8;  iw = 1 / w, u = U iw, v = V iw;
+ * ru = u - x2, rv = v - y2 (the forward transfer error);  a = x iw, b = y iw;  q = (a, b, iw), j0 = (-(a u), -(b u), -(iw u)),
+ * j1 = (-(a v), -(b v), -(iw v)).  The Jacobian rows are J0 = (q, 0, j0) and J1 = (0, q, j1) in the nine entries of H.  A point outside the
+ * set, or whose iw, u, v, ru or rv is not finite, adds +0.0 to every sum (ru, rv: a caller's mask may put a correspondence whose second point
+ * is NaN or infinite into set 0; its NaN would reach the right-hand side through a finite Jacobian and the step would be NaN).
+ * Sums, each under the summation contract "T" of vis_essential_polish (below: 256 partial sums over i mod 256, four wave totals added in rising
+ * order), exactly as stated there.  Only the structurally non-zero products are formed -- a product with a zero of J0 or J1 is not:
+ *   rows / columns 0 ... 2:  A_ab = sum q_a q_b (a <= b);  rows / columns 3 ... 5: the same six sums;  rows 0 ... 2 x columns 3 ... 5: +0.0;
+ *   rows 0 ... 2 x columns 6 ... 8:  sum q_a j0_b;  rows 3 ... 5 x columns 6 ... 8:  sum q_a j1_b;
+ *   rows / columns 6 ... 8:  sum j0_a j0_b + j1_a j1_b (a <= b);
+ *   g_a = sum q_a ru (a = 0 ... 2), g_3+a = sum q_a rv, g_6+a = sum j0_a ru + j1_a rv;  the cost = sum ru ru + rv rv.
+ * Gauge: p = the index of the largest |H_k| of the current iterate, the lowest on a tie (k rising from 0, replaced on > only).  Row and column p
+ * are struck; the eight remaining unknowns keep their rising order.
+ * Step: d = -A^-1 g by LDL^T without pivoting, exactly the PnP refinement's solve written for eight unknowns; a pivot that is not > 0 or not
+ * finite ends the round's iteration (the iterates costed so far still compete).  Update: H_k <- H_k + d for k != p, then H <- H / sqrt(ss) as at
+ * the start.
+ * Passes, rounds and selection are vis_essential_polish's (below), word for word -- set 0 from the input mask's non-zero bytes (every point
+ * without a mask), written to the output mask row as 0 / 1 where the current set lives from then on; n_set_first < min_inliers: VIS_HPOL_FEW, the
+ * start reported with cost_first = cost0 = cost1; passes 0 ... refine_iters per round, the round reporting its iterate of least finite cost, the
+ * earliest on a tie, costs compared within a round only; rounds 0 ... rounds with (1) the new set, (2) n_changed == 0: stop, (3) fewer than
+ * min_inliers: stop with VIS_HPOL_SHRANK, (4) adopt -- with this re-selection test: G = adj(H) of the iterate the last round reported; the point
+ * passes vis_*_homography's two-sided division-free transfer test at t_sel, e12 <= t_sel (w w) forward under H and backward under G, AND
+ * t_sel (w w) is finite in both directions (inf <= inf would pass); a NaN fails.
+ * Record: H = the last round's reported iterate, every entry negated when det = (H0 G0 + H1 G3) + H2 G6 < 0 (G = adj of it): unit Frobenius
+ * norm, det >= 0, like vis_homography_result's.  cost_first, cost0, cost1, the counts and the flags have the meanings of vis_epolish_result's.
+ * h_out (optional): the input vis_homography_result with H replaced by the reported H and n_inliers by n_set_last.  score_h, score_e, model,
+ * best_iter, n_degenerate and n_inliers_e stay the input's: the scores and the H-or-E decision are those of the RANSAC winner, deliberately --
+ * re-scoring under the refined H is not built.
+ * The input record and the input mask are never modified.  Two runs are byte-identical.  Nothing is written into a plan. */
+enum { VIS_HPOL_POLISHED = 1, VIS_HPOL_REJECTED = 2, VIS_HPOL_FEW = 4, VIS_HPOL_NO_MODEL = 8, VIS_HPOL_SHRANK = 16 };
+typedef struct vis_hpolish_params {      /* 32 bytes; the defaults are this library's own */
+    int32_t rounds;                      /* 3      re-selections, 0 ... 8; 0 = the refinement over set 0 alone */
+    int32_t refine_iters;                /* 5      Gauss-Newton steps per round, 1 ... 64 */
+    int32_t min_inliers;                 /* 8      a smaller set is not refined; refused below 5 */
+    int32_t reserved_;                   /* 0 */
+    double  select_chi2;                 /* 5.991  the re-selection's threshold: vis_homography_params.chi2_h; finite and > 0 */
+    double  sigma_px;                    /* 1.0    finite and > 0 */
+} vis_hpolish_params;
+typedef struct vis_hpolish_result {      /* 128 bytes, 8-byte aligned, no implicit padding */
+    double  H[9];                        /* the reported H: row-major, x2 ~ H x1; unit Frobenius norm, det >= 0 */
+    double  cost_first;                  /* iterate 0 of round 0: the start's cost over set 0 */
+    double  cost0, cost1;                /* of the last round run: its iterate 0 and its reported iterate, over that round's set */
+    int32_t n_points, n_set_first, n_set_last;
+    int32_t n_changed;
+    int32_t rounds_run, steps_run, best_step;
+    int32_t flags;                       /* VIS_HPOL_* */
+} vis_hpolish_result;
+void vis_default_hpolish_params(vis_hpolish_params* hp);
+/* One pair, HOST pointers; blocks once like the other single-frame entry points.  h: the pair's homography record; p1xy / p2xy: m x 2 floats
+ * (pixels); mask: m bytes or NULL; mask_out: m bytes; h_out: one record or NULL.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL out or h, m < 0, NULL points or a NULL mask_out with m > 0, hp NULL, hp.rounds < 0 or > 8,
+ * hp.refine_iters < 1 or > 64, hp.min_inliers < 5, a select_chi2 or sigma_px that is not finite and positive, a reserved field that is not 0.
+ * Then VIS_E_STATE without a context.  A refused call writes nothing. */
+int  vis_homography_polish(vis_ctx* ctx, const vis_hpolish_params* hp, const vis_homography_result* h, const float* p1xy, const float* p2xy, int m,
+                           const uint8_t* mask, vis_hpolish_result* out, uint8_t* mask_out, vis_homography_result* h_out);
+/* DEVICE pointers, asynchronous on the context's stream: vis_homography_pose_batch's rows -- d_h: n records, d_mask: n rows of row_cap bytes or
+ * NULL -- and d_mask_out: n rows of row_cap bytes (required), d_out: n records, d_h_out: n records or NULL.  One kernel in two shapes, chosen per
+ * LAUNCH and without effect on a bit: one wave per pair when max_pts <= 64, four waves otherwise.  Rows may be as long as memory allows.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_homography_polish refuses of hp, a NULL or misaligned pointer (8 bytes for records and points,
+ * 4 for counts; d_mask and d_h_out may be NULL), a negative size, d_mask_out overlapping d_mask or d_h_out overlapping d_h.  Then VIS_E_STATE
+ * without a context.  Then VIS_E_CAPACITY when row_cap < max_pts. */
+int  vis_homography_polish_batch(vis_ctx* ctx, const vis_hpolish_params* hp, int n, const vis_homography_result* d_h, const float* d_p1,
+                                 const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask, uint8_t* d_mask_out,
+                                 vis_hpolish_result* d_out, vis_homography_result* d_h_out);
+/* The same on the pairs of the last vis_batch_run, with d_h and d_mask (n rows of mask_cap bytes, or NULL) as vis_batch_homography wrote them for
+ * the same run -- caller buffers, like vis_batch_homography_pose's -- on the POSE stream behind that call, overlapping the next vis_batch_run; the
+ * caller's buffers are in use until vis_batch_sync.  d_mask_out: n rows of row_cap bytes.  A frame without a pair (its record has best_iter =
+ * -1) gets the NO_MODEL record.  vis_batch_homography_pose fed d_h_out and d_mask_out (at row_cap) then decomposes the polished H.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_homography_polish refuses of hp, a NULL d_h, d_mask_out or d_out, a misaligned (8 bytes) d_h,
+ * d_out or d_h_out, n < 0, mask_cap < 0 or row_cap < 0, d_mask_out overlapping d_mask or d_h_out overlapping d_h.  Then VIS_E_STATE without
+ * context / plan / match stage, or when n differs.  Then VIS_E_CAPACITY when row_cap, or with a mask mask_cap, is below the plan's
+ * correspondences per pair. */
+int  vis_batch_homography_polish(vis_ctx* ctx, const vis_hpolish_params* hp, int n, const vis_homography_result* d_h, int mask_cap,
+                                 const uint8_t* d_mask, int row_cap, uint8_t* d_mask_out, vis_hpolish_result* d_out, vis_homography_result* d_h_out);
 
 /* ---- PnP: the pose of a frame against map points, P3P RANSAC and Gauss-Newton refinement (Grunert 1841 as restated by Haralick, Lee,
  * Ottenberg, Noelle: "Review and analysis of solutions of the three point perspective pose estimation problem", 1994; the reference has

@@ -26,6 +26,9 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              hint, default parameters, the draws of --models): one row per pair -- frame index, timestamp, kind (none / rotation / plane), flags
              (VIS_HPF_*), solution, second, n_points, n_tested, n_parallax, n_good (four), d1, d2, d3, t_norm, then R (nine, row-major), t (in
              units of the plane distance), n of the chosen candidate and R, t, n of the second; the JSON line carries the count of each kind.
+  --hpolish: with --hposes, every pair's homography is polished over its inliers before it is decomposed (vis_batch_homography_polish between
+             the two calls, default parameters; the pose call reads the polished record and mask): each row of the CSV gains a last column, the
+             polish's flags (VIS_HPOL_*), and the JSON line carries the count of each flag.
   --pnp out.csv: the pose of every frame against the map points of its keyframe's own pair (vis_batch_triangulate, then vis_batch_pnp with
              VIS_MP_KEPT, default parameters, 200 x 3 draws of default_rng(7)): one row per frame -- frame index, timestamp, q, p, n_linked,
              link flags (VIS_PNPL_*), scale, then n_inliers, n_inliers_refined, best_iter, best_root, flags (VIS_PNP_*), cost0, cost1, R (nine,
@@ -100,6 +103,7 @@ def main():
     ap.add_argument("--points", default=None, metavar="CSV", help="write the triangulated map points of every pair here")
     ap.add_argument("--models", default=None, metavar="CSV", help="write the H-or-E model choice of every pair here")
     ap.add_argument("--hposes", default=None, metavar="CSV", help="write the pose of every pair's homography (chosen and second candidate) here")
+    ap.add_argument("--hpolish", action="store_true", help="with --hposes: polish every pair's homography over its inliers before it is decomposed")
     ap.add_argument("--pnp", default=None, metavar="CSV", help="write every frame's pose against its keyframe's map points here")
     ap.add_argument("--refined", default=None, metavar="CSV", help="write every frame's refined two-view pose here")
     ap.add_argument("--polished", default=None, metavar="CSV", help="write every frame's polished two-view pose here")
@@ -110,6 +114,8 @@ def main():
     a = ap.parse_args()
     if a.roi and not a.rectify:
         raise SystemExit("--roi needs --rectify")
+    if a.hpolish and not a.hposes:
+        raise SystemExit("--hpolish needs --hposes")
 
     names = vislam.image_list(a.directory)[:a.frames]
     if len(names) < 2:
@@ -202,6 +208,12 @@ def main():
         d_hmask = torch.empty(B * hcap, dtype=torch.uint8, device="cuda")
         d_hpose = torch.empty(B * vislam.HPOSE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         hpose_rows, hpose_totals = [], [0, 0, 0]
+    if a.hpolish:
+        hlp = vislam.default_hpolish_params()
+        d_hpol = torch.empty(B * vislam.HPOLISH_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_hrec2 = torch.empty(B * vislam.HOMOGRAPHY_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_hmask2 = torch.empty(B * hcap, dtype=torch.uint8, device="cuda")
+        hpol_totals = dict(polished=0, rejected=0, few=0, no_model=0, shrank=0)
     torch.cuda.synchronize()
     if a.rectify:
         feed = None
@@ -245,7 +257,10 @@ def main():
             ctx.batch_essential_polish(nb, pcap, d_pmask.data_ptr(), d_epol.data_ptr(), 0, epp)
         if a.models or a.hposes:
             ctx.batch_homography(nb, d_hdraws.data_ptr(), hcap, d_hmask.data_ptr() if a.hposes else 0, d_hrec.data_ptr(), hp)
-        if a.hposes:
+        if a.hpolish:                                        # homography -> polish -> homography_pose, queued on the pose stream: no round trip
+            ctx.batch_homography_polish(nb, d_hrec.data_ptr(), hcap, d_hmask.data_ptr(), hcap, d_hmask2.data_ptr(), d_hpol.data_ptr(), d_hrec2.data_ptr(), hlp)
+            ctx.batch_homography_pose(nb, d_hrec2.data_ptr(), hcap, d_hmask2.data_ptr(), 0, d_hpose.data_ptr(), hq)
+        elif a.hposes:
             ctx.batch_homography_pose(nb, d_hrec.data_ptr(), hcap, d_hmask.data_ptr(), 0, d_hpose.data_ptr(), hq)
         if a.klt:
             ctx.batch_klt(d, nb, kcap, d_krec.data_ptr(), d_kpair.data_ptr(), kp=kltp)
@@ -293,10 +308,15 @@ def main():
                     model_rows.append((first + i, stamps[first + i], hrec[i].copy()))
         if a.hposes:
             hpose = d_hpose.cpu().numpy().view(vislam.HPOSE_RESULT_DTYPE)
+            hpol = d_hpol.cpu().numpy().view(vislam.HPOLISH_RESULT_DTYPE) if a.hpolish else None
             for i in range(nb):
+                if hpol is not None:
+                    for key, bit in (("polished", vislam.HPOL_POLISHED), ("rejected", vislam.HPOL_REJECTED), ("few", vislam.HPOL_FEW),
+                                     ("no_model", vislam.HPOL_NO_MODEL), ("shrank", vislam.HPOL_SHRANK)):
+                        hpol_totals[key] += int(bool(int(hpol[i]["flags"]) & bit))
                 if int(hpose[i]["kind"]) != vislam.HP_NONE:
                     hpose_totals[int(hpose[i]["kind"])] += 1
-                    hpose_rows.append((first + i, stamps[first + i], hpose[i].copy()))
+                    hpose_rows.append((first + i, stamps[first + i], hpose[i].copy(), None if hpol is None else int(hpol[i]["flags"])))
         if a.klt:
             krec = d_krec.cpu().numpy().view(vislam.KLT_POINT_DTYPE).reshape(B, kcap)
             kpair, klinks = d_kpair.cpu().numpy().view(vislam.KLT_PAIR_DTYPE), ctx.batch_get_keyframes()
@@ -404,13 +424,15 @@ def main():
         out["klt"] = klt_totals
     if a.hposes:
         with open(a.hposes, "w") as f:
-            for fi, ts, r in hpose_rows:
+            for fi, ts, r, pflags in hpose_rows:
                 ints = [r[k] for k in ("flags", "solution", "second", "n_points", "n_tested", "n_parallax")] + list(r["n_good"])
                 dbl = list(r["sv"]) + [r["t_norm"]] + [v for k in ("R", "t", "n", "R2", "t2", "n2") for v in r[k]]
                 f.write("%d,%d,%s," % (fi, ts, vislam.HP_KIND_NAMES[int(r["kind"])]) + ",".join("%d" % v for v in ints) + "," +
-                        ",".join("%.17g" % v for v in dbl) + "\n")
+                        ",".join("%.17g" % v for v in dbl) + ("" if pflags is None else ",%d" % pflags) + "\n")
         out["hposes_csv"] = a.hposes
         out["hposes"] = dict(zip(vislam.HP_KIND_NAMES, hpose_totals))
+        if a.hpolish:
+            out["hpolish"] = hpol_totals
     if feed:
         feed.close()
     else:

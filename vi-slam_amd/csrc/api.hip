@@ -2074,6 +2074,89 @@ extern "C" int vis_batch_essential_polish(vis_ctx* ctx, const vis_epolish_params
     });
 }
 
+// ---- homography polish: homography_polish.hip k_homography_polish
+extern "C" void vis_default_hpolish_params(vis_hpolish_params* hp) {
+    if (!hp) return;
+    std::memset(hp, 0, sizeof(*hp));
+    hp->rounds = 3; hp->refine_iters = 5; hp->min_inliers = 8; hp->select_chi2 = 5.991; hp->sigma_px = 1.0;
+}
+
+static bool hpolish_params_ok(const vis_hpolish_params* hp) {
+    auto pos = [](double v) { return std::isfinite(v) && v > 0.0; };
+    return hp && hp->rounds >= 0 && hp->rounds <= 8 && hp->refine_iters >= 1 && hp->refine_iters <= 64 && hp->min_inliers >= 5 &&
+           pos(hp->select_chi2) && pos(hp->sigma_px) && !hp->reserved_;
+}
+
+extern "C" int vis_homography_polish(vis_ctx* ctx, const vis_hpolish_params* hp, const vis_homography_result* h, const float* p1xy,
+                                     const float* p2xy, int m, const uint8_t* mask, vis_hpolish_result* out, uint8_t* mask_out,
+                                     vis_homography_result* h_out) {
+    if (!out || !h || m < 0 || (m && (!p1xy || !p2xy || !mask_out)) || !hpolish_params_ok(hp)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    const size_t mc = (size_t)std::max(m, 1), mk = (mc + 3) & ~(size_t)3;
+    float *d_p1, *d_p2; int32_t* d_n; uint8_t *d_mask, *d_mask_out; vis_homography_result *d_h, *d_h_out; vis_hpolish_result* d_out;
+    int rc = vis_carve(ctx, [&](Carver& cv) {
+        d_p1 = cv.take<float>(mc * 2); d_p2 = cv.take<float>(mc * 2);
+        d_h = cv.take<vis_homography_result>(1); d_n = cv.take<int32_t>(1);
+        d_mask = cv.take<uint8_t>(mk); d_mask_out = cv.take<uint8_t>(mk);
+        d_out = cv.take<vis_hpolish_result>(1); d_h_out = cv.take<vis_homography_result>(1);
+    });
+    if (rc) return rc;
+    const int32_t n1 = m;
+    std::vector<uint8_t> mpad;
+    if (mask && m) { mpad.assign(mk, 0); std::memcpy(mpad.data(), mask, (size_t)m); }
+    HostStage hs(ctx);
+    hs.up(d_p1, p1xy, (size_t)m * 8);
+    hs.up(d_p2, p2xy, (size_t)m * 8);
+    hs.up(d_h, h, sizeof(*h));
+    hs.up(d_n, &n1, 4);
+    if (!mpad.empty()) hs.up(d_mask, mpad.data(), mk);
+    hs.flush_ups();
+    rc = homography_polish_run(ctx, hp, 1, (int)mc, d_h, d_p1, d_p2, d_n, (int)mk, mask ? d_mask : nullptr, (int)mk, d_mask_out, d_out, d_h_out);
+    if (rc) return vis_drain(ctx, rc);
+    const void* r_out = hs.down(d_out, sizeof(vis_hpolish_result));
+    const void* r_mask = hs.down(d_mask_out, mk);
+    const void* r_h = hs.down(d_h_out, sizeof(vis_homography_result));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(out, r_out, sizeof(*out));
+    if (m && !(out->flags & VIS_HPOL_NO_MODEL)) std::memcpy(mask_out, r_mask, (size_t)m);    // (NO_MODEL: the row is left untouched, the caller's too)
+    if (h_out) std::memcpy(h_out, r_h, sizeof(*h_out));
+    return VIS_OK;
+}
+
+extern "C" int vis_homography_polish_batch(vis_ctx* ctx, const vis_hpolish_params* hp, int n, const vis_homography_result* d_h, const float* d_p1,
+                                           const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap, const uint8_t* d_mask,
+                                           uint8_t* d_mask_out, vis_hpolish_result* d_out, vis_homography_result* d_h_out) {
+    if (!hpolish_params_ok(hp) || n < 0 || max_pts < 0 || row_cap < 0 || !d_h || !d_npts || !d_out || !d_mask_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
+    if (((uintptr_t)d_h & 7) || ((uintptr_t)d_p1 & 7) || ((uintptr_t)d_p2 & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_h_out & 7) || ((uintptr_t)d_npts & 3)) return VIS_E_INVALID;
+    if (ranges_overlap(d_mask, (size_t)n * row_cap, d_mask_out, (size_t)n * row_cap) ||
+        ranges_overlap(d_h, (size_t)n * sizeof(vis_homography_result), d_h_out, (size_t)n * sizeof(vis_homography_result))) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (row_cap < max_pts) { ctx->err = "vis_homography_polish_batch: row_cap is smaller than max_pts"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return homography_polish_run(ctx, hp, n, max_pts, d_h, d_p1, d_p2, d_npts, row_cap, d_mask, row_cap, d_mask_out, d_out, d_h_out);
+}
+
+extern "C" int vis_batch_homography_polish(vis_ctx* ctx, const vis_hpolish_params* hp, int n, const vis_homography_result* d_h, int mask_cap,
+                                           const uint8_t* d_mask, int row_cap, uint8_t* d_mask_out, vis_hpolish_result* d_out,
+                                           vis_homography_result* d_h_out) {
+    if (!hpolish_params_ok(hp) || !d_h || !d_mask_out || !d_out || ((uintptr_t)d_h & 7) || ((uintptr_t)d_out & 7) || ((uintptr_t)d_h_out & 7) ||
+        n < 0 || mask_cap < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (ranges_overlap(d_mask, (size_t)n * mask_cap, d_mask_out, (size_t)n * row_cap) ||
+        ranges_overlap(d_h, (size_t)n * sizeof(vis_homography_result), d_h_out, (size_t)n * sizeof(vis_homography_result))) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    if (ctx->batch->last_n < 1 || n != ctx->batch->last_n || !(ctx->batch->last_stages & VIS_STAGE_MATCH)) return VIS_E_STATE;
+    if (row_cap < ctx->batch->pose_mcap || (d_mask && mask_cap < ctx->batch->pose_mcap)) {
+        ctx->err = "vis_batch_homography_polish: row_cap or mask_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY;
+    }
+    // on the pose stream behind vis_batch_homography of the same run (batch_epi queues there): d_h and d_mask are complete when the kernel reads
+    // them, and a vis_batch_homography_pose queued behind this call finds d_h_out and d_mask_out complete
+    return batch_epi(ctx, n, "vis_batch_homography_polish", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
+        return homography_polish_run(ctx, hp, n, pl->pose_mcap, d_h, O.p1, O.p2, d_npts, mask_cap, d_mask, row_cap, d_mask_out, d_out, d_h_out);
+    });
+}
+
 extern "C" int vis_batch_triangulate_from(vis_ctx* ctx, const vis_tri_params* tp, int n, const vis_pose_result* d_pose, int mask_cap,
                                           const uint8_t* d_mask, int row_cap, vis_map_point* d_points, uint8_t* d_flags, vis_tri_summary* d_summary) {
     if (!tp || !d_points || !d_flags || !d_summary || ((uintptr_t)d_points & 15) || ((uintptr_t)d_summary & 3)) return VIS_E_INVALID;

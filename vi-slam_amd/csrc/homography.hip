@@ -15,6 +15,7 @@
 // the launch has, so the record does not depend on the shape.
 #include "vis_internal.h"
 #include "ransac_lanes.h"
+#include "h_transfer.h"                // h_adj, h_transfer
 #include <cmath>
 #include <cfloat>
 
@@ -38,14 +39,6 @@ DEV HPt h_point(const float* __restrict__ q1, const float* __restrict__ q2, int 
     return p;
 }
 
-// adj(M) of a row-major 3 x 3: rows c1 x c2, c2 x c0, c0 x c1 of M's columns
-DEV void h_adj(const double (&M)[9], double (&G)[9]) {
-    const double c0[3] = {M[0], M[3], M[6]}, c1[3] = {M[1], M[4], M[7]}, c2[3] = {M[2], M[5], M[8]};
-    double r0[3], r1[3], r2[3];
-    cross3(c1, c2, r0); cross3(c2, c0, r1); cross3(c0, c1, r2);
-    G[0] = r0[0]; G[1] = r0[1]; G[2] = r0[2]; G[3] = r1[0]; G[4] = r1[1]; G[5] = r1[2]; G[6] = r2[0]; G[7] = r2[1]; G[8] = r2[2];
-}
-
 // the projective basis of four points (x_k, y_k, 1): M = [l0 p0 | l1 p1 | l2 p2] row-major; false: a zero or non-finite l or determinant
 DEV bool h_basis(const double (&x)[4], const double (&y)[4], double (&M)[9]) {
     const double p0[3] = {x[0], y[0], 1.0}, p1[3] = {x[1], y[1], 1.0}, p2[3] = {x[2], y[2], 1.0}, p3[3] = {x[3], y[3], 1.0};
@@ -58,13 +51,6 @@ DEV bool h_basis(const double (&x)[4], const double (&y)[4], double (&M)[9]) {
     return !(h_bad(l0) || h_bad(l1) || h_bad(l2) || h_bad(det));
 }
 
-// (e, w w) of the transfer of (x, y, 1) by M against (u, v): the point passes at threshold t iff e <= t (w w)
-DEV void h_transfer(const double (&M)[9], double x, double y, double u, double v, double& e, double& ww) {
-    const double U = (M[0] * x + M[1] * y) + M[2], V = (M[3] * x + M[4] * y) + M[5], w = (M[6] * x + M[7] * y) + M[8];
-    const double du = U - u * w, dv = V - v * w;
-    e = du * du + dv * dv;
-    ww = w * w;
-}
 DEV bool h_inlier(const double (&H)[9], const double (&G)[9], const HPt& p, double t) {
     double e, ww;
     h_transfer(H, p.x1, p.y1, p.x2, p.y2, e, ww);

@@ -16,6 +16,7 @@
 // four waves per pair; it shares every er_* function, er_pass / er_cost through their thread count.
 #include "vis_internal.h"
 #include "ransac_lanes.h"
+#include "ep_sums.h"
 #include <cmath>
 #include <cfloat>
 
@@ -304,7 +305,7 @@ int essential_refine_run(vis_ctx* ctx, const vis_eref_params* ep, int n, int in_
 
 // ---- k_essential_polish: the refinement with its set re-selected under the pose it reached (include/vislam_hip.h states the algorithm and the
 // summation contract "T", tests/essential_polish_ref.py restates both).  NW waves walk a pair: thread tid of NT = 64 NW owns the points
-// i = tid mod NT, so er_pass<NT> / er_cost<NT> leave wave w with W_w, and ep_totals adds the wave totals in rising w on every thread: the same bits
+// i = tid mod NT, so er_pass<NT> / er_cost<NT> leave wave w with W_w, and ep_totals (ep_sums.h) adds the wave totals in rising w on every thread: the same bits
 // everywhere, hence uniform control flow around the barriers.  NW = 1 is the one-wave kernel's order as it stands (W_1 = W_2 = W_3 = +0.0 and a
 // W is never -0.0); a row of at most 64 points gives the same bits under either NW.  The set lives in the caller's output mask row: byte i is
 // read and written by thread i mod NT alone, so no barrier guards it.
@@ -312,43 +313,6 @@ struct EPArgs {
     ERArgs er;                         // thr2 = (select_px / fx)^2; row_cap: of the input mask
     int rounds, out_cap;               // out_cap: bytes between two rows of the output mask
 };
-
-// v[k] <- ((W_0 + W_1) + W_2) + W_3 of the wave totals v[k], n <- the sum of the waves' n, on every thread.  Two barriers: every thread of the
-// workgroup calls it, in uniform control flow
-template <int NW, int K>
-DEV void ep_totals(double (&v)[K], int& n) {
-    if constexpr (NW > 1) {
-        static_assert(NW == 4, "the contract names four wave totals");
-        __shared__ double s_w[NW][K];
-        __shared__ int s_n[NW];
-        const int tid = threadIdx.x;
-        if ((tid & 63) == 0) {
-#pragma unroll
-            for (int k = 0; k < K; k++) s_w[tid >> 6][k] = v[k];
-            s_n[tid >> 6] = n;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int k = 0; k < K; k++) v[k] = ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k];
-        n = (s_n[0] + s_n[1]) + (s_n[2] + s_n[3]);
-        __syncthreads();                                           // read by every wave before the next call writes
-    }
-}
-// two integer counts of the workgroup, on every thread
-template <int NW>
-DEV void ep_counts(int& a, int& b) {
-    for (int off = 32; off > 0; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); }
-    if constexpr (NW > 1) {
-        __shared__ int s_c[NW][2];
-        const int tid = threadIdx.x;
-        if ((tid & 63) == 0) { s_c[tid >> 6][0] = a; s_c[tid >> 6][1] = b; }
-        __syncthreads();
-        a = 0; b = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) { a += s_c[w][0]; b += s_c[w][1]; }
-        __syncthreads();
-    }
-}
 
 // the selection under the pose (R, t): bit 1 of byte i <- point i passes (thr2 den finite and s s <= thr2 den: er_pass's count, point for point);
 // bit 0 stays the current set.  nnew: the points that pass, nchg: the bytes the selection would flip (this thread's share of both)

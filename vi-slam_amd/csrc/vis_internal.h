@@ -518,6 +518,11 @@ int essential_refine_run(vis_ctx* ctx, const vis_eref_params* ep, int n, int in_
 int essential_polish_run(vis_ctx* ctx, const vis_epolish_params* ep, int n, int in_stride, const PoseOut* d_pose, const float* d_p1, const float* d_p2,
                          const int32_t* d_npts, int mask_cap, const uint8_t* d_mask, int out_cap, uint8_t* d_mask_out, vis_epolish_result* d_out,
                          PoseOut* d_pose_out);
+// homography_polish.hip: k_homography_polish on ctx->stream (one wave per pair for in_stride <= 64, else four); hp validated by the caller; d_mask:
+// rows of mask_cap bytes or null, d_mask_out: rows of out_cap bytes (both >= in_stride); d_h_out: n records or null
+int homography_polish_run(vis_ctx* ctx, const vis_hpolish_params* hp, int n, int in_stride, const vis_homography_result* d_h, const float* d_p1,
+                          const float* d_p2, const int32_t* d_npts, int mask_cap, const uint8_t* d_mask, int out_cap, uint8_t* d_mask_out,
+                          vis_hpolish_result* d_out, vis_homography_result* d_h_out);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

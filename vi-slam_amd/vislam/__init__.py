@@ -11,6 +11,7 @@ mirror the reference's surface for the hot path (names, argument meaning, error 
   Context.f2f_batch / batch_f2f                       <-> the same for every pair of a batch
   Context.find_homography / homography_batch / batch_homography   homography RANSAC and the H-or-E model choice (beyond the reference)
   Context.homography_pose / homography_pose_batch / batch_homography_pose   (R, t / d, n) of a pair's homography, both survivors of the vote
+  Context.homography_polish / homography_polish_batch / batch_homography_polish   the homography refined over its inliers, between the two above
   Context.pnp_ransac / pnp_batch / batch_pnp   the pose of a frame against map points: P3P RANSAC + Gauss-Newton refinement (beyond the reference)
   Context.essential_batch                             <-> essential RANSAC + recoverPose on rows that already sit in device memory
   Context.essential_refine / essential_refine_batch / batch_essential_refine   Gauss-Newton refinement of the two-view pose (beyond the reference)
@@ -259,6 +260,26 @@ assert C.sizeof(EssentialPolishParams) == 32 and EPOLISH_RESULT_DTYPE.itemsize =
 EP_POLISHED, EP_REJECTED, EP_FEW, EP_NO_POSE, EP_SHRANK = 1, 2, 4, 8, 16
 
 
+class HomographyPolishParams(C.Structure):
+    """vis_hpolish_params: the knobs of the homography polish (vis_default_hpolish_params: 3, 5, 8, 5.991, 1.0)"""
+    _fields_ = [("rounds", C.c_int32), ("refine_iters", C.c_int32), ("min_inliers", C.c_int32), ("reserved_", C.c_int32),
+                ("select_chi2", C.c_double), ("sigma_px", C.c_double)]
+
+
+class HomographyPolishResult(C.Structure):
+    """vis_hpolish_result: the reported H (unit norm, det >= 0), the start's cost, the last round's costs, the sets' sizes and the counts"""
+    _fields_ = [("H", C.c_double * 9), ("cost_first", C.c_double), ("cost0", C.c_double), ("cost1", C.c_double), ("n_points", C.c_int32),
+                ("n_set_first", C.c_int32), ("n_set_last", C.c_int32), ("n_changed", C.c_int32), ("rounds_run", C.c_int32),
+                ("steps_run", C.c_int32), ("best_step", C.c_int32), ("flags", C.c_int32)]
+
+
+HPOLISH_RESULT_DTYPE = np.dtype([("H", "<f8", (9,)), ("cost_first", "<f8"), ("cost0", "<f8"), ("cost1", "<f8"), ("n_points", "<i4"),
+                                 ("n_set_first", "<i4"), ("n_set_last", "<i4"), ("n_changed", "<i4"), ("rounds_run", "<i4"), ("steps_run", "<i4"),
+                                 ("best_step", "<i4"), ("flags", "<i4")])
+assert C.sizeof(HomographyPolishParams) == 32 and HPOLISH_RESULT_DTYPE.itemsize == C.sizeof(HomographyPolishResult) == 128
+HPOL_POLISHED, HPOL_REJECTED, HPOL_FEW, HPOL_NO_MODEL, HPOL_SHRANK = 1, 2, 4, 8, 16
+
+
 class KltParams(C.Structure):
     """vis_klt_params: the knobs of the pyramidal KLT tracker (vis_default_klt_params: 7, 3, 0, 10, 0.01, 0.1, 0, 0, 3)"""
     _fields_ = [("win_radius", C.c_int32), ("first_level", C.c_int32), ("last_level", C.c_int32), ("max_iters", C.c_int32),
@@ -316,6 +337,7 @@ ABI_SYMBOLS = [
     "vis_f2f_batch", "vis_batch_f2f", "vis_filter_keypoints_batch", "vis_batch_filter_keypoints", "vis_filter_keypoints",
     "vis_default_homography_params", "vis_find_homography", "vis_homography_batch", "vis_batch_homography",
     "vis_default_hpose_params", "vis_homography_pose", "vis_homography_pose_batch", "vis_batch_homography_pose",
+    "vis_default_hpolish_params", "vis_homography_polish", "vis_homography_polish_batch", "vis_batch_homography_polish",
     "vis_default_pnp_params", "vis_pnp_ransac", "vis_pnp_batch", "vis_batch_pnp",
     "vis_essential_batch", "vis_default_eref_params", "vis_essential_refine", "vis_essential_refine_batch", "vis_batch_essential_refine",
     "vis_default_epolish_params", "vis_essential_polish", "vis_essential_polish_batch", "vis_batch_essential_polish", "vis_batch_triangulate_from",
@@ -432,6 +454,13 @@ def _load():
         lib.vis_homography_pose.argtypes = [vp, hqp, vp, vp, vp, ci, vp, vp, vp]
         lib.vis_homography_pose_batch.argtypes = [vp, hqp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp]
         lib.vis_batch_homography_pose.argtypes = [vp, hqp, ci, vp, ci, vp, vp, vp]
+    if hasattr(lib, "vis_batch_homography_polish"):     # (absent from older A/B builds)
+        hlp = C.POINTER(HomographyPolishParams)
+        lib.vis_default_hpolish_params.argtypes = [hlp]
+        lib.vis_default_hpolish_params.restype = None
+        lib.vis_homography_polish.argtypes = [vp, hlp, vp, vp, vp, ci, vp, vp, vp, vp]
+        lib.vis_homography_polish_batch.argtypes = [vp, hlp, ci, vp, vp, vp, vp, ci, ci, vp, vp, vp, vp]
+        lib.vis_batch_homography_polish.argtypes = [vp, hlp, ci, vp, ci, vp, ci, vp, vp, vp]
     if hasattr(lib, "vis_set_align_weights"):           # (absent from older A/B builds)
         lib.vis_default_align_weights.argtypes = [C.POINTER(AlignWeights)]
         lib.vis_default_align_weights.restype = None
@@ -579,6 +608,12 @@ def default_hpose_params():
     hq = HposeParams()
     lib.vis_default_hpose_params(C.byref(hq))
     return hq
+
+
+def default_hpolish_params():
+    hp = HomographyPolishParams()
+    lib.vis_default_hpolish_params(C.byref(hp))
+    return hp
 
 
 def se3_exp(a):
@@ -1217,6 +1252,43 @@ class Context:
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_homography_pose(self._h, C.byref(hq), n, v(d_h_ptr), row_cap, v(d_mask_ptr), v(d_rot_ptr), v(d_out_ptr)),
                   "vis_batch_homography_pose")
+
+    # -- homography polish: the RANSAC winner refined over its inliers, between the two calls above -----------------
+    def homography_polish(self, hrec, p1, p2, mask=None, hp=None):
+        """(HPOLISH_RESULT_DTYPE element, mask uint8[m], HOMOGRAPHY_RESULT_DTYPE element): the pair's homography record hrec refined over its
+        inliers with the set re-selected, the set the reported H was fitted on, and hrec with the reported H and that set's size --
+        homography_pose reads the last two unchanged"""
+        hp = default_hpolish_params() if hp is None else hp
+        p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 2)
+        p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 2)
+        assert len(p1) == len(p2)
+        h = np.frombuffer(np.asarray(hrec).tobytes(), HOMOGRAPHY_RESULT_DTYPE).copy()
+        assert len(h) == 1
+        mask = None if mask is None else np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        assert mask is None or len(mask) >= len(p1)
+        out, ho = np.zeros(1, HPOLISH_RESULT_DTYPE), np.zeros(1, HOMOGRAPHY_RESULT_DTYPE)
+        mo = np.zeros(max(len(p1), 1), np.uint8)
+        self._chk(lib.vis_homography_polish(self._h, C.byref(hp), _ptr(h), _ptr(p1), _ptr(p2), len(p1), _ptr(mask), _ptr(out), _ptr(mo), _ptr(ho)),
+                  "vis_homography_polish")
+        return out[0], mo[:len(p1)], ho[0]
+
+    def homography_polish_batch(self, n, d_h_ptr, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_mask_out_ptr, d_out_ptr,
+                                d_h_out_ptr=0, hp=None):
+        """queue the polish of n homography records on the context's stream (raw DEVICE pointers; 0 / None = NULL for d_mask and d_h_out):
+        homography_pose_batch's buffers, n rows of row_cap output mask bytes, n HPOLISH_RESULT_DTYPE and n HOMOGRAPHY_RESULT_DTYPE records"""
+        hp = default_hpolish_params() if hp is None else hp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_homography_polish_batch(self._h, C.byref(hp), n, v(d_h_ptr), v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr), max_pts, row_cap,
+                                                  v(d_mask_ptr), v(d_mask_out_ptr), v(d_out_ptr), v(d_h_out_ptr)), "vis_homography_polish_batch")
+
+    def batch_homography_polish(self, n, d_h_ptr, mask_cap, d_mask_ptr, row_cap, d_mask_out_ptr, d_out_ptr, d_h_out_ptr=0, hp=None):
+        """the same on the pairs of the last batch_run, from the records and mask rows (mask_cap bytes apart; 0 / None = no mask) batch_homography
+        wrote, on the pose stream behind it; batch_homography_pose fed d_h_out and d_mask_out decomposes the polished H.  The buffers are in use
+        until batch_sync()"""
+        hp = default_hpolish_params() if hp is None else hp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_homography_polish(self._h, C.byref(hp), n, v(d_h_ptr), mask_cap, v(d_mask_ptr), row_cap, v(d_mask_out_ptr),
+                                                  v(d_out_ptr), v(d_h_out_ptr)), "vis_batch_homography_polish")
 
     # -- PnP: the pose of a frame against map points ---------------------------------------------------------------
     def pnp_ransac(self, X, xy, draws, pp=None):
