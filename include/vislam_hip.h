@@ -1249,6 +1249,122 @@ int  vis_rectify_batch(vis_rectify* r, const uint8_t* d_in, int in_stride, int n
  * (src/CameraModel.cpp:103-105).  Through the context's staging block like the other single-frame entry points; blocks once. */
 int  vis_rectify_host(vis_rectify* r, const uint8_t* img, int in_stride, uint8_t* out, int out_stride);
 
+/* ---- feature tracks: the matches of a stream linked over any number of frames, and their N-view triangulation (the reference has neither:
+ * its matcher, like everything above, knows one frame and its keyframe).  "ftrack" because vis_batch_track means CAMERA tracking.
+ * The track contract (tests/ftrack_ref.py restates it; every result below is integer arithmetic and equals it byte for byte).
+ * A LINK LIST of frame i is a list of vis_dmatch whose queryIdx is a keypoint of frame prev[i] and whose trainIdx is a keypoint of frame i
+ * (vis_batch_pnp's orientation).  prev[i] is an index < i or a VIS_KF_* value; any other value counts as VIS_KF_FIRST.  A frame takes part with
+ * nk(i) keypoints: 0 when prev[i] == VIS_KF_NOT_SAVED, else its count clamped to [0, row capacity].  The parent frame of i is frame prev[i] when
+ * that is an index, the carried row when prev[i] == VIS_KF_CARRIED and a row is given (its keypoints are the entries with len > 0), else none.
+ * Correspondence c of the first m entries (m = the list's count clamped to [0, link_cap], with a mask also to mask_cap) is a CANDIDATE iff the
+ * frame has a parent, trainIdx < nk(i) and queryIdx is a keypoint of the parent (both compared unsigned: a negative index is out of range), and
+ * its mask byte, when a mask is given, is non-zero.  A candidate LINKS keypoint trainIdx of frame i to keypoint queryIdx of the parent iff no
+ * candidate earlier in the list has the same trainIdx and none has the same queryIdx: the first in list order wins on BOTH sides, so a track
+ * never forks and never merges.  (A candidate that loses on one side still occupies the other: of (q0, t0), (q0, t1), (q1, t1) only the first
+ * links.  That is what makes the rule one atomic minimum per side and independent of scheduling; the plan's own lists are one-to-one already.)
+ * A linked keypoint continues its parent's track, every other keypoint k < nk(i) starts one.
+ * Per keypoint a vis_ftrack_obs: birth_seq = the stream number of the frame the track started in (frame i of a call is seq0 + i; the plan counts
+ * the frames of every vis_batch_run with VIS_STAGE_DETECT since vis_batch_plan / vis_batch_reset), birth_kp = the keypoint index of its first
+ * observation -- (birth_seq, birth_kp) is the track's identity: unique, no counter, the same however a stream is cut into launches -- len = the
+ * observations up to and including this one (>= 1), prev_kp = the parent's keypoint, or -1 where the track starts.  Entries k >= nk(i) of a
+ * row, up to its capacity, are (-1, -1, 0, -1).
+ * Per frame a vis_ftrack_frame: seq, n_keypoints = nk(i), n_continued, n_started, n_ended = the parent's keypoints that no keypoint of i
+ * continues (0 without a parent), max_len, sum_len (the caller divides; wraps beyond 2^31), flags: VIS_FT_NO_PAIR = no parent (VIS_KF_FIRST,
+ * VIS_KF_NOT_SAVED, frame 0 after a reset), VIS_FT_NO_CARRY = prev[i] is VIS_KF_CARRIED but no row is held (rows form: d_carry_in NULL; plan form:
+ * the launch before was not linked) -- every keypoint of such a frame starts a track; not an error. */
+enum { VIS_FT_NO_PAIR = 1, VIS_FT_NO_CARRY = 2 };
+enum { VIS_FT_SYM = 0, VIS_FT_GOOD = 1 };
+typedef struct vis_ftrack_obs { int32_t birth_seq, birth_kp, len, prev_kp; } vis_ftrack_obs;                               /* 16 bytes */
+typedef struct vis_ftrack_frame { int32_t seq, n_keypoints, n_continued, n_started, n_ended, max_len, sum_len, flags; } vis_ftrack_frame;   /* 32 bytes */
+/* Caller-made rows, DEVICE pointers, asynchronous on the context's stream, no plan.  d_prev, d_nkp, d_nlinks: n entries; d_links: n rows of
+ * link_cap entries; d_mask: NULL or n rows of mask_cap bytes; d_carry_in: NULL or ONE row of row_cap observations, those of the frame
+ * VIS_KF_CARRIED refers to; d_obs: n rows of row_cap records; d_frame: n records.  Every entry of d_obs and d_frame is written.  The workspace
+ * (24 bytes per entry of d_obs) belongs to the context and only grows; a call that grows it SYNCHRONISES.  On the device: the candidates take an
+ * atomic minimum of their list position per side, one pass writes every keypoint's parent, ceil(log2 n) rounds of pointer doubling between two
+ * buffers replace every keypoint's (ancestor, distance) by its ancestor's -- no kernel loops over the frames -- and one workgroup per frame
+ * writes the records and reduces the summary in integers.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL d_prev, d_nkp, d_nlinks, d_obs or d_frame, a NULL d_links with link_cap > 0, a pointer that is
+ * not aligned (16 bytes for d_links, d_carry_in and d_obs, 4 for the rest), n, link_cap, mask_cap, row_cap or seq0 negative.  VIS_E_STATE without a
+ * context.  VIS_E_CAPACITY when n x row_cap exceeds 2^28 entries. */
+int  vis_ftrack_link_rows(vis_ctx* ctx, int n, const int32_t* d_prev, const int32_t* d_nkp, const vis_dmatch* d_links, const int32_t* d_nlinks,
+                          int link_cap, const uint8_t* d_mask, int mask_cap, const vis_ftrack_obs* d_carry_in, int seq0, int row_cap,
+                          vis_ftrack_obs* d_obs, vis_ftrack_frame* d_frame);
+/* The pairs of the last vis_batch_run (which must have included VIS_STAGE_MATCH; n = its frames), with vis_batch_get_keyframes' pairing, keyframe
+ * gate off or on.  source: VIS_FT_SYM = every symmetric match of a pair, VIS_FT_GOOD = the grid-filtered good matches.  d_mask: NULL or caller rows
+ * of mask_cap bytes aligned with that list (a polish's mask); pose_inliers != 0 uses the pose stage's own mask instead (vis_batch_get_inlier_mask,
+ * its first n_points bytes) and excludes a d_mask.  d_obs: n rows of row_cap >= the plan's keypoint capacity; only the first keypoint-capacity
+ * entries of a row are written.  The plan keeps a copy of the row of the last SAVED frame of the launch (beside the keyframe gate's carried
+ * record) and the stream number of frame 0: the next call continues those tracks across the launch boundary, a launch that saved nothing carries
+ * the earlier row forward, vis_batch_plan / vis_batch_reset forget the row and restart seq at 0, and a launch that was not linked makes the frames
+ * of the next one whose pair is the carried keyframe VIS_FT_NO_CARRY.  Calling it again for the same run repeats the result.  Asynchronous on the
+ * POSE stream behind the matcher of that run (and, when a d_mask is given, behind the context's stream), overlapping the next vis_batch_run like
+ * vis_batch_triangulate; the caller's buffers are in use until vis_batch_sync.  The workspace is allocated by the first call of a plan.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL or misaligned d_obs (16 bytes) or d_frame (4), n, mask_cap or row_cap negative, a source that is
+ * neither VIS_FT_SYM nor VIS_FT_GOOD, pose_inliers together with a d_mask.  VIS_E_CAPACITY: row_cap below the plan's keypoint capacity, or with a
+ * d_mask mask_cap below the list's row length (the keypoint capacity, or root^2 for VIS_FT_GOOD).  VIS_E_STATE: no context / plan / match stage, or n
+ * differs.  Then VIS_E_INVALID when pose_inliers is set and the last run had no VIS_STAGE_POSE or source is not the list the pose stage saw. */
+int  vis_batch_ftrack(vis_ctx* ctx, int source, int pose_inliers, int n, const uint8_t* d_mask, int mask_cap, int row_cap,
+                      vis_ftrack_obs* d_obs, vis_ftrack_frame* d_frame);
+
+/* N-view triangulation of the tracks.  d_poses: n x 12 doubles per frame, R row-major then t, x_cam = R X + t in ONE common frame and scale; a
+ * frame whose 12 numbers are not all finite or whose R is all zero has no pose (the pose record's convention).  The poses are the caller's (a
+ * VIO, a chained and scaled PnP, ground truth): where they come from, and a common scale for consecutive two-view poses, is outside this library.
+ * A point is computed for every keypoint (i, k), k < nk(i), that is the LAST observation of its track inside the call: no keypoint of a later
+ * frame names it as its parent (prev[] index and prev_kp < nk of that frame).  Every other entry k < nk(i) gets the zero record and flags 0; entries
+ * k >= nk(i) are left untouched.  The lane walks back from (i, k) along prev_kp / prev[] through at most max_views observations of this call --
+ * observations of earlier launches are not held: a limitation -- and USES those whose frame has a pose and whose pixel (u, v) is finite (a
+ * non-finite pixel drops the view; a finite one, however large, is used as it stands and ends in flags that fail).  Fewer than min_views used
+ * views: VIS_FTP_FEW, n_views set, everything else zero.  Otherwise, all in double, nothing contracted, only + - * / sqrt, sums in view order
+ * from the newest to the oldest, with (fx, fy, cx, cy) of the context's parameters and x = (u - cx) / fx, y = (v - cy) / fy:
+ *   1. DLT: per view the rows r = x P_2 - P_0 and s = y P_2 - P_1 of P = [R | t]; the ten sums A_ab += r_a r_b + s_a s_b (a <= b), mirrored.
+ *   2. The eigenvector of the smallest eigenvalue (the first on ties) by the Jacobi iteration of vis_triangulate; X = (v_0, v_1, v_2) / v_3.
+ *      v_3 == 0, a quotient that is not finite, or a cost of that point (step 3) that is not finite -- the point lies in a camera's plane, or
+ *      something overflowed: VIS_FTP_SINGULAR, n_views set, everything else zero.  No reported number is ever a NaN or an infinity.
+ *   3. Up to gn_iters Gauss-Newton steps on the pixel error.  Per view (U, V, W) = R X + t (each row ((R_i0 X_0 + R_i1 X_1) + R_i2 X_2) + t_i),
+ *      iw = 1 / W, un = U iw, vn = V iw, residual ru = (fx un + cx) - u, rv = (fy vn + cy) - v, Jacobian rows Ju_j = (fx iw) (R_0j - un R_2j),
+ *      Jv_j = (fy iw) (R_1j - vn R_2j); H_ab += Ju_a Ju_b + Jv_a Jv_b (a <= b), g_a += Ju_a ru + Jv_a rv, cost += ru ru + rv rv.  Step by LDL^T
+ *      without pivoting: D0 = H00, L10 = H01 / D0, L20 = H02 / D0, D1 = H11 - (L10 L10) D0, L21 = (H12 - (L20 L10) D0) / D1,
+ *      D2 = (H22 - (L20 L20) D0) - (L21 L21) D1; z0 = -g0, z1 = -g1 - L10 z0, z2 = (-g2 - L20 z0) - L21 z1; d2 = z2 / D2, d1 = z1 / D1 - L21 d2,
+ *      d0 = (z0 / D0 - L10 d1) - L20 d2; X <- X + d.  A pivot that is not > 0 or not finite ends the steps.  EVERY iterate is costed, the DLT point
+ *      included, and the first of least cost is reported (an iterate replaces the best only with cost < best): the cost never rises above the DLT
+ *      point's and a NaN iterate cannot win.
+ *   4. vis_ftrack_point: X, rms_reproj_px = (float)sqrt(cost / n_views), parallax_cos = (float) of a . b / sqrt((a . a)(b . b)) with a, b the
+ *      vectors from X to the centres -R^T t of the newest and the oldest used camera (the COSINE: the device's atan2 and a host's need not agree
+ *      bit for bit, so no angle is formed and the threshold is a cosine, like vis_hpose_params.max_cos_parallax; a quotient that is not finite is
+ *      reported as 1 and fails the threshold), n_views, flags:
+ *      VIS_FTP_FRONT W > 0 in every used view, VIS_FTP_REPROJ_OK ru ru + rv rv <= max_reproj_px^2 in every used view, VIS_FTP_PARALLAX_OK
+ *      parallax_cos (before rounding) <= max_parallax_cos, VIS_FTP_KEPT all three.
+ * d_flags: the flags as bytes, rows of row_cap.  d_summary[i]: the counts of frame i.  Two runs are byte-identical. */
+enum { VIS_FTP_FRONT = 1, VIS_FTP_REPROJ_OK = 2, VIS_FTP_PARALLAX_OK = 4, VIS_FTP_KEPT = 8, VIS_FTP_FEW = 16, VIS_FTP_SINGULAR = 32 };
+typedef struct vis_ftrack_tri_params {   /* 32 bytes; the defaults are this library's own */
+    int32_t max_views;                   /* 16     observations walked back from a track's end, 2 ... 32 */
+    int32_t min_views;                   /* 2      used views below which no point is formed, 2 ... max_views */
+    int32_t gn_iters;                    /* 5      Gauss-Newton steps, 0 ... 10 */
+    int32_t reserved_;                   /* 0 */
+    double  max_reproj_px;               /* 2.0    finite, > 0, at most 1e6 */
+    double  max_parallax_cos;            /* cos(1 degree) = 0.9998476951563913; in (-1, 1] */
+} vis_ftrack_tri_params;
+typedef struct vis_ftrack_point { double X[3]; float rms_reproj_px, parallax_cos; int32_t n_views, flags; } vis_ftrack_point;   /* 40 bytes */
+typedef struct vis_ftrack_tri_summary { int32_t n_ends, n_points, n_kept, n_front, n_reproj_ok, n_parallax_ok, n_few, n_singular; } vis_ftrack_tri_summary;   /* 32 bytes; n_points = ends with neither FEW nor SINGULAR */
+void vis_default_ftrack_tri_params(vis_ftrack_tri_params* tp);
+/* Caller-made rows, DEVICE pointers, asynchronous on the context's stream.  d_prev, d_nkp: n entries; d_obs: n rows of row_cap observations (only
+ * prev_kp is read, and checked against nk of the parent frame); d_xy: n rows of row_cap (u, v) float pixels; d_poses: n x 12 doubles; d_points /
+ * d_flags: n rows of row_cap entries; d_summary: n records.
+ * Refusals, in this order.  VIS_E_INVALID: tp NULL or outside the ranges above, a NULL pointer, a pointer that is not aligned (16 bytes for d_obs, 8
+ * for d_xy, d_poses and d_points, 4 for d_prev, d_nkp and d_summary), n or row_cap negative.  VIS_E_STATE without a context.  VIS_E_CAPACITY when
+ * n x row_cap exceeds 2^28 entries. */
+int  vis_ftrack_triangulate_rows(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, const int32_t* d_prev, const int32_t* d_nkp,
+                                 const vis_ftrack_obs* d_obs, int row_cap, const float* d_xy, const double* d_poses, vis_ftrack_point* d_points,
+                                 uint8_t* d_flags, vis_ftrack_tri_summary* d_summary);
+/* The keypoints of the last vis_batch_run (n = its frames) with the observations vis_batch_ftrack wrote for it (d_obs, rows of row_cap) and
+ * vis_batch_get_keyframes' pairing: on the POSE stream behind vis_batch_ftrack of the same run and behind the context's stream (where d_poses may
+ * have been produced), overlapping the next vis_batch_run; the caller's buffers are in use until vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_ftrack_triangulate_rows refuses of tp, a NULL or misaligned d_obs, d_poses, d_points, d_flags or
+ * d_summary, n or row_cap negative.  VIS_E_CAPACITY: row_cap below the plan's keypoint capacity.  VIS_E_STATE: no context / plan / match stage, or n
+ * differs. */
+int  vis_batch_ftrack_triangulate(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, const vis_ftrack_obs* d_obs, int row_cap,
+                                  const double* d_poses, vis_ftrack_point* d_points, uint8_t* d_flags, vis_ftrack_tri_summary* d_summary);
+
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */
 int  vis_synth_canvas(uint8_t* canvas, int canvas_dim, uint64_t seed);

@@ -29,6 +29,9 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --hpolish: with --hposes, every pair's homography is polished over its inliers before it is decomposed (vis_batch_homography_polish between
              the two calls, default parameters; the pose call reads the polished record and mask): each row of the CSV gains a last column, the
              polish's flags (VIS_HPOL_*), and the JSON line carries the count of each flag.
+  --tracks out.csv: the symmetric matches of every pair linked into feature tracks (vis_batch_ftrack behind every batch, the tracks continuing
+             across the batches): one row per frame -- frame index, timestamp, the vis_ftrack_frame fields and the histogram of the
+             track length at the frame's keypoints (bins 1, 2, 3-4, 5-8, ... 65-); the JSON line carries the totals.
   --pnp out.csv: the pose of every frame against the map points of its keyframe's own pair (vis_batch_triangulate, then vis_batch_pnp with
              VIS_MP_KEPT, default parameters, 200 x 3 draws of default_rng(7)): one row per frame -- frame index, timestamp, q, p, n_linked,
              link flags (VIS_PNPL_*), scale, then n_inliers, n_inliers_refined, best_iter, best_root, flags (VIS_PNP_*), cost0, cost1, R (nine,
@@ -108,6 +111,7 @@ def main():
     ap.add_argument("--refined", default=None, metavar="CSV", help="write every frame's refined two-view pose here")
     ap.add_argument("--polished", default=None, metavar="CSV", help="write every frame's polished two-view pose here")
     ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
+    ap.add_argument("--tracks", default=None, metavar="CSV", help="link the symmetric matches into feature tracks; write every frame's summary and length histogram here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -169,6 +173,12 @@ def main():
         d_krec = torch.empty(B * kcap * vislam.KLT_POINT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         d_kpair = torch.empty(B * vislam.KLT_PAIR_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         klt_rows, klt_totals = [], dict(pairs=0, points=0, tracked=0, oob=0, flat=0, fb=0)
+    if a.tracks:
+        tcap = ctx.keypoint_capacity(w, h)
+        d_tobs = torch.empty(B * tcap * vislam.FTRACK_OBS_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        d_tframe = torch.empty(B * vislam.FTRACK_FRAME_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        TRACK_BINS = (1, 2, 3, 5, 9, 17, 33, 65)                # histogram of the track length at a frame: [1], [2], [3, 4], [5, 8], ... [65, inf)
+        track_rows, track_totals = [], dict(observations=0, started=0, continued=0, max_len=0, no_carry=0)
     if a.weights != "identity":
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
@@ -262,6 +272,8 @@ def main():
             ctx.batch_homography_pose(nb, d_hrec2.data_ptr(), hcap, d_hmask2.data_ptr(), 0, d_hpose.data_ptr(), hq)
         elif a.hposes:
             ctx.batch_homography_pose(nb, d_hrec.data_ptr(), hcap, d_hmask.data_ptr(), 0, d_hpose.data_ptr(), hq)
+        if a.tracks:
+            ctx.batch_ftrack(nb, tcap, d_tobs.data_ptr(), d_tframe.data_ptr())
         if a.klt:
             ctx.batch_klt(d, nb, kcap, d_krec.data_ptr(), d_kpair.data_ptr(), kp=kltp)
         if feed:
@@ -317,6 +329,19 @@ def main():
                 if int(hpose[i]["kind"]) != vislam.HP_NONE:
                     hpose_totals[int(hpose[i]["kind"])] += 1
                     hpose_rows.append((first + i, stamps[first + i], hpose[i].copy(), None if hpol is None else int(hpol[i]["flags"])))
+        if a.tracks:
+            tobs = d_tobs.cpu().numpy().view(vislam.FTRACK_OBS_DTYPE).reshape(B, tcap)
+            tfr = d_tframe.cpu().numpy().view(vislam.FTRACK_FRAME_DTYPE)
+            for i in range(nb):
+                f_ = tfr[i]
+                lens = tobs[i, :int(f_["n_keypoints"])]["len"]
+                hist = np.histogram(lens, bins=TRACK_BINS + (np.iinfo(np.int32).max,))[0]
+                track_totals["observations"] += int(f_["n_keypoints"])
+                track_totals["started"] += int(f_["n_started"])
+                track_totals["continued"] += int(f_["n_continued"])
+                track_totals["max_len"] = max(track_totals["max_len"], int(f_["max_len"]))
+                track_totals["no_carry"] += int(bool(int(f_["flags"]) & vislam.FT_NO_CARRY))
+                track_rows.append((first + i, stamps[first + i], *(int(f_[k]) for k in vislam.FTRACK_FRAME_DTYPE.names), *(int(v) for v in hist)))
         if a.klt:
             krec = d_krec.cpu().numpy().view(vislam.KLT_POINT_DTYPE).reshape(B, kcap)
             kpair, klinks = d_kpair.cpu().numpy().view(vislam.KLT_PAIR_DTYPE), ctx.batch_get_keyframes()
@@ -415,6 +440,12 @@ def main():
                         + ",".join("%.17g" % v for v in r["H"]) + "\n")
         out["models_csv"] = a.models
         out["models"] = dict(zip(vislam.MODEL_NAMES, model_totals))
+    if a.tracks:
+        with open(a.tracks, "w") as f:                          # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
+            for r in track_rows:
+                f.write(",".join("%d" % v for v in r) + "\n")
+        out["tracks_csv"] = a.tracks
+        out["tracks"] = dict(track_totals, mean_len=track_totals["observations"] / max(track_totals["started"], 1), histogram_bins=list(TRACK_BINS))
     if a.klt:
         with open(a.klt, "w") as f:
             for fi, ts, j, x1, y1, r in klt_rows:

@@ -122,6 +122,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     plan_destroy(ctx->single); plan_destroy(ctx->batch);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_ess_ws) (void)hipFree(ctx->d_ess_ws);
+    if (ctx->d_ft_ws) (void)hipFree(ctx->d_ft_ws);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -251,7 +252,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n); F(pl->d_ft_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1233,6 +1234,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     sync_all(ctx);
     ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->pyr_frames = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
+    ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft_run = -1; ctx->batch->ft_have = false;   // vis_batch_ftrack: no carried row, seq restarts at 0
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
@@ -1359,7 +1361,7 @@ static int batch_run_impl(vis_ctx* ctx, const uint8_t* d_frames, int n, int stag
     }
     if (rc) { pl->mo_cur = last_mo; pl->half_valid = pl->grad_valid = false; return rc; }   // nothing of the stream state (carried frame, record set, matcher-output set) has been committed
     pl->have_prev = have_prev; pl->pair0_valid = have_prev;
-    if (detect) { pl->run_count++; pl->carry_from = base + n; }
+    if (detect) { pl->run_count++; pl->carry_from = base + n; pl->seq0 = pl->seq_next; pl->seq_next += n; }
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[8], sA);
     pl->last_n = n; pl->last_base = base;
     pl->last_stages = stages; pl->run_seq++;                      // (what vis_batch_track checks)
@@ -1868,6 +1870,160 @@ extern "C" int vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
                             pl->kcap, sym ? O.sym : O.good, d_npts, O.p2, pl->d_pose, d_points, d_flags, row_cap, require, pl->d_pnp_tab, pl->d_pnp_X,
                             pl->d_pnp_xy, pl->d_pnp_n, d_draws, mask_cap, d_mask, d_out, d_link);
     }, true);
+}
+
+// ---- feature tracks: ftrack.hip
+static bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+static int ensure_ftrack_rows_workspace(vis_ctx* ctx, size_t bytes) {
+    if (bytes <= ctx->ft_ws_bytes) return VIS_OK;
+    sync_all(ctx);                                                 // work queued on any stream may still use the old block
+    if (ctx->d_ft_ws) (void)hipFree(ctx->d_ft_ws);
+    ctx->d_ft_ws = nullptr; ctx->ft_ws_bytes = 0;
+    if (hipMalloc(&ctx->d_ft_ws, bytes) != hipSuccess) {
+        (void)hipGetLastError(); ctx->d_ft_ws = nullptr;
+        ctx->err = "vis_ftrack_link_rows: out of device memory for the workspace"; return VIS_E_NOMEM;
+    }
+    ctx->ft_ws_bytes = bytes;
+    return VIS_OK;
+}
+
+extern "C" int vis_ftrack_link_rows(vis_ctx* ctx, int n, const int32_t* d_prev, const int32_t* d_nkp, const vis_dmatch* d_links, const int32_t* d_nlinks,
+                                    int link_cap, const uint8_t* d_mask, int mask_cap, const vis_ftrack_obs* d_carry_in, int seq0, int row_cap,
+                                    vis_ftrack_obs* d_obs, vis_ftrack_frame* d_frame) {
+    if (!d_prev || !d_nkp || !d_nlinks || !d_obs || !d_frame || (link_cap > 0 && !d_links)) return VIS_E_INVALID;
+    if (!aligned(d_links, 16) || !aligned(d_carry_in, 16) || !aligned(d_obs, 16) || !aligned(d_prev, 4) || !aligned(d_nkp, 4) || !aligned(d_nlinks, 4) ||
+        !aligned(d_frame, 4)) return VIS_E_INVALID;
+    if (n < 0 || link_cap < 0 || mask_cap < 0 || row_cap < 0 || seq0 < 0) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if ((size_t)n * (size_t)row_cap > ((size_t)1 << 28)) { ctx->err = "vis_ftrack_link_rows: n x row_cap exceeds 2^28 entries"; return VIS_E_CAPACITY; }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    FtWork W;
+    Carver measure{nullptr, 0, SIZE_MAX};
+    W.layout(measure, (size_t)n, (size_t)row_cap);
+    int rc = ensure_ftrack_rows_workspace(ctx, std::max(measure.off, (size_t)256));
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_ft_ws, 0, ctx->ft_ws_bytes};
+    W.layout(cv, (size_t)n, (size_t)row_cap);
+    if (cv.overflow) { ctx->err = "vis_ftrack_link_rows: workspace too small (internal)"; return VIS_E_NOMEM; }
+    return ftrack_link_run(ctx, W, n, row_cap, FtFrames{d_prev, 0, d_nkp}, d_links, d_nlinks, link_cap, d_mask, mask_cap, nullptr, 0, d_carry_in, seq0,
+                           row_cap, row_cap, d_obs, d_frame, nullptr);
+}
+
+// the plan's workspace: FtWork for B frames of kcap keypoints and, behind it, the two carried rows -- one list, measured and then bound
+static void ftrack_plan_layout(Carver& cv, Plan* pl, FtWork& W, vis_ftrack_obs* carry[2]) {
+    W.layout(cv, (size_t)pl->B, (size_t)pl->kcap);
+    carry[0] = cv.take<vis_ftrack_obs>((size_t)pl->kcap); carry[1] = cv.take<vis_ftrack_obs>((size_t)pl->kcap);
+}
+static int ensure_ftrack(vis_ctx* ctx, Plan* pl, FtWork& W) {
+    vis_ftrack_obs* carry[2];
+    if (!pl->d_ft_ws) {
+        Carver measure{nullptr, 0, SIZE_MAX};
+        ftrack_plan_layout(measure, pl, W, carry);
+        if (measure.overflow) return VIS_E_NOMEM;
+        if (hipMalloc(&pl->d_ft_ws, measure.off + 256) != hipSuccess) {
+            (void)hipGetLastError(); pl->d_ft_ws = nullptr;
+            ctx->err = "vis_batch_ftrack: out of device memory for the plan's workspace"; return VIS_E_NOMEM;
+        }
+        pl->ft_run = -1; pl->ft_have = false;
+    }
+    Carver cv{(char*)pl->d_ft_ws, 0, SIZE_MAX};
+    ftrack_plan_layout(cv, pl, W, carry);
+    pl->ft_carry[0] = carry[0]; pl->ft_carry[1] = carry[1];
+    return VIS_OK;
+}
+
+// the pairing of the last run as the kernels read it: the gate's link table, or the gate-off rule; the counts of its frames
+static FtFrames plan_frames(Plan* pl) {
+    return FtFrames{pl->kf_min ? pl->last_set().kf_link : nullptr, pl->pair0_valid ? 1 : 0, pl->d_nkp + pl->last_base + 1};
+}
+
+extern "C" int vis_batch_ftrack(vis_ctx* ctx, int source, int pose_inliers, int n, const uint8_t* d_mask, int mask_cap, int row_cap,
+                                vis_ftrack_obs* d_obs, vis_ftrack_frame* d_frame) {
+    if (!d_obs || !d_frame || !aligned(d_obs, 16) || !aligned(d_frame, 4) || n < 0 || mask_cap < 0 || row_cap < 0 ||
+        (source != VIS_FT_SYM && source != VIS_FT_GOOD) || (pose_inliers && d_mask)) return VIS_E_INVALID;
+    if (ctx && ctx->batch) {
+        Plan* pl = ctx->batch;
+        if (row_cap < pl->kcap) { ctx->err = "vis_batch_ftrack: row_cap is smaller than the plan's keypoint capacity"; return VIS_E_CAPACITY; }
+        if (d_mask && mask_cap < (source == VIS_FT_SYM ? pl->kcap : pl->root * pl->root)) { ctx->err = "vis_batch_ftrack: mask_cap is smaller than the list's row length"; return VIS_E_CAPACITY; }
+    }
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_ftrack: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    const bool pose_sym = ctx->p.pose_input == VIS_POSE_SYM;
+    if (pose_inliers && (!(pl->last_stages & VIS_STAGE_POSE) || (source == VIS_FT_SYM) != pose_sym)) {
+        ctx->err = "vis_batch_ftrack: pose_inliers needs VIS_STAGE_POSE and the list the pose stage saw"; return VIS_E_INVALID;
+    }
+    (void)hipSetDevice(ctx->device);
+    FtWork W;
+    { const int rc = ensure_ftrack(ctx, pl, W); if (rc) return rc; }
+    // the row this launch continues: the one the launch before wrote, or -- the call repeated for the same run -- the one it read itself
+    const bool again = pl->ft_run == pl->run_count;
+    const bool have = again ? pl->ft_have : (pl->ft_run >= 0 && pl->ft_run == pl->run_count - 1);
+    const int in = again ? pl->ft_in : (pl->ft_in ^ 1);
+    Plan::MatchOut& O = pl->out();
+    // On the pose stream behind the matcher of the run (the lists and counts of its matcher-output set, the keypoint counts of its record set, the
+    // gate's link table) and, with a caller's mask, behind the context's stream; the pose stage's mask and records are written on the pose stream
+    // itself.  The writers of those buffers wait for the reader event noted here.
+    const int rc = on_pose_stream(ctx, {(unsigned)(FU_MATCHER | (d_mask ? FU_FORK : 0)), ctx->ev_epi_done[pl->mo_cur]}, [&] {
+        const bool sym = source == VIS_FT_SYM;
+        static_assert(sizeof(PoseOut) % 4 == 0 && offsetof(PoseOut, n_points) % 4 == 0, "the pose record's n_points as a strided int32");
+        const int rc2 = ftrack_link_run(ctx, W, n, pl->kcap, plan_frames(pl), sym ? O.sym : O.good, sym ? O.nsym : O.ngood, sym ? pl->kcap : pl->root * pl->root,
+                                        pose_inliers ? pl->d_mask : d_mask, pose_inliers ? pl->pose_mcap : mask_cap,
+                                        pose_inliers ? (const int32_t*)((const char*)pl->d_pose + offsetof(PoseOut, n_points)) : nullptr, (int)(sizeof(PoseOut) / 4),
+                                        have ? pl->ft_carry[in] : nullptr, pl->seq0, row_cap, pl->kcap, d_obs, d_frame, pl->ft_carry[in ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, {&O.readers, &pl->last_set().matcher, pl->kf_min ? &pl->last_set().links : nullptr});
+    if (rc) return rc;
+    pl->ft_in = in; pl->ft_have = have; pl->ft_run = pl->run_count;
+    return VIS_OK;
+}
+
+extern "C" void vis_default_ftrack_tri_params(vis_ftrack_tri_params* tp) {
+    if (!tp) return;
+    tp->max_views = 16; tp->min_views = 2; tp->gn_iters = 5; tp->reserved_ = 0; tp->max_reproj_px = 2.0; tp->max_parallax_cos = 0.9998476951563913;
+}
+
+static bool ftrack_tri_params_ok(const vis_ftrack_tri_params* tp) {
+    return tp && tp->max_views >= 2 && tp->max_views <= 32 && tp->min_views >= 2 && tp->min_views <= tp->max_views && tp->gn_iters >= 0 && tp->gn_iters <= 10 &&
+           std::isfinite(tp->max_reproj_px) && tp->max_reproj_px > 0.0 && tp->max_reproj_px <= 1e6 && tp->max_parallax_cos > -1.0 && tp->max_parallax_cos <= 1.0;
+}
+
+extern "C" int vis_ftrack_triangulate_rows(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, const int32_t* d_prev, const int32_t* d_nkp,
+                                           const vis_ftrack_obs* d_obs, int row_cap, const float* d_xy, const double* d_poses, vis_ftrack_point* d_points,
+                                           uint8_t* d_flags, vis_ftrack_tri_summary* d_summary) {
+    if (!ftrack_tri_params_ok(tp) || !d_prev || !d_nkp || !d_obs || !d_xy || !d_poses || !d_points || !d_flags || !d_summary) return VIS_E_INVALID;
+    if (!aligned(d_obs, 16) || !aligned(d_xy, 8) || !aligned(d_poses, 8) || !aligned(d_points, 8) || !aligned(d_prev, 4) || !aligned(d_nkp, 4) ||
+        !aligned(d_summary, 4) || n < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if ((size_t)n * (size_t)row_cap > ((size_t)1 << 28)) { ctx->err = "vis_ftrack_triangulate_rows: n x row_cap exceeds 2^28 entries"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return ftrack_triangulate_run(ctx, tp, n, row_cap, FtFrames{d_prev, 0, d_nkp}, d_obs, row_cap, d_xy, (size_t)row_cap * 8, 8, d_poses, d_points, d_flags,
+                                  d_summary);
+}
+
+extern "C" int vis_batch_ftrack_triangulate(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, const vis_ftrack_obs* d_obs, int row_cap,
+                                            const double* d_poses, vis_ftrack_point* d_points, uint8_t* d_flags, vis_ftrack_tri_summary* d_summary) {
+    if (!ftrack_tri_params_ok(tp) || !d_obs || !d_poses || !d_points || !d_flags || !d_summary || !aligned(d_obs, 16) || !aligned(d_poses, 8) ||
+        !aligned(d_points, 8) || !aligned(d_summary, 4) || n < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (ctx && ctx->batch && row_cap < ctx->batch->kcap) { ctx->err = "vis_batch_ftrack_triangulate: row_cap is smaller than the plan's keypoint capacity"; return VIS_E_CAPACITY; }
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_ftrack_triangulate: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    if ((size_t)n * (size_t)row_cap > ((size_t)1 << 28)) { ctx->err = "vis_batch_ftrack_triangulate: n x row_cap exceeds 2^28 entries"; return VIS_E_CAPACITY; }
+    // on the pose stream behind vis_batch_ftrack of the run (queued there), behind the matcher that saw the keypoints and behind the context's
+    // stream, where the caller's poses may have been produced; the keypoint records and the link table are read: their writers wait for the event
+    static_assert(offsetof(vis_keypoint, x) == 0 && offsetof(vis_keypoint, y) == 4, "a keypoint record begins with its pixel");
+    return on_pose_stream(ctx, {FU_FORK | FU_MATCHER, ctx->ev_epi_done[pl->mo_cur]}, [&] {
+        const int rc2 = ftrack_triangulate_run(ctx, tp, n, pl->kcap, plan_frames(pl), d_obs, row_cap, pl->d_kps + (size_t)(pl->last_base + 1) * pl->kcap,
+                                               (size_t)pl->kcap * sizeof(vis_keypoint), (int)sizeof(vis_keypoint), d_poses, d_points, d_flags, d_summary);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, {&pl->out().readers, &pl->last_set().matcher, pl->kf_min ? &pl->last_set().links : nullptr});
 }
 
 // ---- the pose stage on device rows: pose_run on a workspace of the context's own

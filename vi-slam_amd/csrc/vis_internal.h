@@ -110,6 +110,14 @@ struct Plan {
     // vis_batch_pnp (pnp.hip k_pnp_link), allocated by the first call of the plan (ensure_pnp): per frame the keypoint table of its keyframe's
     // pair (npairs x kcap), the linked rows (npairs x pose_mcap map points and pixels) and their counts
     int32_t* d_pnp_tab = nullptr; double* d_pnp_X = nullptr; float* d_pnp_xy = nullptr; int32_t* d_pnp_n = nullptr;
+    // vis_batch_ftrack (ftrack.hip), allocated by the first call of the plan (ensure_ftrack): ONE block carved by FtWork::layout for B frames of
+    // kcap keypoints, and behind it the two carried observation rows (kcap records each) used in turn: a call reads ft_carry[ft_in] -- the row of
+    // the last saved frame of the launch before, beside the carried record of the keyframe gate -- and writes the other one.  seq_next counts the
+    // frames of every detecting vis_batch_run since plan / reset, seq0 = the stream number of frame 0 of the last run; ft_run = the run_count of
+    // the last linked launch (-1: none), ft_have = whether that call had a row to read (a repeated call for the same run reads it again)
+    void* d_ft_ws = nullptr; vis_ftrack_obs* ft_carry[2] = {nullptr, nullptr};
+    int ft_in = 0, ft_run = -1; bool ft_have = false;
+    int seq_next = 0, seq0 = 0;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -205,6 +213,8 @@ struct vis_ctx {
     // grow-only workspace of vis_essential_batch (api.hip PoseWork: the pose stage's buffers for n rows), apart from the scratch block so that a
     // host-pointer call between two batches cannot move it
     void* d_ess_ws = nullptr; size_t ess_ws_bytes = 0;
+    // grow-only workspace of vis_ftrack_link_rows (FtWork for n rows of row_cap), apart from the scratch block for the same reason
+    void* d_ft_ws = nullptr; size_t ft_ws_bytes = 0;
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)
@@ -523,6 +533,27 @@ int essential_polish_run(vis_ctx* ctx, const vis_epolish_params* ep, int n, int 
 int homography_polish_run(vis_ctx* ctx, const vis_hpolish_params* hp, int n, int in_stride, const vis_homography_result* d_h, const float* d_p1,
                           const float* d_p2, const int32_t* d_npts, int mask_cap, const uint8_t* d_mask, int out_cap, uint8_t* d_mask_out,
                           vis_hpolish_result* d_out, vis_homography_result* d_h_out);
+// ftrack.hip.  The workspace of one linking call over n frames of R keypoints, declared once: win (2 x n x R: the smallest list position that claimed
+// keypoint k of frame i, then of its parent, 0xFFFFFFFF = none), s0 / s1 (n x R (ancestor, distance) pairs, the two buffers of the pointer doubling), par
+// (n x R parents).  24 bytes per keypoint.
+struct FtWork {
+    uint32_t* win = nullptr; int2* s0 = nullptr; int2* s1 = nullptr; int32_t* par = nullptr;
+    void layout(Carver& cv, size_t n, size_t R) { win = cv.take<uint32_t>(2 * n * R); s0 = cv.take<int2>(n * R); s1 = cv.take<int2>(n * R); par = cv.take<int32_t>(n * R); }
+};
+// The frames' pairing and counts as both forms hold them: prev == nullptr is the gate-off pairing (i - 1; frame 0: the carried frame iff pair0);
+// nkp[i] = keypoints of frame i.
+struct FtFrames { const int32_t* prev; int pair0; const int32_t* nkp; };
+// k_ft_claim + k_ft_parent + the doubling rounds + k_ft_finish (+ k_ft_carry when d_carry_out) on ctx->stream.  R: keypoints per frame the workspace
+// and the counts are sized for; d_links: rows of link_cap; d_mask: rows of mask_cap or null; d_mcnt: null, or a further bound of every list's count
+// (int32 at d_mcnt[i * mcnt_stride]); d_carry: a row of R records or null; d_obs: rows of ocap >= R records of which the first wcap <= ocap are written
+int ftrack_link_run(vis_ctx* ctx, const FtWork& W, int n, int R, FtFrames fr, const vis_dmatch* d_links, const int32_t* d_nlinks, int link_cap,
+                    const uint8_t* d_mask, int mask_cap, const int32_t* d_mcnt, int mcnt_stride, const vis_ftrack_obs* d_carry, int seq0, int ocap,
+                    int wcap, vis_ftrack_obs* d_obs, vis_ftrack_frame* d_frame, vis_ftrack_obs* d_carry_out);
+// k_ftri_clear + k_ftri_mark + k_ftri_points on ctx->stream.  d_xy: the pixel (u, v) of keypoint k of frame i is the two floats at byte
+// i * xy_row + k * xy_step; tp validated by the caller
+int ftrack_triangulate_run(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, int R, FtFrames fr, const vis_ftrack_obs* d_obs, int ocap,
+                           const void* d_xy, size_t xy_row, int xy_step, const double* d_poses, vis_ftrack_point* d_points, uint8_t* d_flags,
+                           vis_ftrack_tri_summary* d_summary);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

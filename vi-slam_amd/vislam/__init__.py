@@ -296,6 +296,25 @@ KLT_TRACKED, KLT_OOB, KLT_FLAT, KLT_ERR, KLT_FB, KLT_INVALID = 1, 2, 4, 8, 16, 3
 KLT_NO_PAIR = 1
 
 
+class FtrackTriParams(C.Structure):
+    """vis_ftrack_tri_params: the knobs of the N-view triangulation of feature tracks (vis_default_ftrack_tri_params: 16, 2, 5, 2.0, cos 1 deg)"""
+    _fields_ = [("max_views", C.c_int32), ("min_views", C.c_int32), ("gn_iters", C.c_int32), ("reserved_", C.c_int32), ("max_reproj_px", C.c_double),
+                ("max_parallax_cos", C.c_double)]
+
+
+FTRACK_OBS_DTYPE = np.dtype([("birth_seq", "<i4"), ("birth_kp", "<i4"), ("len", "<i4"), ("prev_kp", "<i4")])
+FTRACK_FRAME_DTYPE = np.dtype([("seq", "<i4"), ("n_keypoints", "<i4"), ("n_continued", "<i4"), ("n_started", "<i4"), ("n_ended", "<i4"),
+                               ("max_len", "<i4"), ("sum_len", "<i4"), ("flags", "<i4")])
+FTRACK_POINT_DTYPE = np.dtype([("X", "<f8", (3,)), ("rms_reproj_px", "<f4"), ("parallax_cos", "<f4"), ("n_views", "<i4"), ("flags", "<i4")])
+FTRACK_TRI_SUMMARY_DTYPE = np.dtype([("n_ends", "<i4"), ("n_points", "<i4"), ("n_kept", "<i4"), ("n_front", "<i4"), ("n_reproj_ok", "<i4"),
+                                     ("n_parallax_ok", "<i4"), ("n_few", "<i4"), ("n_singular", "<i4")])
+assert FTRACK_OBS_DTYPE.itemsize == 16 and FTRACK_FRAME_DTYPE.itemsize == 32 and FTRACK_POINT_DTYPE.itemsize == 40
+assert FTRACK_TRI_SUMMARY_DTYPE.itemsize == 32 and C.sizeof(FtrackTriParams) == 32
+FT_NO_PAIR, FT_NO_CARRY = 1, 2
+FT_SYM, FT_GOOD = 0, 1
+FTP_FRONT, FTP_REPROJ_OK, FTP_PARALLAX_OK, FTP_KEPT, FTP_FEW, FTP_SINGULAR = 1, 2, 4, 8, 16, 32
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -345,6 +364,7 @@ ABI_SYMBOLS = [
     "vis_debug_pyramid_level",
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
     "vis_default_klt_params", "vis_klt_track", "vis_klt_batch", "vis_batch_klt",
+    "vis_ftrack_link_rows", "vis_batch_ftrack", "vis_default_ftrack_tri_params", "vis_ftrack_triangulate_rows", "vis_batch_ftrack_triangulate",
 ]
 
 
@@ -431,6 +451,14 @@ def _load():
         lib.vis_pnp_ransac.argtypes = [vp, ppp, vp, vp, ci, vp, vp, vp]
         lib.vis_pnp_batch.argtypes = [vp, ppp, ci, vp, ci, vp, vp, ci, vp, ci, vp, vp]
         lib.vis_batch_pnp.argtypes = [vp, ppp, ci, vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    if hasattr(lib, "vis_batch_ftrack"):                # (absent from older A/B builds)
+        ftp = C.POINTER(FtrackTriParams)
+        lib.vis_ftrack_link_rows.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, ci, vp, ci, ci, vp, vp]
+        lib.vis_batch_ftrack.argtypes = [vp, ci, ci, ci, vp, ci, ci, vp, vp]
+        lib.vis_default_ftrack_tri_params.argtypes = [ftp]
+        lib.vis_default_ftrack_tri_params.restype = None
+        lib.vis_ftrack_triangulate_rows.argtypes = [vp, ftp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+        lib.vis_batch_ftrack_triangulate.argtypes = [vp, ftp, ci, vp, ci, vp, vp, vp, vp]
     if hasattr(lib, "vis_essential_refine_batch"):      # (absent from older A/B builds)
         epp = C.POINTER(EssentialRefineParams)
         lib.vis_default_eref_params.argtypes = [epp]
@@ -584,6 +612,12 @@ def default_pnp_params():
     pp = PnpParams()
     lib.vis_default_pnp_params(C.byref(pp))
     return pp
+
+
+def default_ftrack_tri_params():
+    tp = FtrackTriParams()
+    lib.vis_default_ftrack_tri_params(C.byref(tp))
+    return tp
 
 
 def default_eref_params():
@@ -1321,6 +1355,41 @@ class Context:
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_pnp(self._h, C.byref(pp), n, v(d_draws_ptr), v(d_points_ptr), v(d_flags_ptr), row_cap, require, mask_cap,
                                     v(d_mask_ptr), v(d_out_ptr), v(d_link_ptr)), "vis_batch_pnp")
+
+    # -- feature tracks ---------------------------------------------------------------------------------------------
+    def ftrack_link_rows(self, n, d_prev_ptr, d_nkp_ptr, d_links_ptr, d_nlinks_ptr, link_cap, row_cap, d_obs_ptr, d_frame_ptr, seq0=0, d_mask_ptr=0,
+                         mask_cap=0, d_carry_in_ptr=0):
+        """queue the linking of n frames' match lists (rows of link_cap DMATCH_DTYPE, queryIdx in frame prev[i], trainIdx in frame i) into feature
+        tracks on the context's stream (raw DEVICE pointers; 0 / None = NULL for the mask and the carried row): n rows of row_cap FTRACK_OBS_DTYPE
+        and n FTRACK_FRAME_DTYPE records"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_ftrack_link_rows(self._h, n, v(d_prev_ptr), v(d_nkp_ptr), v(d_links_ptr), v(d_nlinks_ptr), link_cap, v(d_mask_ptr), mask_cap,
+                                           v(d_carry_in_ptr), seq0, row_cap, v(d_obs_ptr), v(d_frame_ptr)), "vis_ftrack_link_rows")
+
+    def batch_ftrack(self, n, row_cap, d_obs_ptr, d_frame_ptr, source=FT_SYM, pose_inliers=False, d_mask_ptr=0, mask_cap=0):
+        """link the pairs of the last batch_run (with STAGE_MATCH) into feature tracks on the pose stream, continuing the tracks of the launch
+        linked before it: n rows of row_cap FTRACK_OBS_DTYPE and n FTRACK_FRAME_DTYPE records, in use until batch_sync()"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_ftrack(self._h, source, 1 if pose_inliers else 0, n, v(d_mask_ptr), mask_cap, row_cap, v(d_obs_ptr), v(d_frame_ptr)),
+                  "vis_batch_ftrack")
+
+    def ftrack_triangulate_rows(self, n, d_prev_ptr, d_nkp_ptr, d_obs_ptr, row_cap, d_xy_ptr, d_poses_ptr, d_points_ptr, d_flags_ptr, d_summary_ptr,
+                                tp=None):
+        """queue the N-view triangulation of every track that ends in these n frames on the context's stream (raw DEVICE pointers): d_xy n rows of
+        row_cap (u, v) float pixels, d_poses n x 12 doubles (R row-major, t); n rows of row_cap FTRACK_POINT_DTYPE and flag bytes, n
+        FTRACK_TRI_SUMMARY_DTYPE records"""
+        tp = default_ftrack_tri_params() if tp is None else tp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_ftrack_triangulate_rows(self._h, C.byref(tp), n, v(d_prev_ptr), v(d_nkp_ptr), v(d_obs_ptr), row_cap, v(d_xy_ptr), v(d_poses_ptr),
+                                                  v(d_points_ptr), v(d_flags_ptr), v(d_summary_ptr)), "vis_ftrack_triangulate_rows")
+
+    def batch_ftrack_triangulate(self, n, d_obs_ptr, row_cap, d_poses_ptr, d_points_ptr, d_flags_ptr, d_summary_ptr, tp=None):
+        """the same for the keypoints of the last batch_run with the rows batch_ftrack wrote for it, on the pose stream behind that call; the
+        buffers are in use until batch_sync()"""
+        tp = default_ftrack_tri_params() if tp is None else tp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_ftrack_triangulate(self._h, C.byref(tp), n, v(d_obs_ptr), row_cap, v(d_poses_ptr), v(d_points_ptr), v(d_flags_ptr),
+                                                   v(d_summary_ptr)), "vis_batch_ftrack_triangulate")
 
     # -- the essential-matrix pose on device rows, and its refinement ----------------------------------------------
     def essential_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr):
