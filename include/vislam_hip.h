@@ -238,7 +238,17 @@ int  vis_compute_gradient(vis_ctx* ctx, const uint8_t* img, int w, int h, int st
  * (:413-445): per level l the candidate list as rows (x, y, 1, 1) in the reference's push_back order, built from
  * at most 200 matched keypoints of the previous keyframe.  patch[l] / debug[l] receive up to `cap` rows
  * (VIS_E_CAPACITY if a level has more; n_patch[l] then holds the required count).  Level sizes come from
- * params.w_size >> l, params.h_size >> l (CameraModel w_size[lvl], h_size[lvl]). */
+ * params.w_size >> l, params.h_size >> l (CameraModel w_size[lvl], h_size[lvl]).
+ *   The candidate window, for EVERY float a keypoint can hold.  On level l, with cols x rows the level's size, sp = patch_size[l]
+ *   (5, 3, 2, 5, 5: `patch_size - 1 / 2` in integers) and the level coordinates x = (float)(((double)kp.x + 0.5) * 2^-l - 0.5), y likewise,
+ *   the candidate columns are the integers i with
+ *       0 < i < cols,   i >= trunc(x - sp),   (float)i <= x + sp
+ *   where x - sp and x + sp are the float difference and sum and the comparisons are taken on their values; the rows j likewise with y
+ *   and rows.  The list holds (i, j, 1, 1) for every such column (outer, ascending) and row (inner, ascending), keypoint after keypoint.
+ *   A keypoint whose level coordinate is NaN or infinite contributes none, and so does any whose window cannot touch the level, however
+ *   large the coordinate (the reference's loop `for (int i = (int)(x - sp); (float)i <= x + sp; i++)` converts such a float to int, which
+ *   is undefined, and never ends once x + sp >= 2^31).  Where that loop ends the list is its list.  No float outside [1, size) is
+ *   converted to an integer on this path (csrc/patch_window.h). */
 int  vis_patch_points(vis_ctx* ctx, const vis_keypoint* good, int n, int cap,
                       float* const patch[5], int n_patch[5], float* const debug[5], int n_debug[5]);
 
@@ -275,7 +285,13 @@ void vis_se3_matrix(const vis_se3f* a, float M[16]);
  * vis_compute_gradient write; up to one row / column more than (w>>l) x (h>>l)); 16 <= w, h <= 4095: gray1/gx1/gy1 of the previous keyframe
  * (Frame::grayImage / gradientX / gradientY), gray2 of the current frame, cand1[l] = n_cand[l] rows (x, y, z, 1) as
  * Frame::candidatePoints[l] holds them.  Levels outside [last_level, first_level] may be NULL.  init may be NULL
- * (identity); the reference seeds it from the IMU rotation residual and the ground-truth translation (:1133-1166). */
+ * (identity); the reference seeds it from the IMU rotation residual and the ground-truth translation (:1133-1166).
+ *   VIS_E_INVALID: fx, fy not finite and > 0; cx, cy, epsilon or z_factor not finite.
+ *   A candidate row may hold any float.  Its source pixel is column (int)x, row (int)y where those lie inside the level, that is for
+ *   -1 < x < (w >> l) and -1 < y < (h >> l) ((int)(-0.5) == 0); for every other x or y, NaN included, the row is skipped and the value is
+ *   not converted.  A row whose warped point is NaN, infinite, outside the level, or whose depth P2 is 0 is skipped as well; init is
+ *   taken as given: a NaN in it makes every warped point NaN (the record of a pair without residuals, with that pose), an infinite or
+ *   huge translation is arithmetic like any other (tz = +inf projects every point onto (cx, cy)). */
 int  vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* ap, int w, int h,
                                 const uint8_t* const gray1[5], const uint8_t* const gray2[5],
                                 const int16_t* const gx1[5], const int16_t* const gy1[5],
@@ -286,7 +302,12 @@ int  vis_estimate_pose_features(vis_ctx* ctx, const vis_align_params* ap, int w,
  * candidate points of pair i are generated on the fly from d_pts: max_pts (x, y) floats per pair = the matched
  * keypoints of frame i-1 (Frame::nextGoodMatches, at most 200 are used like the reference), d_npts[i] of them valid; a d_npts[i]
  * above max_pts is clamped to max_pts (below 1: no candidates, the record of a pair without residuals).
- * d_init: n poses or NULL.  Asynchronous on the context's stream.  16 <= w, h <= 4095, stride >= w (any alignment). */
+ * d_init: n poses or NULL.  Asynchronous on the context's stream.  16 <= w, h <= 4095, stride >= w (any alignment).
+ *   The rows of d_pts are device memory the call cannot validate: the candidates of a keypoint are vis_patch_points' window (above),
+ *   which is defined for every float -- a NaN, an infinity or a coordinate of any size whose window does not touch the level contributes no
+ *   candidate, so such an entry among the first min(d_npts[i], max_pts, 200) gives the record of the row without it; entries past that count
+ *   are not read.  d_npts[i] may be any int32.  d_init is taken as given, like vis_estimate_pose_features' init; alignment parameters that
+ *   are not finite are refused (VIS_E_INVALID) before anything is queued. */
 int  vis_align_batch(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int w, int h, int stride, int n,
                      const uint8_t* d_gray, const int16_t* d_gx, const int16_t* d_gy,
                      const float* d_pts, const int32_t* d_npts, int max_pts,
@@ -449,7 +470,9 @@ typedef struct vis_track_result {
                                     (fewer than two frames saved since vis_batch_plan / vis_batch_reset) */
 } vis_track_result;              /* 32 bytes */
 /* final_poseCam to continue from (InitializeSystemGPU's initial camera pose, src/VISystemGPU.cpp:107-115); NULL = identity.  Sets
- * the current pose of the chain (the last residual is kept) and the pose vis_batch_reset restarts at.  Needs a plan; synchronises. */
+ * the current pose of the chain (the last residual is kept) and the pose vis_batch_reset restarts at.  Needs a plan; synchronises.
+ * The pose is taken as given -- not normalised, not tested: a component that is NaN or infinite stays in the chain, and every
+ * final_poseCam composed from it carries what Sophus' product makes of it (d_align is not affected: the alignments do not read it). */
 int  vis_batch_track_init(vis_ctx* ctx, const vis_se3f* pose);
 int  vis_batch_track(vis_ctx* ctx, const vis_align_params* ap, const uint8_t* d_frames, int n,
                      const vis_se3f* d_init, vis_align_result* d_align, vis_track_result* d_track);

@@ -324,8 +324,11 @@ extern "C" int orc_estimate_pose_features(const vis_align_params* ap, int w, int
                 Jw[1][3] = -(fy * (1 + y2 * y2 * inv_z2 * inv_z2));
                 Jw[1][4] = fy * x2 * y2 * inv_z2 * inv_z2;
                 Jw[1][5] = -fy * x2 * inv_z2;
-                const int ix1 = (int)x1, iy1 = (int)y1;                                      // at<uchar>(y1, x1): float -> int
-                if (ix1 < 0 || ix1 >= cols || iy1 < 0 || iy1 >= rows) continue;              // SPEC: the builders never emit such points
+                // at<uchar>(y1, x1): float -> int.  SPEC: the builders never emit points outside the level, and (int) of a NaN or of a float
+                // beyond int's range is undefined (x86 gives INT_MIN, the device 0 or a saturated value): a row is read where
+                // 0 <= (int)x1 < cols, which is -1 < x1 < cols ((int)(-0.5) == 0), and skipped for every other float, unconverted
+                if (!(x1 > -1.f && x1 < (float)cols && y1 > -1.f && y1 < (float)rows)) continue;
+                const int ix1 = (int)x1, iy1 = (int)y1;
                 int rx = (int)std::round(x2), ry = (int)std::round(y2);                      // :1305
                 if (rx > acols - 1) rx = acols - 1;                                          // SPEC clamp (see header): to the Mat's own size
                 if (ry > arows - 1) ry = arows - 1;

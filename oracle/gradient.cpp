@@ -51,6 +51,23 @@ extern "C" int orc_scharr_gradient(const uint8_t* img, int w, int h, int stride,
     return VIS_OK;
 }
 
+// The candidate columns (rows) of one keypoint: the integers i with 0 < i < size, i >= trunc(c - sp) and (float)i <= c + sp, the sum and
+// the difference in float as src/Camera.cpp:381-384 forms them.  SPEC decision where the reference is undefined: its loop
+//   for (int i = (int)(c - sp); (float)i <= c + sp; i++) if (i > 0 && i < size) ...
+// converts a float outside int's range and never ends once c + sp >= 2^31 (i++ overflows while the condition still holds).  The rule is
+// stated on the values instead: a NaN or infinite c has no window, and both ends are brought into [1, size - 1] as doubles before they
+// become ints.  Where the loop ends, this is its list.  (An independent restatement: the product's helper is not included here.)
+static bool candidate_window(float c, int sp, int size, int* first, int* last) {
+    if (!std::isfinite(c)) return false;
+    const float from = c - (float)sp, to = c + (float)sp;
+    double lo = std::trunc((double)from), hi = std::floor((double)to);      // (float)i <= to  <=>  i <= floor(to) for an integer i
+    if (lo < 1.0) lo = 1.0;
+    if (hi > (double)(size - 1)) hi = (double)(size - 1);
+    if (lo > hi) return false;
+    *first = (int)lo; *last = (int)hi;
+    return true;
+}
+
 // src/Camera.cpp:358-410.  `patch_size[lvl] - 1 / 2` is integer arithmetic: 1/2 == 0, so start_point == patch_size.
 extern "C" int orc_patch_points(const vis_keypoint* good, int n, const int32_t* lw, const int32_t* lh, int level,
                                 float* xyzw, int cap, int* n_out) {
@@ -63,12 +80,13 @@ extern "C" int orc_patch_points(const vis_keypoint* good, int n, const int32_t* 
     for (int k = 0; k < m; k++) {
         const float x = (float)(((double)good[k].x + 0.5) * (double)factor_lvl - 0.5);
         const float y = (float)(((double)good[k].y + 0.5) * (double)factor_lvl - 0.5);
-        for (int i = (int)(x - (float)start_point); (float)i <= x + (float)start_point; i++)
-            for (int j = (int)(y - (float)start_point); (float)j <= y + (float)start_point; j++)
-                if (i > 0 && i < lw[level] && j > 0 && j < lh[level]) {
-                    if (xyzw && cnt < cap) { xyzw[4 * cnt] = (float)i; xyzw[4 * cnt + 1] = (float)j; xyzw[4 * cnt + 2] = 1.0f; xyzw[4 * cnt + 3] = 1.0f; }
-                    cnt++;
-                }
+        int i0, i1, j0, j1;
+        if (!candidate_window(x, start_point, lw[level], &i0, &i1) || !candidate_window(y, start_point, lh[level], &j0, &j1)) continue;
+        for (int i = i0; i <= i1; i++)
+            for (int j = j0; j <= j1; j++) {
+                if (xyzw && cnt < cap) { xyzw[4 * cnt] = (float)i; xyzw[4 * cnt + 1] = (float)j; xyzw[4 * cnt + 2] = 1.0f; xyzw[4 * cnt + 3] = 1.0f; }
+                cnt++;
+            }
     }
     *n_out = cnt;
     return (xyzw && cnt > cap) ? VIS_E_CAPACITY : VIS_OK;

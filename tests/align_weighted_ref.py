@@ -116,9 +116,12 @@ def estimate_pose_features(orc, ap, w, h, gray1, gray2, gx1, gy1, cand1, init=No
                 inv_z2 = f32(1) / z2
                 valid = (y2 > 0) & (y2 < arows) & (x2 > 0) & (x2 < acols) & (z2 != 0)
                 inv_z2 = np.where(inv_z2 < 0, f32(0), inv_z2).astype(f32)
-                ix1 = np.trunc(np.where(np.isfinite(x1), x1, -1)).astype(np.int64)
-                iy1 = np.trunc(np.where(np.isfinite(y1), y1, -1)).astype(np.int64)
-                valid &= ~((ix1 < 0) | (ix1 >= cols) | (iy1 < 0) | (iy1 >= rows))
+                # 0 <= (int)x1 < cols is -1 < x1 < cols ((int)(-0.5) == 0): decided on the floats, so that no value outside the level -- NaN,
+                # +-inf, +-3e38 -- is ever cast to an integer
+                inside = (x1 > -1) & (x1 < cols) & (y1 > -1) & (y1 < rows)
+                ix1 = np.trunc(np.where(inside, x1, 0)).astype(np.int64)
+                iy1 = np.trunc(np.where(inside, y1, 0)).astype(np.int64)
+                valid &= inside
                 idx = np.nonzero(valid)[0]
                 nres = len(idx)
                 if nres == 0:

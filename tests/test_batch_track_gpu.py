@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import align_cases
+from batch_track_cases import Oracle as _Oracle, decode as _decode, residual as _residual
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,46 +56,10 @@ def _out(vislam, n, sync=True):
     return a, t
 
 
-def _decode(vislam, a, t, n):
-    ra, rt = a.cpu().numpy().tobytes(), t.cpu().numpy().tobytes()
-    sa, st = C.sizeof(vislam.AlignResult), C.sizeof(vislam.TrackResult)
-    return ([vislam.AlignResult.from_buffer_copy(ra, i * sa) for i in range(n)], [vislam.TrackResult.from_buffer_copy(rt, i * st) for i in range(n)],
-            ra, rt)
-
-
 def _track(vislam, c, ap, ptr, n, d_init=0, out=None):
     a, t = out or _out(vislam, n)
     c.batch_track(ap, ptr, n, d_init, a.data_ptr(), t.data_ptr())
     return a, t
-
-
-def _residual(orc, pose):
-    M = orc.se3_matrix(pose)
-    return orc.se3_from_rt(M[:3, :3], M[:3, 3])
-
-
-class _Oracle:
-    """EstimatePoseFeatures (prev -> cur) on the matched keypoints of prev, cached by pair and points; frames of w x h"""
-    def __init__(self, orc, frames, w=W, h=H):
-        self.orc, self.frames, self.lv, self.cache, self.w, self.h = orc, frames, {}, {}, w, h
-
-    def levels(self, g):
-        if g not in self.lv:
-            pyr = self.orc.half_pyramid(self.frames[g])
-            gx, gy = [], []
-            for lv in pyr:
-                a, b, _ = self.orc.scharr_gradient(lv, 3)
-                gx.append(a); gy.append(b)
-            self.lv[g] = (pyr, gx, gy)
-        return self.lv[g]
-
-    def align(self, j, g, prev_kp):
-        key = (j, g, prev_kp.tobytes())
-        if key not in self.cache:
-            (p0, gx, gy), (p1, _, _) = self.levels(j), self.levels(g)
-            cand = [self.orc.patch_points(prev_kp, self.w, self.h, l) for l in range(5)]
-            self.cache[key] = self.orc.estimate_pose_features(self.orc.default_align_params(), self.w, self.h, p0, p1, gx, gy, cand)
-        return self.cache[key]
 
 
 @pytest.fixture(scope="module")

@@ -51,6 +51,7 @@ struct AlignArgs {
 };
 
 #include "se3_core.h"
+#include "patch_window.h"
 
 // hal::LU32f as cv::invert(DECOMP_LU) uses it: A (6x6, row-major, LDS) -> B = inverse; false = singular.  The matrices are
 // held in registers for the factorisation (fully unrolled; a row exchange with the runtime pivot row is a chain of selects):
@@ -131,9 +132,9 @@ DEV bool warp_offsets(const AlignLevel& V, const uint32_t* plist, int i, const d
     float x2 = P0 * V.fx; x2 = x2 / P2; x2 = x2 + V.cx;
     float y2 = P1 * V.fy; y2 = y2 / P2; y2 = y2 + V.cy;
     x2 = x2 * P3; y2 = y2 * P3;
-    const int ix1 = (int)x1, iy1 = (int)y1;
+    int ix1 = 0, iy1 = 0;
     if (!((y2 > 0 && y2 < V.arows && x2 > 0 && x2 < V.acols) && (P2 != 0))) return false;
-    if (ix1 < 0 || ix1 >= V.cols || iy1 < 0 || iy1 >= V.rows) return false;
+    if (!source_index(x1, V.cols, ix1) || !source_index(y1, V.rows, iy1)) return false;
     int rx = (int)roundf(x2), ry = (int)roundf(y2);
     if (rx > V.acols - 1) rx = V.acols - 1;
     if (ry > V.arows - 1) ry = V.arows - 1;
@@ -187,13 +188,14 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
             const int patch_size = lvl == 1 ? 3 : (lvl == 2 ? 2 : 5);
             const int sp = patch_size - 1 / 2;                                      // :376, integer 1/2 == 0
             const float factor_lvl = (float)(1.0 / (double)(1 << lvl));
-            float x = 0, y = 0; int cnt = 0;
+            // the window of a keypoint, clamped to the level before any float becomes an int (patch_window.h): a coordinate that is NaN,
+            // infinite or beyond int's range gives an empty one, where the reference's loop would not end
+            PatchSpan wx = {1, 0}, wy = {1, 0}; int cnt = 0;
             if (tid < m) {
-                x = (float)(((double)kp[2 * tid] + 0.5) * (double)factor_lvl - 0.5);
-                y = (float)(((double)kp[2 * tid + 1] + 0.5) * (double)factor_lvl - 0.5);
-                for (int i = (int)(x - (float)sp); (float)i <= x + (float)sp; i++)
-                    for (int j = (int)(y - (float)sp); (float)j <= y + (float)sp; j++)
-                        if (i > 0 && i < cols && j > 0 && j < rows) cnt++;
+                const float x = (float)(((double)kp[2 * tid] + 0.5) * (double)factor_lvl - 0.5);
+                const float y = (float)(((double)kp[2 * tid + 1] + 0.5) * (double)factor_lvl - 0.5);
+                wx = patch_span(x, sp, cols); wy = patch_span(y, sp, rows);
+                cnt = patch_span_count(wx) * patch_span_count(wy);
             }
             __syncthreads();                                                         // previous level done with plist / s_pre
             // exclusive prefix of the per-keypoint counts: wave scans by shuffles + the three wave totals (one thread walking
@@ -212,9 +214,9 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
             }
             if (tid < m) {
                 int o = s_pre[tid];
-                for (int i = (int)(x - (float)sp); (float)i <= x + (float)sp; i++)
-                    for (int j = (int)(y - (float)sp); (float)j <= y + (float)sp; j++)
-                        if (i > 0 && i < cols && j > 0 && j < rows) plist[o++] = ((uint32_t)j << 16) | (uint32_t)i;
+                if (cnt)
+                    for (int i = wx.lo; i <= wx.hi; i++)
+                        for (int j = wy.lo; j <= wy.hi; j++) plist[o++] = ((uint32_t)j << 16) | (uint32_t)i;
             }
             N = s_pre[AL_THREADS];
             __syncthreads();
@@ -335,12 +337,13 @@ __global__ __launch_bounds__(AL_THREADS) void k_align(AlignArgs G) {
                         x2 = x2 * P3; y2 = y2 * P3;
                         const float z2 = P2;
                         float inv_z2 = 1 / z2;
-                        const int ix1 = (int)x1, iy1 = (int)y1;
+                        int ix1 = 0, iy1 = 0;
+                        const bool src_in = source_index(x1, cols, ix1) && source_index(y1, rows, iy1);   // (int)x1, (int)y1 where they index the level
                         // the warped point is tested against the size of the Mat it indexes (src/VISystem.cpp:1299: image2.rows / image2.cols
                         // = Camera::Update's level size, up to one row / column MORE than the bookkeeping `size >> lvl`)
                         bool v = (y2 > 0 && y2 < V.arows && x2 > 0 && x2 < V.acols) && (z2 != 0);
                         if (inv_z2 < 0) inv_z2 = 0;
-                        v = v && !(ix1 < 0 || ix1 >= cols || iy1 < 0 || iy1 >= rows);
+                        v = v && src_in;
                         if (v) {
                             int rx = (int)roundf(x2), ry = (int)roundf(y2);
                             if (rx > V.acols - 1) rx = V.acols - 1;
@@ -463,6 +466,10 @@ static int check_align_params(vis_ctx* ctx, const vis_align_params* ap, int w, i
     }
     if (w < 16 || h < 16 || w > VIS_MAX_SIDE || h > VIS_MAX_SIDE || !(ap->fx > 0) || !(ap->fy > 0)) {
         ctx->err = "alignment: 16 <= w, h <= 4095, fx, fy > 0"; return VIS_E_INVALID;
+    }
+    if (!std::isfinite(ap->fx) || !std::isfinite(ap->fy) || !std::isfinite(ap->cx) || !std::isfinite(ap->cy) || !std::isfinite(ap->epsilon) ||
+        !std::isfinite(ap->z_factor)) {
+        ctx->err = "alignment: fx, fy, cx, cy, epsilon and z_factor must be finite"; return VIS_E_INVALID;
     }
     return VIS_OK;
 }

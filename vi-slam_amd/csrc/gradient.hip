@@ -10,6 +10,7 @@
 // HBM bound.  Thread = 8 pixels x GR_ROWS rows with a register sliding window over rows; a row is one unaligned
 // 16-byte load widened to five v_pk_*_i16 operands; the Scharr responses of a pixel pair are 6 packed instructions.
 #include "vis_internal.h"
+#include "patch_window.h"
 
 typedef short pk16 __attribute__((ext_vector_type(2)));
 typedef unsigned short upk16 __attribute__((ext_vector_type(2)));
@@ -204,13 +205,14 @@ __global__ __launch_bounds__(256) void k_patch_points(const vis_keypoint* __rest
     const int lw = lw0 >> level, lh = lh0 >> level;
     const float factor_lvl = (float)(1.0 / (double)(1 << level));
     const int m = min(n, 200);
-    float x = 0, y = 0; int cnt = 0;
+    // the window of a keypoint, clamped to the level before any float becomes an int (patch_window.h): a coordinate that is NaN,
+    // infinite or beyond int's range gives an empty one, where the reference's loop would not end
+    PatchSpan wx = {1, 0}, wy = {1, 0}; int cnt = 0;
     if (tid < m) {
-        x = (float)(((double)good[tid].x + 0.5) * (double)factor_lvl - 0.5);
-        y = (float)(((double)good[tid].y + 0.5) * (double)factor_lvl - 0.5);
-        for (int i = (int)(x - (float)sp); (float)i <= x + (float)sp; i++)
-            for (int j = (int)(y - (float)sp); (float)j <= y + (float)sp; j++)
-                if (i > 0 && i < lw && j > 0 && j < lh) cnt++;
+        const float x = (float)(((double)good[tid].x + 0.5) * (double)factor_lvl - 0.5);
+        const float y = (float)(((double)good[tid].y + 0.5) * (double)factor_lvl - 0.5);
+        wx = patch_span(x, sp, lw); wy = patch_span(y, sp, lh);
+        cnt = patch_span_count(wx) * patch_span_count(wy);
     }
     pre[tid + 1] = cnt;
     if (tid == 0) pre[0] = 0;
@@ -220,9 +222,9 @@ __global__ __launch_bounds__(256) void k_patch_points(const vis_keypoint* __rest
     if (tid < m) {
         int o = pre[tid];
         float* dst = out + (size_t)level * cap * 4;
-        for (int i = (int)(x - (float)sp); (float)i <= x + (float)sp; i++)
-            for (int j = (int)(y - (float)sp); (float)j <= y + (float)sp; j++)
-                if (i > 0 && i < lw && j > 0 && j < lh) {
+        if (cnt)
+            for (int i = wx.lo; i <= wx.hi; i++)
+                for (int j = wy.lo; j <= wy.hi; j++) {
                     if (o < cap) { dst[4 * o] = (float)i; dst[4 * o + 1] = (float)j; dst[4 * o + 2] = 1.0f; dst[4 * o + 3] = 1.0f; }
                     o++;
                 }
