@@ -76,13 +76,19 @@ typedef struct vis_params {
     int32_t patch_size;       /* 31   */
     int32_t fast_threshold;   /* 20   */
     /* matcher post-filters -- src/Matcher.cpp:103 (0.8f), calibration/calibrationEUROC.xml:54 (49) */
+    /* ratio: any float, taken as written -- a match survives iff !(d0 > (double)ratio * d1), so 0 keeps only d0 = 0, a negative ratio
+     * only d0 = d1 = 0, NaN and +inf every match that has two neighbours (tests/match_param_cases.py).
+     * n_cells: the grid is floor(sqrt(n_cells)) squared and that root is at most VIS_MAX_GRID_ROOT, i.e. 1 <= n_cells <=
+     * 1088; a larger n_cells is refused by vis_set_params (VIS_E_INVALID, vis_last_error names the limit), never clamped to another
+     * grid.  sym_mode: one of VIS_SYM_*, anything else is refused. */
     float   ratio;            /* 0.8f */
     int32_t n_cells;          /* 49   */
-    int32_t w_size, h_size;   /* Matcher::setImageDimensions, src/Matcher.cpp:30-34 */
+    int32_t w_size, h_size;   /* Matcher::setImageDimensions, src/Matcher.cpp:30-34; >= 1 */
     int32_t sym_mode;         /* VIS_SYM_* */
     /* essential RANSAC -- src/VISystem.cpp:1680 (prob 0.999, thr 1.0); OpenCV 3.2 maxIters = 1000 */
     double  ransac_prob;      /* 0.999 */
-    double  ransac_threshold; /* 1.0 px */
+    double  ransac_threshold; /* 1.0 px; 1e-18 <= ransac_threshold / fx <= 1e18, else vis_set_params refuses it: 0 and NaN accept
+                               * nothing, +inf everything, a negative value is its positive twin squared (tests/test_ransac_params_ref.py) */
     int32_t ransac_max_iters; /* 1000 */
     int32_t ransac_adaptive;  /* 1 = OpenCV adaptive stop, 0 = always max_iters (timing runs) */
     uint64_t ransac_seed;     /* 0xFFFFFFFFFFFFFFFF = cv::RNG((uint64)-1) */
@@ -90,7 +96,8 @@ typedef struct vis_params {
     double  fx, fy, cx, cy;
     /* F2FRansac -- src/VISystem.cpp:709 (1000 iterations), :523 (threshold 370) */
     int32_t f2f_iters;        /* 1000 */
-    double  f2f_threshold;    /* 370  */
+    double  f2f_threshold;    /* 370; any double, compared as written (error < threshold): NaN counts nothing, 0 and a negative value only an
+                               * |x| that rounding left above 1, +inf every correspondence with a usable normal (tests/test_ransac_params_gpu.py) */
     /* which correspondences the batched pose stage consumes: the reference pipeline feeds the grid-filtered good
      * matches (Frame::next/prevGoodMatches, src/VISystem.cpp:1673-1674); BASELINE config 3 asks for RANSAC on the
      * un-gridded symmetric matches (M up to N) */

@@ -11,7 +11,13 @@ module: shared by tests/test_hostile_inputs_ref.py (CPU) and tests/test_hostile_
 
 Kinds are written "target:name".  The target names the array of `arrays` (a dict) that is changed; "both" = "p1" and "p2".
   pixel kinds (float32 m x 2): nan (x), pinf (y = +inf), ninf (x = -inf), inf_all (both coordinates +inf), big (+-3e38, signs alternating),
-                               dup (p2 = p1 whatever the target: a correspondence that did not move)
+                               dup (p2 = p1 whatever the target: a correspondence that did not move),
+                               mag+<k> / mag-<k> (targets p1, p2, xy only): ONE coordinate of each entry -- x of the even entries of idx, y of
+                               the odd ones -- becomes c +- fx k sqrt(FLT_MAX) rounded to float (c = cx or cy): a finite pixel whose NORMALISED
+                               coordinate is +-k sqrt(FLT_MAX) = +-k 1.84e19, k on MAG_LADDER: from ordinary numbers through the magnitude whose
+                               square overflows a float (where single-precision error radii become +inf) to a pixel of 8e36, a factor 40
+                               below FLT_MAX.  Never on both images: no hole was seen there, and "both:" keeps its six kinds.  Layouts
+                               stride5, first3 and tile_edge
   point kinds (float64 m x 3, target "X"): nan (x), pinf (z = +inf), ninf (x = -inf), inf_all, x1e200, x1e160 (just above sqrt(DBL_MAX) =
                                1.34e154 in camera depth), x1e150 (just below: an ordinary, wrong, finite point), mirror (through the camera
                                centre: the same pixel, W < 0), centre (at the camera centre: W = 0 up to rounding), tiny (every entry becomes
@@ -22,6 +28,7 @@ import numpy as np
 import homography_pose_ref as hpr
 import homography_ref as hr
 import pnp_ref as pr
+import pose_degenerate_cases as pdc
 import triangulate_ref as tr
 
 PIXEL_KINDS = ("nan", "pinf", "ninf", "inf_all", "big", "dup")
@@ -29,6 +36,13 @@ POINT_KINDS = ("nan", "pinf", "ninf", "inf_all", "x1e200", "x1e160", "x1e150", "
 NONFINITE = ("nan", "pinf", "ninf", "inf_all")
 LAYOUTS = ("stride5", "first3", "all", "tile_edge")
 DBL_MAX = 1.7976931348623157e308
+FLT_MAX = float(np.finfo(np.float32).max)
+ROOT_FLT_MAX = float(np.sqrt(np.float64(FLT_MAX)))                     # 1.8446743e19
+# the normalised magnitudes of the mag kinds, in units of sqrt(FLT_MAX); a step whose pixel fx k sqrt(FLT_MAX) would pass FLT_MAX is dropped
+MAG_LADDER = tuple(k for k in (1e-12, 1e-6, 0.5, 0.99, 1.1, 1.6, 2.7, 5.4, 54.0, 1e6, 1e15) if pdc.FOCAL * k * ROOT_FLT_MAX < FLT_MAX)
+MAG_NAMES = tuple(f"mag{s}{k:g}" for k in MAG_LADDER for s in "+-")
+MAG_LAYOUTS = ("stride5", "first3", "tile_edge")
+MAG_NEVER_FROM = 1e-6                                                  # from this step up a ladder entry may be in no essential-matrix mask
 MARGIN = 1e-9                                                          # exact_inlier's verdict is compared where the point is farther than this
 
 
@@ -45,6 +59,13 @@ def layout(name, m, tile=None):
     raise ValueError(name)
 
 
+def mag_pixel(name, axis):
+    """the float32 pixel coordinate (axis 0 = x, 1 = y) of the ladder step "mag+<k>" / "mag-<k>": c +- fx k sqrt(FLT_MAX), finite"""
+    v = np.float32((pdc.CX, pdc.CY)[axis] + float(name[3:]) * ROOT_FLT_MAX * pdc.FOCAL)     # (the sign is part of the number)
+    assert name in MAG_NAMES and np.isfinite(v)
+    return v
+
+
 def _pixels(name, a, idx):
     a = np.array(a, np.float32)
     if name == "nan":
@@ -58,6 +79,8 @@ def _pixels(name, a, idx):
     elif name == "big":
         sgn = np.where(np.arange(len(idx)) % 2 == 0, 1.0, -1.0).astype(np.float32)
         a[idx, 0], a[idx, 1] = np.float32(3e38) * sgn, -np.float32(3e38) * sgn
+    elif name.startswith("mag"):
+        a[idx[0::2], 0], a[idx[1::2], 1] = mag_pixel(name, 0), mag_pixel(name, 1)
     else:
         raise ValueError(name)
     return a
@@ -100,7 +123,7 @@ def hostile(kind, arrays, idx):
         assert name in POINT_KINDS
         out["X"] = _points(name, arrays, idx)
     else:
-        assert name in PIXEL_KINDS
+        assert name in PIXEL_KINDS or (name in MAG_NAMES and target != "both")
         for key in (("p1", "p2") if target == "both" else (target,)):
             out[key] = _pixels(name, arrays[key], idx)
     return out
@@ -109,6 +132,21 @@ def hostile(kind, arrays, idx):
 def pair_kinds():
     """the pixel kinds of a two-image row: every name on image 1, image 2 and both (dup once)"""
     return [f"{t}:{k}" for k in PIXEL_KINDS[:-1] for t in ("p1", "p2", "both")] + ["p2:dup"]
+
+
+def mag_pair_kinds():
+    """the magnitude ladder of a two-image row: every step with both signs on image 1 and on image 2 (never both: see the module text)"""
+    return [f"{t}:{n}" for n in MAG_NAMES for t in ("p1", "p2")]
+
+
+def mag_pnp_kinds():
+    return [f"xy:{n}" for n in MAG_NAMES]
+
+
+def mag_of(kind):
+    """the |k| of a mag kind, None of any other"""
+    name = kind.split(":")[1]
+    return abs(float(name[3:])) if name.startswith("mag") else None
 
 
 def pnp_kinds():
@@ -284,6 +322,11 @@ def pnp_rows():
                 h = hostile(kind, base, idx)
                 rec, mask = pr.pnp(cam, pp, h["X"], h["xy"], draws)
                 rows[kind, lay] = dict(X=h["X"], xy=h["xy"], idx=idx, rec=rec, mask=mask)
+            for kind in (mag_pnp_kinds() if lay in MAG_LAYOUTS else ()):
+                h = hostile(kind, base, idx)
+                with np.errstate(all="ignore"):
+                    rec, mask = pr.pnp(cam, pp, h["X"], h["xy"], draws)
+                rows[kind, lay] = dict(X=h["X"], xy=h["xy"], idx=idx, rec=rec, mask=mask)
         return rows, clean
     return _once("pnp_rows", make)
 
@@ -310,9 +353,10 @@ def h_rows():
             if m not in clean:
                 clean[m] = hr.homography(cam, hp, base["p1"], base["p2"], draws)
             idx = layout(lay, m, TILE)
-            for kind in pair_kinds():
+            for kind in pair_kinds() + (mag_pair_kinds() if lay in MAG_LAYOUTS else []):
                 h = hostile(kind, base, idx)
-                rec, mask = hr.homography(cam, hp, h["p1"], h["p2"], draws)
+                with np.errstate(all="ignore"):
+                    rec, mask = hr.homography(cam, hp, h["p1"], h["p2"], draws)
                 rows[kind, lay] = dict(p1=h["p1"], p2=h["p2"], idx=idx, rec=rec, mask=mask)
         return rows, clean
     return _once("h_rows", make)
@@ -350,7 +394,7 @@ def f2f_rows(p):
             if m not in clean:
                 clean[m] = one(base["p1"], base["p2"], base, np.zeros(0, np.int64))
             idx = layout(lay, m, TILE)
-            for kind in pair_kinds():
+            for kind in pair_kinds() + (mag_pair_kinds() if lay in MAG_LAYOUTS else []):
                 h = hostile(kind, base, idx)
                 rows[kind, lay] = one(h["p1"], h["p2"], base, idx)
         return rows, clean
@@ -359,6 +403,7 @@ def f2f_rows(p):
 
 ESSENTIAL_LENGTHS = (40, 64, 257, 300)                                 # the work-list kernels carry hostile and clean rows together
 ESSENTIAL_LAYOUTS = ("stride5", "first3", "all")
+ESSENTIAL_MAG_LENGTHS = (40, 257, 300)
 
 
 def essential_base(m):
@@ -389,6 +434,11 @@ def essential_rows(orc, op):
                         continue
                     h = hostile(kind, base, idx)
                     rows[kind, lay, m] = one(h["p1"], h["p2"], idx)
+                # the magnitude ladder: on one image (where the single-precision scorer's radii overflowed alone), at 40 and at the
+                # lengths above 256 -- the staged form and the ballot form of k_hyp_score
+                for kind in (mag_pair_kinds() if lay in MAG_LAYOUTS and m in ESSENTIAL_MAG_LENGTHS else []):
+                    h = hostile(kind, base, idx)
+                    rows[kind, lay, m] = one(h["p1"], h["p2"], idx)
         return rows, clean
     return _once("essential_rows", make)
 
@@ -415,7 +465,7 @@ def tri_rows():
         clean = one(base["p1"], base["p2"], np.zeros(0, np.int64))
         for lay in ("stride5", "first3", "all"):
             idx = layout(lay, M)
-            for kind in pair_kinds():
+            for kind in pair_kinds() + (mag_pair_kinds() if lay in MAG_LAYOUTS else []):
                 h = hostile(kind, base, idx)
                 rows[kind, lay] = one(h["p1"], h["p2"], idx)
         rows["t:zero", "none"] = one(base["p1"], base["p2"], np.zeros(0, np.int64), np.zeros(3))
@@ -552,6 +602,8 @@ def check_essential_row(kind, lay, m, row, E, mask, ninl, iters, R, t, ngood, ma
     E, R, t = np.asarray(E, np.float64).reshape(9), np.asarray(R, np.float64).reshape(9), np.asarray(t, np.float64)
     assert int(ninl) == int(np.asarray(mask).sum()) and np.isfinite(E).all(), where
     if kind in PAIR_NONFINITE or (kind in PAIR_NEVER and lay != "all"):   # (a whole row of +-3e38 is two finite points: a model may explain it)
+        assert not np.asarray(mask)[idx].any(), (where, np.flatnonzero(np.asarray(mask)[idx]))
+    if (mag_of(kind) or 0.0) >= MAG_NEVER_FROM:                        # (the scenes are chosen so that none lies on the winner's epipolar line)
         assert not np.asarray(mask)[idx].any(), (where, np.flatnonzero(np.asarray(mask)[idx]))
     if lay == "all" and kind in PAIR_NONFINITE:
         assert not E.any() and int(ninl) == 0 and int(iters) == max_iters and int(ngood) == 0, (where, ninl, iters)

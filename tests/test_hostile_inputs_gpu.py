@@ -1,5 +1,7 @@
 """GPU: the geometry entry points that take caller-supplied rows, on correspondences that are not usable numbers (tests/hostile_cases.py: NaN,
-+-inf, +-3e38, overflowing or degenerate map points, duplicates; every fifth entry, the first three, all, the two sides of an LDS tile's end).
++-inf, +-3e38, overflowing or degenerate map points, duplicates; every fifth entry, the first three, all, the two sides of an LDS tile's end),
+and on finite pixels of one image along a ladder of magnitudes through sqrt(FLT_MAX) in normalised coordinates (the "mag" kinds), which the
+essential RANSAC's single-precision scorer once counted as certain inliers.
 
 Per entry point: the hostile rows are interleaved with clean rows of the existing case lists in one launch, and the clean rows' records and
 masks must be BYTE-IDENTICAL to a launch of the clean rows alone (one bad entry changes nothing for anybody else); every hostile row equals
@@ -95,7 +97,7 @@ def test_pnp_batch(vislam, x_stride):
     clean40 = [pr.make_scene(*case)[:2] for case in pr.table_cases() if case[1] == 40]
     cleanT = [pr.make_scene(cls, m, 0.3, 0.25)[:2] for cls, m in (("general", T - 1), ("plane", T), ("dup", T + 1))]
     for max_pts, lays, clean in ((40, ("stride5", "first3", "all"), clean40), (T + 1, ("tile_edge",), cleanT)):
-        keys = [(kind, lay) for lay in lays for kind in hc.pnp_kinds()]
+        keys = [(kind, lay) for lay in lays for kind in hc.pnp_kinds() + (hc.mag_pnp_kinds() if lay in hc.MAG_LAYOUTS else [])]
         mixed = _interleave([(rows[k]["X"], rows[k]["xy"]) for k in keys], clean)
         recs, masks = _pnp_launch(vislam, torch, c, [r for r, _, _ in mixed], max_pts, x_stride, d_draws)
         alone_r, alone_m = _pnp_launch(vislam, torch, c, clean, max_pts, x_stride, d_draws)
@@ -177,7 +179,7 @@ def test_homography_batch(vislam):
     c = vislam.Context(0, p)
     d_draws = _dev(torch, draws)
     for max_pts, lays, clean in sets:
-        keys = [(kind, lay) for lay in lays for kind in hc.pair_kinds()]
+        keys = [(kind, lay) for lay in lays for kind in hc.pair_kinds() + (hc.mag_pair_kinds() if lay in hc.MAG_LAYOUTS else [])]
         mixed = _interleave([(rows[k]["p1"], rows[k]["p2"]) for k in keys], clean)
         recs, masks, _ = _h_launch(vislam, torch, c, [r for r, _, _ in mixed], max_pts, d_draws)
         alone_r, alone_m, _ = _h_launch(vislam, torch, c, clean, max_pts, d_draws)
@@ -232,7 +234,7 @@ def test_homography_pose_batch(vislam):
     d_draws = _dev(torch, hc.h_draws())
     kinds = set()
     for max_pts, lays, clean in sets:
-        keys = [(kind, lay) for lay in lays for kind in hc.pair_kinds()]
+        keys = [(kind, lay) for lay in lays for kind in hc.pair_kinds() + (hc.mag_pair_kinds() if lay in hc.MAG_LAYOUTS else [])]
         mixed = _interleave([(rows[k]["p1"], rows[k]["p2"]) for k in keys], clean)
         hrecs, masks, bufs = _h_launch(vislam, torch, c, [r for r, _, _ in mixed], max_pts, d_draws)
         poses = _hpose_launch(vislam, torch, c, len(mixed), bufs, max_pts)
@@ -336,7 +338,7 @@ def test_f2f_batch_and_filter(vislam):
         return out
     for max_pts, lays, clean in ((120, ("stride5", "first3", "all"), clean_rows((0, 1, 2, 3, 40, 60, 90, 120))),
                                  (T + 1, ("tile_edge",), clean_rows((T - 1, T, T + 1)))):
-        keys = [(kind, lay) for lay in lays for kind in hc.pair_kinds()]
+        keys = [(kind, lay) for lay in lays for kind in hc.pair_kinds() + (hc.mag_pair_kinds() if lay in hc.MAG_LAYOUTS else [])]
         mixed = _interleave([rows[k] for k in keys], clean)
         recs, keeps, nkeeps = _f2f_launch(vislam, torch, c, [r for r, _, _ in mixed], max_pts, d_draws)
         alone = _f2f_launch(vislam, torch, c, clean, max_pts, d_draws)
@@ -444,6 +446,38 @@ def test_essential_batch(vislam, orc):
     print(f"essential: {len(keys)} hostile and {len(clean)} clean rows, {models} hostile rows with a model")
     recs2, masks2 = _essential_launch(vislam, torch, c, [r for r, _, _ in mixed])
     assert recs2.tobytes() == recs.tobytes() and all(a.tobytes() == b.tobytes() for a, b in zip(masks, masks2))
+    c.close()
+
+
+def test_warp_and_guided_window_on_the_ladder(vislam):
+    """vis_warp_keypoints and the window predicate of the guided 2-NN with keypoints at the magnitudes of hc.MAG_LADDER, in the current frame
+    (whose prediction overflows to +-inf or to inf - inf = NaN) and in the previous one (whose difference from every prediction does): bit
+    for bit the numpy restatement, and from k = 1e-6 up such a keypoint is nobody's neighbour"""
+    import guided_match_ref as gr
+    rng = np.random.default_rng(23)
+    rot = gr.WARP_ROTS[1]
+    xy_cur = gr.warp_points()[:120].copy()
+    xy_prev = np.concatenate([gr.warp(xy_cur, rot), gr.warp(xy_cur[:40], rot) + np.float32(2.0)]).astype(np.float32)
+    pool = rng.integers(0, 256, (6, 32), dtype=np.uint8)
+    d_cur, d_prev = pool[rng.integers(0, 6, len(xy_cur))], pool[rng.integers(0, 6, len(xy_prev))]
+    names = hc.MAG_NAMES
+    lad_cur, lad_prev = 2 * np.arange(len(names)), 3 * np.arange(len(names)) + 1
+    for j, name in enumerate(names):                               # one coordinate each: x and y in turn
+        ax = (j // 2) % 2                                          # (the names alternate in sign)
+        xy_cur[lad_cur[j], ax] = hc.mag_pixel(name, ax)
+        xy_prev[lad_prev[j], 1 - ax] = hc.mag_pixel(name, 1 - ax)
+    assert (np.abs(xy_cur[lad_cur]).max(1) > 1e9).all() and (np.abs(xy_prev[lad_prev]).max(1) > 1e9).all() and np.isfinite(xy_cur).all()
+    far = np.array([hc.mag_of("p1:" + n) >= hc.MAG_NEVER_FROM for n in names])
+    c = vislam.Context(0)
+    got, want = c.warp_keypoints(gr.keypoints(xy_cur), rot), gr.warp(xy_cur, rot)
+    nan = np.isnan(want)
+    assert (np.isnan(got) == nan).all() and got[~nan].tobytes() == want[~nan].tobytes(), np.argwhere(got != want)[:6]
+    assert nan[lad_cur].any() and not nan[lad_cur].all()           # some turn behind the camera, the others project to an ordinary pixel
+    k12, k21, adm = gr.knn2(d_prev, xy_prev, d_cur, xy_cur, rot, gr.RADIUS)
+    assert not adm[:, lad_cur[far]].any() and not adm[lad_prev[far], :].any() and adm.any(1).sum() > 100
+    g12, g21 = c.bf_knn2_hamming_guided_host(d_prev, gr.keypoints(xy_prev), d_cur, gr.keypoints(xy_cur), rot, gr.RADIUS)
+    assert g12.tobytes() == gr.dmatches(k12).tobytes() and g21.tobytes() == gr.dmatches(k21).tobytes()
+    assert (g21["trainIdx"][lad_cur[far]] == -1).all() and (g12["trainIdx"][lad_prev[far]] == -1).all()
     c.close()
 
 

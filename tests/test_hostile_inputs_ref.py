@@ -1,6 +1,7 @@
 """CPU: what the restatements (tests/pnp_ref.py, homography_ref.py + homography_pose_ref.py, f2f_ref.py, triangulate_ref.py) and the CPU
 oracle's essential RANSAC do with correspondences that are not usable numbers: the rows of tests/hostile_cases.py (every kind x layout that
-applies, 40 points and one more than an LDS tile).  tests/test_hostile_inputs_gpu.py holds the kernels to the same records.
+applies, 40 points and one more than an LDS tile; the magnitude ladder of finite pixels on one image).  tests/test_hostile_inputs_gpu.py holds
+the kernels to the same records.
 
 The expected figures were measured on these restatements at the default parameters and are pinned here; the properties (no hostile entry in
 a mask, counts equal mask sums, finite hc.orthonormal winners, masks equal to the predicate evaluated exactly with mpmath) are asserted on
@@ -133,6 +134,19 @@ def test_essential_rows(orc, oracle_params):
         assert row["n_pose_good"] == (32 if kind in hc.PAIR_NONFINITE else {"p1:big": 36}.get(kind, 32)), (kind, row["n_pose_good"])
     row = rows["both:nan", "all", 40]
     assert not row["E"].any() and row["iters_run"] == 1000 and np.isnan(row["R"]).all()
+    # the magnitude ladder: a finite pixel, however large, on one image.  From k = 1e-6 up no ladder entry is in any winner's mask (cap: zero
+    # rows left out; hc.check_essential_row asserted it above on every row -- the scene seed of hc.essential_base is the choice that makes it
+    # true of the ORACLE, so a device mask that holds one is the device's doing), and the 32 clean points of the 8-of-40 rows keep the pose
+    # that the non-finite kinds leave them
+    mags = [k for k in rows if hc.mag_of(k[0]) is not None]
+    assert len(mags) == len(hc.mag_pair_kinds()) * 2 * len(hc.ESSENTIAL_MAG_LENGTHS) and len(hc.MAG_LADDER) == 11
+    left_out = [k for k in mags if hc.mag_of(k[0]) >= hc.MAG_NEVER_FROM and rows[k]["mask"][rows[k]["idx"]].any()]
+    assert left_out == []
+    ref = rows["both:nan", "stride5", 40]
+    for kind in hc.mag_pair_kinds():
+        row = rows[kind, "stride5", 40]
+        assert (row["n_inliers"], row["iters_run"]) == (31, 21) and row["mask"].tobytes() == ref["mask"].tobytes(), (kind, row["n_inliers"], row["iters_run"])
+        assert row["E"].tobytes() == ref["E"].tobytes() and row["R"].tobytes() == ref["R"].tobytes() and row["t"].tobytes() == ref["t"].tobytes(), kind
 
 
 def test_essential_refine_count_needs_a_finite_bound():

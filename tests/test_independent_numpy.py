@@ -794,6 +794,9 @@ def test_half_pyramid_against_a_numpy_restatement_at_odd_sizes(orc):
             prev = cur
 
 
+SAMPSON_LADDER = (1e-12, 1e-6, 0.5, 0.99, 1.1, 1.6, 2.7, 5.4, 54.0, 1e6, 1e15)   # tests/hostile_cases.py MAG_LADDER
+
+
 def test_single_precision_sampson_error_radii_hold():
     """vi-slam_amd/csrc/pose.hip decides the Sampson test in single precision inside rigorous error radii (|s32 - s| < 7 u n1 n2,
     |den32 - den| < 12 u (n1^2 + n2^2) for ||E||_F = 1, u = 2^-24, n = |(x, y, 1)|; the kernel uses 8 u and 16 u) and in the oracle's double
@@ -802,7 +805,9 @@ def test_single_precision_sampson_error_radii_hold():
     (model, point) pairs -- unit-norm E, coordinates up to |4| like the image corners of a short focal length -- against float64, and
     checks that no pair ever leaves the radii the kernel assumes, and that the "certainly in / certainly out" decisions
     (r = fma(-tm, den32, s32^2) against band = kd den32 + 2 es' |s32| + c, see the kernel's comment) never contradict the
-    double-precision rule -- on random pairs and on pairs constructed to sit within a few 10^-7 (relative) of the threshold."""
+    double-precision rule -- on random pairs and on pairs constructed to sit within a few 10^-7 (relative) of the threshold.  Then the
+    same two checks at coordinates up to 30, 1e3 and 1e6 (a focal length down to 1e-3 pixels), and the decisions alone with one coordinate on
+    a ladder of magnitudes through sqrt(FLT_MAX), where the radii overflow."""
     rng = np.random.default_rng(2024)
     f32 = np.float32
     u = 2.0 ** -24
@@ -829,12 +834,14 @@ def test_single_precision_sampson_error_radii_hold():
         es = (f32(8 * u) * n1 * n2).astype(f32); ed = (f32(16 * u) * (n1 * n1 + n2 * n2).astype(f32)).astype(f32)
         return s32, den32, s, den, es, ed
 
-    def decide(s32, den32, es, ed, thr):
+    def decide(s32, den32, es, ed, thr, poison=True):
         n = len(s32)
         thr2 = f32(thr * thr)
         tmid = 0.5 * (float(thr2) + float(np.nextafter(thr2, f32(np.inf))))
         tm, kd, thi16 = f32(tmid), f32(tmid * 2.0 ** -14 * (1 + 2.0 ** -23)), f32(tmid * (1 + 2.0 ** -16) * (1 + 2.0 ** -23))
         es2 = (f32(2) * es * f32(1 + 2.0 ** -10)).astype(f32); c = ((es * es + thi16 * ed) * f32(1 + 2.0 ** -10)).astype(f32)
+        if poison:                                                 # make_pt: radii that are not finite decide nothing
+            c = np.where(c <= np.finfo(f32).max, c, f32(np.nan)).astype(f32)
         r = fma(np.full(n, -tm, f32), den32, (s32.astype(np.float64) * s32.astype(np.float64)).astype(f32))
         band = fma(np.full(n, kd, f32), den32, fma(es2, np.abs(s32), c))
         return r <= -band, r >= band, tmid
@@ -877,6 +884,48 @@ def test_single_precision_sampson_error_radii_hold():
         assert not (tin & ~ttruth).any() and not (tout & ttruth).any(), thr
         und = ~(tin | tout)
         assert 0.2 < und.mean() < 0.98, und.mean()                # both kinds occur: the check is not vacuous
+
+    # larger coordinates (a focal length down to 1e-3 of the image size): the same radii, the same rule
+    n = 300_000
+    for scale in (30.0, 1e3, 1e6):
+        Es, Ps = E[:n], rng.uniform(-1, 1, (n, 4)) * scale
+        s32, den32, s, den, es, ed = replay(Es, Ps)
+        N1 = np.sqrt(Ps[:, 0] ** 2 + Ps[:, 1] ** 2 + 1.0); N2 = np.sqrt(Ps[:, 2] ** 2 + Ps[:, 3] ** 2 + 1.0)
+        rs = np.abs(s32.astype(np.float64) - s) / (u * N1 * N2); rd = np.abs(den32.astype(np.float64) - den) / (u * (N1 * N1 + N2 * N2))
+        assert rs.max() < 7 and rd.max() < 12, (scale, rs.max(), rd.max())
+        for thr in (1.0 / 458.654, 0.25 / 458.654, 3.0 / 150.0):
+            sure_in, sure_out, tmid = decide(s32, den32, es, ed, thr)
+            truth = (s * s) <= tmid * den
+            assert not (sure_in & ~truth).any() and not (sure_out & truth).any(), (scale, thr)
+
+    # one coordinate on a ladder of magnitudes k sqrt(FLT_MAX) around the overflow of n^2 (1.84e19: a finite float pixel of 1e22 at
+    # fx = 458), the other three in +-0.5.  Above it es, ed, c and band are +inf; where den32 overflows and s32^2 does not, r = -inf and
+    # `r <= -band` held for a point far from every epipolar line: make_pt's NaN for a non-finite c is what closes that, and `decide`
+    # above mirrors it (poison).  The parent's rule (poison=False) must be seen to fail here, or the ladder proves nothing
+    root_max = float(np.sqrt(np.float64(np.finfo(f32).max)))
+    n = 100_000
+    parent_wrong = {}
+    with np.errstate(over="ignore", invalid="ignore"):
+        for k in SAMPSON_LADDER:
+            Ek = E[:n]
+            Pk = rng.uniform(-0.5, 0.5, (n, 4))
+            col = rng.integers(0, 4, n)
+            val = k * root_max * rng.choice([-1.0, 1.0], n) * np.where(np.arange(n) % 2 == 0, 1.0, rng.uniform(0.5, 1.0, n))
+            Pk[np.arange(n), col] = val
+            assert np.isfinite(Pk.astype(f32)).all(), k
+            s32, den32, s, den, es, ed = replay(Ek, Pk)
+            thr = 1.0 / 458.654
+            sure_in, sure_out, tmid = decide(s32, den32, es, ed, thr)
+            truth = (s * s) <= tmid * den
+            assert np.isfinite(s * s).all() and np.isfinite(den).all(), k       # the double rule itself is far from its own overflow
+            assert not (sure_in & ~truth).any() and not (sure_out & truth).any(), (k, int((sure_in & ~truth).sum()), int((sure_out & truth).sum()))
+            pin, pout, _ = decide(s32, den32, es, ed, thr, poison=False)
+            parent_wrong[k] = int((pin & ~truth).sum())
+            assert not (pout & truth).any(), k                     # ("certainly out" was never the hole)
+            if k <= 0.5:
+                assert (sure_in | sure_out).mean() > 0.97, k         # below the overflow single precision still decides
+    assert all(parent_wrong[k] == 0 for k in SAMPSON_LADDER if k < 1.0), parent_wrong
+    assert all(parent_wrong[k] > 0 for k in (1.1, 1.6, 2.7, 5.4, 54.0)), parent_wrong   # (100, 10460, 34534, 35192, 4311 of 100 000)
 
 
 def _np_half(src):

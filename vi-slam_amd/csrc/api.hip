@@ -55,15 +55,36 @@ extern "C" void vis_default_params(vis_params* p) {
     p->pose_input = VIS_POSE_GOOD;
 }
 
-static int validate_params(const vis_params& p) {
+// why: what vis_last_error says of a refusal whose reason is not obvious from the header's ranges (left alone otherwise)
+static int validate_params(const vis_params& p, std::string& why) {
     if (p.nfeatures < 1 || p.nlevels < 1 || p.nlevels > VIS_MAX_LEVELS) return VIS_E_INVALID;
     if (!(p.scale_factor > 1.0f) || p.scale_factor > 3.0f) return VIS_E_INVALID;   // k_resize fetches a 12-byte source window per 4 outputs
     if (p.patch_size != 31) return VIS_E_INVALID;                 // the rBRIEF pattern is learned for 31x31
     if (p.edge_threshold < 22 || p.edge_threshold > 255) return VIS_E_INVALID;   // 43x43 raw patch must stay inside
     if (p.fast_threshold < 1 || p.fast_threshold > 254) return VIS_E_INVALID;
     if (p.n_cells < 1 || p.w_size < 1 || p.h_size < 1) return VIS_E_INVALID;
+    // bestMatchesFilter's grid is floor(sqrt(n_cells)) squared; the filter kernel holds at most VIS_MAX_GRID_ROOT^2 cells.  A larger root
+    // is refused, not clamped: a clamped grid is another grid (other cell sizes, other survivors), and nothing would tell the caller
+    if ((int)std::floor(std::sqrt((double)p.n_cells)) > VIS_MAX_GRID_ROOT) {
+        why = "vis_set_params: n_cells " + std::to_string(p.n_cells) + ": floor(sqrt(n_cells)) must not exceed VIS_MAX_GRID_ROOT = " +
+              std::to_string((int)VIS_MAX_GRID_ROOT) + " (n_cells <= " + std::to_string((VIS_MAX_GRID_ROOT + 1) * (VIS_MAX_GRID_ROOT + 1) - 1) + ")";
+        return VIS_E_INVALID;
+    }
+    if (p.sym_mode != VIS_SYM_REFERENCE_EFFECTIVE && p.sym_mode != VIS_SYM_INTENDED) {
+        why = "vis_set_params: sym_mode " + std::to_string(p.sym_mode) + " is none of VIS_SYM_*"; return VIS_E_INVALID;
+    }
     if (p.ransac_max_iters < 1 || p.ransac_max_iters > 100000) return VIS_E_INVALID;
     if (!(p.ransac_prob > 0 && p.ransac_prob < 1) || !(p.fx > 0) || !(p.fy > 0)) return VIS_E_INVALID;
+    // the essential RANSAC compares a float Sampson error with (float)((ransac_threshold / fx)^2) and the scorer takes the float above it:
+    // both must be ordinary floats.  0 and NaN accept nothing (the reference then returns no model after max_iters iterations), +inf accepts
+    // every correspondence under the first model, a negative value is squared into its positive twin: none of them is an estimate anybody asked
+    // for, all are refused.  (f2f_threshold is compared as written, `error < threshold` in double: every double is taken, see the header.)
+    {
+        const double t = p.ransac_threshold / p.fx;
+        if (!(t >= 1e-18 && t <= 1e18)) {
+            why = "vis_set_params: ransac_threshold / fx must lie in [1e-18, 1e18] (finite and positive)"; return VIS_E_INVALID;
+        }
+    }
     if (p.f2f_iters < 0) return VIS_E_INVALID;
     if (p.pose_input != VIS_POSE_GOOD && p.pose_input != VIS_POSE_SYM) return VIS_E_INVALID;
     if (p.keypoint_capacity < 0 || p.keypoint_capacity > 65535) return VIS_E_INVALID;
@@ -162,8 +183,9 @@ static bool same_record_geometry(const vis_params& a, const vis_params& b) {
 
 extern "C" int vis_set_params(vis_ctx* ctx, const vis_params* p) {
     if (!ctx || !p) return VIS_E_INVALID;
-    int rc = validate_params(*p);
-    if (rc) return rc;
+    std::string why;
+    int rc = validate_params(*p, why);
+    if (rc) { if (!why.empty()) ctx->err = why; return rc; }
     sync_all(ctx);
     // The reference changes matcher / pose settings while its keyframes keep their keypoints and descriptors
     // (Matcher::setImageDimensions, computeBestMatches(n_cells)): when only such fields change, the device slots of the

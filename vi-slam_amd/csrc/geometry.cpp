@@ -66,12 +66,12 @@ int vis_compute_levels(const vis_params& p, int w, int h, int stride0, LevelInfo
 // Matcher::bestMatchesFilter window limits: winW = w_size/floor(sqrt(n)) stored as float, limits
 // accumulated in float exactly like `h_final = h_final + winHSize` (src/Matcher.cpp:177-178,203,229).
 void vis_grid_limits(const vis_params& p, int* root, std::vector<float>& hf, std::vector<float>& wf) {
-    int r = (int)std::floor(std::sqrt((double)p.n_cells));
-    if (r < 1) r = 1;
-    if (r > VIS_MAX_GRID_ROOT) r = VIS_MAX_GRID_ROOT;
+    // 1 <= root <= VIS_MAX_GRID_ROOT: validate_params refuses every other n_cells, so the root that sizes the cells is the root that counts them
+    const double rd = std::floor(std::sqrt((double)p.n_cells));
+    const int r = (int)rd;
     *root = r;
-    float winW = (float)(p.w_size / std::floor(std::sqrt((double)p.n_cells)));
-    float winH = (float)(p.h_size / std::floor(std::sqrt((double)p.n_cells)));
+    float winW = (float)(p.w_size / rd);
+    float winH = (float)(p.h_size / rd);
     hf.resize(r); wf.resize(r);
     float a = winH, b = winW;
     for (int j = 0; j < r; j++) { hf[j] = a; wf[j] = b; a = a + winH; b = b + winW; }

@@ -424,8 +424,9 @@ __global__ __launch_bounds__(NT) void k_filter(const vis_keypoint* __restrict__ 
             if (ok) {
                 vis_dmatch m; m.queryIdx = q; m.trainIdx = t; m.imgIdx = -1; m.distance = (float)(a0 >> 16);
                 sym[pos] = m;
-                // sortMatches key: y ascending, ties keep symmetric-match order (stable)
-                keys[pos] = ((uint64_t)fmap_f(K1[q].y) << 32) | (uint32_t)pos;
+                // sortMatches key: y ascending, ties keep symmetric-match order (stable).  y + 0.f: -0 and +0 compare equal in the
+                // reference's sort, so they must map to one key (-0 + 0 = +0; every other value is unchanged)
+                keys[pos] = ((uint64_t)fmap_f(K1[q].y + 0.f) << 32) | (uint32_t)pos;
                 pos++;
             }
         }

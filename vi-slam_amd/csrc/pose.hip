@@ -938,6 +938,11 @@ __global__ __launch_bounds__(256) void k_hyp_models(PoseParams P, int h0, int h_
 //   double sequence it stands in for):   r <= -band  =>  certainly an inlier (and den32 > ed, so D > 0);   r >= band  =>  certainly
 //   not.  Anything else -- a band of about +-0.02 % around the threshold residual at the image centre (+-0.1 % at the image corners
 //   of config 3, n = 4), a NaN, a vanishing den -- takes the double path.  20 full-rate operations and two comparisons per (model, point).
+//   The bounds above assume that nothing overflowed.  A coordinate above sqrt(FLT_MAX) = 1.84e19 (a finite float pixel of 1e22 at fx = 458)
+//   makes n^2, es, ed, c and band +inf; den32 = +inf needs n1^2 + n2^2 = +inf.  With den32 = +inf and s32^2 finite r = -inf, and
+//   -inf <= -inf would be "certainly an inlier" of a point that is none.  The rule: A POINT WHOSE RADII ARE NOT FINITE IS NEVER DECIDED IN
+//   SINGLE PRECISION.  make_pt, once per point, replaces a non-finite c by a NaN, so band is a NaN under every model and both comparisons
+//   fail (tests/test_independent_numpy.py replays this over a ladder of magnitudes around sqrt(FLT_MAX); tests/hostile_cases.py "mag:").
 //   The decisions, hence masks, counts and
 //   iteration numbers, are the oracle's for every input (tests/test_pose_gpu.py, test_configs_gpu.py compare them exactly).
 struct ScorePt { float x1, y1, x2, y2, es2, c; };
@@ -1042,6 +1047,10 @@ __global__ __launch_bounds__(256) void k_hyp_score(PoseParams P, int h0, int h_e
             const float n2 = sqrtf(__fmaf_rn(q.x2, q.x2, __fmaf_rn(q.y2, q.y2, 1.f))) * (1.f + 0x1p-20f);
             const float es = 8.f * 0x1p-24f * n1 * n2, ed = 16.f * 0x1p-24f * (n1 * n1 + n2 * n2);
             q.es2 = 2.f * es * (1.f + 0x1p-10f); q.c = (es * es + thi16 * ed) * (1.f + 0x1p-10f);
+            // radii that overflowed bound nothing: band = +inf, and where den32 overflows too while s32^2 does not, r = -inf <= -inf would
+            // report a certain inlier.  c is infinite whenever n1^2 + n2^2 is, hence whenever den32 can be: a NaN c leaves both comparisons
+            // false for every model, and the point takes the double path
+            if (!(q.c <= FLT_MAX)) q.c = __builtin_nanf("");
             return q;
         };
         if (M <= 256) {
