@@ -1326,7 +1326,9 @@ int  vis_ftrack_link_rows(vis_ctx* ctx, int n, const int32_t* d_prev, const int3
  * entries of a row are written.  The plan keeps a copy of the row of the last SAVED frame of the launch (beside the keyframe gate's carried
  * record) and the stream number of frame 0: the next call continues those tracks across the launch boundary, a launch that saved nothing carries
  * the earlier row forward, vis_batch_plan / vis_batch_reset forget the row and restart seq at 0, and a launch that was not linked makes the frames
- * of the next one whose pair is the carried keyframe VIS_FT_NO_CARRY.  Calling it again for the same run repeats the result.  Asynchronous on the
+ * of the next one whose pair is the carried keyframe VIS_FT_NO_CARRY.  Calling it again for the same run repeats the result: every call of a run
+ * continues the row the run was given, and a vis_batch_run without VIS_STAGE_DETECT in between does not begin a new run.  When the calls of one
+ * run differ (another source, another mask), the row of the LAST call is the one the next run continues.  Asynchronous on the
  * POSE stream behind the matcher of that run (and, when a d_mask is given, behind the context's stream), overlapping the next vis_batch_run like
  * vis_batch_triangulate; the caller's buffers are in use until vis_batch_sync.  The workspace is allocated by the first call of a plan.
  * Refusals, in this order.  VIS_E_INVALID: a NULL or misaligned d_obs (16 bytes) or d_frame (4), n, mask_cap or row_cap negative, a source that is

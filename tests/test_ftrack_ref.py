@@ -15,49 +15,10 @@ import numpy as np
 import pytest
 
 import ftrack_ref as fr
+from ftrack_stream_cases import walk_link
 
 
 # ---------------------------------------------------------------------------------------------- linking
-def walk_link(prev, nkp, links, nlinks, row_cap, mask=None, carry=None, seq0=0):
-    """the independent implementation: frames in order, one dictionary of track identities per frame, no pointer doubling"""
-    n = len(prev)
-    obs = np.zeros((n, row_cap), fr.OBS_DTYPE)
-    obs[:] = fr.EMPTY_OBS
-    frames = np.zeros(n, fr.FRAME_DTYPE)
-    ident = []                                                      # per frame {keypoint: (birth_seq, birth_kp, len)}
-    carried = None if carry is None else {k: (int(c["birth_seq"]), int(c["birth_kp"]), int(c["len"])) for k, c in enumerate(carry) if int(c["len"]) > 0}
-    for i in range(n):
-        p = int(prev[i])
-        nk = 0 if p == fr.KF_NOT_SAVED else min(max(int(nkp[i]), 0), row_cap)
-        parent = ident[p] if 0 <= p < i else carried if (p == fr.KF_CARRIED and carried is not None) else None
-        m = min(max(int(nlinks[i]), 0), links.shape[1])
-        if mask is not None:
-            m = min(m, mask.shape[1])
-        seen_t, seen_q, linked = set(), set(), {}
-        if parent is not None:
-            for c in range(m):
-                q, t = int(links[i, c]["queryIdx"]), int(links[i, c]["trainIdx"])
-                if not (0 <= t < nk) or q not in parent or (mask is not None and mask[i, c] == 0):
-                    continue
-                if t not in seen_t and q not in seen_q:
-                    linked[t] = q
-                seen_t.add(t)
-                seen_q.add(q)
-        cur = {}
-        for k in range(nk):
-            if k in linked:
-                b = parent[linked[k]]
-                cur[k] = (b[0], b[1], b[2] + 1)
-            else:
-                cur[k] = (seq0 + i, k, 1)
-            obs[i, k] = cur[k] + (linked.get(k, -1),)
-        ident.append(cur)
-        lens = [v[2] for v in cur.values()]
-        frames[i] = (seq0 + i, nk, len(linked), nk - len(linked), 0 if parent is None else len(parent) - len(linked), max(lens, default=0),
-                     sum(lens), 0 if parent is not None else fr.FT_NO_CARRY if p == fr.KF_CARRIED else fr.FT_NO_PAIR)
-    return obs, frames
-
-
 def random_stream(seed, n, row_cap, link_cap, gate=True, hostile=True, first_prev=fr.KF_FIRST):
     """(prev, nkp, links, nlinks, mask): mostly one-to-one lists with duplicates on either side, out-of-range indices, empty lists, counts beyond
     their capacities, gated and restarting frames"""
