@@ -152,7 +152,37 @@ void vis_default_params(vis_params* p);
  * (src/MatcherGPU.cpp:30), Matcher::setImageDimensions (src/Matcher.cpp:30-34) */
 int  vis_set_params(vis_ctx* ctx, const vis_params* p);
 int  vis_get_params(vis_ctx* ctx, vis_params* p);
-/* enqueue on this hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); NULL = context's own stream */
+/* Enqueue on this hipStream_t from now on (e.g. the cuda_stream handle of a torch.cuda.Stream() the caller produces its inputs on).
+ * NULL -- the handle 0 -- selects the context's OWN stream, which is created hipStreamNonBlocking: it is ordered with NOTHING of the
+ * caller's, in particular not with the legacy default stream, whose handle is 0 too.  The default stream (torch.cuda.default_stream(),
+ * what torch.cuda.current_stream() is unless the caller changed it) can therefore NOT be passed: a caller that works on it either moves
+ * its producers and consumers to a stream of its own and passes that one, or synchronises the host around the library's calls.
+ * Synchronises: everything queued through the stream set before, and on the context's other streams, is complete when this returns.
+ * The stream must outlive the context (vis_destroy synchronises it) or be unset first (vis_set_stream(ctx, NULL)).
+ *
+ * Streams.  "The context's stream" below is the stream set here (or the own one).  The context has three more, all non-blocking:
+ * an update stream (half pyramid / gradients of vis_batch_run), the match stream and the pose stream.  Every asynchronous call falls
+ * into one of three classes (DESIGN.md has the table, one row per entry point; tests/test_caller_stream_gpu.py checks it):
+ *   1. Calls on the context's stream -- vis_gradient_batch, vis_align_batch, vis_klt_batch, vis_f2f_batch, vis_filter_keypoints_batch,
+ *      vis_homography_batch / _pose_batch / _polish_batch, vis_pnp_batch, vis_essential_batch / _refine_batch / _polish_batch,
+ *      vis_ftrack_link_rows, vis_ftrack_triangulate_rows, vis_rectify_batch (and vis_synth_frames_device, which is ordered the same way
+ *      but blocks the host: see there).  They run in stream order: they wait
+ *      for whatever the caller queued on that stream before the call (the producers of their device inputs), and their outputs may be
+ *      read by anything queued on that stream after the call -- no host synchronisation on either side.  Those that write buffers an
+ *      alignment on the pose stream may still read (vis_gradient_batch, vis_rectify_batch) wait for it first.
+ *   2. vis_batch_run / vis_batch_run_guided.  The detect chain runs on the context's stream, so d_frames may be produced on that stream
+ *      right before the call; the half pyramid and the gradients run on the update stream, which forks from the context's stream and
+ *      is joined by it before the call returns, so d_frames may be overwritten by work queued on the context's stream after the call.
+ *      The matcher (match stream; it reads vis_batch_run_guided's d_rot) and the pose stage (pose stream) are ordered behind the detect
+ *      chain, hence behind what the caller queued before, and are NOT joined: results, vis_batch_half_pyramid, vis_batch_gradients and
+ *      every getter are read after vis_batch_sync (or through a getter, which synchronises); d_rot is in use until then.
+ *   3. Follow-ups of the last vis_batch_run on the pose stream.  vis_batch_align, vis_batch_track, vis_batch_klt, vis_batch_f2f,
+ *      vis_batch_filter_keypoints, vis_batch_homography / _pose / _polish, vis_batch_pnp, vis_batch_essential_refine / _polish,
+ *      vis_batch_ftrack_triangulate, and vis_batch_ftrack when it is given a d_mask, FORK from the context's stream: they wait for what
+ *      was queued on it before the call, so their caller device inputs may be produced there.  vis_batch_triangulate,
+ *      vis_batch_triangulate_from and vis_batch_ftrack without a mask do NOT wait for the context's stream: what they read from caller
+ *      buffers must be complete (or have been written by an earlier follow-up, which the pose stream orders).  None of them is joined
+ *      back: caller buffers are in use, and outputs are read, after vis_batch_sync.  vis_batch_results_async likewise. */
 int  vis_set_stream(vis_ctx* ctx, void* hip_stream);
 int  vis_last_timings(vis_ctx* ctx, vis_timings* t);
 /* per-level geometry the context derived from params for a w x h input
@@ -233,7 +263,8 @@ int  vis_f2f_ransac(vis_ctx* ctx, const vis_keypoint* pts1, const vis_keypoint* 
  * alignment that reads these buffers; vis_gradient_frame_elems returns 0 outside it), stride >= w and stride % 4 == 0,
  * 1 <= scale <= 8 (int16 cannot overflow), output buffers 16-byte aligned (d_frames needs no alignment).  A level that is one pixel
  * wide or high (every side of 16 ... 21 ends in one) is a level like any other: BORDER_REFLECT_101 of a single pixel repeats it, so
- * the response across it is 0. */
+ * the response across it is 0.  vis_gradient_batch is asynchronous on the context's stream (both of its launches, csrc/api.hip), behind an
+ * alignment of the pose stream that still reads gradient buffers. */
 size_t vis_gradient_frame_elems(int w, int h);
 int  vis_gradient_batch(vis_ctx* ctx, const uint8_t* d_frames, int w, int h, int stride, int n, int scale,
                         uint8_t* d_gray, int16_t* d_gx, int16_t* d_gy, uint8_t* d_g);
@@ -1409,7 +1440,9 @@ int  vis_synth_frame_parallax(const uint8_t* canvas, int canvas_dim, uint64_t se
                               int w, int h, uint8_t* out, int out_stride);
 /* n consecutive frames t0 .. t0+n-1 generated on the device into d_out (frame stride = stride*h); d_canvas = the canvas
  * of vis_synth_canvas in device memory.  mode 0 = S-752, 1 = S-752P.  Byte-identical to the host generators.
- * Asynchronous on the context's stream. */
+ * The kernel is queued on the context's stream, behind whatever produced d_canvas there, and d_out may be read by work queued on that
+ * stream after the call -- but the call is NOT asynchronous for the host: it uploads a per-frame table from pageable memory and blocks
+ * until the context's stream has drained, the caller's earlier work on it included.  (A test-stream generator, not a product path.) */
 int  vis_synth_frames_device(vis_ctx* ctx, const uint8_t* d_canvas, int canvas_dim, uint64_t seed, int t0, int n,
                              int w, int h, int stride, int mode, uint8_t* d_out);
 

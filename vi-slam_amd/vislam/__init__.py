@@ -850,8 +850,9 @@ class Context:
         for r in list(getattr(self, "_rectifiers", ())):
             r.close()
         if getattr(self, "_h", None):
-            lib.vis_destroy(self._h)
+            lib.vis_destroy(self._h)                         # (synchronises the stream set_stream gave it: released only now)
             self._h = None
+        self._stream = None
 
     def __del__(self):
         try:
@@ -877,7 +878,8 @@ class Context:
         return aw
 
     def synth_frames_device(self, d_canvas_ptr, dim, seed, t0, n, w, h, stride, d_out_ptr, parallax=False):
-        """frames t0 .. t0+n-1 of the synthetic stream straight into device memory (asynchronous)"""
+        """frames t0 .. t0+n-1 of the synthetic stream straight into device memory: queued on the context's stream, but the call blocks until
+        that stream has drained"""
         self._chk(lib.vis_synth_frames_device(self._h, C.c_void_p(d_canvas_ptr), dim, C.c_uint64(seed), t0, n, w, h, stride,
                                               1 if parallax else 0, C.c_void_p(d_out_ptr)), "vis_synth_frames_device")
 
@@ -886,8 +888,20 @@ class Context:
         context"""
         return Rectify(self, K, dist, Knew, in_size, out_size)
 
-    def set_stream(self, raw_stream):
-        self._chk(lib.vis_set_stream(self._h, C.c_void_p(raw_stream)), "vis_set_stream")
+    def set_stream(self, stream):
+        """the stream the asynchronous calls enqueue on from now on: a torch.cuda.Stream (anything with a .cuda_stream handle) or a raw
+        hipStream_t as an int.  Synchronises: what was queued through the stream set before is complete when this returns.
+
+        The raw handle 0 (or None) selects the context's OWN stream, which is non-blocking: it is NOT ordered with torch's default
+        stream, whose handle is 0 as well.  torch's default stream can therefore not be passed -- a stream object whose handle is 0 is
+        refused (ValueError) instead of silently selecting the own stream; run the producer on a torch.cuda.Stream() and pass that, or
+        synchronise the host.  The stream must outlive the context, or be unset (set_stream(0)) first; the context keeps a reference to
+        a stream object it was given."""
+        raw = getattr(stream, "cuda_stream", stream)
+        if raw is not stream and not raw:
+            raise ValueError("the default stream has handle 0, which vis_set_stream reads as 'the context's own stream': pass a torch.cuda.Stream()")
+        self._chk(lib.vis_set_stream(self._h, C.c_void_p(int(raw) if raw else None)), "vis_set_stream")
+        self._stream = stream if raw else None
 
     def timings(self):
         t = Timings()
