@@ -165,7 +165,7 @@ int  vis_get_params(vis_ctx* ctx, vis_params* p);
  * into one of three classes (DESIGN.md has the table, one row per entry point; tests/test_caller_stream_gpu.py checks it):
  *   1. Calls on the context's stream -- vis_gradient_batch, vis_align_batch, vis_klt_batch, vis_f2f_batch, vis_filter_keypoints_batch,
  *      vis_homography_batch / _pose_batch / _polish_batch, vis_pnp_batch, vis_essential_batch / _refine_batch / _polish_batch,
- *      vis_ftrack_link_rows, vis_ftrack_triangulate_rows, vis_rectify_batch (and vis_synth_frames_device, which is ordered the same way
+ *      vis_ftrack_link_rows, vis_ftrack_triangulate_rows, vis_scale_link_rows, vis_trajectory_rows, vis_rectify_batch (and vis_synth_frames_device, which is ordered the same way
  *      but blocks the host: see there).  They run in stream order: they wait
  *      for whatever the caller queued on that stream before the call (the producers of their device inputs), and their outputs may be
  *      read by anything queued on that stream after the call -- no host synchronisation on either side.  Those that write buffers an
@@ -178,7 +178,7 @@ int  vis_get_params(vis_ctx* ctx, vis_params* p);
  *      every getter are read after vis_batch_sync (or through a getter, which synchronises); d_rot is in use until then.
  *   3. Follow-ups of the last vis_batch_run on the pose stream.  vis_batch_align, vis_batch_track, vis_batch_klt, vis_batch_f2f,
  *      vis_batch_filter_keypoints, vis_batch_homography / _pose / _polish, vis_batch_pnp, vis_batch_essential_refine / _polish,
- *      vis_batch_ftrack_triangulate, and vis_batch_ftrack when it is given a d_mask, FORK from the context's stream: they wait for what
+ *      vis_batch_ftrack_triangulate, vis_batch_scale_links, vis_batch_trajectory, and vis_batch_ftrack when it is given a d_mask, FORK from the context's stream: they wait for what
  *      was queued on it before the call, so their caller device inputs may be produced there.  vis_batch_triangulate,
  *      vis_batch_triangulate_from and vis_batch_ftrack without a mask do NOT wait for the context's stream: what they read from caller
  *      buffers must be complete (or have been written by an earlier follow-up, which the pose stream orders).  None of them is joined
@@ -1371,7 +1371,8 @@ int  vis_batch_ftrack(vis_ctx* ctx, int source, int pose_inliers, int n, const u
 
 /* N-view triangulation of the tracks.  d_poses: n x 12 doubles per frame, R row-major then t, x_cam = R X + t in ONE common frame and scale; a
  * frame whose 12 numbers are not all finite or whose R is all zero has no pose (the pose record's convention).  The poses are the caller's (a
- * VIO, a chained and scaled PnP, ground truth): where they come from, and a common scale for consecutive two-view poses, is outside this library.
+ * VIO, a chained and scaled PnP, ground truth) or the d_poses of vis_trajectory_rows / vis_batch_trajectory below, which chain the two-view poses
+ * of a stream under the common scale of vis_scale_link_rows / vis_batch_scale_links without a host step.
  * A point is computed for every keypoint (i, k), k < nk(i), that is the LAST observation of its track inside the call: no keypoint of a later
  * frame names it as its parent (prev[] index and prev_kp < nk of that frame).  Every other entry k < nk(i) gets the zero record and flags 0; entries
  * k >= nk(i) are left untouched.  The lane walks back from (i, k) along prev_kp / prev[] through at most max_views observations of this call --
@@ -1427,6 +1428,125 @@ int  vis_ftrack_triangulate_rows(vis_ctx* ctx, const vis_ftrack_tri_params* tp, 
  * differs. */
 int  vis_batch_ftrack_triangulate(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, const vis_ftrack_obs* d_obs, int row_cap,
                                   const double* d_poses, vis_ftrack_point* d_points, uint8_t* d_flags, vis_ftrack_tri_summary* d_summary);
+
+/* ---- a scaled trajectory: consecutive two-view poses given one scale, and chained (the reference has neither: its monocular poses stay
+ * pairwise, |t| = 1).  Two steps, each on caller rows and on the plan; tests/scale_link_ref.py and tests/trajectory_ref.py restate them, and every
+ * record equals its restatement byte for byte: double arithmetic, + - * / and comparisons only, nothing contracted.
+ * FRAMES.  prev[i] is an index < i, VIS_KF_CARRIED or VIS_KF_NOT_SAVED; any other value counts as VIS_KF_FIRST (the q / parent fields report the
+ * value so normalised).  A frame HAS A PAIR when prev[i] is an index or VIS_KF_CARRIED; its pose record (R, t, x_i = R x_q + t) is USABLE when its 12
+ * numbers are finite, R is not all zero and (t0 t0 + t1 t1) + t2 t2 is finite and > 0 (vis_essential_refine's convention).
+ *
+ * 1. SCALE LINKS.  Frame i with keyframe q = prev[i]: the length of baseline q -> i in units of the baseline of q's own pair p -> q, from the map
+ * points both pairs share through a keypoint of frame q.  The list of frame i holds vis_dmatch entries with queryIdx a keypoint of q and trainIdx
+ * a keypoint of i (vis_batch_pnp's orientation); its first m entries count, m = the list's count clamped to [0, min(link_cap, pts_cap)]; entry k
+ * has the map point d_points[i][k] and the flag byte d_flags[i][k] of vis_batch_triangulate's layout (X in camera q, in units of baseline q -> i).
+ * An entry QUALIFIES when its flag byte contains every bit of `require`.
+ *   DEPTH ROW of frame i, row_cap doubles, one per keypoint of i: zero throughout unless i has a pair and a usable pose record.  Else keypoint kp
+ *   gets the depth of the FIRST qualifying entry k in list order with trainIdx == kp (an integer minimum of k, as k_pnp_link does; trainIdx is
+ *   compared unsigned against row_cap: a negative index is out of range): z2 = ((R[6] X0 + R[7] X1) + R[8] X2) + t[2] -- the depth in camera i in
+ *   units of i's baseline -- when z2 is finite and > 0, else 0; a keypoint without a qualifying entry gets 0.
+ *   RATIOS of frame i: every qualifying entry c whose queryIdx (unsigned < row_cap) has an entry z2 in q's depth row that is finite and > 0 and
+ *   whose own z1 = X[2] is finite and > 0 gives rho = z2 / z1, kept when finite and > 0; n_shared counts them.  q's row is row q of this call, or
+ *   d_depth_carry_in when q is VIS_KF_CARRIED.
+ *   RECORD: scale = the lower median of the ratios, element (n_shared - 1) / 2 of their ascending order; q25 and q75 = elements (n_shared - 1) / 4
+ *   and 3 (n_shared - 1) / 4 (integer divisions) -- order statistics, defined by value; with n_shared == 0 all three are 0.  flags:
+ *   VIS_SL_NO_PAIR (i has no pair) and VIS_SL_NO_DEPTH (q is VIS_KF_CARRIED without a carried row, or q's row has no entry that is finite and > 0:
+ *   q had no pair, no usable pose or no qualifying point -- a test of the row alone, so a carried row answers as the frame itself would) stand
+ *   alone, with n_shared = 0; otherwise VIS_SL_FEW (n_shared < min_shared), VIS_SL_SPREAD (q75 - q25 > max_rel_spread * scale) and VIS_SL_RANGE (scale not
+ *   inside [min_scale, max_scale]) in any combination, and VIS_SL_OK = 0 when none applies.  No reported number is ever a NaN or an infinity.
+ * On the device: one workgroup per frame and two passes.  The depth pass settles the winner by a 64-bit atomic minimum in the row itself.  The
+ * ratio pass keeps the ratios' bit patterns (a positive finite double orders like its 64-bit pattern; an entry without a ratio is the pattern 0,
+ * which orders first) in LDS when m <= 1024 and in the workspace beyond that, and SELECTS the three ranks in one walk of eight 8-bit digits, an LDS
+ * histogram per rank and digit, integers only, the pass count independent of the data.  Nothing is sorted. */
+enum { VIS_SL_OK = 0, VIS_SL_NO_PAIR = 1, VIS_SL_NO_DEPTH = 2, VIS_SL_FEW = 4, VIS_SL_SPREAD = 8, VIS_SL_RANGE = 16 };
+typedef struct vis_scale_link_params {   /* 32 bytes; the defaults are this library's own */
+    int32_t require;                     /* VIS_MP_KEPT   flag bits an entry must carry, 0 ... 255 */
+    int32_t min_shared;                  /* 8             ratios below which the link is VIS_SL_FEW, 1 ... 2^20 */
+    double  max_rel_spread;              /* 1.0           (q75 - q25) / scale above which it is VIS_SL_SPREAD; finite, >= 0, at most 1e6 (loose on
+                                                          purpose: DESIGN.md 4.19 has the spreads measured at 0.3 px and 1 px of noise) */
+    double  min_scale, max_scale;        /* 1/64, 64      finite, 0 < min_scale <= max_scale */
+} vis_scale_link_params;
+typedef struct vis_scale_link { double scale, q25, q75; int32_t n_shared, q, flags, reserved_; } vis_scale_link;           /* 40 bytes */
+void vis_default_scale_link_params(vis_scale_link_params* sp);
+/* Caller-made rows, DEVICE pointers, asynchronous on the context's stream, no plan.  d_prev, d_nlinks: n entries; d_links: n rows of link_cap;
+ * d_pose: n pose records (only R and t are read); d_points / d_flags: n rows of pts_cap; d_depth_carry_in: NULL or ONE row of row_cap doubles, the
+ * depth row of the frame VIS_KF_CARRIED refers to; d_depth: n rows of row_cap doubles -- a pointer to one of its rows is a later call's carried
+ * row, as vis_ftrack_link_rows chains through d_obs; d_link: n records.  Every entry of d_depth and d_link is written.  The workspace (8 bytes per
+ * list entry, only when min(link_cap, pts_cap) > 1024) belongs to the context and only grows; a call that grows it SYNCHRONISES.
+ * Refusals, in this order.  VIS_E_INVALID: sp NULL or outside the ranges above, a NULL d_prev, d_nlinks, d_pose, d_depth or d_link, a NULL d_links,
+ * d_points or d_flags with min(link_cap, pts_cap) > 0, a pointer that is not aligned (16 bytes for d_links and d_points, 8 for d_pose, d_depth,
+ * d_depth_carry_in and d_link, 4 for d_prev and d_nlinks), n, link_cap, pts_cap or row_cap negative.  VIS_E_STATE without a context.
+ * VIS_E_CAPACITY when n x row_cap or n x link_cap exceeds 2^28 entries. */
+int  vis_scale_link_rows(vis_ctx* ctx, const vis_scale_link_params* sp, int n, const int32_t* d_prev, const vis_dmatch* d_links,
+                         const int32_t* d_nlinks, int link_cap, const vis_pose_result* d_pose, const vis_map_point* d_points, const uint8_t* d_flags,
+                         int pts_cap, const double* d_depth_carry_in, int row_cap, double* d_depth, vis_scale_link* d_link);
+/* The pairs of the last vis_batch_run (which must have included VIS_STAGE_POSE; n = its frames) with vis_batch_get_keyframes' pairing, the pose
+ * stage's lists and records, and d_points / d_flags as vis_batch_triangulate wrote them for that run (rows of row_cap >= the plan's
+ * correspondences per pair), as vis_batch_pnp reads them.  The depth rows (keypoint capacity doubles each) live in the plan's workspace, allocated by
+ * the first call.  The plan keeps the row of the last SAVED frame of the launch, so the pair to the keyframe carried from the launch before has
+ * its depth row -- what vis_batch_pnp cannot do (VIS_PNPL_NO_MAP) -- and the links of a stream are the same bytes however it is cut into
+ * launches.  It keeps TWO rows and uses them in turn: a call repeated for the same run reads the row the run was given.  A launch that saved nothing
+ * carries the earlier row forward; vis_batch_plan / vis_batch_reset forget the row; a run that was not linked makes the next run's carried pairs
+ * VIS_SL_NO_DEPTH.  Asynchronous on the POSE stream behind vis_batch_triangulate of the same run; the caller's buffers are in use until
+ * vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: sp as above, a NULL or misaligned d_points (16), d_flags or d_link (8), n or row_cap negative.
+ * VIS_E_CAPACITY: row_cap below the plan's correspondences per pair.  VIS_E_STATE: no context / plan / pose stage, or n differs. */
+int  vis_batch_scale_links(vis_ctx* ctx, const vis_scale_link_params* sp, int n, const vis_map_point* d_points, const uint8_t* d_flags, int row_cap,
+                           vis_scale_link* d_link);
+
+/* 2. THE CHAIN.  Frame i is NOT SAVED when prev[i] == VIS_KF_NOT_SAVED: the zero record with VIS_TJ_NOT_SAVED.  It HAS A PARENT when prev[i] is an
+ * index q of a frame that is not NOT SAVED, or VIS_KF_CARRIED with a carried record (d_carry_in not NULL and its flags without VIS_TJ_NOT_SAVED and
+ * VIS_TJ_OVERFLOW).  A saved frame with a parent and a usable pose record has an EDGE x_i = R_i x_q + sigma_i t_i, sigma_i = sigma_q s_i; every
+ * other saved frame is a ROOT: identity pose, sigma = 1, the start of a segment (flags VIS_TJ_ROOT, with VIS_TJ_NO_POSE when it has a parent but no
+ * usable pose, VIS_TJ_NO_CARRY when prev[i] == VIS_KF_CARRIED without a carried record).  s_i = d_link[i].scale when d_link[i].flags == VIS_SL_OK,
+ * the scale is finite and > 0 and the parent is not a root (a root of this call, or a carried record with VIS_TJ_ROOT); else s_i = 1 and the edge is a UNIT edge (VIS_TJ_UNIT_EDGE): a gauge edge
+ * -- the first edge below a root always is one, its parent has no pair and so no depth row -- or a held scale.
+ * vis_traj_pose: R, t with x_i = R X + t, X in the root's frame (the layout d_poses of the N-view triangulation reads); sigma; segment_seq = the
+ * root's stream number (frame i of a call is seq0 + i); epoch_seq = the stream number of the frame of the LAST unit edge on the way from the root
+ * to i, for a root its own; hops = edges from the root; unit_edges = unit edges among them (1 = scaled throughout); parent = prev[i] normalised;
+ * flags.  Through the carried record the segment is inherited, hops and unit_edges add, and epoch_seq is the carried one when the path inside the
+ * call has no unit edge.  When any of R, t, sigma would not be finite, or sigma would not be > 0, the record is zero with VIS_TJ_OVERFLOW: no NaN
+ * ever reaches a record.  Orthonormality of R is not repaired (DESIGN.md 4.19 has the measured deviation).
+ * COMPOSITION, division-free.  The state (S, R, U) of a path i -> a means x_i = R x_a + sigma_a U and sigma_i = sigma_a S; an edge is
+ * (s_i, R_i, s_i t_i) (each s_i * t_i[r]); path i -> m (S1, R1, U1) followed by m -> a (S2, R2, U2) is S = S1 S2,
+ * R[3r + c] = (R1[3r] R2[c] + R1[3r + 1] R2[3 + c]) + R1[3r + 2] R2[6 + c], U[r] = (((R1[3r] U2[0] + R1[3r + 1] U2[1]) + R1[3r + 2] U2[2]) + S2 U1[r]);
+ * hops and unit_edges add; the epoch is the first path's when that has a unit edge, else the second's.  At a root the record is (R, U, S).  At the
+ * carried record (Rc, tc, sigma_c): R Rc by the product above, t[r] = (((R[3r] tc[0] + R[3r + 1] tc[1]) + R[3r + 2] tc[2]) + sigma_c U[r]),
+ * sigma = sigma_c S.  The frames are chained by pointer doubling: ceil(log2 n) rounds (reach = 1, 2, 4 ... < n), in each of which every frame whose
+ * ancestor is neither itself nor final replaces its state by the composition with its ancestor's state OF THE ROUND BEFORE -- so the rounding of
+ * a record depends on the frame's position in its call, and two cuts of a stream agree within a bound, not byte for byte.
+ * On the device all rounds run inside ONE launch of one workgroup: every thread keeps up to four frames' states in registers, reads the ancestor's,
+ * and workgroup barriers separate reading from writing; the states live in LDS up to 256 frames and in the workspace beyond.  No loop over frames
+ * depends on data.
+ * d_poses (may be NULL): n x 12 doubles, R then t, of the frames whose epoch_seq (same_epoch_only != 0) or segment_seq (== 0) equals that of the
+ * NEWEST frame with a pose (the largest i whose record is neither NOT_SAVED nor OVERFLOW); every other frame gets a zero row = "no pose", which
+ * vis_batch_ftrack_triangulate skips.  Within one epoch all relative poses share one scale, so no track is triangulated across a held scale. */
+enum { VIS_TJ_ROOT = 1, VIS_TJ_NO_POSE = 2, VIS_TJ_NO_CARRY = 4, VIS_TJ_NOT_SAVED = 8, VIS_TJ_UNIT_EDGE = 16, VIS_TJ_OVERFLOW = 32 };
+enum { VIS_TJ_MAX_FRAMES = 1024 };
+typedef struct vis_traj_pose {           /* 128 bytes */
+    double  R[9], t[3], sigma;
+    int32_t segment_seq, epoch_seq, hops, unit_edges, parent, flags;
+} vis_traj_pose;
+/* Caller-made rows, DEVICE pointers, asynchronous on the context's stream.  d_prev, d_pose, d_link, d_traj: n entries; d_carry_in: NULL or ONE record,
+ * that of the frame VIS_KF_CARRIED refers to.  The workspace (120 bytes per frame, only when n > 256) belongs to the context and only grows; a
+ * call that grows it SYNCHRONISES.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL d_prev, d_pose, d_link or d_traj, a pointer that is not aligned (8 bytes for d_pose, d_link,
+ * d_carry_in, d_traj and d_poses, 4 for d_prev), n or seq0 negative.  VIS_E_STATE without a context.  VIS_E_CAPACITY when n > VIS_TJ_MAX_FRAMES. */
+int  vis_trajectory_rows(vis_ctx* ctx, int n, const int32_t* d_prev, const vis_pose_result* d_pose, const vis_scale_link* d_link,
+                         const vis_traj_pose* d_carry_in, int seq0, int same_epoch_only, vis_traj_pose* d_traj, double* d_poses);
+/* The frames of the last vis_batch_run (with VIS_STAGE_POSE; n = its frames) with the pose stage's records, vis_batch_get_keyframes' pairing and
+ * the links vis_batch_scale_links wrote for that run (d_link), on the POSE stream behind it; seq is the plan's frame counter, the one the feature
+ * tracks use.  The plan carries the record of the last SAVED frame across launches, two records used in turn under the rules of the depth row
+ * above (a run that was not chained makes the next run's carried pairs roots with VIS_TJ_NO_CARRY).  The caller's buffers are in use until
+ * vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL or misaligned d_link, d_traj or d_poses (8; d_poses may be NULL), n negative.  VIS_E_STATE: no
+ * context / plan / pose stage, or n differs.  VIS_E_CAPACITY: n > VIS_TJ_MAX_FRAMES. */
+int  vis_batch_trajectory(vis_ctx* ctx, int n, const vis_scale_link* d_link, int same_epoch_only, vis_traj_pose* d_traj, double* d_poses);
+/* The record the NEXT run's vis_batch_trajectory continues from where a frame's pair is the carried keyframe (rec NULL: none).  HOST pointer;
+ * SYNCHRONISES, like vis_batch_track_init.  VIS_E_STATE without a context or plan. */
+int  vis_batch_trajectory_init(vis_ctx* ctx, const vis_traj_pose* rec);
+/* Out of scope: bundle adjustment, loop closure, a metric scale, feeding the trajectory into vis_batch_track or vis_batch_pnp, and a scale between
+ * siblings of one root in tree-shaped caller rows (each sibling is its own unit edge; the plan's pairing is a chain and never makes them). */
 
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */

@@ -32,7 +32,11 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --tracks out.csv: the symmetric matches of every pair linked into feature tracks (vis_batch_ftrack behind every batch, the tracks continuing
              across the batches): one row per frame -- frame index, timestamp, the vis_ftrack_frame fields and the histogram of the
              track length at the frame's keypoints (bins 1, 2, 3-4, 5-8, ... 65-); the JSON line carries the totals.
-  --pnp out.csv: the pose of every frame against the map points of its keyframe's own pair (vis_batch_triangulate, then vis_batch_pnp with
+  --trajectory out.csv: the two-view poses of the stream chained under one scale (vis_batch_triangulate, vis_batch_scale_links,
+             vis_batch_trajectory, then vis_batch_ftrack and vis_batch_ftrack_triangulate on the trajectory's own d_poses, queued behind every
+             batch with no host step between them): one row per frame -- frame index, timestamp, flags, parent, segment_seq, epoch_seq, hops,
+             unit_edges, the link's n_shared and flags, its scale, sigma, R (9) and t (3) in the root's frame.
+  --pnp out.csv:the pose of every frame against the map points of its keyframe's own pair (vis_batch_triangulate, then vis_batch_pnp with
              VIS_MP_KEPT, default parameters, 200 x 3 draws of default_rng(7)): one row per frame -- frame index, timestamp, q, p, n_linked,
              link flags (VIS_PNPL_*), scale, then n_inliers, n_inliers_refined, best_iter, best_root, flags (VIS_PNP_*), cost0, cost1, R (nine,
              row-major), t (units of the baseline p -> q), R_rel, t_rel; the JSON line carries the counts.
@@ -112,6 +116,7 @@ def main():
     ap.add_argument("--polished", default=None, metavar="CSV", help="write every frame's polished two-view pose here")
     ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
     ap.add_argument("--tracks", default=None, metavar="CSV", help="link the symmetric matches into feature tracks; write every frame's summary and length histogram here")
+    ap.add_argument("--trajectory", default=None, metavar="CSV", help="chain the two-view poses under the scale links; write one pose per frame here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -179,6 +184,16 @@ def main():
         d_tframe = torch.empty(B * vislam.FTRACK_FRAME_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
         TRACK_BINS = (1, 2, 3, 5, 9, 17, 33, 65)                # histogram of the track length at a frame: [1], [2], [3, 4], [5, 8], ... [65, inf)
         track_rows, track_totals = [], dict(observations=0, started=0, continued=0, max_len=0, no_carry=0)
+    if a.trajectory:                                            # buffers of its own: the chain below is queued whatever else was asked for
+        if B > vislam.TJ_MAX_FRAMES:
+            raise SystemExit(f"--trajectory chains at most {vislam.TJ_MAX_FRAMES} frames per batch")
+        jcap, jk = int(np.floor(np.sqrt(p.n_cells))) ** 2, ctx.keypoint_capacity(w, h)
+        z = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        d_jmp, d_jmf, d_jms = z(B * jcap * vislam.MAP_POINT_DTYPE.itemsize), z(B * jcap), z(B * vislam.TRI_SUMMARY_DTYPE.itemsize)
+        d_jlink, d_jtraj, d_jposes = z(B * vislam.SCALE_LINK_DTYPE.itemsize), z(B * vislam.TRAJ_POSE_DTYPE.itemsize), z(B * 96)
+        d_jobs, d_jframe = z(B * jk * vislam.FTRACK_OBS_DTYPE.itemsize), z(B * vislam.FTRACK_FRAME_DTYPE.itemsize)
+        d_jpts, d_jfl, d_jsm = z(B * jk * vislam.FTRACK_POINT_DTYPE.itemsize), z(B * jk), z(B * vislam.FTRACK_TRI_SUMMARY_DTYPE.itemsize)
+        traj_rows, traj_totals = [], dict(links_ok=0, roots=0, unit_edges=0, overflow=0, n_view_points=0, n_view_kept=0)
     if a.weights != "identity":
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
@@ -276,6 +291,12 @@ def main():
             ctx.batch_ftrack(nb, tcap, d_tobs.data_ptr(), d_tframe.data_ptr())
         if a.klt:
             ctx.batch_klt(d, nb, kcap, d_krec.data_ptr(), d_kpair.data_ptr(), kp=kltp)
+        if a.trajectory:                                     # run -> triangulate -> scale links -> trajectory -> ftrack -> N-view triangulation: no host step
+            ctx.batch_triangulate(nb, jcap, d_jmp.data_ptr(), d_jmf.data_ptr(), d_jms.data_ptr())
+            ctx.batch_scale_links(nb, d_jmp.data_ptr(), d_jmf.data_ptr(), jcap, d_jlink.data_ptr())
+            ctx.batch_trajectory(nb, d_jlink.data_ptr(), d_jtraj.data_ptr(), d_jposes.data_ptr())
+            ctx.batch_ftrack(nb, jk, d_jobs.data_ptr(), d_jframe.data_ptr())
+            ctx.batch_ftrack_triangulate(nb, d_jobs.data_ptr(), jk, d_jposes.data_ptr(), d_jpts.data_ptr(), d_jfl.data_ptr(), d_jsm.data_ptr())
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -329,6 +350,16 @@ def main():
                 if int(hpose[i]["kind"]) != vislam.HP_NONE:
                     hpose_totals[int(hpose[i]["kind"])] += 1
                     hpose_rows.append((first + i, stamps[first + i], hpose[i].copy(), None if hpol is None else int(hpol[i]["flags"])))
+        if a.trajectory:
+            jl, jt = d_jlink.cpu().numpy().view(vislam.SCALE_LINK_DTYPE), d_jtraj.cpu().numpy().view(vislam.TRAJ_POSE_DTYPE)
+            js = d_jsm.cpu().numpy().view(vislam.FTRACK_TRI_SUMMARY_DTYPE)
+            for i in range(nb):
+                traj_totals["links_ok"] += int(jl[i]["flags"] == vislam.SL_OK and jl[i]["n_shared"] > 0)
+                for key, bit in (("roots", vislam.TJ_ROOT), ("unit_edges", vislam.TJ_UNIT_EDGE), ("overflow", vislam.TJ_OVERFLOW)):
+                    traj_totals[key] += int(bool(int(jt[i]["flags"]) & bit))
+                traj_totals["n_view_points"] += int(js[i]["n_points"])
+                traj_totals["n_view_kept"] += int(js[i]["n_kept"])
+                traj_rows.append((first + i, stamps[first + i], jt[i].copy(), jl[i].copy()))
         if a.tracks:
             tobs = d_tobs.cpu().numpy().view(vislam.FTRACK_OBS_DTYPE).reshape(B, tcap)
             tfr = d_tframe.cpu().numpy().view(vislam.FTRACK_FRAME_DTYPE)
@@ -440,8 +471,16 @@ def main():
                         + ",".join("%.17g" % v for v in r["H"]) + "\n")
         out["models_csv"] = a.models
         out["models"] = dict(zip(vislam.MODEL_NAMES, model_totals))
+    if a.trajectory:
+        with open(a.trajectory, "w") as f:                      # frame, stamp, the vis_traj_pose integers, the link's n_shared and flags, scale, sigma, R, t
+            for fi, ts, r, l in traj_rows:
+                ints = [r[k] for k in ("flags", "parent", "segment_seq", "epoch_seq", "hops", "unit_edges")] + [l["n_shared"], l["flags"]]
+                dbl = [l["scale"], r["sigma"]] + list(r["R"]) + list(r["t"])
+                f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + "," + ",".join("%.17g" % v for v in dbl) + "\n")
+        out["trajectory_csv"] = a.trajectory
+        out["trajectory"] = traj_totals
     if a.tracks:
-        with open(a.tracks, "w") as f:                          # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
+        with open(a.tracks, "w") as f:                         # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
             for r in track_rows:
                 f.write(",".join("%d" % v for v in r) + "\n")
         out["tracks_csv"] = a.tracks

@@ -144,6 +144,8 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
     if (ctx->d_ess_ws) (void)hipFree(ctx->d_ess_ws);
     if (ctx->d_ft_ws) (void)hipFree(ctx->d_ft_ws);
+    if (ctx->d_sl_ws) (void)hipFree(ctx->d_sl_ws);
+    if (ctx->d_tjr_ws) (void)hipFree(ctx->d_tjr_ws);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -274,7 +276,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n); F(pl->d_ft_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n); F(pl->d_ft_ws); F(pl->d_tj_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1257,6 +1259,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->pyr_frames = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
     ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft_run = -1; ctx->batch->ft_have = false;   // vis_batch_ftrack: no carried row, seq restarts at 0
+    ctx->batch->sl_run = ctx->batch->tj_run = -1; ctx->batch->sl_have = ctx->batch->tj_have = false;   // scale links / trajectory: nothing carried
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
@@ -2046,6 +2049,172 @@ extern "C" int vis_batch_ftrack_triangulate(vis_ctx* ctx, const vis_ftrack_tri_p
         if (!rc2) ctx->pose_pending = true;
         return rc2;
     }, {&pl->out().readers, &pl->last_set().matcher, pl->kf_min ? &pl->last_set().links : nullptr});
+}
+
+// ---- scale links and the chained trajectory: trajectory.hip
+static int ensure_rows_block(vis_ctx* ctx, void*& block, size_t& have, size_t bytes, const char* who) {
+    if (bytes <= have) return VIS_OK;
+    sync_all(ctx);                                                 // work queued on any stream may still use the old block
+    if (block) (void)hipFree(block);
+    block = nullptr; have = 0;
+    if (hipMalloc(&block, bytes) != hipSuccess) {
+        (void)hipGetLastError(); block = nullptr;
+        ctx->err = std::string(who) + ": out of device memory for the workspace"; return VIS_E_NOMEM;
+    }
+    have = bytes;
+    return VIS_OK;
+}
+
+extern "C" void vis_default_scale_link_params(vis_scale_link_params* sp) {
+    if (!sp) return;
+    sp->require = VIS_MP_KEPT; sp->min_shared = 8; sp->max_rel_spread = 1.0; sp->min_scale = 1.0 / 64.0; sp->max_scale = 64.0;
+}
+
+static bool scale_link_params_ok(const vis_scale_link_params* sp) {
+    return sp && sp->require >= 0 && sp->require <= 255 && sp->min_shared >= 1 && sp->min_shared <= (1 << 20) && std::isfinite(sp->max_rel_spread) &&
+           sp->max_rel_spread >= 0.0 && sp->max_rel_spread <= 1e6 && std::isfinite(sp->min_scale) && std::isfinite(sp->max_scale) && sp->min_scale > 0.0 &&
+           sp->min_scale <= sp->max_scale;
+}
+
+extern "C" int vis_scale_link_rows(vis_ctx* ctx, const vis_scale_link_params* sp, int n, const int32_t* d_prev, const vis_dmatch* d_links,
+                                   const int32_t* d_nlinks, int link_cap, const vis_pose_result* d_pose, const vis_map_point* d_points,
+                                   const uint8_t* d_flags, int pts_cap, const double* d_depth_carry_in, int row_cap, double* d_depth,
+                                   vis_scale_link* d_link) {
+    if (!scale_link_params_ok(sp) || !d_prev || !d_nlinks || !d_pose || !d_depth || !d_link) return VIS_E_INVALID;
+    if (std::min(link_cap, pts_cap) > 0 && (!d_links || !d_points || !d_flags)) return VIS_E_INVALID;
+    if (!aligned(d_links, 16) || !aligned(d_points, 16) || !aligned(d_pose, 8) || !aligned(d_depth, 8) || !aligned(d_depth_carry_in, 8) || !aligned(d_link, 8) ||
+        !aligned(d_prev, 4) || !aligned(d_nlinks, 4)) return VIS_E_INVALID;
+    if (n < 0 || link_cap < 0 || pts_cap < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if ((size_t)n * (size_t)row_cap > ((size_t)1 << 28) || (size_t)n * (size_t)link_cap > ((size_t)1 << 28)) {
+        ctx->err = "vis_scale_link_rows: n x row_cap or n x link_cap exceeds 2^28 entries"; return VIS_E_CAPACITY;
+    }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const int mcap = std::min(link_cap, pts_cap);
+    SlWork W;
+    Carver measure{nullptr, 0, SIZE_MAX};
+    W.layout(measure, (size_t)n, (size_t)mcap);
+    const int rc = ensure_rows_block(ctx, ctx->d_sl_ws, ctx->sl_ws_bytes, measure.off, "vis_scale_link_rows");
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_sl_ws, 0, ctx->sl_ws_bytes};
+    W.layout(cv, (size_t)n, (size_t)mcap);
+    if (cv.overflow) { ctx->err = "vis_scale_link_rows: workspace too small (internal)"; return VIS_E_NOMEM; }
+    return scale_link_run(ctx, sp, n, FtFrames{d_prev, 0, nullptr}, d_links, d_nlinks, link_cap, mcap, d_pose, d_points, d_flags, pts_cap, d_depth_carry_in,
+                          row_cap, d_depth, W.keys, d_link, nullptr);
+}
+
+extern "C" int vis_trajectory_rows(vis_ctx* ctx, int n, const int32_t* d_prev, const vis_pose_result* d_pose, const vis_scale_link* d_link,
+                                   const vis_traj_pose* d_carry_in, int seq0, int same_epoch_only, vis_traj_pose* d_traj, double* d_poses) {
+    if (!d_prev || !d_pose || !d_link || !d_traj) return VIS_E_INVALID;
+    if (!aligned(d_pose, 8) || !aligned(d_link, 8) || !aligned(d_carry_in, 8) || !aligned(d_traj, 8) || !aligned(d_poses, 8) || !aligned(d_prev, 4)) return VIS_E_INVALID;
+    if (n < 0 || seq0 < 0) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_TJ_MAX_FRAMES) { ctx->err = "vis_trajectory_rows: more than VIS_TJ_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    TjWork W;
+    Carver measure{nullptr, 0, SIZE_MAX};
+    W.layout(measure, (size_t)n);
+    const int rc = ensure_rows_block(ctx, ctx->d_tjr_ws, ctx->tjr_ws_bytes, measure.off, "vis_trajectory_rows");
+    if (rc) return rc;
+    Carver cv{(char*)ctx->d_tjr_ws, 0, ctx->tjr_ws_bytes};
+    W.layout(cv, (size_t)n);
+    if (cv.overflow) { ctx->err = "vis_trajectory_rows: workspace too small (internal)"; return VIS_E_NOMEM; }
+    return trajectory_run(ctx, n, FtFrames{d_prev, 0, nullptr}, d_pose, d_link, d_carry_in, seq0, same_epoch_only, W.D, W.I, d_traj, d_poses, nullptr);
+}
+
+// the plan's block: one list, measured and then bound
+struct TrajPlanWork { double* depth; double* sl_carry[2]; SlWork sl; TjWork tj; vis_traj_pose* tj_carry[2]; };
+static void traj_plan_layout(Carver& cv, Plan* pl, TrajPlanWork& W) {
+    W.depth = cv.take<double>((size_t)pl->B * pl->kcap);
+    W.sl_carry[0] = cv.take<double>((size_t)pl->kcap); W.sl_carry[1] = cv.take<double>((size_t)pl->kcap);
+    W.sl.layout(cv, (size_t)pl->B, (size_t)pl->pose_mcap);
+    W.tj.layout(cv, (size_t)pl->B);
+    W.tj_carry[0] = cv.take<vis_traj_pose>(1); W.tj_carry[1] = cv.take<vis_traj_pose>(1);
+}
+static int ensure_traj(vis_ctx* ctx, Plan* pl, TrajPlanWork& W) {
+    if (!pl->d_tj_ws) {
+        Carver measure{nullptr, 0, SIZE_MAX};
+        traj_plan_layout(measure, pl, W);
+        if (measure.overflow) return VIS_E_NOMEM;
+        if (hipMalloc(&pl->d_tj_ws, measure.off + 256) != hipSuccess) {
+            (void)hipGetLastError(); pl->d_tj_ws = nullptr;
+            ctx->err = "vis_batch_scale_links / vis_batch_trajectory: out of device memory for the plan's workspace"; return VIS_E_NOMEM;
+        }
+        pl->sl_run = pl->tj_run = -1; pl->sl_have = pl->tj_have = false;
+    }
+    Carver cv{(char*)pl->d_tj_ws, 0, SIZE_MAX};
+    traj_plan_layout(cv, pl, W);
+    pl->sl_depth = W.depth; pl->sl_carry[0] = W.sl_carry[0]; pl->sl_carry[1] = W.sl_carry[1]; pl->tj_carry[0] = W.tj_carry[0]; pl->tj_carry[1] = W.tj_carry[1];
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_scale_links(vis_ctx* ctx, const vis_scale_link_params* sp, int n, const vis_map_point* d_points, const uint8_t* d_flags,
+                                     int row_cap, vis_scale_link* d_link) {
+    if (!scale_link_params_ok(sp) || !d_points || !d_flags || !d_link || !aligned(d_points, 16) || !aligned(d_link, 8) || n < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (ctx && ctx->batch && row_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_scale_links: row_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_scale_links: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;        // (before the workspace is allocated)
+    (void)hipSetDevice(ctx->device);
+    TrajPlanWork W;
+    { const int rc = ensure_traj(ctx, pl, W); if (rc) return rc; }
+    // the row this launch continues: the one the launch before wrote, or -- the call repeated for the same run -- the one it read itself
+    const bool again = pl->sl_run == pl->run_count;
+    const bool have = again ? pl->sl_have : (pl->sl_run >= 0 && pl->sl_run == pl->run_count - 1);
+    const int in = again ? pl->sl_in : (pl->sl_in ^ 1);
+    // on the pose stream behind the pose stage and vis_batch_triangulate of the run, like vis_batch_pnp; the link table is read there too
+    const int rc = batch_epi(ctx, n, "vis_batch_scale_links", [&](Plan* pl_, Plan::MatchOut& O, const int32_t* d_npts) {
+        const bool sym = ctx->p.pose_input == VIS_POSE_SYM;
+        const int rc2 = scale_link_run(ctx, sp, n, plan_frames(pl_), sym ? O.sym : O.good, d_npts, sym ? pl_->kcap : pl_->root * pl_->root, pl_->pose_mcap, pl_->d_pose,
+                                       d_points, d_flags, row_cap, have ? pl_->sl_carry[in] : nullptr, pl_->kcap, pl_->sl_depth, W.sl.keys, d_link, pl_->sl_carry[in ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->sl_in = in; pl->sl_have = have; pl->sl_run = pl->run_count;
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_trajectory(vis_ctx* ctx, int n, const vis_scale_link* d_link, int same_epoch_only, vis_traj_pose* d_traj, double* d_poses) {
+    if (!d_link || !d_traj || !aligned(d_link, 8) || !aligned(d_traj, 8) || !aligned(d_poses, 8) || n < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_trajectory: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_TJ_MAX_FRAMES) { ctx->err = "vis_batch_trajectory: more than VIS_TJ_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    TrajPlanWork W;
+    { const int rc = ensure_traj(ctx, pl, W); if (rc) return rc; }
+    const bool again = pl->tj_run == pl->run_count;
+    const bool have = again ? pl->tj_have : (pl->tj_run >= 0 && pl->tj_run == pl->run_count - 1);
+    const int in = again ? pl->tj_in : (pl->tj_in ^ 1);
+    // on the pose stream behind vis_batch_scale_links of the run, which wrote d_link there, and behind the pose stage
+    const int rc = batch_epi(ctx, n, "vis_batch_trajectory", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = trajectory_run(ctx, n, plan_frames(pl_), pl_->d_pose, d_link, have ? pl_->tj_carry[in] : nullptr, pl_->seq0, same_epoch_only, W.tj.D, W.tj.I,
+                                       d_traj, d_poses, pl_->tj_carry[in ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->tj_in = in; pl->tj_have = have; pl->tj_run = pl->run_count;
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_trajectory_init(vis_ctx* ctx, const vis_traj_pose* rec) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                 // (a chain kernel in flight reads and writes the records)
+    Plan* pl = ctx->batch;
+    TrajPlanWork W;
+    { const int rc = ensure_traj(ctx, pl, W); if (rc) return rc; }
+    if (!rec) { pl->tj_run = -1; pl->tj_have = false; return VIS_OK; }
+    // the record takes the place of what a call for the current run would have left for the next one
+    HIPCHK(ctx, hipMemcpy(pl->tj_carry[pl->tj_in ^ 1], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->tj_run = pl->run_count;
+    return VIS_OK;
 }
 
 // ---- the pose stage on device rows: pose_run on a workspace of the context's own

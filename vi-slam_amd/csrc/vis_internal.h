@@ -118,6 +118,11 @@ struct Plan {
     void* d_ft_ws = nullptr; vis_ftrack_obs* ft_carry[2] = {nullptr, nullptr};
     int ft_in = 0, ft_run = -1; bool ft_have = false;
     int seq_next = 0, seq0 = 0;
+    // vis_batch_scale_links / vis_batch_trajectory (trajectory.hip), allocated by the first call of either (ensure_traj): ONE block -- the depth
+    // rows (B x kcap doubles), the two carried depth rows, SlWork for B pairs of pose_mcap entries, TjWork for B frames, the two carried records.
+    // sl_* / tj_*: the turn, the run_count of the last call and whether it had something to read, with the meaning of ft_in / ft_run / ft_have
+    void* d_tj_ws = nullptr; double* sl_depth = nullptr; double* sl_carry[2] = {nullptr, nullptr}; vis_traj_pose* tj_carry[2] = {nullptr, nullptr};
+    int sl_in = 0, sl_run = -1, tj_in = 0, tj_run = -1; bool sl_have = false, tj_have = false;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -215,6 +220,8 @@ struct vis_ctx {
     void* d_ess_ws = nullptr; size_t ess_ws_bytes = 0;
     // grow-only workspace of vis_ftrack_link_rows (FtWork for n rows of row_cap), apart from the scratch block for the same reason
     void* d_ft_ws = nullptr; size_t ft_ws_bytes = 0;
+    // grow-only workspaces of vis_scale_link_rows (SlWork) and vis_trajectory_rows (TjWork): two blocks, so neither call can move the other's
+    void* d_sl_ws = nullptr; size_t sl_ws_bytes = 0; void* d_tjr_ws = nullptr; size_t tjr_ws_bytes = 0;
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)
@@ -554,6 +561,27 @@ int ftrack_link_run(vis_ctx* ctx, const FtWork& W, int n, int R, FtFrames fr, co
 int ftrack_triangulate_run(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, int R, FtFrames fr, const vis_ftrack_obs* d_obs, int ocap,
                            const void* d_xy, size_t xy_row, int xy_step, const double* d_poses, vis_ftrack_point* d_points, uint8_t* d_flags,
                            vis_ftrack_tri_summary* d_summary);
+// trajectory.hip.  SL_LDS_CAP: list entries per pair up to which the ratio pass keeps its keys in LDS; TJ_LDS_N: frames per call up to which the chain
+// keeps its elements in LDS.  The workspaces beyond those sizes, declared once: keys (n x mcap 64-bit patterns), D / I (13 doubles and 4 ints per
+// frame, structure of arrays).
+#define SL_LDS_CAP 1024
+#define TJ_LDS_N 256
+struct SlWork {
+    unsigned long long* keys = nullptr;
+    void layout(Carver& cv, size_t n, size_t mcap) { keys = mcap > SL_LDS_CAP ? cv.take<unsigned long long>(n * mcap) : nullptr; }
+};
+struct TjWork {
+    double* D = nullptr; int32_t* I = nullptr;
+    void layout(Carver& cv, size_t n) { D = n > TJ_LDS_N ? cv.take<double>(13 * n) : nullptr; I = n > TJ_LDS_N ? cv.take<int32_t>(4 * n) : nullptr; }
+};
+// k_sl_depth + k_sl_ratio (+ k_sl_carry when d_carry_out) on ctx->stream; sp validated by the caller.  d_links: rows of link_cap of which the first
+// mcap <= min(link_cap, pts_cap) count; d_points / d_flags: rows of pts_cap; d_carry: a row of row_cap doubles or null; d_depth: n rows of row_cap
+int scale_link_run(vis_ctx* ctx, const vis_scale_link_params* sp, int n, FtFrames fr, const vis_dmatch* d_links, const int32_t* d_nlinks, int link_cap,
+                   int mcap, const PoseOut* d_pose, const vis_map_point* d_points, const uint8_t* d_flags, int pts_cap, const double* d_carry,
+                   int row_cap, double* d_depth, unsigned long long* d_keys, vis_scale_link* d_link, double* d_carry_out);
+// k_tj_chain on ctx->stream: one launch.  d_carry: one record or null; d_poses, d_carry_out: null or the outputs
+int trajectory_run(vis_ctx* ctx, int n, FtFrames fr, const PoseOut* d_pose, const vis_scale_link* d_link, const vis_traj_pose* d_carry, int seq0,
+                   int same_epoch_only, double* d_wsD, int32_t* d_wsI, vis_traj_pose* d_traj, double* d_poses, vis_traj_pose* d_carry_out);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

@@ -315,6 +315,26 @@ FT_SYM, FT_GOOD = 0, 1
 FTP_FRONT, FTP_REPROJ_OK, FTP_PARALLAX_OK, FTP_KEPT, FTP_FEW, FTP_SINGULAR = 1, 2, 4, 8, 16, 32
 
 
+class ScaleLinkParams(C.Structure):
+    """vis_scale_link_params: the knobs of the scale links (vis_default_scale_link_params: VIS_MP_KEPT, 8, 1.0, 1/64, 64)"""
+    _fields_ = [("require", C.c_int32), ("min_shared", C.c_int32), ("max_rel_spread", C.c_double), ("min_scale", C.c_double), ("max_scale", C.c_double)]
+
+
+class TrajPose(C.Structure):
+    """vis_traj_pose as a host structure (vis_batch_trajectory_init)"""
+    _fields_ = [("R", C.c_double * 9), ("t", C.c_double * 3), ("sigma", C.c_double), ("segment_seq", C.c_int32), ("epoch_seq", C.c_int32),
+                ("hops", C.c_int32), ("unit_edges", C.c_int32), ("parent", C.c_int32), ("flags", C.c_int32)]
+
+
+SCALE_LINK_DTYPE = np.dtype([("scale", "<f8"), ("q25", "<f8"), ("q75", "<f8"), ("n_shared", "<i4"), ("q", "<i4"), ("flags", "<i4"), ("reserved_", "<i4")])
+TRAJ_POSE_DTYPE = np.dtype([("R", "<f8", (9,)), ("t", "<f8", (3,)), ("sigma", "<f8"), ("segment_seq", "<i4"), ("epoch_seq", "<i4"), ("hops", "<i4"),
+                            ("unit_edges", "<i4"), ("parent", "<i4"), ("flags", "<i4")])
+assert SCALE_LINK_DTYPE.itemsize == 40 and TRAJ_POSE_DTYPE.itemsize == 128 == C.sizeof(TrajPose) and C.sizeof(ScaleLinkParams) == 32
+SL_OK, SL_NO_PAIR, SL_NO_DEPTH, SL_FEW, SL_SPREAD, SL_RANGE = 0, 1, 2, 4, 8, 16
+TJ_ROOT, TJ_NO_POSE, TJ_NO_CARRY, TJ_NOT_SAVED, TJ_UNIT_EDGE, TJ_OVERFLOW = 1, 2, 4, 8, 16, 32
+TJ_MAX_FRAMES = 1024
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -365,6 +385,8 @@ ABI_SYMBOLS = [
     "vis_warp_keypoints", "vis_bf_knn2_hamming_guided", "vis_bf_knn2_hamming_guided_host", "vis_good_matches_guided", "vis_batch_run_guided",
     "vis_default_klt_params", "vis_klt_track", "vis_klt_batch", "vis_batch_klt",
     "vis_ftrack_link_rows", "vis_batch_ftrack", "vis_default_ftrack_tri_params", "vis_ftrack_triangulate_rows", "vis_batch_ftrack_triangulate",
+    "vis_default_scale_link_params", "vis_scale_link_rows", "vis_batch_scale_links", "vis_trajectory_rows", "vis_batch_trajectory",
+    "vis_batch_trajectory_init",
 ]
 
 
@@ -459,6 +481,15 @@ def _load():
         lib.vis_default_ftrack_tri_params.restype = None
         lib.vis_ftrack_triangulate_rows.argtypes = [vp, ftp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
         lib.vis_batch_ftrack_triangulate.argtypes = [vp, ftp, ci, vp, ci, vp, vp, vp, vp]
+    if hasattr(lib, "vis_batch_trajectory"):            # (absent from older A/B builds)
+        slp = C.POINTER(ScaleLinkParams)
+        lib.vis_default_scale_link_params.argtypes = [slp]
+        lib.vis_default_scale_link_params.restype = None
+        lib.vis_scale_link_rows.argtypes = [vp, slp, ci, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, vp, vp]
+        lib.vis_batch_scale_links.argtypes = [vp, slp, ci, vp, vp, ci, vp]
+        lib.vis_trajectory_rows.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, vp, vp]
+        lib.vis_batch_trajectory.argtypes = [vp, ci, vp, ci, vp, vp]
+        lib.vis_batch_trajectory_init.argtypes = [vp, C.POINTER(TrajPose)]
     if hasattr(lib, "vis_essential_refine_batch"):      # (absent from older A/B builds)
         epp = C.POINTER(EssentialRefineParams)
         lib.vis_default_eref_params.argtypes = [epp]
@@ -612,6 +643,12 @@ def default_pnp_params():
     pp = PnpParams()
     lib.vis_default_pnp_params(C.byref(pp))
     return pp
+
+
+def default_scale_link_params():
+    sp = ScaleLinkParams()
+    lib.vis_default_scale_link_params(C.byref(sp))
+    return sp
 
 
 def default_ftrack_tri_params():
@@ -1404,6 +1441,41 @@ class Context:
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_ftrack_triangulate(self._h, C.byref(tp), n, v(d_obs_ptr), row_cap, v(d_poses_ptr), v(d_points_ptr), v(d_flags_ptr),
                                                    v(d_summary_ptr)), "vis_batch_ftrack_triangulate")
+
+    # -- a scaled trajectory: scale links between consecutive pairs, and the chain -----------------------------------
+    def scale_link_rows(self, n, d_prev_ptr, d_links_ptr, d_nlinks_ptr, link_cap, d_pose_ptr, d_points_ptr, d_flags_ptr, pts_cap, row_cap,
+                        d_depth_ptr, d_link_ptr, d_depth_carry_in_ptr=0, sp=None):
+        """queue the scale links of n frames of caller rows on the context's stream (raw DEVICE pointers; 0 / None = NULL for the carried depth
+        row): n rows of row_cap doubles (the depth rows) and n SCALE_LINK_DTYPE records"""
+        sp = default_scale_link_params() if sp is None else sp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_scale_link_rows(self._h, C.byref(sp), n, v(d_prev_ptr), v(d_links_ptr), v(d_nlinks_ptr), link_cap, v(d_pose_ptr), v(d_points_ptr),
+                                          v(d_flags_ptr), pts_cap, v(d_depth_carry_in_ptr), row_cap, v(d_depth_ptr), v(d_link_ptr)), "vis_scale_link_rows")
+
+    def batch_scale_links(self, n, d_points_ptr, d_flags_ptr, row_cap, d_link_ptr, sp=None):
+        """the same for the pairs of the last batch_run with the rows batch_triangulate wrote for it, on the pose stream; the plan carries the depth
+        row of the last saved frame to the next launch.  n SCALE_LINK_DTYPE records, in use until batch_sync()"""
+        sp = default_scale_link_params() if sp is None else sp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_scale_links(self._h, C.byref(sp), n, v(d_points_ptr), v(d_flags_ptr), row_cap, v(d_link_ptr)), "vis_batch_scale_links")
+
+    def trajectory_rows(self, n, d_prev_ptr, d_pose_ptr, d_link_ptr, d_traj_ptr, d_poses_ptr=0, d_carry_in_ptr=0, seq0=0, same_epoch_only=True):
+        """queue the chain of n frames of caller rows on the context's stream: n TRAJ_POSE_DTYPE records and, when d_poses_ptr is given, n x 12
+        doubles for ftrack_triangulate_rows / batch_ftrack_triangulate"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_trajectory_rows(self._h, n, v(d_prev_ptr), v(d_pose_ptr), v(d_link_ptr), v(d_carry_in_ptr), seq0, 1 if same_epoch_only else 0,
+                                          v(d_traj_ptr), v(d_poses_ptr)), "vis_trajectory_rows")
+
+    def batch_trajectory(self, n, d_link_ptr, d_traj_ptr, d_poses_ptr=0, same_epoch_only=True):
+        """the same for the frames of the last batch_run with the links batch_scale_links wrote for it, on the pose stream behind that call"""
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_trajectory(self._h, n, v(d_link_ptr), 1 if same_epoch_only else 0, v(d_traj_ptr), v(d_poses_ptr)), "vis_batch_trajectory")
+
+    def batch_trajectory_init(self, rec=None):
+        """the record (a TRAJ_POSE_DTYPE element or a TrajPose; None: none) the next run's batch_trajectory continues from; synchronises"""
+        if rec is not None and not isinstance(rec, TrajPose):
+            rec = TrajPose.from_buffer_copy(np.asarray(rec, TRAJ_POSE_DTYPE).tobytes())
+        self._chk(lib.vis_batch_trajectory_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_trajectory_init")
 
     # -- the essential-matrix pose on device rows, and its refinement ----------------------------------------------
     def essential_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr):
