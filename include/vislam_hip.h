@@ -165,7 +165,7 @@ int  vis_get_params(vis_ctx* ctx, vis_params* p);
  * into one of three classes (DESIGN.md has the table, one row per entry point; tests/test_caller_stream_gpu.py checks it):
  *   1. Calls on the context's stream -- vis_gradient_batch, vis_align_batch, vis_klt_batch, vis_f2f_batch, vis_filter_keypoints_batch,
  *      vis_homography_batch / _pose_batch / _polish_batch, vis_pnp_batch, vis_essential_batch / _refine_batch / _polish_batch,
- *      vis_ftrack_link_rows, vis_ftrack_triangulate_rows, vis_scale_link_rows, vis_trajectory_rows, vis_rectify_batch (and vis_synth_frames_device, which is ordered the same way
+ *      vis_ftrack_link_rows, vis_ftrack_triangulate_rows, vis_scale_link_rows, vis_trajectory_rows, vis_imu_preintegrate_rows, vis_rectify_batch (and vis_synth_frames_device, which is ordered the same way
  *      but blocks the host: see there).  They run in stream order: they wait
  *      for whatever the caller queued on that stream before the call (the producers of their device inputs), and their outputs may be
  *      read by anything queued on that stream after the call -- no host synchronisation on either side.  Those that write buffers an
@@ -178,7 +178,7 @@ int  vis_get_params(vis_ctx* ctx, vis_params* p);
  *      every getter are read after vis_batch_sync (or through a getter, which synchronises); d_rot is in use until then.
  *   3. Follow-ups of the last vis_batch_run on the pose stream.  vis_batch_align, vis_batch_track, vis_batch_klt, vis_batch_f2f,
  *      vis_batch_filter_keypoints, vis_batch_homography / _pose / _polish, vis_batch_pnp, vis_batch_essential_refine / _polish,
- *      vis_batch_ftrack_triangulate, vis_batch_scale_links, vis_batch_trajectory, and vis_batch_ftrack when it is given a d_mask, FORK from the context's stream: they wait for what
+ *      vis_batch_ftrack_triangulate, vis_batch_scale_links, vis_batch_trajectory, vis_batch_imu, and vis_batch_ftrack when it is given a d_mask, FORK from the context's stream: they wait for what
  *      was queued on it before the call, so their caller device inputs may be produced there.  vis_batch_triangulate,
  *      vis_batch_triangulate_from and vis_batch_ftrack without a mask do NOT wait for the context's stream: what they read from caller
  *      buffers must be complete (or have been written by an earlier follow-up, which the pose stream orders).  None of them is joined
@@ -586,7 +586,7 @@ int  vis_batch_triangulate(vis_ctx* ctx, const vis_tri_params* tp, int n, int ro
 
 /* ---- IMU-aided translation and epipolar keypoint filter: VISystem::F2FRansac (src/VISystem.cpp:612-769) and VISystem::FilterKeypoints
  * (:542-610) for the pairs of a batch -- the pose steps of the ground-truth main's AddFrame (:358-359, :523-527).  The rotation of every
- * pair is an INPUT (the reference integrates the IMU for it; that is outside this library).  Both use one test per correspondence:
+ * pair is an INPUT (the reference integrates the IMU for it; vis_batch_imu / vis_imu_preintegrate_rows below write it on the device).  Both use one test per correspondence:
  *     -1000 / log10(|dir . normal|) < threshold,   normal = bearing1 x (R bearing2),  bearings ((u - cx) / fx, (v - cy) / fy, 1) normalised
  * with dir = a RANSAC hypothesis (F2FRansac) or the given translation's direction (FilterKeypoints).  The device decides it by two compares
  * and evaluates the expression itself only in a narrow band around 10^(-1000 / threshold): the result is that of the expression for every input
@@ -1547,6 +1547,109 @@ int  vis_batch_trajectory(vis_ctx* ctx, int n, const vis_scale_link* d_link, int
 int  vis_batch_trajectory_init(vis_ctx* ctx, const vis_traj_pose* rec);
 /* Out of scope: bundle adjustment, loop closure, a metric scale, feeding the trajectory into vis_batch_track or vis_batch_pnp, and a scale between
  * siblings of one root in tree-shaped caller rows (each sibling is its own unit edge; the plan's pairing is a chain and never makes them). */
+
+/* ---- IMU preintegration: the rotation of every pair (the d_rot of vis_batch_f2f, vis_batch_filter_keypoints, vis_batch_run_guided and the hint of
+ * vis_batch_homography_pose) and the pair's motion deltas, on the device, with the plan's own pairing.  The reference computes the same quantity,
+ * RotationResCam = imu2camRotation^T R(t_keyframe)^T R(t_frame) imu2camRotation, from the orientation of an external filter node; here standard
+ * preintegration (Lupton & Sukkarieh 2012; Forster et al. 2017, restated from the papers) takes the filter's place.  tests/imu_ref.py restates every
+ * operation below, and every record equals the restatement byte for byte: double arithmetic, + - * / and comparisons only (no sin, cos, sqrt),
+ * nothing contracted.  "finite(x)" is |x| <= DBL_MAX.
+ * PRODUCTS, summed left to right as in the trajectory's composition: (A B)[3r + c] = (A[3r] B[c] + A[3r + 1] B[3 + c]) + A[3r + 2] B[6 + c];
+ * (A^T B)[3r + c] = (A[r] B[c] + A[3 + r] B[3 + c]) + A[6 + r] B[6 + c]; (A x)[r] = (A[3r] x[0] + A[3r + 1] x[1]) + A[3r + 2] x[2].
+ * SAMPLES: t in seconds, rising; w in rad/s and a in m/s^2 in the IMU frame.  ub(x) = the first sample index with t > x and lb(x) = the first
+ * with t >= x, by binary search (lo = 0, hi = n_samples; mid = (lo + hi) >> 1; `t[mid] <= x` resp. `t[mid] < x` moves lo to mid + 1, else hi to mid),
+ * so a launch's sample array may overlap the one before.
+ * 1. INTERVALS.  Interval i is (ta, tb] = (t_{i-1}, t_i] of d_tframe, t_{-1} = the carry's t_last.  Its delta starts as the identity (R = I, v = p = 0,
+ * JRg = 0, n_steps = 0, flags = 0) with dt = tb - ta (0 when that is not finite).  Interval 0 without a carried time: VIS_IMU_NO_START, dt = 0,
+ * nothing more.  ta or tb not finite: VIS_IMU_NONFINITE.  n_samples == 0: VIS_IMU_EMPTY | VIS_IMU_EXTRAPOLATED.  Else the VALUE at a breakpoint x
+ * (ta, then tb), with j = ub(x): j == 0 holds sample 0 and j == n_samples holds the last sample, each VIS_IMU_EXTRAPOLATED unless that sample's t
+ * equals x; otherwise u = (x - t[j-1]) / (t[j] - t[j-1]) and every component is s[j-1] + u (s[j] - s[j-1]).  The samples strictly inside are
+ * [ub(ta), lb(tb)); none: VIS_IMU_EMPTY.  Every sample so used (held, bracketing or inside) must have finite t, w and a, else VIS_IMU_NONFINITE and
+ * no sub-step is taken.  The sub-steps run from (ta, value) over the inside samples to (tb, value); one from (t0, w0, a0) to (t1, w1, a1):
+ *   h = t1 - t0; not h > 0: VIS_IMU_ORDER, skipped.  Else n_steps += 1; h > max_gap_s: VIS_IMU_GAP;
+ *   phi[k] = (0.5 (w0[k] + w1[k]) - bg[k]) h; xx = phi0 phi0, yy, zz, xy = phi0 phi1, xz, yz alike; th2 = (xx + yy) + zz;
+ *   th2 > max_angle max_angle: VIS_IMU_FAST;
+ *   A, B, C = the Horner sums c[0] + th2 (c[1] + th2 (... + th2 c[9])) of VIS_IMU_COEF_A / _B / _C: sin th / th, (1 - cos th) / th^2, (th - sin th) / th^3;
+ *   dR = Exp(phi) = { 1 - B (yy + zz), B xy - A phi2, B xz + A phi1;  B xy + A phi2, 1 - B (xx + zz), B yz - A phi0;  B xz - A phi1, B yz + A phi0, 1 - B (xx + yy) };
+ *   Jr(phi)       = { 1 - C (yy + zz), C xy + B phi2, C xz - B phi1;  C xy - B phi2, 1 - C (xx + zz), C yz + B phi0;  C xz + B phi1, C yz - B phi0, 1 - C (xx + yy) };
+ *   R' = R dR; am[r] = 0.5 ((R (a0 - ba))[r] + (R' (a1 - ba))[r]); p[r] = p[r] + (v[r] h + (0.5 am[r]) (h h)); then v[r] = v[r] + am[r] h;
+ *   JRg[k] = (dR^T JRg)[k] - Jr[k] h; R = R'.
+ * Ten terms: the first dropped term bounds the truncation, th^20 / 21! (A), / 22! (B), / 23! (C) -- 2e-20 at th = 1, below half an ulp of the sums,
+ * and 2.1e-14 at th = 2.  max_angle defaults to 1; a sub-step beyond it is integrated all the same and says so (VIS_IMU_FAST).  The scheme is the
+ * midpoint rule, second order in the sample period.  At the end any number of the delta that is not finite, or VIS_IMU_NONFINITE from above, gives
+ * the identity again with dt, n_steps and the flags kept and VIS_IMU_NONFINITE set: no NaN or infinity reaches a record.
+ * 2. PAIRS.  prev[i] as for vis_trajectory_rows.  The pair of frame i with keyframe q = prev[i] is the COMPOSITION of the intervals q + 1 ... i -- by
+ * definition; a direct integration over (t_q, t_i] differs at the discretisation level, because a frame time inside a sample gap adds a breakpoint
+ * (DESIGN.md 4.20).  X o Y (X earlier) = (R1 R2, v1[r] + (R1 v2)[r], (p1[r] + v1[r] dt2) + (R1 p2)[r], dt1 + dt2, (R2^T JRg1)[k] + JRg2[k]), n_steps added, flags
+ * OR-ed; a composition with a number that is not finite is the identity with dt (0 when not finite), n_steps, flags kept and VIS_IMU_NONFINITE.
+ * TABLE: T_0[i] = interval i, T_k[i] = T_{k-1}[i - 2^{k-1}] o T_{k-1}[i] for i >= 2^k - 1.  A pair of L = i - q intervals takes the set bits k of L
+ * in rising order from pos = i: the first gives acc = T_k[pos], every later one acc = T_k[pos] o acc, and pos -= 2^k after each.  So a record depends
+ * on its own intervals alone, not on the frame's place in the call, and with the gate off a stream's records are the same bytes however it is cut.
+ * prev[i] == VIS_KF_CARRIED: L = i + 1 (intervals 0 ... i) and, when the carry has VIS_IMU_CARRY_OPEN, record = carry.open o acc.  Without a carry
+ * (NULL, or without VIS_IMU_CARRY_TIME): the identity, dt = 0, VIS_IMU_NO_CARRY.  VIS_KF_NOT_SAVED / VIS_KF_FIRST: the identity, dt = 0, VIS_IMU_NO_PAIR.
+ * q = prev[i] normalised.  CARRY OUT: t_last = t_{n-1}; with `last` the largest i that is not VIS_KF_NOT_SAVED, open = the L = n - 1 - last intervals
+ * last + 1 ... n - 1 (L = 0: the identity, dt = 0, and no VIS_IMU_CARRY_OPEN); when no frame was saved, L = n and open = carry.open o acc where the
+ * carry has VIS_IMU_CARRY_OPEN.  valid = VIS_IMU_CARRY_TIME, with VIS_IMU_CARRY_OPEN when open spans an interval.
+ * d_rot[9 i] = (float)(r_ic^T R r_ic): (r_ic^T R) first, then times r_ic, in double, each entry narrowed once -- "current-frame rays -> previous
+ * frame", RotationResCam.  The identity for a frame flagged VIS_IMU_NO_PAIR, VIS_IMU_NO_CARRY or VIS_IMU_NONFINITE, or when an entry exceeds FLT_MAX.
+ * On the device: k_imu_intervals, one lane per interval, a serial loop over its sub-steps; k_imu_pairs, ONE launch of one workgroup that builds
+ * every level (workgroup barriers between them; levels above the call's longest pair are not built, which no result depends on), composes the
+ * pairs and writes d_delta, d_rot and the carry.  No loop's length depends on the gate's decisions. */
+enum { VIS_IMU_OK = 0, VIS_IMU_NO_PAIR = 1, VIS_IMU_NO_CARRY = 2, VIS_IMU_NO_START = 4, VIS_IMU_EMPTY = 8, VIS_IMU_EXTRAPOLATED = 16, VIS_IMU_GAP = 32,
+       VIS_IMU_FAST = 64, VIS_IMU_ORDER = 128, VIS_IMU_NONFINITE = 256 };
+enum { VIS_IMU_CARRY_TIME = 1, VIS_IMU_CARRY_OPEN = 2 };
+enum { VIS_IMU_MAX_FRAMES = 1024, VIS_IMU_EXP_TERMS = 10 };
+/* (-1)^k / (2k + 1)!, / (2k + 2)!, / (2k + 3)!, k = 0 ... 9, each the double nearest to the quotient */
+#define VIS_IMU_COEF_A { 1.0, -0.16666666666666666, 0.008333333333333333, -0.0001984126984126984, 2.7557319223985893e-06, -2.505210838544172e-08, 1.6059043836821613e-10, -7.647163731819816e-13, 2.8114572543455206e-15, -8.22063524662433e-18 }
+#define VIS_IMU_COEF_B { 0.5, -0.041666666666666664, 0.001388888888888889, -2.48015873015873e-05, 2.755731922398589e-07, -2.08767569878681e-09, 1.1470745597729725e-11, -4.779477332387385e-14, 1.5619206968586225e-16, -4.110317623312165e-19 }
+#define VIS_IMU_COEF_C { 0.16666666666666666, -0.008333333333333333, 0.0001984126984126984, -2.7557319223985893e-06, 2.505210838544172e-08, -1.6059043836821613e-10, 7.647163731819816e-13, -2.8114572543455206e-15, 8.22063524662433e-18, -1.9572941063391263e-20 }
+typedef struct vis_imu_sample { double t, w[3], a[3]; } vis_imu_sample;                                                  /* 56 bytes */
+typedef struct vis_imu_params {          /* 136 bytes; every field finite */
+    double bg[3], ba[3];                 /* 0             the biases subtracted from w and a */
+    double r_ic[9];                      /* identity      the reference's imu2camRotation, row-major */
+    double max_gap_s;                    /* 0.05          a sub-step longer than this flags the interval VIS_IMU_GAP; > 0 */
+    double max_angle;                    /* 1.0           a sub-step turning further (rad) flags it VIS_IMU_FAST; > 0 */
+} vis_imu_params;
+/* R: vectors of the IMU frame at the later time -> the IMU frame at the earlier time (R_q^T R_i); v, p: the preintegrated velocity and position
+ * increments in the earlier frame, gravity NOT subtracted; dt; JRg = d(log R) / d(bg); n_steps = sub-steps taken; q = prev[i] normalised */
+typedef struct vis_imu_delta { double R[9], v[3], p[3], dt, JRg[9]; int32_t n_steps, flags, q, reserved_; } vis_imu_delta;   /* 216 bytes */
+/* t_last: the time of the last frame of the call before; open: the delta from the last SAVED frame to t_last; valid: VIS_IMU_CARRY_* */
+typedef struct vis_imu_carry { double t_last; vis_imu_delta open; int32_t valid, reserved_; } vis_imu_carry;             /* 232 bytes */
+void vis_default_imu_params(vis_imu_params* ip);
+/* ONE interval (t_a, t_b], HOST pointers, blocks once: row 0 of vis_imu_preintegrate_rows for one frame at t_b whose pair is VIS_KF_CARRIED and whose
+ * carry holds t_a alone.  rot (9 floats) may be NULL.
+ * Refusals, in this order.  VIS_E_INVALID: ip NULL or out of range (a field not finite, a bound not > 0), delta NULL, n_samples negative, samples
+ * NULL with n_samples > 0.  VIS_E_STATE without a context. */
+int  vis_imu_preintegrate(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_sample* samples, int n_samples, double t_a, double t_b,
+                          vis_imu_delta* delta, float* rot);
+/* Caller rows, DEVICE pointers, asynchronous on the context's stream.  d_samples: n_samples records; d_tframe, d_prev, d_delta: n entries; d_rot: NULL or
+ * n x 9 floats; d_carry_in: NULL or one record; d_carry_out: NULL or one record (it may not be d_carry_in).  Every entry of d_delta (and d_rot) is
+ * written.  The workspace (208 bytes x frames x levels, levels = the bits of n: 25 doubles and the two integers of a table entry) belongs to the
+ * context and only grows; a call that grows it SYNCHRONISES.
+ * GUIDED MATCHING.  vis_batch_run_guided reads d_rot before the gate of its own run has paired the frames.  With the gate OFF the pairing is known
+ * beforehand -- prev[i] = i - 1, frame 0 VIS_KF_CARRIED (VIS_KF_FIRST for the first launch of a stream) -- so this call with such a d_prev, queued on the
+ * context's stream ahead of vis_batch_run_guided, feeds it with no host step; pass each call's d_carry_out as the next call's d_carry_in (two
+ * records in turn).  With the gate ON a guided run driven by the IMU needs the integration between the gate and the matcher inside the run: out of scope.
+ * Refusals, in this order.  VIS_E_INVALID: ip as above; a NULL d_tframe, d_prev or d_delta; d_samples NULL with n_samples > 0; a pointer that is not
+ * aligned (8 bytes for d_samples, d_tframe, d_carry_in, d_delta, d_carry_out; 4 for d_prev and d_rot); n or n_samples negative; d_carry_out equal to
+ * d_carry_in and not NULL.  VIS_E_STATE without a context.  VIS_E_CAPACITY when n > VIS_IMU_MAX_FRAMES. */
+int  vis_imu_preintegrate_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                               const int32_t* d_prev, const vis_imu_carry* d_carry_in, vis_imu_delta* d_delta, float* d_rot, vis_imu_carry* d_carry_out);
+/* The frames of the last vis_batch_run (with VIS_STAGE_MATCH; n = its frames) with vis_batch_get_keyframes' pairing, on the POSE stream through the
+ * scaffold every follow-up uses: it FORKS from the context's stream, so d_samples and d_tframe may be produced there, and vis_batch_f2f,
+ * vis_batch_filter_keypoints and vis_batch_homography_pose queued after it read its d_rot with no host step.  The plan keeps TWO carry records and
+ * uses them in turn under the rules of the depth row of vis_batch_scale_links: a repeated call reads the record the run was given; vis_batch_plan /
+ * vis_batch_reset forget it; a run that was not integrated makes the next run's carried pairs VIS_IMU_NO_CARRY.  The caller's buffers are in use until
+ * vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: ip as above; a NULL d_tframe or d_delta; d_samples NULL with n_samples > 0; a misaligned pointer (8; d_rot 4);
+ * n or n_samples negative.  VIS_E_STATE: no context / plan / match stage, or n differs.  VIS_E_CAPACITY: n > VIS_IMU_MAX_FRAMES. */
+int  vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                   vis_imu_delta* d_delta, float* d_rot);
+/* The carry the NEXT run's vis_batch_imu continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_trajectory_init.
+ * VIS_E_STATE without a context or plan. */
+int  vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec);
+/* Out of scope: the bias Jacobians of v and p and the 9 x 9 covariance, bias estimation, gravity alignment and a metric scale for
+ * vis_batch_trajectory, the IMU-to-camera lever arm, a guided run with the gate on, and the adapters' IMU arguments (still accepted and ignored). */
 
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */

@@ -52,6 +52,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              batch, default parameters with a forward-backward bound of 1 px; adds VIS_STAGE_GRADIENT): one row per point -- frame index,
              timestamp, point index (the keypoint's place in the previous frame's list), x1, y1, x2, y2, flags (VIS_KLT_*), fb, min_eig, sad,
              iters, levels; the JSON line carries the counts.  The pair to a frame of the batch before has no rows (VIS_KLT_NO_PAIR).
+  --imu imu0/data.csv --imu-out out.csv: preintegrate the IMU between the frames of every pair on the device (vis_batch_imu behind every batch, the
+             plan's own pairing, default parameters; the carry continues across the batches).  The CSV is EuRoC's: timestamp in ns, w (rad/s), a
+             (m/s^2), lines that start with # skipped; frame times come from the image file names; both are taken relative to the first frame's
+             stamp, in seconds.  One row per frame -- frame index, timestamp, flags (VIS_IMU_*), q, n_steps, dt, R (9), v (3), p (3).
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -117,6 +121,8 @@ def main():
     ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
     ap.add_argument("--tracks", default=None, metavar="CSV", help="link the symmetric matches into feature tracks; write every frame's summary and length histogram here")
     ap.add_argument("--trajectory", default=None, metavar="CSV", help="chain the two-view poses under the scale links; write one pose per frame here")
+    ap.add_argument("--imu", default=None, metavar="CSV", help="EuRoC imu0/data.csv: timestamp [ns], w, a")
+    ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -194,6 +200,21 @@ def main():
         d_jobs, d_jframe = z(B * jk * vislam.FTRACK_OBS_DTYPE.itemsize), z(B * vislam.FTRACK_FRAME_DTYPE.itemsize)
         d_jpts, d_jfl, d_jsm = z(B * jk * vislam.FTRACK_POINT_DTYPE.itemsize), z(B * jk), z(B * vislam.FTRACK_TRI_SUMMARY_DTYPE.itemsize)
         traj_rows, traj_totals = [], dict(links_ok=0, roots=0, unit_edges=0, overflow=0, n_view_points=0, n_view_kept=0)
+    if a.imu:
+        if not a.imu_out:
+            raise SystemExit("--imu needs --imu-out")
+        if B > vislam.IMU_MAX_FRAMES:
+            raise SystemExit(f"--imu integrates at most {vislam.IMU_MAX_FRAMES} frames per batch")
+        with open(a.imu) as f:
+            lines = [l.split(",") for l in f if l.strip() and not l.startswith("#")]
+        imu_s = np.zeros(len(lines), vislam.IMU_SAMPLE_DTYPE)
+        for j, l in enumerate(lines):                           # (integer ns less the first frame's stamp: exact in a double, then seconds)
+            imu_s[j]["t"], imu_s[j]["w"], imu_s[j]["a"] = (int(l[0]) - stamps[0]) * 1e-9, [float(v) for v in l[1:4]], [float(v) for v in l[4:7]]
+        up = lambda arr: torch.from_numpy(np.ascontiguousarray(arr).reshape(-1).view(np.uint8).copy()).cuda()
+        d_isamples, d_itf = up(imu_s if len(imu_s) else np.zeros(1, vislam.IMU_SAMPLE_DTYPE)), up(np.asarray([(t - stamps[0]) * 1e-9 for t in stamps], np.float64))
+        d_idelta, d_irot = torch.zeros(B * 216, dtype=torch.uint8, device="cuda"), torch.zeros(B * 36, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        imu_rows, imu_totals = [], dict(paired=0, flagged=0)
     if a.weights != "identity":
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
@@ -291,6 +312,8 @@ def main():
             ctx.batch_ftrack(nb, tcap, d_tobs.data_ptr(), d_tframe.data_ptr())
         if a.klt:
             ctx.batch_klt(d, nb, kcap, d_krec.data_ptr(), d_kpair.data_ptr(), kp=kltp)
+        if a.imu:
+            ctx.batch_imu(nb, d_isamples.data_ptr() if len(imu_s) else 0, len(imu_s), d_itf.data_ptr() + 8 * first, d_idelta.data_ptr(), d_irot.data_ptr())
         if a.trajectory:                                     # run -> triangulate -> scale links -> trajectory -> ftrack -> N-view triangulation: no host step
             ctx.batch_triangulate(nb, jcap, d_jmp.data_ptr(), d_jmf.data_ptr(), d_jms.data_ptr())
             ctx.batch_scale_links(nb, d_jmp.data_ptr(), d_jmf.data_ptr(), jcap, d_jlink.data_ptr())
@@ -360,6 +383,13 @@ def main():
                 traj_totals["n_view_points"] += int(js[i]["n_points"])
                 traj_totals["n_view_kept"] += int(js[i]["n_kept"])
                 traj_rows.append((first + i, stamps[first + i], jt[i].copy(), jl[i].copy()))
+        if a.imu:
+            idl = d_idelta.cpu().numpy().view(vislam.IMU_DELTA_DTYPE)
+            for i in range(nb):
+                fl = int(idl[i]["flags"])
+                imu_totals["paired"] += int(not fl & (vislam.IMU_NO_PAIR | vislam.IMU_NO_CARRY))
+                imu_totals["flagged"] += int(bool(fl & ~(vislam.IMU_NO_PAIR | vislam.IMU_NO_CARRY)))
+                imu_rows.append((first + i, stamps[first + i], idl[i].copy()))
         if a.tracks:
             tobs = d_tobs.cpu().numpy().view(vislam.FTRACK_OBS_DTYPE).reshape(B, tcap)
             tfr = d_tframe.cpu().numpy().view(vislam.FTRACK_FRAME_DTYPE)
@@ -479,6 +509,13 @@ def main():
                 f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + "," + ",".join("%.17g" % v for v in dbl) + "\n")
         out["trajectory_csv"] = a.trajectory
         out["trajectory"] = traj_totals
+    if a.imu:
+        with open(a.imu_out, "w") as f:                         # frame, stamp, flags, q, n_steps, dt, R, v, p
+            for fi, ts, r in imu_rows:
+                dbl = [r["dt"]] + list(r["R"]) + list(r["v"]) + list(r["p"])
+                f.write("%d,%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"], r["n_steps"]) + ",".join("%.17g" % v for v in dbl) + "\n")
+        out["imu_csv"] = a.imu_out
+        out["imu"] = dict(imu_totals, samples=len(imu_s))
     if a.tracks:
         with open(a.tracks, "w") as f:                         # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
             for r in track_rows:

@@ -146,6 +146,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->d_ft_ws) (void)hipFree(ctx->d_ft_ws);
     if (ctx->d_sl_ws) (void)hipFree(ctx->d_sl_ws);
     if (ctx->d_tjr_ws) (void)hipFree(ctx->d_tjr_ws);
+    if (ctx->d_imu_ws) (void)hipFree(ctx->d_imu_ws);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -276,7 +277,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n); F(pl->d_ft_ws); F(pl->d_tj_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1260,6 +1261,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
     ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft_run = -1; ctx->batch->ft_have = false;   // vis_batch_ftrack: no carried row, seq restarts at 0
     ctx->batch->sl_run = ctx->batch->tj_run = -1; ctx->batch->sl_have = ctx->batch->tj_have = false;   // scale links / trajectory: nothing carried
+    ctx->batch->imu_run = -1; ctx->batch->imu_have = false;        // vis_batch_imu: no carried time, no open delta
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
@@ -2214,6 +2216,129 @@ extern "C" int vis_batch_trajectory_init(vis_ctx* ctx, const vis_traj_pose* rec)
     // the record takes the place of what a call for the current run would have left for the next one
     HIPCHK(ctx, hipMemcpy(pl->tj_carry[pl->tj_in ^ 1], rec, sizeof(*rec), hipMemcpyHostToDevice));
     pl->tj_run = pl->run_count;
+    return VIS_OK;
+}
+
+// ---- IMU preintegration: imu.hip
+extern "C" void vis_default_imu_params(vis_imu_params* ip) {
+    if (!ip) return;
+    for (int k = 0; k < 3; k++) ip->bg[k] = ip->ba[k] = 0.0;
+    for (int k = 0; k < 9; k++) ip->r_ic[k] = (k & 3) == 0 ? 1.0 : 0.0;
+    ip->max_gap_s = 0.05; ip->max_angle = 1.0;
+}
+
+static bool imu_params_ok(const vis_imu_params* ip) {
+    if (!ip) return false;
+    for (int k = 0; k < 3; k++) if (!std::isfinite(ip->bg[k]) || !std::isfinite(ip->ba[k])) return false;
+    for (int k = 0; k < 9; k++) if (!std::isfinite(ip->r_ic[k])) return false;
+    return std::isfinite(ip->max_gap_s) && std::isfinite(ip->max_angle) && ip->max_gap_s > 0.0 && ip->max_angle > 0.0;
+}
+
+extern "C" int vis_imu_preintegrate_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                                         const int32_t* d_prev, const vis_imu_carry* d_carry_in, vis_imu_delta* d_delta, float* d_rot,
+                                         vis_imu_carry* d_carry_out) {
+    if (!imu_params_ok(ip) || !d_tframe || !d_prev || !d_delta || (n_samples > 0 && !d_samples)) return VIS_E_INVALID;
+    if (!aligned(d_samples, 8) || !aligned(d_tframe, 8) || !aligned(d_carry_in, 8) || !aligned(d_delta, 8) || !aligned(d_carry_out, 8) || !aligned(d_prev, 4) ||
+        !aligned(d_rot, 4)) return VIS_E_INVALID;
+    if (n < 0 || n_samples < 0 || (d_carry_out && d_carry_out == d_carry_in)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES) { ctx->err = "vis_imu_preintegrate_rows: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const int rc = ensure_rows_block(ctx, ctx->d_imu_ws, ctx->imu_ws_bytes, imu_table_bytes(n), "vis_imu_preintegrate_rows");
+    if (rc) return rc;
+    return imu_launch(ctx, ip, n, FtFrames{d_prev, 0, nullptr}, d_samples, n_samples, d_tframe, d_carry_in, ctx->d_imu_ws, d_delta, d_rot, d_carry_out);
+}
+
+extern "C" int vis_imu_preintegrate(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_sample* samples, int n_samples, double t_a, double t_b,
+                                    vis_imu_delta* delta, float* rot) {
+    if (!imu_params_ok(ip) || !delta || n_samples < 0 || (n_samples > 0 && !samples)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    int rc = ensure_rows_block(ctx, ctx->d_imu_ws, ctx->imu_ws_bytes, imu_table_bytes(1), "vis_imu_preintegrate");
+    if (rc) return rc;
+    vis_imu_sample* d_s; double* d_t; int32_t* d_prev; vis_imu_carry* d_c; vis_imu_delta* d_d; float* d_r;
+    rc = vis_carve(ctx, [&](Carver& cv) {
+        d_s = cv.take<vis_imu_sample>((size_t)std::max(n_samples, 1)); d_t = cv.take<double>(1); d_prev = cv.take<int32_t>(1);
+        d_c = cv.take<vis_imu_carry>(1); d_d = cv.take<vis_imu_delta>(1); d_r = cv.take<float>(9);
+    });
+    if (rc) return rc;
+    vis_imu_carry c;
+    std::memset(&c, 0, sizeof(c));
+    c.t_last = t_a; c.valid = VIS_IMU_CARRY_TIME;
+    const int32_t prev = VIS_KF_CARRIED;
+    HostStage hs(ctx);
+    hs.up(d_s, samples, (size_t)n_samples * sizeof(vis_imu_sample));
+    hs.up(d_t, &t_b, sizeof(t_b));
+    hs.up(d_prev, &prev, sizeof(prev));
+    hs.up(d_c, &c, sizeof(c));
+    hs.flush_ups();
+    rc = imu_launch(ctx, ip, 1, FtFrames{d_prev, 0, nullptr}, d_s, n_samples, d_t, d_c, ctx->d_imu_ws, d_d, d_r, nullptr);
+    if (rc) return vis_drain(ctx, rc);
+    const void* h_d = hs.down(d_d, sizeof(vis_imu_delta));
+    const void* h_r = hs.down(d_r, 9 * sizeof(float));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(delta, h_d, sizeof(vis_imu_delta));
+    if (rot) std::memcpy(rot, h_r, 9 * sizeof(float));
+    return VIS_OK;
+}
+
+// the plan's block: the lifting table for B frames and the two carried records
+static int ensure_imu(vis_ctx* ctx, Plan* pl, void*& table) {
+    const size_t tb = (imu_table_bytes(pl->B) + 255) & ~(size_t)255;
+    if (!pl->d_imu_ws) {
+        if (hipMalloc(&pl->d_imu_ws, tb + 2 * 256) != hipSuccess) {
+            (void)hipGetLastError(); pl->d_imu_ws = nullptr;
+            ctx->err = "vis_batch_imu: out of device memory for the plan's workspace"; return VIS_E_NOMEM;
+        }
+        pl->imu_run = -1; pl->imu_have = false;
+    }
+    static_assert(sizeof(vis_imu_carry) <= 256, "a carried record per 256-byte piece");
+    table = pl->d_imu_ws;
+    pl->imu_carry[0] = (vis_imu_carry*)((char*)pl->d_imu_ws + tb); pl->imu_carry[1] = (vis_imu_carry*)((char*)pl->d_imu_ws + tb + 256);
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                             vis_imu_delta* d_delta, float* d_rot) {
+    if (!imu_params_ok(ip) || !d_tframe || !d_delta || (n_samples > 0 && !d_samples)) return VIS_E_INVALID;
+    if (!aligned(d_samples, 8) || !aligned(d_tframe, 8) || !aligned(d_delta, 8) || !aligned(d_rot, 4) || n < 0 || n_samples < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_imu: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES || n > pl->B) { ctx->err = "vis_batch_imu: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    void* table = nullptr;
+    { const int rc = ensure_imu(ctx, pl, table); if (rc) return rc; }
+    // the record this launch continues: the one the launch before wrote, or -- the call repeated for the same run -- the one it read itself
+    const bool again = pl->imu_run == pl->run_count;
+    const bool have = again ? pl->imu_have : (pl->imu_run >= 0 && pl->imu_run == pl->run_count - 1);
+    const int in = again ? pl->imu_in : (pl->imu_in ^ 1);
+    // on the pose stream behind the matcher of the run (the gate's link table) and behind the context's stream (the caller's samples and times)
+    const int rc = batch_epi(ctx, n, "vis_batch_imu", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = imu_launch(ctx, ip, n, plan_frames(pl_), d_samples, n_samples, d_tframe, have ? pl_->imu_carry[in] : nullptr, table, d_delta, d_rot,
+                                   pl_->imu_carry[in ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->imu_in = in; pl->imu_have = have; pl->imu_run = pl->run_count;
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                 // (a kernel in flight reads and writes the records)
+    Plan* pl = ctx->batch;
+    void* table = nullptr;
+    { const int rc = ensure_imu(ctx, pl, table); if (rc) return rc; }
+    if (!rec) { pl->imu_run = -1; pl->imu_have = false; return VIS_OK; }
+    // the record takes the place of what a call for the current run would have left for the next one
+    HIPCHK(ctx, hipMemcpy(pl->imu_carry[pl->imu_in ^ 1], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->imu_run = pl->run_count;
     return VIS_OK;
 }
 

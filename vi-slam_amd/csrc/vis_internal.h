@@ -123,6 +123,10 @@ struct Plan {
     // sl_* / tj_*: the turn, the run_count of the last call and whether it had something to read, with the meaning of ft_in / ft_run / ft_have
     void* d_tj_ws = nullptr; double* sl_depth = nullptr; double* sl_carry[2] = {nullptr, nullptr}; vis_traj_pose* tj_carry[2] = {nullptr, nullptr};
     int sl_in = 0, sl_run = -1, tj_in = 0, tj_run = -1; bool sl_have = false, tj_have = false;
+    // vis_batch_imu (imu.hip), allocated by the first call or by vis_batch_imu_init (ensure_imu): the lifting table for B frames and the two carried
+    // records; imu_in / imu_run / imu_have with the meaning of ft_in / ft_run / ft_have
+    void* d_imu_ws = nullptr; vis_imu_carry* imu_carry[2] = {nullptr, nullptr};
+    int imu_in = 0, imu_run = -1; bool imu_have = false;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -222,6 +226,8 @@ struct vis_ctx {
     void* d_ft_ws = nullptr; size_t ft_ws_bytes = 0;
     // grow-only workspaces of vis_scale_link_rows (SlWork) and vis_trajectory_rows (TjWork): two blocks, so neither call can move the other's
     void* d_sl_ws = nullptr; size_t sl_ws_bytes = 0; void* d_tjr_ws = nullptr; size_t tjr_ws_bytes = 0;
+    // grow-only workspace of vis_imu_preintegrate_rows and vis_imu_preintegrate (the lifting table, imu_ws_bytes)
+    void* d_imu_ws = nullptr; size_t imu_ws_bytes = 0;
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)
@@ -582,6 +588,11 @@ int scale_link_run(vis_ctx* ctx, const vis_scale_link_params* sp, int n, FtFrame
 // k_tj_chain on ctx->stream: one launch.  d_carry: one record or null; d_poses, d_carry_out: null or the outputs
 int trajectory_run(vis_ctx* ctx, int n, FtFrames fr, const PoseOut* d_pose, const vis_scale_link* d_link, const vis_traj_pose* d_carry, int seq0,
                    int same_epoch_only, double* d_wsD, int32_t* d_wsI, vis_traj_pose* d_traj, double* d_poses, vis_traj_pose* d_carry_out);
+// imu.hip.  The lifting table of n frames: 26 eight-byte slots x frames x levels, levels = the bits of n (imu_table_bytes).  k_imu_intervals +
+// k_imu_pairs on ctx->stream; ip validated by the caller; d_carry, d_rot, d_carry_out: null or the record / rows
+size_t imu_table_bytes(int n);
+int imu_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+            const vis_imu_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, float* d_rot, vis_imu_carry* d_carry_out);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

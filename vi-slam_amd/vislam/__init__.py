@@ -335,6 +335,38 @@ TJ_ROOT, TJ_NO_POSE, TJ_NO_CARRY, TJ_NOT_SAVED, TJ_UNIT_EDGE, TJ_OVERFLOW = 1, 2
 TJ_MAX_FRAMES = 1024
 
 
+class ImuParams(C.Structure):
+    """vis_imu_params: biases, the IMU-to-camera rotation (row-major) and the two flagging bounds (vis_default_imu_params: 0, identity, 0.05 s, 1 rad)"""
+    _fields_ = [("bg", C.c_double * 3), ("ba", C.c_double * 3), ("r_ic", C.c_double * 9), ("max_gap_s", C.c_double), ("max_angle", C.c_double)]
+
+
+class ImuSample(C.Structure):
+    """vis_imu_sample: t (s), w (rad/s), a (m/s^2)"""
+    _fields_ = [("t", C.c_double), ("w", C.c_double * 3), ("a", C.c_double * 3)]
+
+
+class ImuDelta(C.Structure):
+    """vis_imu_delta as a host structure (vis_imu_preintegrate)"""
+    _fields_ = [("R", C.c_double * 9), ("v", C.c_double * 3), ("p", C.c_double * 3), ("dt", C.c_double), ("JRg", C.c_double * 9),
+                ("n_steps", C.c_int32), ("flags", C.c_int32), ("q", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class ImuCarry(C.Structure):
+    """vis_imu_carry as a host structure (vis_batch_imu_init)"""
+    _fields_ = [("t_last", C.c_double), ("open", ImuDelta), ("valid", C.c_int32), ("reserved_", C.c_int32)]
+
+
+IMU_SAMPLE_DTYPE = np.dtype([("t", "<f8"), ("w", "<f8", (3,)), ("a", "<f8", (3,))])
+IMU_DELTA_DTYPE = np.dtype([("R", "<f8", (9,)), ("v", "<f8", (3,)), ("p", "<f8", (3,)), ("dt", "<f8"), ("JRg", "<f8", (9,)), ("n_steps", "<i4"),
+                            ("flags", "<i4"), ("q", "<i4"), ("reserved_", "<i4")])
+IMU_CARRY_DTYPE = np.dtype([("t_last", "<f8"), ("open", IMU_DELTA_DTYPE), ("valid", "<i4"), ("reserved_", "<i4")])
+assert IMU_SAMPLE_DTYPE.itemsize == 56 == C.sizeof(ImuSample) and IMU_DELTA_DTYPE.itemsize == 216 == C.sizeof(ImuDelta)
+assert IMU_CARRY_DTYPE.itemsize == 232 == C.sizeof(ImuCarry) and C.sizeof(ImuParams) == 136
+IMU_OK, IMU_NO_PAIR, IMU_NO_CARRY, IMU_NO_START, IMU_EMPTY, IMU_EXTRAPOLATED, IMU_GAP, IMU_FAST, IMU_ORDER, IMU_NONFINITE = 0, 1, 2, 4, 8, 16, 32, 64, 128, 256
+IMU_CARRY_TIME, IMU_CARRY_OPEN = 1, 2
+IMU_MAX_FRAMES = 1024
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -387,6 +419,7 @@ ABI_SYMBOLS = [
     "vis_ftrack_link_rows", "vis_batch_ftrack", "vis_default_ftrack_tri_params", "vis_ftrack_triangulate_rows", "vis_batch_ftrack_triangulate",
     "vis_default_scale_link_params", "vis_scale_link_rows", "vis_batch_scale_links", "vis_trajectory_rows", "vis_batch_trajectory",
     "vis_batch_trajectory_init",
+    "vis_default_imu_params", "vis_imu_preintegrate", "vis_imu_preintegrate_rows", "vis_batch_imu", "vis_batch_imu_init",
 ]
 
 
@@ -490,6 +523,14 @@ def _load():
         lib.vis_trajectory_rows.argtypes = [vp, ci, vp, vp, vp, vp, ci, ci, vp, vp]
         lib.vis_batch_trajectory.argtypes = [vp, ci, vp, ci, vp, vp]
         lib.vis_batch_trajectory_init.argtypes = [vp, C.POINTER(TrajPose)]
+    if hasattr(lib, "vis_batch_imu"):                   # (absent from older A/B builds)
+        imp = C.POINTER(ImuParams)
+        lib.vis_default_imu_params.argtypes = [imp]
+        lib.vis_default_imu_params.restype = None
+        lib.vis_imu_preintegrate.argtypes = [vp, imp, vp, ci, C.c_double, C.c_double, C.POINTER(ImuDelta), vp]
+        lib.vis_imu_preintegrate_rows.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_imu.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp]
+        lib.vis_batch_imu_init.argtypes = [vp, C.POINTER(ImuCarry)]
     if hasattr(lib, "vis_essential_refine_batch"):      # (absent from older A/B builds)
         epp = C.POINTER(EssentialRefineParams)
         lib.vis_default_eref_params.argtypes = [epp]
@@ -643,6 +684,12 @@ def default_pnp_params():
     pp = PnpParams()
     lib.vis_default_pnp_params(C.byref(pp))
     return pp
+
+
+def default_imu_params():
+    ip = ImuParams()
+    lib.vis_default_imu_params(C.byref(ip))
+    return ip
 
 
 def default_scale_link_params():
@@ -1476,6 +1523,38 @@ class Context:
         if rec is not None and not isinstance(rec, TrajPose):
             rec = TrajPose.from_buffer_copy(np.asarray(rec, TRAJ_POSE_DTYPE).tobytes())
         self._chk(lib.vis_batch_trajectory_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_trajectory_init")
+
+    # -- IMU preintegration: the rotation and the motion deltas of every pair ------------------------------------------
+    def imu_preintegrate(self, samples, t_a, t_b, ip=None):
+        """one interval (t_a, t_b] of host samples (IMU_SAMPLE_DTYPE): (an IMU_DELTA_DTYPE record, the 3 x 3 float32 camera-frame rotation); blocks"""
+        ip = default_imu_params() if ip is None else ip
+        s = np.ascontiguousarray(samples, IMU_SAMPLE_DTYPE)
+        d, rot = ImuDelta(), np.zeros(9, np.float32)
+        self._chk(lib.vis_imu_preintegrate(self._h, C.byref(ip), C.c_void_p(s.ctypes.data) if len(s) else None, len(s), t_a, t_b, C.byref(d),
+                                           C.c_void_p(rot.ctypes.data)), "vis_imu_preintegrate")
+        return np.frombuffer(bytes(d), IMU_DELTA_DTYPE)[0], rot.reshape(3, 3)
+
+    def imu_preintegrate_rows(self, n, d_samples_ptr, n_samples, d_tframe_ptr, d_prev_ptr, d_delta_ptr, d_rot_ptr=0, d_carry_in_ptr=0, d_carry_out_ptr=0,
+                              ip=None):
+        """queue the pair deltas of n frames of caller rows on the context's stream (raw DEVICE pointers; 0 / None = NULL): n IMU_DELTA_DTYPE records,
+        n x 9 float32 rotations for batch_f2f / batch_filter_keypoints / batch_run_guided, and the IMU_CARRY_DTYPE record of the next call"""
+        ip = default_imu_params() if ip is None else ip
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_imu_preintegrate_rows(self._h, C.byref(ip), n, v(d_samples_ptr), n_samples, v(d_tframe_ptr), v(d_prev_ptr), v(d_carry_in_ptr),
+                                                v(d_delta_ptr), v(d_rot_ptr), v(d_carry_out_ptr)), "vis_imu_preintegrate_rows")
+
+    def batch_imu(self, n, d_samples_ptr, n_samples, d_tframe_ptr, d_delta_ptr, d_rot_ptr=0, ip=None):
+        """the same for the frames of the last batch_run with batch_get_keyframes' pairing, on the pose stream; the plan carries the open delta and
+        the last frame time to the next launch.  The buffers are in use until batch_sync()"""
+        ip = default_imu_params() if ip is None else ip
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_imu(self._h, C.byref(ip), n, v(d_samples_ptr), n_samples, v(d_tframe_ptr), v(d_delta_ptr), v(d_rot_ptr)), "vis_batch_imu")
+
+    def batch_imu_init(self, rec=None):
+        """the carry (an IMU_CARRY_DTYPE element or an ImuCarry; None: none) the next run's batch_imu continues from; synchronises"""
+        if rec is not None and not isinstance(rec, ImuCarry):
+            rec = ImuCarry.from_buffer_copy(np.asarray(rec, IMU_CARRY_DTYPE).tobytes())
+        self._chk(lib.vis_batch_imu_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_imu_init")
 
     # -- the essential-matrix pose on device rows, and its refinement ----------------------------------------------
     def essential_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr):
