@@ -35,8 +35,10 @@ def _filled(torch, nbytes):
     return t
 
 
-def link_on_device(vislam, c, prev, nkp, links, nlinks, row_cap, mask=None, carry=None, seq0=0):
-    """(obs (n, row_cap), frames (n)) of one vis_ftrack_link_rows; the guard entries behind both outputs checked"""
+def prepare_link(vislam, prev, nkp, links, nlinks, row_cap, mask=None, carry=None, seq0=0):
+    """the inputs of one vis_ftrack_link_rows uploaded and its outputs filled (both synchronise the device); the answer is call(c), which queues the
+    call on context c and synchronises nothing.  call(c) answers collect() -> (obs (n, row_cap), frames (n)), for after a synchronise: it checks the
+    guard entries behind both outputs"""
     import torch
     n, link_cap = len(prev), links.shape[1]
     keep = [_dev(torch, np.asarray(a)) for a in (np.asarray(prev, np.int32), np.asarray(nkp, np.int32), links.reshape(-1).view(np.uint8) if links.size else np.zeros(16, np.uint8),
@@ -44,12 +46,24 @@ def link_on_device(vislam, c, prev, nkp, links, nlinks, row_cap, mask=None, carr
     d_mask = _dev(torch, mask) if mask is not None else None
     d_carry = _dev(torch, carry.view(np.uint8)) if carry is not None else None
     obs, frames = _filled(torch, (n * row_cap + 3) * 16), _filled(torch, (n + 2) * 32)
-    c.ftrack_link_rows(n, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), link_cap, row_cap, obs.data_ptr(), frames.data_ptr(),
-                       seq0, d_mask.data_ptr() if mask is not None else 0, mask.shape[1] if mask is not None else 0, d_carry.data_ptr() if carry is not None else 0)
+
+    def collect():
+        ro, rf = obs.cpu().numpy(), frames.cpu().numpy()
+        assert (ro[n * row_cap * 16:] == FILL).all() and (rf[n * 32:] == FILL).all()
+        return ro[:n * row_cap * 16].view(vislam.FTRACK_OBS_DTYPE).reshape(n, row_cap), rf[:n * 32].view(vislam.FTRACK_FRAME_DTYPE)
+
+    def call(c):
+        c.ftrack_link_rows(n, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), keep[3].data_ptr(), link_cap, row_cap, obs.data_ptr(), frames.data_ptr(),
+                           seq0, d_mask.data_ptr() if mask is not None else 0, mask.shape[1] if mask is not None else 0, d_carry.data_ptr() if carry is not None else 0)
+        return collect
+    return call
+
+
+def link_on_device(vislam, c, *rows, **kw):
+    """(obs (n, row_cap), frames (n)) of one vis_ftrack_link_rows; the guard entries behind both outputs checked"""
+    collect = prepare_link(vislam, *rows, **kw)(c)
     c.batch_sync()
-    ro, rf = obs.cpu().numpy(), frames.cpu().numpy()
-    assert (ro[n * row_cap * 16:] == FILL).all() and (rf[n * 32:] == FILL).all()
-    return ro[:n * row_cap * 16].view(vislam.FTRACK_OBS_DTYPE).reshape(n, row_cap), rf[:n * 32].view(vislam.FTRACK_FRAME_DTYPE)
+    return collect()
 
 
 def check_link(vislam, c, prev, nkp, links, nlinks, row_cap, mask=None, carry=None, seq0=0, where=None):

@@ -35,19 +35,33 @@ def _payload(t, nbytes):
     return h[GUARD:GUARD + nbytes]
 
 
-def rows_on_device(vislam, c, P, samples, tframe, prev, carry=None, want_rot=True, want_carry=True):
-    """(d_delta, d_rot (n, 9), d_carry_out) of one vis_imu_preintegrate_rows, the guards around all three checked"""
+def prepare_rows(vislam, P, samples, tframe, prev, carry=None, want_rot=True, want_carry=True):
+    """the inputs of one vis_imu_preintegrate_rows uploaded and its outputs filled (both synchronise the device); the answer is call(c), which queues
+    the call on context c and synchronises nothing.  call(c) answers collect() -> (d_delta, d_rot (n, 9), d_carry_out), for after a synchronise: it
+    checks the guards around all three"""
     import torch
     n = len(tframe)
     keep = [_dev(torch, np.asarray(samples, ir.SAMPLE_DTYPE)), _dev(torch, np.asarray(tframe, np.float64)), _dev(torch, np.asarray(prev, np.int32))]
     d_carry = _dev(torch, np.asarray(carry, ir.CARRY_DTYPE).reshape(1)) if carry is not None else None
     delta, rot, cout = _guarded(torch, n * 216), _guarded(torch, n * 36), _guarded(torch, 232)
-    c.imu_preintegrate_rows(n, keep[0].data_ptr() if len(samples) else 0, len(samples), keep[1].data_ptr(), keep[2].data_ptr(), delta.data_ptr() + GUARD,
-                            rot.data_ptr() + GUARD if want_rot else 0, d_carry.data_ptr() if carry is not None else 0,
-                            cout.data_ptr() + GUARD if want_carry else 0, ip=ic.struct_params(vislam, P))
+
+    def collect():
+        return (_payload(delta, n * 216).view(vislam.IMU_DELTA_DTYPE), _payload(rot, n * 36 if want_rot else 0).view(np.float32).reshape(-1, 9),
+                _payload(cout, 232 if want_carry else 0).view(vislam.IMU_CARRY_DTYPE))
+
+    def call(c):
+        c.imu_preintegrate_rows(n, keep[0].data_ptr() if len(samples) else 0, len(samples), keep[1].data_ptr(), keep[2].data_ptr(), delta.data_ptr() + GUARD,
+                                rot.data_ptr() + GUARD if want_rot else 0, d_carry.data_ptr() if carry is not None else 0,
+                                cout.data_ptr() + GUARD if want_carry else 0, ip=ic.struct_params(vislam, P))
+        return collect
+    return call
+
+
+def rows_on_device(vislam, c, P, *rows, **kw):
+    """(d_delta, d_rot (n, 9), d_carry_out) of one vis_imu_preintegrate_rows, the guards around all three checked"""
+    collect = prepare_rows(vislam, P, *rows, **kw)(c)
     c.batch_sync()
-    return (_payload(delta, n * 216).view(vislam.IMU_DELTA_DTYPE), _payload(rot, n * 36 if want_rot else 0).view(np.float32).reshape(-1, 9),
-            _payload(cout, 232 if want_carry else 0).view(vislam.IMU_CARRY_DTYPE))
+    return collect()
 
 
 def check(vislam, c, P, samples, tframe, prev, carry=None, where=None):

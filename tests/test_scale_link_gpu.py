@@ -36,19 +36,33 @@ def c_params(vislam, sp):
     return p
 
 
-def links_on_device(vislam, c, sp, prev, links, nlinks, pose, points, flags, row_cap, carry=None):
-    """(depth (n, row_cap), link (n)) of one vis_scale_link_rows; the guard bytes behind both outputs checked"""
+def prepare_links(vislam, sp, prev, links, nlinks, pose, points, flags, row_cap, carry=None):
+    """the inputs of one vis_scale_link_rows uploaded and its outputs filled (both synchronise the device); the answer is call(c), which queues the
+    call on context c and synchronises nothing.  call(c) answers collect() -> (depth (n, row_cap), link (n)), for after a synchronise: it checks the
+    guard bytes behind both outputs"""
     import torch
     n = len(prev)
     keep = [_dev(torch, a) for a in (np.asarray(prev, np.int32), links, np.asarray(nlinks, np.int32), pose, points, flags)]
     d_carry = _dev(torch, np.asarray(carry, np.float64)) if carry is not None else None
     depth, link = _filled(torch, (n * row_cap + 3) * 8), _filled(torch, (n + 2) * 40)
-    c.scale_link_rows(n, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), links.shape[1], keep[3].data_ptr(), keep[4].data_ptr(), keep[5].data_ptr(),
-                      points.shape[1], row_cap, depth.data_ptr(), link.data_ptr(), d_carry.data_ptr() if carry is not None else 0, c_params(vislam, sp))
+
+    def collect():
+        rd, rl = depth.cpu().numpy(), link.cpu().numpy()
+        assert (rd[n * row_cap * 8:] == FILL).all() and (rl[n * 40:] == FILL).all()
+        return rd[:n * row_cap * 8].view(np.float64).reshape(n, row_cap), rl[:n * 40].view(vislam.SCALE_LINK_DTYPE)
+
+    def call(c):
+        c.scale_link_rows(n, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), links.shape[1], keep[3].data_ptr(), keep[4].data_ptr(), keep[5].data_ptr(),
+                          points.shape[1], row_cap, depth.data_ptr(), link.data_ptr(), d_carry.data_ptr() if carry is not None else 0, c_params(vislam, sp))
+        return collect
+    return call
+
+
+def links_on_device(vislam, c, sp, *rows):
+    """(depth (n, row_cap), link (n)) of one vis_scale_link_rows; the guard bytes behind both outputs checked"""
+    collect = prepare_links(vislam, sp, *rows)(c)
     c.batch_sync()
-    rd, rl = depth.cpu().numpy(), link.cpu().numpy()
-    assert (rd[n * row_cap * 8:] == FILL).all() and (rl[n * 40:] == FILL).all()
-    return rd[:n * row_cap * 8].view(np.float64).reshape(n, row_cap), rl[:n * 40].view(vislam.SCALE_LINK_DTYPE)
+    return collect()
 
 
 def check(vislam, c, sp, case, row_cap, carry=None, where=None):

@@ -28,19 +28,33 @@ def _filled(torch, nbytes):
     return t
 
 
-def chain_on_device(vislam, c, prev, pose, link, carry=None, seq0=0, same_epoch_only=True, dense=True):
-    """(records (n), d_poses (n, 12) or None) of one vis_trajectory_rows; the guard bytes behind both outputs checked"""
+def prepare_chain(vislam, prev, pose, link, carry=None, seq0=0, same_epoch_only=True, dense=True):
+    """the inputs of one vis_trajectory_rows uploaded and its outputs filled (both synchronise the device); the answer is call(c), which queues the
+    call on context c and synchronises nothing.  call(c) answers collect() -> (records (n), d_poses (n, 12) or None), for after a synchronise: it
+    checks the guard bytes behind both outputs"""
     import torch
     n = len(prev)
     keep = [_dev(torch, a) for a in (np.asarray(prev, np.int32), pose, link)]
     d_carry = _dev(torch, np.asarray(carry, tj.TRAJ_DTYPE).reshape(1)) if carry is not None else None
     rec, poses = _filled(torch, (n + 2) * 128), _filled(torch, (n * 12 + 5) * 8)
-    c.trajectory_rows(n, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), rec.data_ptr(), poses.data_ptr() if dense else 0,
-                      d_carry.data_ptr() if carry is not None else 0, seq0, same_epoch_only)
+
+    def collect():
+        rr, rp = rec.cpu().numpy(), poses.cpu().numpy()
+        assert (rr[n * 128:] == FILL).all() and (rp[n * 96 if dense else 0:] == FILL).all()
+        return rr[:n * 128].view(vislam.TRAJ_POSE_DTYPE), rp[:n * 96].view(np.float64).reshape(n, 12) if dense else None
+
+    def call(c):
+        c.trajectory_rows(n, keep[0].data_ptr(), keep[1].data_ptr(), keep[2].data_ptr(), rec.data_ptr(), poses.data_ptr() if dense else 0,
+                          d_carry.data_ptr() if carry is not None else 0, seq0, same_epoch_only)
+        return collect
+    return call
+
+
+def chain_on_device(vislam, c, *rows, **kw):
+    """(records (n), d_poses (n, 12) or None) of one vis_trajectory_rows; the guard bytes behind both outputs checked"""
+    collect = prepare_chain(vislam, *rows, **kw)(c)
     c.batch_sync()
-    rr, rp = rec.cpu().numpy(), poses.cpu().numpy()
-    assert (rr[n * 128:] == FILL).all() and (rp[n * 96 if dense else 0:] == FILL).all()
-    return rr[:n * 128].view(vislam.TRAJ_POSE_DTYPE), rp[:n * 96].view(np.float64).reshape(n, 12) if dense else None
+    return collect()
 
 
 def check(vislam, c, prev, pose, link, carry=None, seq0=0, same_epoch_only=True, where=None):

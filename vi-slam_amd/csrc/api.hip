@@ -142,11 +142,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
     plan_destroy(ctx->single); plan_destroy(ctx->batch);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    if (ctx->d_ess_ws) (void)hipFree(ctx->d_ess_ws);
-    if (ctx->d_ft_ws) (void)hipFree(ctx->d_ft_ws);
-    if (ctx->d_sl_ws) (void)hipFree(ctx->d_sl_ws);
-    if (ctx->d_tjr_ws) (void)hipFree(ctx->d_tjr_ws);
-    if (ctx->d_imu_ws) (void)hipFree(ctx->d_imu_ws);
+    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws}) if (b->p) (void)hipFree(b->p);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -277,7 +273,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_tab); F(pl->d_pnp_X); F(pl->d_pnp_xy); F(pl->d_pnp_n); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -458,6 +454,21 @@ int vis_ensure_scratch(vis_ctx* ctx, size_t bytes) {
     ctx->d_scratch = nullptr; ctx->scratch_bytes = 0;
     HIPCHK(ctx, hipMalloc(&ctx->d_scratch, bytes));
     ctx->scratch_bytes = bytes;
+    return VIS_OK;
+}
+// the grow rule of the device-rows workspaces (vis_internal.h)
+int vis_grow_block(vis_ctx* ctx, DevBlock& b, size_t bytes, const char* who, bool* replaced) {
+    if (replaced) *replaced = false;
+    if (bytes <= b.bytes) return VIS_OK;
+    sync_all(ctx);                                                 // work queued on any stream may still use the old block
+    if (b.p) (void)hipFree(b.p);
+    b = DevBlock{};
+    if (hipMalloc(&b.p, bytes) != hipSuccess) {
+        (void)hipGetLastError(); b.p = nullptr;
+        ctx->err = std::string(who) + ": out of device memory for the workspace"; return VIS_E_NOMEM;
+    }
+    b.bytes = bytes;
+    if (replaced) *replaced = true;
     return VIS_OK;
 }
 
@@ -1259,9 +1270,9 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     sync_all(ctx);
     ctx->batch->have_prev = false; ctx->batch->last_n = 0; ctx->batch->pyr_frames = 0; ctx->batch->carry_from = 0; ctx->batch->pair0_valid = false;
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
-    ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft_run = -1; ctx->batch->ft_have = false;   // vis_batch_ftrack: no carried row, seq restarts at 0
-    ctx->batch->sl_run = ctx->batch->tj_run = -1; ctx->batch->sl_have = ctx->batch->tj_have = false;   // scale links / trajectory: nothing carried
-    ctx->batch->imu_run = -1; ctx->batch->imu_have = false;        // vis_batch_imu: no carried time, no open delta
+    ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft.forget();   // vis_batch_ftrack: no carried row, seq restarts at 0
+    ctx->batch->sl.forget(); ctx->batch->tj.forget();              // scale links / trajectory: nothing carried
+    ctx->batch->imu.forget();                                      // vis_batch_imu: no carried time, no open delta
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
@@ -1857,19 +1868,31 @@ extern "C" int vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     return pnp_batch_run(ctx, pp, n, max_pts, d_X, x_stride, d_xy, d_npts, d_draws, row_cap, d_mask, d_out);
 }
 
-static int ensure_pnp(vis_ctx* ctx, Plan* pl) {
-    if (pl->d_pnp_tab && pl->d_pnp_X && pl->d_pnp_xy && pl->d_pnp_n) return VIS_OK;
-    auto drop = [&]() {                                            // all four or none: a failed call leaves nothing behind for the next one to overwrite
-        (void)hipFree(pl->d_pnp_tab); (void)hipFree(pl->d_pnp_X); (void)hipFree(pl->d_pnp_xy); (void)hipFree(pl->d_pnp_n);
-        pl->d_pnp_tab = nullptr; pl->d_pnp_X = nullptr; pl->d_pnp_xy = nullptr; pl->d_pnp_n = nullptr;
-    };
-    drop();
-    const bool ok = hipMalloc((void**)&pl->d_pnp_tab, (size_t)pl->npairs * pl->kcap * sizeof(int32_t)) == hipSuccess &&
-                    hipMalloc((void**)&pl->d_pnp_X, (size_t)pl->npairs * pl->pose_mcap * 3 * sizeof(double)) == hipSuccess &&
-                    hipMalloc((void**)&pl->d_pnp_xy, (size_t)pl->npairs * pl->pose_mcap * 2 * sizeof(float)) == hipSuccess &&
-                    hipMalloc((void**)&pl->d_pnp_n, (size_t)pl->npairs * sizeof(int32_t)) == hipSuccess;
-    if (!ok) { drop(); (void)hipGetLastError(); ctx->err = "vis_batch_pnp: out of device memory for the plan's workspace"; return VIS_E_NOMEM; }
+// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws), in ONE place: the list is measured and the block allocated by the
+// first call of the plan that needs it; every call binds the list to the block, into a work struct of its own.  The block is never replaced.
+template <class Layout> static int plan_block(vis_ctx* ctx, void*& block, const char* who, Layout&& layout) {
+    if (!block) {
+        Carver measure{nullptr, 0, SIZE_MAX};
+        layout(measure);
+        if (measure.overflow) { ctx->err = std::string(who) + ": the plan's workspace exceeds the address space"; return VIS_E_NOMEM; }
+        if (hipMalloc(&block, measure.off + 256) != hipSuccess) {
+            (void)hipGetLastError(); block = nullptr;
+            ctx->err = std::string(who) + ": out of device memory for the plan's workspace"; return VIS_E_NOMEM;
+        }
+    }
+    Carver cv{(char*)block, 0, SIZE_MAX};
+    layout(cv);
     return VIS_OK;
+}
+
+struct PnpPlanWork { int32_t* tab; double* X; float* xy; int32_t* n; };
+static int ensure_pnp(vis_ctx* ctx, Plan* pl, PnpPlanWork& W) {
+    return plan_block(ctx, pl->d_pnp_ws, "vis_batch_pnp", [&](Carver& cv) {
+        W.tab = cv.take<int32_t>((size_t)pl->npairs * pl->kcap);
+        W.X = cv.take<double>((size_t)pl->npairs * pl->pose_mcap * 3);
+        W.xy = cv.take<float>((size_t)pl->npairs * pl->pose_mcap * 2);
+        W.n = cv.take<int32_t>((size_t)pl->npairs);
+    });
 }
 
 extern "C" int vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, const int32_t* d_draws, const vis_map_point* d_points,
@@ -1882,38 +1905,22 @@ extern "C" int vis_batch_pnp(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     if (ctx && ctx->batch && d_mask && mask_cap < ctx->batch->pose_mcap) { ctx->err = "vis_batch_pnp: mask_cap is smaller than the plan's correspondences per pair"; return VIS_E_CAPACITY; }
     if (!ctx || !ctx->batch) return VIS_E_STATE;
     if (!(ctx->batch->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_pnp: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
-    {
-        Plan* pl = ctx->batch;
-        if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;    // (before the workspace is allocated)
-        (void)hipSetDevice(ctx->device);
-        const int rc = ensure_pnp(ctx, pl);
-        if (rc) return rc;
-    }
+    if (ctx->batch->last_n < 1 || n != ctx->batch->last_n) return VIS_E_STATE;    // (before the workspace is allocated)
+    (void)hipSetDevice(ctx->device);
+    PnpPlanWork W;
+    { const int rc = ensure_pnp(ctx, ctx->batch, W); if (rc) return rc; }
     // on the pose stream (batch_epi queues there) behind the pose stage that wrote the pose records and behind vis_batch_triangulate of the same
     // run, which wrote d_points / d_flags on that stream; the link table is read there too: the next gate kernel of the record set waits for it
     return batch_epi(ctx, n, "vis_batch_pnp", [&](Plan* pl, Plan::MatchOut& O, const int32_t* d_npts) {
         const bool sym = ctx->p.pose_input == VIS_POSE_SYM;
         return pnp_link_run(ctx, pp, n, pl->kf_min ? pl->last_set().kf_link : nullptr, pl->pair0_valid ? 1 : 0, pl->pose_mcap, sym ? pl->kcap : pl->root * pl->root,
-                            pl->kcap, sym ? O.sym : O.good, d_npts, O.p2, pl->d_pose, d_points, d_flags, row_cap, require, pl->d_pnp_tab, pl->d_pnp_X,
-                            pl->d_pnp_xy, pl->d_pnp_n, d_draws, mask_cap, d_mask, d_out, d_link);
+                            pl->kcap, sym ? O.sym : O.good, d_npts, O.p2, pl->d_pose, d_points, d_flags, row_cap, require, W.tab, W.X,
+                            W.xy, W.n, d_draws, mask_cap, d_mask, d_out, d_link);
     }, true);
 }
 
 // ---- feature tracks: ftrack.hip
 static bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-static int ensure_ftrack_rows_workspace(vis_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->ft_ws_bytes) return VIS_OK;
-    sync_all(ctx);                                                 // work queued on any stream may still use the old block
-    if (ctx->d_ft_ws) (void)hipFree(ctx->d_ft_ws);
-    ctx->d_ft_ws = nullptr; ctx->ft_ws_bytes = 0;
-    if (hipMalloc(&ctx->d_ft_ws, bytes) != hipSuccess) {
-        (void)hipGetLastError(); ctx->d_ft_ws = nullptr;
-        ctx->err = "vis_ftrack_link_rows: out of device memory for the workspace"; return VIS_E_NOMEM;
-    }
-    ctx->ft_ws_bytes = bytes;
-    return VIS_OK;
-}
 
 extern "C" int vis_ftrack_link_rows(vis_ctx* ctx, int n, const int32_t* d_prev, const int32_t* d_nkp, const vis_dmatch* d_links, const int32_t* d_nlinks,
                                     int link_cap, const uint8_t* d_mask, int mask_cap, const vis_ftrack_obs* d_carry_in, int seq0, int row_cap,
@@ -1927,38 +1934,19 @@ extern "C" int vis_ftrack_link_rows(vis_ctx* ctx, int n, const int32_t* d_prev, 
     if (n == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
     FtWork W;
-    Carver measure{nullptr, 0, SIZE_MAX};
-    W.layout(measure, (size_t)n, (size_t)row_cap);
-    int rc = ensure_ftrack_rows_workspace(ctx, std::max(measure.off, (size_t)256));
+    const int rc = vis_carve_block(ctx, ctx->ft_ws, "vis_ftrack_link_rows", [&](Carver& cv) { W.layout(cv, (size_t)n, (size_t)row_cap); }, 256);
     if (rc) return rc;
-    Carver cv{(char*)ctx->d_ft_ws, 0, ctx->ft_ws_bytes};
-    W.layout(cv, (size_t)n, (size_t)row_cap);
-    if (cv.overflow) { ctx->err = "vis_ftrack_link_rows: workspace too small (internal)"; return VIS_E_NOMEM; }
     return ftrack_link_run(ctx, W, n, row_cap, FtFrames{d_prev, 0, d_nkp}, d_links, d_nlinks, link_cap, d_mask, mask_cap, nullptr, 0, d_carry_in, seq0,
                            row_cap, row_cap, d_obs, d_frame, nullptr);
 }
 
 // the plan's workspace: FtWork for B frames of kcap keypoints and, behind it, the two carried rows -- one list, measured and then bound
-static void ftrack_plan_layout(Carver& cv, Plan* pl, FtWork& W, vis_ftrack_obs* carry[2]) {
-    W.layout(cv, (size_t)pl->B, (size_t)pl->kcap);
-    carry[0] = cv.take<vis_ftrack_obs>((size_t)pl->kcap); carry[1] = cv.take<vis_ftrack_obs>((size_t)pl->kcap);
-}
-static int ensure_ftrack(vis_ctx* ctx, Plan* pl, FtWork& W) {
-    vis_ftrack_obs* carry[2];
-    if (!pl->d_ft_ws) {
-        Carver measure{nullptr, 0, SIZE_MAX};
-        ftrack_plan_layout(measure, pl, W, carry);
-        if (measure.overflow) return VIS_E_NOMEM;
-        if (hipMalloc(&pl->d_ft_ws, measure.off + 256) != hipSuccess) {
-            (void)hipGetLastError(); pl->d_ft_ws = nullptr;
-            ctx->err = "vis_batch_ftrack: out of device memory for the plan's workspace"; return VIS_E_NOMEM;
-        }
-        pl->ft_run = -1; pl->ft_have = false;
-    }
-    Carver cv{(char*)pl->d_ft_ws, 0, SIZE_MAX};
-    ftrack_plan_layout(cv, pl, W, carry);
-    pl->ft_carry[0] = carry[0]; pl->ft_carry[1] = carry[1];
-    return VIS_OK;
+struct FtPlanWork { FtWork ft; vis_ftrack_obs* carry[2]; };
+static int ensure_ftrack(vis_ctx* ctx, Plan* pl, FtPlanWork& W) {
+    return plan_block(ctx, pl->d_ft_ws, "vis_batch_ftrack", [&](Carver& cv) {
+        W.ft.layout(cv, (size_t)pl->B, (size_t)pl->kcap);
+        W.carry[0] = cv.take<vis_ftrack_obs>((size_t)pl->kcap); W.carry[1] = cv.take<vis_ftrack_obs>((size_t)pl->kcap);
+    });
 }
 
 // the pairing of the last run as the kernels read it: the gate's link table, or the gate-off rule; the counts of its frames
@@ -1984,12 +1972,9 @@ extern "C" int vis_batch_ftrack(vis_ctx* ctx, int source, int pose_inliers, int 
         ctx->err = "vis_batch_ftrack: pose_inliers needs VIS_STAGE_POSE and the list the pose stage saw"; return VIS_E_INVALID;
     }
     (void)hipSetDevice(ctx->device);
-    FtWork W;
+    FtPlanWork W;
     { const int rc = ensure_ftrack(ctx, pl, W); if (rc) return rc; }
-    // the row this launch continues: the one the launch before wrote, or -- the call repeated for the same run -- the one it read itself
-    const bool again = pl->ft_run == pl->run_count;
-    const bool have = again ? pl->ft_have : (pl->ft_run >= 0 && pl->ft_run == pl->run_count - 1);
-    const int in = again ? pl->ft_in : (pl->ft_in ^ 1);
+    const Turn::Pick row = pl->ft.pick(pl->run_count);
     Plan::MatchOut& O = pl->out();
     // On the pose stream behind the matcher of the run (the lists and counts of its matcher-output set, the keypoint counts of its record set, the
     // gate's link table) and, with a caller's mask, behind the context's stream; the pose stage's mask and records are written on the pose stream
@@ -1997,15 +1982,15 @@ extern "C" int vis_batch_ftrack(vis_ctx* ctx, int source, int pose_inliers, int 
     const int rc = on_pose_stream(ctx, {(unsigned)(FU_MATCHER | (d_mask ? FU_FORK : 0)), ctx->ev_epi_done[pl->mo_cur]}, [&] {
         const bool sym = source == VIS_FT_SYM;
         static_assert(sizeof(PoseOut) % 4 == 0 && offsetof(PoseOut, n_points) % 4 == 0, "the pose record's n_points as a strided int32");
-        const int rc2 = ftrack_link_run(ctx, W, n, pl->kcap, plan_frames(pl), sym ? O.sym : O.good, sym ? O.nsym : O.ngood, sym ? pl->kcap : pl->root * pl->root,
+        const int rc2 = ftrack_link_run(ctx, W.ft, n, pl->kcap, plan_frames(pl), sym ? O.sym : O.good, sym ? O.nsym : O.ngood, sym ? pl->kcap : pl->root * pl->root,
                                         pose_inliers ? pl->d_mask : d_mask, pose_inliers ? pl->pose_mcap : mask_cap,
                                         pose_inliers ? (const int32_t*)((const char*)pl->d_pose + offsetof(PoseOut, n_points)) : nullptr, (int)(sizeof(PoseOut) / 4),
-                                        have ? pl->ft_carry[in] : nullptr, pl->seq0, row_cap, pl->kcap, d_obs, d_frame, pl->ft_carry[in ^ 1]);
+                                        row.have ? W.carry[row.slot] : nullptr, pl->seq0, row_cap, pl->kcap, d_obs, d_frame, W.carry[row.slot ^ 1]);
         if (!rc2) ctx->pose_pending = true;
         return rc2;
     }, {&O.readers, &pl->last_set().matcher, pl->kf_min ? &pl->last_set().links : nullptr});
     if (rc) return rc;
-    pl->ft_in = in; pl->ft_have = have; pl->ft_run = pl->run_count;
+    pl->ft.commit(row, pl->run_count);
     return VIS_OK;
 }
 
@@ -2054,19 +2039,6 @@ extern "C" int vis_batch_ftrack_triangulate(vis_ctx* ctx, const vis_ftrack_tri_p
 }
 
 // ---- scale links and the chained trajectory: trajectory.hip
-static int ensure_rows_block(vis_ctx* ctx, void*& block, size_t& have, size_t bytes, const char* who) {
-    if (bytes <= have) return VIS_OK;
-    sync_all(ctx);                                                 // work queued on any stream may still use the old block
-    if (block) (void)hipFree(block);
-    block = nullptr; have = 0;
-    if (hipMalloc(&block, bytes) != hipSuccess) {
-        (void)hipGetLastError(); block = nullptr;
-        ctx->err = std::string(who) + ": out of device memory for the workspace"; return VIS_E_NOMEM;
-    }
-    have = bytes;
-    return VIS_OK;
-}
-
 extern "C" void vis_default_scale_link_params(vis_scale_link_params* sp) {
     if (!sp) return;
     sp->require = VIS_MP_KEPT; sp->min_shared = 8; sp->max_rel_spread = 1.0; sp->min_scale = 1.0 / 64.0; sp->max_scale = 64.0;
@@ -2095,13 +2067,8 @@ extern "C" int vis_scale_link_rows(vis_ctx* ctx, const vis_scale_link_params* sp
     (void)hipSetDevice(ctx->device);
     const int mcap = std::min(link_cap, pts_cap);
     SlWork W;
-    Carver measure{nullptr, 0, SIZE_MAX};
-    W.layout(measure, (size_t)n, (size_t)mcap);
-    const int rc = ensure_rows_block(ctx, ctx->d_sl_ws, ctx->sl_ws_bytes, measure.off, "vis_scale_link_rows");
+    const int rc = vis_carve_block(ctx, ctx->sl_ws, "vis_scale_link_rows", [&](Carver& cv) { W.layout(cv, (size_t)n, (size_t)mcap); });
     if (rc) return rc;
-    Carver cv{(char*)ctx->d_sl_ws, 0, ctx->sl_ws_bytes};
-    W.layout(cv, (size_t)n, (size_t)mcap);
-    if (cv.overflow) { ctx->err = "vis_scale_link_rows: workspace too small (internal)"; return VIS_E_NOMEM; }
     return scale_link_run(ctx, sp, n, FtFrames{d_prev, 0, nullptr}, d_links, d_nlinks, link_cap, mcap, d_pose, d_points, d_flags, pts_cap, d_depth_carry_in,
                           row_cap, d_depth, W.keys, d_link, nullptr);
 }
@@ -2116,40 +2083,21 @@ extern "C" int vis_trajectory_rows(vis_ctx* ctx, int n, const int32_t* d_prev, c
     if (n == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
     TjWork W;
-    Carver measure{nullptr, 0, SIZE_MAX};
-    W.layout(measure, (size_t)n);
-    const int rc = ensure_rows_block(ctx, ctx->d_tjr_ws, ctx->tjr_ws_bytes, measure.off, "vis_trajectory_rows");
+    const int rc = vis_carve_block(ctx, ctx->tjr_ws, "vis_trajectory_rows", [&](Carver& cv) { W.layout(cv, (size_t)n); });
     if (rc) return rc;
-    Carver cv{(char*)ctx->d_tjr_ws, 0, ctx->tjr_ws_bytes};
-    W.layout(cv, (size_t)n);
-    if (cv.overflow) { ctx->err = "vis_trajectory_rows: workspace too small (internal)"; return VIS_E_NOMEM; }
     return trajectory_run(ctx, n, FtFrames{d_prev, 0, nullptr}, d_pose, d_link, d_carry_in, seq0, same_epoch_only, W.D, W.I, d_traj, d_poses, nullptr);
 }
 
 // the plan's block: one list, measured and then bound
 struct TrajPlanWork { double* depth; double* sl_carry[2]; SlWork sl; TjWork tj; vis_traj_pose* tj_carry[2]; };
-static void traj_plan_layout(Carver& cv, Plan* pl, TrajPlanWork& W) {
-    W.depth = cv.take<double>((size_t)pl->B * pl->kcap);
-    W.sl_carry[0] = cv.take<double>((size_t)pl->kcap); W.sl_carry[1] = cv.take<double>((size_t)pl->kcap);
-    W.sl.layout(cv, (size_t)pl->B, (size_t)pl->pose_mcap);
-    W.tj.layout(cv, (size_t)pl->B);
-    W.tj_carry[0] = cv.take<vis_traj_pose>(1); W.tj_carry[1] = cv.take<vis_traj_pose>(1);
-}
 static int ensure_traj(vis_ctx* ctx, Plan* pl, TrajPlanWork& W) {
-    if (!pl->d_tj_ws) {
-        Carver measure{nullptr, 0, SIZE_MAX};
-        traj_plan_layout(measure, pl, W);
-        if (measure.overflow) return VIS_E_NOMEM;
-        if (hipMalloc(&pl->d_tj_ws, measure.off + 256) != hipSuccess) {
-            (void)hipGetLastError(); pl->d_tj_ws = nullptr;
-            ctx->err = "vis_batch_scale_links / vis_batch_trajectory: out of device memory for the plan's workspace"; return VIS_E_NOMEM;
-        }
-        pl->sl_run = pl->tj_run = -1; pl->sl_have = pl->tj_have = false;
-    }
-    Carver cv{(char*)pl->d_tj_ws, 0, SIZE_MAX};
-    traj_plan_layout(cv, pl, W);
-    pl->sl_depth = W.depth; pl->sl_carry[0] = W.sl_carry[0]; pl->sl_carry[1] = W.sl_carry[1]; pl->tj_carry[0] = W.tj_carry[0]; pl->tj_carry[1] = W.tj_carry[1];
-    return VIS_OK;
+    return plan_block(ctx, pl->d_tj_ws, "vis_batch_scale_links / vis_batch_trajectory", [&](Carver& cv) {
+        W.depth = cv.take<double>((size_t)pl->B * pl->kcap);
+        W.sl_carry[0] = cv.take<double>((size_t)pl->kcap); W.sl_carry[1] = cv.take<double>((size_t)pl->kcap);
+        W.sl.layout(cv, (size_t)pl->B, (size_t)pl->pose_mcap);
+        W.tj.layout(cv, (size_t)pl->B);
+        W.tj_carry[0] = cv.take<vis_traj_pose>(1); W.tj_carry[1] = cv.take<vis_traj_pose>(1);
+    });
 }
 
 extern "C" int vis_batch_scale_links(vis_ctx* ctx, const vis_scale_link_params* sp, int n, const vis_map_point* d_points, const uint8_t* d_flags,
@@ -2163,20 +2111,17 @@ extern "C" int vis_batch_scale_links(vis_ctx* ctx, const vis_scale_link_params* 
     (void)hipSetDevice(ctx->device);
     TrajPlanWork W;
     { const int rc = ensure_traj(ctx, pl, W); if (rc) return rc; }
-    // the row this launch continues: the one the launch before wrote, or -- the call repeated for the same run -- the one it read itself
-    const bool again = pl->sl_run == pl->run_count;
-    const bool have = again ? pl->sl_have : (pl->sl_run >= 0 && pl->sl_run == pl->run_count - 1);
-    const int in = again ? pl->sl_in : (pl->sl_in ^ 1);
+    const Turn::Pick row = pl->sl.pick(pl->run_count);
     // on the pose stream behind the pose stage and vis_batch_triangulate of the run, like vis_batch_pnp; the link table is read there too
     const int rc = batch_epi(ctx, n, "vis_batch_scale_links", [&](Plan* pl_, Plan::MatchOut& O, const int32_t* d_npts) {
         const bool sym = ctx->p.pose_input == VIS_POSE_SYM;
         const int rc2 = scale_link_run(ctx, sp, n, plan_frames(pl_), sym ? O.sym : O.good, d_npts, sym ? pl_->kcap : pl_->root * pl_->root, pl_->pose_mcap, pl_->d_pose,
-                                       d_points, d_flags, row_cap, have ? pl_->sl_carry[in] : nullptr, pl_->kcap, pl_->sl_depth, W.sl.keys, d_link, pl_->sl_carry[in ^ 1]);
+                                       d_points, d_flags, row_cap, row.have ? W.sl_carry[row.slot] : nullptr, pl_->kcap, W.depth, W.sl.keys, d_link, W.sl_carry[row.slot ^ 1]);
         if (!rc2) ctx->pose_pending = true;
         return rc2;
     }, true);
     if (rc) return rc;
-    pl->sl_in = in; pl->sl_have = have; pl->sl_run = pl->run_count;
+    pl->sl.commit(row, pl->run_count);
     return VIS_OK;
 }
 
@@ -2190,18 +2135,16 @@ extern "C" int vis_batch_trajectory(vis_ctx* ctx, int n, const vis_scale_link* d
     (void)hipSetDevice(ctx->device);
     TrajPlanWork W;
     { const int rc = ensure_traj(ctx, pl, W); if (rc) return rc; }
-    const bool again = pl->tj_run == pl->run_count;
-    const bool have = again ? pl->tj_have : (pl->tj_run >= 0 && pl->tj_run == pl->run_count - 1);
-    const int in = again ? pl->tj_in : (pl->tj_in ^ 1);
+    const Turn::Pick rec = pl->tj.pick(pl->run_count);
     // on the pose stream behind vis_batch_scale_links of the run, which wrote d_link there, and behind the pose stage
     const int rc = batch_epi(ctx, n, "vis_batch_trajectory", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
-        const int rc2 = trajectory_run(ctx, n, plan_frames(pl_), pl_->d_pose, d_link, have ? pl_->tj_carry[in] : nullptr, pl_->seq0, same_epoch_only, W.tj.D, W.tj.I,
-                                       d_traj, d_poses, pl_->tj_carry[in ^ 1]);
+        const int rc2 = trajectory_run(ctx, n, plan_frames(pl_), pl_->d_pose, d_link, rec.have ? W.tj_carry[rec.slot] : nullptr, pl_->seq0, same_epoch_only, W.tj.D, W.tj.I,
+                                       d_traj, d_poses, W.tj_carry[rec.slot ^ 1]);
         if (!rc2) ctx->pose_pending = true;
         return rc2;
     }, true);
     if (rc) return rc;
-    pl->tj_in = in; pl->tj_have = have; pl->tj_run = pl->run_count;
+    pl->tj.commit(rec, pl->run_count);
     return VIS_OK;
 }
 
@@ -2212,10 +2155,9 @@ extern "C" int vis_batch_trajectory_init(vis_ctx* ctx, const vis_traj_pose* rec)
     Plan* pl = ctx->batch;
     TrajPlanWork W;
     { const int rc = ensure_traj(ctx, pl, W); if (rc) return rc; }
-    if (!rec) { pl->tj_run = -1; pl->tj_have = false; return VIS_OK; }
-    // the record takes the place of what a call for the current run would have left for the next one
-    HIPCHK(ctx, hipMemcpy(pl->tj_carry[pl->tj_in ^ 1], rec, sizeof(*rec), hipMemcpyHostToDevice));
-    pl->tj_run = pl->run_count;
+    if (!rec) { pl->tj.forget(); return VIS_OK; }
+    HIPCHK(ctx, hipMemcpy(W.tj_carry[pl->tj.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->tj.seeded(pl->run_count);
     return VIS_OK;
 }
 
@@ -2245,9 +2187,9 @@ extern "C" int vis_imu_preintegrate_rows(vis_ctx* ctx, const vis_imu_params* ip,
     if (n > VIS_IMU_MAX_FRAMES) { ctx->err = "vis_imu_preintegrate_rows: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
     if (n == 0) return VIS_OK;
     (void)hipSetDevice(ctx->device);
-    const int rc = ensure_rows_block(ctx, ctx->d_imu_ws, ctx->imu_ws_bytes, imu_table_bytes(n), "vis_imu_preintegrate_rows");
+    const int rc = vis_grow_block(ctx, ctx->imu_ws, imu_table_bytes(n), "vis_imu_preintegrate_rows");
     if (rc) return rc;
-    return imu_launch(ctx, ip, n, FtFrames{d_prev, 0, nullptr}, d_samples, n_samples, d_tframe, d_carry_in, ctx->d_imu_ws, d_delta, d_rot, d_carry_out);
+    return imu_launch(ctx, ip, n, FtFrames{d_prev, 0, nullptr}, d_samples, n_samples, d_tframe, d_carry_in, ctx->imu_ws.p, d_delta, d_rot, d_carry_out);
 }
 
 extern "C" int vis_imu_preintegrate(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_sample* samples, int n_samples, double t_a, double t_b,
@@ -2255,7 +2197,7 @@ extern "C" int vis_imu_preintegrate(vis_ctx* ctx, const vis_imu_params* ip, cons
     if (!imu_params_ok(ip) || !delta || n_samples < 0 || (n_samples > 0 && !samples)) return VIS_E_INVALID;
     if (!ctx) return VIS_E_STATE;
     (void)hipSetDevice(ctx->device);
-    int rc = ensure_rows_block(ctx, ctx->d_imu_ws, ctx->imu_ws_bytes, imu_table_bytes(1), "vis_imu_preintegrate");
+    int rc = vis_grow_block(ctx, ctx->imu_ws, imu_table_bytes(1), "vis_imu_preintegrate");
     if (rc) return rc;
     vis_imu_sample* d_s; double* d_t; int32_t* d_prev; vis_imu_carry* d_c; vis_imu_delta* d_d; float* d_r;
     rc = vis_carve(ctx, [&](Carver& cv) {
@@ -2273,7 +2215,7 @@ extern "C" int vis_imu_preintegrate(vis_ctx* ctx, const vis_imu_params* ip, cons
     hs.up(d_prev, &prev, sizeof(prev));
     hs.up(d_c, &c, sizeof(c));
     hs.flush_ups();
-    rc = imu_launch(ctx, ip, 1, FtFrames{d_prev, 0, nullptr}, d_s, n_samples, d_t, d_c, ctx->d_imu_ws, d_d, d_r, nullptr);
+    rc = imu_launch(ctx, ip, 1, FtFrames{d_prev, 0, nullptr}, d_s, n_samples, d_t, d_c, ctx->imu_ws.p, d_d, d_r, nullptr);
     if (rc) return vis_drain(ctx, rc);
     const void* h_d = hs.down(d_d, sizeof(vis_imu_delta));
     const void* h_r = hs.down(d_r, 9 * sizeof(float));
@@ -2285,19 +2227,11 @@ extern "C" int vis_imu_preintegrate(vis_ctx* ctx, const vis_imu_params* ip, cons
 }
 
 // the plan's block: the lifting table for B frames and the two carried records
-static int ensure_imu(vis_ctx* ctx, Plan* pl, void*& table) {
-    const size_t tb = (imu_table_bytes(pl->B) + 255) & ~(size_t)255;
-    if (!pl->d_imu_ws) {
-        if (hipMalloc(&pl->d_imu_ws, tb + 2 * 256) != hipSuccess) {
-            (void)hipGetLastError(); pl->d_imu_ws = nullptr;
-            ctx->err = "vis_batch_imu: out of device memory for the plan's workspace"; return VIS_E_NOMEM;
-        }
-        pl->imu_run = -1; pl->imu_have = false;
-    }
-    static_assert(sizeof(vis_imu_carry) <= 256, "a carried record per 256-byte piece");
-    table = pl->d_imu_ws;
-    pl->imu_carry[0] = (vis_imu_carry*)((char*)pl->d_imu_ws + tb); pl->imu_carry[1] = (vis_imu_carry*)((char*)pl->d_imu_ws + tb + 256);
-    return VIS_OK;
+struct ImuPlanWork { void* table; vis_imu_carry* carry[2]; };
+static int ensure_imu(vis_ctx* ctx, Plan* pl, ImuPlanWork& W) {
+    return plan_block(ctx, pl->d_imu_ws, "vis_batch_imu", [&](Carver& cv) {
+        W.table = cv.take<char>(imu_table_bytes(pl->B)); W.carry[0] = cv.take<vis_imu_carry>(1); W.carry[1] = cv.take<vis_imu_carry>(1);
+    });
 }
 
 extern "C" int vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
@@ -2310,21 +2244,18 @@ extern "C" int vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, cons
     if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
     if (n > VIS_IMU_MAX_FRAMES || n > pl->B) { ctx->err = "vis_batch_imu: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
     (void)hipSetDevice(ctx->device);
-    void* table = nullptr;
-    { const int rc = ensure_imu(ctx, pl, table); if (rc) return rc; }
-    // the record this launch continues: the one the launch before wrote, or -- the call repeated for the same run -- the one it read itself
-    const bool again = pl->imu_run == pl->run_count;
-    const bool have = again ? pl->imu_have : (pl->imu_run >= 0 && pl->imu_run == pl->run_count - 1);
-    const int in = again ? pl->imu_in : (pl->imu_in ^ 1);
+    ImuPlanWork W;
+    { const int rc = ensure_imu(ctx, pl, W); if (rc) return rc; }
+    const Turn::Pick rec = pl->imu.pick(pl->run_count);
     // on the pose stream behind the matcher of the run (the gate's link table) and behind the context's stream (the caller's samples and times)
     const int rc = batch_epi(ctx, n, "vis_batch_imu", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
-        const int rc2 = imu_launch(ctx, ip, n, plan_frames(pl_), d_samples, n_samples, d_tframe, have ? pl_->imu_carry[in] : nullptr, table, d_delta, d_rot,
-                                   pl_->imu_carry[in ^ 1]);
+        const int rc2 = imu_launch(ctx, ip, n, plan_frames(pl_), d_samples, n_samples, d_tframe, rec.have ? W.carry[rec.slot] : nullptr, W.table, d_delta, d_rot,
+                                   W.carry[rec.slot ^ 1]);
         if (!rc2) ctx->pose_pending = true;
         return rc2;
     }, true);
     if (rc) return rc;
-    pl->imu_in = in; pl->imu_have = have; pl->imu_run = pl->run_count;
+    pl->imu.commit(rec, pl->run_count);
     return VIS_OK;
 }
 
@@ -2333,33 +2264,15 @@ extern "C" int vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec) {
     (void)hipSetDevice(ctx->device);
     sync_all(ctx);                                                 // (a kernel in flight reads and writes the records)
     Plan* pl = ctx->batch;
-    void* table = nullptr;
-    { const int rc = ensure_imu(ctx, pl, table); if (rc) return rc; }
-    if (!rec) { pl->imu_run = -1; pl->imu_have = false; return VIS_OK; }
-    // the record takes the place of what a call for the current run would have left for the next one
-    HIPCHK(ctx, hipMemcpy(pl->imu_carry[pl->imu_in ^ 1], rec, sizeof(*rec), hipMemcpyHostToDevice));
-    pl->imu_run = pl->run_count;
+    ImuPlanWork W;
+    { const int rc = ensure_imu(ctx, pl, W); if (rc) return rc; }
+    if (!rec) { pl->imu.forget(); return VIS_OK; }
+    HIPCHK(ctx, hipMemcpy(W.carry[pl->imu.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->imu.seeded(pl->run_count);
     return VIS_OK;
 }
 
 // ---- the pose stage on device rows: pose_run on a workspace of the context's own
-static int ensure_essential_workspace(vis_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->ess_ws_bytes) return VIS_OK;
-    sync_all(ctx);                                                 // work queued on any stream may still use the old block
-    if (ctx->d_ess_ws) (void)hipFree(ctx->d_ess_ws);
-    ctx->d_ess_ws = nullptr; ctx->ess_ws_bytes = 0;
-    if (hipMalloc(&ctx->d_ess_ws, bytes) != hipSuccess) {
-        (void)hipGetLastError(); ctx->d_ess_ws = nullptr;
-        ctx->err = "vis_essential_batch: out of device memory for the workspace"; return VIS_E_NOMEM;
-    }
-    ctx->ess_ws_bytes = bytes;
-    // defence in depth, as plan_fill's: nothing reads these buffers before it writes them, but fresh memory must never hold an index.  On the
-    // context's stream, in front of the kernels the caller queues next: that stream does not wait for the null stream (hipStreamNonBlocking), so a
-    // plain hipMemset could still be clearing the block under them
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_ess_ws, 0, bytes, ctx->stream));
-    return VIS_OK;
-}
-
 extern "C" int vis_essential_batch(vis_ctx* ctx, int n, const float* d_p1, const float* d_p2, const int32_t* d_npts, int max_pts, int row_cap,
                                    uint8_t* d_mask, vis_pose_result* d_out) {
     if (n < 0 || max_pts < 0 || row_cap < 0 || !d_npts || !d_out || (max_pts && (!d_p1 || !d_p2))) return VIS_E_INVALID;
@@ -2375,14 +2288,13 @@ extern "C" int vis_essential_batch(vis_ctx* ctx, int n, const float* d_p1, const
     }
     const int iters = ctx->p.ransac_max_iters, mcap = max_pts;
     PoseWork W;
-    Carver measure{nullptr, 0, SIZE_MAX};
-    W.layout(measure, (size_t)n, (size_t)mcap, (size_t)iters);
-    if (measure.overflow) return VIS_E_NOMEM;
-    int rc = ensure_essential_workspace(ctx, measure.off);
+    bool fresh = false;
+    int rc = vis_carve_block(ctx, ctx->ess_ws, "vis_essential_batch", [&](Carver& cv) { W.layout(cv, (size_t)n, (size_t)mcap, (size_t)iters); }, 0, &fresh);
     if (rc) return rc;
-    Carver cv{(char*)ctx->d_ess_ws, 0, ctx->ess_ws_bytes};
-    W.layout(cv, (size_t)n, (size_t)mcap, (size_t)iters);
-    if (cv.overflow) { ctx->err = "vis_essential_batch: workspace too small (internal)"; return VIS_E_NOMEM; }
+    // defence in depth, as plan_fill's: nothing reads these buffers before it writes them, but fresh memory must never hold an index.  On the
+    // context's stream, in front of the kernels the caller queues next: that stream does not wait for the null stream (hipStreamNonBlocking), so a
+    // plain hipMemset could still be clearing the block under them
+    if (fresh) HIPCHK(ctx, hipMemsetAsync(ctx->ess_ws.p, 0, ctx->ess_ws.bytes, ctx->stream));
     rc = vis_build_sample_table(ctx, VIS_POSE_TABLE_M);            // (already there since vis_set_params: the single calls' table, the same sample stream)
     if (rc) return rc;
     rc = pose_run(ctx, n, mcap, iters, d_p1, d_p2, d_npts, W.n1, W.n2, W.samples, W.models, W.counts, W.rstate, nullptr, W.mask, d_out, 1, 1,

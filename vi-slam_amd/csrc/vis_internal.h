@@ -56,6 +56,26 @@ struct ReaderGuard {
     void clear() { *this = ReaderGuard(); }
 };
 
+// Which of a plan's TWO carried rows a follow-up launch continues (vis_batch_ftrack, _scale_links, _trajectory, _imu: "the rules of the depth row",
+// include/vislam_hip.h).  A launch reads row `slot` -- the row of the last saved frame of the launch before, beside the carried record of the keyframe
+// gate -- and writes the other one, slot ^ 1: two rows, so that a call never reads the row it writes and a call repeated for the same run reads again
+// the row it read itself.  in = the row the last committed launch read, run = its run_count (-1: none), have = whether it had a row to read.
+// pick() changes nothing; the caller commits once its launch was queued.  A run that was skipped leaves nothing to read.  Bookkeeping only,
+// like ReaderGuard::note (host/stage_selftest.cpp walks the table of cases on the CPU).
+struct Turn {
+    int in = 0, run = -1; bool have = false;
+    struct Pick { int slot; bool have; };
+    Pick pick(int run_count) const { return run == run_count ? Pick{in, have} : Pick{in ^ 1, run >= 0 && run == run_count - 1}; }
+    void commit(Pick p, int run_count) { in = p.slot; have = p.have; run = run_count; }
+    void forget() { run = -1; have = false; }                      // vis_batch_reset, an _init call without a record (`in` stays: either row will do)
+    // an _init call's record takes the place of what a call for the current run would have left for the next one: copy it to seed_slot(), then seeded()
+    int seed_slot() const { return in ^ 1; }
+    void seeded(int run_count) { run = run_count; }
+};
+
+// a grow-only device block of the context (vis_grow_block)
+struct DevBlock { void* p = nullptr; size_t bytes = 0; };
+
 // vis_batch_track's keyframe snapshot: one frame in the layout of a gradient-set frame (vis_grad_frame_elems elements per array),
 // level 0 of gray dense (w x h); valid = the pair to the carried keyframe may read it (set per call, not stored)
 struct TrackSnapshot { uint8_t* gray = nullptr; int16_t* gx = nullptr; int16_t* gy = nullptr; bool valid = false; };
@@ -107,26 +127,21 @@ struct Plan {
     // guided matching (match.hip k_warp): npairs x kcap predictions + 16 floats (the rotation of a single-frame call); allocated by the
     // first guided call of the plan (ensure_warp), so a context that never asks for a window has the footprint it always had
     float2* d_warp = nullptr;
-    // vis_batch_pnp (pnp.hip k_pnp_link), allocated by the first call of the plan (ensure_pnp): per frame the keypoint table of its keyframe's
-    // pair (npairs x kcap), the linked rows (npairs x pose_mcap map points and pixels) and their counts
-    int32_t* d_pnp_tab = nullptr; double* d_pnp_X = nullptr; float* d_pnp_xy = nullptr; int32_t* d_pnp_n = nullptr;
-    // vis_batch_ftrack (ftrack.hip), allocated by the first call of the plan (ensure_ftrack): ONE block carved by FtWork::layout for B frames of
-    // kcap keypoints, and behind it the two carried observation rows (kcap records each) used in turn: a call reads ft_carry[ft_in] -- the row of
-    // the last saved frame of the launch before, beside the carried record of the keyframe gate -- and writes the other one.  seq_next counts the
-    // frames of every detecting vis_batch_run since plan / reset, seq0 = the stream number of frame 0 of the last run; ft_run = the run_count of
-    // the last linked launch (-1: none), ft_have = whether that call had a row to read (a repeated call for the same run reads it again)
-    void* d_ft_ws = nullptr; vis_ftrack_obs* ft_carry[2] = {nullptr, nullptr};
-    int ft_in = 0, ft_run = -1; bool ft_have = false;
+    // The follow-ups' blocks, each allocated ONCE by the first call of the plan that needs it and never replaced (api.hip plan_block: one list per
+    // block, measured for the allocation and bound by every call into a work struct of its own; plan_destroy frees them), and the turns of the
+    // carried rows that four of them hold (Turn).  A plan starts with the turns' defaults and nothing commits before the block exists.
+    // vis_batch_pnp (PnpPlanWork): per frame the keypoint table of its keyframe's pair (npairs x kcap), the linked rows (npairs x pose_mcap map
+    // points and pixels) and their counts
+    void* d_pnp_ws = nullptr;
+    // vis_batch_ftrack (FtPlanWork): FtWork for B frames of kcap keypoints and, behind it, the two carried observation rows (kcap records each).
+    // seq_next counts the frames of every detecting vis_batch_run since plan / reset, seq0 = the stream number of frame 0 of the last run
+    void* d_ft_ws = nullptr; Turn ft;
     int seq_next = 0, seq0 = 0;
-    // vis_batch_scale_links / vis_batch_trajectory (trajectory.hip), allocated by the first call of either (ensure_traj): ONE block -- the depth
-    // rows (B x kcap doubles), the two carried depth rows, SlWork for B pairs of pose_mcap entries, TjWork for B frames, the two carried records.
-    // sl_* / tj_*: the turn, the run_count of the last call and whether it had something to read, with the meaning of ft_in / ft_run / ft_have
-    void* d_tj_ws = nullptr; double* sl_depth = nullptr; double* sl_carry[2] = {nullptr, nullptr}; vis_traj_pose* tj_carry[2] = {nullptr, nullptr};
-    int sl_in = 0, sl_run = -1, tj_in = 0, tj_run = -1; bool sl_have = false, tj_have = false;
-    // vis_batch_imu (imu.hip), allocated by the first call or by vis_batch_imu_init (ensure_imu): the lifting table for B frames and the two carried
-    // records; imu_in / imu_run / imu_have with the meaning of ft_in / ft_run / ft_have
-    void* d_imu_ws = nullptr; vis_imu_carry* imu_carry[2] = {nullptr, nullptr};
-    int imu_in = 0, imu_run = -1; bool imu_have = false;
+    // vis_batch_scale_links / vis_batch_trajectory (TrajPlanWork), allocated by the first call of either: the depth rows (B x kcap doubles), the two
+    // carried depth rows, SlWork for B pairs of pose_mcap entries, TjWork for B frames, the two carried records
+    void* d_tj_ws = nullptr; Turn sl, tj;
+    // vis_batch_imu (ImuPlanWork), allocated by the first call or by vis_batch_imu_init: the lifting table for B frames and the two carried records
+    void* d_imu_ws = nullptr; Turn imu;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -219,15 +234,12 @@ struct vis_ctx {
     bool ev_ok = false;
     // grow-only scratch for the *_host entry points
     void* d_scratch = nullptr; size_t scratch_bytes = 0;
-    // grow-only workspace of vis_essential_batch (api.hip PoseWork: the pose stage's buffers for n rows), apart from the scratch block so that a
-    // host-pointer call between two batches cannot move it
-    void* d_ess_ws = nullptr; size_t ess_ws_bytes = 0;
-    // grow-only workspace of vis_ftrack_link_rows (FtWork for n rows of row_cap), apart from the scratch block for the same reason
-    void* d_ft_ws = nullptr; size_t ft_ws_bytes = 0;
-    // grow-only workspaces of vis_scale_link_rows (SlWork) and vis_trajectory_rows (TjWork): two blocks, so neither call can move the other's
-    void* d_sl_ws = nullptr; size_t sl_ws_bytes = 0; void* d_tjr_ws = nullptr; size_t tjr_ws_bytes = 0;
-    // grow-only workspace of vis_imu_preintegrate_rows and vis_imu_preintegrate (the lifting table, imu_ws_bytes)
-    void* d_imu_ws = nullptr; size_t imu_ws_bytes = 0;
+    // The grow-only workspaces of the device-rows calls, grown by vis_grow_block alone (vis_carve_block where the call carves a list) and freed by
+    // vis_destroy: vis_essential_batch (api.hip PoseWork: the pose stage's buffers for n rows), vis_ftrack_link_rows (FtWork for n rows of
+    // row_cap), vis_scale_link_rows (SlWork), vis_trajectory_rows (TjWork), vis_imu_preintegrate_rows and vis_imu_preintegrate (the lifting
+    // table).  FIVE blocks, apart from the scratch block and from each other: a host-pointer call between two batches, or another of these calls,
+    // cannot move the block a queued call was given
+    DevBlock ess_ws, ft_ws, sl_ws, tjr_ws, imu_ws;
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)
@@ -444,6 +456,23 @@ template <class Layout> int vis_carve(vis_ctx* ctx, Layout&& layout, int ways = 
     Carver cv{(char*)ctx->d_scratch, 0, ctx->scratch_bytes};
     layout(cv);
     if (cv.overflow) { ctx->err = "device scratch block too small (internal)"; return VIS_E_NOMEM; }
+    return VIS_OK;
+}
+// The grow rule of the context's device-rows workspaces, in ONE place (api.hip): a request that fits -- a zero-byte one always does -- changes
+// nothing; otherwise every stream of the context is drained (work queued on any of them may still use the old block), the block is freed and a new
+// one allocated, or the call refused: VIS_E_NOMEM, "<who>: out of device memory for the workspace".  *replaced = the block is a new one.
+// (vis_ensure_scratch is the same rule written apart: it answers a failed allocation with VIS_E_HIP and the runtime's text.)
+int vis_grow_block(vis_ctx* ctx, DevBlock& b, size_t bytes, const char* who, bool* replaced = nullptr);
+// vis_carve's twin for such a block: the list runs measuring, the block grows to that size (at_least: a floor), the list runs bound to the block
+template <class Layout> int vis_carve_block(vis_ctx* ctx, DevBlock& b, const char* who, Layout&& layout, size_t at_least = 0, bool* replaced = nullptr) {
+    Carver measure{nullptr, 0, SIZE_MAX};
+    layout(measure);
+    if (measure.overflow) { ctx->err = std::string(who) + ": the workspace exceeds the address space"; return VIS_E_NOMEM; }
+    const int rc = vis_grow_block(ctx, b, std::max(measure.off, at_least), who, replaced);
+    if (rc) return rc;
+    Carver cv{(char*)b.p, 0, b.bytes};
+    layout(cv);
+    if (cv.overflow) { ctx->err = std::string(who) + ": workspace too small (internal)"; return VIS_E_NOMEM; }
     return VIS_OK;
 }
 // a launch failed behind queued uploads: drain the stream (they read the pinned block, which the next call may refill), then report

@@ -5,6 +5,10 @@
 //      write of caller memory waits for; StreamScope, the alignments' ring and note_readers(): the bookkeeping of on_pose_stream()
 //   4. Carver / the one buffer list of a host-pointer call (vis_carve): the measuring and the binding pass walk the same offsets, a take
 //      beyond the block is refused, and the pinned bound derived from the list holds a stage that passes every buffer up and down
+//   5. vis_carve_block / vis_grow_block (the context's grow-only device-rows workspaces) on host buffers that stand in for blocks: a list fits a
+//      block of exactly its measured size, a block that is large enough is neither touched nor reported as replaced, a list of nothing asks for
+//      nothing.  The growing branch itself (drain, free, allocate) needs a device: tests/test_block_growth_gpu.py drives it
+//   6. Turn (which of a plan's two carried rows a follow-up launch continues): the table of repeated, skipped, forgotten and seeded runs
 // (round 5's host SIGSEGV, gpurun_out/r5r_gdb.log: a stage that kept the address of a block a later vis_ensure_pin had freed; see
 // csrc/vis_internal.h at HostStage).  Compiled by `make -C vi-slam_amd/csrc selftest` with hipcc as host code against the library;
 // tests/test_abi.py runs it.  Prints one line per check and exits non-zero on the first failure.
@@ -129,6 +133,55 @@ int main() {
             CHECK(!hs.overflow && hs.off <= pin.size());
         }
         p.h_pin = nullptr; p.h_pin_bytes = 0;
+        // the same list carved into a grow-only block of the context (vis_carve_block), host buffers standing in for device blocks
+        vis_ctx q;
+        DevBlock exact{dev.data(), measure.off};                              // exactly the measured size: fits, so the grow rule changes nothing
+        bool replaced = true;
+        CHECK(vis_carve_block(&q, exact, "selftest", layout, 0, &replaced) == VIS_OK && !replaced);
+        CHECK(exact.p == dev.data() && exact.bytes == measure.off);           // the measured size is what the bound pass consumes: no overflow
+        CHECK(d[0] == dev.data() && d[1] == dev.data() + 1024 && d[2] == dev.data() + 1280 && d[3] == dev.data() + 1792);
+        std::vector<char> big(3 * measure.off);
+        DevBlock roomy{big.data(), big.size()};                               // larger than the list, and than the list's floor: neither touched nor replaced
+        replaced = true;
+        CHECK(vis_carve_block(&q, roomy, "selftest", layout, 2 * measure.off, &replaced) == VIS_OK && !replaced);
+        CHECK(roomy.p == big.data() && roomy.bytes == big.size() && d[0] == big.data() && d[3] == big.data() + 1792);
+        DevBlock none;                                                        // a list of nothing asks for nothing: no block, no allocation
+        void* z = dev.data();
+        replaced = true;
+        CHECK(vis_carve_block(&q, none, "selftest", [&](Carver& cv) { z = cv.take<char>(0); }, 0, &replaced) == VIS_OK && !replaced);
+        CHECK(none.p == nullptr && none.bytes == 0 && z == nullptr);
+        CHECK(vis_grow_block(&q, none, 0, "selftest", &replaced) == VIS_OK && !replaced && none.p == nullptr);
+        CHECK(vis_grow_block(&q, exact, measure.off, "selftest") == VIS_OK && exact.p == dev.data());
+        CHECK(q.err.empty());
+    }
+    {
+        // the turn of a plan's two carried rows (Turn): the table of cases; a pick is committed unless it says otherwise
+        Turn t;
+        auto is = [](Turn::Pick p, int slot, bool have) { return p.slot == slot && p.have == have; };
+        auto step = [&](int run) { const Turn::Pick p = t.pick(run); t.commit(p, run); return p; };
+        CHECK(t.in == 0 && t.run == -1 && !t.have);
+        CHECK(is(step(0), 1, false));                                         // 1  fresh: nothing to read, the launch writes row 0
+        CHECK(is(step(0), 1, false));                                         // 2  repeated for the same run: the same answer
+        CHECK(is(step(1), 0, true));                                          // 3  the next run reads row 0 and writes row 1
+        CHECK(is(step(1), 0, true));                                          // 4  repeated: reads row 0 again
+        CHECK(is(step(3), 1, false));                                         // 5  run 2 was skipped: nothing to read
+        const Turn before = t;
+        CHECK(is(t.pick(4), 0, true) && t.in == before.in && t.run == before.run && t.have == before.have);   // 6  a pick alone changes nothing
+        t.forget();
+        CHECK(t.in == before.in && is(step(4), 0, false));                    // 7  forgotten: nothing to read; `in` survived
+        CHECK(t.seed_slot() == 1);                                            // 8  a record seeded at run 4 goes where a call for run 4 would have written
+        t.seeded(4);
+        CHECK(!t.have && is(step(5), 1, true));                               //    and run 5 reads it
+        const int seed = t.seed_slot();
+        t.seeded(5); t.forget();
+        CHECK(seed == 0 && is(step(5), 0, false));                            // 9  forgotten after a seed: nothing to read
+        Turn u;                                                               // 10 fresh, seeded at run 0
+        CHECK(u.seed_slot() == 1);
+        u.seeded(0);
+        CHECK(is(u.pick(1), 1, true));                                        //    run 1 reads the seed
+        CHECK(is(u.pick(0), 0, false));                                       //    a call for the seeded run itself writes row 1: it overwrites the seed (pinned as it is)
+        u.commit(u.pick(1), 1);
+        CHECK(is(u.pick(0), 0, false));                                       //    (and so after run 1 was committed)
     }
     std::printf(fails ? "stage_selftest FAILED (%d)\n" : "stage_selftest passed\n", fails);
     return fails ? 1 : 0;
