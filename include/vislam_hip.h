@@ -1545,7 +1545,8 @@ int  vis_batch_trajectory(vis_ctx* ctx, int n, const vis_scale_link* d_link, int
 /* The record the NEXT run's vis_batch_trajectory continues from where a frame's pair is the carried keyframe (rec NULL: none).  HOST pointer;
  * SYNCHRONISES, like vis_batch_track_init.  VIS_E_STATE without a context or plan. */
 int  vis_batch_trajectory_init(vis_ctx* ctx, const vis_traj_pose* rec);
-/* Out of scope: bundle adjustment, loop closure, a metric scale, feeding the trajectory into vis_batch_track or vis_batch_pnp, and a scale between
+/* Out of scope: bundle adjustment, loop closure, feeding the trajectory into vis_batch_track or vis_batch_pnp (the metric scale is
+ * vis_batch_vi_align's, which reads these records and changes none), and a scale between
  * siblings of one root in tree-shaped caller rows (each sibling is its own unit edge; the plan's pairing is a chain and never makes them). */
 
 /* ---- IMU preintegration: the rotation of every pair (the d_rot of vis_batch_f2f, vis_batch_filter_keypoints, vis_batch_run_guided and the hint of
@@ -1648,8 +1649,117 @@ int  vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_
 /* The carry the NEXT run's vis_batch_imu continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_trajectory_init.
  * VIS_E_STATE without a context or plan. */
 int  vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec);
-/* Out of scope: the bias Jacobians of v and p and the 9 x 9 covariance, bias estimation, gravity alignment and a metric scale for
- * vis_batch_trajectory, the IMU-to-camera lever arm, a guided run with the gate on, and the adapters' IMU arguments (still accepted and ignored). */
+/* Out of scope: the bias Jacobians of v and p and the 9 x 9 covariance (so no accelerometer-bias estimate; the gyro bias, gravity, the metric scale
+ * and the lever arm are vis_vi_align_rows / vis_batch_vi_align below), a guided run with the gate on, and the adapters' IMU arguments (still accepted
+ * and ignored). */
+
+/* ---- visual-inertial alignment: the gyro bias, gravity in the root's frame, the factor from trajectory units to metres and a velocity per frame,
+ * from the records of vis_batch_trajectory and vis_batch_imu (after Mur-Artal & Tardos 2017 and Qin et al. 2018, restated from the equations; the
+ * reference has no such step).  tests/vi_align_ref.py restates every operation below and every record equals it byte for byte: double arithmetic,
+ * + - * / sqrt and comparisons only, nothing contracted; products and finite() as in the IMU block; Exp is its ten-term series.
+ * (A^T x)[r] = (A[r] x[0] + A[3 + r] x[1]) + A[6 + r] x[2]; a.b = (a[0] b[0] + a[1] b[1]) + a[2] b[2].
+ * FRAMES.  q_i = prev[i] normalised as for vis_trajectory_rows.  The TAIL of frame i from its trajectory record T (x = R X + t): zero when T.flags has
+ * VIS_TJ_NOT_SAVED or VIS_TJ_OVERFLOW; else C = -(R^T t) (the camera centre), M = r_ic R and Rw[3r + c] = M[3c + r] (IMU -> root, so that
+ * Rw_q^T Rw_i = r_ic (R_q R_i^T) r_ic^T is the delta's R), L = R^T p_ci (the lever term; the metric IMU position is s C + L); zero again when one of
+ * the 15 numbers is not finite; else segment_seq and epoch_seq of T and VIS_VIT_POSED, with VIS_VIT_EDGE when T.flags lacks VIS_TJ_ROOT, T.parent == q_i
+ * and q_i is an index or VIS_KF_CARRIED.  The delta of frame i is USABLE when its flags have none of VIS_IMU_NO_PAIR | NO_CARRY | NO_START | NONFINITE
+ * nor of `reject`, its 25 numbers are finite, dt > 0 and its q equals T.parent.  The PARENT of frame i is frame q_i (its tail, its delta) or, for
+ * VIS_KF_CARRIED, the carry's `last` tail with `last_delta`, usable when that tail has VIS_VIT_DELTA; the GRANDPARENT is the parent's parent, the
+ * carry's `parent` tail when the parent is the carried frame, the carry's `last` when the parent's pair is VIS_KF_CARRIED.  Without a carry those
+ * tails are zero.  (S, E) = segment_seq and epoch_seq of the newest posed frame of the call, the carry's when the call has none, else (-1, -1).
+ * 1. GYRO BIAS.  Frame i is a PAIR when it has an edge, a posed parent b and a usable delta (R, JRg = J): V = Rw_b^T Rw_i, Er = R^T V,
+ * e = (0.5 (Er[7] - Er[5]), 0.5 (Er[2] - Er[6]), 0.5 (Er[3] - Er[1])) (sin(angle) axis: no inverse function); ten terms: (J^T J)[a][b] =
+ * (J[a] J[b] + J[3 + a] J[3 + b]) + J[6 + a] J[6 + b] for a <= b in row order, (J^T e)[a] = (J[a] e0 + J[3 + a] e1) + J[6 + a] e2, e.e; a pair with
+ * a term that is not finite does not count.  Pairs of every segment and epoch count.  With the totals H, b, c0 and n_pairs: n_pairs < min_pairs gives
+ * VIS_VIA_GYRO_FEW; else H dbg = b by LDL^T (below), a failure VIS_VIA_GYRO_SINGULAR; both leave dbg = 0.  c1 = the sum over THIS CALL's pairs of e.e
+ * with R Exp(J dbg) in the place of R (c0_call is the same sum before the step).
+ * 2. SCALE AND GRAVITY.  Frame c is a TRIPLE with parent b and grandparent a when c and b have edges and (segment_seq, epoch_seq) = (S, E), a is
+ * posed (it may be the tail of the epoch's unit edge) and both deltas, b's (a -> b, dt1, dv, dp) and c's (b -> c, dt2, dp'), are usable:
+ *   lam[r] = (C_c[r] - C_b[r]) dt1 - (C_b[r] - C_a[r]) dt2;  beta = -(((0.5 dt1) dt2) (dt1 + dt2));
+ *   gam[r] = (((Rw_b dp')[r] dt1 - (Rw_a dp)[r] dt2) + (Rw_a dv)[r] (dt1 dt2)) - ((L_c[r] - L_b[r]) dt1 - (L_b[r] - L_a[r]) dt2);
+ * with d1[r] = (C_c[r] - C_b[r]) dt1, d2[r] = (C_b[r] - C_a[r]) dt2 and lam[r] = d1[r] - d2[r] (the same roundings): lam s + beta g = gam.  Eleven
+ * terms: lam.lam, lam[0] beta, lam[1] beta, lam[2] beta, beta beta, lam.gam, beta gam[0], beta gam[1], beta gam[2], gam.gam and the EXCITATION
+ * SCALE d1.d1 + d2.d2 (what lam.lam is the small difference of); not all finite: no triple.  The carried `lin` is M = sum A^T A,
+ * A = [lam | beta I], as the rows of its upper triangle (beta beta three times, +0.0 between them), then r = sum A^T gam (4), sum gam.gam and
+ * the summed excitation scale (lin[15]).  n_triples < min_triples: VIS_VIA_FEW.  Else M x = r by LDL^T; a failure, or M[0][0] not >
+ * VIS_VIA_EXCITATION_REL lin[15] -- the baselines' second differences are rounding noise of the baselines, as under a constant velocity, where
+ * M[0][0] stays > 0 by accident -- or a |g_lin| that is not finite is VIS_VIA_SINGULAR, and s_lin, g_lin, g_lin_norm report 0; else s_lin = x[0],
+ * g_lin = x[1 ... 3], g_lin_norm = sqrt(g_lin.g_lin); | g_lin_norm - G | > g_tol G sets VIS_VIA_GRAVITY_NORM (a lack of excitation; not a
+ * failure); s_lin not > 0: VIS_VIA_SCALE.
+ * 3. GRAVITY OF NORM G, from M and r alone.  gh = g_lin / g_lin_norm (each entry), s = s_lin; refine_iters times: k = the first index of the smallest
+ * |gh[k]|; d[j] = (j == k) - gh[k] gh[j], b1 = d / sqrt(d.d), b2 = gh x b1; x0 = G gh; rr[i] = r[i] - ((M[i][1] x0[0] + M[i][2] x0[1]) + M[i][3] x0[2]);
+ * q = (rr[0], b1.rr[1...3], b2.rr[1...3]); w1[i] = M[1 + i][1...3].b1, w2 alike; N = {M[0][0], M[0][1...3].b1, M[0][1...3].b2; ., b1.w1, b1.w2; ., .,
+ * b2.w2}; N y = q by LDL^T; g[j] = (x0[j] + y[1] b1[j]) + y[2] b2[j]; gh = g / sqrt(g.g); s = y[0].  A failed solve or a norm that is not finite and
+ * > 0: VIS_VIA_SINGULAR; s not finite and > 0: VIS_VIA_SCALE.  Reported: s and g = G gh; any of VIS_VIA_FEW | SINGULAR | SCALE reports s = 1, g = 0.
+ * LDL^T without pivoting, vis_essential_refine's: D[j] = A[j][j] - sum_c (L[j][c] L[j][c]) D[c], a D[j] that is not finite and > 0 fails;
+ * L[i][j] = (A[i][j] - sum_c (L[i][c] L[j][c]) D[c]) / D[j]; z[i] = b[i] - sum_c L[i][c] z[c]; x[i] = z[i] / D[i] - sum_{c > i} L[c][i] x[c], c rising,
+ * every sum subtracted term by term; an x that is not finite fails.
+ * 4. STATES under the reported (s, g).  p[r] = s C[r] + L[r] for a posed frame of (S, E) (VIS_VIS_HAS_P); for one that also has an edge, a usable
+ * delta (dt, dv, dp) and a posed parent b of segment S: v[r] = (((p[r] - p_b[r]) / dt + (0.5 g[r]) dt) + (Rw_b z)[r]), z[k] = dv[k] - dp[k] / dt
+ * (VIS_VIS_HAS_V); res = sqrt(rho.rho), rho[r] = (lam[r] s + beta g[r]) - gam[r], for a triple (VIS_VIS_HAS_TRIPLE); VIS_VIS_HAS_PAIR; q = q_i.
+ * Numbers that are not finite stay 0 without their flag; rms = sqrt(sum rho.rho / n_triples_call).
+ * SUMS: the per-frame terms, zero where a frame does not count, under the summation contract "T" of vis_essential_polish with frames in the place of
+ * points; a total is carried + call, one addition per entry, the carried first.  The carried linear sums count only when the carry's (segment_seq,
+ * epoch_seq) is (S, E) (else VIS_VIA_RESTART); the gyro sums always.  Gyro totals that are not all finite become zero sums and a zero count with
+ * VIS_VIA_GYRO_SINGULAR, linear ones with VIS_VIA_SINGULAR; c0_call, c1 and the sum under rms report 0 when they are not finite.
+ * CARRY OUT: the totals, (S, E), the tail of the last SAVED frame (q_i != VIS_KF_NOT_SAVED) with VIS_VIT_DELTA when its delta is usable, that delta
+ * (else a zero record), its parent's tail (flags & VIS_VIT_POSED), valid = VIS_VIC_VALID; a call that saved nothing passes the three through.  A
+ * carry counts when it has VIS_VIC_VALID and its 81 numbers are finite; one that is not finite is ignored with VIS_VIA_BAD_CARRY.  Two cuts of a
+ * stream agree within a bound, not byte for byte.
+ * On the device: k_via_align, ONE launch of one workgroup of 256 threads, each with at most four frames; tails are recomputed from the trajectory
+ * records where they are needed, so there is no workspace; barriers separate the newest-frame search, the sums, the solves (on every thread, the same
+ * bits), the second pass and the records.  No loop's length depends on the gate's decisions. */
+enum { VIS_VIA_OK = 0, VIS_VIA_GYRO_FEW = 1, VIS_VIA_GYRO_SINGULAR = 2, VIS_VIA_FEW = 4, VIS_VIA_SINGULAR = 8, VIS_VIA_SCALE = 16,
+       VIS_VIA_GRAVITY_NORM = 32, VIS_VIA_RESTART = 64, VIS_VIA_BAD_CARRY = 128 };
+enum { VIS_VIS_HAS_P = 1, VIS_VIS_HAS_V = 2, VIS_VIS_HAS_TRIPLE = 4, VIS_VIS_HAS_PAIR = 8 };
+enum { VIS_VIT_POSED = 1, VIS_VIT_EDGE = 2, VIS_VIT_DELTA = 4 };
+enum { VIS_VIC_VALID = 1 };
+enum { VIS_VIA_MAX_FRAMES = 1024 };
+#define VIS_VIA_EXCITATION_REL 9.094947017729282e-13       /* 2^-40: a relative second difference of 1e-6, below any visual baseline's own error */
+typedef struct vis_vi_align_params {     /* 128 bytes; every field finite */
+    double  r_ic[9];                     /* identity      vis_imu_params' r_ic */
+    double  p_ci[3];                     /* 0             the IMU origin in camera coordinates, metres */
+    double  G;                           /* 9.81          the norm of gravity, m/s^2; > 0 */
+    double  g_tol;                       /* 0.1           | |g_lin| - G | above g_tol G sets VIS_VIA_GRAVITY_NORM; >= 0 */
+    int32_t min_pairs, min_triples;      /* 8, 8          >= 1 */
+    int32_t refine_iters;                /* 4             0 ... 16 */
+    int32_t reject;                      /* VIS_IMU_EMPTY | VIS_IMU_GAP   delta flags that make a delta unusable */
+} vis_vi_align_params;
+typedef struct vis_vi_state { double p[3], v[3], res; int32_t flags, q; } vis_vi_state;                                    /* 64 bytes */
+typedef struct vis_vi_align {            /* 160 bytes */
+    double  dbg[3], c0, c0_call, c1, s, g[3], s_lin, g_lin[3], g_lin_norm, rms;
+    int32_t n_pairs, n_triples, n_pairs_call, n_triples_call, segment_seq, epoch_seq, flags, reserved_;
+} vis_vi_align;
+typedef struct vis_vi_tail { double C[3], Rw[9], L[3]; int32_t segment_seq, epoch_seq, flags, reserved_; } vis_vi_tail;    /* 136 bytes */
+typedef struct vis_vi_carry {            /* 720 bytes */
+    double  gyro[10], lin[16];
+    int32_t n_pairs, n_triples, segment_seq, epoch_seq;
+    vis_vi_tail last, parent;
+    vis_imu_delta last_delta;
+    int32_t valid, reserved_;
+} vis_vi_carry;
+void vis_default_vi_align_params(vis_vi_align_params* vp);
+/* Caller rows, DEVICE pointers, asynchronous on the context's stream, no workspace.  d_prev, d_traj, d_delta: n entries; d_state: NULL or n records;
+ * d_result: ONE record; d_carry_in, d_carry_out: NULL or one record each, and not the same one.  n = 0 writes the solution of the carried totals.
+ * Refusals, in this order.  VIS_E_INVALID: vp NULL or out of range; a NULL d_prev, d_traj, d_delta or d_result; a pointer that is not aligned (8
+ * bytes; d_prev 4); n negative; d_carry_out equal to d_carry_in and not NULL.  VIS_E_STATE without a context.  VIS_E_CAPACITY when n > VIS_VIA_MAX_FRAMES. */
+int  vis_vi_align_rows(vis_ctx* ctx, const vis_vi_align_params* vp, int n, const int32_t* d_prev, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
+                       const vis_vi_carry* d_carry_in, vis_vi_state* d_state, vis_vi_align* d_result, vis_vi_carry* d_carry_out);
+/* The frames of the last vis_batch_run (with VIS_STAGE_POSE; n = its frames) with vis_batch_get_keyframes' pairing, on the POSE stream through the
+ * follow-up scaffold, behind vis_batch_trajectory and vis_batch_imu of the run, whose d_traj and d_delta it reads: run -> triangulate -> scale links ->
+ * trajectory -> imu -> alignment queues with no host step.  The plan keeps TWO carry records used in turn under the rules of the depth row of
+ * vis_batch_scale_links (a repeated call reads what the run was given; vis_batch_plan / vis_batch_reset forget it; a run that was not aligned leaves
+ * the next one without a carry).  The caller's buffers are in use until vis_batch_sync.
+ * Refusals, in this order.  VIS_E_INVALID: vp as above; a NULL or misaligned (8) d_traj, d_delta or d_result, a misaligned d_state; n negative.
+ * VIS_E_STATE: no context / plan / pose stage, or n differs.  VIS_E_CAPACITY: n > VIS_VIA_MAX_FRAMES. */
+int  vis_batch_vi_align(vis_ctx* ctx, const vis_vi_align_params* vp, int n, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
+                        vis_vi_state* d_state, vis_vi_align* d_result);
+/* The carry the NEXT run's vis_batch_vi_align continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_imu_init.
+ * VIS_E_STATE without a context or plan. */
+int  vis_batch_vi_align_init(vis_ctx* ctx, const vis_vi_carry* rec);
+/* Out of scope: the accelerometer bias (it needs the bias Jacobians of v and p, which vis_imu_delta does not have); dv and dp are not corrected for
+ * dbg (pass bg + dbg to the next vis_batch_imu); covariances or weights; feeding anything back into the trajectory, vis_batch_track or vis_batch_pnp.
+ * There is no host-pointer single form: one interval aligns nothing. */
 
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */

@@ -56,6 +56,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              plan's own pairing, default parameters; the carry continues across the batches).  The CSV is EuRoC's: timestamp in ns, w (rad/s), a
              (m/s^2), lines that start with # skipped; frame times come from the image file names; both are taken relative to the first frame's
              stamp, in seconds.  One row per frame -- frame index, timestamp, flags (VIS_IMU_*), q, n_steps, dt, R (9), v (3), p (3).
+  --vi-align out.csv: with --imu and --trajectory, align the chained trajectory with the IMU on the device (vis_batch_vi_align behind
+             vis_batch_trajectory and vis_batch_imu of every batch, default parameters; the sums and tails continue across the batches).  One row
+             per frame -- frame index, timestamp, flags (VIS_VIS_*), q, res, p (3), v (3), under the batch's own solution; the JSON line carries the
+             LAST batch's record: flags (VIS_VIA_*), pairs, triples, dbg, s, g, |g_lin|, rms.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -123,6 +127,7 @@ def main():
     ap.add_argument("--trajectory", default=None, metavar="CSV", help="chain the two-view poses under the scale links; write one pose per frame here")
     ap.add_argument("--imu", default=None, metavar="CSV", help="EuRoC imu0/data.csv: timestamp [ns], w, a")
     ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
+    ap.add_argument("--vi-align", default=None, metavar="CSV", help="with --imu and --trajectory: gyro bias, gravity, metric scale; one state per frame here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
     ap.add_argument("--roi", default=None, metavar="x1,y1,x2,y2", help="with --rectify: the window of the rectified image to process")
@@ -215,6 +220,12 @@ def main():
         d_idelta, d_irot = torch.zeros(B * 216, dtype=torch.uint8, device="cuda"), torch.zeros(B * 36, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         imu_rows, imu_totals = [], dict(paired=0, flagged=0)
+    if a.vi_align:
+        if not (a.imu and a.trajectory):
+            raise SystemExit("--vi-align needs --imu and --trajectory")
+        d_vstate, d_vres = torch.zeros(B * 64, dtype=torch.uint8, device="cuda"), torch.zeros(160, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        via_rows, via_last = [], None
     if a.weights != "identity":
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
@@ -320,6 +331,8 @@ def main():
             ctx.batch_trajectory(nb, d_jlink.data_ptr(), d_jtraj.data_ptr(), d_jposes.data_ptr())
             ctx.batch_ftrack(nb, jk, d_jobs.data_ptr(), d_jframe.data_ptr())
             ctx.batch_ftrack_triangulate(nb, d_jobs.data_ptr(), jk, d_jposes.data_ptr(), d_jpts.data_ptr(), d_jfl.data_ptr(), d_jsm.data_ptr())
+        if a.vi_align:                                       # behind the trajectory and the deltas of the batch, on the same stream
+            ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_vres.data_ptr(), d_vstate.data_ptr())
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -390,6 +403,9 @@ def main():
                 imu_totals["paired"] += int(not fl & (vislam.IMU_NO_PAIR | vislam.IMU_NO_CARRY))
                 imu_totals["flagged"] += int(bool(fl & ~(vislam.IMU_NO_PAIR | vislam.IMU_NO_CARRY)))
                 imu_rows.append((first + i, stamps[first + i], idl[i].copy()))
+        if a.vi_align:
+            vst, via_last = d_vstate.cpu().numpy().view(vislam.VI_STATE_DTYPE), d_vres.cpu().numpy().view(vislam.VI_ALIGN_DTYPE)[0].copy()
+            via_rows += [(first + i, stamps[first + i], vst[i].copy()) for i in range(nb)]
         if a.tracks:
             tobs = d_tobs.cpu().numpy().view(vislam.FTRACK_OBS_DTYPE).reshape(B, tcap)
             tfr = d_tframe.cpu().numpy().view(vislam.FTRACK_FRAME_DTYPE)
@@ -516,6 +532,15 @@ def main():
                 f.write("%d,%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"], r["n_steps"]) + ",".join("%.17g" % v for v in dbl) + "\n")
         out["imu_csv"] = a.imu_out
         out["imu"] = dict(imu_totals, samples=len(imu_s))
+    if a.vi_align:
+        with open(a.vi_align, "w") as f:                        # frame, stamp, flags, q, res, p, v
+            for fi, ts, r in via_rows:
+                f.write("%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"]) + ",".join("%.17g" % v for v in [r["res"]] + list(r["p"]) + list(r["v"])) + "\n")
+        out["vi_align_csv"] = a.vi_align
+        if via_last is not None:
+            out["vi_align"] = dict(flags=int(via_last["flags"]), pairs=int(via_last["n_pairs"]), triples=int(via_last["n_triples"]),
+                                   dbg=[float(v) for v in via_last["dbg"]], s=float(via_last["s"]), g=[float(v) for v in via_last["g"]],
+                                   g_lin_norm=float(via_last["g_lin_norm"]), rms=float(via_last["rms"]))
     if a.tracks:
         with open(a.tracks, "w") as f:                         # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
             for r in track_rows:

@@ -273,7 +273,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_via_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1273,6 +1273,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft.forget();   // vis_batch_ftrack: no carried row, seq restarts at 0
     ctx->batch->sl.forget(); ctx->batch->tj.forget();              // scale links / trajectory: nothing carried
     ctx->batch->imu.forget();                                      // vis_batch_imu: no carried time, no open delta
+    ctx->batch->via.forget();                                      // vis_batch_vi_align: no carried sums, no tails
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
@@ -1868,7 +1869,7 @@ extern "C" int vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     return pnp_batch_run(ctx, pp, n, max_pts, d_X, x_stride, d_xy, d_npts, d_draws, row_cap, d_mask, d_out);
 }
 
-// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws), in ONE place: the list is measured and the block allocated by the
+// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_via_ws), in ONE place: the list is measured and the block allocated by the
 // first call of the plan that needs it; every call binds the list to the block, into a work struct of its own.  The block is never replaced.
 template <class Layout> static int plan_block(vis_ctx* ctx, void*& block, const char* who, Layout&& layout) {
     if (!block) {
@@ -2269,6 +2270,79 @@ extern "C" int vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec) {
     if (!rec) { pl->imu.forget(); return VIS_OK; }
     HIPCHK(ctx, hipMemcpy(W.carry[pl->imu.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
     pl->imu.seeded(pl->run_count);
+    return VIS_OK;
+}
+
+// ---- visual-inertial alignment: vi_align.hip
+extern "C" void vis_default_vi_align_params(vis_vi_align_params* vp) {
+    if (!vp) return;
+    for (int k = 0; k < 9; k++) vp->r_ic[k] = (k & 3) == 0 ? 1.0 : 0.0;
+    for (int k = 0; k < 3; k++) vp->p_ci[k] = 0.0;
+    vp->G = 9.81; vp->g_tol = 0.1;
+    vp->min_pairs = 8; vp->min_triples = 8; vp->refine_iters = 4; vp->reject = VIS_IMU_EMPTY | VIS_IMU_GAP;
+}
+
+static bool vi_align_params_ok(const vis_vi_align_params* vp) {
+    if (!vp) return false;
+    for (int k = 0; k < 9; k++) if (!std::isfinite(vp->r_ic[k])) return false;
+    for (int k = 0; k < 3; k++) if (!std::isfinite(vp->p_ci[k])) return false;
+    if (!std::isfinite(vp->G) || !std::isfinite(vp->g_tol) || !(vp->G > 0.0) || !(vp->g_tol >= 0.0)) return false;
+    return vp->min_pairs >= 1 && vp->min_triples >= 1 && vp->refine_iters >= 0 && vp->refine_iters <= 16;
+}
+
+extern "C" int vis_vi_align_rows(vis_ctx* ctx, const vis_vi_align_params* vp, int n, const int32_t* d_prev, const vis_traj_pose* d_traj,
+                                 const vis_imu_delta* d_delta, const vis_vi_carry* d_carry_in, vis_vi_state* d_state, vis_vi_align* d_result,
+                                 vis_vi_carry* d_carry_out) {
+    if (!vi_align_params_ok(vp) || !d_prev || !d_traj || !d_delta || !d_result) return VIS_E_INVALID;
+    if (!aligned(d_traj, 8) || !aligned(d_delta, 8) || !aligned(d_carry_in, 8) || !aligned(d_state, 8) || !aligned(d_result, 8) || !aligned(d_carry_out, 8) ||
+        !aligned(d_prev, 4)) return VIS_E_INVALID;
+    if (n < 0 || (d_carry_out && d_carry_out == d_carry_in)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_vi_align_rows: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return via_launch(ctx, vp, n, FtFrames{d_prev, 0, nullptr}, d_traj, d_delta, d_carry_in, d_state, d_result, d_carry_out);
+}
+
+// the plan's block: the two carried records
+struct ViaPlanWork { vis_vi_carry* carry[2]; };
+static int ensure_via(vis_ctx* ctx, Plan* pl, ViaPlanWork& W) {
+    return plan_block(ctx, pl->d_via_ws, "vis_batch_vi_align", [&](Carver& cv) { W.carry[0] = cv.take<vis_vi_carry>(1); W.carry[1] = cv.take<vis_vi_carry>(1); });
+}
+
+extern "C" int vis_batch_vi_align(vis_ctx* ctx, const vis_vi_align_params* vp, int n, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
+                                  vis_vi_state* d_state, vis_vi_align* d_result) {
+    if (!vi_align_params_ok(vp) || !d_traj || !d_delta || !d_result) return VIS_E_INVALID;
+    if (!aligned(d_traj, 8) || !aligned(d_delta, 8) || !aligned(d_state, 8) || !aligned(d_result, 8) || n < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_vi_align: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_batch_vi_align: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    ViaPlanWork W;
+    { const int rc = ensure_via(ctx, pl, W); if (rc) return rc; }
+    const Turn::Pick rec = pl->via.pick(pl->run_count);
+    // on the pose stream behind vis_batch_trajectory and vis_batch_imu of the run, which wrote d_traj and d_delta there
+    const int rc = batch_epi(ctx, n, "vis_batch_vi_align", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = via_launch(ctx, vp, n, plan_frames(pl_), d_traj, d_delta, rec.have ? W.carry[rec.slot] : nullptr, d_state, d_result, W.carry[rec.slot ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->via.commit(rec, pl->run_count);
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_vi_align_init(vis_ctx* ctx, const vis_vi_carry* rec) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                 // (a kernel in flight reads and writes the records)
+    Plan* pl = ctx->batch;
+    ViaPlanWork W;
+    { const int rc = ensure_via(ctx, pl, W); if (rc) return rc; }
+    if (!rec) { pl->via.forget(); return VIS_OK; }
+    HIPCHK(ctx, hipMemcpy(W.carry[pl->via.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->via.seeded(pl->run_count);
     return VIS_OK;
 }
 

@@ -56,7 +56,7 @@ struct ReaderGuard {
     void clear() { *this = ReaderGuard(); }
 };
 
-// Which of a plan's TWO carried rows a follow-up launch continues (vis_batch_ftrack, _scale_links, _trajectory, _imu: "the rules of the depth row",
+// Which of a plan's TWO carried rows a follow-up launch continues (vis_batch_ftrack, _scale_links, _trajectory, _imu, _vi_align: "the rules of the depth row",
 // include/vislam_hip.h).  A launch reads row `slot` -- the row of the last saved frame of the launch before, beside the carried record of the keyframe
 // gate -- and writes the other one, slot ^ 1: two rows, so that a call never reads the row it writes and a call repeated for the same run reads again
 // the row it read itself.  in = the row the last committed launch read, run = its run_count (-1: none), have = whether it had a row to read.
@@ -129,7 +129,7 @@ struct Plan {
     float2* d_warp = nullptr;
     // The follow-ups' blocks, each allocated ONCE by the first call of the plan that needs it and never replaced (api.hip plan_block: one list per
     // block, measured for the allocation and bound by every call into a work struct of its own; plan_destroy frees them), and the turns of the
-    // carried rows that four of them hold (Turn).  A plan starts with the turns' defaults and nothing commits before the block exists.
+    // carried rows that five of them hold (Turn).  A plan starts with the turns' defaults and nothing commits before the block exists.
     // vis_batch_pnp (PnpPlanWork): per frame the keypoint table of its keyframe's pair (npairs x kcap), the linked rows (npairs x pose_mcap map
     // points and pixels) and their counts
     void* d_pnp_ws = nullptr;
@@ -142,6 +142,8 @@ struct Plan {
     void* d_tj_ws = nullptr; Turn sl, tj;
     // vis_batch_imu (ImuPlanWork), allocated by the first call or by vis_batch_imu_init: the lifting table for B frames and the two carried records
     void* d_imu_ws = nullptr; Turn imu;
+    // vis_batch_vi_align (ViaPlanWork), allocated by the first call or by vis_batch_vi_align_init: the two carried records
+    void* d_via_ws = nullptr; Turn via;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -622,6 +624,9 @@ int trajectory_run(vis_ctx* ctx, int n, FtFrames fr, const PoseOut* d_pose, cons
 size_t imu_table_bytes(int n);
 int imu_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
             const vis_imu_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, float* d_rot, vis_imu_carry* d_carry_out);
+// vi_align.hip.  k_via_align on ctx->stream: one launch, no workspace; vp validated by the caller; d_carry, d_state, d_carry_out: null or the records
+int via_launch(vis_ctx* ctx, const vis_vi_align_params* vp, int n, FtFrames fr, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
+               const vis_vi_carry* d_carry, vis_vi_state* d_state, vis_vi_align* d_result, vis_vi_carry* d_carry_out);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

@@ -367,6 +367,43 @@ IMU_CARRY_TIME, IMU_CARRY_OPEN = 1, 2
 IMU_MAX_FRAMES = 1024
 
 
+class ViAlignParams(C.Structure):
+    """vis_vi_align_params (vis_default_vi_align_params: identity, 0, 9.81, 0.1, 8, 8, 4, IMU_EMPTY | IMU_GAP)"""
+    _fields_ = [("r_ic", C.c_double * 9), ("p_ci", C.c_double * 3), ("G", C.c_double), ("g_tol", C.c_double), ("min_pairs", C.c_int32),
+                ("min_triples", C.c_int32), ("refine_iters", C.c_int32), ("reject", C.c_int32)]
+
+
+class ViTail(C.Structure):
+    """vis_vi_tail: camera centre, IMU-to-root rotation and lever term of a frame, its segment and epoch, VIT_* flags"""
+    _fields_ = [("C", C.c_double * 3), ("Rw", C.c_double * 9), ("L", C.c_double * 3), ("segment_seq", C.c_int32), ("epoch_seq", C.c_int32),
+                ("flags", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class ViCarry(C.Structure):
+    """vis_vi_carry as a host structure (vis_batch_vi_align_init)"""
+    _fields_ = [("gyro", C.c_double * 10), ("lin", C.c_double * 16), ("n_pairs", C.c_int32), ("n_triples", C.c_int32), ("segment_seq", C.c_int32),
+                ("epoch_seq", C.c_int32), ("last", ViTail), ("parent", ViTail), ("last_delta", ImuDelta), ("valid", C.c_int32), ("reserved_", C.c_int32)]
+
+
+VI_STATE_DTYPE = np.dtype([("p", "<f8", (3,)), ("v", "<f8", (3,)), ("res", "<f8"), ("flags", "<i4"), ("q", "<i4")])
+VI_ALIGN_DTYPE = np.dtype([("dbg", "<f8", (3,)), ("c0", "<f8"), ("c0_call", "<f8"), ("c1", "<f8"), ("s", "<f8"), ("g", "<f8", (3,)), ("s_lin", "<f8"),
+                           ("g_lin", "<f8", (3,)), ("g_lin_norm", "<f8"), ("rms", "<f8"), ("n_pairs", "<i4"), ("n_triples", "<i4"),
+                           ("n_pairs_call", "<i4"), ("n_triples_call", "<i4"), ("segment_seq", "<i4"), ("epoch_seq", "<i4"), ("flags", "<i4"),
+                           ("reserved_", "<i4")])
+VI_TAIL_DTYPE = np.dtype([("C", "<f8", (3,)), ("Rw", "<f8", (9,)), ("L", "<f8", (3,)), ("segment_seq", "<i4"), ("epoch_seq", "<i4"), ("flags", "<i4"),
+                          ("reserved_", "<i4")])
+VI_CARRY_DTYPE = np.dtype([("gyro", "<f8", (10,)), ("lin", "<f8", (16,)), ("n_pairs", "<i4"), ("n_triples", "<i4"), ("segment_seq", "<i4"),
+                           ("epoch_seq", "<i4"), ("last", VI_TAIL_DTYPE), ("parent", VI_TAIL_DTYPE), ("last_delta", IMU_DELTA_DTYPE), ("valid", "<i4"),
+                           ("reserved_", "<i4")])
+assert VI_STATE_DTYPE.itemsize == 64 and VI_ALIGN_DTYPE.itemsize == 160 and VI_TAIL_DTYPE.itemsize == 136 == C.sizeof(ViTail)
+assert VI_CARRY_DTYPE.itemsize == 720 == C.sizeof(ViCarry) and C.sizeof(ViAlignParams) == 128
+VIA_OK, VIA_GYRO_FEW, VIA_GYRO_SINGULAR, VIA_FEW, VIA_SINGULAR, VIA_SCALE, VIA_GRAVITY_NORM, VIA_RESTART, VIA_BAD_CARRY = 0, 1, 2, 4, 8, 16, 32, 64, 128
+VIS_HAS_P, VIS_HAS_V, VIS_HAS_TRIPLE, VIS_HAS_PAIR = 1, 2, 4, 8
+VIT_POSED, VIT_EDGE, VIT_DELTA = 1, 2, 4
+VIC_VALID = 1
+VIA_MAX_FRAMES = 1024
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -420,6 +457,7 @@ ABI_SYMBOLS = [
     "vis_default_scale_link_params", "vis_scale_link_rows", "vis_batch_scale_links", "vis_trajectory_rows", "vis_batch_trajectory",
     "vis_batch_trajectory_init",
     "vis_default_imu_params", "vis_imu_preintegrate", "vis_imu_preintegrate_rows", "vis_batch_imu", "vis_batch_imu_init",
+    "vis_default_vi_align_params", "vis_vi_align_rows", "vis_batch_vi_align", "vis_batch_vi_align_init",
 ]
 
 
@@ -531,6 +569,13 @@ def _load():
         lib.vis_imu_preintegrate_rows.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
         lib.vis_batch_imu.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp]
         lib.vis_batch_imu_init.argtypes = [vp, C.POINTER(ImuCarry)]
+    if hasattr(lib, "vis_batch_vi_align"):              # (absent from older A/B builds)
+        vap = C.POINTER(ViAlignParams)
+        lib.vis_default_vi_align_params.argtypes = [vap]
+        lib.vis_default_vi_align_params.restype = None
+        lib.vis_vi_align_rows.argtypes = [vp, vap, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_vi_align.argtypes = [vp, vap, ci, vp, vp, vp, vp]
+        lib.vis_batch_vi_align_init.argtypes = [vp, C.POINTER(ViCarry)]
     if hasattr(lib, "vis_essential_refine_batch"):      # (absent from older A/B builds)
         epp = C.POINTER(EssentialRefineParams)
         lib.vis_default_eref_params.argtypes = [epp]
@@ -690,6 +735,12 @@ def default_imu_params():
     ip = ImuParams()
     lib.vis_default_imu_params(C.byref(ip))
     return ip
+
+
+def default_vi_align_params():
+    vp = ViAlignParams()
+    lib.vis_default_vi_align_params(C.byref(vp))
+    return vp
 
 
 def default_scale_link_params():
@@ -1555,6 +1606,28 @@ class Context:
         if rec is not None and not isinstance(rec, ImuCarry):
             rec = ImuCarry.from_buffer_copy(np.asarray(rec, IMU_CARRY_DTYPE).tobytes())
         self._chk(lib.vis_batch_imu_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_imu_init")
+
+    # -- visual-inertial alignment: gyro bias, gravity, metric scale, velocities ---------------------------------------
+    def vi_align_rows(self, n, d_prev_ptr, d_traj_ptr, d_delta_ptr, d_result_ptr, d_state_ptr=0, d_carry_in_ptr=0, d_carry_out_ptr=0, vp=None):
+        """queue the alignment of n frames of caller rows on the context's stream (raw DEVICE pointers; 0 / None = NULL): TRAJ records and
+        IMU_DELTA_DTYPE records in, n VI_STATE_DTYPE records, ONE VI_ALIGN_DTYPE record and the VI_CARRY_DTYPE record of the next call out"""
+        vp = default_vi_align_params() if vp is None else vp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_vi_align_rows(self._h, C.byref(vp), n, v(d_prev_ptr), v(d_traj_ptr), v(d_delta_ptr), v(d_carry_in_ptr), v(d_state_ptr),
+                                        v(d_result_ptr), v(d_carry_out_ptr)), "vis_vi_align_rows")
+
+    def batch_vi_align(self, n, d_traj_ptr, d_delta_ptr, d_result_ptr, d_state_ptr=0, vp=None):
+        """the same for the frames of the last batch_run, behind batch_trajectory and batch_imu of the run, which wrote d_traj and d_delta; the plan
+        carries the sums and the tails to the next launch.  The buffers are in use until batch_sync()"""
+        vp = default_vi_align_params() if vp is None else vp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_vi_align(self._h, C.byref(vp), n, v(d_traj_ptr), v(d_delta_ptr), v(d_state_ptr), v(d_result_ptr)), "vis_batch_vi_align")
+
+    def batch_vi_align_init(self, rec=None):
+        """the carry (a VI_CARRY_DTYPE element or a ViCarry; None: none) the next run's batch_vi_align continues from; synchronises"""
+        if rec is not None and not isinstance(rec, ViCarry):
+            rec = ViCarry.from_buffer_copy(np.asarray(rec, VI_CARRY_DTYPE).tobytes())
+        self._chk(lib.vis_batch_vi_align_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_vi_align_init")
 
     # -- the essential-matrix pose on device rows, and its refinement ----------------------------------------------
     def essential_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr):
