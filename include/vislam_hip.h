@@ -1649,9 +1649,75 @@ int  vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_
 /* The carry the NEXT run's vis_batch_imu continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_trajectory_init.
  * VIS_E_STATE without a context or plan. */
 int  vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec);
-/* Out of scope: the bias Jacobians of v and p and the 9 x 9 covariance (so no accelerometer-bias estimate; the gyro bias, gravity, the metric scale
- * and the lever arm are vis_vi_align_rows / vis_batch_vi_align below), a guided run with the gate on, and the adapters' IMU arguments (still accepted
- * and ignored). */
+/* Out of scope: the 9 x 9 covariance (the bias Jacobians of v and p are the block below; the gyro bias, gravity, the metric scale and the lever arm
+ * are vis_vi_align_rows / vis_batch_vi_align), a guided run with the gate on, and the adapters' IMU arguments (still accepted and ignored). */
+
+/* ---- Bias Jacobians of the deltas and the first-order bias correction.  The three calls below are vis_imu_preintegrate, vis_imu_preintegrate_rows
+ * and vis_batch_imu with one more output row, d_jac: Jvg = dv / dbg, Jva = dv / dba, Jpg = dp / dbg, Jpa = dp / dba (3 x 3 row-major), the derivatives
+ * of the SCHEME above (midpoint rule, ten-term Exp), which is what a finite difference of tests/imu_ref.py measures.  d_delta, d_rot and the carried
+ * delta are the sibling's BYTE FOR BYTE on every input: the delta's operations are the same ones in the same order, and a Jacobian never changes a
+ * delta.  tests/imu_jac_ref.py restates every operation below; every record equals it byte for byte.  Double arithmetic, + - * / only, nothing
+ * contracted.  ([u]x M)[c] = u[1] M[6 + c] - u[2] M[3 + c], [3 + c] = u[2] M[c] - u[0] M[6 + c], [6 + c] = u[0] M[3 + c] - u[1] M[c], c = 0, 1, 2.
+ * SUB-STEP, with R, J = JRg before it, R', J' after it, u0 = a0 - ba, u1 = a1 - ba, all from the sub-step above, and k = 0 ... 8:
+ *   G0 = R ([u0]x J), G1 = R' ([u1]x J') (products as above); Dg[k] = -0.5 (G0[k] + G1[k]); Da[k] = -0.5 (R[k] + R'[k]);
+ *   Jpg[k] = Jpg[k] + (Jvg[k] h + (0.5 Dg[k]) (h h)); then Jvg[k] = Jvg[k] + Dg[k] h; Jpa, Jva alike with Da (the p lines use the old v Jacobians).
+ * An interval starts with zero Jacobians and flags 0.  SETTLE, the rule every Jacobian record ends on, with the flags of ITS delta: zero matrices when
+ * the delta's flags have any of VIS_IMU_NO_PAIR | NO_CARRY | NO_START | NONFINITE (a voided delta has zero Jacobians) or the record's flags already
+ * have VIS_IMU_JAC_NONFINITE; else, when one of the 36 numbers is not finite: VIS_IMU_JAC_NONFINITE and zero matrices.  The flag is sticky: flags are
+ * OR-ed through compositions.  No NaN or infinity reaches a record or a carry.  An interval settles after the delta's own finite() rule.
+ * COMPOSITION X o Y (X earlier), after the delta's O = X o Y, with Wv = X.R ([Y.v]x X.JRg), Wp = X.R ([Y.p]x X.JRg):
+ *   Jpa[k] = (X.Jpa[k] + X.Jva[k] Y.dt) + (X.R Y.Jpa)[k];                 Jva[k] = X.Jva[k] + (X.R Y.Jva)[k];
+ *   Jpg[k] = ((X.Jpg[k] + X.Jvg[k] Y.dt) + (X.R Y.Jpg)[k]) - Wp[k];       Jvg[k] = (X.Jvg[k] + (X.R Y.Jvg)[k]) - Wv[k];
+ * flags = X.flags | Y.flags; then SETTLE with O's flags.  TABLE, PAIRS and CARRY are the delta's, entry for entry: the same levels, the same set
+ * bits, the carried open delta composed in front where the delta's is; so with the gate off a stream's Jacobians are the same bytes however it is
+ * cut, and with the gate on two cuts agree within a bound.  A frame without a pair has zero Jacobians and flags 0.  q = the delta's q
+ * (0 in a carry).  The table is a separate one of 496 bytes x frames x levels (62 slots: the 26 of vis_imu_preintegrate_rows, then the four blocks);
+ * vis_imu_preintegrate_rows, vis_batch_imu and vis_imu_preintegrate keep their table, their kernels' work and their results.
+ * On the device: k_imu_intervals<true> and k_imu_pairs<true>, the launches of the siblings; a composition folds one block at a time. */
+enum { VIS_IMU_JAC_OK = 0, VIS_IMU_JAC_NONFINITE = 1 };
+typedef struct vis_imu_bias_jac { double Jvg[9], Jva[9], Jpg[9], Jpa[9]; int32_t flags, q; } vis_imu_bias_jac;           /* 296 bytes */
+/* vis_imu_carry and the Jacobians of its open delta */
+typedef struct vis_imu_jac_carry { vis_imu_carry carry; vis_imu_bias_jac open_jac; } vis_imu_jac_carry;                   /* 528 bytes */
+/* vis_imu_preintegrate with the Jacobians of the interval.  Refusals in its order, jac NULL beside delta NULL. */
+int  vis_imu_preintegrate_jac(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_sample* samples, int n_samples, double t_a, double t_b,
+                              vis_imu_delta* delta, vis_imu_bias_jac* jac, float* rot);
+/* vis_imu_preintegrate_rows with d_jac (n records, 8-byte aligned, not NULL) and carries that hold the open delta's Jacobians.  The workspace is a
+ * block of the context's own, apart from vis_imu_preintegrate_rows', under the same rule: it only grows, and a call that grows it SYNCHRONISES.
+ * Refusals in the sibling's order and codes, d_jac beside d_delta. */
+int  vis_imu_preintegrate_jac_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                                   const int32_t* d_prev, const vis_imu_jac_carry* d_carry_in, vis_imu_delta* d_delta, vis_imu_bias_jac* d_jac, float* d_rot,
+                                   vis_imu_jac_carry* d_carry_out);
+/* vis_batch_imu with d_jac, on the POSE stream through the follow-up scaffold, with TWO carried vis_imu_jac_carry records of its own under the same
+ * turn rule -- apart from vis_batch_imu's, so that either may be called for a run, or both.  Refusals in vis_batch_imu's order and codes. */
+int  vis_batch_imu_jac(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                       vis_imu_delta* d_delta, vis_imu_bias_jac* d_jac, float* d_rot);
+/* The carry the NEXT run's vis_batch_imu_jac continues from (rec NULL: none).  HOST pointer; SYNCHRONISES.  VIS_E_STATE without a context or plan. */
+int  vis_batch_imu_jac_init(vis_ctx* ctx, const vis_imu_jac_carry* rec);
+/* THE CORRECTION: the records of a bias step (dbg, dba) to first order, with no second pass over the samples.  d_dbg: THREE doubles on the device --
+ * the first 24 bytes of a vis_vi_align record are its dbg, so the alignment's result is passed as it is, with no host step; d_dba: three doubles or
+ * NULL for (0, 0, 0).  Of ip, r_ic and max_angle are used.  Per frame, with (R, v, p, JRg) of d_delta[i] and the blocks of d_jac[i], in this order:
+ *   flags with any of VIS_IMU_NO_PAIR | NO_CARRY | NO_START | NONFINITE, or one of the delta's 25 numbers not finite: VIS_IMC_UNUSABLE;
+ *   d_jac[i].flags has VIS_IMU_JAC_NONFINITE: VIS_IMC_JAC;  one of the six bias numbers not finite: VIS_IMC_BIAS;
+ *   phi = JRg dbg, xx ... th2 as in the sub-step; th2 > max_angle max_angle: VIS_IMC_ANGLE;
+ *   R' = R Exp(phi) (A, B by the ten-term sums, dR as in the sub-step); v'[r] = v[r] + ((Jvg dbg)[r] + (Jva dba)[r]); p'[r] = p[r] + ((Jpg dbg)[r] +
+ *   (Jpa dba)[r]); one of the 15 numbers not finite: VIS_IMC_NONFINITE; else VIS_IMC_OK.
+ * VIS_IMC_OK writes the record with R', v', p' in the place of R, v, p and dt, JRg, n_steps, flags, q, reserved_ kept; every other status copies the
+ * record unchanged.  d_status[i] (NULL or n int32) = the status.  d_rot_out (NULL or n x 9 floats) = d_rot's rule on the record written.  The
+ * Jacobians are those of the OLD biases: after the step they are first-order stale, like JRg.  d_delta_out may not alias d_delta.  k_imu_correct, one
+ * lane per frame, asynchronous on the context's stream, no workspace.
+ * Refusals, in this order.  VIS_E_INVALID: ip as above; a NULL d_delta, d_jac, d_dbg or d_delta_out; a pointer that is not aligned (8 bytes; d_rot_out
+ * and d_status 4); n negative; d_delta_out equal to d_delta.  VIS_E_STATE without a context.  VIS_E_CAPACITY when n > VIS_IMU_MAX_FRAMES. */
+enum { VIS_IMC_OK = 0, VIS_IMC_UNUSABLE = 1, VIS_IMC_JAC = 2, VIS_IMC_BIAS = 4, VIS_IMC_ANGLE = 8, VIS_IMC_NONFINITE = 16 };
+int  vis_imu_correct_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
+                          const double* d_dba, vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status);
+/* The same for the frames of the last vis_batch_run, on the POSE stream through the follow-up scaffold: queued behind vis_batch_vi_align, it reads
+ * that call's d_result as d_dbg, and a second vis_batch_vi_align queued behind it reads d_delta_out -- align, correct, align again with no host step.
+ * (The second alignment of a run is a repeated call: it reads the carry the first one read.)  The caller's buffers are in use until vis_batch_sync.
+ * Refusals as above; VIS_E_STATE: no context / plan / match stage, or n differs. */
+int  vis_batch_imu_correct(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
+                           const double* d_dba, vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status);
+/* Out of scope: the accelerometer-bias ESTIMATE (the Jacobians it needs are here; the estimator is not), covariance propagation, the host adapters' IMU
+ * arguments, a guided run with the gate on. */
 
 /* ---- visual-inertial alignment: the gyro bias, gravity in the root's frame, the factor from trajectory units to metres and a velocity per frame,
  * from the records of vis_batch_trajectory and vis_batch_imu (after Mur-Artal & Tardos 2017 and Qin et al. 2018, restated from the equations; the
@@ -1757,8 +1823,9 @@ int  vis_batch_vi_align(vis_ctx* ctx, const vis_vi_align_params* vp, int n, cons
 /* The carry the NEXT run's vis_batch_vi_align continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_imu_init.
  * VIS_E_STATE without a context or plan. */
 int  vis_batch_vi_align_init(vis_ctx* ctx, const vis_vi_carry* rec);
-/* Out of scope: the accelerometer bias (it needs the bias Jacobians of v and p, which vis_imu_delta does not have); dv and dp are not corrected for
- * dbg (pass bg + dbg to the next vis_batch_imu); covariances or weights; feeding anything back into the trajectory, vis_batch_track or vis_batch_pnp.
+/* Out of scope: the accelerometer bias (its estimator; the bias Jacobians of v and p it needs are vis_imu_bias_jac); this call does not correct dv
+ * and dp for dbg itself (vis_batch_imu_correct does, from d_result, and a second call of this one reads the corrected records; or pass bg + dbg to
+ * the next vis_batch_imu); covariances or weights; feeding anything back into the trajectory, vis_batch_track or vis_batch_pnp.
  * There is no host-pointer single form: one interval aligns nothing. */
 
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */

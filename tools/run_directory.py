@@ -60,6 +60,11 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              vis_batch_trajectory and vis_batch_imu of every batch, default parameters; the sums and tails continue across the batches).  One row
              per frame -- frame index, timestamp, flags (VIS_VIS_*), q, res, p (3), v (3), under the batch's own solution; the JSON line carries the
              LAST batch's record: flags (VIS_VIA_*), pairs, triples, dbg, s, g, |g_lin|, rms.
+  --imu-jac out.csv: with --imu, integrate with the bias Jacobians of v and p (vis_batch_imu_jac in vis_batch_imu's place: the same deltas).  One row per
+             frame -- frame index, timestamp, flags (VIS_IMU_JAC_*), q, Jvg (9), Jva (9), Jpg (9), Jpa (9).
+  --recorrect: with --vi-align and --imu-jac, close the loop on the device: align, correct the batch's deltas for the estimated gyro bias
+             (vis_batch_imu_correct reads dbg from the alignment's record), align again on the corrected records.  The states and the JSON record are
+             the second alignment's; the JSON line adds the first alignment's dbg, c0_call and c1 and the number of records corrected in the last batch.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -127,6 +132,8 @@ def main():
     ap.add_argument("--trajectory", default=None, metavar="CSV", help="chain the two-view poses under the scale links; write one pose per frame here")
     ap.add_argument("--imu", default=None, metavar="CSV", help="EuRoC imu0/data.csv: timestamp [ns], w, a")
     ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
+    ap.add_argument("--imu-jac", default=None, metavar="CSV", help="with --imu: write every frame's bias Jacobians of v and p here")
+    ap.add_argument("--recorrect", action="store_true", help="with --vi-align and --imu-jac: align, correct the deltas for dbg, align again")
     ap.add_argument("--vi-align", default=None, metavar="CSV", help="with --imu and --trajectory: gyro bias, gravity, metric scale; one state per frame here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
@@ -220,12 +227,22 @@ def main():
         d_idelta, d_irot = torch.zeros(B * 216, dtype=torch.uint8, device="cuda"), torch.zeros(B * 36, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         imu_rows, imu_totals = [], dict(paired=0, flagged=0)
+        if a.imu_jac:
+            d_ijac, jac_rows = torch.zeros(B * 296, dtype=torch.uint8, device="cuda"), []
+            torch.cuda.synchronize()
+    if a.imu_jac and not a.imu:
+        raise SystemExit("--imu-jac needs --imu")
+    if a.recorrect and not (a.vi_align and a.imu_jac):
+        raise SystemExit("--recorrect needs --vi-align and --imu-jac")
     if a.vi_align:
         if not (a.imu and a.trajectory):
             raise SystemExit("--vi-align needs --imu and --trajectory")
         d_vstate, d_vres = torch.zeros(B * 64, dtype=torch.uint8, device="cuda"), torch.zeros(160, dtype=torch.uint8, device="cuda")
         torch.cuda.synchronize()
         via_rows, via_last = [], None
+        if a.recorrect:
+            d_idelta2, d_istatus, d_vres1 = (torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for nbytes in (B * 216, B * 4, 160))
+            torch.cuda.synchronize()
     if a.weights != "identity":
         aw = vislam.default_align_weights()
         aw.mode = vislam.W_TUKEY if a.weights == "tukey" else vislam.W_TUKEY_SIGNED
@@ -323,7 +340,10 @@ def main():
             ctx.batch_ftrack(nb, tcap, d_tobs.data_ptr(), d_tframe.data_ptr())
         if a.klt:
             ctx.batch_klt(d, nb, kcap, d_krec.data_ptr(), d_kpair.data_ptr(), kp=kltp)
-        if a.imu:
+        if a.imu and a.imu_jac:
+            ctx.batch_imu_jac(nb, d_isamples.data_ptr() if len(imu_s) else 0, len(imu_s), d_itf.data_ptr() + 8 * first, d_idelta.data_ptr(), d_ijac.data_ptr(),
+                              d_irot.data_ptr())
+        elif a.imu:
             ctx.batch_imu(nb, d_isamples.data_ptr() if len(imu_s) else 0, len(imu_s), d_itf.data_ptr() + 8 * first, d_idelta.data_ptr(), d_irot.data_ptr())
         if a.trajectory:                                     # run -> triangulate -> scale links -> trajectory -> ftrack -> N-view triangulation: no host step
             ctx.batch_triangulate(nb, jcap, d_jmp.data_ptr(), d_jmf.data_ptr(), d_jms.data_ptr())
@@ -331,7 +351,11 @@ def main():
             ctx.batch_trajectory(nb, d_jlink.data_ptr(), d_jtraj.data_ptr(), d_jposes.data_ptr())
             ctx.batch_ftrack(nb, jk, d_jobs.data_ptr(), d_jframe.data_ptr())
             ctx.batch_ftrack_triangulate(nb, d_jobs.data_ptr(), jk, d_jposes.data_ptr(), d_jpts.data_ptr(), d_jfl.data_ptr(), d_jsm.data_ptr())
-        if a.vi_align:                                       # behind the trajectory and the deltas of the batch, on the same stream
+        if a.vi_align and a.recorrect:                       # align -> correct by the record's dbg -> align again: queued, no host step
+            ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_vres1.data_ptr(), d_vstate.data_ptr())
+            ctx.batch_imu_correct(nb, d_idelta.data_ptr(), d_ijac.data_ptr(), d_vres1.data_ptr(), d_idelta2.data_ptr(), 0, 0, d_istatus.data_ptr())
+            ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta2.data_ptr(), d_vres.data_ptr(), d_vstate.data_ptr())
+        elif a.vi_align:                                     # behind the trajectory and the deltas of the batch, on the same stream
             ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_vres.data_ptr(), d_vstate.data_ptr())
         if feed:
             feed.release(k)
@@ -403,9 +427,15 @@ def main():
                 imu_totals["paired"] += int(not fl & (vislam.IMU_NO_PAIR | vislam.IMU_NO_CARRY))
                 imu_totals["flagged"] += int(bool(fl & ~(vislam.IMU_NO_PAIR | vislam.IMU_NO_CARRY)))
                 imu_rows.append((first + i, stamps[first + i], idl[i].copy()))
+            if a.imu_jac:
+                ijc = d_ijac.cpu().numpy().view(vislam.IMU_BIAS_JAC_DTYPE)
+                jac_rows += [(first + i, stamps[first + i], ijc[i].copy()) for i in range(nb)]
         if a.vi_align:
             vst, via_last = d_vstate.cpu().numpy().view(vislam.VI_STATE_DTYPE), d_vres.cpu().numpy().view(vislam.VI_ALIGN_DTYPE)[0].copy()
             via_rows += [(first + i, stamps[first + i], vst[i].copy()) for i in range(nb)]
+            if a.recorrect:
+                via_first = d_vres1.cpu().numpy().view(vislam.VI_ALIGN_DTYPE)[0].copy()
+                via_corrected = int((d_istatus.cpu().numpy().view(np.int32)[:nb] == vislam.IMC_OK).sum())
         if a.tracks:
             tobs = d_tobs.cpu().numpy().view(vislam.FTRACK_OBS_DTYPE).reshape(B, tcap)
             tfr = d_tframe.cpu().numpy().view(vislam.FTRACK_FRAME_DTYPE)
@@ -532,6 +562,12 @@ def main():
                 f.write("%d,%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"], r["n_steps"]) + ",".join("%.17g" % v for v in dbl) + "\n")
         out["imu_csv"] = a.imu_out
         out["imu"] = dict(imu_totals, samples=len(imu_s))
+        if a.imu_jac:
+            with open(a.imu_jac, "w") as f:                     # frame, stamp, flags, q, Jvg, Jva, Jpg, Jpa
+                for fi, ts, r in jac_rows:
+                    dbl = list(r["Jvg"]) + list(r["Jva"]) + list(r["Jpg"]) + list(r["Jpa"])
+                    f.write("%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"]) + ",".join("%.17g" % v for v in dbl) + "\n")
+            out["imu_jac_csv"] = a.imu_jac
     if a.vi_align:
         with open(a.vi_align, "w") as f:                        # frame, stamp, flags, q, res, p, v
             for fi, ts, r in via_rows:
@@ -541,6 +577,9 @@ def main():
             out["vi_align"] = dict(flags=int(via_last["flags"]), pairs=int(via_last["n_pairs"]), triples=int(via_last["n_triples"]),
                                    dbg=[float(v) for v in via_last["dbg"]], s=float(via_last["s"]), g=[float(v) for v in via_last["g"]],
                                    g_lin_norm=float(via_last["g_lin_norm"]), rms=float(via_last["rms"]))
+            if a.recorrect:
+                out["recorrect"] = dict(dbg_first=[float(v) for v in via_first["dbg"]], c0_call_first=float(via_first["c0_call"]),
+                                        c1_first=float(via_first["c1"]), c0_call=float(via_last["c0_call"]), corrected_in_the_last_batch=via_corrected)
     if a.tracks:
         with open(a.tracks, "w") as f:                         # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
             for r in track_rows:

@@ -142,7 +142,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
     plan_destroy(ctx->single); plan_destroy(ctx->batch);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws}) if (b->p) (void)hipFree(b->p);
+    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws, &ctx->imuj_ws}) if (b->p) (void)hipFree(b->p);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -273,7 +273,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_via_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_imuj_ws); F(pl->d_via_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1272,6 +1272,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
     ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft.forget();   // vis_batch_ftrack: no carried row, seq restarts at 0
     ctx->batch->sl.forget(); ctx->batch->tj.forget();              // scale links / trajectory: nothing carried
+    ctx->batch->imuj.forget();                                     // vis_batch_imu_jac: the same
     ctx->batch->imu.forget();                                      // vis_batch_imu: no carried time, no open delta
     ctx->batch->via.forget();                                      // vis_batch_vi_align: no carried sums, no tails
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
@@ -1869,7 +1870,7 @@ extern "C" int vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     return pnp_batch_run(ctx, pp, n, max_pts, d_X, x_stride, d_xy, d_npts, d_draws, row_cap, d_mask, d_out);
 }
 
-// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_via_ws), in ONE place: the list is measured and the block allocated by the
+// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_imuj_ws, d_via_ws), in ONE place: the list is measured and the block allocated by the
 // first call of the plan that needs it; every call binds the list to the block, into a work struct of its own.  The block is never replaced.
 template <class Layout> static int plan_block(vis_ctx* ctx, void*& block, const char* who, Layout&& layout) {
     if (!block) {
@@ -2271,6 +2272,141 @@ extern "C" int vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec) {
     HIPCHK(ctx, hipMemcpy(W.carry[pl->imu.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
     pl->imu.seeded(pl->run_count);
     return VIS_OK;
+}
+
+// ---- the same three calls with the bias Jacobians of v and p (k_imu_intervals<true>, k_imu_pairs<true>, a table and carried records of their own), and
+// the first-order bias correction of the records (k_imu_correct)
+extern "C" int vis_imu_preintegrate_jac_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                                             const int32_t* d_prev, const vis_imu_jac_carry* d_carry_in, vis_imu_delta* d_delta, vis_imu_bias_jac* d_jac,
+                                             float* d_rot, vis_imu_jac_carry* d_carry_out) {
+    if (!imu_params_ok(ip) || !d_tframe || !d_prev || !d_delta || !d_jac || (n_samples > 0 && !d_samples)) return VIS_E_INVALID;
+    if (!aligned(d_samples, 8) || !aligned(d_tframe, 8) || !aligned(d_carry_in, 8) || !aligned(d_delta, 8) || !aligned(d_jac, 8) || !aligned(d_carry_out, 8) ||
+        !aligned(d_prev, 4) || !aligned(d_rot, 4)) return VIS_E_INVALID;
+    if (n < 0 || n_samples < 0 || (d_carry_out && d_carry_out == d_carry_in)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES) { ctx->err = "vis_imu_preintegrate_jac_rows: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const int rc = vis_grow_block(ctx, ctx->imuj_ws, imu_jac_table_bytes(n), "vis_imu_preintegrate_jac_rows");
+    if (rc) return rc;
+    return imu_jac_launch(ctx, ip, n, FtFrames{d_prev, 0, nullptr}, d_samples, n_samples, d_tframe, d_carry_in, ctx->imuj_ws.p, d_delta, d_jac, d_rot, d_carry_out);
+}
+
+extern "C" int vis_imu_preintegrate_jac(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_sample* samples, int n_samples, double t_a, double t_b,
+                                        vis_imu_delta* delta, vis_imu_bias_jac* jac, float* rot) {
+    if (!imu_params_ok(ip) || !delta || !jac || n_samples < 0 || (n_samples > 0 && !samples)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    int rc = vis_grow_block(ctx, ctx->imuj_ws, imu_jac_table_bytes(1), "vis_imu_preintegrate_jac");
+    if (rc) return rc;
+    vis_imu_sample* d_s; double* d_t; int32_t* d_prev; vis_imu_jac_carry* d_c; vis_imu_delta* d_d; vis_imu_bias_jac* d_j; float* d_r;
+    rc = vis_carve(ctx, [&](Carver& cv) {
+        d_s = cv.take<vis_imu_sample>((size_t)std::max(n_samples, 1)); d_t = cv.take<double>(1); d_prev = cv.take<int32_t>(1);
+        d_c = cv.take<vis_imu_jac_carry>(1); d_d = cv.take<vis_imu_delta>(1); d_j = cv.take<vis_imu_bias_jac>(1); d_r = cv.take<float>(9);
+    });
+    if (rc) return rc;
+    vis_imu_jac_carry c;
+    std::memset(&c, 0, sizeof(c));
+    c.carry.t_last = t_a; c.carry.valid = VIS_IMU_CARRY_TIME;
+    const int32_t prev = VIS_KF_CARRIED;
+    HostStage hs(ctx);
+    hs.up(d_s, samples, (size_t)n_samples * sizeof(vis_imu_sample));
+    hs.up(d_t, &t_b, sizeof(t_b));
+    hs.up(d_prev, &prev, sizeof(prev));
+    hs.up(d_c, &c, sizeof(c));
+    hs.flush_ups();
+    rc = imu_jac_launch(ctx, ip, 1, FtFrames{d_prev, 0, nullptr}, d_s, n_samples, d_t, d_c, ctx->imuj_ws.p, d_d, d_j, d_r, nullptr);
+    if (rc) return vis_drain(ctx, rc);
+    const void* h_d = hs.down(d_d, sizeof(vis_imu_delta));
+    const void* h_j = hs.down(d_j, sizeof(vis_imu_bias_jac));
+    const void* h_r = hs.down(d_r, 9 * sizeof(float));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(delta, h_d, sizeof(vis_imu_delta));
+    std::memcpy(jac, h_j, sizeof(vis_imu_bias_jac));
+    if (rot) std::memcpy(rot, h_r, 9 * sizeof(float));
+    return VIS_OK;
+}
+
+// the plan's block: the 62-slot lifting table for B frames and the two carried records
+struct ImuJacPlanWork { void* table; vis_imu_jac_carry* carry[2]; };
+static int ensure_imu_jac(vis_ctx* ctx, Plan* pl, ImuJacPlanWork& W) {
+    return plan_block(ctx, pl->d_imuj_ws, "vis_batch_imu_jac", [&](Carver& cv) {
+        W.table = cv.take<char>(imu_jac_table_bytes(pl->B)); W.carry[0] = cv.take<vis_imu_jac_carry>(1); W.carry[1] = cv.take<vis_imu_jac_carry>(1);
+    });
+}
+
+extern "C" int vis_batch_imu_jac(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                                 vis_imu_delta* d_delta, vis_imu_bias_jac* d_jac, float* d_rot) {
+    if (!imu_params_ok(ip) || !d_tframe || !d_delta || !d_jac || (n_samples > 0 && !d_samples)) return VIS_E_INVALID;
+    if (!aligned(d_samples, 8) || !aligned(d_tframe, 8) || !aligned(d_delta, 8) || !aligned(d_jac, 8) || !aligned(d_rot, 4) || n < 0 || n_samples < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_imu_jac: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES || n > pl->B) { ctx->err = "vis_batch_imu_jac: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    ImuJacPlanWork W;
+    { const int rc = ensure_imu_jac(ctx, pl, W); if (rc) return rc; }
+    const Turn::Pick rec = pl->imuj.pick(pl->run_count);
+    // on the pose stream behind the matcher of the run (the gate's link table) and behind the context's stream (the caller's samples and times)
+    const int rc = batch_epi(ctx, n, "vis_batch_imu_jac", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = imu_jac_launch(ctx, ip, n, plan_frames(pl_), d_samples, n_samples, d_tframe, rec.have ? W.carry[rec.slot] : nullptr, W.table, d_delta, d_jac,
+                                       d_rot, W.carry[rec.slot ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->imuj.commit(rec, pl->run_count);
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_imu_jac_init(vis_ctx* ctx, const vis_imu_jac_carry* rec) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                 // (a kernel in flight reads and writes the records)
+    Plan* pl = ctx->batch;
+    ImuJacPlanWork W;
+    { const int rc = ensure_imu_jac(ctx, pl, W); if (rc) return rc; }
+    if (!rec) { pl->imuj.forget(); return VIS_OK; }
+    HIPCHK(ctx, hipMemcpy(W.carry[pl->imuj.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->imuj.seeded(pl->run_count);
+    return VIS_OK;
+}
+
+static int imu_correct_args(const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg, const double* d_dba,
+                            vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status) {
+    if (!imu_params_ok(ip) || !d_delta || !d_jac || !d_dbg || !d_delta_out) return VIS_E_INVALID;
+    if (!aligned(d_delta, 8) || !aligned(d_jac, 8) || !aligned(d_dbg, 8) || !aligned(d_dba, 8) || !aligned(d_delta_out, 8) || !aligned(d_rot_out, 4) ||
+        !aligned(d_status, 4)) return VIS_E_INVALID;
+    if (n < 0 || d_delta_out == d_delta) return VIS_E_INVALID;
+    return VIS_OK;
+}
+
+extern "C" int vis_imu_correct_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
+                                    const double* d_dba, vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status) {
+    { const int rc = imu_correct_args(ip, n, d_delta, d_jac, d_dbg, d_dba, d_delta_out, d_rot_out, d_status); if (rc) return rc; }
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES) { ctx->err = "vis_imu_correct_rows: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return imu_correct_launch(ctx, ip, n, d_delta, d_jac, d_dbg, d_dba, d_delta_out, d_rot_out, d_status);
+}
+
+extern "C" int vis_batch_imu_correct(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
+                                     const double* d_dba, vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status) {
+    { const int rc = imu_correct_args(ip, n, d_delta, d_jac, d_dbg, d_dba, d_delta_out, d_rot_out, d_status); if (rc) return rc; }
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_imu_correct: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES) { ctx->err = "vis_batch_imu_correct: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    // on the pose stream behind vis_batch_imu_jac and vis_batch_vi_align of the run, which wrote d_delta, d_jac and d_dbg there
+    return batch_epi(ctx, n, "vis_batch_imu_correct", [&](Plan*, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = imu_correct_launch(ctx, ip, n, d_delta, d_jac, d_dbg, d_dba, d_delta_out, d_rot_out, d_status);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    });
 }
 
 // ---- visual-inertial alignment: vi_align.hip

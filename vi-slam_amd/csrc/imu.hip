@@ -5,6 +5,10 @@
 // A table entry is 26 eight-byte slots (25 doubles, n_steps and flags packed into the last), structure of arrays: slot s of entry i of level k
 // is ws[((size_t)k * 26 + s) * n + i], so consecutive frames read consecutive addresses.  Levels are separate arrays: a round reads level k - 1 and
 // writes level k, nothing is read and written in one round, one barrier a round suffices.
+// The Jacobian variants (k_imu_intervals<true>, k_imu_pairs<true>: vis_imu_preintegrate_jac_rows, vis_batch_imu_jac) are separate instantiations with a
+// table of their own of 62 slots: the 26 above, then Jvg, Jva, Jpg, Jpa (9 doubles each); the Jacobian flags ride in bits 16 and up of the flags half
+// of slot 25 (a table entry's delta flags come from intervals alone and stay below bit 9).  A composition folds one block at a time into the
+// accumulator: two whole entries are never held.  k_imu_correct applies a bias step to the records, a lane per frame.
 #include "vis_internal.h"
 #include <cmath>
 
@@ -12,6 +16,13 @@
 #define IMU_IV_BLOCK 64
 
 struct ImuDelta { double R[9], v[3], p[3], dt, J[9]; int n_steps, flags; };
+struct ImuJac { double vg[9], va[9], pg[9], pa[9]; int flags; };
+struct ImuNoJac {};
+template <bool JAC> struct ImuJacOf { typedef ImuNoJac type; };
+template <> struct ImuJacOf<true> { typedef ImuJac type; };
+// what the Jacobian variants read and write beside the delta's rows: the carried open delta's Jacobians, the rows, the carry's
+struct ImuJacIO { const vis_imu_bias_jac* cin; vis_imu_bias_jac* rows; vis_imu_bias_jac* cout; };
+#define IMU_VOID_FLAGS (VIS_IMU_NO_PAIR | VIS_IMU_NO_CARRY | VIS_IMU_NO_START | VIS_IMU_NONFINITE)
 
 __device__ __forceinline__ bool imu_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }     // false for NaN and +-inf
 __device__ __forceinline__ int imu_prev(const FtFrames& fr, int i) {
@@ -73,8 +84,59 @@ __device__ __forceinline__ void imu_compose(const ImuDelta& X, const ImuDelta& Y
     if (!imu_all_finite(O)) imu_void(O);
 }
 
-__device__ __forceinline__ void imu_ws_store(unsigned long long* ws, int n, int level, int i, const ImuDelta& d) {
-    unsigned long long* b = ws + (size_t)level * 26 * n + i;
+// ---- the bias Jacobians of v and p
+__device__ __forceinline__ void imu_jac_zero(ImuJac& q) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.vg[k] = q.va[k] = q.pg[k] = q.pa[k] = 0.0;
+}
+__device__ __forceinline__ void imu_jac_zero(ImuNoJac&) {}
+__device__ __forceinline__ void imu_skmul(const double* u, const double* M, double* S) {      // [u]x M
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        S[c] = u[1] * M[6 + c] - u[2] * M[3 + c];
+        S[3 + c] = u[2] * M[c] - u[0] * M[6 + c];
+        S[6 + c] = u[0] * M[3 + c] - u[1] * M[c];
+    }
+}
+// the rule every Jacobian record ends on: zero beside a voided delta or a flagged record; not finite beside a finite delta: zero and flagged
+__device__ __forceinline__ void imu_jac_settle(int dflags, ImuJac& q) {
+    bool zero = (dflags & IMU_VOID_FLAGS) || (q.flags & VIS_IMU_JAC_NONFINITE);
+    if (!zero) {
+        bool fin = true;
+#pragma unroll
+        for (int k = 0; k < 9; k++) fin = fin && imu_finite(q.vg[k]) && imu_finite(q.va[k]) && imu_finite(q.pg[k]) && imu_finite(q.pa[k]);
+        if (!fin) { q.flags |= VIS_IMU_JAC_NONFINITE; zero = true; }
+    }
+    if (zero) imu_jac_zero(q);
+}
+__device__ __forceinline__ void imu_jac_settle(int, ImuNoJac&) {}
+// the Jacobians of X o Y folded into q (in: Y's, out: the composition's), one block at a time; X's blocks come through ldx(block, M) (0 Jvg, 1 Jva, 2 Jpg,
+// 3 Jpa), Y is the delta BEFORE the composition and oflags the composed delta's flags
+template <class LoadX> __device__ __forceinline__ void imu_jac_fold(const ImuDelta& X, int xflags, LoadX ldx, const ImuDelta& Y, int oflags, ImuJac& q) {
+    double S[9], W[9], Xv[9], Xp[9], M[9];
+    q.flags |= xflags;
+    ldx(3, Xp); ldx(1, Xv);
+    imu_mul(X.R, q.pa, M);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.pa[k] = (Xp[k] + Xv[k] * Y.dt) + M[k];
+    imu_mul(X.R, q.va, M);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.va[k] = Xv[k] + M[k];
+    ldx(2, Xp); ldx(0, Xv);
+    imu_skmul(Y.p, X.J, S); imu_mul(X.R, S, W);
+    imu_mul(X.R, q.pg, M);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.pg[k] = ((Xp[k] + Xv[k] * Y.dt) + M[k]) - W[k];
+    imu_skmul(Y.v, X.J, S); imu_mul(X.R, S, W);
+    imu_mul(X.R, q.vg, M);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.vg[k] = (Xv[k] + M[k]) - W[k];
+    imu_jac_settle(oflags, q);
+}
+
+// SL = the slots of a table entry: 26, or 62 with the Jacobians; jflags = the Jacobian flags (0 without)
+template <int SL> __device__ __forceinline__ void imu_ws_store(unsigned long long* ws, int n, int level, int i, const ImuDelta& d, int jflags = 0) {
+    unsigned long long* b = ws + (size_t)level * SL * n + i;
 #pragma unroll
     for (int k = 0; k < 9; k++) b[(size_t)k * n] = (unsigned long long)__double_as_longlong(d.R[k]);
 #pragma unroll
@@ -82,10 +144,11 @@ __device__ __forceinline__ void imu_ws_store(unsigned long long* ws, int n, int 
     b[(size_t)15 * n] = (unsigned long long)__double_as_longlong(d.dt);
 #pragma unroll
     for (int k = 0; k < 9; k++) b[(size_t)(16 + k) * n] = (unsigned long long)__double_as_longlong(d.J[k]);
-    b[(size_t)25 * n] = ((unsigned long long)(uint32_t)d.flags << 32) | (unsigned long long)(uint32_t)d.n_steps;
+    b[(size_t)25 * n] = ((unsigned long long)(uint32_t)(d.flags | (jflags << 16)) << 32) | (unsigned long long)(uint32_t)d.n_steps;
 }
-__device__ __forceinline__ void imu_ws_load(const unsigned long long* ws, int n, int level, int i, ImuDelta& d) {
-    const unsigned long long* b = ws + (size_t)level * 26 * n + i;
+// (jflags: where the Jacobian flags of the entry go; the delta's flags are the low 16 bits either way, which is all of them without Jacobians)
+template <int SL> __device__ __forceinline__ void imu_ws_load(const unsigned long long* ws, int n, int level, int i, ImuDelta& d, int* jflags = nullptr) {
+    const unsigned long long* b = ws + (size_t)level * SL * n + i;
 #pragma unroll
     for (int k = 0; k < 9; k++) d.R[k] = __longlong_as_double((long long)b[(size_t)k * n]);
 #pragma unroll
@@ -95,7 +158,83 @@ __device__ __forceinline__ void imu_ws_load(const unsigned long long* ws, int n,
     for (int k = 0; k < 9; k++) d.J[k] = __longlong_as_double((long long)b[(size_t)(16 + k) * n]);
     const unsigned long long w = b[(size_t)25 * n];
     d.n_steps = (int)(uint32_t)(w & 0xFFFFFFFFull); d.flags = (int)(uint32_t)(w >> 32);
+    if (jflags) { *jflags = (int)((uint32_t)d.flags >> 16); d.flags &= 0xFFFF; }
 }
+// block b (0 Jvg, 1 Jva, 2 Jpg, 3 Jpa) of entry i of a 62-slot table
+__device__ __forceinline__ void imu_ws_load_block(const unsigned long long* ws, int n, int level, int i, int b, double* M) {
+    const unsigned long long* p = ws + ((size_t)level * 62 + 26 + 9 * b) * n + i;
+#pragma unroll
+    for (int k = 0; k < 9; k++) M[k] = __longlong_as_double((long long)p[(size_t)k * n]);
+}
+__device__ __forceinline__ void imu_ws_store_block(unsigned long long* ws, int n, int level, int i, int b, const double* M) {
+    unsigned long long* p = ws + ((size_t)level * 62 + 26 + 9 * b) * n + i;
+#pragma unroll
+    for (int k = 0; k < 9; k++) p[(size_t)k * n] = (unsigned long long)__double_as_longlong(M[k]);
+}
+// a whole entry: the delta and, with Jacobians, the four blocks
+__device__ __forceinline__ void imu_entry_store(unsigned long long* ws, int n, int level, int i, const ImuDelta& d, const ImuNoJac&) { imu_ws_store<26>(ws, n, level, i, d); }
+__device__ __forceinline__ void imu_entry_store(unsigned long long* ws, int n, int level, int i, const ImuDelta& d, const ImuJac& q) {
+    imu_ws_store<62>(ws, n, level, i, d, q.flags);
+    imu_ws_store_block(ws, n, level, i, 0, q.vg); imu_ws_store_block(ws, n, level, i, 1, q.va);
+    imu_ws_store_block(ws, n, level, i, 2, q.pg); imu_ws_store_block(ws, n, level, i, 3, q.pa);
+}
+__device__ __forceinline__ void imu_entry_load(const unsigned long long* ws, int n, int level, int i, ImuDelta& d, ImuNoJac&) { imu_ws_load<26>(ws, n, level, i, d); }
+__device__ __forceinline__ void imu_entry_load(const unsigned long long* ws, int n, int level, int i, ImuDelta& d, ImuJac& q) {
+    imu_ws_load<62>(ws, n, level, i, d, &q.flags);
+    imu_ws_load_block(ws, n, level, i, 0, q.vg); imu_ws_load_block(ws, n, level, i, 1, q.va);
+    imu_ws_load_block(ws, n, level, i, 2, q.pg); imu_ws_load_block(ws, n, level, i, 3, q.pa);
+}
+// acc = T_k[pos] o acc.  Without Jacobians the two deltas; with them the entry's delta and flags are loaded, its blocks one at a time
+__device__ __forceinline__ void imu_entry_fold(const unsigned long long* ws, int n, int level, int pos, ImuDelta& acc, ImuNoJac&) {
+    ImuDelta e, o;
+    imu_ws_load<26>(ws, n, level, pos, e);
+    imu_compose(e, acc, o);
+    acc = o;
+}
+__device__ __forceinline__ void imu_entry_fold(const unsigned long long* ws, int n, int level, int pos, ImuDelta& acc, ImuJac& q) {
+    ImuDelta e, o;
+    int ef;
+    imu_ws_load<62>(ws, n, level, pos, e, &ef);
+    imu_compose(e, acc, o);
+    imu_jac_fold(e, ef, [&](int b, double* M) { imu_ws_load_block(ws, n, level, pos, b, M); }, acc, o.flags, q);
+    acc = o;
+}
+// acc = the carried open delta o acc
+__device__ __forceinline__ void imu_carry_load(const vis_imu_carry* carry, ImuDelta& c) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) { c.R[k] = carry->open.R[k]; c.J[k] = carry->open.JRg[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { c.v[k] = carry->open.v[k]; c.p[k] = carry->open.p[k]; }
+    c.dt = carry->open.dt; c.n_steps = carry->open.n_steps; c.flags = carry->open.flags;
+}
+__device__ __forceinline__ void imu_carry_fold(const vis_imu_carry* carry, const ImuJacIO&, ImuDelta& acc, ImuNoJac&) {
+    ImuDelta c, o;
+    imu_carry_load(carry, c);
+    imu_compose(c, acc, o);
+    acc = o;
+}
+__device__ __forceinline__ void imu_carry_fold(const vis_imu_carry* carry, const ImuJacIO& io, ImuDelta& acc, ImuJac& q) {
+    ImuDelta c, o;
+    imu_carry_load(carry, c);
+    imu_compose(c, acc, o);
+    const vis_imu_bias_jac* cj = io.cin;
+    imu_jac_fold(c, cj->flags, [&](int b, double* M) {
+        const double* src = b == 0 ? cj->Jvg : (b == 1 ? cj->Jva : (b == 2 ? cj->Jpg : cj->Jpa));
+#pragma unroll
+        for (int k = 0; k < 9; k++) M[k] = src[k];
+    }, acc, o.flags, q);
+    acc = o;
+}
+__device__ __forceinline__ void imu_jac_record(const ImuJac& q, int prev, vis_imu_bias_jac* out) {
+    vis_imu_bias_jac o;
+#pragma unroll
+    for (int k = 0; k < 9; k++) { o.Jvg[k] = q.vg[k]; o.Jva[k] = q.va[k]; o.Jpg[k] = q.pg[k]; o.Jpa[k] = q.pa[k]; }
+    o.flags = q.flags; o.q = prev;
+    *out = o;
+}
+__device__ __forceinline__ void imu_jac_record(const ImuNoJac&, int, vis_imu_bias_jac*) {}
+__device__ __forceinline__ void imu_jac_clear(ImuJac& q) { imu_jac_zero(q); q.flags = 0; }
+__device__ __forceinline__ void imu_jac_clear(ImuNoJac&) {}
 
 // ---------------------------------------------------------------------------------------------- step 1: the intervals
 struct ImuPoint { double t, w[3], a[3]; };
@@ -145,7 +284,23 @@ __device__ __forceinline__ double imu_horner(const double* c, double x) {
     for (int k = VIS_IMU_EXP_TERMS - 2; k >= 0; k--) acc = c[k] + x * acc;
     return acc;
 }
-__device__ __forceinline__ void imu_substep(ImuDelta& d, const vis_imu_params& P, const ImuPoint& s0, const ImuPoint& s1) {
+// the Jacobians' share of a sub-step, BEFORE R and JRg move on: R, J the old ones, Rn, Jn the new; p's lines use the old v Jacobians, as p uses the old v
+__device__ __forceinline__ void imu_substep_jac(ImuJac& q, const double* R, const double* J, const double* Rn, const double* Jn, const double* u0,
+                                                const double* u1, double h) {
+    double S[9], G0[9], G1[9];
+    imu_skmul(u0, J, S); imu_mul(R, S, G0);
+    imu_skmul(u1, Jn, S); imu_mul(Rn, S, G1);
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        const double Dg = -0.5 * (G0[k] + G1[k]), Da = -0.5 * (R[k] + Rn[k]);
+        q.pg[k] = q.pg[k] + (q.vg[k] * h + (0.5 * Dg) * (h * h));
+        q.vg[k] = q.vg[k] + Dg * h;
+        q.pa[k] = q.pa[k] + (q.va[k] * h + (0.5 * Da) * (h * h));
+        q.va[k] = q.va[k] + Da * h;
+    }
+}
+__device__ __forceinline__ void imu_substep_jac(ImuNoJac&, const double*, const double*, const double*, const double*, const double*, const double*, double) {}
+template <class Jac> __device__ __forceinline__ void imu_substep(ImuDelta& d, Jac& q, const vis_imu_params& P, const ImuPoint& s0, const ImuPoint& s1) {
     constexpr double cA[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_A, cB[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_B, cC[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_C;
     const double h = s1.t - s0.t;
     if (!(h > 0.0)) { d.flags |= VIS_IMU_ORDER; return; }
@@ -177,19 +332,25 @@ __device__ __forceinline__ void imu_substep(ImuDelta& d, const vis_imu_params& P
         d.v[r] = d.v[r] + am * h;
     }
     imu_tmul(dR, d.J, M);
+    double Jn[9];
 #pragma unroll
-    for (int k = 0; k < 9; k++) { d.J[k] = M[k] - Jr[k] * h; d.R[k] = Rn[k]; }
+    for (int k = 0; k < 9; k++) Jn[k] = M[k] - Jr[k] * h;
+    imu_substep_jac(q, d.R, d.J, Rn, Jn, u0, u1, h);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { d.J[k] = Jn[k]; d.R[k] = Rn[k]; }
 }
 
-__global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_intervals(vis_imu_params P, int n, const vis_imu_sample* __restrict__ samples, int n_samples,
+template <bool JAC> __global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_intervals(vis_imu_params P, int n, const vis_imu_sample* __restrict__ samples, int n_samples,
                                                                 const double* __restrict__ tframe, const vis_imu_carry* __restrict__ carry,
                                                                 unsigned long long* __restrict__ ws) {
     const int i = blockIdx.x * IMU_IV_BLOCK + threadIdx.x;
     if (i >= n) return;
     ImuDelta d;
+    typename ImuJacOf<JAC>::type q;
     imu_identity(d);
+    imu_jac_clear(q);
     const bool start = i > 0 || (carry && (carry->valid & VIS_IMU_CARRY_TIME));
-    if (!start) { d.flags = VIS_IMU_NO_START; imu_ws_store(ws, n, 0, i, d); return; }
+    if (!start) { d.flags = VIS_IMU_NO_START; imu_entry_store(ws, n, 0, i, d, q); return; }
     const double ta = i > 0 ? tframe[i - 1] : carry->t_last, tb = tframe[i];
     d.dt = tb - ta;
     if (!imu_finite(d.dt)) d.dt = 0.0;
@@ -211,27 +372,26 @@ __global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_intervals(vis_imu_params P
             ImuPoint cur = pa;
             for (int j = lo; j < hi; j++) {
                 ImuPoint s; imu_read(samples, j, s);
-                imu_substep(d, P, cur, s);
+                imu_substep(d, q, P, cur, s);
                 cur = s;
             }
-            imu_substep(d, P, cur, pb);
+            imu_substep(d, q, P, cur, pb);
         }
     }
     if (bad || !imu_all_finite(d)) imu_void(d);
-    imu_ws_store(ws, n, 0, i, d);
+    imu_jac_settle(d.flags, q);
+    imu_entry_store(ws, n, 0, i, d, q);
 }
 
 // ---------------------------------------------------------------------------------------------- step 2: the pairs
 // the composition of the L intervals that end at frame i (the set bits of L, rising; pos walks back); L >= 1
-__device__ __forceinline__ void imu_lift(const unsigned long long* ws, int n, int i, int L, ImuDelta& acc) {
+template <class Jac> __device__ __forceinline__ void imu_lift(const unsigned long long* ws, int n, int i, int L, ImuDelta& acc, Jac& q) {
     int pos = i;
     bool first = true;
     for (int k = 0; (1 << k) <= L; k++) {
         if (!(L & (1 << k))) continue;
-        ImuDelta e;
-        imu_ws_load(ws, n, k, pos, e);
-        if (first) { acc = e; first = false; }
-        else { ImuDelta o; imu_compose(e, acc, o); acc = o; }
+        if (first) { imu_entry_load(ws, n, k, pos, acc, q); first = false; }
+        else imu_entry_fold(ws, n, k, pos, acc, q);
         pos -= 1 << k;
     }
 }
@@ -243,9 +403,23 @@ __device__ __forceinline__ void imu_record(const ImuDelta& d, int q, vis_imu_del
     o.dt = d.dt; o.n_steps = d.n_steps; o.flags = d.flags; o.q = q; o.reserved_ = 0;
 }
 
-__global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis_imu_params P, int n, FtFrames fr, const double* __restrict__ tframe,
+// d_rot's rule: (float)(r_ic^T R r_ic), the identity for a frame without a delta or an entry beyond FLT_MAX
+__device__ __forceinline__ void imu_rot_row(const double* r_ic, const ImuDelta& d, float* rot) {
+    double T[9], M[9];
+    imu_tmul(r_ic, d.R, T);
+    imu_mul(T, r_ic, M);
+    bool ok = !(d.flags & (VIS_IMU_NO_PAIR | VIS_IMU_NO_CARRY | VIS_IMU_NONFINITE));
+#pragma unroll
+    for (int k = 0; k < 9; k++) ok = ok && fabs(M[k]) <= 3.4028234663852886e38;
+#pragma unroll
+    for (int k = 0; k < 9; k++) rot[k] = ok ? (float)M[k] : ((k & 3) == 0 ? 1.0f : 0.0f);
+}
+
+template <bool JAC> __global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis_imu_params P, int n, FtFrames fr, const double* __restrict__ tframe,
                                                          const vis_imu_carry* __restrict__ carry, unsigned long long* __restrict__ ws,
-                                                         vis_imu_delta* __restrict__ delta, float* __restrict__ rot, vis_imu_carry* __restrict__ carry_out) {
+                                                         vis_imu_delta* __restrict__ delta, float* __restrict__ rot, vis_imu_carry* __restrict__ carry_out,
+                                                         ImuJacIO jio) {
+    typedef typename ImuJacOf<JAC>::type Jac;
     __shared__ int s_maxL, s_last;
     const int tid = threadIdx.x;
     const bool have_carry = carry && (carry->valid & VIS_IMU_CARRY_TIME);
@@ -270,11 +444,11 @@ __global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis_imu_params P, int n
         const int half = 1 << (k - 1);
         for (int i = tid; i < n; i += IMU_BLOCK) {
             if (i < (1 << k) - 1) continue;
-            ImuDelta a, b, o;
-            imu_ws_load(ws, n, k - 1, i - half, a);
-            imu_ws_load(ws, n, k - 1, i, b);
-            imu_compose(a, b, o);
-            imu_ws_store(ws, n, k, i, o);
+            ImuDelta o;
+            Jac q;
+            imu_entry_load(ws, n, k - 1, i, o, q);
+            imu_entry_fold(ws, n, k - 1, i - half, o, q);
+            imu_entry_store(ws, n, k, i, o, q);
         }
         __syncthreads();
     }
@@ -282,77 +456,140 @@ __global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis_imu_params P, int n
     for (int i = tid; i < n; i += IMU_BLOCK) {
         const int p = imu_prev(fr, i);
         ImuDelta d;
+        Jac q;
         imu_identity(d);
+        imu_jac_clear(q);
         if (p == VIS_KF_NOT_SAVED || p == VIS_KF_FIRST) d.flags = VIS_IMU_NO_PAIR;
         else if (p == VIS_KF_CARRIED && !have_carry) d.flags = VIS_IMU_NO_CARRY;
         else {
-            imu_lift(ws, n, i, p >= 0 ? i - p : i + 1, d);
-            if (p == VIS_KF_CARRIED && (carry->valid & VIS_IMU_CARRY_OPEN)) {
-                ImuDelta c, o;
-#pragma unroll
-                for (int k = 0; k < 9; k++) { c.R[k] = carry->open.R[k]; c.J[k] = carry->open.JRg[k]; }
-#pragma unroll
-                for (int k = 0; k < 3; k++) { c.v[k] = carry->open.v[k]; c.p[k] = carry->open.p[k]; }
-                c.dt = carry->open.dt; c.n_steps = carry->open.n_steps; c.flags = carry->open.flags;
-                imu_compose(c, d, o);
-                d = o;
-            }
+            imu_lift(ws, n, i, p >= 0 ? i - p : i + 1, d, q);
+            if (p == VIS_KF_CARRIED && (carry->valid & VIS_IMU_CARRY_OPEN)) imu_carry_fold(carry, jio, d, q);
         }
         vis_imu_delta o;
         imu_record(d, p, o);
         delta[i] = o;
-        if (rot) {
-            double T[9], M[9];
-            imu_tmul(P.r_ic, d.R, T);
-            imu_mul(T, P.r_ic, M);
-            bool ok = !(d.flags & (VIS_IMU_NO_PAIR | VIS_IMU_NO_CARRY | VIS_IMU_NONFINITE));
-#pragma unroll
-            for (int k = 0; k < 9; k++) ok = ok && fabs(M[k]) <= 3.4028234663852886e38;
-#pragma unroll
-            for (int k = 0; k < 9; k++) rot[(size_t)i * 9 + k] = ok ? (float)M[k] : ((k & 3) == 0 ? 1.0f : 0.0f);
-        }
+        if (JAC) imu_jac_record(q, p, jio.rows + i);
+        if (rot) imu_rot_row(P.r_ic, d, rot + (size_t)i * 9);
     }
     // ---- the carry
     if (carry_out && tid == 0) {
         ImuDelta d;
+        Jac q;
         imu_identity(d);
+        imu_jac_clear(q);
         int valid = VIS_IMU_CARRY_TIME;
         if (Lc > 0) {
-            imu_lift(ws, n, n - 1, Lc, d);
+            imu_lift(ws, n, n - 1, Lc, d, q);
             valid |= VIS_IMU_CARRY_OPEN;
-            if (last < 0 && have_carry && (carry->valid & VIS_IMU_CARRY_OPEN)) {
-                ImuDelta c, o;
-#pragma unroll
-                for (int k = 0; k < 9; k++) { c.R[k] = carry->open.R[k]; c.J[k] = carry->open.JRg[k]; }
-#pragma unroll
-                for (int k = 0; k < 3; k++) { c.v[k] = carry->open.v[k]; c.p[k] = carry->open.p[k]; }
-                c.dt = carry->open.dt; c.n_steps = carry->open.n_steps; c.flags = carry->open.flags;
-                imu_compose(c, d, o);
-                d = o;
-            }
+            if (last < 0 && have_carry && (carry->valid & VIS_IMU_CARRY_OPEN)) imu_carry_fold(carry, jio, d, q);
         }
         vis_imu_carry co;
         co.t_last = tframe[n - 1];
         imu_record(d, 0, co.open);
         co.valid = valid; co.reserved_ = 0;
         *carry_out = co;
+        if (JAC) imu_jac_record(q, 0, jio.cout);
     }
 }
 
-size_t imu_table_bytes(int n) {
+// ---------------------------------------------------------------------------------------------- the bias correction of the records
+// One lane per frame: R' = R Exp(JRg dbg), v' = v + (Jvg dbg + Jva dba), p' = p + (Jpg dbg + Jpa dba); a record that cannot be corrected is copied
+__global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_correct(vis_imu_params P, int n, const vis_imu_delta* __restrict__ delta, const vis_imu_bias_jac* __restrict__ jac,
+                                                              const double* __restrict__ dbg, const double* __restrict__ dba, vis_imu_delta* __restrict__ out,
+                                                              float* __restrict__ rot, int32_t* __restrict__ status) {
+    constexpr double cA[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_A, cB[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_B;
+    const int i = blockIdx.x * IMU_IV_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    vis_imu_delta r = delta[i];
+    ImuDelta d;
+#pragma unroll
+    for (int k = 0; k < 9; k++) { d.R[k] = r.R[k]; d.J[k] = r.JRg[k]; }
+#pragma unroll
+    for (int k = 0; k < 3; k++) { d.v[k] = r.v[k]; d.p[k] = r.p[k]; }
+    d.dt = r.dt; d.n_steps = r.n_steps; d.flags = r.flags;
+    double bg[3], ba[3];
+    bool bfin = true;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { bg[k] = dbg[k]; ba[k] = dba ? dba[k] : 0.0; bfin = bfin && imu_finite(bg[k]) && imu_finite(ba[k]); }
+    int st = VIS_IMC_OK;
+    if ((d.flags & IMU_VOID_FLAGS) || !imu_all_finite(d)) st = VIS_IMC_UNUSABLE;
+    else if (jac[i].flags & VIS_IMU_JAC_NONFINITE) st = VIS_IMC_JAC;
+    else if (!bfin) st = VIS_IMC_BIAS;
+    else {
+        double phi[3];
+        imu_mulv(d.J, bg, phi);
+        const double xx = phi[0] * phi[0], yy = phi[1] * phi[1], zz = phi[2] * phi[2], xy = phi[0] * phi[1], xz = phi[0] * phi[2], yz = phi[1] * phi[2];
+        const double th2 = (xx + yy) + zz;
+        if (th2 > P.max_angle * P.max_angle) st = VIS_IMC_ANGLE;
+        else {
+            const double A = imu_horner(cA, th2), B = imu_horner(cB, th2);
+            const double dR[9] = {1.0 - B * (yy + zz), B * xy - A * phi[2], B * xz + A * phi[1],
+                                  B * xy + A * phi[2], 1.0 - B * (xx + zz), B * yz - A * phi[0],
+                                  B * xz - A * phi[1], B * yz + A * phi[0], 1.0 - B * (xx + yy)};
+            double Rn[9], vg[3], va[3], pg[3], pa[3], vn[3], pn[3];
+            imu_mul(d.R, dR, Rn);
+            const vis_imu_bias_jac* j = jac + i;
+            imu_mulv(j->Jvg, bg, vg); imu_mulv(j->Jva, ba, va); imu_mulv(j->Jpg, bg, pg); imu_mulv(j->Jpa, ba, pa);
+            bool fin = true;
+#pragma unroll
+            for (int k = 0; k < 3; k++) { vn[k] = d.v[k] + (vg[k] + va[k]); pn[k] = d.p[k] + (pg[k] + pa[k]); fin = fin && imu_finite(vn[k]) && imu_finite(pn[k]); }
+#pragma unroll
+            for (int k = 0; k < 9; k++) fin = fin && imu_finite(Rn[k]);
+            if (!fin) st = VIS_IMC_NONFINITE;
+            else {
+#pragma unroll
+                for (int k = 0; k < 9; k++) { d.R[k] = Rn[k]; r.R[k] = Rn[k]; }
+#pragma unroll
+                for (int k = 0; k < 3; k++) { r.v[k] = vn[k]; r.p[k] = pn[k]; }
+            }
+        }
+    }
+    out[i] = r;
+    if (status) status[i] = st;
+    if (rot) imu_rot_row(P.r_ic, d, rot + (size_t)i * 9);
+}
+
+static size_t imu_table_bytes_of(int n, int slots) {
     int levels = 1;
     while ((1 << levels) <= n) levels++;
-    return (size_t)levels * 26 * sizeof(unsigned long long) * (size_t)(n > 0 ? n : 1);
+    return (size_t)levels * slots * sizeof(unsigned long long) * (size_t)(n > 0 ? n : 1);
 }
+size_t imu_table_bytes(int n) { return imu_table_bytes_of(n, 26); }
+size_t imu_jac_table_bytes(int n) { return imu_table_bytes_of(n, 62); }
 
 int imu_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
             const vis_imu_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, float* d_rot, vis_imu_carry* d_carry_out) {
     if (n < 1) return VIS_OK;
     if (n > VIS_IMU_MAX_FRAMES || !d_ws || n_samples < 0) return VIS_E_INVALID;
-    hipLaunchKernelGGL(k_imu_intervals, dim3((n + IMU_IV_BLOCK - 1) / IMU_IV_BLOCK), dim3(IMU_IV_BLOCK), 0, ctx->stream, *ip, n, d_samples, n_samples, d_tframe,
+    hipLaunchKernelGGL(k_imu_intervals<false>, dim3((n + IMU_IV_BLOCK - 1) / IMU_IV_BLOCK), dim3(IMU_IV_BLOCK), 0, ctx->stream, *ip, n, d_samples, n_samples, d_tframe,
                        d_carry, (unsigned long long*)d_ws);
     HIPCHK(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_imu_pairs, dim3(1), dim3(IMU_BLOCK), 0, ctx->stream, *ip, n, fr, d_tframe, d_carry, (unsigned long long*)d_ws, d_delta, d_rot, d_carry_out);
+    hipLaunchKernelGGL(k_imu_pairs<false>, dim3(1), dim3(IMU_BLOCK), 0, ctx->stream, *ip, n, fr, d_tframe, d_carry, (unsigned long long*)d_ws, d_delta, d_rot, d_carry_out,
+                       ImuJacIO{nullptr, nullptr, nullptr});
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+int imu_jac_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
+                   const vis_imu_jac_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, vis_imu_bias_jac* d_jac, float* d_rot, vis_imu_jac_carry* d_carry_out) {
+    if (n < 1) return VIS_OK;
+    if (n > VIS_IMU_MAX_FRAMES || !d_ws || !d_jac || n_samples < 0) return VIS_E_INVALID;
+    const vis_imu_carry* cin = d_carry ? &d_carry->carry : nullptr;
+    vis_imu_carry* cout = d_carry_out ? &d_carry_out->carry : nullptr;
+    hipLaunchKernelGGL(k_imu_intervals<true>, dim3((n + IMU_IV_BLOCK - 1) / IMU_IV_BLOCK), dim3(IMU_IV_BLOCK), 0, ctx->stream, *ip, n, d_samples, n_samples, d_tframe,
+                       cin, (unsigned long long*)d_ws);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_imu_pairs<true>, dim3(1), dim3(IMU_BLOCK), 0, ctx->stream, *ip, n, fr, d_tframe, cin, (unsigned long long*)d_ws, d_delta, d_rot, cout,
+                       ImuJacIO{d_carry ? &d_carry->open_jac : nullptr, d_jac, d_carry_out ? &d_carry_out->open_jac : nullptr});
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+int imu_correct_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
+                       const double* d_dba, vis_imu_delta* d_out, float* d_rot, int32_t* d_status) {
+    if (n < 1) return VIS_OK;
+    hipLaunchKernelGGL(k_imu_correct, dim3((n + IMU_IV_BLOCK - 1) / IMU_IV_BLOCK), dim3(IMU_IV_BLOCK), 0, ctx->stream, *ip, n, d_delta, d_jac, d_dbg, d_dba, d_out,
+                       d_rot, d_status);
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

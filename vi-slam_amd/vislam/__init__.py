@@ -367,6 +367,23 @@ IMU_CARRY_TIME, IMU_CARRY_OPEN = 1, 2
 IMU_MAX_FRAMES = 1024
 
 
+class ImuBiasJac(C.Structure):
+    """vis_imu_bias_jac: dv / dbg, dv / dba, dp / dbg, dp / dba of a delta (3 x 3 row-major), IMU_JAC_* flags, the delta's q"""
+    _fields_ = [("Jvg", C.c_double * 9), ("Jva", C.c_double * 9), ("Jpg", C.c_double * 9), ("Jpa", C.c_double * 9), ("flags", C.c_int32), ("q", C.c_int32)]
+
+
+class ImuJacCarry(C.Structure):
+    """vis_imu_jac_carry as a host structure (vis_batch_imu_jac_init): vis_imu_carry and the Jacobians of its open delta"""
+    _fields_ = [("carry", ImuCarry), ("open_jac", ImuBiasJac)]
+
+
+IMU_BIAS_JAC_DTYPE = np.dtype([("Jvg", "<f8", (9,)), ("Jva", "<f8", (9,)), ("Jpg", "<f8", (9,)), ("Jpa", "<f8", (9,)), ("flags", "<i4"), ("q", "<i4")])
+IMU_JAC_CARRY_DTYPE = np.dtype([("carry", IMU_CARRY_DTYPE), ("open_jac", IMU_BIAS_JAC_DTYPE)])
+assert IMU_BIAS_JAC_DTYPE.itemsize == 296 == C.sizeof(ImuBiasJac) and IMU_JAC_CARRY_DTYPE.itemsize == 528 == C.sizeof(ImuJacCarry)
+IMU_JAC_OK, IMU_JAC_NONFINITE = 0, 1
+IMC_OK, IMC_UNUSABLE, IMC_JAC, IMC_BIAS, IMC_ANGLE, IMC_NONFINITE = 0, 1, 2, 4, 8, 16
+
+
 class ViAlignParams(C.Structure):
     """vis_vi_align_params (vis_default_vi_align_params: identity, 0, 9.81, 0.1, 8, 8, 4, IMU_EMPTY | IMU_GAP)"""
     _fields_ = [("r_ic", C.c_double * 9), ("p_ci", C.c_double * 3), ("G", C.c_double), ("g_tol", C.c_double), ("min_pairs", C.c_int32),
@@ -457,6 +474,8 @@ ABI_SYMBOLS = [
     "vis_default_scale_link_params", "vis_scale_link_rows", "vis_batch_scale_links", "vis_trajectory_rows", "vis_batch_trajectory",
     "vis_batch_trajectory_init",
     "vis_default_imu_params", "vis_imu_preintegrate", "vis_imu_preintegrate_rows", "vis_batch_imu", "vis_batch_imu_init",
+    "vis_imu_preintegrate_jac", "vis_imu_preintegrate_jac_rows", "vis_batch_imu_jac", "vis_batch_imu_jac_init", "vis_imu_correct_rows",
+    "vis_batch_imu_correct",
     "vis_default_vi_align_params", "vis_vi_align_rows", "vis_batch_vi_align", "vis_batch_vi_align_init",
 ]
 
@@ -569,6 +588,14 @@ def _load():
         lib.vis_imu_preintegrate_rows.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
         lib.vis_batch_imu.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp]
         lib.vis_batch_imu_init.argtypes = [vp, C.POINTER(ImuCarry)]
+    if hasattr(lib, "vis_batch_imu_jac"):               # (absent from older A/B builds)
+        imp = C.POINTER(ImuParams)
+        lib.vis_imu_preintegrate_jac.argtypes = [vp, imp, vp, ci, C.c_double, C.c_double, C.POINTER(ImuDelta), C.POINTER(ImuBiasJac), vp]
+        lib.vis_imu_preintegrate_jac_rows.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_imu_jac.argtypes = [vp, imp, ci, vp, ci, vp, vp, vp, vp]
+        lib.vis_batch_imu_jac_init.argtypes = [vp, C.POINTER(ImuJacCarry)]
+        lib.vis_imu_correct_rows.argtypes = [vp, imp, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_imu_correct.argtypes = [vp, imp, ci, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "vis_batch_vi_align"):              # (absent from older A/B builds)
         vap = C.POINTER(ViAlignParams)
         lib.vis_default_vi_align_params.argtypes = [vap]
@@ -1606,6 +1633,52 @@ class Context:
         if rec is not None and not isinstance(rec, ImuCarry):
             rec = ImuCarry.from_buffer_copy(np.asarray(rec, IMU_CARRY_DTYPE).tobytes())
         self._chk(lib.vis_batch_imu_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_imu_init")
+
+    # -- the same with the bias Jacobians of v and p, and the first-order bias correction of the records ----------------
+    def imu_preintegrate_jac(self, samples, t_a, t_b, ip=None):
+        """imu_preintegrate with the Jacobians: (an IMU_DELTA_DTYPE record, an IMU_BIAS_JAC_DTYPE record, the 3 x 3 float32 rotation); blocks"""
+        ip = default_imu_params() if ip is None else ip
+        s = np.ascontiguousarray(samples, IMU_SAMPLE_DTYPE)
+        d, j, rot = ImuDelta(), ImuBiasJac(), np.zeros(9, np.float32)
+        self._chk(lib.vis_imu_preintegrate_jac(self._h, C.byref(ip), C.c_void_p(s.ctypes.data) if len(s) else None, len(s), t_a, t_b, C.byref(d), C.byref(j),
+                                               C.c_void_p(rot.ctypes.data)), "vis_imu_preintegrate_jac")
+        return np.frombuffer(bytes(d), IMU_DELTA_DTYPE)[0], np.frombuffer(bytes(j), IMU_BIAS_JAC_DTYPE)[0], rot.reshape(3, 3)
+
+    def imu_preintegrate_jac_rows(self, n, d_samples_ptr, n_samples, d_tframe_ptr, d_prev_ptr, d_delta_ptr, d_jac_ptr, d_rot_ptr=0, d_carry_in_ptr=0,
+                                  d_carry_out_ptr=0, ip=None):
+        """imu_preintegrate_rows with n IMU_BIAS_JAC_DTYPE records beside the deltas and IMU_JAC_CARRY_DTYPE carries (raw DEVICE pointers)"""
+        ip = default_imu_params() if ip is None else ip
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_imu_preintegrate_jac_rows(self._h, C.byref(ip), n, v(d_samples_ptr), n_samples, v(d_tframe_ptr), v(d_prev_ptr), v(d_carry_in_ptr),
+                                                    v(d_delta_ptr), v(d_jac_ptr), v(d_rot_ptr), v(d_carry_out_ptr)), "vis_imu_preintegrate_jac_rows")
+
+    def batch_imu_jac(self, n, d_samples_ptr, n_samples, d_tframe_ptr, d_delta_ptr, d_jac_ptr, d_rot_ptr=0, ip=None):
+        """batch_imu with the Jacobians, on the pose stream, with carried records of its own.  The buffers are in use until batch_sync()"""
+        ip = default_imu_params() if ip is None else ip
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_imu_jac(self._h, C.byref(ip), n, v(d_samples_ptr), n_samples, v(d_tframe_ptr), v(d_delta_ptr), v(d_jac_ptr), v(d_rot_ptr)),
+                  "vis_batch_imu_jac")
+
+    def batch_imu_jac_init(self, rec=None):
+        """the carry (an IMU_JAC_CARRY_DTYPE element or an ImuJacCarry; None: none) the next run's batch_imu_jac continues from; synchronises"""
+        if rec is not None and not isinstance(rec, ImuJacCarry):
+            rec = ImuJacCarry.from_buffer_copy(np.asarray(rec, IMU_JAC_CARRY_DTYPE).tobytes())
+        self._chk(lib.vis_batch_imu_jac_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_imu_jac_init")
+
+    def imu_correct_rows(self, n, d_delta_ptr, d_jac_ptr, d_dbg_ptr, d_delta_out_ptr, d_dba_ptr=0, d_rot_out_ptr=0, d_status_ptr=0, ip=None):
+        """queue the first-order correction of n records for a bias step on the context's stream (raw DEVICE pointers): d_dbg three doubles (the head
+        of a VI_ALIGN_DTYPE record will do), d_dba three doubles or NULL; n corrected IMU_DELTA_DTYPE records, n x 9 float32 rotations, n int32 IMC_*"""
+        ip = default_imu_params() if ip is None else ip
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_imu_correct_rows(self._h, C.byref(ip), n, v(d_delta_ptr), v(d_jac_ptr), v(d_dbg_ptr), v(d_dba_ptr), v(d_delta_out_ptr),
+                                           v(d_rot_out_ptr), v(d_status_ptr)), "vis_imu_correct_rows")
+
+    def batch_imu_correct(self, n, d_delta_ptr, d_jac_ptr, d_dbg_ptr, d_delta_out_ptr, d_dba_ptr=0, d_rot_out_ptr=0, d_status_ptr=0, ip=None):
+        """the same for the frames of the last batch_run on the pose stream, behind batch_vi_align, whose d_result it may read as d_dbg"""
+        ip = default_imu_params() if ip is None else ip
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_imu_correct(self._h, C.byref(ip), n, v(d_delta_ptr), v(d_jac_ptr), v(d_dbg_ptr), v(d_dba_ptr), v(d_delta_out_ptr),
+                                            v(d_rot_out_ptr), v(d_status_ptr)), "vis_batch_imu_correct")
 
     # -- visual-inertial alignment: gyro bias, gravity, metric scale, velocities ---------------------------------------
     def vi_align_rows(self, n, d_prev_ptr, d_traj_ptr, d_delta_ptr, d_result_ptr, d_state_ptr=0, d_carry_in_ptr=0, d_carry_out_ptr=0, vp=None):
