@@ -1713,11 +1713,12 @@ int  vis_imu_correct_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const v
 /* The same for the frames of the last vis_batch_run, on the POSE stream through the follow-up scaffold: queued behind vis_batch_vi_align, it reads
  * that call's d_result as d_dbg, and a second vis_batch_vi_align queued behind it reads d_delta_out -- align, correct, align again with no host step.
  * (The second alignment of a run is a repeated call: it reads the carry the first one read.)  The caller's buffers are in use until vis_batch_sync.
+ * Behind vis_batch_vi_align_ba, d_dbg = d_result and d_dba = &d_result->dba (byte 160 of that record) pass both estimated steps the same way.
  * Refusals as above; VIS_E_STATE: no context / plan / match stage, or n differs. */
 int  vis_batch_imu_correct(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
                            const double* d_dba, vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status);
-/* Out of scope: the accelerometer-bias ESTIMATE (the Jacobians it needs are here; the estimator is not), covariance propagation, the host adapters' IMU
- * arguments, a guided run with the gate on. */
+/* Out of scope: covariance propagation, the host adapters' IMU arguments, a guided run with the gate on.  (The accelerometer-bias estimate that reads
+ * Jva and Jpa is vis_batch_vi_align_ba.) */
 
 /* ---- visual-inertial alignment: the gyro bias, gravity in the root's frame, the factor from trajectory units to metres and a velocity per frame,
  * from the records of vis_batch_trajectory and vis_batch_imu (after Mur-Artal & Tardos 2017 and Qin et al. 2018, restated from the equations; the
@@ -1823,10 +1824,89 @@ int  vis_batch_vi_align(vis_ctx* ctx, const vis_vi_align_params* vp, int n, cons
 /* The carry the NEXT run's vis_batch_vi_align continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_imu_init.
  * VIS_E_STATE without a context or plan. */
 int  vis_batch_vi_align_init(vis_ctx* ctx, const vis_vi_carry* rec);
-/* Out of scope: the accelerometer bias (its estimator; the bias Jacobians of v and p it needs are vis_imu_bias_jac); this call does not correct dv
+/* Out of scope: this call does not estimate the accelerometer bias (vis_vi_align_ba_rows / vis_batch_vi_align_ba below do) and does not correct dv
  * and dp for dbg itself (vis_batch_imu_correct does, from d_result, and a second call of this one reads the corrected records; or pass bg + dbg to
  * the next vis_batch_imu); covariances or weights; feeding anything back into the trajectory, vis_batch_track or vis_batch_pnp.
  * There is no host-pointer single form: one interval aligns nothing. */
+
+/* ---- visual-inertial alignment WITH THE ACCELEROMETER BIAS: the sibling of the block above that also solves for the step dba of the accelerometer
+ * bias (Mur-Artal & Tardos 2017, step 3, restated from the equations), from the same records and the Jacobian records of vis_batch_imu_jac.
+ * tests/vi_align_ba_ref.py restates every operation below and every record equals it byte for byte; arithmetic, products, a.b, finite() and contract
+ * "T" as above.  THE EMBEDDED RECORD `a`, and the embedded carry, EQUAL vis_vi_align_rows' BYTE FOR BYTE on every input (d_carry_in's `carry` in the
+ * place of its d_carry_in): the same terms over all pairs and triples, the same contract, the same solves; nothing below changes them.
+ * A Jacobian record is USABLE beside its delta when its flags lack VIS_IMU_JAC_NONFINITE, its 36 numbers are finite and its q equals the delta's q.
+ * The Jacobian record of the carried frame is the carry's last_jac beside last_delta.  A BIAS TRIPLE is a triple a -> b -> c of step 2 above (its
+ * eleven terms finite) whose two Jacobian records, b's and c's, are usable and whose 32 terms below are finite.  With lam, beta, gam, d1, d2 of step
+ * 2 above, Jpa_c of c's record, Jpa_b and Jva_b of b's, (X Y)[3r + c] = (X[3r] Y[c] + X[3r + 1] Y[3 + c]) + X[3r + 2] Y[6 + c], and k = 0 ... 8:
+ *   B[k] = ((Rw_b Jpa_c)[k] dt1 - (Rw_a Jpa_b)[k] dt2) + (Rw_a Jva_b)[k] (dt1 dt2);   nB[k] = -B[k];
+ *   lam s + beta g + nB dba = gam                      (x = (s, g, dba), 7 unknowns, A = [lam | beta I | nB]);
+ * dba is the step vis_imu_correct_rows applies (v + Jva dba, p + Jpa dba).  (nB^T v)[c] = (nB[c] v[0] + nB[3 + c] v[1]) + nB[6 + c] v[2].  The 32 TERMS,
+ * in the order of the carried `ba`: [0] lam.lam; [1 + c] lam[c] beta; [4] beta beta; [5 + c] (nB^T lam)[c]; [8 + k] beta nB[k]; [17 ...] (nB^T nB)[a][b] =
+ * (nB[a] nB[b] + nB[3 + a] nB[3 + b]) + nB[6 + a] nB[6 + b] for a <= b in row order (6); [23] lam.gam; [24 + r] beta gam[r]; [27 + c] (nB^T gam)[c];
+ * [30] gam.gam; [31] the excitation scale d1.d1 + d2.d2.  They are summed over the bias triples of the call under contract T, apart from the 11 sums
+ * of step 2; a total is carried + call, the carried first, and the carried ones count under the rule of the linear sums ((S, E) of the carry).  Totals
+ * that are not all finite become zero sums and a zero count with VIS_VIAB_UNOBSERVABLE.  M7 (7 x 7, symmetric): [0][0] = ba[0]; [0][1 + c] = ba[1 + c];
+ * [1 + r][1 + c] = ba[4] when r == c, else +0.0; [0][4 + c] = ba[5 + c]; [1 + r][4 + c] = ba[8 + 3r + c]; [4 + a][4 + b] = ba[17 ...]; r7 = ba[23 ... 29].
+ * SOLVE.  n_ba_triples < min_ba_triples: VIS_VIAB_FEW.  Else M7 x = r7 by the LDL^T above WITH THE RELATIVE PIVOT TEST: a D[j] that is not finite, not
+ * > 0 or not > pivot_rel A[j][j] fails (under a rotation about one fixed axis the bias along the axis is a copy of a gravity column, D[6] / M7[6][6]
+ * is rounding noise of either sign, and D > 0 alone lets it through).  A failure, ba[0] not > VIS_VIA_EXCITATION_REL ba[31], or a
+ * sqrt(x[1...3].x[1...3]) that is not finite: VIS_VIAB_UNOBSERVABLE and s_lin7, g_lin7, g_lin7_norm, dba_lin report 0; else they are x[0], x[1 ... 3],
+ * that norm and x[4 ... 6]; s_lin7 not > 0: VIS_VIAB_SCALE.  Then refine_iters rounds of step 3 above with the bias columns appended, from gh = g_lin7 /
+ * g_lin7_norm, s = s_lin7, dba = dba_lin: k, d, b1, b2, x0 as there; rr[i] = r7[i] - ((M7[i][1] x0[0] + M7[i][2] x0[1]) + M7[i][3] x0[2]), i = 0 ... 6;
+ * q = (rr[0], b1.rr[1...3], b2.rr[1...3], rr[4], rr[5], rr[6]); w1[i] = M7[1 + i][1...3].b1, w2 alike; N (6 x 6, symmetric): [0][0] = M7[0][0], [0][1] =
+ * M7[0][1...3].b1, [0][2] = M7[0][1...3].b2, [1][1] = b1.w1, [1][2] = b1.w2, [2][2] = b2.w2, [0][3 + c] = M7[0][4 + c], [1][3 + c] = b1.(M7[1][4 + c],
+ * M7[2][4 + c], M7[3][4 + c]), [2][3 + c] the same with b2, [3 + a][3 + c] = M7[4 + a][4 + c]; N y = q by the same LDL^T with the same pivot test;
+ * g[j] = (x0[j] + y[1] b1[j]) + y[2] b2[j]; gh = g / sqrt(g.g); s = y[0]; dba = y[3 ... 5].  A failed solve, a norm that is not finite and > 0, or a G gh
+ * or dba that is not finite: VIS_VIAB_UNOBSERVABLE; s not finite and > 0: VIS_VIAB_SCALE.
+ * REPORTED: s_ba = s, g_ba = G gh, dba.  FALLBACK: with any of VIS_VIAB_FEW | UNOBSERVABLE | SCALE, dba = 0, s_ba and g_ba are a.s and a.g, rms_ba = 0 and
+ * the states are vis_vi_align_rows' byte for byte -- a correction queued behind a failed estimate changes nothing.  No NaN or infinity reaches a
+ * record or a carry.
+ * STATES without a fallback: those of step 4 above under (s_ba, g_ba), with dv[k] + (Jva dba)[k] and dp[k] + (Jpa dba)[k] of the frame's own Jacobian
+ * record in the place of dv and dp, VIS_VIS_HAS_V only where that record is usable; VIS_VIS_HAS_TRIPLE and res for the BIAS triples, rho[r] = ((lam[r] s_ba
+ * + beta g_ba[r]) + (nB dba)[r]) - gam[r] (which is - (B dba)[r], the same bits); rms_ba = sqrt(sum rho.rho / n_ba_triples_call).
+ * CARRY: vis_vi_align_rows' carry, the 32 totals and their count, and the Jacobian record of last_delta where both are usable, else (and with no
+ * saved frame and no carry) a zero record with VIS_IMU_JAC_NONFINITE; a call that saved nothing passes last_jac through.  The bias part of a carry
+ * counts when the embedded carry counts and its 32 + 36 numbers are finite; else it is ignored -- no carried sums, a last_jac that is not usable --
+ * with VIS_VIAB_BAD_CARRY.
+ * THE CHAIN: dba is at byte 160 of the result, dbg at byte 0, so vis_batch_imu_jac -> vis_batch_vi_align_ba -> vis_batch_imu_correct(d_dbg = d_result,
+ * d_dba = &d_result->dba) -> vis_batch_vi_align_ba on the corrected records queues with no host step.
+ * On the device: k_via_align<true>, the sibling's ONE launch of one workgroup of 256 threads with the bias sums as a pass of their own between its
+ * sums and its solves; no workspace, tails recomputed; k_via_align<false> is the sibling as it was. */
+enum { VIS_VIAB_OK = 0, VIS_VIAB_FEW = 1, VIS_VIAB_UNOBSERVABLE = 2, VIS_VIAB_SCALE = 4, VIS_VIAB_BAD_CARRY = 8 };
+enum { VIS_VIAB_SUMS = 32 };
+#define VIS_VIAB_PIVOT_REL 9.313225746154785e-10           /* 2^-30: between the pivot ratios of one-axis (1e-16) and two-axis (> 1e-6) rotations */
+typedef struct vis_vi_align_ba_params {  /* 32 bytes */
+    double  pivot_rel;                   /* VIS_VIAB_PIVOT_REL   a pivot not > pivot_rel times its diagonal entry fails; finite, 0 <= pivot_rel < 1 */
+    int32_t min_ba_triples;              /* 16            >= 1 */
+    int32_t reserved_[5];                /* 0 */
+} vis_vi_align_ba_params;
+typedef struct vis_vi_align_ba {         /* 304 bytes; dba at byte 160 */
+    vis_vi_align a;                      /* vis_vi_align_rows' record of the same inputs */
+    double  dba[3], s_ba, g_ba[3], dba_lin[3], s_lin7, g_lin7[3], g_lin7_norm, rms_ba;
+    int32_t n_ba_triples, n_ba_triples_call, ba_flags, reserved_;
+} vis_vi_align_ba;
+typedef struct vis_vi_ba_carry {         /* 1280 bytes */
+    vis_vi_carry carry;
+    double  ba[VIS_VIAB_SUMS];
+    int32_t n_ba_triples, reserved_;
+    vis_imu_bias_jac last_jac;           /* of carry.last_delta */
+} vis_vi_ba_carry;
+void vis_default_vi_align_ba_params(vis_vi_align_ba_params* bp);
+/* vis_vi_align_rows with d_jac (n records) beside d_delta.  Refusals in the sibling's order and codes: VIS_E_INVALID for vp or bp NULL or out of
+ * range; a NULL d_prev, d_traj, d_delta, d_jac or d_result; a pointer that is not aligned (8 bytes; d_prev 4); n negative; d_carry_out equal to
+ * d_carry_in and not NULL.  VIS_E_STATE without a context.  VIS_E_CAPACITY when n > VIS_VIA_MAX_FRAMES. */
+int  vis_vi_align_ba_rows(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_vi_align_ba_params* bp, int n, const int32_t* d_prev,
+                          const vis_traj_pose* d_traj, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const vis_vi_ba_carry* d_carry_in,
+                          vis_vi_state* d_state, vis_vi_align_ba* d_result, vis_vi_ba_carry* d_carry_out);
+/* vis_batch_vi_align with d_jac, on the POSE stream through the follow-up scaffold, behind vis_batch_trajectory and vis_batch_imu_jac of the run, with
+ * TWO carried vis_vi_ba_carry records of its own under the same turn rule -- apart from vis_batch_vi_align's, so that either may be called for a run,
+ * or both.  &d_result->dba is a valid d_dba of vis_batch_imu_correct (THE CHAIN above).  Refusals in vis_batch_vi_align's order and codes. */
+int  vis_batch_vi_align_ba(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_vi_align_ba_params* bp, int n, const vis_traj_pose* d_traj,
+                           const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, vis_vi_state* d_state, vis_vi_align_ba* d_result);
+/* The carry the NEXT run's vis_batch_vi_align_ba continues from (rec NULL: none).  HOST pointer; SYNCHRONISES.  VIS_E_STATE without a context or plan. */
+int  vis_batch_vi_align_ba_init(vis_ctx* ctx, const vis_vi_ba_carry* rec);
+/* Out of scope: folding dbg into dv and dp inside the same call (the queued correct -> align_ba does that); covariances and weights; a prior on the
+ * bias; feeding the result back into the trajectory, vis_batch_track or PnP; more than 1024 frames per call; a host-pointer single form. */
 
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */

@@ -65,6 +65,11 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
   --recorrect: with --vi-align and --imu-jac, close the loop on the device: align, correct the batch's deltas for the estimated gyro bias
              (vis_batch_imu_correct reads dbg from the alignment's record), align again on the corrected records.  The states and the JSON record are
              the second alignment's; the JSON line adds the first alignment's dbg, c0_call and c1 and the number of records corrected in the last batch.
+  --vi-align-ba out.csv: with --imu, --imu-jac and --trajectory, the alignment that also estimates the accelerometer-bias step (vis_batch_vi_align_ba
+             behind vis_batch_trajectory and vis_batch_imu_jac, default parameters, its own carried sums).  One row per frame as for --vi-align, under
+             (s_ba, g_ba, dba); the JSON line carries the LAST batch's record: ba_flags (VIS_VIAB_*), flags, pairs, bias triples, dbg, dba, s_ba, g_ba,
+             rms_ba.  With --recorrect the correction reads dbg AND dba from the first alignment's record and the second alignment is this call again;
+             the JSON line adds dbg_first and dba_first.
   --rectify CALIB.xml: undistort every batch on the device before vis_batch_run (vi::CameraModel, src/CameraModel.cpp:84-105: the
              calibration's in/out_width/height, calibration_values and rectification; K' = getOptimalNewCameraMatrix(alpha = 1)):
              raw frames -> device -> vis_rectify_batch -> the out_width x out_height image, or its window --roi x1,y1,x2,y2
@@ -134,6 +139,7 @@ def main():
     ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
     ap.add_argument("--imu-jac", default=None, metavar="CSV", help="with --imu: write every frame's bias Jacobians of v and p here")
     ap.add_argument("--recorrect", action="store_true", help="with --vi-align and --imu-jac: align, correct the deltas for dbg, align again")
+    ap.add_argument("--vi-align-ba", default=None, metavar="CSV", help="with --imu, --imu-jac and --trajectory: align with the accelerometer bias; states here")
     ap.add_argument("--vi-align", default=None, metavar="CSV", help="with --imu and --trajectory: gyro bias, gravity, metric scale; one state per frame here")
     ap.add_argument("--K", default="458.654,457.296,367.215,248.375", help="fx,fy,cx,cy of the alignment (--track); default EuRoC cam0")
     ap.add_argument("--rectify", default=None, metavar="CALIB.xml", help="undistort on the device with this reference-format calibration")
@@ -232,8 +238,17 @@ def main():
             torch.cuda.synchronize()
     if a.imu_jac and not a.imu:
         raise SystemExit("--imu-jac needs --imu")
-    if a.recorrect and not (a.vi_align and a.imu_jac):
+    if a.recorrect and not ((a.vi_align or a.vi_align_ba) and a.imu_jac):
         raise SystemExit("--recorrect needs --vi-align and --imu-jac")
+    if a.vi_align_ba:
+        if not (a.imu and a.imu_jac and a.trajectory):
+            raise SystemExit("--vi-align-ba needs --imu-jac and --trajectory")
+        d_bstate, d_bres, d_bres1 = (torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for nbytes in (B * 64, 304, 304))
+        torch.cuda.synchronize()
+        viab_rows, viab_last = [], None
+        if a.recorrect:
+            d_bdelta2, d_bstatus = (torch.zeros(nbytes, dtype=torch.uint8, device="cuda") for nbytes in (B * 216, B * 4))
+            torch.cuda.synchronize()
     if a.vi_align:
         if not (a.imu and a.trajectory):
             raise SystemExit("--vi-align needs --imu and --trajectory")
@@ -357,6 +372,13 @@ def main():
             ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta2.data_ptr(), d_vres.data_ptr(), d_vstate.data_ptr())
         elif a.vi_align:                                     # behind the trajectory and the deltas of the batch, on the same stream
             ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_vres.data_ptr(), d_vstate.data_ptr())
+        if a.vi_align_ba and a.recorrect:                    # align_ba -> correct by the record's dbg and dba -> align_ba again: queued, no host step
+            ctx.batch_vi_align_ba(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_ijac.data_ptr(), d_bres1.data_ptr(), d_bstate.data_ptr())
+            ctx.batch_imu_correct(nb, d_idelta.data_ptr(), d_ijac.data_ptr(), d_bres1.data_ptr(), d_bdelta2.data_ptr(),
+                                  d_bres1.data_ptr() + vislam.VI_ALIGN_BA_DBA_OFFSET, 0, d_bstatus.data_ptr())
+            ctx.batch_vi_align_ba(nb, d_jtraj.data_ptr(), d_bdelta2.data_ptr(), d_ijac.data_ptr(), d_bres.data_ptr(), d_bstate.data_ptr())
+        elif a.vi_align_ba:
+            ctx.batch_vi_align_ba(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_ijac.data_ptr(), d_bres.data_ptr(), d_bstate.data_ptr())
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -436,6 +458,12 @@ def main():
             if a.recorrect:
                 via_first = d_vres1.cpu().numpy().view(vislam.VI_ALIGN_DTYPE)[0].copy()
                 via_corrected = int((d_istatus.cpu().numpy().view(np.int32)[:nb] == vislam.IMC_OK).sum())
+        if a.vi_align_ba:
+            bst, viab_last = d_bstate.cpu().numpy().view(vislam.VI_STATE_DTYPE), d_bres.cpu().numpy().view(vislam.VI_ALIGN_BA_DTYPE)[0].copy()
+            viab_rows += [(first + i, stamps[first + i], bst[i].copy()) for i in range(nb)]
+            if a.recorrect:
+                viab_first = d_bres1.cpu().numpy().view(vislam.VI_ALIGN_BA_DTYPE)[0].copy()
+                viab_corrected = int((d_bstatus.cpu().numpy().view(np.int32)[:nb] == vislam.IMC_OK).sum())
         if a.tracks:
             tobs = d_tobs.cpu().numpy().view(vislam.FTRACK_OBS_DTYPE).reshape(B, tcap)
             tfr = d_tframe.cpu().numpy().view(vislam.FTRACK_FRAME_DTYPE)
@@ -580,6 +608,20 @@ def main():
             if a.recorrect:
                 out["recorrect"] = dict(dbg_first=[float(v) for v in via_first["dbg"]], c0_call_first=float(via_first["c0_call"]),
                                         c1_first=float(via_first["c1"]), c0_call=float(via_last["c0_call"]), corrected_in_the_last_batch=via_corrected)
+    if a.vi_align_ba:
+        with open(a.vi_align_ba, "w") as f:                     # frame, stamp, flags, q, res, p, v
+            for fi, ts, r in viab_rows:
+                f.write("%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"]) + ",".join("%.17g" % v for v in [r["res"]] + list(r["p"]) + list(r["v"])) + "\n")
+        out["vi_align_ba_csv"] = a.vi_align_ba
+        if viab_last is not None:
+            r = viab_last
+            out["vi_align_ba"] = dict(ba_flags=int(r["ba_flags"]), flags=int(r["a"]["flags"]), pairs=int(r["a"]["n_pairs"]), bias_triples=int(r["n_ba_triples"]),
+                                      dbg=[float(v) for v in r["a"]["dbg"]], dba=[float(v) for v in r["dba"]], s_ba=float(r["s_ba"]),
+                                      g_ba=[float(v) for v in r["g_ba"]], rms_ba=float(r["rms_ba"]))
+            if a.recorrect:
+                rc = dict(dbg_first=[float(v) for v in viab_first["a"]["dbg"]], dba_first=[float(v) for v in viab_first["dba"]],
+                          corrected_in_the_last_batch=viab_corrected)
+                out["recorrect"] = dict(out.get("recorrect", {}), **rc)
     if a.tracks:
         with open(a.tracks, "w") as f:                         # frame, stamp, the vis_ftrack_frame fields, the histogram of len over TRACK_BINS
             for r in track_rows:

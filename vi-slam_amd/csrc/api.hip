@@ -273,7 +273,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_imuj_ws); F(pl->d_via_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_imuj_ws); F(pl->d_via_ws); F(pl->d_viab_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1275,6 +1275,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     ctx->batch->imuj.forget();                                     // vis_batch_imu_jac: the same
     ctx->batch->imu.forget();                                      // vis_batch_imu: no carried time, no open delta
     ctx->batch->via.forget();                                      // vis_batch_vi_align: no carried sums, no tails
+    ctx->batch->viab.forget();                                     // vis_batch_vi_align_ba: the same
     ctx->batch->run_seq = ctx->batch->track_seq = 0;              // vis_batch_track: the chain restarts at vis_batch_track_init's pose
     { const int rc = reset_track_state(ctx, ctx->batch, false); if (rc) return rc; }
     if (ctx->batch->speculate) {                                   // a new stream: no prediction
@@ -1870,7 +1871,7 @@ extern "C" int vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     return pnp_batch_run(ctx, pp, n, max_pts, d_X, x_stride, d_xy, d_npts, d_draws, row_cap, d_mask, d_out);
 }
 
-// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_imuj_ws, d_via_ws), in ONE place: the list is measured and the block allocated by the
+// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_imuj_ws, d_via_ws, d_viab_ws), in ONE place: the list is measured and the block allocated by the
 // first call of the plan that needs it; every call binds the list to the block, into a work struct of its own.  The block is never replaced.
 template <class Layout> static int plan_block(vis_ctx* ctx, void*& block, const char* who, Layout&& layout) {
     if (!block) {
@@ -2479,6 +2480,75 @@ extern "C" int vis_batch_vi_align_init(vis_ctx* ctx, const vis_vi_carry* rec) {
     if (!rec) { pl->via.forget(); return VIS_OK; }
     HIPCHK(ctx, hipMemcpy(W.carry[pl->via.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
     pl->via.seeded(pl->run_count);
+    return VIS_OK;
+}
+
+// ---- visual-inertial alignment with the accelerometer bias: k_via_align<true>
+extern "C" void vis_default_vi_align_ba_params(vis_vi_align_ba_params* bp) {
+    if (!bp) return;
+    bp->pivot_rel = VIS_VIAB_PIVOT_REL; bp->min_ba_triples = 16;
+    for (int k = 0; k < 5; k++) bp->reserved_[k] = 0;
+}
+
+static bool vi_align_ba_params_ok(const vis_vi_align_ba_params* bp) {
+    return bp && std::isfinite(bp->pivot_rel) && bp->pivot_rel >= 0.0 && bp->pivot_rel < 1.0 && bp->min_ba_triples >= 1;
+}
+
+extern "C" int vis_vi_align_ba_rows(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_vi_align_ba_params* bp, int n, const int32_t* d_prev,
+                                    const vis_traj_pose* d_traj, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac,
+                                    const vis_vi_ba_carry* d_carry_in, vis_vi_state* d_state, vis_vi_align_ba* d_result, vis_vi_ba_carry* d_carry_out) {
+    if (!vi_align_params_ok(vp) || !vi_align_ba_params_ok(bp) || !d_prev || !d_traj || !d_delta || !d_jac || !d_result) return VIS_E_INVALID;
+    if (!aligned(d_traj, 8) || !aligned(d_delta, 8) || !aligned(d_jac, 8) || !aligned(d_carry_in, 8) || !aligned(d_state, 8) || !aligned(d_result, 8) ||
+        !aligned(d_carry_out, 8) || !aligned(d_prev, 4)) return VIS_E_INVALID;
+    if (n < 0 || (d_carry_out && d_carry_out == d_carry_in)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_vi_align_ba_rows: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return via_ba_launch(ctx, vp, bp, n, FtFrames{d_prev, 0, nullptr}, d_traj, d_delta, d_jac, d_carry_in, d_state, d_result, d_carry_out);
+}
+
+// the plan's block: the two carried records
+struct ViabPlanWork { vis_vi_ba_carry* carry[2]; };
+static int ensure_viab(vis_ctx* ctx, Plan* pl, ViabPlanWork& W) {
+    return plan_block(ctx, pl->d_viab_ws, "vis_batch_vi_align_ba",
+                      [&](Carver& cv) { W.carry[0] = cv.take<vis_vi_ba_carry>(1); W.carry[1] = cv.take<vis_vi_ba_carry>(1); });
+}
+
+extern "C" int vis_batch_vi_align_ba(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_vi_align_ba_params* bp, int n, const vis_traj_pose* d_traj,
+                                     const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, vis_vi_state* d_state, vis_vi_align_ba* d_result) {
+    if (!vi_align_params_ok(vp) || !vi_align_ba_params_ok(bp) || !d_traj || !d_delta || !d_jac || !d_result) return VIS_E_INVALID;
+    if (!aligned(d_traj, 8) || !aligned(d_delta, 8) || !aligned(d_jac, 8) || !aligned(d_state, 8) || !aligned(d_result, 8) || n < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_vi_align_ba: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_batch_vi_align_ba: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    ViabPlanWork W;
+    { const int rc = ensure_viab(ctx, pl, W); if (rc) return rc; }
+    const Turn::Pick rec = pl->viab.pick(pl->run_count);
+    // on the pose stream behind vis_batch_trajectory and vis_batch_imu_jac (or vis_batch_imu_correct) of the run, which wrote d_traj, d_delta and d_jac there
+    const int rc = batch_epi(ctx, n, "vis_batch_vi_align_ba", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = via_ba_launch(ctx, vp, bp, n, plan_frames(pl_), d_traj, d_delta, d_jac, rec.have ? W.carry[rec.slot] : nullptr, d_state, d_result,
+                                      W.carry[rec.slot ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->viab.commit(rec, pl->run_count);
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_vi_align_ba_init(vis_ctx* ctx, const vis_vi_ba_carry* rec) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                 // (a kernel in flight reads and writes the records)
+    Plan* pl = ctx->batch;
+    ViabPlanWork W;
+    { const int rc = ensure_viab(ctx, pl, W); if (rc) return rc; }
+    if (!rec) { pl->viab.forget(); return VIS_OK; }
+    HIPCHK(ctx, hipMemcpy(W.carry[pl->viab.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->viab.seeded(pl->run_count);
     return VIS_OK;
 }
 

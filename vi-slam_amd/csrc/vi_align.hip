@@ -178,6 +178,8 @@ struct ViaFrame {
     bool use_c, use_b;
 };
 struct ViaCarryIn { const vis_vi_carry* rec; };            // null: none that counts
+template <bool BA> struct ViaBaArgs {};                                           // k_via_align<true>'s own arguments; none for <false>
+template <> struct ViaBaArgs<true> { vis_vi_align_ba_params bp; const vis_imu_bias_jac* jac; };
 
 DEV void via_gather(const vis_vi_align_params& P, const FtFrames& fr, const vis_traj_pose* __restrict__ traj, const vis_imu_delta* __restrict__ delta,
                     const vis_vi_carry* __restrict__ carry, int i, ViaFrame& F) {
@@ -259,10 +261,203 @@ DEV bool via_linear_terms(const double* lam, double beta, const double* gam, dou
     return fin;
 }
 
+// ---- the accelerometer bias (vis_vi_align_ba_rows): k_via_align<true>
+// via_ldl with the relative pivot test: a D[j] that is not finite, not > 0 or not > rel A[j][j] fails
+template <int N>
+DEV bool via_ldl_rel(const double (&A)[N][N], const double (&b)[N], double (&x)[N], double rel) {
+    double L[N][N], D[N], z[N];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        double s = A[j][j];
+#pragma unroll
+        for (int c = 0; c < j; c++) s = s - (L[j][c] * L[j][c]) * D[c];
+        D[j] = s;
+        ok = ok && s > 0.0 && via_finite(s) && s > rel * A[j][j];
+#pragma unroll
+        for (int i = j + 1; i < N; i++) {
+            double v = A[i][j];
+#pragma unroll
+            for (int c = 0; c < j; c++) v = v - (L[i][c] * L[j][c]) * D[c];
+            L[i][j] = v / s;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        double v = b[i];
+#pragma unroll
+        for (int c = 0; c < i; c++) v = v - L[i][c] * z[c];
+        z[i] = v;
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; i--) {
+        double v = z[i] / D[i];
+#pragma unroll
+        for (int c = i + 1; c < N; c++) v = v - L[c][i] * x[c];
+        x[i] = v;
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) ok = ok && via_finite(x[i]);
+    return ok;
+}
+DEV bool via_jac_usable(const vis_imu_bias_jac* __restrict__ J, int dq) {
+    if (J->flags & VIS_IMU_JAC_NONFINITE) return false;
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 9; k++) fin = fin && via_finite(J->Jvg[k]) && via_finite(J->Jva[k]) && via_finite(J->Jpg[k]) && via_finite(J->Jpa[k]);
+    return fin && J->q == dq;
+}
+// the Jacobian record of frame i's parent beside that parent's delta (null: none), and whether the two of the triple are usable
+DEV const vis_imu_bias_jac* via_parent_jac(const ViaFrame& F, const vis_imu_delta* __restrict__ delta, const vis_imu_bias_jac* __restrict__ jac,
+                                           const vis_vi_ba_carry* __restrict__ bcarry, bool& usable) {
+    usable = false;
+    if (F.q >= 0) { usable = via_jac_usable(jac + F.q, delta[F.q].q); return jac + F.q; }
+    if (F.q == VIS_KF_CARRIED && bcarry) { usable = via_jac_usable(&bcarry->last_jac, bcarry->carry.last_delta.q); return &bcarry->last_jac; }
+    return nullptr;
+}
+// nB = -B of the triple of F; Jc: the frame's own record, Jb: its parent's
+DEV void via_neg_b(const ViaFrame& F, const vis_imu_bias_jac* __restrict__ Jc, const vis_imu_bias_jac* __restrict__ Jb, double* nB) {
+    double X[9], P1[9], P2[9], P3[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) X[k] = Jc->Jpa[k];
+    via_mul(F.b.Rw, X, P1);
+#pragma unroll
+    for (int k = 0; k < 9; k++) X[k] = Jb->Jpa[k];
+    via_mul(F.a.Rw, X, P2);
+#pragma unroll
+    for (int k = 0; k < 9; k++) X[k] = Jb->Jva[k];
+    via_mul(F.a.Rw, X, P3);
+#pragma unroll
+    for (int k = 0; k < 9; k++) nB[k] = -((P1[k] * F.dt1 - P2[k] * F.dt2) + P3[k] * (F.dt1 * F.dt2));
+}
+DEV double via_col(const double* nB, const double* v, int c) { return (nB[c] * v[0] + nB[3 + c] * v[1]) + nB[6 + c] * v[2]; }
+// the 32 terms of a bias triple; false: one is not finite
+DEV bool via_ba_terms(const double* lam, double beta, const double* gam, double exc, const double* nB, double* t) {
+    t[0] = via_dot(lam, lam); t[1] = lam[0] * beta; t[2] = lam[1] * beta; t[3] = lam[2] * beta; t[4] = beta * beta;
+#pragma unroll
+    for (int c = 0; c < 3; c++) { t[5 + c] = via_col(nB, lam, c); t[27 + c] = via_col(nB, gam, c); t[24 + c] = beta * gam[c]; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) t[8 + k] = beta * nB[k];
+    int k = 17;
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = a; b < 3; b++, k++) t[k] = (nB[a] * nB[b] + nB[3 + a] * nB[3 + b]) + nB[6 + a] * nB[6 + b];
+    t[23] = via_dot(lam, gam); t[30] = via_dot(gam, gam); t[31] = exc;
+    bool fin = true;
+#pragma unroll
+    for (int j = 0; j < VIS_VIAB_SUMS; j++) fin = fin && via_finite(t[j]);
+    return fin;
+}
+// frame i as a bias triple: its parts and nB; false: it is none
+DEV bool via_bias_triple(const ViaFrame& F, int S, int E, const vis_imu_delta* __restrict__ delta, const vis_imu_bias_jac* __restrict__ jac,
+                         const vis_vi_ba_carry* __restrict__ bcarry, int i, double* lam, double& beta, double* gam, double& exc, double* nB) {
+    if (!via_is_triple(F, S, E)) return false;
+    double t11[11];
+    via_triple_parts(F, lam, beta, gam, exc);
+    if (!via_linear_terms(lam, beta, gam, exc, t11)) return false;
+    bool jb_ok;
+    const vis_imu_bias_jac* Jb = via_parent_jac(F, delta, jac, bcarry, jb_ok);
+    if (!jb_ok || !via_jac_usable(jac + i, delta[i].q)) return false;
+    via_neg_b(F, jac + i, Jb, nB);
+    return true;
+}
+struct ViaBa { double s, g[3], dba[3], s_lin, g_lin[3], dba_lin[3], g_norm; int flags; };
+// the 7 x 7 solve and the rounds on the tangent plane, from the 32 totals alone; o.s, o.g come in as the 4-unknown solution and stay on a fallback
+DEV void via_ba_solve(const vis_vi_align_params& P, const vis_vi_align_ba_params& BP, const double* ba, int n_ba, ViaBa& o) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) o.dba[k] = o.g_lin[k] = o.dba_lin[k] = 0.0;
+    o.s_lin = 0.0; o.g_norm = 0.0;
+    if (n_ba < BP.min_ba_triples) { o.flags |= VIS_VIAB_FEW; return; }
+    double M[7][7], r[7], x[7];
+    M[0][0] = ba[0];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        M[0][1 + c] = M[1 + c][0] = ba[1 + c];
+        M[0][4 + c] = M[4 + c][0] = ba[5 + c];
+#pragma unroll
+        for (int rr = 0; rr < 3; rr++) {
+            M[1 + rr][1 + c] = rr == c ? ba[4] : 0.0;
+            M[1 + rr][4 + c] = M[4 + c][1 + rr] = ba[8 + 3 * rr + c];
+        }
+    }
+    {
+        int k = 17;
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = a; b < 3; b++, k++) M[4 + a][4 + b] = M[4 + b][4 + a] = ba[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) r[k] = ba[23 + k];
+    const bool ok7 = via_ldl_rel<7>(M, r, x, BP.pivot_rel);
+    const double gn = sqrt(via_dot(x + 1, x + 1));
+    if (!ok7 || !(ba[0] > VIS_VIA_EXCITATION_REL * ba[31]) || !via_finite(gn)) { o.flags |= VIS_VIAB_UNOBSERVABLE; return; }
+    o.s_lin = x[0]; o.g_norm = gn;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { o.g_lin[k] = x[1 + k]; o.dba_lin[k] = x[4 + k]; }
+    if (!(o.s_lin > 0.0)) { o.flags |= VIS_VIAB_SCALE; return; }
+    double gh[3], s3 = o.s_lin, d3[3] = {o.dba_lin[0], o.dba_lin[1], o.dba_lin[2]};
+    double nn = via_normalise(o.g_lin, gh);
+    bool ok = via_finite(nn) && nn > 0.0;
+    for (int it = 0; it < P.refine_iters && ok; it++) {
+        int k = 0;
+        if (fabs(gh[1]) < fabs(gh[k])) k = 1;
+        if (fabs(gh[2]) < fabs(k == 1 ? gh[1] : gh[0])) k = 2;
+        const double ghk = k == 0 ? gh[0] : (k == 1 ? gh[1] : gh[2]);
+        double d[3], b1[3], b2[3], x0[3], rr[7], w1[3], w2[3], q[6], y[6], N[6][6];
+#pragma unroll
+        for (int j = 0; j < 3; j++) d[j] = (j == k ? 1.0 : 0.0) - ghk * gh[j];
+        (void)via_normalise(d, b1);
+        cross3(gh, b1, b2);
+#pragma unroll
+        for (int j = 0; j < 3; j++) x0[j] = P.G * gh[j];
+#pragma unroll
+        for (int i = 0; i < 7; i++) rr[i] = r[i] - ((M[i][1] * x0[0] + M[i][2] * x0[1]) + M[i][3] * x0[2]);
+        q[0] = rr[0]; q[1] = via_dot(b1, rr + 1); q[2] = via_dot(b2, rr + 1); q[3] = rr[4]; q[4] = rr[5]; q[5] = rr[6];
+#pragma unroll
+        for (int i = 0; i < 3; i++) { w1[i] = via_dot(&M[1 + i][1], b1); w2[i] = via_dot(&M[1 + i][1], b2); }
+        N[0][0] = M[0][0];
+        N[0][1] = N[1][0] = via_dot(&M[0][1], b1);
+        N[0][2] = N[2][0] = via_dot(&M[0][1], b2);
+        N[1][1] = via_dot(b1, w1); N[2][2] = via_dot(b2, w2);
+        N[1][2] = N[2][1] = via_dot(b1, w2);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double col[3] = {M[1][4 + c], M[2][4 + c], M[3][4 + c]};
+            N[0][3 + c] = N[3 + c][0] = M[0][4 + c];
+            N[1][3 + c] = N[3 + c][1] = via_dot(b1, col);
+            N[2][3 + c] = N[3 + c][2] = via_dot(b2, col);
+#pragma unroll
+            for (int a = 0; a < 3; a++) N[3 + a][3 + c] = M[4 + a][4 + c];
+        }
+        ok = via_ldl_rel<6>(N, q, y, BP.pivot_rel);
+        if (!ok) break;
+        double gg[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) gg[j] = (x0[j] + y[1] * b1[j]) + y[2] * b2[j];
+        nn = via_normalise(gg, gh);
+        ok = via_finite(nn) && nn > 0.0 && via_finite(gh[0]) && via_finite(gh[1]) && via_finite(gh[2]);
+        s3 = y[0]; d3[0] = y[3]; d3[1] = y[4]; d3[2] = y[5];
+    }
+    const double g3[3] = {P.G * gh[0], P.G * gh[1], P.G * gh[2]};
+    if (!ok || !via_finite(g3[0]) || !via_finite(g3[1]) || !via_finite(g3[2]) || !via_finite(d3[0]) || !via_finite(d3[1]) || !via_finite(d3[2]))
+        o.flags |= VIS_VIAB_UNOBSERVABLE;
+    else if (!(via_finite(s3) && s3 > 0.0)) o.flags |= VIS_VIAB_SCALE;
+    else {
+        o.s = s3;
+#pragma unroll
+        for (int k = 0; k < 3; k++) { o.g[k] = g3[k]; o.dba[k] = d3[k]; }
+    }
+}
+
+
+template <bool BA>
 __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, int n, FtFrames fr, const vis_traj_pose* __restrict__ traj,
                                                          const vis_imu_delta* __restrict__ delta, const vis_vi_carry* __restrict__ carry_in,
                                                          vis_vi_state* __restrict__ state, vis_vi_align* __restrict__ result,
-                                                         vis_vi_carry* __restrict__ carry_out) {
+                                                         vis_vi_carry* __restrict__ carry_out, ViaBaArgs<BA> X) {
+    // BA: carry_in, result and carry_out are the heads of a vis_vi_ba_carry, a vis_vi_align_ba and a vis_vi_ba_carry; X has the rest
     __shared__ int s_posed, s_saved, s_bad;
     const int tid = threadIdx.x;
     if (tid == 0) { s_posed = -1; s_saved = -1; s_bad = 0; }
@@ -276,6 +471,13 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
         else if (tid < 56) num = reinterpret_cast<const double*>(&carry_in->parent) + (tid - 41);
         else if (tid < 81) num = reinterpret_cast<const double*>(&carry_in->last_delta) + (tid - 56);
         if (num && !via_finite(*num)) atomicOr(&s_bad, 1);
+        if constexpr (BA) {                                       // the bias part: 32 sums and the 36 numbers of last_jac
+            const vis_vi_ba_carry* bc = reinterpret_cast<const vis_vi_ba_carry*>(carry_in);
+            num = nullptr;
+            if (tid >= 81 && tid < 113) num = bc->ba + (tid - 81);
+            else if (tid >= 113 && tid < 149) num = reinterpret_cast<const double*>(&bc->last_jac) + (tid - 113);
+            if (num && !via_finite(*num)) atomicOr(&s_bad, 2);
+        }
     }
     {
         int posed = -1, saved = -1;
@@ -289,7 +491,7 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
         atomicMax(&s_posed, posed); atomicMax(&s_saved, saved);
     }
     __syncthreads();
-    const bool bad_carry = s_bad != 0;
+    const bool bad_carry = BA ? (s_bad & 1) != 0 : s_bad != 0;
     const vis_vi_carry* carry = given && !bad_carry ? carry_in : nullptr;
     const int newest = s_posed, last = s_saved;
     int flags = bad_carry ? VIS_VIA_BAD_CARRY : 0;
@@ -327,6 +529,46 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
     for (int k = 0; k < 21; k++) sums[k] = wave_sum(sums[k]);
     { int none = 0; ep_totals<4>(sums, none); }
     ep_counts<4>(np_call, nt_call);
+    // ---- phase 2b (BA): the terms of the bias triples and their sums, a pass of its own
+    [[maybe_unused]] const vis_vi_ba_carry* bcarry = nullptr;
+    [[maybe_unused]] double ba[BA ? VIS_VIAB_SUMS : 1];
+    [[maybe_unused]] int nb_call = 0, n_ba = 0, ba_flags = 0;
+    if constexpr (BA) {
+        if (carry) {
+            if (s_bad & 2) ba_flags = VIS_VIAB_BAD_CARRY;
+            else bcarry = reinterpret_cast<const vis_vi_ba_carry*>(carry_in);
+        }
+#pragma unroll
+        for (int k = 0; k < VIS_VIAB_SUMS; k++) ba[k] = 0.0;
+        for (int i = tid; i < n; i += VIA_BLOCK) {
+            ViaFrame F;
+            via_gather(P, fr, traj, delta, carry, i, F);
+            double lam[3], beta, gam[3], exc, nB[9], t[VIS_VIAB_SUMS];
+            if (via_bias_triple(F, S, E, delta, X.jac, bcarry, i, lam, beta, gam, exc, nB) && via_ba_terms(lam, beta, gam, exc, nB, t)) {
+                nb_call++;
+#pragma unroll
+                for (int k = 0; k < VIS_VIAB_SUMS; k++) ba[k] = ba[k] + t[k];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < VIS_VIAB_SUMS; k++) ba[k] = wave_sum(ba[k]);
+        { int none = 0; ep_totals<4>(ba, none); }
+        { int none = 0; ep_counts<4>(nb_call, none); }
+        n_ba = nb_call;
+        if (bcarry && carry->segment_seq == S && carry->epoch_seq == E) {
+#pragma unroll
+            for (int k = 0; k < VIS_VIAB_SUMS; k++) ba[k] = bcarry->ba[k] + ba[k];
+            n_ba = bcarry->n_ba_triples + nb_call;
+        }
+        bool fin = true;
+#pragma unroll
+        for (int k = 0; k < VIS_VIAB_SUMS; k++) fin = fin && via_finite(ba[k]);
+        if (!fin) {
+#pragma unroll
+            for (int k = 0; k < VIS_VIAB_SUMS; k++) ba[k] = 0.0;
+            n_ba = 0; ba_flags |= VIS_VIAB_UNOBSERVABLE;
+        }
+    }
     // ---- phase 3: the totals and the solves, on every thread
     double gyro[10], lin[16];
 #pragma unroll
@@ -437,8 +679,15 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
             }
         }
     }
+    [[maybe_unused]] ViaBa bo;
+    [[maybe_unused]] bool ba_ok = false;
+    if constexpr (BA) {
+        bo.s = s; bo.g[0] = g[0]; bo.g[1] = g[1]; bo.g[2] = g[2]; bo.flags = ba_flags;
+        via_ba_solve(P, X.bp, ba, n_ba, bo);
+        ba_ok = !(bo.flags & (VIS_VIAB_FEW | VIS_VIAB_UNOBSERVABLE | VIS_VIAB_SCALE));
+    }
     // ---- phase 4: the second pass and the states
-    double sums2[2] = {0.0, 0.0};
+    double sums2[BA ? 3 : 2] = {0.0, 0.0};
     for (int i = tid; i < n; i += VIA_BLOCK) {
         ViaFrame F;
         via_gather(P, fr, traj, delta, carry, i, F);
@@ -489,10 +738,47 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
                 if (via_finite(rr)) { sums2[1] = sums2[1] + rr; st.res = sqrt(rr); }
             }
         }
+        if constexpr (BA) {
+            if (ba_ok) {                                          // the states under (s_ba, g_ba, dba) in the place of those under (s, g)
+#pragma unroll
+                for (int k = 0; k < 3; k++) st.p[k] = st.v[k] = 0.0;
+                st.res = 0.0; f &= VIS_VIS_HAS_PAIR;
+                double pa[3];
+#pragma unroll
+                for (int r = 0; r < 3; r++) pa[r] = bo.s * F.c.C[r] + F.c.L[r];
+                if (in_se && via_finite(pa[0]) && via_finite(pa[1]) && via_finite(pa[2])) { st.p[0] = pa[0]; st.p[1] = pa[1]; st.p[2] = pa[2]; f |= VIS_VIS_HAS_P; }
+                if (in_se && (F.c.flags & VIS_VIT_EDGE) && F.use_c && (F.b.flags & VIS_VIT_POSED) && F.b.seg == S && via_jac_usable(X.jac + i, delta[i].q)) {
+                    double Jv[9], Jp[9], ev[3], ep[3], z[3], w[3], v[3];
+#pragma unroll
+                    for (int k = 0; k < 9; k++) { Jv[k] = X.jac[i].Jva[k]; Jp[k] = X.jac[i].Jpa[k]; }
+                    via_mulv(Jv, bo.dba, ev); via_mulv(Jp, bo.dba, ep);
+#pragma unroll
+                    for (int k = 0; k < 3; k++) z[k] = (F.dv2[k] + ev[k]) - (F.dp2[k] + ep[k]) / F.dt2;
+                    via_mulv(F.b.Rw, z, w);
+#pragma unroll
+                    for (int r = 0; r < 3; r++) {
+                        const double pb = bo.s * F.b.C[r] + F.b.L[r];
+                        v[r] = ((pa[r] - pb) / F.dt2 + (0.5 * bo.g[r]) * F.dt2) + w[r];
+                    }
+                    if (via_finite(v[0]) && via_finite(v[1]) && via_finite(v[2])) { st.v[0] = v[0]; st.v[1] = v[1]; st.v[2] = v[2]; f |= VIS_VIS_HAS_V; }
+                }
+                double lam[3], beta, gam[3], exc, nB[9], t32[VIS_VIAB_SUMS];
+                if (via_bias_triple(F, S, E, delta, X.jac, bcarry, i, lam, beta, gam, exc, nB) && via_ba_terms(lam, beta, gam, exc, nB, t32)) {
+                    f |= VIS_VIS_HAS_TRIPLE;
+                    double Bd[3], rho[3];
+                    via_mulv(nB, bo.dba, Bd);
+#pragma unroll
+                    for (int r = 0; r < 3; r++) rho[r] = ((lam[r] * bo.s + beta * bo.g[r]) + Bd[r]) - gam[r];
+                    const double rr = via_dot(rho, rho);
+                    if (via_finite(rr)) { sums2[2] = sums2[2] + rr; st.res = sqrt(rr); }
+                }
+            }
+        }
         st.flags = f;
         if (state) state[i] = st;
     }
     sums2[0] = wave_sum(sums2[0]); sums2[1] = wave_sum(sums2[1]);
+    if constexpr (BA) sums2[2] = wave_sum(sums2[2]);
     { int none = 0; ep_totals<4>(sums2, none); }
     // ---- phase 5: the result and the carry
     if (tid != 0) return;
@@ -504,7 +790,29 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
     res.n_pairs = n_pairs; res.n_triples = n_triples; res.n_pairs_call = np_call; res.n_triples_call = nt_call;
     res.segment_seq = S; res.epoch_seq = E; res.flags = flags; res.reserved_ = 0;
     *result = res;
+    if constexpr (BA) {
+        vis_vi_align_ba* rb = reinterpret_cast<vis_vi_align_ba*>(result);
+#pragma unroll
+        for (int k = 0; k < 3; k++) { rb->dba[k] = bo.dba[k]; rb->g_ba[k] = bo.g[k]; rb->dba_lin[k] = bo.dba_lin[k]; rb->g_lin7[k] = bo.g_lin[k]; }
+        rb->s_ba = bo.s; rb->s_lin7 = bo.s_lin; rb->g_lin7_norm = bo.g_norm;
+        rb->rms_ba = ba_ok && nb_call > 0 && via_finite(sums2[2]) ? sqrt(sums2[2] / (double)nb_call) : 0.0;
+        rb->n_ba_triples = n_ba; rb->n_ba_triples_call = nb_call; rb->ba_flags = bo.flags; rb->reserved_ = 0;
+    }
     if (!carry_out) return;
+    if constexpr (BA) {
+        vis_vi_ba_carry* cb = reinterpret_cast<vis_vi_ba_carry*>(carry_out);
+#pragma unroll
+        for (int k = 0; k < VIS_VIAB_SUMS; k++) cb->ba[k] = ba[k];
+        cb->n_ba_triples = n_ba; cb->reserved_ = 0;
+        vis_imu_bias_jac zj;
+#pragma unroll
+        for (int k = 0; k < 9; k++) zj.Jvg[k] = zj.Jva[k] = zj.Jpg[k] = zj.Jpa[k] = 0.0;
+        zj.flags = VIS_IMU_JAC_NONFINITE; zj.q = 0;
+        if (last >= 0) {
+            if (via_usable(P, delta + last, traj[last].parent) && via_jac_usable(X.jac + last, delta[last].q)) zj = X.jac[last];
+        } else if (bcarry) zj = bcarry->last_jac;
+        cb->last_jac = zj;
+    }
 #pragma unroll
     for (int k = 0; k < 10; k++) carry_out->gyro[k] = gyro[k];
 #pragma unroll
@@ -542,7 +850,18 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
 int via_launch(vis_ctx* ctx, const vis_vi_align_params* vp, int n, FtFrames fr, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
                const vis_vi_carry* d_carry, vis_vi_state* d_state, vis_vi_align* d_result, vis_vi_carry* d_carry_out) {
     if (n < 0 || n > VIS_VIA_MAX_FRAMES || !d_result) return VIS_E_INVALID;
-    hipLaunchKernelGGL(k_via_align, dim3(1), dim3(VIA_BLOCK), 0, ctx->stream, *vp, n, fr, d_traj, d_delta, d_carry, d_state, d_result, d_carry_out);
+    hipLaunchKernelGGL(k_via_align<false>, dim3(1), dim3(VIA_BLOCK), 0, ctx->stream, *vp, n, fr, d_traj, d_delta, d_carry, d_state, d_result, d_carry_out,
+                       ViaBaArgs<false>{});
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+int via_ba_launch(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_vi_align_ba_params* bp, int n, FtFrames fr, const vis_traj_pose* d_traj,
+                  const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const vis_vi_ba_carry* d_carry, vis_vi_state* d_state,
+                  vis_vi_align_ba* d_result, vis_vi_ba_carry* d_carry_out) {
+    if (n < 0 || n > VIS_VIA_MAX_FRAMES || !d_result || !d_jac) return VIS_E_INVALID;
+    hipLaunchKernelGGL(k_via_align<true>, dim3(1), dim3(VIA_BLOCK), 0, ctx->stream, *vp, n, fr, d_traj, d_delta, d_carry ? &d_carry->carry : nullptr, d_state,
+                       &d_result->a, d_carry_out ? &d_carry_out->carry : nullptr, ViaBaArgs<true>{*bp, d_jac});
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

@@ -56,7 +56,7 @@ struct ReaderGuard {
     void clear() { *this = ReaderGuard(); }
 };
 
-// Which of a plan's TWO carried rows a follow-up launch continues (vis_batch_ftrack, _scale_links, _trajectory, _imu, _vi_align: "the rules of the depth row",
+// Which of a plan's TWO carried rows a follow-up launch continues (vis_batch_ftrack, _scale_links, _trajectory, _imu, _vi_align, _vi_align_ba: "the rules of the depth row",
 // include/vislam_hip.h).  A launch reads row `slot` -- the row of the last saved frame of the launch before, beside the carried record of the keyframe
 // gate -- and writes the other one, slot ^ 1: two rows, so that a call never reads the row it writes and a call repeated for the same run reads again
 // the row it read itself.  in = the row the last committed launch read, run = its run_count (-1: none), have = whether it had a row to read.
@@ -147,6 +147,8 @@ struct Plan {
     void* d_imuj_ws = nullptr; Turn imuj;
     // vis_batch_vi_align (ViaPlanWork), allocated by the first call or by vis_batch_vi_align_init: the two carried records
     void* d_via_ws = nullptr; Turn via;
+    // vis_batch_vi_align_ba (ViabPlanWork), allocated by the first call or by vis_batch_vi_align_ba_init: its own two carried records
+    void* d_viab_ws = nullptr; Turn viab;
     // pairs
     int32_t* d_pair_q = nullptr;             // npairs: query record index (-1 = no pair)
     int32_t* d_pair_t = nullptr;
@@ -637,6 +639,10 @@ int imu_correct_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_
 // vi_align.hip.  k_via_align on ctx->stream: one launch, no workspace; vp validated by the caller; d_carry, d_state, d_carry_out: null or the records
 int via_launch(vis_ctx* ctx, const vis_vi_align_params* vp, int n, FtFrames fr, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
                const vis_vi_carry* d_carry, vis_vi_state* d_state, vis_vi_align* d_result, vis_vi_carry* d_carry_out);
+// the same with the accelerometer bias: k_via_align<true>; bp validated by the caller; d_jac: n records
+int via_ba_launch(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_vi_align_ba_params* bp, int n, FtFrames fr, const vis_traj_pose* d_traj,
+                  const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const vis_vi_ba_carry* d_carry, vis_vi_state* d_state,
+                  vis_vi_align_ba* d_result, vis_vi_ba_carry* d_carry_out);
 // refine.hip: the first d_npts[i] (clamped) bytes of every row of in_stride bytes -> rows of row_cap bytes (vis_essential_batch's mask)
 int mask_rows_run(vis_ctx* ctx, int n, int in_stride, int row_cap, const int32_t* d_npts, const uint8_t* d_src, uint8_t* d_dst);
 #define VIS_RSTATE_WORDS 16

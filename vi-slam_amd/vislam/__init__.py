@@ -421,6 +421,28 @@ VIC_VALID = 1
 VIA_MAX_FRAMES = 1024
 
 
+class ViAlignBaParams(C.Structure):
+    """vis_vi_align_ba_params (vis_default_vi_align_ba_params: 2^-30, 16)"""
+    _fields_ = [("pivot_rel", C.c_double), ("min_ba_triples", C.c_int32), ("reserved_", C.c_int32 * 5)]
+
+
+class ViBaCarry(C.Structure):
+    """vis_vi_ba_carry as a host structure (vis_batch_vi_align_ba_init): vis_vi_carry, the 32 bias sums, their count, the Jacobians of last_delta"""
+    _fields_ = [("carry", ViCarry), ("ba", C.c_double * 32), ("n_ba_triples", C.c_int32), ("reserved_", C.c_int32), ("last_jac", ImuBiasJac)]
+
+
+VI_ALIGN_BA_DTYPE = np.dtype([("a", VI_ALIGN_DTYPE), ("dba", "<f8", (3,)), ("s_ba", "<f8"), ("g_ba", "<f8", (3,)), ("dba_lin", "<f8", (3,)),
+                              ("s_lin7", "<f8"), ("g_lin7", "<f8", (3,)), ("g_lin7_norm", "<f8"), ("rms_ba", "<f8"), ("n_ba_triples", "<i4"),
+                              ("n_ba_triples_call", "<i4"), ("ba_flags", "<i4"), ("reserved_", "<i4")])
+VI_BA_CARRY_DTYPE = np.dtype([("carry", VI_CARRY_DTYPE), ("ba", "<f8", (32,)), ("n_ba_triples", "<i4"), ("reserved_", "<i4"),
+                              ("last_jac", IMU_BIAS_JAC_DTYPE)])
+assert VI_ALIGN_BA_DTYPE.itemsize == 304 and VI_BA_CARRY_DTYPE.itemsize == 1280 == C.sizeof(ViBaCarry) and C.sizeof(ViAlignBaParams) == 32
+VI_ALIGN_BA_DBA_OFFSET = VI_ALIGN_BA_DTYPE.fields["dba"][1]            # 160: d_result + this is a d_dba of imu_correct_rows / batch_imu_correct
+VIAB_OK, VIAB_FEW, VIAB_UNOBSERVABLE, VIAB_SCALE, VIAB_BAD_CARRY = 0, 1, 2, 4, 8
+VIAB_SUMS = 32
+VIAB_PIVOT_REL = 2.0 ** -30
+
+
 class Timings(C.Structure):
     _fields_ = [("ms_total", C.c_float), ("ms_pyramid", C.c_float), ("ms_fast", C.c_float),
                 ("ms_select", C.c_float), ("ms_describe", C.c_float), ("ms_knn", C.c_float),
@@ -477,6 +499,7 @@ ABI_SYMBOLS = [
     "vis_imu_preintegrate_jac", "vis_imu_preintegrate_jac_rows", "vis_batch_imu_jac", "vis_batch_imu_jac_init", "vis_imu_correct_rows",
     "vis_batch_imu_correct",
     "vis_default_vi_align_params", "vis_vi_align_rows", "vis_batch_vi_align", "vis_batch_vi_align_init",
+    "vis_default_vi_align_ba_params", "vis_vi_align_ba_rows", "vis_batch_vi_align_ba", "vis_batch_vi_align_ba_init",
 ]
 
 
@@ -603,6 +626,13 @@ def _load():
         lib.vis_vi_align_rows.argtypes = [vp, vap, ci, vp, vp, vp, vp, vp, vp, vp]
         lib.vis_batch_vi_align.argtypes = [vp, vap, ci, vp, vp, vp, vp]
         lib.vis_batch_vi_align_init.argtypes = [vp, C.POINTER(ViCarry)]
+    if hasattr(lib, "vis_batch_vi_align_ba"):           # (absent from older A/B builds)
+        vap, vbp = C.POINTER(ViAlignParams), C.POINTER(ViAlignBaParams)
+        lib.vis_default_vi_align_ba_params.argtypes = [vbp]
+        lib.vis_default_vi_align_ba_params.restype = None
+        lib.vis_vi_align_ba_rows.argtypes = [vp, vap, vbp, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_vi_align_ba.argtypes = [vp, vap, vbp, ci, vp, vp, vp, vp, vp]
+        lib.vis_batch_vi_align_ba_init.argtypes = [vp, C.POINTER(ViBaCarry)]
     if hasattr(lib, "vis_essential_refine_batch"):      # (absent from older A/B builds)
         epp = C.POINTER(EssentialRefineParams)
         lib.vis_default_eref_params.argtypes = [epp]
@@ -762,6 +792,12 @@ def default_imu_params():
     ip = ImuParams()
     lib.vis_default_imu_params(C.byref(ip))
     return ip
+
+
+def default_vi_align_ba_params():
+    bp = ViAlignBaParams()
+    lib.vis_default_vi_align_ba_params(C.byref(bp))
+    return bp
 
 
 def default_vi_align_params():
@@ -1701,6 +1737,34 @@ class Context:
         if rec is not None and not isinstance(rec, ViCarry):
             rec = ViCarry.from_buffer_copy(np.asarray(rec, VI_CARRY_DTYPE).tobytes())
         self._chk(lib.vis_batch_vi_align_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_vi_align_init")
+
+    # -- visual-inertial alignment with the accelerometer bias ---------------------------------------------------------
+    def vi_align_ba_rows(self, n, d_prev_ptr, d_traj_ptr, d_delta_ptr, d_jac_ptr, d_result_ptr, d_state_ptr=0, d_carry_in_ptr=0, d_carry_out_ptr=0,
+                         vp=None, bp=None):
+        """vi_align_rows that also solves for the accelerometer-bias step: IMU_BIAS_JAC_DTYPE records beside the deltas in, n VI_STATE_DTYPE records,
+        ONE VI_ALIGN_BA_DTYPE record (its `a` is vi_align_rows' record; d_result + VI_ALIGN_BA_DBA_OFFSET is a d_dba of imu_correct_rows) and the
+        VI_BA_CARRY_DTYPE record of the next call out"""
+        vp = default_vi_align_params() if vp is None else vp
+        bp = default_vi_align_ba_params() if bp is None else bp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_vi_align_ba_rows(self._h, C.byref(vp), C.byref(bp), n, v(d_prev_ptr), v(d_traj_ptr), v(d_delta_ptr), v(d_jac_ptr),
+                                           v(d_carry_in_ptr), v(d_state_ptr), v(d_result_ptr), v(d_carry_out_ptr)), "vis_vi_align_ba_rows")
+
+    def batch_vi_align_ba(self, n, d_traj_ptr, d_delta_ptr, d_jac_ptr, d_result_ptr, d_state_ptr=0, vp=None, bp=None):
+        """the same for the frames of the last batch_run, behind batch_trajectory and batch_imu_jac of the run; the plan carries its own sums and
+        tails, apart from batch_vi_align's.  batch_imu_correct(..., d_dbg_ptr=d_result_ptr, d_dba_ptr=d_result_ptr + VI_ALIGN_BA_DBA_OFFSET) queued
+        behind it applies both estimated steps with no host step.  The buffers are in use until batch_sync()"""
+        vp = default_vi_align_params() if vp is None else vp
+        bp = default_vi_align_ba_params() if bp is None else bp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_vi_align_ba(self._h, C.byref(vp), C.byref(bp), n, v(d_traj_ptr), v(d_delta_ptr), v(d_jac_ptr), v(d_state_ptr),
+                                            v(d_result_ptr)), "vis_batch_vi_align_ba")
+
+    def batch_vi_align_ba_init(self, rec=None):
+        """the carry (a VI_BA_CARRY_DTYPE element or a ViBaCarry; None: none) the next run's batch_vi_align_ba continues from; synchronises"""
+        if rec is not None and not isinstance(rec, ViBaCarry):
+            rec = ViBaCarry.from_buffer_copy(np.asarray(rec, VI_BA_CARRY_DTYPE).tobytes())
+        self._chk(lib.vis_batch_vi_align_ba_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_vi_align_ba_init")
 
     # -- the essential-matrix pose on device rows, and its refinement ----------------------------------------------
     def essential_batch(self, n, d_p1_ptr, d_p2_ptr, d_npts_ptr, max_pts, row_cap, d_mask_ptr, d_out_ptr):
