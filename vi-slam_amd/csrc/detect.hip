@@ -20,6 +20,7 @@
 // next level's resize source; candidates/keypoints are O(N) and tiny.  k_resize streams at 84 % of the copy ceiling; k_fast is a chain of
 // latency-bound phases with vector + scalar issue saturated; k_describe is bound by the LDS array with vector issue right behind it.
 #include "vis_internal.h"
+#include "resize_index.h"
 #include <cfloat>
 #include <cmath>
 #include <vector>
@@ -76,10 +77,13 @@ typedef unsigned short us2_t __attribute__((ext_vector_type(2)));
 // does not pay: predicated or scalar-branched loads measured 0.66 ms for the pyramid of 1024 frames against 0.62 without any sharing
 // and 0.51 with a compile-time pattern -- so k_resize tests the wave's pattern against the ones that occur at scale 1.2 and falls
 // back to SHARE = 0 (everything loaded) for any other wave.  Same values in every case.
-template <uint32_t SHARE>
+// FULL: every lane of the wave has all RS_ROWS rows inside the level (decided once per wave by k_resize), the stores carry no predicate;
+// FULL = false keeps it (rows_left = the lane's rows inside the level).  A store goes to the frame base (SGPRs) + one 32-bit lane
+// offset that advances by the stride, like the loads.
+template <uint32_t SHARE, bool FULL>
 __device__ __forceinline__ void resize_rows(const uint8_t* __restrict__ fbase, uint32_t wb, uint32_t asel, const uint32_t (&YX)[RS_ROWS], const uint32_t (&YY)[RS_ROWS],
                                             const uint4* __restrict__ yrow, const uint32_t (&sel)[4],
-                                            const uint32_t (&coef)[4], uint8_t* __restrict__ dbase, int dstride, int dy0, int dh, uint32_t keep) {
+                                            const uint32_t (&coef)[4], uint8_t* __restrict__ dfbase, uint32_t doff, uint32_t dstride, int rows_left, uint32_t keep) {
     uint64_t W0[RS_ROWS], W1[RS_ROWS];
 #pragma unroll
     for (int r = 0; r < RS_ROWS; r++) {
@@ -98,7 +102,7 @@ __device__ __forceinline__ void resize_rows(const uint8_t* __restrict__ fbase, u
     for (int r = 1; r < RS_ROWS; r++) if ((SHARE >> r) & 1u) W0[r] = W1[r - 1];
 #pragma unroll
     for (int r = 0; r < RS_ROWS; r++) {
-        uint32_t v[4];
+        uint32_t v[4];                                      // the pixels x 4, + 2 for the rounding shift (<= 1022)
         const uint32_t B0 = yrow[r].z, B1 = yrow[r].w;      // the Q11 row weights (<< 16) stay in LDS until their row is due
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -107,10 +111,15 @@ __device__ __forceinline__ void resize_rows(const uint8_t* __restrict__ fbase, u
             const uint32_t r0 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, p0), __builtin_bit_cast(us2_t, coef[k]), 0u, false);
             const uint32_t r1 = __builtin_amdgcn_udot2(__builtin_bit_cast(us2_t, p1), __builtin_bit_cast(us2_t, coef[k]), 0u, false);
             // (B * (r >> 4)) >> 16 as ONE v_mul_hi_u32 with the weight pre-shifted by 16 (B <= 2048, r >> 4 <= 32640)
-            v[k] = (__umulhi(B0, r0 >> 4) + __umulhi(B1, r1 >> 4) + 2u) >> 2;               // <= 255
+            v[k] = __umulhi(B0, r0 >> 4) + __umulhi(B1, r1 >> 4) + 2u;
         }
-        const uint32_t out = ((v[3] << 8 | v[2]) << 16) | (v[1] << 8 | v[0]);
-        if (dy0 + r < dh) *reinterpret_cast<uint32_t*>(dbase + (uint32_t)__umul24(dy0 + r, dstride)) = out & keep;
+        // >> 2 on pixels 0 | 2 and 1 | 3 as halves of one register each (v_pk_lshrrev_b16: no carry between the halves, no rounding or
+        // mask constants in registers), then the odd pair moves into the byte gaps of the even one
+        const us2_t e02 = __builtin_bit_cast(us2_t, (v[2] << 16) + v[0]) >> (unsigned short)2;
+        const us2_t e13 = __builtin_bit_cast(us2_t, (v[3] << 16) + v[1]) >> (unsigned short)2;
+        const uint32_t out = (__builtin_bit_cast(uint32_t, e13) << 8) | __builtin_bit_cast(uint32_t, e02);
+        if (FULL || r < rows_left) *reinterpret_cast<uint32_t*>(dfbase + doff) = out & keep;
+        doff += dstride;
     }
 }
 
@@ -161,38 +170,44 @@ template <bool NARROW>
 __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src, int sw, int sh, int sstride, size_t sframe,
                                                 uint8_t* __restrict__ dst, int dw, int dh, int dstride, size_t dframe,
                                                 double scale_x, double scale_y,
-                                                int bx_count, int per_frame, int nframes, const uint32_t* __restrict__ tab) {
+                                                int bx_count, int per_frame, int nframes, const uint32_t* __restrict__ tab, uint32_t magic) {
     int f, inner;
     if (!xcd_frame_map(blockIdx.x, per_frame, nframes, f, inner)) return;
-    // flat (row group, 4-pixel column group) index: rows are narrower than 256 px on most levels, a 2-D block
-    // mapping leaves a quarter of the lanes idle
-    const int idx = inner * 256 + threadIdx.y * 64 + threadIdx.x;
-    int rg = (int)(((float)idx + 0.5f) * (1.0f / (float)bx_count));
-    int cg = idx - rg * bx_count;
-    if (cg < 0) { rg--; cg += bx_count; } else if (cg >= bx_count) { rg++; cg -= bx_count; }
-    const int dx4 = cg * 4, dy0 = rg * RS_ROWS;
     if (NARROW) {
         // Neither the row coefficients (two source row offsets, two Q11 weights: the same for every thread of a row) nor the column
         // coefficients (the same for every thread of a column group) are computed here: k_resize_tab tabulated them once per plan
         // (the kernel is VALU-issue bound and the double-precision coordinate arithmetic was a quarter of its instructions).  A
         // thread's dependency chain is table entry -> source bytes; the rows of the workgroup go through LDS.
         __shared__ uint4 yc[256];
-        const int tid = threadIdx.y * 64 + threadIdx.x;
-        int rg_first = (int)(((float)(inner * 256) + 0.5f) * (1.0f / (float)bx_count));
-        { const int c0 = inner * 256 - rg_first * bx_count; if (c0 < 0) rg_first--; else if (c0 >= bx_count) rg_first++; }
-        int rg_last = (int)(((float)(inner * 256 + 255) + 0.5f) * (1.0f / (float)bx_count));
-        { const int c1 = inner * 256 + 255 - rg_last * bx_count; if (c1 < 0) rg_last--; else if (c1 >= bx_count) rg_last++; }
-        const int row_first = rg_first * RS_ROWS, nrows = (rg_last - rg_first + 1) * RS_ROWS;
-        const uint4* tab4 = reinterpret_cast<const uint4*>(tab);
-        // nrows <= 256: the host sends narrower levels (< 12 groups per row) to the wide variant
-        if (tid < nrows) yc[tid] = tab4[3 * bx_count + min(row_first + tid, dh - 1)];
+        // flat (row group, 4-pixel column group) index (resize_index.h), decoded by one multiply-high with the level's magic number.
+        // What depends on the workgroup or the wave alone is computed from uniform integers, i.e. on the scalar unit.
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.y);
+        const uint32_t idx_wg = (uint32_t)inner * 256u, idx_wave = idx_wg + wave * 64u;
+        const uint32_t tid = wave * 64u + threadIdx.x;
+        uint32_t rg, cg;
+        resize_index_decode(idx_wave + threadIdx.x, magic, (uint32_t)bx_count, rg, cg);
+        const uint32_t dy0 = rg * RS_ROWS;
+        const uint32_t rg_first = resize_index_row_group(idx_wg, magic), rg_last = resize_index_row_group(idx_wg + 255u, magic);
+        const uint32_t row_first = rg_first * RS_ROWS, nrows = (rg_last - rg_first + 1u) * RS_ROWS;
+        // the wave's last lane has its largest row group: is any of the wave's rows outside the level?
+        const bool partial = (resize_index_row_group(idx_wave + 63u, magic) + 1u) * RS_ROWS > (uint32_t)dh;
+        // table records at the table base (SGPRs) + a 32-bit byte offset (the table is 48 bytes per column group + 16 per row: < 2^17)
+        const uint8_t* tabb = reinterpret_cast<const uint8_t*>(tab);
+        // (the column records are requested first: the row record has to come back before the barrier, the others travel with it)
         uint4 s4, c4, m4;
-        if (dy0 < dh) { s4 = tab4[3 * cg]; c4 = tab4[3 * cg + 1]; m4 = tab4[3 * cg + 2]; }
+        if (dy0 < (uint32_t)dh) {
+            const uint32_t o = __umul24(cg, 48u);
+            s4 = *reinterpret_cast<const uint4*>(tabb + o); c4 = *reinterpret_cast<const uint4*>(tabb + (o + 16u)); m4 = *reinterpret_cast<const uint4*>(tabb + (o + 32u));
+        }
+        // nrows <= 256: the host sends narrower levels (< 12 groups per row) to the wide variant
+        if (tid < nrows) yc[tid] = *reinterpret_cast<const uint4*>(tabb + (48u * (uint32_t)bx_count + 16u * min(row_first + tid, (uint32_t)dh - 1u)));
         __syncthreads();
-        if (dy0 >= dh) return;
+        if (dy0 >= (uint32_t)dh) return;
         const uint32_t sel[4] = {s4.x, s4.y, s4.z, s4.w}, coef[4] = {c4.x, c4.y, c4.z, c4.w};
         const uint32_t wb = m4.x, keep = m4.y, asel = m4.z;
-        uint8_t* dbase = dst + (size_t)f * dframe + dx4;
+        uint8_t* dfbase = dst + (size_t)f * dframe;
+        const uint32_t doff = __umul24(dy0, (uint32_t)dstride) + cg * 4u;     // (rows and strides are far below 2^24)
+        const int rows_left = dh - (int)dy0;
         const uint8_t* fbase = src + (size_t)f * sframe;
         const uint4* yrow = yc + (dy0 - row_first);
         uint32_t YX[RS_ROWS], YY[RS_ROWS];
@@ -205,12 +220,21 @@ __global__ __launch_bounds__(256) void k_resize(const uint8_t* __restrict__ src,
         // At scale 1.2 the source row advances by two once every five rows (at row p of a group of five).
         // Any pattern that is a SUBSET of the wave's is exact (an unshared row is simply loaded); the second list covers waves that
         // straddle two row groups whose phase differs by one, so that only waves at a clamped border or of another scale load every row.
-#define RS_CASE(M) if ((M & ~share) == 0u) { resize_rows<M>(fbase, wb, asel, YX, YY, yrow, sel, coef, dbase, dstride, dy0, dh, keep); return; }
-        RS_CASE(0x1Eu) RS_CASE(0x1Cu) RS_CASE(0x1Au) RS_CASE(0x16u) RS_CASE(0x0Eu) RS_CASE(0x18u) RS_CASE(0x12u) RS_CASE(0x06u)
+        // The sharing cases store without a per-row predicate.  A wave with a partial row group (the last of a level whose height is no
+        // multiple of RS_ROWS) goes, like a wave of no listed pattern, to the one instance that loads every row and predicates its stores.
+#define RS_CASE(M) if ((M & ~share) == 0u) { resize_rows<M, true>(fbase, wb, asel, YX, YY, yrow, sel, coef, dfbase, doff, (uint32_t)dstride, rows_left, keep); return; }
+        if (!partial) { RS_CASE(0x1Eu) RS_CASE(0x1Cu) RS_CASE(0x1Au) RS_CASE(0x16u) RS_CASE(0x0Eu) RS_CASE(0x18u) RS_CASE(0x12u) RS_CASE(0x06u) }
 #undef RS_CASE
-        resize_rows<0u>(fbase, wb, asel, YX, YY, yrow, sel, coef, dbase, dstride, dy0, dh, keep);
+        resize_rows<0u, false>(fbase, wb, asel, YX, YY, yrow, sel, coef, dfbase, doff, (uint32_t)dstride, rows_left, keep);
         return;
     }
+    // flat (row group, 4-pixel column group) index: rows are narrower than 256 px on most levels, a 2-D block
+    // mapping leaves a quarter of the lanes idle
+    const int idx = inner * 256 + threadIdx.y * 64 + threadIdx.x;
+    int rg = (int)(((float)idx + 0.5f) * (1.0f / (float)bx_count));
+    int cg = idx - rg * bx_count;
+    if (cg < 0) { rg--; cg += bx_count; } else if (cg >= bx_count) { rg++; cg -= bx_count; }
+    const int dx4 = cg * 4, dy0 = rg * RS_ROWS;
     if (dy0 >= dh) return;
     int sxs[4], a0s[4], a1s[4];
 #pragma unroll
@@ -1304,7 +1328,8 @@ int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int re
     for (int l = 1; l < L; l++) {
         const LevelInfo& V = pl->lv[l];
         const LevelInfo& U = pl->lv[l - 1];
-        const int bxc = (V.w + 3) / 4, per_frame = (bxc * ((V.h + RS_ROWS - 1) / RS_ROWS) + 255) / 256;   // bxc = 4-px groups per row
+        const int bxc = (V.w + 3) / 4, per_frame = resize_index_blocks(bxc, V.h, RS_ROWS);   // bxc = 4-px groups per row
+        const uint32_t magic = resize_index_magic((uint32_t)bxc);                           // (only the narrow variant decodes with it)
         // scale exactly as cv::resize derives it: inv_scale = (double)dsize/ssize; scale = 1./inv_scale
         const double scale_x = 1. / ((double)V.w / U.w), scale_y = 1. / ((double)V.h / U.h);
         if (scale_x <= 2.0 && bxc >= 12) {       // (256 threads then span at most 23 row groups = 230 rows of coefficients)
@@ -1315,10 +1340,10 @@ int launch_detect(vis_ctx* ctx, Plan* pl, const uint8_t* d_frames, int n, int re
                 HIPCHK(ctx, hipStreamSynchronize(st));       // (once: later launches may come from another stream)
             }
             hipLaunchKernelGGL(k_resize<true>, dim3(xcd_grid(n, per_frame)), dim3(64, 4), 0, st, D.lv[l - 1].img, U.w, U.h, U.stride, U.frame_bytes,
-                               pl->d_pyr[l], V.w, V.h, V.stride, V.frame_bytes, scale_x, scale_y, bxc, per_frame, n, (const uint32_t*)pl->d_rs_tab[l]);
+                               pl->d_pyr[l], V.w, V.h, V.stride, V.frame_bytes, scale_x, scale_y, bxc, per_frame, n, (const uint32_t*)pl->d_rs_tab[l], magic);
         } else
             hipLaunchKernelGGL(k_resize<false>, dim3(xcd_grid(n, per_frame)), dim3(64, 4), 0, st, D.lv[l - 1].img, U.w, U.h, U.stride, U.frame_bytes,
-                               pl->d_pyr[l], V.w, V.h, V.stride, V.frame_bytes, scale_x, scale_y, bxc, per_frame, n, (const uint32_t*)nullptr);
+                               pl->d_pyr[l], V.w, V.h, V.stride, V.frame_bytes, scale_x, scale_y, bxc, per_frame, n, (const uint32_t*)nullptr, magic);
     }
     if (ctx->ev_ok) (void)hipEventRecord(ctx->ev[1], st);
     if (after_resize) HIPCHK(ctx, hipEventRecord(after_resize, st));      // the side stream's streaming work starts here (vis_batch_run); behind k_fast or k_select instead: same frames/s (round 5)
