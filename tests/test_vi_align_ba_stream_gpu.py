@@ -1,6 +1,8 @@
 """GPU: the alignment with the accelerometer bias as a stream, through vis_batch_run on the 37 small synthetic frames of tests/ftrack_stream_cases.py
 with the 200 Hz IMU of tests/imu_cases.py beside them, keyframe gate off and on.  (The synthetic images and the synthetic IMU are unrelated motions:
-the solution is flagged or meaningless, which is part of what is compared -- the planted motion is tests/test_vi_align_ba_gpu.py's.)
+the solution is flagged or meaningless, which is part of what is compared -- the planted motion is tests/test_vi_align_ba_gpu.py's, and
+the chain from pixels to the biases on ONE world is tests/test_vi_chain_gpu.py's, row level: a frame-stream version needs an image generator whose
+camera accelerates -- these frames move at constant velocity, which never excites the alignment -- and is out of scope.)
 
 a. Per launch: vis_batch_vi_align_ba behind triangulate -> scale links -> trajectory -> imu_jac, beside vis_batch_vi_align of the same run, whose
    records stay its own (test_vi_align_stream_gpu's check) and are the embedded record; against vis_vi_align_ba_rows fed with the downloaded records,

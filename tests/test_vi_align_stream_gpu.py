@@ -1,6 +1,8 @@
 """GPU: the visual-inertial alignment as a stream, through vis_batch_run on the 37 small synthetic frames of tests/ftrack_stream_cases.py with the
 200 Hz IMU of tests/imu_cases.py beside them, keyframe gate off and on.  (The synthetic images and the synthetic IMU are unrelated motions: the
-solution is flagged or meaningless, which is part of what is compared -- the planted motion is tests/test_vi_align_gpu.py's.)
+solution is flagged or meaningless, which is part of what is compared -- the planted motion is tests/test_vi_align_gpu.py's, and the chain from
+pixels to the biases on ONE world is tests/test_vi_chain_gpu.py's, row level: a frame-stream version needs an image generator whose camera
+accelerates -- these frames move at constant velocity, which never excites the alignment -- and is out of scope.)
 
 a. Per launch: vis_batch_vi_align behind triangulate -> scale links -> trajectory -> imu, against vis_vi_align_rows fed with the downloaded records,
    vis_batch_get_keyframes' pairing and the carry so far, BYTE FOR BYTE, and both against the restatement.
