@@ -1649,8 +1649,8 @@ int  vis_batch_imu(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_
 /* The carry the NEXT run's vis_batch_imu continues from (rec NULL: none).  HOST pointer; SYNCHRONISES, like vis_batch_trajectory_init.
  * VIS_E_STATE without a context or plan. */
 int  vis_batch_imu_init(vis_ctx* ctx, const vis_imu_carry* rec);
-/* Out of scope: the 9 x 9 covariance (the bias Jacobians of v and p are the block below; the gyro bias, gravity, the metric scale and the lever arm
- * are vis_vi_align_rows / vis_batch_vi_align), a guided run with the gate on, and the adapters' IMU arguments (still accepted and ignored). */
+/* Out of scope: a guided run with the gate on, and the adapters' IMU arguments (still accepted and ignored).  (The bias Jacobians of v and p and the
+ * 9 x 9 covariance are the blocks below; the gyro bias, gravity, the metric scale and the lever arm are vis_vi_align_rows / vis_batch_vi_align.) */
 
 /* ---- Bias Jacobians of the deltas and the first-order bias correction.  The three calls below are vis_imu_preintegrate, vis_imu_preintegrate_rows
  * and vis_batch_imu with one more output row, d_jac: Jvg = dv / dbg, Jva = dv / dba, Jpg = dp / dbg, Jpa = dp / dba (3 x 3 row-major), the derivatives
@@ -1717,8 +1717,68 @@ int  vis_imu_correct_rows(vis_ctx* ctx, const vis_imu_params* ip, int n, const v
  * Refusals as above; VIS_E_STATE: no context / plan / match stage, or n differs. */
 int  vis_batch_imu_correct(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
                            const double* d_dba, vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status);
-/* Out of scope: covariance propagation, the host adapters' IMU arguments, a guided run with the gate on.  (The accelerometer-bias estimate that reads
- * Jva and Jpa is vis_batch_vi_align_ba.) */
+/* Out of scope: the host adapters' IMU arguments, a guided run with the gate on.  (The accelerometer-bias estimate that reads Jva and Jpa is
+ * vis_batch_vi_align_ba; the covariance is the block below.) */
+
+/* ---- THE COVARIANCE of a delta.  The three calls below are vis_imu_preintegrate, vis_imu_preintegrate_rows and vis_batch_imu with one more output
+ * row, d_cov: the 9 x 9 covariance of the error (dphi, dv, dp) of the delta, the error defined by R Exp(dphi), v + dv, p + dp, driven by white gyro and
+ * accelerometer noise of the densities of vis_imu_noise (Forster et al. 2017, restated from the equations for THIS scheme: the linear map is the one
+ * the bias Jacobians above follow, driven by noise in the place of a constant bias).  The bias Jacobians are NOT computed by these calls (a caller
+ * who wants both queues both; k_imu_pairs<true> has no registers to spare).  d_delta, d_rot and the carried delta are the sibling's BYTE FOR BYTE on
+ * every input.  tests/imu_cov_ref.py restates every operation below; every record equals it byte for byte.  Double arithmetic, + - * / only, nothing
+ * contracted; products (A B), (A^T B), (A x) as in the IMU block, and (A B^T)[3r + c] = (A[3r] B[3c] + A[3r + 1] B[3c + 1]) + A[3r + 2] B[3c + 2];
+ * (M [u]x)[3r] = M[3r + 1] u[2] - M[3r + 2] u[1], [3r + 1] = M[3r + 2] u[0] - M[3r] u[2], [3r + 2] = M[3r] u[1] - M[3r + 1] u[0].
+ * BLOCKS.  S is kept as six 3 x 3 blocks, named by (row, column): A = phi-phi, B = v-phi, C = v-v, D = p-phi, E = p-v, F = p-p.  A, C and F are computed
+ * as their UPPER TRIANGLES only (entries 00 01 02 11 12 22; where a product below reads one of them in full, the lower entries are copies), so the
+ * matrix is symmetric by construction.  vis_imu_cov.S is the upper triangle of the 9 x 9 in row order, entry (r, c), r <= c, at r 9 - r (r - 1) / 2 +
+ * (c - r): rows 0 - 2 hold A's triangle, B^T and D^T, rows 3 - 5 C's triangle and E^T, rows 6 - 8 F's triangle.
+ * PROPAGATION by F = [a 0 0; b I 0; c t I] (3 x 3 blocks; a = M^T for a given M), P(X; M, b, c, t) = F X F^T, block by block and in this order:
+ *   A'  = M^T (X.A M);                                       U = (b X.A) + X.B;         B' = U M;
+ *   C'  = (U b^T) + ((b X.B^T) + X.C);                       V = ((c X.A) + t X.B) + X.D;   D' = V M;
+ *   Y   = ((c X.B^T) + t X.C) + X.E;                         E' = (V b^T) + Y;
+ *   Z   = ((c X.D^T) + t X.E^T) + X.F;                       F' = ((V c^T) + t Y) + Z;            (each line entry by entry; t X.B is t times the entry)
+ * SUB-STEP, with R, dR, Jr, R', u0, u1, h of the sub-step above, hh = 0.5 h, qg = (sigma_g sigma_g) / h, qa = (sigma_a sigma_a) / h -- a sub-step is ONE
+ * measurement of the mean rate and the mean specific force, each with independent noise of covariance (sigma^2 / h) I:
+ *   S1 = R' [u1]x;  W = (R [u0]x) + (S1 dR^T);  b[k] = -(hh W[k]);  c[k] = hh b[k];  K1[k] = Jr[k] h;  K2[k] = -(hh (S1 K1)[k]);  K3[k] = (R[k] + R'[k]) hh;
+ *   N.A = qg (K1 K1^T);  N.B = qg (K2 K1^T);  N.C = qg (K2 K2^T) + qa (K3 K3^T);  N.D = hh N.B;  N.E = hh N.C;  N.F = hh N.E  (entry by entry);
+ *   S = P(S; dR, b, c, h) + N  (each entry: the propagated term first).
+ * That is F S F^T + G diag(qg I, qa I) G^T with F = [dR^T 0 0; -h/2 W I 0; -h^2/4 W h I I] and G = [Jr h 0; -h/2 R' [u1]x Jr h, (R + R') h/2; h/2 times
+ * that row].  An interval starts with S = 0 and flags 0.
+ * COMPOSITION X o Y (X earlier), after the delta's O = X o Y:  b[k] = -(X.R [Y.v]x)[k];  c[k] = -(X.R [Y.p]x)[k];
+ *   G-term: A = Y.A;  B = X.R Y.B;  C = (X.R Y.C) X.R^T;  D = X.R Y.D;  E = (X.R Y.E) X.R^T;  F = (X.R Y.F) X.R^T;
+ *   S = P(X.S; Y.R, b, c, Y.dt) + G-term  (each entry: the propagated term first);  flags = X.flags | Y.flags; then SETTLE with O's flags.
+ * SETTLE is the Jacobians' rule with VIS_IMU_COV_NONFINITE and the 45 numbers: S = 0 beside a voided delta or in a flagged record; else a number that
+ * is not finite zeroes S and sets the flag, which is sticky.  No NaN or infinity reaches a record or a carry.  TABLE, PAIRS and CARRY are the delta's,
+ * entry for entry; so with the gate off a stream's covariances are the same bytes however it is cut, and with the gate on two cuts agree within a
+ * bound.  A frame without a pair has S = 0 and flags 0.  q = the delta's q (0 in a carry).  The table is a separate one of 568 bytes x
+ * frames x levels (71 slots: the 26 of vis_imu_preintegrate_rows, then A's six, B, C's six, D, E, F's six).
+ * On the device: k_imu_cov_intervals and k_imu_cov_pairs, the launches of the siblings and their bodies; a composition folds one block at a time.
+ * Out of scope: bias random-walk states (a 15 x 15 covariance), the covariance of the bias-corrected records of vis_imu_correct_rows. */
+enum { VIS_IMU_COV_OK = 0, VIS_IMU_COV_NONFINITE = 1 };
+typedef struct vis_imu_noise {           /* 16 bytes; both finite and >= 0 */
+    double sigma_g;                      /* 1.6968e-4     gyro noise density, rad/s/sqrt(Hz) (EuRoC's ADIS16448) */
+    double sigma_a;                      /* 2.0e-3        accelerometer noise density, m/s^2/sqrt(Hz) */
+} vis_imu_noise;
+typedef struct vis_imu_cov { double S[45]; int32_t flags, q; } vis_imu_cov;                                              /* 368 bytes */
+/* vis_imu_carry and the covariance of its open delta */
+typedef struct vis_imu_cov_carry { vis_imu_carry carry; vis_imu_cov open_cov; } vis_imu_cov_carry;                       /* 600 bytes */
+void vis_default_imu_noise(vis_imu_noise* np);
+/* vis_imu_preintegrate with the covariance of the interval.  Refusals in its order: np NULL or out of range directly after ip, cov NULL beside delta NULL. */
+int  vis_imu_preintegrate_cov(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, const vis_imu_sample* samples, int n_samples, double t_a,
+                              double t_b, vis_imu_delta* delta, vis_imu_cov* cov, float* rot);
+/* vis_imu_preintegrate_rows with d_cov (n records, 8-byte aligned, not NULL) and carries that hold the open delta's covariance.  The workspace is a
+ * block of the context's own, apart from the siblings', under the same rule: it only grows, and a call that grows it SYNCHRONISES.
+ * Refusals in the sibling's order and codes, np directly after ip, d_cov beside d_delta. */
+int  vis_imu_preintegrate_cov_rows(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, int n, const vis_imu_sample* d_samples, int n_samples,
+                                   const double* d_tframe, const int32_t* d_prev, const vis_imu_cov_carry* d_carry_in, vis_imu_delta* d_delta,
+                                   vis_imu_cov* d_cov, float* d_rot, vis_imu_cov_carry* d_carry_out);
+/* vis_batch_imu with d_cov, on the POSE stream through the follow-up scaffold, with TWO carried vis_imu_cov_carry records of its own under the same
+ * turn rule -- apart from vis_batch_imu's and vis_batch_imu_jac's, so that any of the three may follow a run, or all.  Refusals in vis_batch_imu's
+ * order and codes, np directly after ip. */
+int  vis_batch_imu_cov(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, int n, const vis_imu_sample* d_samples, int n_samples,
+                       const double* d_tframe, vis_imu_delta* d_delta, vis_imu_cov* d_cov, float* d_rot);
+/* The carry the NEXT run's vis_batch_imu_cov continues from (rec NULL: none).  HOST pointer; SYNCHRONISES.  VIS_E_STATE without a context or plan. */
+int  vis_batch_imu_cov_init(vis_ctx* ctx, const vis_imu_cov_carry* rec);
 
 /* ---- visual-inertial alignment: the gyro bias, gravity in the root's frame, the factor from trajectory units to metres and a velocity per frame,
  * from the records of vis_batch_trajectory and vis_batch_imu (after Mur-Artal & Tardos 2017 and Qin et al. 2018, restated from the equations; the
@@ -1826,7 +1886,7 @@ int  vis_batch_vi_align(vis_ctx* ctx, const vis_vi_align_params* vp, int n, cons
 int  vis_batch_vi_align_init(vis_ctx* ctx, const vis_vi_carry* rec);
 /* Out of scope: this call does not estimate the accelerometer bias (vis_vi_align_ba_rows / vis_batch_vi_align_ba below do) and does not correct dv
  * and dp for dbg itself (vis_batch_imu_correct does, from d_result, and a second call of this one reads the corrected records; or pass bg + dbg to
- * the next vis_batch_imu); covariances or weights; feeding anything back into the trajectory, vis_batch_track or vis_batch_pnp.
+ * the next vis_batch_imu); weights by the deltas' covariances; feeding anything back into the trajectory, vis_batch_track or vis_batch_pnp.
  * There is no host-pointer single form: one interval aligns nothing. */
 
 /* ---- visual-inertial alignment WITH THE ACCELEROMETER BIAS: the sibling of the block above that also solves for the step dba of the accelerometer
@@ -1905,8 +1965,51 @@ int  vis_batch_vi_align_ba(vis_ctx* ctx, const vis_vi_align_params* vp, const vi
                            const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, vis_vi_state* d_state, vis_vi_align_ba* d_result);
 /* The carry the NEXT run's vis_batch_vi_align_ba continues from (rec NULL: none).  HOST pointer; SYNCHRONISES.  VIS_E_STATE without a context or plan. */
 int  vis_batch_vi_align_ba_init(vis_ctx* ctx, const vis_vi_ba_carry* rec);
-/* Out of scope: folding dbg into dv and dp inside the same call (the queued correct -> align_ba does that); covariances and weights; a prior on the
- * bias; feeding the result back into the trajectory, vis_batch_track or PnP; more than 1024 frames per call; a host-pointer single form. */
+/* Out of scope: folding dbg into dv and dp inside the same call (the queued correct -> align_ba does that); weights by the deltas' covariances (the
+ * covariance itself is vis_batch_imu_cov, its whitened residual vis_batch_imu_factor below); a prior on the bias; feeding the result back into the
+ * trajectory, vis_batch_track or PnP; more than 1024 frames per call; a host-pointer single form. */
+
+/* ---- THE INERTIAL FACTOR of a pair: the residual of the pair's delta against the aligned states of the frame and its parent, whitened by the
+ * delta's covariance -- what says how far a visual pose may disagree with the IMU before it is wrong.  It reads the records of vis_batch_trajectory,
+ * vis_batch_imu_cov and vis_batch_vi_align (or vis_batch_vi_align_ba: the head of a vis_vi_align_ba record is a vis_vi_align record and is passed as it
+ * is) and writes one vis_imu_factor a frame.  tests/imu_factor_ref.py restates every operation; every record equals it byte for byte.  Double
+ * arithmetic, + - * / and comparisons only, nothing contracted; products, tails, "usable delta" and LDL^T are the alignment block's, finite() the IMU's.
+ * Frame i with q = prev[i] normalised, T = d_traj[i], the tails of i (pair q) and of q (pair prev[q] normalised), in this order:
+ *   q < 0 (no pair, or the parent is the carried frame), or the tail of i lacks VIS_VIT_EDGE, or the tail of q lacks VIS_VIT_POSED: VIS_IMF_NO_PARENT,
+ *     and nothing more is looked at.  Else, OR-ed:
+ *   d_state[i] or d_state[q] lacks VIS_VIS_HAS_P or VIS_VIS_HAS_V: VIS_IMF_NO_STATE;  d_result->flags has any of VIS_VIA_FEW | SINGULAR | SCALE:
+ *     VIS_IMF_NO_ALIGN;  the delta is not usable (parent = T.parent), or d_cov[i].flags has VIS_IMU_COV_NONFINITE, or one of its 45 numbers is not
+ *     finite, or its q is not the delta's: VIS_IMF_UNUSABLE.
+ * With none of them, (R, dv, dp, dt) of the delta, b = q, g = d_result->g, p and v of d_state:
+ *   r[0..2] = e of the alignment's step 1 (V = Rw_b^T Rw_i, Er = R^T V, the sine-axis vector: no inverse function);
+ *   w[k] = (v_i[k] - v_b[k]) - g[k] dt;                                   r[3 + k] = (Rw_b^T w)[k] - dv[k];
+ *   w[k] = ((p_i[k] - p_b[k]) - v_b[k] dt) - (0.5 g[k]) (dt dt);          r[6 + k] = (Rw_b^T w)[k] - dp[k];
+ * a residual that is not finite: VIS_IMF_NONFINITE.  A = the 9 x 9 of d_cov[i].S with var_rot, var_v, var_p added to its diagonal by threes (one
+ * addition an entry); A y = r by LDL^T (9) and A[0..2][0..2] y3 = r[0..2] by LDL^T (3); a failed solve: VIS_IMF_SINGULAR; chi2 = r[0] y[0] + r[1] y[1]
+ * + ... + r[8] y[8] summed left to right, chi2_rot = (r[0] y3[0] + r[1] y3[1]) + r[2] y3[2]; one that is not finite: VIS_IMF_NONFINITE.  Every flagged
+ * record is all zeros but for its flags and q.  For a calibrated covariance and exact states chi2 has mean 9 and chi2_rot mean 3.
+ * k_imu_factor, one lane per frame, asynchronous, no workspace.  Out of scope: the factor of a pair whose parent is the carried frame (the parent's
+ * state and tail would have to be carried across launches), covariance-weighted alignment, feeding anything back. */
+enum { VIS_IMF_OK = 0, VIS_IMF_NO_PARENT = 1, VIS_IMF_NO_STATE = 2, VIS_IMF_NO_ALIGN = 4, VIS_IMF_UNUSABLE = 8, VIS_IMF_SINGULAR = 16, VIS_IMF_NONFINITE = 32 };
+typedef struct vis_imu_factor_params {   /* 24 bytes; every field finite and >= 0 */
+    double var_rot, var_v, var_p;        /* 0, 0, 0       added to the diagonal of S: the variance of the visual pose's own error in rad^2, (m/s)^2, m^2 */
+} vis_imu_factor_params;
+typedef struct vis_imu_factor { double r[9], chi2, chi2_rot; int32_t flags, q; } vis_imu_factor;                           /* 96 bytes */
+void vis_default_imu_factor_params(vis_imu_factor_params* fp);
+/* Caller rows, DEVICE pointers, asynchronous on the context's stream, no workspace.  d_prev, d_traj, d_delta, d_cov, d_state, d_factor: n entries;
+ * d_result: ONE vis_vi_align record.  Of vp, r_ic, p_ci and reject are used.
+ * Refusals, in this order.  VIS_E_INVALID: vp NULL or out of range; fp NULL or out of range; a NULL d_prev, d_traj, d_delta, d_cov, d_state, d_result
+ * or d_factor; a pointer that is not aligned (8 bytes; d_prev 4); n negative.  VIS_E_STATE without a context.  VIS_E_CAPACITY when n > VIS_VIA_MAX_FRAMES. */
+int  vis_imu_factor_rows(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, const int32_t* d_prev,
+                         const vis_traj_pose* d_traj, const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state,
+                         const vis_vi_align* d_result, vis_imu_factor* d_factor);
+/* The frames of the last vis_batch_run (with VIS_STAGE_POSE; n = its frames) with vis_batch_get_keyframes' pairing, on the POSE stream through the
+ * follow-up scaffold: queued behind vis_batch_trajectory, vis_batch_imu_cov and vis_batch_vi_align (or vis_batch_vi_align_ba) of the run, it reads
+ * their buffers with no host step.  The caller's buffers are in use until vis_batch_sync.
+ * Refusals as above without d_prev; VIS_E_STATE: no context / plan / pose stage, or n differs. */
+int  vis_batch_imu_factor(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, const vis_traj_pose* d_traj,
+                          const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state, const vis_vi_align* d_result,
+                          vis_imu_factor* d_factor);
 
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */

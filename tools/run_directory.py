@@ -62,6 +62,13 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              LAST batch's record: flags (VIS_VIA_*), pairs, triples, dbg, s, g, |g_lin|, rms.
   --imu-jac out.csv: with --imu, integrate with the bias Jacobians of v and p (vis_batch_imu_jac in vis_batch_imu's place: the same deltas).  One row per
              frame -- frame index, timestamp, flags (VIS_IMU_JAC_*), q, Jvg (9), Jva (9), Jpg (9), Jpa (9).
+  --imu-cov out.csv [--imu-noise SG,SA]: with --imu, the 9 x 9 covariance of every delta's error (dphi, dv, dp) (vis_batch_imu_cov queued beside the
+             integration above, with carried records of its own; SG, SA: the gyro and accelerometer noise densities in rad/s/sqrt(Hz) and
+             m/s^2/sqrt(Hz), default EuRoC's 1.6968e-4,2.0e-3).  One row per frame -- frame index, timestamp, flags (VIS_IMU_COV_*), q, the 45 numbers
+             of the upper triangle in row order.
+  --imu-factor out.csv: with --imu-cov and --vi-align or --vi-align-ba, the inertial factor of every pair (vis_batch_imu_factor queued behind the
+             covariance and the alignment of the batch: --vi-align-ba's record and states when both alignments run).  One row per frame -- frame index,
+             timestamp, flags (VIS_IMF_*), q, chi2, chi2_rot, r (9); the JSON line counts the solved factors and gives their median chi2.
   --recorrect: with --vi-align and --imu-jac, close the loop on the device: align, correct the batch's deltas for the estimated gyro bias
              (vis_batch_imu_correct reads dbg from the alignment's record), align again on the corrected records.  The states and the JSON record are
              the second alignment's; the JSON line adds the first alignment's dbg, c0_call and c1 and the number of records corrected in the last batch.
@@ -138,6 +145,9 @@ def main():
     ap.add_argument("--imu", default=None, metavar="CSV", help="EuRoC imu0/data.csv: timestamp [ns], w, a")
     ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
     ap.add_argument("--imu-jac", default=None, metavar="CSV", help="with --imu: write every frame's bias Jacobians of v and p here")
+    ap.add_argument("--imu-cov", default=None, metavar="CSV", help="with --imu: write every frame's 9 x 9 covariance of the delta here")
+    ap.add_argument("--imu-noise", default=None, metavar="SG,SA", help="with --imu-cov: the gyro and accelerometer noise densities (default EuRoC's)")
+    ap.add_argument("--imu-factor", default=None, metavar="CSV", help="with --imu-cov and --vi-align / --vi-align-ba: write every pair's inertial factor here")
     ap.add_argument("--recorrect", action="store_true", help="with --vi-align and --imu-jac: align, correct the deltas for dbg, align again")
     ap.add_argument("--vi-align-ba", default=None, metavar="CSV", help="with --imu, --imu-jac and --trajectory: align with the accelerometer bias; states here")
     ap.add_argument("--vi-align", default=None, metavar="CSV", help="with --imu and --trajectory: gyro bias, gravity, metric scale; one state per frame here")
@@ -236,8 +246,21 @@ def main():
         if a.imu_jac:
             d_ijac, jac_rows = torch.zeros(B * 296, dtype=torch.uint8, device="cuda"), []
             torch.cuda.synchronize()
+        if a.imu_cov:
+            d_icov, d_cdelta, cov_rows = torch.zeros(B * 368, dtype=torch.uint8, device="cuda"), torch.zeros(B * 216, dtype=torch.uint8, device="cuda"), []
+            noise = vislam.default_imu_noise()
+            if a.imu_noise:
+                noise.sigma_g, noise.sigma_a = (float(v) for v in a.imu_noise.split(","))
+            torch.cuda.synchronize()
     if a.imu_jac and not a.imu:
         raise SystemExit("--imu-jac needs --imu")
+    if (a.imu_cov and not a.imu) or (a.imu_noise and not a.imu_cov):
+        raise SystemExit("--imu-cov needs --imu, --imu-noise needs --imu-cov")
+    if a.imu_factor:
+        if not (a.imu_cov and (a.vi_align or a.vi_align_ba)):
+            raise SystemExit("--imu-factor needs --imu-cov and --vi-align or --vi-align-ba")
+        d_ifac, fac_rows = torch.zeros(B * 96, dtype=torch.uint8, device="cuda"), []
+        torch.cuda.synchronize()
     if a.recorrect and not ((a.vi_align or a.vi_align_ba) and a.imu_jac):
         raise SystemExit("--recorrect needs --vi-align and --imu-jac")
     if a.vi_align_ba:
@@ -360,6 +383,9 @@ def main():
                               d_irot.data_ptr())
         elif a.imu:
             ctx.batch_imu(nb, d_isamples.data_ptr() if len(imu_s) else 0, len(imu_s), d_itf.data_ptr() + 8 * first, d_idelta.data_ptr(), d_irot.data_ptr())
+        if a.imu and a.imu_cov:                              # (a caller who wants the covariance beside the deltas or the Jacobians queues both)
+            ctx.batch_imu_cov(nb, d_isamples.data_ptr() if len(imu_s) else 0, len(imu_s), d_itf.data_ptr() + 8 * first, d_cdelta.data_ptr(), d_icov.data_ptr(),
+                              noise=noise)
         if a.trajectory:                                     # run -> triangulate -> scale links -> trajectory -> ftrack -> N-view triangulation: no host step
             ctx.batch_triangulate(nb, jcap, d_jmp.data_ptr(), d_jmf.data_ptr(), d_jms.data_ptr())
             ctx.batch_scale_links(nb, d_jmp.data_ptr(), d_jmf.data_ptr(), jcap, d_jlink.data_ptr())
@@ -379,6 +405,9 @@ def main():
             ctx.batch_vi_align_ba(nb, d_jtraj.data_ptr(), d_bdelta2.data_ptr(), d_ijac.data_ptr(), d_bres.data_ptr(), d_bstate.data_ptr())
         elif a.vi_align_ba:
             ctx.batch_vi_align_ba(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_ijac.data_ptr(), d_bres.data_ptr(), d_bstate.data_ptr())
+        if a.imu_factor:                                     # behind the covariance and the alignment of the batch: their buffers, no host step
+            d_fres, d_fstate = (d_bres, d_bstate) if a.vi_align_ba else (d_vres, d_vstate)
+            ctx.batch_imu_factor(nb, d_jtraj.data_ptr(), d_cdelta.data_ptr(), d_icov.data_ptr(), d_fstate.data_ptr(), d_fres.data_ptr(), d_ifac.data_ptr())
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
@@ -452,6 +481,13 @@ def main():
             if a.imu_jac:
                 ijc = d_ijac.cpu().numpy().view(vislam.IMU_BIAS_JAC_DTYPE)
                 jac_rows += [(first + i, stamps[first + i], ijc[i].copy()) for i in range(nb)]
+            if a.imu_cov:
+                icv = d_icov.cpu().numpy().view(vislam.IMU_COV_DTYPE)
+                assert d_cdelta.cpu().numpy()[:nb * 216].tobytes() == idl[:nb].tobytes()      # a covariance never changes a delta
+                cov_rows += [(first + i, stamps[first + i], icv[i].copy()) for i in range(nb)]
+            if a.imu_factor:
+                ifc = d_ifac.cpu().numpy().view(vislam.IMU_FACTOR_DTYPE)
+                fac_rows += [(first + i, stamps[first + i], ifc[i].copy()) for i in range(nb)]
         if a.vi_align:
             vst, via_last = d_vstate.cpu().numpy().view(vislam.VI_STATE_DTYPE), d_vres.cpu().numpy().view(vislam.VI_ALIGN_DTYPE)[0].copy()
             via_rows += [(first + i, stamps[first + i], vst[i].copy()) for i in range(nb)]
@@ -596,6 +632,19 @@ def main():
                     dbl = list(r["Jvg"]) + list(r["Jva"]) + list(r["Jpg"]) + list(r["Jpa"])
                     f.write("%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"]) + ",".join("%.17g" % v for v in dbl) + "\n")
             out["imu_jac_csv"] = a.imu_jac
+        if a.imu_cov:
+            with open(a.imu_cov, "w") as f:                     # frame, stamp, flags, q, the 45 of the upper triangle
+                for fi, ts, r in cov_rows:
+                    f.write("%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"]) + ",".join("%.17g" % v for v in r["S"]) + "\n")
+            out["imu_cov_csv"] = a.imu_cov
+            out["imu_noise"] = [noise.sigma_g, noise.sigma_a]
+        if a.imu_factor:
+            with open(a.imu_factor, "w") as f:                  # frame, stamp, flags, q, chi2, chi2_rot, r
+                for fi, ts, r in fac_rows:
+                    f.write("%d,%d,%d,%d," % (fi, ts, r["flags"], r["q"]) + ",".join("%.17g" % v for v in [r["chi2"], r["chi2_rot"]] + list(r["r"])) + "\n")
+            solved = [float(r["chi2"]) for _, _, r in fac_rows if int(r["flags"]) == 0]
+            out["imu_factor_csv"] = a.imu_factor
+            out["imu_factor"] = dict(solved=len(solved), median_chi2=float(np.median(solved)) if solved else None)
     if a.vi_align:
         with open(a.vi_align, "w") as f:                        # frame, stamp, flags, q, res, p, v
             for fi, ts, r in via_rows:

@@ -142,7 +142,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
     plan_destroy(ctx->single); plan_destroy(ctx->batch);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws, &ctx->imuj_ws}) if (b->p) (void)hipFree(b->p);
+    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws, &ctx->imuj_ws, &ctx->imuc_ws}) if (b->p) (void)hipFree(b->p);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);
@@ -273,7 +273,7 @@ void plan_destroy(Plan* pl) {
         F(pl->d_cand[l]); F(pl->d_seg_kp[l]);
     }
     F(pl->d_fast_tiles); F(pl->d_tile_cnt); F(pl->d_seg_cnt); F(pl->d_flags); F(pl->d_angle_tab); for (Plan::GradSet& g : pl->grad) { F(g.half); F(g.gx); F(g.gy); F(g.g); } F(pl->d_tau); F(pl->d_seg_cut); F(pl->d_fix);
-    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_imuj_ws); F(pl->d_via_ws); F(pl->d_viab_ws);
+    F(pl->d_kps); F(pl->d_desc); F(pl->d_nkp); F(pl->d_descx); F(pl->d_warp); F(pl->d_pnp_ws); F(pl->d_ft_ws); F(pl->d_tj_ws); F(pl->d_imu_ws); F(pl->d_imuj_ws); F(pl->d_imuc_ws); F(pl->d_via_ws); F(pl->d_viab_ws);
     for (Plan::RecordSet& r : pl->rec) { F(r.pq); F(r.pt); F(r.pqn); F(r.gq); F(r.kf_link); }
     F(pl->d_kf_state);
     F(pl->snap.gray); F(pl->d_track_state);
@@ -1272,6 +1272,7 @@ extern "C" int vis_batch_reset(vis_ctx* ctx) {
     { const int rc = reset_keyframe_state(ctx, ctx->batch); if (rc) return rc; }   // keyframe gate: nothing saved, nothing carried
     ctx->batch->seq_next = ctx->batch->seq0 = 0; ctx->batch->ft.forget();   // vis_batch_ftrack: no carried row, seq restarts at 0
     ctx->batch->sl.forget(); ctx->batch->tj.forget();              // scale links / trajectory: nothing carried
+    ctx->batch->imuc.forget();                                     // vis_batch_imu_cov: the same
     ctx->batch->imuj.forget();                                     // vis_batch_imu_jac: the same
     ctx->batch->imu.forget();                                      // vis_batch_imu: no carried time, no open delta
     ctx->batch->via.forget();                                      // vis_batch_vi_align: no carried sums, no tails
@@ -1871,7 +1872,7 @@ extern "C" int vis_pnp_batch(vis_ctx* ctx, const vis_pnp_params* pp, int n, cons
     return pnp_batch_run(ctx, pp, n, max_pts, d_X, x_stride, d_xy, d_npts, d_draws, row_cap, d_mask, d_out);
 }
 
-// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_imuj_ws, d_via_ws, d_viab_ws), in ONE place: the list is measured and the block allocated by the
+// A plan's lazily allocated block (Plan::d_pnp_ws, d_ft_ws, d_tj_ws, d_imu_ws, d_imuj_ws, d_imuc_ws, d_via_ws, d_viab_ws), in ONE place: the list is measured and the block allocated by the
 // first call of the plan that needs it; every call binds the list to the block, into a work struct of its own.  The block is never replaced.
 template <class Layout> static int plan_block(vis_ctx* ctx, void*& block, const char* who, Layout&& layout) {
     if (!block) {
@@ -2375,6 +2376,114 @@ extern "C" int vis_batch_imu_jac_init(vis_ctx* ctx, const vis_imu_jac_carry* rec
     return VIS_OK;
 }
 
+// ---- the same three calls with the 9 x 9 covariance of the delta (k_imu_cov_intervals, k_imu_cov_pairs, a table and carried records of their own)
+extern "C" void vis_default_imu_noise(vis_imu_noise* np) {
+    if (!np) return;
+    np->sigma_g = 1.6968e-4; np->sigma_a = 2.0e-3;
+}
+
+static bool imu_noise_ok(const vis_imu_noise* np) {
+    return np && std::isfinite(np->sigma_g) && std::isfinite(np->sigma_a) && np->sigma_g >= 0.0 && np->sigma_a >= 0.0;
+}
+
+extern "C" int vis_imu_preintegrate_cov_rows(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, int n, const vis_imu_sample* d_samples, int n_samples,
+                                             const double* d_tframe, const int32_t* d_prev, const vis_imu_cov_carry* d_carry_in, vis_imu_delta* d_delta,
+                                             vis_imu_cov* d_cov, float* d_rot, vis_imu_cov_carry* d_carry_out) {
+    if (!imu_params_ok(ip) || !imu_noise_ok(np) || !d_tframe || !d_prev || !d_delta || !d_cov || (n_samples > 0 && !d_samples)) return VIS_E_INVALID;
+    if (!aligned(d_samples, 8) || !aligned(d_tframe, 8) || !aligned(d_carry_in, 8) || !aligned(d_delta, 8) || !aligned(d_cov, 8) || !aligned(d_carry_out, 8) ||
+        !aligned(d_prev, 4) || !aligned(d_rot, 4)) return VIS_E_INVALID;
+    if (n < 0 || n_samples < 0 || (d_carry_out && d_carry_out == d_carry_in)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES) { ctx->err = "vis_imu_preintegrate_cov_rows: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    if (n == 0) return VIS_OK;
+    (void)hipSetDevice(ctx->device);
+    const int rc = vis_grow_block(ctx, ctx->imuc_ws, imu_cov_table_bytes(n), "vis_imu_preintegrate_cov_rows");
+    if (rc) return rc;
+    return imu_cov_launch(ctx, ip, np, n, FtFrames{d_prev, 0, nullptr}, d_samples, n_samples, d_tframe, d_carry_in, ctx->imuc_ws.p, d_delta, d_cov, d_rot, d_carry_out);
+}
+
+extern "C" int vis_imu_preintegrate_cov(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, const vis_imu_sample* samples, int n_samples, double t_a,
+                                        double t_b, vis_imu_delta* delta, vis_imu_cov* cov, float* rot) {
+    if (!imu_params_ok(ip) || !imu_noise_ok(np) || !delta || !cov || n_samples < 0 || (n_samples > 0 && !samples)) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    int rc = vis_grow_block(ctx, ctx->imuc_ws, imu_cov_table_bytes(1), "vis_imu_preintegrate_cov");
+    if (rc) return rc;
+    vis_imu_sample* d_s; double* d_t; int32_t* d_prev; vis_imu_cov_carry* d_c; vis_imu_delta* d_d; vis_imu_cov* d_v; float* d_r;
+    rc = vis_carve(ctx, [&](Carver& cv) {
+        d_s = cv.take<vis_imu_sample>((size_t)std::max(n_samples, 1)); d_t = cv.take<double>(1); d_prev = cv.take<int32_t>(1);
+        d_c = cv.take<vis_imu_cov_carry>(1); d_d = cv.take<vis_imu_delta>(1); d_v = cv.take<vis_imu_cov>(1); d_r = cv.take<float>(9);
+    });
+    if (rc) return rc;
+    vis_imu_cov_carry c;
+    std::memset(&c, 0, sizeof(c));
+    c.carry.t_last = t_a; c.carry.valid = VIS_IMU_CARRY_TIME;
+    const int32_t prev = VIS_KF_CARRIED;
+    HostStage hs(ctx);
+    hs.up(d_s, samples, (size_t)n_samples * sizeof(vis_imu_sample));
+    hs.up(d_t, &t_b, sizeof(t_b));
+    hs.up(d_prev, &prev, sizeof(prev));
+    hs.up(d_c, &c, sizeof(c));
+    hs.flush_ups();
+    rc = imu_cov_launch(ctx, ip, np, 1, FtFrames{d_prev, 0, nullptr}, d_s, n_samples, d_t, d_c, ctx->imuc_ws.p, d_d, d_v, d_r, nullptr);
+    if (rc) return vis_drain(ctx, rc);
+    const void* h_d = hs.down(d_d, sizeof(vis_imu_delta));
+    const void* h_v = hs.down(d_v, sizeof(vis_imu_cov));
+    const void* h_r = hs.down(d_r, 9 * sizeof(float));
+    rc = hs.wait();
+    if (rc) return rc;
+    std::memcpy(delta, h_d, sizeof(vis_imu_delta));
+    std::memcpy(cov, h_v, sizeof(vis_imu_cov));
+    if (rot) std::memcpy(rot, h_r, 9 * sizeof(float));
+    return VIS_OK;
+}
+
+// the plan's block: the 71-slot lifting table for B frames and the two carried records
+struct ImuCovPlanWork { void* table; vis_imu_cov_carry* carry[2]; };
+static int ensure_imu_cov(vis_ctx* ctx, Plan* pl, ImuCovPlanWork& W) {
+    return plan_block(ctx, pl->d_imuc_ws, "vis_batch_imu_cov", [&](Carver& cv) {
+        W.table = cv.take<char>(imu_cov_table_bytes(pl->B)); W.carry[0] = cv.take<vis_imu_cov_carry>(1); W.carry[1] = cv.take<vis_imu_cov_carry>(1);
+    });
+}
+
+extern "C" int vis_batch_imu_cov(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, int n, const vis_imu_sample* d_samples, int n_samples,
+                                 const double* d_tframe, vis_imu_delta* d_delta, vis_imu_cov* d_cov, float* d_rot) {
+    if (!imu_params_ok(ip) || !imu_noise_ok(np) || !d_tframe || !d_delta || !d_cov || (n_samples > 0 && !d_samples)) return VIS_E_INVALID;
+    if (!aligned(d_samples, 8) || !aligned(d_tframe, 8) || !aligned(d_delta, 8) || !aligned(d_cov, 8) || !aligned(d_rot, 4) || n < 0 || n_samples < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_imu_cov: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_IMU_MAX_FRAMES || n > pl->B) { ctx->err = "vis_batch_imu_cov: more than VIS_IMU_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    ImuCovPlanWork W;
+    { const int rc = ensure_imu_cov(ctx, pl, W); if (rc) return rc; }
+    const Turn::Pick rec = pl->imuc.pick(pl->run_count);
+    // on the pose stream behind the matcher of the run (the gate's link table) and behind the context's stream (the caller's samples and times)
+    const int rc = batch_epi(ctx, n, "vis_batch_imu_cov", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = imu_cov_launch(ctx, ip, np, n, plan_frames(pl_), d_samples, n_samples, d_tframe, rec.have ? W.carry[rec.slot] : nullptr, W.table, d_delta, d_cov,
+                                       d_rot, W.carry[rec.slot ^ 1]);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, true);
+    if (rc) return rc;
+    pl->imuc.commit(rec, pl->run_count);
+    return VIS_OK;
+}
+
+extern "C" int vis_batch_imu_cov_init(vis_ctx* ctx, const vis_imu_cov_carry* rec) {
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    (void)hipSetDevice(ctx->device);
+    sync_all(ctx);                                                 // (a kernel in flight reads and writes the records)
+    Plan* pl = ctx->batch;
+    ImuCovPlanWork W;
+    { const int rc = ensure_imu_cov(ctx, pl, W); if (rc) return rc; }
+    if (!rec) { pl->imuc.forget(); return VIS_OK; }
+    HIPCHK(ctx, hipMemcpy(W.carry[pl->imuc.seed_slot()], rec, sizeof(*rec), hipMemcpyHostToDevice));
+    pl->imuc.seeded(pl->run_count);
+    return VIS_OK;
+}
+
 static int imu_correct_args(const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg, const double* d_dba,
                             vis_imu_delta* d_delta_out, float* d_rot_out, int32_t* d_status) {
     if (!imu_params_ok(ip) || !d_delta || !d_jac || !d_dbg || !d_delta_out) return VIS_E_INVALID;
@@ -2438,6 +2547,53 @@ extern "C" int vis_vi_align_rows(vis_ctx* ctx, const vis_vi_align_params* vp, in
     if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_vi_align_rows: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
     (void)hipSetDevice(ctx->device);
     return via_launch(ctx, vp, n, FtFrames{d_prev, 0, nullptr}, d_traj, d_delta, d_carry_in, d_state, d_result, d_carry_out);
+}
+
+// ---- the inertial factor of a pair (k_imu_factor, vi_align.hip)
+extern "C" void vis_default_imu_factor_params(vis_imu_factor_params* fp) {
+    if (!fp) return;
+    fp->var_rot = fp->var_v = fp->var_p = 0.0;
+}
+
+// (rows: the caller-rows form, which also takes d_prev)
+static int imu_factor_args(const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, bool rows, const int32_t* d_prev, const vis_traj_pose* d_traj,
+                           const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state, const vis_vi_align* d_result,
+                           const vis_imu_factor* d_factor) {
+    if (!vi_align_params_ok(vp)) return VIS_E_INVALID;
+    if (!fp || !std::isfinite(fp->var_rot) || !std::isfinite(fp->var_v) || !std::isfinite(fp->var_p) || fp->var_rot < 0.0 || fp->var_v < 0.0 || fp->var_p < 0.0)
+        return VIS_E_INVALID;
+    if ((rows && !d_prev) || !d_traj || !d_delta || !d_cov || !d_state || !d_result || !d_factor) return VIS_E_INVALID;
+    if (!aligned(d_traj, 8) || !aligned(d_delta, 8) || !aligned(d_cov, 8) || !aligned(d_state, 8) || !aligned(d_result, 8) || !aligned(d_factor, 8) ||
+        !aligned(d_prev, 4)) return VIS_E_INVALID;
+    return n < 0 ? VIS_E_INVALID : VIS_OK;
+}
+
+extern "C" int vis_imu_factor_rows(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, const int32_t* d_prev,
+                                   const vis_traj_pose* d_traj, const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state,
+                                   const vis_vi_align* d_result, vis_imu_factor* d_factor) {
+    { const int rc = imu_factor_args(vp, fp, n, true, d_prev, d_traj, d_delta, d_cov, d_state, d_result, d_factor); if (rc) return rc; }
+    if (!ctx) return VIS_E_STATE;
+    if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_imu_factor_rows: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return imu_factor_launch(ctx, vp, fp, n, FtFrames{d_prev, 0, nullptr}, d_traj, d_delta, d_cov, d_state, d_result, d_factor);
+}
+
+extern "C" int vis_batch_imu_factor(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, const vis_traj_pose* d_traj,
+                                    const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state, const vis_vi_align* d_result,
+                                    vis_imu_factor* d_factor) {
+    { const int rc = imu_factor_args(vp, fp, n, false, nullptr, d_traj, d_delta, d_cov, d_state, d_result, d_factor); if (rc) return rc; }
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (!(pl->last_stages & VIS_STAGE_POSE)) { ctx->err = "vis_batch_imu_factor: the last vis_batch_run had no VIS_STAGE_POSE"; return VIS_E_STATE; }
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (n > VIS_VIA_MAX_FRAMES) { ctx->err = "vis_batch_imu_factor: more than VIS_VIA_MAX_FRAMES frames"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    // on the pose stream behind vis_batch_trajectory, vis_batch_imu_cov and vis_batch_vi_align of the run, which wrote every input there
+    return batch_epi(ctx, n, "vis_batch_imu_factor", [&](Plan* pl_, Plan::MatchOut&, const int32_t*) {
+        const int rc2 = imu_factor_launch(ctx, vp, fp, n, plan_frames(pl_), d_traj, d_delta, d_cov, d_state, d_result, d_factor);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    });
 }
 
 // the plan's block: the two carried records

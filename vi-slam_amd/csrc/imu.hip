@@ -9,6 +9,9 @@
 // table of their own of 62 slots: the 26 above, then Jvg, Jva, Jpg, Jpa (9 doubles each); the Jacobian flags ride in bits 16 and up of the flags half
 // of slot 25 (a table entry's delta flags come from intervals alone and stay below bit 9).  A composition folds one block at a time into the
 // accumulator: two whole entries are never held.  k_imu_correct applies a bias step to the records, a lane per frame.
+// The covariance variants (k_imu_cov_intervals, k_imu_cov_pairs: vis_imu_preintegrate_cov_rows, vis_batch_imu_cov) share the kernels' bodies
+// (imu_intervals_body, imu_pairs_body) and carry the 9 x 9 covariance of (dphi, dv, dp) as six 3 x 3 blocks in a table of 71 slots: the 26, then
+// A (6), B (9), C (6), D (9), E (9), F (6); the covariance flags ride where the Jacobian flags do.
 #include "vis_internal.h"
 #include <cmath>
 
@@ -22,6 +25,10 @@ template <bool JAC> struct ImuJacOf { typedef ImuNoJac type; };
 template <> struct ImuJacOf<true> { typedef ImuJac type; };
 // what the Jacobian variants read and write beside the delta's rows: the carried open delta's Jacobians, the rows, the carry's
 struct ImuJacIO { const vis_imu_bias_jac* cin; vis_imu_bias_jac* rows; vis_imu_bias_jac* cout; };
+// the covariance of (dphi, dv, dp) by 3 x 3 blocks: A phi-phi, C v-v, F p-p (upper triangles 00 01 02 11 12 22), B v-phi, D p-phi, E p-v (full, row-major);
+// sg2, sa2: the squared densities, carried beside the accumulator so that the sub-step's hook needs no further argument
+struct ImuCov { double A[6], B[9], C[6], D[9], E[9], F[6]; int flags; double sg2, sa2; };
+struct ImuCovIO { const vis_imu_cov* cin; vis_imu_cov* rows; vis_imu_cov* cout; };
 #define IMU_VOID_FLAGS (VIS_IMU_NO_PAIR | VIS_IMU_NO_CARRY | VIS_IMU_NO_START | VIS_IMU_NONFINITE)
 
 __device__ __forceinline__ bool imu_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }     // false for NaN and +-inf
@@ -236,6 +243,240 @@ __device__ __forceinline__ void imu_jac_record(const ImuNoJac&, int, vis_imu_bia
 __device__ __forceinline__ void imu_jac_clear(ImuJac& q) { imu_jac_zero(q); q.flags = 0; }
 __device__ __forceinline__ void imu_jac_clear(ImuNoJac&) {}
 
+// ---- the covariance of (dphi, dv, dp): include/vislam_hip.h "THE COVARIANCE", restated by tests/imu_cov_ref.py.  The overloads below carry the names of the
+// Jacobians' (imu_jac_clear, _settle, _record, imu_entry_*, imu_carry_fold, imu_substep_jac) so that the sub-step, the lifting and the kernels' bodies are shared
+#define IMU_COV_SLOTS 71
+__device__ __forceinline__ void imu_mult(const double* A, const double* B, double* M) {       // A B^T
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) M[3 * r + c] = (A[3 * r] * B[3 * c] + A[3 * r + 1] * B[3 * c + 1]) + A[3 * r + 2] * B[3 * c + 2];
+}
+__device__ __forceinline__ void imu_mskew(const double* M, const double* u, double* S) {      // M [u]x
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        S[3 * r] = M[3 * r + 1] * u[2] - M[3 * r + 2] * u[1];
+        S[3 * r + 1] = M[3 * r + 2] * u[0] - M[3 * r] * u[2];
+        S[3 * r + 2] = M[3 * r] * u[1] - M[3 * r + 1] * u[0];
+    }
+}
+__device__ __forceinline__ constexpr int imu_up(int j) { return j < 3 ? j : (j < 5 ? j + 1 : 8); }             // entry j of an upper triangle in the full matrix
+__device__ __forceinline__ constexpr int imu_sym(int i, int j) { return i * 3 - i * (i - 1) / 2 + (j - i); }    // i <= j
+__device__ __forceinline__ constexpr int imu_idx9(int r, int c) { return r * 9 - r * (r - 1) / 2 + (c - r); }   // r <= c, the 45 of vis_imu_cov
+__device__ __forceinline__ void imu_sym_full(const double* s, double* M) {
+    M[0] = s[0]; M[1] = s[1]; M[2] = s[2]; M[3] = s[1]; M[4] = s[3]; M[5] = s[4]; M[6] = s[2]; M[7] = s[4]; M[8] = s[5];
+}
+__device__ __forceinline__ void imu_cov_zero(ImuCov& q) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.B[k] = q.D[k] = q.E[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) q.A[k] = q.C[k] = q.F[k] = 0.0;
+}
+__device__ __forceinline__ void imu_jac_clear(ImuCov& q) { imu_cov_zero(q); q.flags = 0; }
+__device__ __forceinline__ void imu_jac_settle(int dflags, ImuCov& q) {
+    bool zero = (dflags & IMU_VOID_FLAGS) || (q.flags & VIS_IMU_COV_NONFINITE);
+    if (!zero) {
+        bool fin = true;
+#pragma unroll
+        for (int k = 0; k < 9; k++) fin = fin && imu_finite(q.B[k]) && imu_finite(q.D[k]) && imu_finite(q.E[k]);
+#pragma unroll
+        for (int k = 0; k < 6; k++) fin = fin && imu_finite(q.A[k]) && imu_finite(q.C[k]) && imu_finite(q.F[k]);
+        if (!fin) { q.flags |= VIS_IMU_COV_NONFINITE; zero = true; }
+    }
+    if (zero) imu_cov_zero(q);
+}
+// block blk (0 A, 1 B, 2 C, 3 D, 4 E, 5 F) as a full 3 x 3: of an accumulator, of a record's 45, of entry i of a 71-slot table
+__device__ __forceinline__ void imu_cov_block(const ImuCov& q, int blk, double* M) {
+    if (blk == 0) imu_sym_full(q.A, M);
+    else if (blk == 2) imu_sym_full(q.C, M);
+    else if (blk == 5) imu_sym_full(q.F, M);
+    else {
+        const double* s = blk == 1 ? q.B : (blk == 3 ? q.D : q.E);
+#pragma unroll
+        for (int k = 0; k < 9; k++) M[k] = s[k];
+    }
+}
+__device__ __forceinline__ void imu_cov_rec_block(const double* S, int blk, double* M) {
+    const int bi = blk == 0 ? 0 : (blk < 3 ? 1 : 2), bj = (blk == 0 || blk == 1 || blk == 3) ? 0 : (blk == 5 ? 2 : 1);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int r = 3 * bi + i, c = 3 * bj + j;
+            M[3 * i + j] = S[imu_idx9(r < c ? r : c, r < c ? c : r)];
+        }
+}
+__device__ __forceinline__ constexpr int imu_cov_off(int blk) { return 26 + (blk == 0 ? 0 : (blk == 1 ? 6 : (blk == 2 ? 15 : (blk == 3 ? 21 : (blk == 4 ? 30 : 39))))); }
+__device__ __forceinline__ void imu_cov_ws_block(const unsigned long long* ws, int n, int level, int i, int blk, double* M) {
+    const unsigned long long* p = ws + ((size_t)level * IMU_COV_SLOTS + imu_cov_off(blk)) * n + i;
+    if (blk == 0 || blk == 2 || blk == 5) {
+        double s[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) s[k] = __longlong_as_double((long long)p[(size_t)k * n]);
+        imu_sym_full(s, M);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 9; k++) M[k] = __longlong_as_double((long long)p[(size_t)k * n]);
+    }
+}
+// F X F^T added to q, one block at a time, for F = [a 0 0; b I 0; c t I] with a = M^T; X's blocks come through ldx(blk, full 3 x 3)
+template <class LoadX> __device__ __forceinline__ void imu_cov_fterm(const double* M, const double* b, const double* c, double t, LoadX ldx, ImuCov& q) {
+    double A[9], B[9], U[9], V[9], Y[9], T[9], W[9];
+    ldx(0, A); ldx(1, B);
+    imu_mul(A, M, T); imu_tmul(M, T, W);
+#pragma unroll
+    for (int j = 0; j < 6; j++) q.A[j] = W[imu_up(j)] + q.A[j];
+    imu_mul(b, A, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) U[k] = T[k] + B[k];
+    imu_mul(U, M, W);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.B[k] = W[k] + q.B[k];
+    {
+        double C[9];
+        ldx(2, C);
+        imu_mult(U, b, W); imu_mult(b, B, T);
+#pragma unroll
+        for (int j = 0; j < 6; j++) q.C[j] = (W[imu_up(j)] + (T[imu_up(j)] + C[imu_up(j)])) + q.C[j];
+        imu_mult(c, B, T);
+#pragma unroll
+        for (int k = 0; k < 9; k++) Y[k] = T[k] + t * C[k];
+    }
+    double D[9], E[9];
+    ldx(3, D);
+    imu_mul(c, A, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) V[k] = (T[k] + t * B[k]) + D[k];
+    imu_mul(V, M, W);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.D[k] = W[k] + q.D[k];
+    ldx(4, E);
+#pragma unroll
+    for (int k = 0; k < 9; k++) Y[k] = Y[k] + E[k];
+    imu_mult(V, b, W);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.E[k] = (W[k] + Y[k]) + q.E[k];
+    ldx(5, A);                                                     // (A is done with: the p-p block of X)
+    imu_mult(c, D, T); imu_mult(V, c, W);
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+#pragma unroll
+        for (int j = i; j < 3; j++) {
+            const double Z = (T[3 * i + j] + t * E[3 * j + i]) + A[3 * i + j];
+            q.F[imu_sym(i, j)] = ((W[3 * i + j] + t * Y[3 * i + j]) + Z) + q.F[imu_sym(i, j)];
+        }
+}
+// the covariance's share of a sub-step, BEFORE R moves on: the noise of the step, then F S F^T added
+__device__ __forceinline__ void imu_substep_jac(ImuCov& q, const double* R, const double*, const double* Rn, const double*, const double* dR, const double* Jr,
+                                                const double* u0, const double* u1, double h) {
+    const double hh = 0.5 * h, qg = q.sg2 / h, qa = q.sa2 / h;
+    double S0[9], S1[9], T[9], b[9], c[9], K1[9], K2[9], K3[9], N1[9], N2[9], N3[9];
+    imu_mskew(R, u0, S0); imu_mskew(Rn, u1, S1); imu_mult(S1, dR, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { b[k] = -(hh * (S0[k] + T[k])); c[k] = hh * b[k]; K1[k] = Jr[k] * h; }
+    imu_mul(S1, K1, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { K2[k] = -(hh * T[k]); K3[k] = (R[k] + Rn[k]) * hh; }
+    const ImuCov X = q;
+    imu_mult(K1, K1, N1); imu_mult(K2, K1, N2); imu_mult(K2, K2, T); imu_mult(K3, K3, N3);
+#pragma unroll
+    for (int j = 0; j < 6; j++) { q.A[j] = qg * N1[imu_up(j)]; q.C[j] = qg * T[imu_up(j)] + qa * N3[imu_up(j)]; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) { q.B[k] = qg * N2[k]; q.D[k] = hh * q.B[k]; }
+    imu_sym_full(q.C, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.E[k] = hh * T[k];
+#pragma unroll
+    for (int j = 0; j < 6; j++) q.F[j] = hh * q.E[imu_up(j)];
+    imu_cov_fterm(dR, b, c, h, [&](int blk, double* Mx) { imu_cov_block(X, blk, Mx); }, q);
+}
+// the covariance of X o Y folded into q (in: Y's, out: the composition's): G Y.S G^T in place, then F X.S F^T added block by block
+template <class LoadX> __device__ __forceinline__ void imu_cov_fold(const ImuDelta& X, int xflags, LoadX ldx, const ImuDelta& Y, int oflags, ImuCov& q) {
+    double b[9], c[9], T[9], W[9], Fl[9];
+    q.flags |= xflags;
+    imu_mul(X.R, q.B, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.B[k] = T[k];
+    imu_mul(X.R, q.D, T);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.D[k] = T[k];
+    imu_mul(X.R, q.E, T); imu_mult(T, X.R, W);
+#pragma unroll
+    for (int k = 0; k < 9; k++) q.E[k] = W[k];
+    imu_sym_full(q.C, Fl); imu_mul(X.R, Fl, T); imu_mult(T, X.R, W);
+#pragma unroll
+    for (int j = 0; j < 6; j++) q.C[j] = W[imu_up(j)];
+    imu_sym_full(q.F, Fl); imu_mul(X.R, Fl, T); imu_mult(T, X.R, W);
+#pragma unroll
+    for (int j = 0; j < 6; j++) q.F[j] = W[imu_up(j)];
+    imu_mskew(X.R, Y.v, T); imu_mskew(X.R, Y.p, W);
+#pragma unroll
+    for (int k = 0; k < 9; k++) { b[k] = -T[k]; c[k] = -W[k]; }
+    imu_cov_fterm(Y.R, b, c, Y.dt, ldx, q);
+    imu_jac_settle(oflags, q);
+}
+__device__ __forceinline__ void imu_entry_store(unsigned long long* ws, int n, int level, int i, const ImuDelta& d, const ImuCov& q) {
+    imu_ws_store<IMU_COV_SLOTS>(ws, n, level, i, d, q.flags);
+    unsigned long long* p = ws + ((size_t)level * IMU_COV_SLOTS + 26) * n + i;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        p[(size_t)k * n] = (unsigned long long)__double_as_longlong(q.A[k]);
+        p[(size_t)(15 + k) * n] = (unsigned long long)__double_as_longlong(q.C[k]);
+        p[(size_t)(39 + k) * n] = (unsigned long long)__double_as_longlong(q.F[k]);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        p[(size_t)(6 + k) * n] = (unsigned long long)__double_as_longlong(q.B[k]);
+        p[(size_t)(21 + k) * n] = (unsigned long long)__double_as_longlong(q.D[k]);
+        p[(size_t)(30 + k) * n] = (unsigned long long)__double_as_longlong(q.E[k]);
+    }
+}
+__device__ __forceinline__ void imu_entry_load(const unsigned long long* ws, int n, int level, int i, ImuDelta& d, ImuCov& q) {
+    imu_ws_load<IMU_COV_SLOTS>(ws, n, level, i, d, &q.flags);
+    const unsigned long long* p = ws + ((size_t)level * IMU_COV_SLOTS + 26) * n + i;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        q.A[k] = __longlong_as_double((long long)p[(size_t)k * n]);
+        q.C[k] = __longlong_as_double((long long)p[(size_t)(15 + k) * n]);
+        q.F[k] = __longlong_as_double((long long)p[(size_t)(39 + k) * n]);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+        q.B[k] = __longlong_as_double((long long)p[(size_t)(6 + k) * n]);
+        q.D[k] = __longlong_as_double((long long)p[(size_t)(21 + k) * n]);
+        q.E[k] = __longlong_as_double((long long)p[(size_t)(30 + k) * n]);
+    }
+    q.sg2 = q.sa2 = 0.0;
+}
+__device__ __forceinline__ void imu_entry_fold(const unsigned long long* ws, int n, int level, int pos, ImuDelta& acc, ImuCov& q) {
+    ImuDelta e, o;
+    int ef;
+    imu_ws_load<IMU_COV_SLOTS>(ws, n, level, pos, e, &ef);
+    imu_compose(e, acc, o);
+    imu_cov_fold(e, ef, [&](int blk, double* M) { imu_cov_ws_block(ws, n, level, pos, blk, M); }, acc, o.flags, q);
+    acc = o;
+}
+__device__ __forceinline__ void imu_carry_fold(const vis_imu_carry* carry, const ImuCovIO& io, ImuDelta& acc, ImuCov& q) {
+    ImuDelta c, o;
+    imu_carry_load(carry, c);
+    imu_compose(c, acc, o);
+    const vis_imu_cov* cc = io.cin;
+    imu_cov_fold(c, cc->flags, [&](int blk, double* M) { imu_cov_rec_block(cc->S, blk, M); }, acc, o.flags, q);
+    acc = o;
+}
+__device__ __forceinline__ void imu_jac_record(const ImuCov& q, int prev, vis_imu_cov* out) {
+    vis_imu_cov o;
+#pragma unroll
+    for (int r = 0; r < 9; r++)
+#pragma unroll
+        for (int c = r; c < 9; c++) {
+            const int br = r / 3, bc = c / 3, i = r % 3, j = c % 3;
+            o.S[imu_idx9(r, c)] = br == bc ? (br == 0 ? q.A : (br == 1 ? q.C : q.F))[imu_sym(i, j)] : (br == 0 ? (bc == 1 ? q.B : q.D) : q.E)[3 * j + i];
+        }
+    o.flags = q.flags; o.q = prev;
+    *out = o;
+}
+
 // ---------------------------------------------------------------------------------------------- step 1: the intervals
 struct ImuPoint { double t, w[3], a[3]; };
 __device__ __forceinline__ void imu_read(const vis_imu_sample* s, int j, ImuPoint& o) {
@@ -285,8 +526,8 @@ __device__ __forceinline__ double imu_horner(const double* c, double x) {
     return acc;
 }
 // the Jacobians' share of a sub-step, BEFORE R and JRg move on: R, J the old ones, Rn, Jn the new; p's lines use the old v Jacobians, as p uses the old v
-__device__ __forceinline__ void imu_substep_jac(ImuJac& q, const double* R, const double* J, const double* Rn, const double* Jn, const double* u0,
-                                                const double* u1, double h) {
+__device__ __forceinline__ void imu_substep_jac(ImuJac& q, const double* R, const double* J, const double* Rn, const double* Jn, const double*, const double*,
+                                                const double* u0, const double* u1, double h) {
     double S[9], G0[9], G1[9];
     imu_skmul(u0, J, S); imu_mul(R, S, G0);
     imu_skmul(u1, Jn, S); imu_mul(Rn, S, G1);
@@ -299,7 +540,8 @@ __device__ __forceinline__ void imu_substep_jac(ImuJac& q, const double* R, cons
         q.va[k] = q.va[k] + Da * h;
     }
 }
-__device__ __forceinline__ void imu_substep_jac(ImuNoJac&, const double*, const double*, const double*, const double*, const double*, const double*, double) {}
+__device__ __forceinline__ void imu_substep_jac(ImuNoJac&, const double*, const double*, const double*, const double*, const double*, const double*, const double*,
+                                                const double*, double) {}
 template <class Jac> __device__ __forceinline__ void imu_substep(ImuDelta& d, Jac& q, const vis_imu_params& P, const ImuPoint& s0, const ImuPoint& s1) {
     constexpr double cA[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_A, cB[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_B, cC[VIS_IMU_EXP_TERMS] = VIS_IMU_COEF_C;
     const double h = s1.t - s0.t;
@@ -335,20 +577,22 @@ template <class Jac> __device__ __forceinline__ void imu_substep(ImuDelta& d, Ja
     double Jn[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) Jn[k] = M[k] - Jr[k] * h;
-    imu_substep_jac(q, d.R, d.J, Rn, Jn, u0, u1, h);
+    imu_substep_jac(q, d.R, d.J, Rn, Jn, dR, Jr, u0, u1, h);
 #pragma unroll
     for (int k = 0; k < 9; k++) { d.J[k] = Jn[k]; d.R[k] = Rn[k]; }
 }
 
-template <bool JAC> __global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_intervals(vis_imu_params P, int n, const vis_imu_sample* __restrict__ samples, int n_samples,
-                                                                const double* __restrict__ tframe, const vis_imu_carry* __restrict__ carry,
-                                                                unsigned long long* __restrict__ ws) {
+// the body of the interval kernels; q: the cleared accumulator of the variant
+template <class Jac, class Init> __device__ __forceinline__ void imu_intervals_body(const vis_imu_params& P, Init init, int n, const vis_imu_sample* __restrict__ samples, int n_samples,
+                                                                        const double* __restrict__ tframe, const vis_imu_carry* __restrict__ carry,
+                                                                        unsigned long long* __restrict__ ws) {
     const int i = blockIdx.x * IMU_IV_BLOCK + threadIdx.x;
     if (i >= n) return;
     ImuDelta d;
-    typename ImuJacOf<JAC>::type q;
+    Jac q;
     imu_identity(d);
     imu_jac_clear(q);
+    init(q);
     const bool start = i > 0 || (carry && (carry->valid & VIS_IMU_CARRY_TIME));
     if (!start) { d.flags = VIS_IMU_NO_START; imu_entry_store(ws, n, 0, i, d, q); return; }
     const double ta = i > 0 ? tframe[i - 1] : carry->t_last, tb = tframe[i];
@@ -381,6 +625,18 @@ template <bool JAC> __global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_interv
     if (bad || !imu_all_finite(d)) imu_void(d);
     imu_jac_settle(d.flags, q);
     imu_entry_store(ws, n, 0, i, d, q);
+}
+template <bool JAC> __global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_intervals(vis_imu_params P, int n, const vis_imu_sample* __restrict__ samples, int n_samples,
+                                                                const double* __restrict__ tframe, const vis_imu_carry* __restrict__ carry,
+                                                                unsigned long long* __restrict__ ws) {
+    typedef typename ImuJacOf<JAC>::type Jac;
+    imu_intervals_body<Jac>(P, [](Jac&) {}, n, samples, n_samples, tframe, carry, ws);
+}
+// the covariance's: the same intervals with the 45 numbers beside the delta, a table of 71 slots
+__global__ __launch_bounds__(IMU_IV_BLOCK) void k_imu_cov_intervals(vis_imu_params P, vis_imu_noise N, int n, const vis_imu_sample* __restrict__ samples, int n_samples,
+                                                                    const double* __restrict__ tframe, const vis_imu_carry* __restrict__ carry,
+                                                                    unsigned long long* __restrict__ ws) {
+    imu_intervals_body<ImuCov>(P, [&](ImuCov& q) { q.sg2 = N.sigma_g * N.sigma_g; q.sa2 = N.sigma_a * N.sigma_a; }, n, samples, n_samples, tframe, carry, ws);
 }
 
 // ---------------------------------------------------------------------------------------------- step 2: the pairs
@@ -415,11 +671,11 @@ __device__ __forceinline__ void imu_rot_row(const double* r_ic, const ImuDelta& 
     for (int k = 0; k < 9; k++) rot[k] = ok ? (float)M[k] : ((k & 3) == 0 ? 1.0f : 0.0f);
 }
 
-template <bool JAC> __global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis_imu_params P, int n, FtFrames fr, const double* __restrict__ tframe,
-                                                         const vis_imu_carry* __restrict__ carry, unsigned long long* __restrict__ ws,
-                                                         vis_imu_delta* __restrict__ delta, float* __restrict__ rot, vis_imu_carry* __restrict__ carry_out,
-                                                         ImuJacIO jio) {
-    typedef typename ImuJacOf<JAC>::type Jac;
+// the body of the pairs kernels; JAC: the variant writes rows and a carried record of its own through jio
+template <class Jac, bool JAC, class IO> __device__ __forceinline__ void imu_pairs_body(const vis_imu_params& P, int n, const FtFrames& fr, const double* __restrict__ tframe,
+                                                                                const vis_imu_carry* __restrict__ carry, unsigned long long* __restrict__ ws,
+                                                                                vis_imu_delta* __restrict__ delta, float* __restrict__ rot,
+                                                                                vis_imu_carry* __restrict__ carry_out, const IO& jio) {
     __shared__ int s_maxL, s_last;
     const int tid = threadIdx.x;
     const bool have_carry = carry && (carry->valid & VIS_IMU_CARRY_TIME);
@@ -491,6 +747,18 @@ template <bool JAC> __global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis
         if (JAC) imu_jac_record(q, 0, jio.cout);
     }
 }
+template <bool JAC> __global__ __launch_bounds__(IMU_BLOCK) void k_imu_pairs(vis_imu_params P, int n, FtFrames fr, const double* __restrict__ tframe,
+                                                         const vis_imu_carry* __restrict__ carry, unsigned long long* __restrict__ ws,
+                                                         vis_imu_delta* __restrict__ delta, float* __restrict__ rot, vis_imu_carry* __restrict__ carry_out,
+                                                         ImuJacIO jio) {
+    imu_pairs_body<typename ImuJacOf<JAC>::type, JAC>(P, n, fr, tframe, carry, ws, delta, rot, carry_out, jio);
+}
+__global__ __launch_bounds__(IMU_BLOCK) void k_imu_cov_pairs(vis_imu_params P, int n, FtFrames fr, const double* __restrict__ tframe,
+                                                             const vis_imu_carry* __restrict__ carry, unsigned long long* __restrict__ ws,
+                                                             vis_imu_delta* __restrict__ delta, float* __restrict__ rot, vis_imu_carry* __restrict__ carry_out,
+                                                             ImuCovIO cio) {
+    imu_pairs_body<ImuCov, true>(P, n, fr, tframe, carry, ws, delta, rot, carry_out, cio);
+}
 
 // ---------------------------------------------------------------------------------------------- the bias correction of the records
 // One lane per frame: R' = R Exp(JRg dbg), v' = v + (Jvg dbg + Jva dba), p' = p + (Jpg dbg + Jpa dba); a record that cannot be corrected is copied
@@ -556,6 +824,7 @@ static size_t imu_table_bytes_of(int n, int slots) {
 }
 size_t imu_table_bytes(int n) { return imu_table_bytes_of(n, 26); }
 size_t imu_jac_table_bytes(int n) { return imu_table_bytes_of(n, 62); }
+size_t imu_cov_table_bytes(int n) { return imu_table_bytes_of(n, IMU_COV_SLOTS); }
 
 int imu_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
             const vis_imu_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, float* d_rot, vis_imu_carry* d_carry_out) {
@@ -581,6 +850,22 @@ int imu_jac_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, c
     HIPCHK(ctx, hipGetLastError());
     hipLaunchKernelGGL(k_imu_pairs<true>, dim3(1), dim3(IMU_BLOCK), 0, ctx->stream, *ip, n, fr, d_tframe, cin, (unsigned long long*)d_ws, d_delta, d_rot, cout,
                        ImuJacIO{d_carry ? &d_carry->open_jac : nullptr, d_jac, d_carry_out ? &d_carry_out->open_jac : nullptr});
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
+int imu_cov_launch(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples,
+                   const double* d_tframe, const vis_imu_cov_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, vis_imu_cov* d_cov, float* d_rot,
+                   vis_imu_cov_carry* d_carry_out) {
+    if (n < 1) return VIS_OK;
+    if (n > VIS_IMU_MAX_FRAMES || !d_ws || !d_cov || n_samples < 0) return VIS_E_INVALID;
+    const vis_imu_carry* cin = d_carry ? &d_carry->carry : nullptr;
+    vis_imu_carry* cout = d_carry_out ? &d_carry_out->carry : nullptr;
+    hipLaunchKernelGGL(k_imu_cov_intervals, dim3((n + IMU_IV_BLOCK - 1) / IMU_IV_BLOCK), dim3(IMU_IV_BLOCK), 0, ctx->stream, *ip, *np, n, d_samples, n_samples, d_tframe,
+                       cin, (unsigned long long*)d_ws);
+    HIPCHK(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_imu_cov_pairs, dim3(1), dim3(IMU_BLOCK), 0, ctx->stream, *ip, n, fr, d_tframe, cin, (unsigned long long*)d_ws, d_delta, d_rot, cout,
+                       ImuCovIO{d_carry ? &d_carry->open_cov : nullptr, d_cov, d_carry_out ? &d_carry_out->open_cov : nullptr});
     HIPCHK(ctx, hipGetLastError());
     return VIS_OK;
 }

@@ -847,6 +847,98 @@ __global__ __launch_bounds__(VIA_BLOCK) void k_via_align(vis_vi_align_params P, 
     }
 }
 
+// ---------------------------------------------------------------------------------------------- the inertial factor of a pair
+// One lane per frame: the residual of the pair's delta against the aligned states of the frame and its parent, and its chi-square under the
+// delta's covariance (include/vislam_hip.h "THE INERTIAL FACTOR"; tests/imu_factor_ref.py restates it).  No workspace; tails are recomputed.
+#define VIF_BLOCK 64
+__global__ __launch_bounds__(VIF_BLOCK) void k_imu_factor(vis_vi_align_params P, vis_imu_factor_params FP, int n, FtFrames fr, const vis_traj_pose* __restrict__ traj,
+                                                          const vis_imu_delta* __restrict__ delta, const vis_imu_cov* __restrict__ cov,
+                                                          const vis_vi_state* __restrict__ state, const vis_vi_align* __restrict__ result,
+                                                          vis_imu_factor* __restrict__ out) {
+    const int i = blockIdx.x * VIF_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const int q = via_prev(fr, i);
+    vis_imu_factor o;
+#pragma unroll
+    for (int k = 0; k < 9; k++) o.r[k] = 0.0;
+    o.chi2 = o.chi2_rot = 0.0; o.flags = 0; o.q = q;
+    ViaTail tc, tb;
+    if (q >= 0) {
+        via_tail(P, traj + i, q, tc);
+        via_tail(P, traj + q, via_prev(fr, q), tb);
+    }
+    if (q < 0 || !(tc.flags & VIS_VIT_EDGE) || !(tb.flags & VIS_VIT_POSED)) { o.flags = VIS_IMF_NO_PARENT; out[i] = o; return; }
+    const int need = VIS_VIS_HAS_P | VIS_VIS_HAS_V;
+    if ((state[i].flags & need) != need || (state[q].flags & need) != need) o.flags |= VIS_IMF_NO_STATE;
+    if (result->flags & (VIS_VIA_FEW | VIS_VIA_SINGULAR | VIS_VIA_SCALE)) o.flags |= VIS_IMF_NO_ALIGN;
+    const vis_imu_delta* D = delta + i;
+    const vis_imu_cov* S = cov + i;
+    bool sfin = true;
+    for (int k = 0; k < 45; k++) sfin = sfin && via_finite(S->S[k]);
+    if (!via_usable(P, D, traj[i].parent) || (S->flags & VIS_IMU_COV_NONFINITE) || !sfin || S->q != D->q) o.flags |= VIS_IMF_UNUSABLE;
+    if (o.flags) { out[i] = o; return; }
+    // the residual
+    double r[9], V[9], dR[9], w[3], x[3], g[3];
+    const double dt = D->dt;
+#pragma unroll
+    for (int k = 0; k < 9; k++) dR[k] = D->R[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) g[k] = result->g[k];
+    via_tmul(tb.Rw, tc.Rw, V);
+    via_rot_error(dR, V, r);
+#pragma unroll
+    for (int k = 0; k < 3; k++) w[k] = (state[i].v[k] - state[q].v[k]) - g[k] * dt;
+    via_tmulv(tb.Rw, w, x);
+#pragma unroll
+    for (int k = 0; k < 3; k++) r[3 + k] = x[k] - D->v[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) w[k] = ((state[i].p[k] - state[q].p[k]) - state[q].v[k] * dt) - (0.5 * g[k]) * (dt * dt);
+    via_tmulv(tb.Rw, w, x);
+#pragma unroll
+    for (int k = 0; k < 3; k++) r[6 + k] = x[k] - D->p[k];
+    bool fin = true;
+#pragma unroll
+    for (int k = 0; k < 9; k++) fin = fin && via_finite(r[k]);
+    if (!fin) { o.flags = VIS_IMF_NONFINITE; out[i] = o; return; }
+    // chi-square: (S + diag) y = r by LDL^T, the lower triangle read from the record's upper one
+    double A[9][9], y[9], A3[3][3], r3[3], y3[3];
+#pragma unroll
+    for (int a = 0; a < 9; a++)
+#pragma unroll
+        for (int b = 0; b <= a; b++) {
+            const double s = S->S[b * 9 - b * (b - 1) / 2 + (a - b)];
+            A[a][b] = a == b ? s + (a < 3 ? FP.var_rot : (a < 6 ? FP.var_v : FP.var_p)) : s;
+            A[b][a] = A[a][b];
+        }
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+        r3[a] = r[a];
+#pragma unroll
+        for (int b = 0; b < 3; b++) A3[a][b] = A[a][b];
+    }
+    if (!via_ldl<9>(A, r, y) || !via_ldl<3>(A3, r3, y3)) { o.flags = VIS_IMF_SINGULAR; out[i] = o; return; }
+    double c9 = r[0] * y[0];
+#pragma unroll
+    for (int k = 1; k < 9; k++) c9 = c9 + r[k] * y[k];
+    const double c3 = (r[0] * y3[0] + r[1] * y3[1]) + r[2] * y3[2];
+    if (!via_finite(c9) || !via_finite(c3)) { o.flags = VIS_IMF_NONFINITE; out[i] = o; return; }
+#pragma unroll
+    for (int k = 0; k < 9; k++) o.r[k] = r[k];
+    o.chi2 = c9; o.chi2_rot = c3;
+    out[i] = o;
+}
+
+int imu_factor_launch(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, FtFrames fr, const vis_traj_pose* d_traj,
+                      const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state, const vis_vi_align* d_result,
+                      vis_imu_factor* d_factor) {
+    if (n < 1) return VIS_OK;
+    if (n > VIS_VIA_MAX_FRAMES) return VIS_E_INVALID;
+    hipLaunchKernelGGL(k_imu_factor, dim3((n + VIF_BLOCK - 1) / VIF_BLOCK), dim3(VIF_BLOCK), 0, ctx->stream, *vp, *fp, n, fr, d_traj, d_delta, d_cov, d_state, d_result,
+                       d_factor);
+    HIPCHK(ctx, hipGetLastError());
+    return VIS_OK;
+}
+
 int via_launch(vis_ctx* ctx, const vis_vi_align_params* vp, int n, FtFrames fr, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
                const vis_vi_carry* d_carry, vis_vi_state* d_state, vis_vi_align* d_result, vis_vi_carry* d_carry_out) {
     if (n < 0 || n > VIS_VIA_MAX_FRAMES || !d_result) return VIS_E_INVALID;

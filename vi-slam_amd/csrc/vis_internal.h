@@ -145,6 +145,9 @@ struct Plan {
     // vis_batch_imu_jac (ImuJacPlanWork), allocated by the first call or by vis_batch_imu_jac_init: the 62-slot lifting table for B frames and the two
     // carried vis_imu_jac_carry records
     void* d_imuj_ws = nullptr; Turn imuj;
+    // vis_batch_imu_cov (ImuCovPlanWork), allocated by the first call or by vis_batch_imu_cov_init: the 71-slot lifting table for B frames and the two
+    // carried vis_imu_cov_carry records
+    void* d_imuc_ws = nullptr; Turn imuc;
     // vis_batch_vi_align (ViaPlanWork), allocated by the first call or by vis_batch_vi_align_init: the two carried records
     void* d_via_ws = nullptr; Turn via;
     // vis_batch_vi_align_ba (ViabPlanWork), allocated by the first call or by vis_batch_vi_align_ba_init: its own two carried records
@@ -244,9 +247,10 @@ struct vis_ctx {
     // The grow-only workspaces of the device-rows calls, grown by vis_grow_block alone (vis_carve_block where the call carves a list) and freed by
     // vis_destroy: vis_essential_batch (api.hip PoseWork: the pose stage's buffers for n rows), vis_ftrack_link_rows (FtWork for n rows of
     // row_cap), vis_scale_link_rows (SlWork), vis_trajectory_rows (TjWork), vis_imu_preintegrate_rows and vis_imu_preintegrate (the lifting
-    // table), vis_imu_preintegrate_jac_rows and vis_imu_preintegrate_jac (the table with the Jacobians' blocks).  SIX blocks, apart from the scratch
+    // table), vis_imu_preintegrate_jac_rows and vis_imu_preintegrate_jac (the table with the Jacobians' blocks), vis_imu_preintegrate_cov_rows and
+    // vis_imu_preintegrate_cov (the table with the covariance's blocks).  SEVEN blocks, apart from the scratch
     // block and from each other: a host-pointer call between two batches, or another of these calls, cannot move the block a queued call was given
-    DevBlock ess_ws, ft_ws, sl_ws, tjr_ws, imu_ws, imuj_ws;
+    DevBlock ess_ws, ft_ws, sl_ws, tjr_ws, imu_ws, imuj_ws, imuc_ws;
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)
@@ -633,10 +637,19 @@ int imu_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const
 size_t imu_jac_table_bytes(int n);
 int imu_jac_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples, const double* d_tframe,
                    const vis_imu_jac_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, vis_imu_bias_jac* d_jac, float* d_rot, vis_imu_jac_carry* d_carry_out);
+// the same with the covariance: a table of 71 slots (imu_cov_table_bytes), k_imu_cov_intervals + k_imu_cov_pairs; np validated by the caller; d_cov: n records
+size_t imu_cov_table_bytes(int n);
+int imu_cov_launch(vis_ctx* ctx, const vis_imu_params* ip, const vis_imu_noise* np, int n, FtFrames fr, const vis_imu_sample* d_samples, int n_samples,
+                   const double* d_tframe, const vis_imu_cov_carry* d_carry, void* d_ws, vis_imu_delta* d_delta, vis_imu_cov* d_cov, float* d_rot,
+                   vis_imu_cov_carry* d_carry_out);
 // k_imu_correct on ctx->stream: the records of a bias step; d_dba, d_rot, d_status: null or the rows
 int imu_correct_launch(vis_ctx* ctx, const vis_imu_params* ip, int n, const vis_imu_delta* d_delta, const vis_imu_bias_jac* d_jac, const double* d_dbg,
                        const double* d_dba, vis_imu_delta* d_out, float* d_rot, int32_t* d_status);
 // vi_align.hip.  k_via_align on ctx->stream: one launch, no workspace; vp validated by the caller; d_carry, d_state, d_carry_out: null or the records
+// k_imu_factor on ctx->stream: the whitened inertial residual of every pair; vp, fp validated by the caller; d_result: one record
+int imu_factor_launch(vis_ctx* ctx, const vis_vi_align_params* vp, const vis_imu_factor_params* fp, int n, FtFrames fr, const vis_traj_pose* d_traj,
+                      const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state, const vis_vi_align* d_result,
+                      vis_imu_factor* d_factor);
 int via_launch(vis_ctx* ctx, const vis_vi_align_params* vp, int n, FtFrames fr, const vis_traj_pose* d_traj, const vis_imu_delta* d_delta,
                const vis_vi_carry* d_carry, vis_vi_state* d_state, vis_vi_align* d_result, vis_vi_carry* d_carry_out);
 // the same with the accelerometer bias: k_via_align<true>; bp validated by the caller; d_jac: n records

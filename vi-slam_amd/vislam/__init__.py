@@ -384,6 +384,44 @@ IMU_JAC_OK, IMU_JAC_NONFINITE = 0, 1
 IMC_OK, IMC_UNUSABLE, IMC_JAC, IMC_BIAS, IMC_ANGLE, IMC_NONFINITE = 0, 1, 2, 4, 8, 16
 
 
+class ImuNoise(C.Structure):
+    """vis_imu_noise (vis_default_imu_noise: 1.6968e-4 rad/s/sqrt(Hz), 2.0e-3 m/s^2/sqrt(Hz)): the continuous-time densities of the gyro and the accelerometer"""
+    _fields_ = [("sigma_g", C.c_double), ("sigma_a", C.c_double)]
+
+
+class ImuCov(C.Structure):
+    """vis_imu_cov: the upper triangle, in row order, of the 9 x 9 covariance of (dphi, dv, dp) of a delta, IMU_COV_* flags, the delta's q"""
+    _fields_ = [("S", C.c_double * 45), ("flags", C.c_int32), ("q", C.c_int32)]
+
+
+class ImuCovCarry(C.Structure):
+    """vis_imu_cov_carry as a host structure (vis_batch_imu_cov_init): vis_imu_carry and the covariance of its open delta"""
+    _fields_ = [("carry", ImuCarry), ("open_cov", ImuCov)]
+
+
+IMU_COV_DTYPE = np.dtype([("S", "<f8", (45,)), ("flags", "<i4"), ("q", "<i4")])
+IMU_COV_CARRY_DTYPE = np.dtype([("carry", IMU_CARRY_DTYPE), ("open_cov", IMU_COV_DTYPE)])
+assert IMU_COV_DTYPE.itemsize == 368 == C.sizeof(ImuCov) and IMU_COV_CARRY_DTYPE.itemsize == 600 == C.sizeof(ImuCovCarry) and C.sizeof(ImuNoise) == 16
+IMU_COV_OK, IMU_COV_NONFINITE = 0, 1
+
+
+class ImuFactorParams(C.Structure):
+    """vis_imu_factor_params (vis_default_imu_factor_params: 0, 0, 0): variances added to the diagonal of the covariance by threes"""
+    _fields_ = [("var_rot", C.c_double), ("var_v", C.c_double), ("var_p", C.c_double)]
+
+
+IMU_FACTOR_DTYPE = np.dtype([("r", "<f8", (9,)), ("chi2", "<f8"), ("chi2_rot", "<f8"), ("flags", "<i4"), ("q", "<i4")])
+assert IMU_FACTOR_DTYPE.itemsize == 96 and C.sizeof(ImuFactorParams) == 24
+IMF_OK, IMF_NO_PARENT, IMF_NO_STATE, IMF_NO_ALIGN, IMF_UNUSABLE, IMF_SINGULAR, IMF_NONFINITE = 0, 1, 2, 4, 8, 16, 32
+
+
+def imu_cov_matrix(rec):
+    """the symmetric 9 x 9 float64 matrix of an IMU_COV_DTYPE record"""
+    M = np.zeros((9, 9))
+    M[np.triu_indices(9)] = np.asarray(rec["S"], np.float64)
+    return M + np.triu(M, 1).T
+
+
 class ViAlignParams(C.Structure):
     """vis_vi_align_params (vis_default_vi_align_params: identity, 0, 9.81, 0.1, 8, 8, 4, IMU_EMPTY | IMU_GAP)"""
     _fields_ = [("r_ic", C.c_double * 9), ("p_ci", C.c_double * 3), ("G", C.c_double), ("g_tol", C.c_double), ("min_pairs", C.c_int32),
@@ -498,6 +536,8 @@ ABI_SYMBOLS = [
     "vis_default_imu_params", "vis_imu_preintegrate", "vis_imu_preintegrate_rows", "vis_batch_imu", "vis_batch_imu_init",
     "vis_imu_preintegrate_jac", "vis_imu_preintegrate_jac_rows", "vis_batch_imu_jac", "vis_batch_imu_jac_init", "vis_imu_correct_rows",
     "vis_batch_imu_correct",
+    "vis_default_imu_noise", "vis_imu_preintegrate_cov", "vis_imu_preintegrate_cov_rows", "vis_batch_imu_cov", "vis_batch_imu_cov_init",
+    "vis_default_imu_factor_params", "vis_imu_factor_rows", "vis_batch_imu_factor",
     "vis_default_vi_align_params", "vis_vi_align_rows", "vis_batch_vi_align", "vis_batch_vi_align_init",
     "vis_default_vi_align_ba_params", "vis_vi_align_ba_rows", "vis_batch_vi_align_ba", "vis_batch_vi_align_ba_init",
 ]
@@ -619,6 +659,20 @@ def _load():
         lib.vis_batch_imu_jac_init.argtypes = [vp, C.POINTER(ImuJacCarry)]
         lib.vis_imu_correct_rows.argtypes = [vp, imp, ci, vp, vp, vp, vp, vp, vp, vp]
         lib.vis_batch_imu_correct.argtypes = [vp, imp, ci, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "vis_batch_imu_cov"):               # (absent from older A/B builds)
+        imp, inp = C.POINTER(ImuParams), C.POINTER(ImuNoise)
+        lib.vis_default_imu_noise.argtypes = [inp]
+        lib.vis_default_imu_noise.restype = None
+        lib.vis_imu_preintegrate_cov.argtypes = [vp, imp, inp, vp, ci, C.c_double, C.c_double, C.POINTER(ImuDelta), C.POINTER(ImuCov), vp]
+        lib.vis_imu_preintegrate_cov_rows.argtypes = [vp, imp, inp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_imu_cov.argtypes = [vp, imp, inp, ci, vp, ci, vp, vp, vp, vp]
+        lib.vis_batch_imu_cov_init.argtypes = [vp, C.POINTER(ImuCovCarry)]
+    if hasattr(lib, "vis_batch_imu_factor"):            # (absent from older A/B builds)
+        vap, ifp = C.POINTER(ViAlignParams), C.POINTER(ImuFactorParams)
+        lib.vis_default_imu_factor_params.argtypes = [ifp]
+        lib.vis_default_imu_factor_params.restype = None
+        lib.vis_imu_factor_rows.argtypes = [vp, vap, ifp, ci, vp, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_imu_factor.argtypes = [vp, vap, ifp, ci, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "vis_batch_vi_align"):              # (absent from older A/B builds)
         vap = C.POINTER(ViAlignParams)
         lib.vis_default_vi_align_params.argtypes = [vap]
@@ -792,6 +846,18 @@ def default_imu_params():
     ip = ImuParams()
     lib.vis_default_imu_params(C.byref(ip))
     return ip
+
+
+def default_imu_factor_params():
+    fp = ImuFactorParams()
+    lib.vis_default_imu_factor_params(C.byref(fp))
+    return fp
+
+
+def default_imu_noise():
+    noise = ImuNoise()
+    lib.vis_default_imu_noise(C.byref(noise))
+    return noise
 
 
 def default_vi_align_ba_params():
@@ -1701,6 +1767,41 @@ class Context:
             rec = ImuJacCarry.from_buffer_copy(np.asarray(rec, IMU_JAC_CARRY_DTYPE).tobytes())
         self._chk(lib.vis_batch_imu_jac_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_imu_jac_init")
 
+    # -- the same with the 9 x 9 covariance of the delta's error --------------------------------------------------------
+    def imu_preintegrate_cov(self, samples, t_a, t_b, ip=None, noise=None):
+        """imu_preintegrate with the covariance: (an IMU_DELTA_DTYPE record, an IMU_COV_DTYPE record, the 3 x 3 float32 rotation); blocks"""
+        ip = default_imu_params() if ip is None else ip
+        noise = default_imu_noise() if noise is None else noise
+        s = np.ascontiguousarray(samples, IMU_SAMPLE_DTYPE)
+        d, c, rot = ImuDelta(), ImuCov(), np.zeros(9, np.float32)
+        self._chk(lib.vis_imu_preintegrate_cov(self._h, C.byref(ip), C.byref(noise), C.c_void_p(s.ctypes.data) if len(s) else None, len(s), t_a, t_b, C.byref(d),
+                                               C.byref(c), C.c_void_p(rot.ctypes.data)), "vis_imu_preintegrate_cov")
+        return np.frombuffer(bytes(d), IMU_DELTA_DTYPE)[0], np.frombuffer(bytes(c), IMU_COV_DTYPE)[0], rot.reshape(3, 3)
+
+    def imu_preintegrate_cov_rows(self, n, d_samples_ptr, n_samples, d_tframe_ptr, d_prev_ptr, d_delta_ptr, d_cov_ptr, d_rot_ptr=0, d_carry_in_ptr=0,
+                                  d_carry_out_ptr=0, ip=None, noise=None):
+        """imu_preintegrate_rows with n IMU_COV_DTYPE records beside the deltas and IMU_COV_CARRY_DTYPE carries (raw DEVICE pointers)"""
+        ip = default_imu_params() if ip is None else ip
+        noise = default_imu_noise() if noise is None else noise
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_imu_preintegrate_cov_rows(self._h, C.byref(ip), C.byref(noise), n, v(d_samples_ptr), n_samples, v(d_tframe_ptr), v(d_prev_ptr),
+                                                    v(d_carry_in_ptr), v(d_delta_ptr), v(d_cov_ptr), v(d_rot_ptr), v(d_carry_out_ptr)),
+                  "vis_imu_preintegrate_cov_rows")
+
+    def batch_imu_cov(self, n, d_samples_ptr, n_samples, d_tframe_ptr, d_delta_ptr, d_cov_ptr, d_rot_ptr=0, ip=None, noise=None):
+        """batch_imu with the covariance, on the pose stream, with carried records of its own.  The buffers are in use until batch_sync()"""
+        ip = default_imu_params() if ip is None else ip
+        noise = default_imu_noise() if noise is None else noise
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_imu_cov(self._h, C.byref(ip), C.byref(noise), n, v(d_samples_ptr), n_samples, v(d_tframe_ptr), v(d_delta_ptr), v(d_cov_ptr),
+                                        v(d_rot_ptr)), "vis_batch_imu_cov")
+
+    def batch_imu_cov_init(self, rec=None):
+        """the carry (an IMU_COV_CARRY_DTYPE element or an ImuCovCarry; None: none) the next run's batch_imu_cov continues from; synchronises"""
+        if rec is not None and not isinstance(rec, ImuCovCarry):
+            rec = ImuCovCarry.from_buffer_copy(np.asarray(rec, IMU_COV_CARRY_DTYPE).tobytes())
+        self._chk(lib.vis_batch_imu_cov_init(self._h, C.byref(rec) if rec is not None else None), "vis_batch_imu_cov_init")
+
     def imu_correct_rows(self, n, d_delta_ptr, d_jac_ptr, d_dbg_ptr, d_delta_out_ptr, d_dba_ptr=0, d_rot_out_ptr=0, d_status_ptr=0, ip=None):
         """queue the first-order correction of n records for a bias step on the context's stream (raw DEVICE pointers): d_dbg three doubles (the head
         of a VI_ALIGN_DTYPE record will do), d_dba three doubles or NULL; n corrected IMU_DELTA_DTYPE records, n x 9 float32 rotations, n int32 IMC_*"""
@@ -1731,6 +1832,25 @@ class Context:
         vp = default_vi_align_params() if vp is None else vp
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_vi_align(self._h, C.byref(vp), n, v(d_traj_ptr), v(d_delta_ptr), v(d_state_ptr), v(d_result_ptr)), "vis_batch_vi_align")
+
+    # -- the inertial factor of a pair: the delta's residual against the aligned states, whitened by its covariance ---------
+    def imu_factor_rows(self, n, d_prev_ptr, d_traj_ptr, d_delta_ptr, d_cov_ptr, d_state_ptr, d_result_ptr, d_factor_ptr, vp=None, fp=None):
+        """queue the factors of n frames of caller rows on the context's stream (raw DEVICE pointers): n IMU_FACTOR_DTYPE records from the trajectory
+        records, the deltas, their IMU_COV_DTYPE covariances, the VI_STATE_DTYPE states and ONE VI_ALIGN_DTYPE record (or the head of a VI_ALIGN_BA one)"""
+        vp = default_vi_align_params() if vp is None else vp
+        fp = default_imu_factor_params() if fp is None else fp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_imu_factor_rows(self._h, C.byref(vp), C.byref(fp), n, v(d_prev_ptr), v(d_traj_ptr), v(d_delta_ptr), v(d_cov_ptr), v(d_state_ptr),
+                                          v(d_result_ptr), v(d_factor_ptr)), "vis_imu_factor_rows")
+
+    def batch_imu_factor(self, n, d_traj_ptr, d_delta_ptr, d_cov_ptr, d_state_ptr, d_result_ptr, d_factor_ptr, vp=None, fp=None):
+        """the same for the frames of the last batch_run, on the pose stream behind batch_trajectory, batch_imu_cov and batch_vi_align (or _ba) of the
+        run, which wrote the inputs.  The buffers are in use until batch_sync()"""
+        vp = default_vi_align_params() if vp is None else vp
+        fp = default_imu_factor_params() if fp is None else fp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_imu_factor(self._h, C.byref(vp), C.byref(fp), n, v(d_traj_ptr), v(d_delta_ptr), v(d_cov_ptr), v(d_state_ptr), v(d_result_ptr),
+                                           v(d_factor_ptr)), "vis_batch_imu_factor")
 
     def batch_vi_align_init(self, rec=None):
         """the carry (a VI_CARRY_DTYPE element or a ViCarry; None: none) the next run's batch_vi_align continues from; synchronises"""
