@@ -2011,6 +2011,96 @@ int  vis_batch_imu_factor(vis_ctx* ctx, const vis_vi_align_params* vp, const vis
                           const vis_imu_delta* d_delta, const vis_imu_cov* d_cov, const vis_vi_state* d_state, const vis_vi_align* d_result,
                           vis_imu_factor* d_factor);
 
+/* ---- windowed bundle adjustment over feature tracks (csrc/ba.hip; tests/ba_ref.py restates it and every record, flag byte and output pose equals
+ * the restatement byte for byte).  Poses and points are refined TOGETHER by a Schur-complement Levenberg-Marquardt solve, one workgroup per window,
+ * all windows in one launch; a second kernel chains the windows through the frames they share and a third moves the points.  Double precision,
+ * + - * / sqrt only, nothing contracted, every sum in one fixed order, LDL^T without pivoting, no floating-point atomics: two runs are
+ * byte-identical and nothing depends on the launch shape.  Additive: VIS_ABI_VERSION stays 5.
+ * WINDOWS.  S = stride.  Window j covers frames first = j S ... last = min(first + S, n - 1); there are ceil((n - 1) / S) of them.  With n <= 1
+ *   there is none: the poses are copied, nothing else is written.  A frame HAS A POSE under the rule of the N-view triangulation, on the INPUT
+ *   poses.  anchor = the first posed frame of the window (-1: none), held fixed; the FREE frames are the posed frames after it, camera index c =
+ *   their rank (n_free <= 16, so at most 96 unknowns after the points are eliminated).  Window j OWNS the slots (i, k < nk(i)) of frames
+ *   first + 1 ... last, window 0 also those of frame 0; entries k >= nk(i) are left untouched.
+ * POINTS, in slot order (frame rising, keypoint rising).  An owned slot that a keypoint of a later owned frame names as its parent (k_ftri_mark's
+ *   rule inside the window) gets the zero record and flag byte 0.  Every other owned slot is a window-end: steps 1-3 of vis_ftrack_triangulate_rows
+ *   (the same device functions) over its walk restricted to frames >= anchor, with max_views 17, min_views, gn_iters = tri_gn_iters,
+ *   max_reproj_px = init_reproj_px, under the input poses.  VIS_FTP_FEW there -> VIS_BAP_FEW (n_views set, the rest zero); singular, not in front in
+ *   every used view or a view's e2 above init_reproj_px^2 -> VIS_BAP_INIT_REJECTED (n_views, rms0_px when the cost was finite, X zero); else
+ *   VIS_BAP_USED with X and rms0_px = rms1_px = the triangulation's rms.  A keypoint is a point of at most one window.
+ *   n_points, n_obs: the used points and their views.  n_free == 0 or n_points < min_points: VIS_BA_FEW, nothing is solved, cost1 = cost0.
+ * OBSERVATION at pose P and point X with pixel (u, v): U, V, W, iw, un, vn, ru, rv, Ju_k, Jv_k exactly as in step 3 of the N-view triangulation,
+ *   fu = fx iw, fv = fy iw, e2 = ru ru + rv rv, e = sqrt(e2); w = 1 and term = e2 when huber_px == 0 or e <= huber_px, else w = huber_px / e and
+ *   term = (2 huber_px) e - huber_px huber_px.  The camera rows belong to the PnP refinement's update R <- C(omega) R, t <- C(omega) t + dt
+ *   (the projection Jacobian times [ -[x_cam]x | I ]):
+ *     Cu = (-(fu (un V)), fu (W + un U), -(fu V), fu, 0, -(fu un)),   Cv = (-(fv (W + vn V)), fv (vn U), fv U, 0, fv, -(fv vn)).
+ * ONE LINEARISATION at the current state, lambda the damping.
+ *   Per point, views in walk order (newest to oldest): V_ab += w (Ju_a Ju_b + Jv_a Jv_b) (a <= b), g_a += w (Ju_a ru + Jv_a rv); the diagonal of V
+ *   times (1 + lambda); D0 ... D2, L10, L20, L21 by the 3 x 3 LDL^T of the triangulation -- a pivot not > 0 or not finite: the point SITS THE
+ *   LINEARISATION OUT (no term anywhere, its X stays).  Vi = the inverse: column j is the solution of e_j by z0 = b0, z1 = b1 - L10 z0,
+ *   z2 = (b2 - L20 z0) - L21 z1, x2 = z2 / D2, x1 = z1 / D1 - L21 x2, x0 = (z0 / D0 - L10 x1) - L20 x2, and Vi_jk (j <= k) is read from column k.
+ *   Per free view W_ak = w (Cu_a Ju_k + Cv_a Jv_k) (6 x 3) and Y_ak = (W_a0 Vi_0k + W_a1 Vi_1k) + W_a2 Vi_2k.
+ *   Over the points in slot order, absent terms skipped, every accumulator from 0.0: U_ab += w (Cu_a Cu_b + Cv_a Cv_b) (a <= b) and
+ *   b_a += w (Cu_a ru + Cv_a rv) per free camera; T[6 c1 + a][6 c2 + b] += (Y1_a0 W2_b0 + Y1_a1 W2_b1) + Y1_a2 W2_b2 for row <= column;
+ *   Tg[6 c + a] += (Y_a0 g_0 + Y_a1 g_1) + Y_a2 g_2.  A = Ud - T, Ud = U inside the diagonal blocks with its diagonal entries times (1 + lambda), 0.0
+ *   elsewhere; rhs = -(b - Tg).  LDL^T without pivoting by the PnP refinement's recurrences, terms in rising column order:
+ *   D_j = A_jj - sum_c (L_jc L_jc) D_c, L_ij = (A_ij - sum_c (L_ic L_jc) D_c) / D_j, z_i = rhs_i - sum_{c<i} L_ic z_c,
+ *   d_i = z_i / D_i - sum_{c>i} L_ci d_c.  A pivot not > 0 or not finite: the linearisation is a REJECTION.
+ *   Candidate: the free poses by the PnP refinement's Cayley update with d_c; per point Q_k = the sum over its free views in walk order of
+ *   ((((W_0k d_0 + W_1k d_1) + W_2k d_2) + W_3k d_3) + W_4k d_4) + W_5k d_5, s_k = -g_k - Q_k, dX_k = (Vi_k0 s_0 + Vi_k1 s_1) + Vi_k2 s_2, X + dX.
+ *   cost = the sum over the points in slot order of (the sum over the views in walk order of term).  The candidate is ACCEPTED iff its cost is
+ *   finite and < the current cost: lambda <- max(lambda / 10, 1e-12); else REJECTED: lambda <- min(10 lambda, 1e12), the state is kept.
+ *   lm_iters counts linearisations, so cost1 <= cost0 always, and lm_iters == 0 returns the input bytes.
+ * AFTER THE SOLVE.  rms1_px = (float) sqrt(sum e2 / n_views) at the final state.  With n_accepted > 0 the scale gauge: ca, cin, cout = the centres
+ *   -R^T t of the anchor (input) and of the last posed frame (input, final); scale = sqrt(|cin - ca|^2) / sqrt(|cout - ca|^2); not finite or not
+ *   > 0: scale = 1, VIS_BA_NO_SCALE, nothing applied; else c' = ca + scale (c - ca), t' = -(R c') for every free frame and X' = ca + scale (X - ca).
+ * STITCH, in window order, one fixed sequence inside one launch.  A_in = the anchor's input pose.  A_out = A_in for window 0 and for a window
+ *   whose anchor is not its first frame -- the previous window did not deliver it: VIS_BA_RESTART (j > 0) -- else the output pose of the shared
+ *   frame.  A_out == A_in byte for byte: the window's poses and points ARE the output.  Else pose_i <- (pose_i o A_in^-1) o A_out (R_rel = R_i
+ *   R_a^T, t_rel = t_i - R_rel t_a; R = R_rel R_out, t = R_rel t_out + t_rel; every dot product (a0 b0 + a1 b1) + a2 b2) and
+ *   X <- R_out^T ((R_a X + t_a) - t_out).  An output pose that is not finite is replaced by the input pose, a moved point that is not finite keeps its X.  A VIS_BA_FEW window contributes its
+ *   input relative poses; a frame without a pose, window 0's anchor and a restarted anchor get their input bytes.
+ * A window's record (but for VIS_BA_RESTART) depends only on its own frames; the stitched poses depend on earlier windows by construction.  The
+ * absolute pose after stitching is not reliably better than the input: the windows are joined through single frames and each window's scale is
+ * normalised to the input's span.  No reported number is ever a NaN or an infinity.
+ * Out of scope: observations older than the window, sweeps across windows or overlap by more than one frame, inertial factors, intrinsics as
+ * unknowns, writing refined poses into the plan, loop closure. */
+enum { VIS_BA_REFINED = 1, VIS_BA_FEW = 2, VIS_BA_RESTART = 4, VIS_BA_NO_SCALE = 8 };
+enum { VIS_BAP_USED = 1, VIS_BAP_INIT_REJECTED = 2, VIS_BAP_FEW = 4 };
+typedef struct vis_ba_params {   /* 48 bytes; the defaults are this library's own */
+    int32_t stride;              /* 8      free frames per window S, 1 ... 16 (<= 96 unknowns) */
+    int32_t min_views;           /* 2      used views below which a track is no point, 2 ... 17 */
+    int32_t min_points;          /* 12     points below which a window is copied, >= 1 */
+    int32_t lm_iters;            /* 10     linearisations, 0 ... 30 */
+    int32_t tri_gn_iters;        /* 5      as vis_ftrack_tri_params.gn_iters, 0 ... 10 */
+    int32_t reserved_;           /* 0 */
+    double  huber_px;            /* 2.4477 (sqrt 5.991); 0 = plain squares; finite, >= 0 */
+    double  init_reproj_px;      /* 16.0   gate on the initial point; finite, > 0, <= 1e6 */
+    double  lambda0;             /* 1e-4;  in [1e-12, 1e12] */
+} vis_ba_params;
+typedef struct vis_ba_window {   /* 80 bytes */
+    int32_t first, last, anchor, n_free, n_points, n_obs, n_lin, n_accepted, n_rejected, flags, reserved_[2];
+    double  cost0, cost1, lambda, scale;
+} vis_ba_window;
+typedef struct vis_ba_point { double X[3]; float rms0_px, rms1_px; int32_t n_views, flags; } vis_ba_point;   /* 40 bytes */
+void vis_default_ba_params(vis_ba_params* bp);
+/* Caller-made rows, DEVICE pointers, asynchronous on the context's stream.  d_prev, d_nkp, d_obs, d_xy, d_poses as vis_ftrack_triangulate_rows
+ * reads them; d_poses_out: n x 12 doubles (must not overlap d_poses); d_windows: ceil((n - 1) / stride) records; d_points / d_flags: n rows of
+ * row_cap entries.
+ * Refusals, in this order.  VIS_E_INVALID: bp NULL or outside the ranges above, a NULL pointer, a pointer that is not aligned (16 bytes for d_obs,
+ * 8 for d_xy, d_poses, d_poses_out, d_windows and d_points, 4 for d_prev and d_nkp), n or row_cap negative.  VIS_E_STATE without a context.
+ * VIS_E_CAPACITY when n x row_cap exceeds 2^28 entries. */
+int  vis_ba_rows(vis_ctx* ctx, const vis_ba_params* bp, int n, const int32_t* d_prev, const int32_t* d_nkp, const vis_ftrack_obs* d_obs, int row_cap,
+                 const float* d_xy, const double* d_poses, double* d_poses_out, vis_ba_window* d_windows, vis_ba_point* d_points, uint8_t* d_flags);
+/* The keypoints and the pairing of the last vis_batch_run (n = its frames) with the observations vis_batch_ftrack wrote for it: on the POSE stream
+ * through the follow-up scaffold, behind vis_batch_ftrack of the run and behind the context's stream (where d_poses may have been produced), exactly
+ * as vis_batch_ftrack_triangulate is queued; the caller's buffers are in use until vis_batch_sync.  d_poses_out may be handed to
+ * vis_batch_ftrack_triangulate, vis_batch_vi_align and vis_batch_imu_factor with no host step.  Nothing is written into the plan.
+ * Refusals, in this order.  VIS_E_INVALID: what vis_ba_rows refuses of bp, a NULL or misaligned d_obs, d_poses, d_poses_out, d_windows, d_points or
+ * d_flags, n or row_cap negative.  VIS_E_STATE: no context / plan / match stage, or n differs.  VIS_E_CAPACITY: row_cap below the plan's keypoint
+ * capacity, or n x row_cap beyond 2^28 entries. */
+int  vis_batch_ba(vis_ctx* ctx, const vis_ba_params* bp, int n, const vis_ftrack_obs* d_obs, int row_cap, const double* d_poses, double* d_poses_out,
+                  vis_ba_window* d_windows, vis_ba_point* d_points, uint8_t* d_flags);
+
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */
 int  vis_synth_canvas(uint8_t* canvas, int canvas_dim, uint64_t seed);

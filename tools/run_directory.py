@@ -56,6 +56,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              plan's own pairing, default parameters; the carry continues across the batches).  The CSV is EuRoC's: timestamp in ns, w (rad/s), a
              (m/s^2), lines that start with # skipped; frame times come from the image file names; both are taken relative to the first frame's
              stamp, in seconds.  One row per frame -- frame index, timestamp, flags (VIS_IMU_*), q, n_steps, dt, R (9), v (3), p (3).
+  --ba out.csv: with --trajectory, the windowed bundle adjustment of the chained poses over the feature tracks (vis_batch_ba behind
+             vis_batch_trajectory and vis_batch_ftrack, default parameters; the N-view triangulation then reads the adjusted poses): one row per frame
+             -- frame, stamp, the flags and the point count of the frame's window, the adjusted R (row-major) and t.  A batch is adjusted on its own:
+             observations of earlier batches are not held.
   --vi-align out.csv: with --imu and --trajectory, align the chained trajectory with the IMU on the device (vis_batch_vi_align behind
              vis_batch_trajectory and vis_batch_imu of every batch, default parameters; the sums and tails continue across the batches).  One row
              per frame -- frame index, timestamp, flags (VIS_VIS_*), q, res, p (3), v (3), under the batch's own solution; the JSON line carries the
@@ -142,6 +146,7 @@ def main():
     ap.add_argument("--klt", default=None, metavar="CSV", help="write the KLT track of every keypoint of every pair here")
     ap.add_argument("--tracks", default=None, metavar="CSV", help="link the symmetric matches into feature tracks; write every frame's summary and length histogram here")
     ap.add_argument("--trajectory", default=None, metavar="CSV", help="chain the two-view poses under the scale links; write one pose per frame here")
+    ap.add_argument("--ba", default=None, metavar="CSV", help="with --trajectory: windowed bundle adjustment of the chained poses; one adjusted pose per frame here")
     ap.add_argument("--imu", default=None, metavar="CSV", help="EuRoC imu0/data.csv: timestamp [ns], w, a")
     ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
     ap.add_argument("--imu-jac", default=None, metavar="CSV", help="with --imu: write every frame's bias Jacobians of v and p here")
@@ -228,6 +233,14 @@ def main():
         d_jobs, d_jframe = z(B * jk * vislam.FTRACK_OBS_DTYPE.itemsize), z(B * vislam.FTRACK_FRAME_DTYPE.itemsize)
         d_jpts, d_jfl, d_jsm = z(B * jk * vislam.FTRACK_POINT_DTYPE.itemsize), z(B * jk), z(B * vislam.FTRACK_TRI_SUMMARY_DTYPE.itemsize)
         traj_rows, traj_totals = [], dict(links_ok=0, roots=0, unit_edges=0, overflow=0, n_view_points=0, n_view_kept=0)
+    if a.ba:
+        if not a.trajectory:
+            raise SystemExit("--ba needs --trajectory")
+        bap = vislam.default_ba_params()
+        nbw = vislam.ba_windows(B, bap.stride)
+        d_bposes, d_bwin = z(B * 96), z(max(nbw, 1) * vislam.BA_WINDOW_DTYPE.itemsize)
+        d_bpts, d_bfl = z(B * jk * vislam.BA_POINT_DTYPE.itemsize), z(B * jk)
+        ba_rows, ba_totals = [], dict(windows=0, refined=0, few=0, restart=0, no_scale=0, points=0, observations=0, accepted=0, rejected=0, cost0=0.0, cost1=0.0)
     if a.imu:
         if not a.imu_out:
             raise SystemExit("--imu needs --imu-out")
@@ -391,7 +404,10 @@ def main():
             ctx.batch_scale_links(nb, d_jmp.data_ptr(), d_jmf.data_ptr(), jcap, d_jlink.data_ptr())
             ctx.batch_trajectory(nb, d_jlink.data_ptr(), d_jtraj.data_ptr(), d_jposes.data_ptr())
             ctx.batch_ftrack(nb, jk, d_jobs.data_ptr(), d_jframe.data_ptr())
-            ctx.batch_ftrack_triangulate(nb, d_jobs.data_ptr(), jk, d_jposes.data_ptr(), d_jpts.data_ptr(), d_jfl.data_ptr(), d_jsm.data_ptr())
+            if a.ba:                                         # ... -> bundle adjustment -> the N-view points under the adjusted poses
+                ctx.batch_ba(nb, d_jobs.data_ptr(), jk, d_jposes.data_ptr(), d_bposes.data_ptr(), d_bwin.data_ptr(), d_bpts.data_ptr(), d_bfl.data_ptr(), bap)
+            ctx.batch_ftrack_triangulate(nb, d_jobs.data_ptr(), jk, (d_bposes if a.ba else d_jposes).data_ptr(), d_jpts.data_ptr(), d_jfl.data_ptr(),
+                                         d_jsm.data_ptr())
         if a.vi_align and a.recorrect:                       # align -> correct by the record's dbg -> align again: queued, no host step
             ctx.batch_vi_align(nb, d_jtraj.data_ptr(), d_idelta.data_ptr(), d_vres1.data_ptr(), d_vstate.data_ptr())
             ctx.batch_imu_correct(nb, d_idelta.data_ptr(), d_ijac.data_ptr(), d_vres1.data_ptr(), d_idelta2.data_ptr(), 0, 0, d_istatus.data_ptr())
@@ -471,6 +487,19 @@ def main():
                 traj_totals["n_view_points"] += int(js[i]["n_points"])
                 traj_totals["n_view_kept"] += int(js[i]["n_kept"])
                 traj_rows.append((first + i, stamps[first + i], jt[i].copy(), jl[i].copy()))
+        if a.ba:
+            bw = d_bwin.cpu().numpy().view(vislam.BA_WINDOW_DTYPE)[:vislam.ba_windows(nb, bap.stride)]
+            bpo = d_bposes.cpu().numpy().view(np.float64).reshape(B, 12)
+            ba_totals["windows"] += len(bw)
+            for key, bit in (("refined", vislam.BA_REFINED), ("few", vislam.BA_FEW), ("restart", vislam.BA_RESTART), ("no_scale", vislam.BA_NO_SCALE)):
+                ba_totals[key] += int((bw["flags"] & bit != 0).sum())
+            for key, field in (("points", "n_points"), ("observations", "n_obs"), ("accepted", "n_accepted"), ("rejected", "n_rejected")):
+                ba_totals[key] += int(bw[field].sum())
+            ba_totals["cost0"] += float(bw["cost0"].sum())
+            ba_totals["cost1"] += float(bw["cost1"].sum())
+            for i in range(nb):
+                j = 0 if i == 0 else (i - 1) // bap.stride
+                ba_rows.append((first + i, stamps[first + i], int(bw[j]["flags"]), int(bw[j]["n_points"]), bpo[i].copy()))
         if a.imu:
             idl = d_idelta.cpu().numpy().view(vislam.IMU_DELTA_DTYPE)
             for i in range(nb):
@@ -619,6 +648,12 @@ def main():
                 f.write("%d,%d," % (fi, ts) + ",".join("%d" % v for v in ints) + "," + ",".join("%.17g" % v for v in dbl) + "\n")
         out["trajectory_csv"] = a.trajectory
         out["trajectory"] = traj_totals
+    if a.ba:
+        with open(a.ba, "w") as f:                              # frame, stamp, its window's flags and points, the adjusted R, t
+            for fi, ts, wf, wn, pose in ba_rows:
+                f.write("%d,%d,%d,%d," % (fi, ts, wf, wn) + ",".join("%.17g" % v for v in pose) + "\n")
+        out["ba_csv"] = a.ba
+        out["ba"] = ba_totals
     if a.imu:
         with open(a.imu_out, "w") as f:                         # frame, stamp, flags, q, n_steps, dt, R, v, p
             for fi, ts, r in imu_rows:

@@ -2042,6 +2042,52 @@ extern "C" int vis_batch_ftrack_triangulate(vis_ctx* ctx, const vis_ftrack_tri_p
     }, {&pl->out().readers, &pl->last_set().matcher, pl->kf_min ? &pl->last_set().links : nullptr});
 }
 
+// ---- windowed bundle adjustment over the tracks: ba.hip
+extern "C" void vis_default_ba_params(vis_ba_params* bp) {
+    if (!bp) return;
+    bp->stride = 8; bp->min_views = 2; bp->min_points = 12; bp->lm_iters = 10; bp->tri_gn_iters = 5; bp->reserved_ = 0;
+    bp->huber_px = 2.4477; bp->init_reproj_px = 16.0; bp->lambda0 = 1e-4;
+}
+
+static bool ba_params_ok(const vis_ba_params* bp) {
+    return bp && bp->stride >= 1 && bp->stride <= 16 && bp->min_views >= 2 && bp->min_views <= 17 && bp->min_points >= 1 && bp->lm_iters >= 0 &&
+           bp->lm_iters <= 30 && bp->tri_gn_iters >= 0 && bp->tri_gn_iters <= 10 && std::isfinite(bp->huber_px) && bp->huber_px >= 0.0 &&
+           std::isfinite(bp->init_reproj_px) && bp->init_reproj_px > 0.0 && bp->init_reproj_px <= 1e6 && bp->lambda0 >= 1e-12 && bp->lambda0 <= 1e12;
+}
+
+extern "C" int vis_ba_rows(vis_ctx* ctx, const vis_ba_params* bp, int n, const int32_t* d_prev, const int32_t* d_nkp, const vis_ftrack_obs* d_obs,
+                           int row_cap, const float* d_xy, const double* d_poses, double* d_poses_out, vis_ba_window* d_windows, vis_ba_point* d_points,
+                           uint8_t* d_flags) {
+    if (!ba_params_ok(bp) || !d_prev || !d_nkp || !d_obs || !d_xy || !d_poses || !d_poses_out || !d_windows || !d_points || !d_flags) return VIS_E_INVALID;
+    if (!aligned(d_obs, 16) || !aligned(d_xy, 8) || !aligned(d_poses, 8) || !aligned(d_poses_out, 8) || !aligned(d_windows, 8) || !aligned(d_points, 8) ||
+        !aligned(d_prev, 4) || !aligned(d_nkp, 4) || n < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (!ctx) return VIS_E_STATE;
+    if ((size_t)n * (size_t)row_cap > ((size_t)1 << 28)) { ctx->err = "vis_ba_rows: n x row_cap exceeds 2^28 entries"; return VIS_E_CAPACITY; }
+    (void)hipSetDevice(ctx->device);
+    return ba_run(ctx, bp, n, row_cap, FtFrames{d_prev, 0, d_nkp}, d_obs, row_cap, d_xy, (size_t)row_cap * 8, 8, d_poses, d_poses_out, d_windows, d_points,
+                  d_flags);
+}
+
+extern "C" int vis_batch_ba(vis_ctx* ctx, const vis_ba_params* bp, int n, const vis_ftrack_obs* d_obs, int row_cap, const double* d_poses,
+                            double* d_poses_out, vis_ba_window* d_windows, vis_ba_point* d_points, uint8_t* d_flags) {
+    if (!ba_params_ok(bp) || !d_obs || !d_poses || !d_poses_out || !d_windows || !d_points || !d_flags || !aligned(d_obs, 16) || !aligned(d_poses, 8) ||
+        !aligned(d_poses_out, 8) || !aligned(d_windows, 8) || !aligned(d_points, 8) || n < 0 || row_cap < 0) return VIS_E_INVALID;
+    if (!ctx || !ctx->batch) return VIS_E_STATE;
+    Plan* pl = ctx->batch;
+    if (pl->last_n < 1 || n != pl->last_n) return VIS_E_STATE;
+    if (!(pl->last_stages & VIS_STAGE_MATCH)) { ctx->err = "vis_batch_ba: the last vis_batch_run had no VIS_STAGE_MATCH"; return VIS_E_STATE; }
+    if (row_cap < pl->kcap) { ctx->err = "vis_batch_ba: row_cap is smaller than the plan's keypoint capacity"; return VIS_E_CAPACITY; }
+    if ((size_t)n * (size_t)row_cap > ((size_t)1 << 28)) { ctx->err = "vis_batch_ba: n x row_cap exceeds 2^28 entries"; return VIS_E_CAPACITY; }
+    // queued exactly as vis_batch_ftrack_triangulate: on the pose stream behind vis_batch_ftrack of the run, behind the matcher that saw the keypoints
+    // and behind the context's stream, where the caller's poses may have been produced; nothing of the plan is written
+    return on_pose_stream(ctx, {FU_FORK | FU_MATCHER, ctx->ev_epi_done[pl->mo_cur]}, [&] {
+        const int rc2 = ba_run(ctx, bp, n, pl->kcap, plan_frames(pl), d_obs, row_cap, pl->d_kps + (size_t)(pl->last_base + 1) * pl->kcap,
+                               (size_t)pl->kcap * sizeof(vis_keypoint), (int)sizeof(vis_keypoint), d_poses, d_poses_out, d_windows, d_points, d_flags);
+        if (!rc2) ctx->pose_pending = true;
+        return rc2;
+    }, {&pl->out().readers, &pl->last_set().matcher, pl->kf_min ? &pl->last_set().links : nullptr});
+}
+
 // ---- scale links and the chained trajectory: trajectory.hip
 extern "C" void vis_default_scale_link_params(vis_scale_link_params* sp) {
     if (!sp) return;

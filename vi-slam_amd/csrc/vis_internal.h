@@ -607,6 +607,10 @@ int ftrack_link_run(vis_ctx* ctx, const FtWork& W, int n, int R, FtFrames fr, co
 int ftrack_triangulate_run(vis_ctx* ctx, const vis_ftrack_tri_params* tp, int n, int R, FtFrames fr, const vis_ftrack_obs* d_obs, int ocap,
                            const void* d_xy, size_t xy_row, int xy_step, const double* d_poses, vis_ftrack_point* d_points, uint8_t* d_flags,
                            vis_ftrack_tri_summary* d_summary);
+// ba.hip.  The poses copied to d_poses_out, then k_ba_window (one workgroup per window) + k_ba_stitch + k_ba_points on ctx->stream, no workspace (a
+// cache of every used point's views was built and measured: DESIGN.md 4.26 has why it is not here); bp validated by the caller; d_xy as above
+int ba_run(vis_ctx* ctx, const vis_ba_params* bp, int n, int R, FtFrames fr, const vis_ftrack_obs* d_obs, int ocap, const void* d_xy, size_t xy_row,
+           int xy_step, const double* d_poses, double* d_poses_out, vis_ba_window* d_windows, vis_ba_point* d_points, uint8_t* d_flags);
 // trajectory.hip.  SL_LDS_CAP: list entries per pair up to which the ratio pass keeps its keys in LDS; TJ_LDS_N: frames per call up to which the chain
 // keeps its elements in LDS.  The workspaces beyond those sizes, declared once: keys (n x mcap 64-bit patterns), D / I (13 doubles and 4 ints per
 // frame, structure of arrays).

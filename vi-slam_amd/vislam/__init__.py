@@ -310,6 +310,28 @@ FTRACK_TRI_SUMMARY_DTYPE = np.dtype([("n_ends", "<i4"), ("n_points", "<i4"), ("n
                                      ("n_parallax_ok", "<i4"), ("n_few", "<i4"), ("n_singular", "<i4")])
 assert FTRACK_OBS_DTYPE.itemsize == 16 and FTRACK_FRAME_DTYPE.itemsize == 32 and FTRACK_POINT_DTYPE.itemsize == 40
 assert FTRACK_TRI_SUMMARY_DTYPE.itemsize == 32 and C.sizeof(FtrackTriParams) == 32
+
+
+class BaParams(C.Structure):
+    """vis_ba_params: the knobs of the windowed bundle adjustment (vis_default_ba_params: 8, 2, 12, 10, 5, 2.4477, 16.0, 1e-4)"""
+    _fields_ = [("stride", C.c_int32), ("min_views", C.c_int32), ("min_points", C.c_int32), ("lm_iters", C.c_int32), ("tri_gn_iters", C.c_int32),
+                ("reserved_", C.c_int32), ("huber_px", C.c_double), ("init_reproj_px", C.c_double), ("lambda0", C.c_double)]
+
+
+BA_WINDOW_DTYPE = np.dtype([("first", "<i4"), ("last", "<i4"), ("anchor", "<i4"), ("n_free", "<i4"), ("n_points", "<i4"), ("n_obs", "<i4"),
+                            ("n_lin", "<i4"), ("n_accepted", "<i4"), ("n_rejected", "<i4"), ("flags", "<i4"), ("reserved_", "<i4", (2,)),
+                            ("cost0", "<f8"), ("cost1", "<f8"), ("lambda_", "<f8"), ("scale", "<f8")])
+BA_POINT_DTYPE = np.dtype([("X", "<f8", (3,)), ("rms0_px", "<f4"), ("rms1_px", "<f4"), ("n_views", "<i4"), ("flags", "<i4")])
+assert BA_WINDOW_DTYPE.itemsize == 80 and BA_POINT_DTYPE.itemsize == 40 and C.sizeof(BaParams) == 48
+BA_REFINED, BA_FEW, BA_RESTART, BA_NO_SCALE = 1, 2, 4, 8
+BAP_USED, BAP_INIT_REJECTED, BAP_FEW = 1, 2, 4
+
+
+def ba_windows(n, stride):
+    """the number of vis_ba_window records vis_ba_rows / vis_batch_ba write for n frames"""
+    return (n - 1 + stride - 1) // stride if n > 1 else 0
+
+
 FT_NO_PAIR, FT_NO_CARRY = 1, 2
 FT_SYM, FT_GOOD = 0, 1
 FTP_FRONT, FTP_REPROJ_OK, FTP_PARALLAX_OK, FTP_KEPT, FTP_FEW, FTP_SINGULAR = 1, 2, 4, 8, 16, 32
@@ -540,6 +562,7 @@ ABI_SYMBOLS = [
     "vis_default_imu_factor_params", "vis_imu_factor_rows", "vis_batch_imu_factor",
     "vis_default_vi_align_params", "vis_vi_align_rows", "vis_batch_vi_align", "vis_batch_vi_align_init",
     "vis_default_vi_align_ba_params", "vis_vi_align_ba_rows", "vis_batch_vi_align_ba", "vis_batch_vi_align_ba_init",
+    "vis_default_ba_params", "vis_ba_rows", "vis_batch_ba",
 ]
 
 
@@ -634,6 +657,12 @@ def _load():
         lib.vis_default_ftrack_tri_params.restype = None
         lib.vis_ftrack_triangulate_rows.argtypes = [vp, ftp, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp]
         lib.vis_batch_ftrack_triangulate.argtypes = [vp, ftp, ci, vp, ci, vp, vp, vp, vp]
+    if hasattr(lib, "vis_batch_ba"):                    # (absent from older A/B builds)
+        bap = C.POINTER(BaParams)
+        lib.vis_default_ba_params.argtypes = [bap]
+        lib.vis_default_ba_params.restype = None
+        lib.vis_ba_rows.argtypes = [vp, bap, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
+        lib.vis_batch_ba.argtypes = [vp, bap, ci, vp, ci, vp, vp, vp, vp, vp]
     if hasattr(lib, "vis_batch_trajectory"):            # (absent from older A/B builds)
         slp = C.POINTER(ScaleLinkParams)
         lib.vis_default_scale_link_params.argtypes = [slp]
@@ -876,6 +905,12 @@ def default_scale_link_params():
     sp = ScaleLinkParams()
     lib.vis_default_scale_link_params(C.byref(sp))
     return sp
+
+
+def default_ba_params():
+    bp = BaParams()
+    lib.vis_default_ba_params(C.byref(bp))
+    return bp
 
 
 def default_ftrack_tri_params():
@@ -1668,6 +1703,25 @@ class Context:
         v = lambda a: C.c_void_p(a) if a else None
         self._chk(lib.vis_batch_ftrack_triangulate(self._h, C.byref(tp), n, v(d_obs_ptr), row_cap, v(d_poses_ptr), v(d_points_ptr), v(d_flags_ptr),
                                                    v(d_summary_ptr)), "vis_batch_ftrack_triangulate")
+
+    # -- windowed bundle adjustment over the tracks -------------------------------------------------------------------
+    def ba_rows(self, n, d_prev_ptr, d_nkp_ptr, d_obs_ptr, row_cap, d_xy_ptr, d_poses_ptr, d_poses_out_ptr, d_windows_ptr, d_points_ptr, d_flags_ptr,
+                bp=None):
+        """queue the windowed bundle adjustment of these n frames on the context's stream (raw DEVICE pointers): the rows of
+        ftrack_triangulate_rows in; n x 12 doubles of refined poses, ba_windows(n, stride) BA_WINDOW_DTYPE records, n rows of row_cap
+        BA_POINT_DTYPE and flag bytes out"""
+        bp = default_ba_params() if bp is None else bp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_ba_rows(self._h, C.byref(bp), n, v(d_prev_ptr), v(d_nkp_ptr), v(d_obs_ptr), row_cap, v(d_xy_ptr), v(d_poses_ptr),
+                                  v(d_poses_out_ptr), v(d_windows_ptr), v(d_points_ptr), v(d_flags_ptr)), "vis_ba_rows")
+
+    def batch_ba(self, n, d_obs_ptr, row_cap, d_poses_ptr, d_poses_out_ptr, d_windows_ptr, d_points_ptr, d_flags_ptr, bp=None):
+        """the same for the keypoints of the last batch_run with the rows batch_ftrack wrote for it, on the pose stream behind that call; the
+        buffers are in use until batch_sync()"""
+        bp = default_ba_params() if bp is None else bp
+        v = lambda a: C.c_void_p(a) if a else None
+        self._chk(lib.vis_batch_ba(self._h, C.byref(bp), n, v(d_obs_ptr), row_cap, v(d_poses_ptr), v(d_poses_out_ptr), v(d_windows_ptr),
+                                   v(d_points_ptr), v(d_flags_ptr)), "vis_batch_ba")
 
     # -- a scaled trajectory: scale links between consecutive pairs, and the chain -----------------------------------
     def scale_link_rows(self, n, d_prev_ptr, d_links_ptr, d_nlinks_ptr, link_cap, d_pose_ptr, d_points_ptr, d_flags_ptr, pts_cap, row_cap,
