@@ -2101,6 +2101,102 @@ int  vis_ba_rows(vis_ctx* ctx, const vis_ba_params* bp, int n, const int32_t* d_
 int  vis_batch_ba(vis_ctx* ctx, const vis_ba_params* bp, int n, const vis_ftrack_obs* d_obs, int row_cap, const double* d_poses, double* d_poses_out,
                   vis_ba_window* d_windows, vis_ba_point* d_points, uint8_t* d_flags);
 
+/* ---- loop-closure candidates: a keyframe database on the device and a brute-force scorer (csrc/kfdb.hip; tests/kfdb_ref.py restates it and every
+ * output equals the restatement byte for byte: everything here is integer arithmetic).  Place recognition without a vocabulary: a query frame is
+ * matched against EVERY stored keyframe with the matcher's own rules and the number of symmetric matches is the score.  Additive:
+ * VIS_ABI_VERSION stays 5.
+ * SCORE of a couple (entry E with nE descriptors, query Q with nQ): the length of the symmetric list vis_good_matches_host gives for the pair with E
+ *   as the first frame (queryIdx) and Q as the second (trainIdx), ratio = lp.ratio and sym_mode = lp.sym_mode -- k_filter's computeSymMatches on the
+ *   matcher's keys (Hamming << 16) | row: ties go to the lower row, a side with fewer than two neighbours fails the ratio test (so a couple with
+ *   nE < 2 or nQ < 2 scores 0).  The MATCH LIST of a couple is that list in its order: queryIdx rising, imgIdx = the slot, distance = the Hamming
+ *   distance as float.
+ * THE DATABASE belongs to a context, not to a plan: it outlives vis_batch_plan and vis_batch_reset (vis_destroy does NOT free it: destroy it first).
+ *   A ring of entry_cap slots of kp_cap keypoints.  Adding n rows takes the n slots head, head + 1 ... modulo entry_cap, in row order, and moves the
+ *   head; the oldest entries are overwritten (with n > entry_cap a later row of the same call overwrites an earlier one).  The slot never depends
+ *   on device data: a row with count <= 0 or id < 0 becomes an EMPTY entry (count 0) that is never scored.  Counts are clamped to
+ *   [0, min(row_cap, kp_cap)].  Per entry the device keeps the descriptors as the matcher's FP4 operand (lossless), the pixel (x, y) of every
+ *   keypoint, the count and the id.
+ * ELIGIBLE: entry e may be scored for query q iff the entry is not empty, id_q >= 0 and (int64) id_e + lp.min_gap <= id_q.  Otherwise its score
+ *   is -1.  A query with id_q < 0 or count <= 0 (counts clamped like an entry's) is SKIPPED: flags = VIS_LOOP_SKIPPED, every score -1, no candidate.
+ *   A query sees exactly what EARLIER calls on that database added, so the answer is NOT independent of how a stream is cut into launches: query
+ *   before add in every launch (tools/run_directory.py --loops), and with min_gap >= the launch length the cut cannot matter.
+ * CANDIDATES per query: the lp.topk eligible entries with score >= lp.min_score, ordered by score falling, then id rising, then slot rising, as
+ *   vis_loop_cand; rows with fewer are filled with (-1, -1, 0, 0).  vis_loop_query: the id as given, n_keypoints = the count the
+ *   query took part with (clamped; 0 when it was skipped), n_scored = the eligible entries, n_cand, best_score = the largest score (-1 when nothing
+ *   was scored), flags.
+ * MATCHES of a chosen candidate: for query i the call reads ONE vis_loop_cand at d_cand + i * cand_stride records (the caller picks the rank by
+ *   offsetting the pointer).  When slot is in [0, entry_cap), the slot is not empty and still holds that id, and query i has a count > 0: the first
+ *   min(count, max_pts) entries of the couple's match list (when d_matches is given), d_p1 = the entry's pixels and d_p2 = the query's pixels of
+ *   those entries, d_npts[i] = the FULL count (the consumers clamp it to max_pts, so a truncated row is visible).  Otherwise d_npts[i] = 0 and
+ *   the rows are left untouched.  The rows are what vis_essential_batch, vis_homography_batch and vis_pnp_batch read.
+ * ORDER.  The rows forms run on the context's stream; the batch forms on the POSE stream through the follow-up scaffold behind the matcher of the
+ *   last vis_batch_run (like vis_batch_ftrack) and behind the context's stream.  A database carries its own reader events and a last-writer
+ *   event: calls on one database take effect in CALL ORDER whichever stream they ride -- an add waits for the pending queries, a query for the
+ *   last add.  The rows forms expand the query descriptors into a grow-only block of the context: a call that grows it SYNCHRONISES (every
+ *   stream of the context is drained before the old block is freed).
+ * LIMITS.  One workgroup per (query, slot) couple; its winner tables take 4 (nE + nQ) bytes of LDS beside 9 KB of tiles: 137 KB at kp_cap 16384
+ *   (one workgroup per CU), 10 KB at 1300.  kp_cap <= 16384 is the MFMA matcher's ageing-key limit.  Brute force over entry_cap entries per
+ *   query: DESIGN.md 4.27 has the measured cost.
+ * Out of scope: a coarse prefilter or vocabulary, Sim(3) or pose-graph correction, feeding a verified loop into vis_batch_ba or
+ * vis_batch_trajectory, host adapters, descriptors other than the 32-byte ORB rows. */
+enum { VIS_LOOP_SKIPPED = 1 };
+typedef struct vis_loop_params {     /* 24 bytes; the defaults are this library's own */
+    float   ratio;                   /* 0.8f   taken as written, like vis_params.ratio */
+    int32_t sym_mode;                /* VIS_SYM_INTENDED; one of VIS_SYM_* */
+    int32_t min_gap;                 /* 30     ids between an entry and a query that may be scored against it, >= 0 */
+    int32_t topk;                    /* 4      candidates per query, 1 ... 16 */
+    int32_t min_score;               /* 30     any value (twice the score of unrelated views, an eighteenth of a revisit's) */
+    int32_t reserved_;               /* 0 */
+} vis_loop_params;
+typedef struct vis_loop_cand { int32_t id, slot, score, n_keypoints; } vis_loop_cand;                                        /* 16 bytes */
+typedef struct vis_loop_query { int32_t id, n_keypoints, n_scored, n_cand, best_score, flags, reserved_[2]; } vis_loop_query; /* 32 bytes */
+typedef struct vis_kfdb vis_kfdb;
+typedef struct vis_kfdb_info_t { int32_t entry_cap, kp_cap, head, reserved_; int64_t total_added; } vis_kfdb_info_t;        /* 24 bytes */
+void vis_default_loop_params(vis_loop_params* lp);
+/* Lifetime and bookkeeping.  Refusals, in this order: VIS_E_INVALID (the out pointer NULL, entry_cap outside 1 ... 65536, kp_cap outside
+ * 1 ... 16384, cap negative, a NULL or misaligned (4 bytes) output); VIS_E_STATE without a context / database; VIS_E_INVALID for a slot outside
+ * [0, entry_cap); VIS_E_NOMEM (create).  vis_kfdb_reset empties every slot and puts the head at 0 (queued as a writer on the context's stream);
+ * vis_kfdb_get_entry blocks: id, count and the first min(count, cap) pixel pairs of one slot (HOST pointers; xy may be NULL with cap 0). */
+int  vis_kfdb_create(vis_ctx* ctx, int entry_cap, int kp_cap, vis_kfdb** db);
+void vis_kfdb_destroy(vis_kfdb* db);
+int  vis_kfdb_reset(vis_kfdb* db);
+int  vis_kfdb_info(vis_kfdb* db, vis_kfdb_info_t* info);
+int  vis_kfdb_get_entry(vis_kfdb* db, int slot, int32_t* id, int32_t* count, float* xy, int cap);
+/* Add n rows: DEVICE pointers, asynchronous on the context's stream.  d_kps: n rows of row_cap vis_keypoint; d_desc: n rows of row_cap x 32 bytes;
+ * d_nkp, d_ids: n int32.
+ * Refusals, in this order.  VIS_E_INVALID: a NULL pointer, a pointer that is not aligned (4 bytes; d_desc 4), n or row_cap negative.  VIS_E_STATE
+ * without a database. */
+int  vis_kfdb_add_rows(vis_kfdb* db, int n, const vis_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_nkp, int row_cap, const int32_t* d_ids);
+/* The frames i of the last vis_batch_run (n = its frames) with (seq0 + i) % step == 0, seq0 = the stream number of its frame 0 (frames counted
+ * since vis_batch_plan / vis_batch_reset): the host knows seq0, so the slots are host-decided.  Id = seq0 + i; a frame the keyframe gate did not
+ * save becomes an empty entry.
+ * Refusals, in this order.  VIS_E_INVALID: n negative or step < 1.  VIS_E_STATE: no database / plan / detect stage in the last run, or n differs.
+ * VIS_E_CAPACITY: the plan's keypoint capacity exceeds kp_cap -- never a silent cut. */
+int  vis_batch_kfdb_add(vis_kfdb* db, int n, int step);
+/* Score n query rows against the database: DEVICE pointers, asynchronous on the context's stream.  d_desc, d_nkp, d_ids as in vis_kfdb_add_rows;
+ * d_scores: NULL, or n x entry_cap int32 (the whole score row, -1 where not scored); d_cand: n x lp.topk records; d_query: n records.
+ * Refusals, in this order.  VIS_E_INVALID: lp NULL or outside its ranges, a NULL pointer (d_scores may be), a pointer that is not aligned (4 bytes),
+ * n or row_cap negative.  VIS_E_STATE without a database.  VIS_E_CAPACITY when n x entry_cap exceeds 2^28 couples.
+ * Without d_scores the score rows live in a grow-only block of the database: a call that grows it synchronises, and such a query is ordered like
+ * an add (two of them never share the block). */
+int  vis_kfdb_query_rows(vis_kfdb* db, const vis_loop_params* lp, int n, const uint8_t* d_desc, const int32_t* d_nkp, int row_cap, const int32_t* d_ids,
+                         int32_t* d_scores, vis_loop_cand* d_cand, vis_loop_query* d_query);
+/* The same for the frames of the last vis_batch_run: ids and counts are the run's, the operands the plan's expanded descriptors; a frame not on the
+ * step, or one the keyframe gate did not save, is skipped; a frame off the step launches no work.  The last run must have included VIS_STAGE_MATCH (the expanded descriptors are the matcher's;
+ * VIS_E_STATE otherwise), where vis_batch_kfdb_add needs the detect stage alone.  Refusals as vis_batch_kfdb_add, after lp and the pointers as above. */
+int  vis_batch_kfdb_query(vis_kfdb* db, const vis_loop_params* lp, int n, int step, int32_t* d_scores, vis_loop_cand* d_cand, vis_loop_query* d_query);
+/* The matches of one chosen candidate per query.  d_kps: n rows of row_cap vis_keypoint of the queries; d_matches: NULL, or n rows of max_pts
+ * vis_dmatch; d_p1, d_p2: n rows of max_pts (x, y) floats; d_npts: n int32.
+ * Refusals, in this order.  VIS_E_INVALID: lp as above, a NULL pointer (d_matches may be), a pointer that is not aligned (8 bytes for d_p1 / d_p2,
+ * 4 otherwise), n, row_cap, cand_stride or max_pts negative.  VIS_E_STATE without a database. */
+int  vis_kfdb_match_rows(vis_kfdb* db, const vis_loop_params* lp, int n, const vis_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_nkp,
+                         int row_cap, const vis_loop_cand* d_cand, int cand_stride, int max_pts, vis_dmatch* d_matches, float* d_p1, float* d_p2,
+                         int32_t* d_npts);
+/* The same for the frames of the last vis_batch_run (keypoints, operands and counts are the plan's; a frame the gate did not save has count 0).
+ * Refusals as vis_batch_kfdb_add (step apart), after lp and the pointers as above. */
+int  vis_batch_kfdb_match(vis_kfdb* db, const vis_loop_params* lp, int n, const vis_loop_cand* d_cand, int cand_stride, int max_pts,
+                          vis_dmatch* d_matches, float* d_p1, float* d_p2, int32_t* d_npts);
+
 /* ---- synthetic EuRoC-shaped stream ("S-752") -------- */
 /* Integer-only generator, identical bytes on every machine.  canvas: canvas_dim^2 bytes. */
 int  vis_synth_canvas(uint8_t* canvas, int canvas_dim, uint64_t seed);

@@ -60,6 +60,10 @@ MH_01 can run `python tools/run_directory.py /data/MH_01/mav0/cam0/data --frames
              vis_batch_trajectory and vis_batch_ftrack, default parameters; the N-view triangulation then reads the adjusted poses): one row per frame
              -- frame, stamp, the flags and the point count of the frame's window, the adjusted R (row-major) and t.  A batch is adjusted on its own:
              observations of earlier batches are not held.
+  --loops out.csv [--loop-step K --loop-gap G --loop-entries N]: loop-closure candidates (vis_batch_kfdb_query, _match and _add behind every batch: query
+             first, then add, so a frame sees the keyframes of EARLIER batches only; every K-th frame is a query and a keyframe, an entry must be G
+             frames older than its query, the database holds the last N keyframes).  The rank-0 candidate's matches go through vis_essential_batch.
+             One row per query with a candidate -- frame, stamp, the candidate's frame, score, match count, RANSAC inliers.
   --vi-align out.csv: with --imu and --trajectory, align the chained trajectory with the IMU on the device (vis_batch_vi_align behind
              vis_batch_trajectory and vis_batch_imu of every batch, default parameters; the sums and tails continue across the batches).  One row
              per frame -- frame index, timestamp, flags (VIS_VIS_*), q, res, p (3), v (3), under the batch's own solution; the JSON line carries the
@@ -147,6 +151,10 @@ def main():
     ap.add_argument("--tracks", default=None, metavar="CSV", help="link the symmetric matches into feature tracks; write every frame's summary and length histogram here")
     ap.add_argument("--trajectory", default=None, metavar="CSV", help="chain the two-view poses under the scale links; write one pose per frame here")
     ap.add_argument("--ba", default=None, metavar="CSV", help="with --trajectory: windowed bundle adjustment of the chained poses; one adjusted pose per frame here")
+    ap.add_argument("--loops", default=None, metavar="CSV", help="loop-closure candidates of every loop-step-th frame against the keyframe database; one row per query with a candidate")
+    ap.add_argument("--loop-step", type=int, default=8)
+    ap.add_argument("--loop-gap", type=int, default=30)
+    ap.add_argument("--loop-entries", type=int, default=1024)
     ap.add_argument("--imu", default=None, metavar="CSV", help="EuRoC imu0/data.csv: timestamp [ns], w, a")
     ap.add_argument("--imu-out", default=None, metavar="CSV", help="with --imu: write every frame's preintegrated pair delta here")
     ap.add_argument("--imu-jac", default=None, metavar="CSV", help="with --imu: write every frame's bias Jacobians of v and p here")
@@ -241,6 +249,18 @@ def main():
         d_bposes, d_bwin = z(B * 96), z(max(nbw, 1) * vislam.BA_WINDOW_DTYPE.itemsize)
         d_bpts, d_bfl = z(B * jk * vislam.BA_POINT_DTYPE.itemsize), z(B * jk)
         ba_rows, ba_totals = [], dict(windows=0, refined=0, few=0, restart=0, no_scale=0, points=0, observations=0, accepted=0, rejected=0, cost0=0.0, cost1=0.0)
+    if a.loops:
+        if a.loop_step < 1 or a.loop_gap < 0 or not 1 <= a.loop_entries <= 65536:
+            raise SystemExit("--loop-step >= 1, --loop-gap >= 0, 1 <= --loop-entries <= 65536")
+        lk = ctx.keypoint_capacity(w, h)
+        lcap = min(lk, 8192)                                 # (the limit of every RANSAC problem)
+        lpp = vislam.default_loop_params()
+        lpp.min_gap = a.loop_gap
+        ldb = ctx.kfdb(a.loop_entries, lk)
+        zl = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+        d_lcand, d_lquery = zl(B * lpp.topk * vislam.LOOP_CAND_DTYPE.itemsize), zl(B * vislam.LOOP_QUERY_DTYPE.itemsize)
+        d_lp1, d_lp2, d_lnpts, d_lpose = zl(B * lcap * 8), zl(B * lcap * 8), zl(B * 4), zl(B * vislam.POSE_RESULT_DTYPE.itemsize)
+        loop_rows, loop_totals = [], dict(queries=0, couples=0, candidates=0, verified=0)
     if a.imu:
         if not a.imu_out:
             raise SystemExit("--imu needs --imu-out")
@@ -424,9 +444,28 @@ def main():
         if a.imu_factor:                                     # behind the covariance and the alignment of the batch: their buffers, no host step
             d_fres, d_fstate = (d_bres, d_bstate) if a.vi_align_ba else (d_vres, d_vstate)
             ctx.batch_imu_factor(nb, d_jtraj.data_ptr(), d_cdelta.data_ptr(), d_icov.data_ptr(), d_fstate.data_ptr(), d_fres.data_ptr(), d_ifac.data_ptr())
+        if a.loops:                                          # query -> the rank-0 candidate's matches -> add: queued on the pose stream, no host step
+            ldb.batch_query(nb, 0, d_lcand.data_ptr(), d_lquery.data_ptr(), a.loop_step, lpp)
+            ldb.batch_match(nb, d_lcand.data_ptr(), lpp.topk, lcap, 0, d_lp1.data_ptr(), d_lp2.data_ptr(), d_lnpts.data_ptr(), lpp)
+            ldb.batch_add(nb, a.loop_step)
         if feed:
             feed.release(k)
         ctx.batch_sync()                                     # (results are fetched per batch below: this harness reports, it does not pipeline)
+        if a.loops:                                          # (vis_essential_batch rides the context's stream: behind the synchronisation)
+            ctx.essential_batch(nb, d_lp1.data_ptr(), d_lp2.data_ptr(), d_lnpts.data_ptr(), lcap, 0, 0, d_lpose.data_ptr())
+            ctx.batch_sync()
+            lc = d_lcand.cpu().numpy().view(vislam.LOOP_CAND_DTYPE).reshape(B, lpp.topk)
+            lq = d_lquery.cpu().numpy().view(vislam.LOOP_QUERY_DTYPE)
+            ln, lpo = d_lnpts.cpu().numpy().view(np.int32), d_lpose.cpu().numpy().view(vislam.POSE_RESULT_DTYPE)
+            for i in range(nb):
+                if lq[i]["flags"] & vislam.LOOP_SKIPPED:
+                    continue
+                loop_totals["queries"] += 1
+                loop_totals["couples"] += int(lq[i]["n_scored"])
+                if lc[i, 0]["slot"] >= 0:
+                    loop_totals["candidates"] += 1
+                    loop_totals["verified"] += int(lpo[i]["n_inliers"] >= 30)
+                    loop_rows.append((first + i, stamps[first + i], int(lc[i, 0]["id"]), int(lc[i, 0]["score"]), int(ln[i]), int(lpo[i]["n_inliers"])))
         if a.rectify and host is not None:                   # --check: the oracle reads the frames the device rectified
             host[first:first + nb] = d_rect[k][:nb * h * stride].cpu().numpy().reshape(nb, h, stride)[:, :, :w]
         if a.track:
@@ -654,6 +693,12 @@ def main():
                 f.write("%d,%d,%d,%d," % (fi, ts, wf, wn) + ",".join("%.17g" % v for v in pose) + "\n")
         out["ba_csv"] = a.ba
         out["ba"] = ba_totals
+    if a.loops:
+        with open(a.loops, "w") as f:                           # frame, stamp, the candidate's frame, score, matches, RANSAC inliers
+            for row in loop_rows:
+                f.write("%d,%d,%d,%d,%d,%d\n" % row)
+        out["loops_csv"] = a.loops
+        out["loops"] = loop_totals
     if a.imu:
         with open(a.imu_out, "w") as f:                         # frame, stamp, flags, q, n_steps, dt, R, v, p
             for fi, ts, r in imu_rows:

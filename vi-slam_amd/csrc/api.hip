@@ -142,7 +142,7 @@ extern "C" void vis_destroy(vis_ctx* ctx) {
     if (ctx->pose_stream) (void)hipStreamSynchronize(ctx->pose_stream);
     plan_destroy(ctx->single); plan_destroy(ctx->batch);
     if (ctx->d_scratch) (void)hipFree(ctx->d_scratch);
-    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws, &ctx->imuj_ws, &ctx->imuc_ws}) if (b->p) (void)hipFree(b->p);
+    for (const DevBlock* b : {&ctx->ess_ws, &ctx->ft_ws, &ctx->sl_ws, &ctx->tjr_ws, &ctx->imu_ws, &ctx->imuj_ws, &ctx->imuc_ws, &ctx->kfdb_ws}) if (b->p) (void)hipFree(b->p);
     if (ctx->h_pin) (void)hipHostFree(ctx->h_pin);
     if (ctx->d_sample_table) (void)hipFree(ctx->d_sample_table);
     for (int i = 0; i < 12; i++) (void)hipEventDestroy(ctx->ev[i]);

@@ -251,6 +251,7 @@ struct vis_ctx {
     // vis_imu_preintegrate_cov (the table with the covariance's blocks).  SEVEN blocks, apart from the scratch
     // block and from each other: a host-pointer call between two batches, or another of these calls, cannot move the block a queued call was given
     DevBlock ess_ws, ft_ws, sl_ws, tjr_ws, imu_ws, imuj_ws, imuc_ws;
+    DevBlock kfdb_ws;                        // vis_kfdb_query_rows / vis_kfdb_match_rows (kfdb.hip): the queries' expanded descriptors
     // grow-only PINNED host block of the single-frame entry points: a caller's pageable buffer is copied through it, so that every
     // upload / download of a call is an asynchronous copy on the context's stream and the call blocks ONCE, at its end (HostStage, api.hip)
     void* h_pin = nullptr; size_t h_pin_bytes = 0; void* h_pin_dev = nullptr;   // (h_pin_dev: the block's device address; nullptr = not device-accessible)

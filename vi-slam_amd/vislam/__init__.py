@@ -332,6 +332,24 @@ def ba_windows(n, stride):
     return (n - 1 + stride - 1) // stride if n > 1 else 0
 
 
+class LoopParams(C.Structure):
+    """vis_loop_params: the knobs of the loop-candidate scorer (vis_default_loop_params: 0.8f, SYM_INTENDED, 30, 4, 30)"""
+    _fields_ = [("ratio", C.c_float), ("sym_mode", C.c_int32), ("min_gap", C.c_int32), ("topk", C.c_int32), ("min_score", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+class KfDbInfo(C.Structure):
+    """vis_kfdb_info_t"""
+    _fields_ = [("entry_cap", C.c_int32), ("kp_cap", C.c_int32), ("head", C.c_int32), ("reserved_", C.c_int32), ("total_added", C.c_int64)]
+
+
+LOOP_CAND_DTYPE = np.dtype([("id", "<i4"), ("slot", "<i4"), ("score", "<i4"), ("n_keypoints", "<i4")])
+LOOP_QUERY_DTYPE = np.dtype([("id", "<i4"), ("n_keypoints", "<i4"), ("n_scored", "<i4"), ("n_cand", "<i4"), ("best_score", "<i4"), ("flags", "<i4"),
+                             ("reserved_", "<i4", (2,))])
+assert LOOP_CAND_DTYPE.itemsize == 16 and LOOP_QUERY_DTYPE.itemsize == 32 and C.sizeof(LoopParams) == 24 and C.sizeof(KfDbInfo) == 24
+LOOP_SKIPPED = 1
+
+
 FT_NO_PAIR, FT_NO_CARRY = 1, 2
 FT_SYM, FT_GOOD = 0, 1
 FTP_FRONT, FTP_REPROJ_OK, FTP_PARALLAX_OK, FTP_KEPT, FTP_FEW, FTP_SINGULAR = 1, 2, 4, 8, 16, 32
@@ -563,6 +581,8 @@ ABI_SYMBOLS = [
     "vis_default_vi_align_params", "vis_vi_align_rows", "vis_batch_vi_align", "vis_batch_vi_align_init",
     "vis_default_vi_align_ba_params", "vis_vi_align_ba_rows", "vis_batch_vi_align_ba", "vis_batch_vi_align_ba_init",
     "vis_default_ba_params", "vis_ba_rows", "vis_batch_ba",
+    "vis_default_loop_params", "vis_kfdb_create", "vis_kfdb_destroy", "vis_kfdb_reset", "vis_kfdb_info", "vis_kfdb_get_entry", "vis_kfdb_add_rows",
+    "vis_batch_kfdb_add", "vis_kfdb_query_rows", "vis_batch_kfdb_query", "vis_kfdb_match_rows", "vis_batch_kfdb_match",
 ]
 
 
@@ -663,6 +683,22 @@ def _load():
         lib.vis_default_ba_params.restype = None
         lib.vis_ba_rows.argtypes = [vp, bap, ci, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp]
         lib.vis_batch_ba.argtypes = [vp, bap, ci, vp, ci, vp, vp, vp, vp, vp]
+    if hasattr(lib, "vis_kfdb_create"):                 # (absent from older A/B builds)
+        lpp = C.POINTER(LoopParams)
+        lib.vis_default_loop_params.argtypes = [lpp]
+        lib.vis_default_loop_params.restype = None
+        lib.vis_kfdb_create.argtypes = [vp, ci, ci, C.POINTER(C.c_void_p)]
+        lib.vis_kfdb_destroy.argtypes = [vp]
+        lib.vis_kfdb_destroy.restype = None
+        lib.vis_kfdb_reset.argtypes = [vp]
+        lib.vis_kfdb_info.argtypes = [vp, C.POINTER(KfDbInfo)]
+        lib.vis_kfdb_get_entry.argtypes = [vp, ci, C.POINTER(C.c_int32), C.POINTER(C.c_int32), vp, ci]
+        lib.vis_kfdb_add_rows.argtypes = [vp, ci, vp, vp, vp, ci, vp]
+        lib.vis_batch_kfdb_add.argtypes = [vp, ci, ci]
+        lib.vis_kfdb_query_rows.argtypes = [vp, lpp, ci, vp, vp, ci, vp, vp, vp, vp]
+        lib.vis_batch_kfdb_query.argtypes = [vp, lpp, ci, ci, vp, vp, vp]
+        lib.vis_kfdb_match_rows.argtypes = [vp, lpp, ci, vp, vp, vp, ci, vp, ci, ci, vp, vp, vp, vp]
+        lib.vis_batch_kfdb_match.argtypes = [vp, lpp, ci, vp, ci, ci, vp, vp, vp, vp]
     if hasattr(lib, "vis_batch_trajectory"):            # (absent from older A/B builds)
         slp = C.POINTER(ScaleLinkParams)
         lib.vis_default_scale_link_params.argtypes = [slp]
@@ -907,6 +943,12 @@ def default_scale_link_params():
     return sp
 
 
+def default_loop_params():
+    lp = LoopParams()
+    lib.vis_default_loop_params(C.byref(lp))
+    return lp
+
+
 def default_ba_params():
     bp = BaParams()
     lib.vis_default_ba_params(C.byref(bp))
@@ -1086,6 +1128,74 @@ class Rectify:
             self.ctx._rectifiers.remove(self)
 
 
+class KfDb:
+    """a keyframe database on the device (vis_kfdb_*): a ring of entry_cap slots of kp_cap keypoints, scored by brute force against query frames;
+    made by Context.kfdb.  It outlives batch_plan and batch_reset; the context closes it when it closes itself.  Every pointer is a raw DEVICE
+    pointer; the rows forms are asynchronous on the context's stream, the batch forms on the pose stream (in use until batch_sync())."""
+
+    def __init__(self, ctx, entry_cap, kp_cap):
+        self.ctx, self.entry_cap, self.kp_cap = ctx, entry_cap, kp_cap
+        self._d = C.c_void_p()
+        ctx._chk(lib.vis_kfdb_create(ctx._h, entry_cap, kp_cap, C.byref(self._d)), "vis_kfdb_create")
+        ctx._kfdbs.append(self)
+
+    def close(self):
+        if self._d:
+            lib.vis_kfdb_destroy(self._d)                # (while the context lives: Context.close closes its databases first)
+            self._d = C.c_void_p()
+        if self in self.ctx._kfdbs:
+            self.ctx._kfdbs.remove(self)
+
+    def reset(self):
+        self.ctx._chk(lib.vis_kfdb_reset(self._d), "vis_kfdb_reset")
+
+    def info(self):
+        o = KfDbInfo()
+        self.ctx._chk(lib.vis_kfdb_info(self._d, C.byref(o)), "vis_kfdb_info")
+        return o
+
+    def get_entry(self, slot):
+        """(id, count, (count, 2) float32 pixels) of one slot; blocks"""
+        i, c = C.c_int32(0), C.c_int32(0)
+        xy = np.zeros((self.kp_cap, 2), np.float32)
+        self.ctx._chk(lib.vis_kfdb_get_entry(self._d, slot, C.byref(i), C.byref(c), _ptr(xy), self.kp_cap), "vis_kfdb_get_entry")
+        return i.value, c.value, xy[:max(c.value, 0)].copy()
+
+    def add_rows(self, n, d_kps_ptr, d_desc_ptr, d_nkp_ptr, row_cap, d_ids_ptr):
+        v = lambda a: C.c_void_p(a) if a else None
+        self.ctx._chk(lib.vis_kfdb_add_rows(self._d, n, v(d_kps_ptr), v(d_desc_ptr), v(d_nkp_ptr), row_cap, v(d_ids_ptr)), "vis_kfdb_add_rows")
+
+    def batch_add(self, n, step=1):
+        """the frames of the last batch_run on the step, id = their stream number"""
+        self.ctx._chk(lib.vis_batch_kfdb_add(self._d, n, step), "vis_batch_kfdb_add")
+
+    def query_rows(self, n, d_desc_ptr, d_nkp_ptr, row_cap, d_ids_ptr, d_scores_ptr, d_cand_ptr, d_query_ptr, lp=None):
+        """scores (n x entry_cap int32, or 0), n x topk LOOP_CAND_DTYPE and n LOOP_QUERY_DTYPE records of n query rows"""
+        lp = default_loop_params() if lp is None else lp
+        v = lambda a: C.c_void_p(a) if a else None
+        self.ctx._chk(lib.vis_kfdb_query_rows(self._d, C.byref(lp), n, v(d_desc_ptr), v(d_nkp_ptr), row_cap, v(d_ids_ptr), v(d_scores_ptr), v(d_cand_ptr),
+                                              v(d_query_ptr)), "vis_kfdb_query_rows")
+
+    def batch_query(self, n, d_scores_ptr, d_cand_ptr, d_query_ptr, step=1, lp=None):
+        lp = default_loop_params() if lp is None else lp
+        v = lambda a: C.c_void_p(a) if a else None
+        self.ctx._chk(lib.vis_batch_kfdb_query(self._d, C.byref(lp), n, step, v(d_scores_ptr), v(d_cand_ptr), v(d_query_ptr)), "vis_batch_kfdb_query")
+
+    def match_rows(self, n, d_kps_ptr, d_desc_ptr, d_nkp_ptr, row_cap, d_cand_ptr, cand_stride, max_pts, d_matches_ptr, d_p1_ptr, d_p2_ptr, d_npts_ptr,
+                   lp=None):
+        """the match list and the pixel rows (what essential_batch reads) of ONE candidate per query: the record at d_cand_ptr + 16 i cand_stride"""
+        lp = default_loop_params() if lp is None else lp
+        v = lambda a: C.c_void_p(a) if a else None
+        self.ctx._chk(lib.vis_kfdb_match_rows(self._d, C.byref(lp), n, v(d_kps_ptr), v(d_desc_ptr), v(d_nkp_ptr), row_cap, v(d_cand_ptr), cand_stride,
+                                              max_pts, v(d_matches_ptr), v(d_p1_ptr), v(d_p2_ptr), v(d_npts_ptr)), "vis_kfdb_match_rows")
+
+    def batch_match(self, n, d_cand_ptr, cand_stride, max_pts, d_matches_ptr, d_p1_ptr, d_p2_ptr, d_npts_ptr, lp=None):
+        lp = default_loop_params() if lp is None else lp
+        v = lambda a: C.c_void_p(a) if a else None
+        self.ctx._chk(lib.vis_batch_kfdb_match(self._d, C.byref(lp), n, v(d_cand_ptr), cand_stride, max_pts, v(d_matches_ptr), v(d_p1_ptr), v(d_p2_ptr),
+                                               v(d_npts_ptr)), "vis_batch_kfdb_match")
+
+
 class Feeder:
     """pinned-host double-buffered H2D feeder (vis_feeder_*)"""
 
@@ -1137,6 +1247,7 @@ class Context:
     def __init__(self, device=0, params=None):
         self._h = C.c_void_p()
         self._rectifiers = []                                # open Rectify objects: closed before the context
+        self._kfdbs = []                                     # open KfDb objects: the same
         rc = lib.vis_create(int(device), C.byref(self._h))
         if rc:
             self._h = None
@@ -1146,7 +1257,7 @@ class Context:
             self.set_params(params)
 
     def close(self):
-        for r in list(getattr(self, "_rectifiers", ())):
+        for r in list(getattr(self, "_rectifiers", ())) + list(getattr(self, "_kfdbs", ())):
             r.close()
         if getattr(self, "_h", None):
             lib.vis_destroy(self._h)                         # (synchronises the stream set_stream gave it: released only now)
@@ -1181,6 +1292,10 @@ class Context:
         that stream has drained"""
         self._chk(lib.vis_synth_frames_device(self._h, C.c_void_p(d_canvas_ptr), dim, C.c_uint64(seed), t0, n, w, h, stride,
                                               1 if parallax else 0, C.c_void_p(d_out_ptr)), "vis_synth_frames_device")
+
+    def kfdb(self, entry_cap, kp_cap):
+        """vis_kfdb_create: a keyframe database for loop-closure candidates"""
+        return KfDb(self, entry_cap, kp_cap)
 
     def rectify(self, K, dist, Knew, in_size, out_size):
         """vis_rectify_create: the rectification tables of (K, dist) onto K' for in_size -> out_size ((w, h)); close() before the
