@@ -278,10 +278,11 @@ def _candidate(W, cidx, free, P, X, d, ok, Vi, g, Wc, cam_of):
     return Pn, Xn
 
 
-def ba_rows(bp, cam, prev, nkp, obs, xy, poses, points=None, flags=None, log=None):
+def ba_rows(bp, cam, prev, nkp, obs, xy, poses, points=None, flags=None, log=None, stats=None):
     """obs: (n, row_cap) fr.OBS_DTYPE; xy: (n, row_cap, 2) float32; poses: (n, 12) float64.  points / flags: the buffers as they stand before the
     call (entries k >= nk(i), and everything when n <= 1, keep their bytes).  log: a list that receives (window, linearisation, what) with what in
-    "accept", "reject", "pivot".  Returns (poses_out (n, 12), windows, points (n, row_cap) POINT_DTYPE, flags (n, row_cap) uint8)."""
+    "accept", "reject", "pivot".  stats: a list that receives (window, linearisation, the number of used points that sat it out).
+    Returns (poses_out (n, 12), windows, points (n, row_cap) POINT_DTYPE, flags (n, row_cap) uint8)."""
     n, R = obs.shape
     poses = np.ascontiguousarray(poses, np.float64).reshape(n, 12)
     out = poses.copy()
@@ -369,6 +370,8 @@ def ba_rows(bp, cam, prev, nkp, obs, xy, poses, points=None, flags=None, log=Non
                 lam, nrej = min(10.0 * lam, 1e12), nrej + 1
             if log is not None:
                 log.append((j, it, what))
+            if stats is not None:
+                stats.append((j, it, int((~ok).sum())))
         rec["n_lin"], rec["n_accepted"], rec["n_rejected"], rec["cost1"], rec["lambda_"] = bp.lm_iters, nacc, nrej, cur, lam
         rec["flags"] = BA_REFINED
         o = _observe(cam, bp, W, P, X)
