@@ -95,6 +95,12 @@ def clamp_count(n, row_cap, kp_cap):
     return min(max(int(n), 0), min(row_cap, kp_cap))
 
 
+def row_cap_of(desc, n):
+    """the row capacity of a call's padded descriptor rows; 0 for no rows or rows without room for a keypoint"""
+    d = np.asarray(desc)
+    return 0 if n == 0 or d.size == 0 else d.reshape(n, -1, 32).shape[1]
+
+
 class KfDb:
     """the ring as the contract states it; keys_fn(e_desc, q_desc) -> (k12, k21) may be replaced (the CPU oracle's 2-NN for sets too large for numpy)"""
 
@@ -113,7 +119,7 @@ class KfDb:
     def add_rows(self, kps, desc, nkp, ids):
         """kps (n, row_cap) KEYPOINT_DTYPE, desc (n, row_cap, 32), nkp / ids (n,): the n slots behind the head, in order"""
         n = len(nkp)
-        row_cap = np.asarray(desc).reshape(n, -1, 32).shape[1] if n else 0
+        row_cap = row_cap_of(desc, n)
         for i in range(n):
             s = (self.head + i) % self.entry_cap
             c = clamp_count(nkp[i], row_cap, self.kp_cap)
@@ -130,11 +136,13 @@ class KfDb:
     def eligible(self, slot, id_q, lp):
         return self.cnt[slot] > 0 and id_q >= 0 and int(self.id[slot]) + int(lp.min_gap) <= int(id_q)
 
-    def query_rows(self, lp, desc, nkp, ids):
-        """-> (scores (n, entry_cap) int32, cand (n, topk) CAND_DTYPE, query (n,) QUERY_DTYPE)"""
+    def query_rows(self, lp, desc, nkp, ids, rank_key=None):
+        """-> (scores (n, entry_cap) int32, cand (n, topk) CAND_DTYPE, query (n,) QUERY_DTYPE); rank_key(score, id, slot): a sort key in place of
+        the contract's (score falling, id rising, slot rising) -- for the tests that show a table tells the orders apart"""
         assert params_ok(lp)
+        rank_key = rank_key or (lambda sc, i_, s_: (-sc, i_, s_))
         n = len(nkp)
-        row_cap = np.asarray(desc).reshape(n, -1, 32).shape[1] if n else 0
+        row_cap = row_cap_of(desc, n)
         scores = np.full((n, self.entry_cap), -1, np.int32)
         cand = np.zeros((n, lp.topk), CAND_DTYPE)
         cand["id"], cand["slot"] = -1, -1
@@ -149,7 +157,7 @@ class KfDb:
                     if self.eligible(s, int(ids[i]), lp):
                         scores[i, s] = len(couple_list(self.desc[s], qd, lp, s, self.keys_fn))
             order = sorted((s for s in range(self.entry_cap) if scores[i, s] >= 0 and scores[i, s] >= lp.min_score),
-                           key=lambda s: (-int(scores[i, s]), int(self.id[s]), s))[:lp.topk]
+                           key=lambda s: rank_key(int(scores[i, s]), int(self.id[s]), s))[:lp.topk]
             for r, s in enumerate(order):
                 cand[i, r] = (self.id[s], s, scores[i, s], self.cnt[s])
             query[i] = (ids[i], c, int((scores[i] >= 0).sum()), len(order), int(scores[i].max()), 0 if c > 0 else LOOP_SKIPPED, (0, 0))
@@ -160,7 +168,7 @@ class KfDb:
         buffers as they were, returned with what the call writes"""
         assert params_ok(lp)
         n = len(nkp)
-        row_cap = np.asarray(desc).reshape(n, -1, 32).shape[1] if n else 0
+        row_cap = row_cap_of(desc, n)
         matches = None if matches is None else matches.copy()
         p1, p2, npts = p1.copy(), p2.copy(), npts.copy()
         for i in range(n):

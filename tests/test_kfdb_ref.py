@@ -180,3 +180,146 @@ def test_match_rows_and_stale_candidates():
     db.add_rows(kps2, desc2, nkp2, np.array([2], np.int32))           # slot 0 is overwritten: the candidate (0, 0, ...) is stale now
     _, _, _, npts = db.match_rows(lp, qk, qd, qn, cand, 4, None, fill(np.float32, (5, 4, 2)), fill(np.float32, (5, 4, 2)), fill(np.int32, (5,)))
     assert npts.tolist() == [0, 3, 0, 0, 0]
+
+
+# ---- the builders of tests/test_kfdb_limits_gpu.py: the oracle agrees with the restatement on every one of them, and they discriminate ------
+@pytest.fixture(scope="module")
+def ladders():
+    return {ns: kc.ladder(ns) for ns in kc.LADDER_NS}
+
+
+def test_ladder_shape(ladders):
+    """every position pair of the issue's list, f at every fixed index named, the random rows far from f"""
+    for ns, cs in ladders.items():
+        P = kc.ladder_positions(ns)
+        assert set(kc.LADDER_P) <= set(P) and (ns == 64 or {64, 65} <= set(P)) and max(P) == ns - 1
+        pairs = {(a, b) for i, a in enumerate(P) for b in P[i + 1:]}
+        for kind in ("tie", "ab", "ba"):
+            assert {(c["a"], c["b"]) for c in cs if c["kind"] == kind} == pairs
+        assert {c["f"] for c in cs} == {0, 31, 32, 63, 64, 255, 256, 257} and {c["kind"] for c in cs} >= {"control_ab", "control_ba"}
+        for c in cs:
+            d = kr.hamming(c["fixed"][c["f"]][None], np.concatenate([c["fixed"], c["swept"]]))[0]
+            d[c["f"]] = d[len(c["fixed"]) + c["a"]] = d[len(c["fixed"]) + c["b"]] = 999
+            assert d.min() > 64 and len(c["swept"]) == ns and len(c["fixed"]) == dict(kc.LADDER_FIXED_BY_F)[c["f"]]
+    assert sum(len(cs) for cs in ladders.values()) == 3 * (120 + 153) + 4
+
+
+@pytest.mark.parametrize("planted_is_entry", [True, False], ids=["planted_entry", "planted_query"])
+def test_ladder_restatement_equals_the_oracle(vislam, orc, ladders, planted_is_entry):
+    """keys and list of every ladder couple; the plant decides the list as the builder says: the tie names the lower row, 32 against 39 drops f,
+    32 against 40 keeps it"""
+    for ns, cs in ladders.items():
+        for c in cs:
+            E, Q = kc.ladder_sets(c, planted_is_entry)
+            p, lp = oracle_params(vislam, c["ratio"], kr.SYM_INTENDED), kr.Params(ratio=c["ratio"], sym_mode=kr.SYM_INTENDED)
+            o12, o21 = orc.knn2_hamming(E, Q)
+            k12, k21 = kr.couple_keys(E, Q)
+            assert (kr.keys_from_dmatch(o12) == k12).all() and (kr.keys_from_dmatch(o21) == k21).all(), (ns, c["kind"], c["a"], c["b"])
+            got = kr.sym_list(k12, k21, lp.ratio, lp.sym_mode)
+            assert got.tobytes() == oracle_list(orc, p, E, Q).tobytes(), (ns, c["kind"], c["a"], c["b"])
+            assert kc.ladder_match_of_f(c, planted_is_entry, got) == c["expect"], (ns, c["kind"], c["a"], c["b"])
+            kf = (k12 if planted_is_entry else k21)[c["f"]]
+            first, second = (c["b"], c["a"]) if c["kind"] in ("ba", "control_ba") else (c["a"], c["b"])
+            assert (kf & 0xFFFF).tolist() == [first, second] and (kf >> 16).tolist() == {"tie": [3, 3], "ab": [32, 39], "ba": [32, 39]}.get(c["kind"], [32, 40])
+
+
+@pytest.mark.parametrize("wrong", [kc.wrong_knn2_tie_to_the_higher_row, kc.wrong_knn2_second_is_the_third, kc.wrong_knn2_halves_merged_by_their_seconds])
+def test_ladder_discriminates(ladders, wrong):
+    """each deliberately wrong 2-NN changes the expected bytes of ladder couples, in both orientations -- and of none of the wrong kind: a tie
+    does not notice a lost second neighbour, a first / second pair does not notice the tie rule"""
+    changed = {(o, k): 0 for o in (True, False) for k in ("tie", "ab", "ba")}
+    for cs in ladders.values():
+        for c in cs[::5] + [x for x in cs if (x["a"], x["b"]) in ((3, 4), (31, 32), (0, 63))]:
+            lp = kr.Params(ratio=c["ratio"], sym_mode=kr.SYM_INTENDED)
+            for o in (True, False):
+                E, Q = kc.ladder_sets(c, o)
+                if kr.couple_list(E, Q, lp).tobytes() != kr.couple_list(E, Q, lp, keys_fn=kc.wrong_keys(wrong)).tobytes() and c["kind"] in ("tie", "ab", "ba"):
+                    changed[(o, c["kind"])] += 1
+    print(wrong.__name__, changed)
+    tie_rule = wrong is kc.wrong_knn2_tie_to_the_higher_row
+    for o in (True, False):
+        assert (changed[(o, "tie")] > 0) == tie_rule and (changed[(o, "ab")] > 0) == (not tie_rule) and (changed[(o, "ba")] > 0) == (not tie_rule), changed
+
+
+@pytest.mark.parametrize("sym_mode", [kr.SYM_REFERENCE_EFFECTIVE, kr.SYM_INTENDED])
+@pytest.mark.parametrize("ratio", [kc.F8, 1.0])
+def test_all_equal_sets_against_the_oracle(vislam, orc, ratio, sym_mode):
+    """every distance 0: entry 0 and query 0 take each other, the score is 1; every distance 256: 256 > 0.8f * 256 drops everything, ratio 1.0 keeps
+    the same single match"""
+    entries, queries = kc.all_equal_sets()
+    p, lp = oracle_params(vislam, ratio, sym_mode), kr.Params(ratio=ratio, sym_mode=sym_mode)
+    n4 = len(kc.ALL_EQUAL_COUNTS)
+    for i, E in enumerate(entries):
+        for j, Q in enumerate(queries):
+            got = kr.couple_list(E, Q, lp)
+            assert got.tobytes() == oracle_list(orc, p, E, Q).tobytes(), (i, j)
+            if i < n4 and j < n4:
+                assert got[["queryIdx", "trainIdx"]].tolist() == [(0, 0)] and got["distance"][0] == 0
+            if i >= n4 and j >= n4:
+                assert got["distance"].tolist() == ([256.0] if ratio == 1.0 else [])
+
+
+@pytest.mark.parametrize("entry_cap", kc.RING_CAPS)
+def test_ring_tables_tell_the_orders_apart(entry_cap):
+    """the large-ring tables: the scores are the planted ones, 15 / 16 / 17 entries at or above the three min_scores, and a top-k ordered by
+    (score, slot) instead of (score, id, slot) gives other bytes"""
+    db = kr.KfDb(entry_cap, 32)
+    kps, desc, nkp, ids = kc.ring_table(entry_cap)
+    db.add_rows(kps, desc, nkp, ids)
+    qk, qd, qn, qi = kc.ring_queries(entry_cap)
+    for ms, count in kc.RING_MIN_SCORES.items():
+        lp = kr.Params(min_gap=0, topk=16, min_score=ms)
+        scores, cand, query = db.query_rows(lp, qd, qn, qi)
+        assert [int(scores[0, s]) for g in kc.RING_GROUPS[entry_cap] for s in g] == [9 - i for i, g in enumerate(kc.RING_GROUPS[entry_cap]) for _ in g]
+        assert (scores[0, [30, 40, 70, 71]] == [6, 6, 5, 4]).all() and scores[0].max() == 12 and (scores[0] >= ms).sum() == count
+        assert query["n_cand"].tolist()[:2] == [min(count, 16), 0] and query["flags"].tolist() == [0, 1, 0]
+        assert 0 < query["n_cand"][2] < 15                                 # (the entries of score 12 are too young for the last query)
+        assert query["n_scored"].tolist()[0] == entry_cap and 17 < query["n_scored"][2] < entry_cap
+        by_slot = db.query_rows(lp, qd, qn, qi, rank_key=lambda sc, i_, s_: (-sc, s_))
+        assert by_slot[1].tobytes() != cand.tobytes() and by_slot[0].tobytes() == scores.tobytes()
+        slots = cand["slot"][0, :count].tolist()
+        assert slots.index(40) < slots.index(30)                           # id 800 before id 900
+        for g in kc.RING_GROUPS[entry_cap]:
+            at = [slots.index(s) for s in g]
+            assert at == list(range(at[0], at[0] + len(g)))                # equal (score, id): slot rising, next to each other
+    for ms, count in ((-2 ** 31, 16), (2 ** 31 - 1, 0)):
+        assert db.query_rows(kr.Params(min_gap=0, topk=16, min_score=ms), qd, qn, qi)[2]["n_cand"].tolist() == [count, 0, count]
+
+
+def test_long_adds_in_the_restatement():
+    """one add call that laps a ring of 7 slots thousands of times leaves the last 7 rows, as adding them one call at a time does"""
+    n = 65536 + 7 * 3 + 2
+    kps, desc, nkp, ids = kc.scored_rows(n, 4)
+    one, many = kr.KfDb(7, 8), kr.KfDb(7, 8)
+    one.add_rows(kps, desc, nkp, ids)
+    many.add_rows(kps[:n - 7], desc[:n - 7], nkp[:n - 7], ids[:n - 7])
+    many.add_rows(kps[n - 7:], desc[n - 7:], nkp[n - 7:], ids[n - 7:])
+    assert (one.head, one.total) == (many.head, many.total) == (n % 7, n) and one.id.tolist() == many.id.tolist() and one.cnt.tolist() == many.cnt.tolist()
+    assert sorted(one.id.tolist()) == sorted(ids[n - 7:].tolist()) and (one.cnt > 0).sum() >= 3
+
+
+def test_ratio_ends_give_different_scores():
+    """ratios 1.0, 2.0, +inf, -1.0 and the smallest float32 denormal on a planted couple: the restatement evaluates !(d0 > (double)(float)ratio * d1)
+    as written; at least two of them differ (they all do but 2.0 and +inf)"""
+    E, Q, _ = kc.planted_sets(1234, 300, 257)
+    for mode in (kr.SYM_REFERENCE_EFFECTIVE, kr.SYM_INTENDED):
+        scores = [len(kr.couple_list(E, Q, kr.Params(ratio=r, sym_mode=mode))) for r in kc.RATIO_ENDS]
+        print("ratio ends", kc.RATIO_ENDS, "mode", mode, "scores", scores)
+        assert len(set(scores)) >= 2 and scores[0] > scores[3] and scores[4] >= 1 and scores[2] >= scores[0]
+
+
+def test_rows_without_room_and_calls_without_rows():
+    """row_cap 0 and n 0 in the restatement: empty entries and a moving head; nothing at all"""
+    db = kr.KfDb(4, 32)
+    kps, desc, nkp = kc.table([(5, 1), (3, 2)])
+    db.add_rows(kps, desc, nkp, np.array([0, 1], np.int32))
+    db.add_rows(kps[:0], desc[:0], nkp[:0], np.zeros(0, np.int32))
+    assert (db.head, db.total) == (2, 2)
+    db.add_rows(kps[:, :0], desc[:, :0], nkp, np.array([2, 3], np.int32))
+    assert (db.head, db.total) == (0, 4) and db.cnt.tolist() == [24, 24, 0, 0] and db.id.tolist() == [0, 1, 2, 3]
+    qk, qd, qn = kc.query_base(2)
+    lp = kr.Params(min_gap=0, min_score=0)
+    scores, cand, query = db.query_rows(lp, qd[:, :0], qn, np.array([9, 9], np.int32))
+    assert (scores == -1).all() and query["flags"].tolist() == [1, 1] and query["n_keypoints"].tolist() == [0, 0]
+    scores, cand, query = db.query_rows(lp, qd[:0], qn[:0], np.zeros(0, np.int32))
+    assert scores.shape == (0, 4) and cand.shape == (0, 4) and query.shape == (0,)
