@@ -86,8 +86,15 @@ def gradient(img, x, y, r):
     return (sample(img, x, y, r) + 8192) >> 14
 
 
-def _pass(kp, A, B_gray, start, guess):
-    """one pass over the finite starts `start` (k x 2 float64): template frame A = (gray, gx, gy), target intensities B_gray"""
+SUMS = ("gxx", "gxy", "gyy", "bx", "by")
+
+
+def _pass(kp, A, B_gray, start, guess, wrap=None):
+    """one pass over the finite starts `start` (k x 2 float64): template frame A = (gray, gx, gy), target intensities B_gray.
+    wrap = one of SUMS: that sum is taken modulo 2^32 (what an int accumulator would hold) -- a deliberately wrong variant, for the tests
+    that prove a scene reaches beyond 32 bits (tests/test_klt_limits_ref.py)"""
+    assert wrap is None or wrap in SUMS
+    isum = lambda name, v: (v.astype(np.int32).astype(np.int64) if wrap == name else v).astype(np.float64)
     k = len(start)
     r, first, last = kp.win_radius, kp.first_level, kp.last_level
     n = (2 * r + 1) ** 2
@@ -115,9 +122,9 @@ def _pass(kp, A, B_gray, start, guess):
         T = intensity(A[0][l], p[idx, 0], p[idx, 1], r)
         Dx = gradient(A[1][l], p[idx, 0], p[idx, 1], r)
         Dy = gradient(A[2][l], p[idx, 0], p[idx, 1], r)
-        fxx = (Dx * Dx).sum((1, 2)).astype(np.float64)
-        fxy = (Dx * Dy).sum((1, 2)).astype(np.float64)
-        fyy = (Dy * Dy).sum((1, 2)).astype(np.float64)
+        fxx = isum("gxx", (Dx * Dx).sum((1, 2)))
+        fxy = isum("gxy", (Dx * Dy).sum((1, 2)))
+        fyy = isum("gyy", (Dy * Dy).sum((1, 2)))
         det = fxx * fyy - fxy * fxy
         lam = ((fxx + fyy) - np.sqrt((fxx - fyy) * (fxx - fyy) + 4.0 * (fxy * fxy))) / lam_den
         if at_last:
@@ -140,8 +147,8 @@ def _pass(kp, A, B_gray, start, guess):
             if not len(a):
                 break
             e = intensity(B_gray[l], q[a, 0], q[a, 1], r) - T[a]
-            bx = (Dx[a] * e).sum((1, 2)).astype(np.float64)
-            by = (Dy[a] * e).sum((1, 2)).astype(np.float64)
+            bx = isum("bx", (Dx[a] * e).sum((1, 2)))
+            by = isum("by", (Dy[a] * e).sum((1, 2)))
             ux = -(s * (fyy[a] * bx - fxy[a] * by)) / det[a]
             uy = -(s * (fxx[a] * by - fxy[a] * bx)) / det[a]
             d[idx[a], 0] = d[idx[a], 0] + ux
@@ -161,8 +168,8 @@ def _pass(kp, A, B_gray, start, guess):
     return dict(lost=lost, end=end, sad=sad, lam=lam_last, have_lam=have_lam, iters=iters, levels=levels)
 
 
-def track(kp, f1, f2, pts, guess=None):
-    """records of the points `pts` (m x 2 float32) of frame f1 tracked into frame f2"""
+def track(kp, f1, f2, pts, guess=None, wrap=None):
+    """records of the points `pts` (m x 2 float32) of frame f1 tracked into frame f2 (wrap: see _pass; None is the contract)"""
     pts = np.asarray(pts, np.float32).reshape(-1, 2)
     m = len(pts)
     rec = np.zeros(m, POINT_DTYPE)
@@ -175,7 +182,7 @@ def track(kp, f1, f2, pts, guess=None):
     p0 = p0_all[v]
     g = None if guess is None else np.asarray(guess, np.float32).reshape(m, 2).astype(np.float64)[v]
     n = (2 * kp.win_radius + 1) ** 2
-    fw = _pass(kp, f1, f2[0], p0, g)
+    fw = _pass(kp, f1, f2[0], p0, g, wrap)
     flags = fw["lost"].copy()
     res = np.where((flags == 0)[:, None], fw["end"], p0).astype(np.float32)
     sad = np.where(flags == 0, fw["sad"], 0)
@@ -185,7 +192,7 @@ def track(kp, f1, f2, pts, guess=None):
     if kp.fb_max_px > 0.0:
         b = np.nonzero(flags == 0)[0]
         if len(b):
-            bw = _pass(kp, f2, f1[0], res[b].astype(np.float64), p0[b])
+            bw = _pass(kp, f2, f1[0], res[b].astype(np.float64), p0[b], wrap)
             dd = bw["end"] - p0[b]
             d2 = dd[:, 0] * dd[:, 0] + dd[:, 1] * dd[:, 1]
             lostb = bw["lost"] != 0

@@ -4,103 +4,18 @@ gradients downloaded from the device: point records, pair records and compacted 
 
 Scenes: tests/klt_ref.py blob_frames (analytic, with a textureless box) at 160 x 120 (level 3 is 20 x 15: r = 7 fits nowhere, the level is
 skipped for every point), 150 x 110 (half-to-even level sizes: level 2 is 38 x 28), both also at a padded stride, and 16 x 16 with r = 2."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import homography_ref as hr
 import klt_ref as kr
 import stride_range_cases as src
+from klt_device import FILL, PB, PH, PW, REC, Set as _Set, compare as _compare, dev as _dev, filled as _filled, launch as _launch
+from klt_device import plan_launches as _plan_launches, want as _want
+from klt_limit_cases import BLOB_SHIFT as SHIFT, blob_frames as _frames, blob_points as _points
 
 pytestmark = pytest.mark.gpu
-FILL = 0xEE
-REC = 32
-SHIFT = (3.3, -2.2)
-FLAT_BOX = (96, 20, 136, 60)                                       # x0, y0, x1, y1 at 160 x 120 (scaled with the frame)
-
-
-def _dev(torch, a):
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def _filled(torch, nbytes):
-    t = torch.full((max(nbytes, 16),), FILL, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()                                       # (the fill ran on torch's stream: finished before the library's streams write)
-    return t
-
-
-def _levels(flat, w, h):
-    """one frame of a gradient set -> its five level arrays"""
-    lw, lh = kr.half_dims(w, h)
-    out, off = [], 0
-    for l in range(5):
-        out.append(flat[off:off + lw[l] * lh[l]].reshape(lh[l], lw[l]))
-        off += lw[l] * lh[l]
-    return out
-
-
-class _Set:
-    """n frames on the device at a row stride, their gradient set made by vis_gradient_batch, and the same as host frames for the restatement"""
-    def __init__(self, vislam, torch, c, frames, stride, scale):
-        self.n, self.h, self.w = frames.shape
-        self.stride, self.scale = stride, scale
-        fe = vislam.gradient_frame_elems(self.w, self.h)
-        self.d_frames = _dev(torch, src.padded(frames, stride))
-        self.d_gray = torch.zeros(self.n * fe, dtype=torch.uint8, device="cuda")
-        self.d_gx = torch.zeros(self.n * fe, dtype=torch.int16, device="cuda")
-        self.d_gy = torch.zeros(self.n * fe, dtype=torch.int16, device="cuda")
-        d_g = torch.zeros(self.n * fe, dtype=torch.uint8, device="cuda")
-        torch.cuda.synchronize()
-        c.gradient_batch(self.d_frames.data_ptr(), self.w, self.h, stride, self.n, self.d_gray.data_ptr(), self.d_gx.data_ptr(), self.d_gy.data_ptr(),
-                         d_g.data_ptr(), scale)
-        c.batch_sync()
-        gray, gx, gy = self.d_gray.cpu().numpy(), self.d_gx.cpu().numpy(), self.d_gy.cpu().numpy()
-        self.host = []
-        for i in range(self.n):
-            g = _levels(gray[i * fe:(i + 1) * fe], self.w, self.h)
-            g[0] = frames[i]                                       # level 0 of the intensities is the frame itself
-            self.host.append((g, _levels(gx[i * fe:(i + 1) * fe], self.w, self.h), _levels(gy[i * fe:(i + 1) * fe], self.w, self.h)))
-
-
-_frames_cache, _want_cache = {}, {}
-
-
-def _frames(w, h, n):
-    """A, B, A, B ...: every pair is a shift by SHIFT one way or the other"""
-    if (w, h) not in _frames_cache:
-        sx, sy = w / 160.0, h / 120.0
-        box = None if w < 64 else (FLAT_BOX[0] * sx, FLAT_BOX[1] * sy, FLAT_BOX[2] * sx, FLAT_BOX[3] * sy)
-        s = SHIFT if w >= 64 else (0.6, -0.4)
-        _frames_cache[(w, h)] = kr.blob_frames(w, h, [(0.0, 0.0), s], nblobs=160 if w >= 64 else 2000, flat_box=box)
-    a, b = _frames_cache[(w, h)]
-    return np.stack([a if i % 2 == 0 else b for i in range(n)])
-
-
-def _points(w, h, r, count):
-    """`count` points: a fractional and an integer grid, points whose window leaves each level on each side (and just stays inside), the
-    textureless box, and coordinates that are not finite or absurdly large"""
-    lw, lh = kr.half_dims(w, h)
-    pts = []
-    for l in range(4):
-        back = lambda v: (v + 0.5) * (1 << l) - 0.5                # a level-l position at level 0
-        for xl in (r - 0.5, r + 0.25, lw[l] - r - 2 + 0.5, lw[l] - r - 1 + 0.1):
-            pts.append((back(xl), h * 0.5 + l))
-        for yl in (r - 0.5, r + 0.25, lh[l] - r - 2 + 0.5, lh[l] - r - 1 + 0.1):
-            pts.append((w * 0.45 + l, back(yl)))
-    sx, sy = w / 160.0, h / 120.0
-    pts += [((FLAT_BOX[0] + FLAT_BOX[2]) * 0.5 * sx + i, (FLAT_BOX[1] + FLAT_BOX[3]) * 0.5 * sy - i) for i in range(3)]
-    nan, inf = np.nan, np.inf
-    pts += [(nan, 20.0), (20.0, nan), (inf, 20.0), (20.0, -inf), (1e30, 20.0), (20.0, -1e30), (1e9, 1e9), (-5.0, 20.0), (w + 40.0, h + 40.0)]
-    k = 0
-    while len(pts) < count:                                        # the grid: every third point on whole pixels
-        gx, gy = (k * 37) % 23, (k * 17) % 19
-        x, y = w * (0.12 + 0.76 * gx / 22.0), h * (0.14 + 0.72 * gy / 18.0)
-        pts.append((float(np.floor(x)), float(np.floor(y))) if k % 3 == 0 else (x + 0.31, y + 0.77))
-        k += 1
-    return np.array(pts[:count], np.float32)
+_want_cache = {}
 
 
 def _rows(w, h, r, n, max_pts, npts, seed=0):
@@ -112,62 +27,6 @@ def _rows(w, h, r, n, max_pts, npts, seed=0):
     guess[:, 2::5, 0] = np.nan                                     # a non-finite guess is treated as absent
     guess[:, 3::11] = np.float32(1e30)                             # a finite absurd one is used: the window leaves the level
     return pts, np.asarray(npts, np.int32), guess.astype(np.float32)
-
-
-def _want(S, kp, pts, npts, guess, max_pts):
-    want = []
-    for i in range(1, S.n):
-        m = min(max(int(npts[i]), 0), max_pts)
-        want.append(kr.track(kp, S.host[i - 1], S.host[i], pts[i, :m], None if guess is None else guess[i, :m]))
-    return want
-
-
-def _launch(vislam, torch, c, S, kp, pts, npts, guess, max_pts, compacted=True):
-    """one vis_klt_batch -> (record rows n x max_pts, pair records, p1 rows, p2 rows, ntracked); the guard bytes behind every buffer checked"""
-    n = S.n
-    d_pts, d_npts = _dev(torch, pts), _dev(torch, npts)
-    d_guess = None if guess is None else _dev(torch, guess)
-    out, pair = _filled(torch, (n * max_pts + 2) * REC), _filled(torch, (n + 2) * 32)
-    p1, p2, nt = _filled(torch, n * max_pts * 8 + 64), _filled(torch, n * max_pts * 8 + 64), _filled(torch, n * 4 + 64)
-    vkp = vislam.KltParams(*[getattr(kp, f) for f in kr.P_FIELDS])
-    c.klt_batch(S.d_frames.data_ptr(), S.w, S.h, S.stride, n, S.d_gray.data_ptr(), S.d_gx.data_ptr(), S.d_gy.data_ptr(), d_pts.data_ptr(),
-                d_npts.data_ptr(), max_pts, out.data_ptr(), pair.data_ptr(), 0 if d_guess is None else d_guess.data_ptr(),
-                p1.data_ptr() if compacted else 0, p2.data_ptr() if compacted else 0, nt.data_ptr() if compacted else 0, vkp)
-    c.batch_sync()
-    raw, praw, r1, r2, rn = (t.cpu().numpy() for t in (out, pair, p1, p2, nt))
-    assert (raw[n * max_pts * REC:] == FILL).all() and (praw[n * 32:] == FILL).all()
-    assert (r1[n * max_pts * 8:] == FILL).all() and (r2[n * max_pts * 8:] == FILL).all() and (rn[n * 4:] == FILL).all()
-    if not compacted:
-        assert (r1 == FILL).all() and (r2 == FILL).all() and (rn == FILL).all()
-    return (raw[:n * max_pts * REC].view(vislam.KLT_POINT_DTYPE).reshape(n, max_pts), praw[:n * 32].view(vislam.KLT_PAIR_DTYPE),
-            r1[:n * max_pts * 8].reshape(n, max_pts * 8), r2[:n * max_pts * 8].reshape(n, max_pts * 8), rn[:n * 4].view(np.int32))
-
-
-def _compare(got, want, pts, npts, max_pts, where, compacted=True):
-    recs, pairs, r1, r2, rn = got
-    n = len(recs)
-    assert not recs[0].tobytes().strip(b"\0"), where               # row 0: zeroed records, the pair record of no pair
-    assert pairs[0].tobytes() == kr.pair_record(None, no_pair=True).tobytes(), where
-    flags = 0
-    for i in range(1, n):
-        m = min(max(int(npts[i]), 0), max_pts)
-        w = want[i - 1]
-        assert len(w) == m
-        if recs[i, :m].tobytes() != w.tobytes():
-            bad = [k for k in range(m) if recs[i, k].tobytes() != w[k].tobytes()]
-            raise AssertionError((where, i, bad[:5], [(pts[i, k].tolist(), recs[i, k], w[k]) for k in bad[:3]]))
-        assert (recs[i, m:].view(np.uint8) == FILL).all(), (where, i)     # records behind the pair's points are left alone
-        assert pairs[i].tobytes() == kr.pair_record(w).tobytes(), (where, i, pairs[i])
-        if compacted:
-            a, b = kr.compact(pts[i, :m], w)
-            k = len(a)
-            assert int(rn[i]) == k == int(pairs[i]["n_tracked"]), (where, i)
-            assert r1[i, :k * 8].tobytes() == a.tobytes() and r2[i, :k * 8].tobytes() == b.tobytes(), (where, i)
-            assert (r1[i, k * 8:] == FILL).all() and (r2[i, k * 8:] == FILL).all(), (where, i)
-        flags |= int(np.bitwise_or.reduce(w["flags"])) if m else 0
-    if compacted:
-        assert int(rn[0]) == 0 and (r1[0] == FILL).all() and (r2[0] == FILL).all(), where
-    return flags
 
 
 @pytest.fixture(scope="module")
@@ -280,66 +139,6 @@ def test_single_call_equals_the_batch_row(vislam, c):
 
 
 # ---------------------------------------------------------------------------------------------- the plan's pairs
-PW, PH, PB = 320, 240, 8
-
-
-def _fetch(ptr, nbytes):
-    hip = C.CDLL("libamdhip64.so")
-    host = np.empty(nbytes, np.uint8)
-    assert hip.hipMemcpy(C.c_void_p(host.ctypes.data), C.c_void_p(ptr), C.c_size_t(nbytes), 2) == 0     # device to host
-    return host
-
-
-def _plan_launches(vislam, torch, frames, gate, kp):
-    """two launches of 8 through vis_batch_run(DETECT | GRADIENT) + vis_batch_klt -> per launch what the call wrote, the pairing, the
-    keypoints and the plan's pyramids and gradients as host frames"""
-    p = src.plan_params(vislam, PW, PH, gate)
-    p.nfeatures = 200
-    c = vislam.Context(0, p)
-    c.batch_plan(PW, PH, PW, PB)
-    cap = c.keypoint_capacity(PW, PH)
-    dev = _dev(torch, frames)
-    fe = vislam.gradient_frame_elems(PW, PH)
-    vkp = vislam.KltParams(*[getattr(kp, f) for f in kr.P_FIELDS])
-    out = []
-    for li in range(2):
-        ptr = dev.data_ptr() + li * PB * PW * PH
-        c.batch_run(ptr, PB, vislam.STAGE_DETECT | vislam.STAGE_GRADIENT)
-        recs, pair = _filled(torch, (PB * cap + 1) * REC), _filled(torch, (PB + 1) * 32)
-        p1, p2, nt = _filled(torch, PB * cap * 8 + 16), _filled(torch, PB * cap * 8 + 16), _filled(torch, PB * 4 + 16)
-        if li == 0:
-            bad = vislam.default_klt_params()
-            bad.scharr_scale = 1
-            args = (C.c_void_p(ptr), PB, None, cap, C.c_void_p(recs.data_ptr()), C.c_void_p(pair.data_ptr()), None, None, None)
-            assert vislam.lib.vis_batch_klt(c._h, C.byref(bad), *args) == -1                                   # the plan's gradients have scale 3
-            assert vislam.lib.vis_batch_klt(c._h, C.byref(vkp), C.c_void_p(ptr), PB - 1, *args[2:]) == -5       # VIS_E_STATE: n differs
-            assert vislam.lib.vis_batch_klt(c._h, C.byref(vkp), C.c_void_p(ptr), PB, None, cap - 1, *args[4:]) == -4   # VIS_E_CAPACITY
-        c.batch_klt(ptr, PB, cap, recs.data_ptr(), pair.data_ptr(), 0, p1.data_ptr(), p2.data_ptr(), nt.data_ptr(), vkp)
-        c.batch_sync()
-        assert c.batch_status() == 0
-        pg, px, py, _, pfe = c.batch_gradients()
-        assert pfe == fe
-        gray, gx, gy = _fetch(pg, PB * fe), _fetch(px, 2 * PB * fe).view(np.int16), _fetch(py, 2 * PB * fe).view(np.int16)
-        host = []
-        for i in range(PB):
-            g = _levels(gray[i * fe:(i + 1) * fe], PW, PH)
-            g[0] = frames[li * PB + i]
-            host.append((g, _levels(gx[i * fe:(i + 1) * fe], PW, PH), _levels(gy[i * fe:(i + 1) * fe], PW, PH)))
-        raw, praw, r1, r2, rn = (t.cpu().numpy() for t in (recs, pair, p1, p2, nt))
-        assert (raw[PB * cap * REC:] == FILL).all() and (praw[PB * 32:] == FILL).all() and (rn[PB * 4:] == FILL).all()
-        assert (r1[PB * cap * 8:] == FILL).all() and (r2[PB * cap * 8:] == FILL).all()
-        out.append(dict(recs=raw[:PB * cap * REC].view(vislam.KLT_POINT_DTYPE).reshape(PB, cap), pairs=praw[:PB * 32].view(vislam.KLT_PAIR_DTYPE),
-                        p1=r1[:PB * cap * 8].reshape(PB, cap * 8), p2=r2[:PB * cap * 8].reshape(PB, cap * 8), nt=rn[:PB * 4].view(np.int32),
-                        links=c.batch_get_keyframes(), kps=[c.batch_keypoints(i)[0] for i in range(PB)], host=host, cap=cap))
-    # a run without the gradient stage, or without detection, leaves nothing to track on
-    c.batch_run(dev.data_ptr(), PB, vislam.STAGE_DETECT | vislam.STAGE_MATCH)
-    args = (C.byref(vkp), C.c_void_p(dev.data_ptr()), PB, None, cap, C.c_void_p(recs.data_ptr()), C.c_void_p(pair.data_ptr()), None, None, None)
-    assert vislam.lib.vis_batch_klt(c._h, *args) == -5
-    c.batch_sync()
-    c.close()
-    return out
-
-
 @pytest.mark.parametrize("gate", [False, True], ids=["gate_off", "gate_on"])
 def test_plan_pairs_equal_the_restatement(vislam, canvas, gate):
     """every keypoint of frame prev[i] tracked into frame i; the pair to the carried frame and the frames without a pair are zeroed rows
